@@ -19,7 +19,11 @@ per GPU); the only data-path collective is the RCCL all-gather of encoder output
 as that range's last kernel is enqueued (efficientconformer_amd/dist.py), so range 0 is on the wire during range 1's last stage
 and range 1's collective overlaps the head of range 0 and the next step's encoder.  The CTC head consumes the gathered chunks
 (every rank ends up with the labels of the GLOBAL batch) on a head stream; `--gather labels` gathers label ids instead.
-Rank 0 prints ONE JSON line.  `value` counts VALID (un-padded) mel frames of all ranks per second.
+Rank 0 prints ONE JSON line.  `value` counts VALID (un-padded) mel frames of all ranks per second; `ms_per_step` is the wall clock of one
+timed step.  A plain run only sets up, warms up, times the K steps and prints that line.  `--full` adds the un-timed legs after the timed
+region: `check` (the last step against each row range / utterance run alone and against the oracle), `roofline` + `kernel_classes`,
+`reference_batch_semantics` and `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step returned (encoder outputs, lengths,
+labels) as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -132,7 +136,17 @@ def parse():
                          "split: the label-exact mode on the fp16 matrix pipe (operands split into two fp16 numbers, three MFMAs per product)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU work: build the batch plan, join the process group (gloo) and print the JSON skeleton (CPU tests)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the un-timed legs: the self-check (`check`), the roofline leg (`roofline`, `kernel_classes`), "
+                         "the reference's collated-batch semantics and the CPU baseline (`cpu_baseline`); --no-check / --no-roofline / "
+                         "--no-cpu-baseline drop single legs.  Without --full a run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32; integer arrays as float64), "
+                         "at most 64 MB in all: larger outputs are cut to a fixed, seeded sample of rows (DIR/<name>_rows.npy lists them)")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_check = args.no_roofline = args.no_cpu_baseline = True
+    return args
 
 
 def launch_ranks(args):
@@ -217,6 +231,44 @@ def step(model, audio, lens, range_pad=None, **kw):
     enc, enc_len, _ = model.encoder(audio, lens, range_pad=range_pad, **kw)
     labels, label_len = head(model, enc, enc_len)
     return enc, enc_len, labels, label_len
+
+
+DUMP_BUDGET = 63_000_000     # bytes of the .npy payloads of --dump-outputs (64 MB in all with the headers)
+
+
+def step_outputs(model, last, multi, args):
+    """name -> tensor: what the timed path handed its caller in the last timed step (rank 0's view on the multi-rank path)."""
+    lab = ("tokens", "token_len") if isinstance(model, Transducer) else ("labels", "label_len")
+    if multi and args.gather == "outputs":
+        out = {}
+        for i, ch in enumerate(last["chunks"]):
+            out.update({"range%d_encoder_out" % i: ch.out, "range%d_encoder_out_len" % i: ch.out_len,
+                        "range%d_%s" % (i, lab[0]): ch.labels[0], "range%d_%s" % (i, lab[1]): ch.labels[1]})
+        return out
+    out = {"encoder_out": last["enc"][0], "encoder_out_len": last["enc"][1], lab[0]: last["labels"][0], lab[1]: last["labels"][1]}
+    if "gathered_labels" in last:
+        out.update({"gathered_" + lab[0]: last["gathered_labels"][0], "gathered_" + lab[1]: last["gathered_labels"][1]})
+    return out
+
+
+def dump_outputs(path, tensors, budget=DUMP_BUDGET, seed=0):
+    """Write every tensor as <path>/<name>.npy: floating tensors as float32, integer ones as float64 (exact).  If the whole exceeds `budget`
+    bytes, every array of two or more dimensions keeps the same fraction of its rows, chosen by a generator seeded with `seed` (arrays with
+    the same number of rows keep the same rows), and <name>_rows.npy lists them: the same arguments write the same files."""
+    os.makedirs(path, exist_ok=True)
+    size = lambda t: t.numel() * (4 if t.is_floating_point() else 8)
+    small = sum(size(t) for t in tensors.values() if t.dim() < 2)
+    big = sum(size(t) for t in tensors.values() if t.dim() >= 2)
+    frac = 1.0 if small + big <= budget else max(0.0, budget - small - 8 * sum(t.shape[0] for t in tensors.values() if t.dim() >= 2)) / big
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.dim() >= 2 and frac < 1.0:
+            k = max(1, int(t.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(seed).choice(t.shape[0], k, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.float().cpu().numpy() if t.is_floating_point() else t.cpu().numpy().astype(np.float64)
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def self_check_transducer(model, sd, plan, audio, lens, lens_np, last):
@@ -784,6 +836,8 @@ def main():
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         elapsed = float(mx[0])
     all_valid, all_padded = float(tot[1]), float(tot[2])
+    if rank == 0 and args.dump_outputs:            # un-timed, before any other leg runs a forward
+        dump_outputs(args.dump_outputs, step_outputs(model, last, multi, args))
 
     # what every rank's transport looked like (the driver's SCALE record should show that RCCL saw N ranks): backend and
     # communicator size as torch.distributed reports them, GPU_MAX_HW_QUEUES as this process exported it before the HIP runtime started, the device,

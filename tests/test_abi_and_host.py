@@ -313,6 +313,35 @@ def test_bench_rejects_a_world_size_that_contradicts_gpus():
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
 
 
+def test_bench_full_gates_the_untimed_legs_and_dump_outputs_is_seeded_and_bounded(tmp_path, monkeypatch):
+    """A plain bench run skips check / roofline / cpu_baseline unless --full is given; --dump-outputs writes float32 / float64 .npy files,
+    the same ones for the same outputs, within 64 MB (a seeded row sample of what is larger, the same rows for arrays of equal length)."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3"])
+    a = bench.parse()
+    assert a.steps == 3 and not a.full and a.no_check and a.no_roofline and a.no_cpu_baseline and a.dump_outputs == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full and not a.no_check and not a.no_roofline and a.no_cpu_baseline and a.dump_outputs == str(tmp_path)
+    g = torch.Generator().manual_seed(0)
+    outs = {"encoder_out": torch.randn(96, 200, 900, generator=g), "encoder_out_len": torch.arange(96),
+            "labels": torch.randint(0, 256, (96, 200), dtype=torch.int32, generator=g), "label_len": torch.arange(96, dtype=torch.int32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "encoder_out_rows.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    for f in files:
+        x = np.load(tmp_path / "a" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, np.load(tmp_path / "b" / f)), f
+    rows = np.load(tmp_path / "a" / "encoder_out_rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "a" / "labels_rows.npy").astype(np.int64))
+    assert np.array_equal(np.load(tmp_path / "a" / "encoder_out.npy"), outs["encoder_out"][rows].numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "labels.npy"), outs["labels"][rows].double().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "label_len.npy"), np.arange(96, dtype=np.float64))
+
+
 def test_raw_ddp_state_dict_with_frontend_buffers_loads():
     """A raw DDP state dict carries `encoder.module.preprocessing.*` torchaudio buffers (model.py:367-370 strips `.module.`):
     the infix is stripped first, then the frontend buffers are dropped."""
@@ -361,17 +390,16 @@ SHIPPED = ["ConformerCTCSmall", "ConformerCTCMedium", "ConformerCTCLarge", "Conf
 
 
 @pytest.mark.parametrize("name", SHIPPED)
-def test_every_shipped_config_has_a_name_and_a_plan(name):
-    """All 12 model configs the reference ships (configs/*.json) resolve by name; where the reference tree is present (build
-    container) the named config must equal the JSON file key for key on everything the hot path reads."""
+def test_every_shipped_config_has_a_name_and_a_plan(name, golden_dir):
+    """All 12 model configs the reference ships (configs/*.json) resolve by name, and the named config equals the JSON file key for key
+    on everything the hot path reads (tests/golden/reference_configs.json: encoder_params, vocab_size, decoder_params and joint_params
+    of each file)."""
     import json
     cfg = named_config(name)
     plan = build_plan(cfg["encoder_params"])
     assert len(plan.blocks) == cfg["encoder_params"]["num_blocks"]
-    path = os.path.join("/root/reference/configs", name + ".json")
-    if not os.path.exists(path):
-        return
-    ref = json.load(open(path))
+    with open(os.path.join(golden_dir, "reference_configs.json")) as f:
+        ref = json.load(f)[name]
     ours, theirs = cfg["encoder_params"], ref["encoder_params"]
     for k in ("arch", "num_blocks", "dim_model", "ff_ratio", "num_heads", "kernel_size", "conv_stride", "att_stride", "strided_blocks", "expand_blocks",
               "att_group_size", "relative_pos_enc", "max_pos_encoding", "subsampling_module", "subsampling_layers", "subsampling_filters",

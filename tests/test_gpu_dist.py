@@ -50,7 +50,7 @@ def test_bench_two_ranks_on_one_gpu(gather):
     """`python bench.py --gpus 2` end to end (launcher, per-range all-gather on the comm stream, head on the gathered chunks on the head
     stream, max-over-ranks timing), both ranks on cuda:0 over gloo."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--one-device", "--batch", "16",
-                        "--steps", "3", "--warmup", "1", "--no-roofline", "--no-cpu-baseline", "--gather", gather],
+                        "--steps", "3", "--warmup", "1", "--full", "--no-roofline", "--no-cpu-baseline", "--gather", gather],
                        capture_output=True, text=True, timeout=600, env=_env())
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout[-2000:], r.stderr[-3000:])
