@@ -285,6 +285,11 @@ bool get_ln(EcEncoder* e, const std::string& prefix, int D, LNp* out, std::strin
     return out->g && out->b;
 }
 
+// Largest |value x 2^10| the fused split images (sxf_sub / sxf_ffn / sxf_chain) hold as two fp16 halves (fp16 max 65504): |w| < 63.48 after
+// folding.  An image with a value beyond it is not built - that block / the front end runs the per-module split kernels - and the per-module
+// images (h = fp16(w)) refuse |w| >= kSplitImgMax itself (split-mode operand envelopes).  Nothing is clamped.
+constexpr float kSplitImgMax = 65000.f;
+
 // BatchNorm(eval) fold: y = (x - mean) / sqrt(var + 1e-5) * gamma + beta  -> per-channel scale / shift
 bool bn_fold(EcEncoder* e, const std::string& prefix, int C, std::vector<float>* scale, std::vector<float>* shift, std::string* err) {
     const HostTensor *g = find(e, prefix + ".weight"), *b = find(e, prefix + ".bias");
@@ -1816,9 +1821,10 @@ int effconf_encoder_finalize(EcEncoder* e) {
             const HostTensor *cw = find(e, "subsampling_module.layers.0.0.weight"), *lw = find(e, "linear.weight"), *lb = find(e, "linear.bias");
             if (nt && cw && lw && lb && (int64_t)cw->data.size() == (int64_t)Co * 9 && (int64_t)lw->data.size() == (int64_t)N * Co * Fo && (int)lb->data.size() == N) {
                 auto half_bits = [](float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; };
+                bool over = false;                     // a folded value the image cannot hold: no fused front end (per-module kernels)
                 auto put = [&](std::vector<uint16_t>& img, size_t hi_at, size_t lo_at, double wv) {
-                    float ws = (float)(wv * 1024.0);
-                    ws = ws > 65000.f ? 65000.f : (ws < -65000.f ? -65000.f : ws);
+                    const float ws = (float)(wv * 1024.0);
+                    if (!(std::fabs(ws) < kSplitImgMax)) { over = true; return; }
                     const _Float16 hh = (_Float16)ws;
                     img[hi_at] = half_bits((float)hh);
                     img[lo_at] = half_bits(ws - (float)hh);
@@ -1843,24 +1849,30 @@ int effconf_encoder_finalize(EcEncoder* e) {
                     }
                 std::vector<float> bp(DP2, 0.f);
                 for (int n = 0; n < N; ++n) bp[n] = lb->data[n];
-                e->xsub_cimg = upload(e, cimg); e->xsub_wimg = upload(e, wimg); e->xsub_bias = upload(e, bp); e->xsub_ncb = ncb; e->xsub_fo = Fo;
+                if (!over) { e->xsub_cimg = upload(e, cimg); e->xsub_wimg = upload(e, wimg); e->xsub_bias = upload(e, bp); e->xsub_ncb = ncb; e->xsub_fo = Fo; }
             }
         }
         if (e->exact_split) {
             // every 2-D weight (nn.Linear [N][K], 1x1 Conv1d [N][K][1]) as two fp16 images h = fp16(w), l = fp16((w - h) * 2048), K padded
             // with zeros to whole 32-wide k-tiles and stored k-tile major; the three attention projections of a block additionally stacked (q | k | v)
             auto half_bits = [](float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; };
-            auto clampf = [](float f) { return f > 65000.f ? 65000.f : (f < -65000.f ? -65000.f : f); };
+            std::string range_err;                 // the first tensor with an element the per-module images cannot hold: finalize fails
             auto add_split = [&](const std::string& prefix, const std::vector<const float*>& rows, int K) {
                 const int N = (int)rows.size(), ldh = ec_round_up(K, 32);
                 std::vector<uint16_t> hi((size_t)N * ldh, 0), lo(hi.size(), 0);
                 for (int n = 0; n < N; ++n)
                     for (int k = 0; k < K; ++k) {
                         const float wv = rows[n][k];
-                        const _Float16 h = (_Float16)clampf(wv);
+                        if (!(std::fabs(wv) < kSplitImgMax)) {
+                            if (range_err.empty())
+                                range_err = "split mode: " + prefix + ".weight[" + std::to_string(n) + "][" + std::to_string(k) + "] = " + std::to_string(wv) +
+                                            " is outside the split images' range |w| < 65000";
+                            return;
+                        }
+                        const _Float16 h = (_Float16)wv;
                         const size_t at = ((size_t)(k / 32) * N + n) * 32 + k % 32;       // k-tile major (kernels.h: SxGemmParams)
                         hi[at] = half_bits((float)h);
-                        lo[at] = half_bits(clampf((wv - (float)h) * 2048.0f));
+                        lo[at] = half_bits((wv - (float)h) * 2048.0f);                      // |w - h| <= 2^-11 |w|: |l| < 2^15
                     }
                 e->xsplit[prefix] = EcEncoder::SplitW{upload(e, hi), upload(e, lo), ldh};
             };
@@ -1892,6 +1904,7 @@ int effconf_encoder_finalize(EcEncoder* e) {
                 add_split(m + "qkv_layer", rows, D);
                 e->xw[m + "qkv_layer.bias"] = upload(e, bias);
             }
+            if (!range_err.empty()) return fail(range_err);
             // weight images of the fused FFN kernel (sxf_ffn.hip; kernels.h: SxfFfnParams)
             for (size_t k = 0; k < e->blocks.size(); ++k)
                 for (int which = 0; which < 2; ++which) {
@@ -1906,8 +1919,10 @@ int effconf_encoder_finalize(EcEncoder* e) {
                     const int DP1 = 16 * ks1, DP2 = 32 * nt2, nch = (F + 31) / 32;
                     const size_t per = (size_t)64 * (DP1 + DP2);
                     std::vector<uint16_t> img((size_t)nch * per, 0);
+                    bool over = false;                 // a folded value the image cannot hold: this FFN (and the chains using it) runs per-module
                     auto put = [&](size_t hi_at, size_t lo_at, float wv) {      // same-scale halves at the weight scale 2^10 (sx_common.h split2s; sxf_ffn.hip SW)
-                        const float ws = clampf(wv * 1024.0f);
+                        const float ws = wv * 1024.0f;
+                        if (!(std::fabs(ws) < kSplitImgMax)) { over = true; return; }
                         const _Float16 hh = (_Float16)ws;
                         img[hi_at] = half_bits((float)hh);
                         img[lo_at] = half_bits(ws - (float)hh);
@@ -1934,6 +1949,7 @@ int effconf_encoder_finalize(EcEncoder* e) {
                                     0.5f * w2->data[(size_t)n * F + hid]);
                             }
                     }
+                    if (over) continue;
                     std::vector<float> b2h(DP2, 0.f);
                     for (int n = 0; n < D; ++n) b2h[n] = 0.5f * b2->data[n];
                     e->bw[k].xf_img[which] = upload(e, img); e->bw[k].xf_b2[which] = upload(e, b2h); e->bw[k].xf_nch[which] = nch;
@@ -1942,8 +1958,10 @@ int effconf_encoder_finalize(EcEncoder* e) {
             // 16-block, position 8 kh + e holds feature 8 (e >> 2) + 4 kh + (e & 3) - because every operand of a product is a converted accumulator tile.
             {
                 auto perm16 = [](int pos) { const int khh = pos >> 3, ee = pos & 7; return 8 * (ee >> 2) + 4 * khh + (ee & 3); };
+                bool over = false;                     // set by put: a folded value the image being built cannot hold (that chain is not built)
                 auto put = [&](std::vector<uint16_t>& img, size_t hi_at, size_t lo_at, double wv) {
-                    const float ws = clampf((float)(wv * 1024.0));
+                    const float ws = (float)(wv * 1024.0);
+                    if (!(std::fabs(ws) < kSplitImgMax)) { over = true; return; }
                     const _Float16 hh = (_Float16)ws;
                     img[hi_at] = half_bits((float)hh);
                     img[lo_at] = half_bits(ws - (float)hh);
@@ -1997,7 +2015,7 @@ int effconf_encoder_finalize(EcEncoder* e) {
                             f1_chunk(img, (size_t)c * per, DP1, Dw, rows, bias, g->data.data(), bt->data.data());
                             f2_chunk(img, (size_t)c * per + (size_t)64 * DP1, DP2, c, w2->data.data(), Dw, F, F, 0.5);
                         }
-                        return upload(e, img);
+                        return over ? nullptr : upload(e, img);
                     };
                     if (sxc_supported(D) && sxf_ffn_supported(D)) {
                         int ks, nt; sxf_ffn_shape(D, &ks, &nt);
@@ -2010,6 +2028,7 @@ int effconf_encoder_finalize(EcEncoder* e) {
                                   (int64_t)w1->data.size() == (int64_t)2 * De * D && (int)b1->data.size() == 2 * De && (int)ag->data.size() == D && (int)ab->data.size() == D;
                         for (int i = 0; i < 3; ++i) ok = ok && wq[i] && bq[i] && (int)wq[i]->data.size() == D * D && (int)bq[i]->data.size() == D;
                         if (ok) {
+                            over = false;
                             std::vector<uint16_t> io((size_t)nt * 64 * DP2, 0);
                             for (int c = 0; c < nt; ++c) f2_chunk(io, (size_t)c * 64 * DP2, DP2, c, wo->data.data(), D, D, D, 1.0);
                             std::vector<uint16_t> ip((size_t)2 * nte * 64 * DP1, 0);
@@ -2025,9 +2044,11 @@ int effconf_encoder_finalize(EcEncoder* e) {
                                 for (int r = 0; r < 32; ++r) { const int n = 32 * cc + r; rows[r] = n < D ? wq[which]->data.data() + (size_t)n * D : nullptr; bias[r] = n < D ? bq[which]->data[n] : 0.f; }
                                 f1_chunk(iq, (size_t)c * 64 * DP1, DP1, D, rows, bias, ag->data.data(), ab->data.data());
                             }
+                            if (!over) {
                             W.xc_wo = upload(e, io); W.xc_bo = upload(e, padded(bo->data, DP2, 1.f)); W.xc_p1 = upload(e, ip); W.xc_nch_p1 = 2 * nte; W.xc_qkv = upload(e, iq);
                             W.xc_f[0] = ffn_image(0, D);
                             W.xc_in = W.xc_f[0] != nullptr;
+                            }
                         }
                     }
                     if (sxc_supported(De) && sxf_ffn_supported(De)) {
@@ -2035,11 +2056,14 @@ int effconf_encoder_finalize(EcEncoder* e) {
                         const int DP2 = 32 * nt;
                         const HostTensor *w2 = find(e, cm + "7.weight"), *b2 = find(e, cm + "7.bias");
                         if (w2 && b2 && (int64_t)w2->data.size() == (int64_t)De * De && (int)b2->data.size() == De) {
+                            over = false;
                             std::vector<uint16_t> i2((size_t)nt * 64 * DP2, 0);
                             for (int c = 0; c < nt; ++c) f2_chunk(i2, (size_t)c * 64 * DP2, DP2, c, w2->data.data(), De, De, De, 1.0);
-                            W.xc_p2 = upload(e, i2); W.xc_bp2 = upload(e, padded(b2->data, DP2, 1.f));
-                            W.xc_f[1] = ffn_image(1, De);
-                            W.xc_out = W.xc_f[1] != nullptr;
+                            if (!over) {
+                                W.xc_p2 = upload(e, i2); W.xc_bp2 = upload(e, padded(b2->data, DP2, 1.f));
+                                W.xc_f[1] = ffn_image(1, De);
+                                W.xc_out = W.xc_f[1] != nullptr;
+                            }
                         }
                     }
                 }
@@ -2389,7 +2413,7 @@ int effconf_debug_dwconv(const uint16_t* g, int32_t batch, int32_t frames, int32
 int effconf_debug_sxf_ffn(EcEncoder* e, int32_t block, int32_t which, const float* x, int32_t rows, float* y, int32_t with_norm, int32_t ablate, void* stream) {
     if (!e || !e->finalized || block < 0 || block >= (int)e->blocks.size() || which < 1 || which > 2 || !x || !y || rows <= 0) return fail("bad argument");
     const BlockW& W = e->bw[block];
-    if (!W.xf_img[which - 1]) return fail("no fused split FFN image for this block (finalize with exact_fp32 = 2; width not built)");
+    if (!W.xf_img[which - 1]) return fail("no fused split FFN image for this block (finalize with exact_fp32 = 2; width not built, or a folded weight beyond the image's range)");
     SxfFfnParams fp{};
     const int D = which == 2 ? e->blocks[block].dim_expand : e->blocks[block].dim_model;
     fp.X = x; fp.ldx = D; fp.Y = y; fp.ldy = D; fp.wimg = W.xf_img[which - 1]; fp.b2 = W.xf_b2[which - 1]; fp.M = rows; fp.D = D; fp.nchunk = W.xf_nch[which - 1];

@@ -16,7 +16,8 @@ __device__ __forceinline__ uint32_t pack_h2(_Float16 a, _Float16 b) {
 
 // two fp32 values -> their (h, l) fp16 pairs.  h by v_cvt_pkrtz_f16_f32 (one instruction for the pair; truncation is as good as rounding
 // here - any h within 2^-10 of x leaves a remainder the second half represents - and it saturates instead of overflowing), l rounded to
-// nearest.  Values beyond the fp16 range saturate (operands of this path are LayerNorm-ed / gated activations and weights, far inside it).
+// nearest.  Values beyond the fp16 range saturate.  The per-module images refuse |w| >= 65000 at finalize (encoder.hip kSplitImgMax); the activation
+// operands are NOT range-checked: their envelopes are stated in DESIGN.md section 4b (split-mode operand envelopes), not guaranteed by this helper.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_t& lo) {

@@ -16,8 +16,12 @@ this image; reference call sites models/modules.py:81-82, 90, 93).  It restates
 torchaudio's published ``Spectrogram(power=2)`` + ``MelScale(htk, norm=None)``
 algorithm and is cross-checked only against an independent numpy DFT.
 
-All tensors are torch CPU float32; ``sd`` is a state dict with the reference's
+All tensors are torch CPU float32 by default; ``sd`` is a state dict with the reference's
 key names without the ``encoder.`` prefix (efficientconformer_amd/params.py).
+``encoder_from_mel(..., dtype=torch.float64)`` runs the same arithmetic in float64
+(weights, positional tables and masks included): the basis the stressed-weight
+tests compare against, where a float32 oracle's own error approaches the
+label-exact modes' bound.  The float32 default is unchanged bit for bit.
 """
 from __future__ import annotations
 
@@ -110,23 +114,23 @@ def ffn(x: torch.Tensor, sd, prefix: str) -> torch.Tensor:
 #     key-padding mask attentions.py:1326-1340, 1377-1403; wrapper modules.py:472-488
 # --------------------------------------------------------------------------
 
-def rel_sinusoid_rows(tp: int, dim: int, group: int) -> torch.Tensor:
+def rel_sinusoid_rows(tp: int, dim: int, group: int, dtype=torch.float) -> torch.Tensor:
     """R[m] = sinusoid(p = Tp-1-floor(G/2)-m), m in [0, 2Tp-G)  (the slice the reference takes of its
     precomputed table, attentions.py:1251 / 1309; same fp32 operation order as the table build 1219-1226)."""
     hi = tp - 1 - group // 2
-    pos = torch.arange(hi, -hi - 1, -1, dtype=torch.float).unsqueeze(1)
-    angles = pos / 10000 ** (2 * torch.arange(0, dim // 2, dtype=torch.float).unsqueeze(0) / dim)
-    r = torch.zeros(pos.shape[0], dim)
+    pos = torch.arange(hi, -hi - 1, -1, dtype=dtype).unsqueeze(1)
+    angles = pos / 10000 ** (2 * torch.arange(0, dim // 2, dtype=dtype).unsqueeze(0) / dim)
+    r = torch.zeros(pos.shape[0], dim, dtype=dtype)
     r[:, 0::2] = angles.sin()
     r[:, 1::2] = angles.cos()
     return r
 
 
-def rel_sinusoid_rows_causal(tp: int, dim: int) -> torch.Tensor:
+def rel_sinusoid_rows_causal(tp: int, dim: int, dtype=torch.float) -> torch.Tensor:
     """causal tables: R[m] = sinusoid(p = Tp-1-m), m in [0, Tp)  (attentions.py:1243-1247 / 1296-1300: the slice [max_len - T, max_len))"""
-    pos = torch.arange(tp - 1, -1, -1, dtype=torch.float).unsqueeze(1)
-    angles = pos / 10000 ** (2 * torch.arange(0, dim // 2, dtype=torch.float).unsqueeze(0) / dim)
-    r = torch.zeros(pos.shape[0], dim)
+    pos = torch.arange(tp - 1, -1, -1, dtype=dtype).unsqueeze(1)
+    angles = pos / 10000 ** (2 * torch.arange(0, dim // 2, dtype=dtype).unsqueeze(0) / dim)
+    r = torch.zeros(pos.shape[0], dim, dtype=dtype)
     r[:, 0::2] = angles.sin()
     r[:, 1::2] = angles.cos()
     return r
@@ -154,7 +158,8 @@ def relpos_attention(x: torch.Tensor, lens: Optional[torch.Tensor], sd, prefix: 
     qv = q + _t(sd, m + "v")
     tg = tp // group
     d = group * dim // heads                               # attentions.py:643
-    rows = rel_sinusoid_rows_causal(tp, dim) if causal else rel_sinusoid_rows(tp, dim, group)
+    ft = x.dtype                                           # float32 unless the whole forward runs in float64
+    rows = rel_sinusoid_rows_causal(tp, dim, ft) if causal else rel_sinusoid_rows(tp, dim, group, ft)
     e = F.linear(rows, _t(sd, m + "pos_layer.weight"), _t(sd, m + "pos_layer.bias"))
 
     def split(z, rows):                                    # (B, rows*G, D) -> (B, H, rows, d): a pure view + transpose
@@ -175,22 +180,22 @@ def relpos_attention(x: torch.Tensor, lens: Optional[torch.Tensor], sd, prefix: 
     if left is not None or right is not None:                  # streaming mask, on the positions the slicing keeps
         pos = torch.arange(tg) * (mask_stride * group)
         delta = pos.unsqueeze(0) - pos.unsqueeze(1)            # [i][j] = pos_j - pos_i
-        band = torch.zeros(tg, tg)
+        band = torch.zeros(tg, tg, dtype=ft)
         if right is not None:
-            band = torch.maximum(band, (delta > right).float())
+            band = torch.maximum(band, (delta > right).to(ft))
         if left is not None:
-            band = torch.maximum(band, (delta < -left).float())
+            band = torch.maximum(band, (delta < -left).to(ft))
     else:
         band = None
     if lens is not None:
         # key group j masked iff its first frame G*j >= lens[b] (mask[:, :, ::G, ::G], attentions.py:698;
         # chunk padding is masked too, attentions.py:128-131); additive -1e9 as in the reference (:701)
-        masked = (torch.arange(tg).unsqueeze(0) * group >= lens.unsqueeze(1)).float()[:, None, None, :]
+        masked = (torch.arange(tg).unsqueeze(0) * group >= lens.unsqueeze(1)).to(ft)[:, None, None, :]
         if band is not None:
             masked = torch.maximum(masked, band[None, None])   # streaming_mask.maximum(padding_mask), attentions.py:1399
         s = s + masked * -1e9
     elif pad or band is not None:
-        masked = (torch.arange(tg) * group >= t).float()[None, None, None, :]
+        masked = (torch.arange(tg) * group >= t).to(ft)[None, None, None, :]
         if band is not None:
             masked = torch.maximum(masked, band[None, None])
         s = s + masked * -1e9
@@ -210,7 +215,8 @@ def mhsa_module(x, lens, sd, prefix, heads, group, return_probs: bool = False, *
 # a7  convolution module  (modules.py:511-525; layers.py:122-136; activations.py:28-29, 37-39)
 # --------------------------------------------------------------------------
 
-def conv_module(x: torch.Tensor, sd, prefix: str, kernel: int, stride: int, causal: bool = False) -> torch.Tensor:
+def conv_module_pre_bn(x: torch.Tensor, sd, prefix: str, kernel: int, stride: int, causal: bool = False) -> torch.Tensor:
+    """The convolution module up to the depthwise convolution's output (B, De, To): what its BatchNorm sees."""
     d = x.shape[-1]
     p = prefix + ".layers"
     h = F.layer_norm(x, (d,), _t(sd, p + ".0.weight"), _t(sd, p + ".0.bias"), LN_EPS)
@@ -219,7 +225,12 @@ def conv_module(x: torch.Tensor, sd, prefix: str, kernel: int, stride: int, caus
     h = (a * torch.sigmoid(g)).transpose(1, 2)                                        # (B, De, T)
     half = (kernel - 1) // 2
     h = F.pad(h, (kernel - 1, 0) if causal else (half, half))                         # "causal" / "same" pre-padding, layers.py:97-101
-    h = F.conv1d(h, _t(sd, p + ".4.weight"), _t(sd, p + ".4.bias"), stride=stride, groups=h.shape[1])
+    return F.conv1d(h, _t(sd, p + ".4.weight"), _t(sd, p + ".4.bias"), stride=stride, groups=h.shape[1])
+
+
+def conv_module(x: torch.Tensor, sd, prefix: str, kernel: int, stride: int, causal: bool = False) -> torch.Tensor:
+    p = prefix + ".layers"
+    h = conv_module_pre_bn(x, sd, prefix, kernel, stride, causal)
     h = F.batch_norm(h, _t(sd, p + ".5.running_mean"), _t(sd, p + ".5.running_var"),
                      _t(sd, p + ".5.weight"), _t(sd, p + ".5.bias"), False, 0.0, BN_EPS)
     h = (h * torch.sigmoid(h)).transpose(1, 2)                                        # (B, To, De)
@@ -266,8 +277,23 @@ def conformer_block(x, lens, sd, bp, trace: Optional[dict] = None, plan=None):
 # a3/a4/a9  encoder shell  (encoders.py:97-142)
 # --------------------------------------------------------------------------
 
-def encoder_from_mel(mel: torch.Tensor, mel_len: Optional[torch.Tensor], sd, plan, trace: Optional[dict] = None):
-    """mel (B, n_mels, Tm), lengths in mel frames -> (x (B, T_out, D_last), out_len)."""
+def cast_state_dict(sd, dtype=torch.float64) -> Dict[str, torch.Tensor]:
+    """The floating-point tensors of ``sd`` as torch tensors of ``dtype`` (integer ones unchanged)."""
+    out = {}
+    for k in sd:
+        v = _t(sd, k)
+        out[k] = v.to(dtype) if v.is_floating_point() else v
+    return out
+
+
+def encoder_from_mel(mel: torch.Tensor, mel_len: Optional[torch.Tensor], sd, plan, trace: Optional[dict] = None,
+                     dtype: torch.dtype = torch.float32):
+    """mel (B, n_mels, Tm), lengths in mel frames -> (x (B, T_out, D_last), out_len).
+    ``dtype``: float32 (the default, the reference's own precision) or float64: weights, input, positional tables and masks
+    in that type throughout."""
+    if dtype != torch.float32:
+        sd = cast_state_dict(sd, dtype)
+        mel = mel.to(dtype)
     x, lens = subsample(mel, mel_len, sd, plan.sub_layers)
     if trace is not None:
         trace["subsample"] = x
