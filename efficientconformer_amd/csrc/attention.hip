@@ -437,6 +437,7 @@ __global__ __launch_bounds__(NWV * 64, (NWV == 4 && DP <= 96) ? 2 : 1) void relp
 #undef AT_TICK
 }
 
+#ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py) only
 unsigned long long* g_attn_prof = nullptr;
 void attn_prof_dump() {
     unsigned long long all[4 * 16];
@@ -452,6 +453,7 @@ void attn_prof_dump() {
         for (int i = 0; i < 11; ++i) fprintf(stderr, "[attn phases]   %-20s %10.0f cyc/wave  %5.1f%%\n", names[i], (double)h[i] / h[15], 100.0 * h[i] / tot);
     }
 }
+#endif
 
 __global__ void attn_pad_rows_kernel(GemmParams p, int B) {
     // rows t in [T, Tp): Q = 0 -> Qu = u (and Qv = u + (v - u) = v in the attention kernel);  K = V = 0
@@ -505,6 +507,7 @@ int launch_dp_w(const AttnParams& p, hipStream_t s) {
     static LdsAttr attr;
     ensure_dynamic_lds(reinterpret_cast<const void*>(&relpos_attention_kernel<DP, NWV, false>), SM::TOTAL, attr);
     const int qtiles = (p.Tg + NWV * 16 - 1) / (NWV * 16);
+#ifdef EFFCONF_PHASE_PROF
     if constexpr (NWV == 4 && DP <= 128) {
         static const bool prof = getenv("EFFCONF_ATTN_PHASES") != nullptr;
         if (prof) {
@@ -517,21 +520,16 @@ int launch_dp_w(const AttnParams& p, hipStream_t s) {
             return hipGetLastError() == hipSuccess ? 0 : -1;
         }
     }
+#endif
     hipLaunchKernelGGL((relpos_attention_kernel<DP, NWV, false>), dim3(p.B * p.H * qtiles), dim3(NWV * 64), SM::TOTAL, s, p, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// 64-query (4-wave) workgroups, two per CU: the kernel is latency-bound on its K / V / E loads (phase profile above), and two
+// independent workgroups per CU hide more of it than one 128-query workgroup that stages K / V half as often (1.31 -> 1.23 ms
+// per step once the loads run two key blocks ahead)
 template <int DP>
-int launch_dp(const AttnParams& p, hipStream_t s) {
-    // 64-query (4-wave) workgroups, two per CU: the kernel is latency-bound on its K / V / E loads (phase profile above), and two
-    // independent workgroups per CU hide more of it than one 128-query workgroup that stages K / V half as often (1.31 -> 1.23 ms
-    // per step once the loads run two key blocks ahead).  Option "attn_waves" = 8 selects the 128-query variant.
-    const int force = p.force_waves;
-    constexpr bool fits8 = AttnSmem<DP, 8>::TOTAL <= 160 * 1024;
-    if constexpr (fits8)
-        if (force == 8) return launch_dp_w<DP, 8>(p, s);
-    return launch_dp_w<DP, 4>(p, s);
-}
+int launch_dp(const AttnParams& p, hipStream_t s) { return launch_dp_w<DP, 4>(p, s); }
 
 }  // namespace
 

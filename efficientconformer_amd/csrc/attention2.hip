@@ -533,16 +533,14 @@ int launch_relpos_attention2(const AttnParams& p0, int waves, hipStream_t s) {
 #endif
     if (p.dpad < p.d || p.q_rowstride != p.e_rowstride) return -2;
     if (p.rag_off && (waves != 1 || !p.rag_wg || p.q_rowstride != p.G * p.D)) return -2;      // ragged: natural layout, 64-query workgroups
-#define ATT2_CASE(DPV) case DPV: return waves == 1 ? launch2<DPV, 4, 1>(p, s) : launch2<DPV, 2, 2>(p, s);
-    // head width 96 (EfficientConformer Small stage 1): with two staging sets the kernel needs 9 registers more than two waves per SIMD allow
-    // and reloads loop-invariant addresses from scratch inside the key loop; ONE set (loads one key block ahead) fits: attention class
-    // 1.625 -> 1.555 ms per step (option attn_waves = 2 restores the two sets for comparison)
-    if (waves == 1 && p.dpad == 96 && p.force_waves != 2) return launch2<96, 4, 1, 1>(p, s);
-    // head width 64 (stages 2 / 3 of EfficientConformer Small): since the skew rows hold 64 floats the workgroup needs 52 KB of LDS, and with ONE staging set
-    // 168 registers - THREE workgroups per CU instead of two (the kernel is bound by per-workgroup latency): step 5.235 -> 5.14 ms (profiles/r5_27_*)
-    if (waves == 1 && p.dpad == 64 && p.force_waves != 2) return launch2<64, 4, 1, 1>(p, s);
+#define ATT2_CASE(DPV, SETS1) case DPV: return waves == 1 ? launch2<DPV, 4, 1, SETS1>(p, s) : launch2<DPV, 2, 2>(p, s);
+    // variant 1 runs ONE staging set (loads one key block ahead) at head widths 64 and 96:
+    //   96 (EfficientConformer Small stage 1): with two sets the kernel needs 9 registers more than two waves per SIMD allow and reloads
+    //      loop-invariant addresses from scratch inside the key loop; one set fits: attention class 1.625 -> 1.555 ms per step;
+    //   64 (stages 2 / 3 of EfficientConformer Small): since the skew rows hold 64 floats the workgroup needs 52 KB of LDS, and with one set
+    //      168 registers - THREE workgroups per CU instead of two (the kernel is bound by per-workgroup latency): step 5.235 -> 5.14 ms (profiles/r5_27_*)
     switch (p.dpad) {
-        ATT2_CASE(32) ATT2_CASE(64) ATT2_CASE(96) ATT2_CASE(128)
+        ATT2_CASE(32, 0) ATT2_CASE(64, 1) ATT2_CASE(96, 1) ATT2_CASE(128, 0)
         case 160: return launch2<160, 4, 1>(p, s);       // d = 135 (Medium / Large stage 1): one wave per SIMD either way; the 32-query variant spills
     }
 #undef ATT2_CASE

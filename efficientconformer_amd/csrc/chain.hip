@@ -214,7 +214,7 @@ __device__ __forceinline__ void load_a(const char* ab, size_t pitch, int row_byt
     }
 }
 
-// PROF (tuning only, EFFCONF_CHAIN_PHASES=81 | 162 | 163: KS = 8 full chain, KS = 16 head / tail): s_memtime per phase of the FFN stages -
+// PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN_PHASES=81 | 162 | 163: KS = 8 full chain, KS = 16 head / tail): s_memtime per phase of the FFN stages -
 // 0 advance (DMA wait + barrier + refill), 1 GEMM1, 2 Swish, 3 GEMM2, 4 everything else, 5 waves
 template <int KS, int NW, int NBUF, int KIND, bool PROF = false>
 __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_kernel(const ChainDev cd, unsigned long long* prof = nullptr) {
@@ -328,9 +328,11 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
     // is done with chunk k-1, whose buffer is refilled right after it.  Waiting one chunk AHEAD lets half of the waves run their
     // FFN iterations one phase late (barrier between Swish and the second GEMM instead of before the first, see ffn_stage):
     // the two waves sharing a SIMD then alternate between the MFMA pipe and the VALU instead of competing for the same one.
-    // Global stores issued between barriers (st1: since the last advance, st2: the interval before) sit in the same in-order
-    // vmcnt FIFO as the DMAs: they are younger than the chunk being waited for, so they are simply allowed to stay outstanding
-    // (waiting for them — i.e. for HBM write acknowledgements — cost ~10k cycles per Q/K/V chunk: s_memtime profile).
+    // Global stores issued between barriers (st1: since the last advance, st2: the interval before) share the vmcnt counter with
+    // the DMAs but may retire before an older DMA, so they are never counted into the allowed vmcnt.  The wait allows only the
+    // DMAs of the chunks ahead: vmcnt <= PER * ahead leaves at least PER loads retired beyond them, loads retire in order, so the
+    // waited chunk has landed whatever the stores do.  Stores may still stay outstanding when none are in flight since the
+    // last two barriers (st1 + st2 == 0: the exact per-chunk wait; waiting for HBM write acknowledgements cost ~10k cycles per Q/K/V chunk).
     int gc = 0, st1 = 0, st2 = 0;                          // next chunk to consume; store instructions in flight
     // Unpipelined 8-wave shapes (D = 168: no registers for the pipelined loop's second accumulator) wait one chunk AHEAD (barrier k: chunk
     // k + 1 has landed too; late waves, below); everything else uses the plain rule (barrier k: chunk k has landed)
@@ -350,7 +352,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
         // limit early and the barrier releases readers of a chunk whose last pieces have not landed - they read the ring slot's PREVIOUS weights.  Seen as a bf16-rounding
         // size perturbation of the last utterance of a row range in ~0.5 % of forwards with several ranges in flight (tools/stream_stress.py, profiles/r6_105 .. r6_108:
         // none in 6000 iterations with the queue drained here); allowing only the DMAs ahead is safe whatever order the stores retire in (loads retire in order)
-        else wait_vmcnt_dyn(PER * ahead + (p.count_stores ? st1 + ((AHEAD ? NBUF >= 4 : NBUF >= 3) ? st2 : 0) : 0));
+        else wait_vmcnt_dyn(PER * ahead);
         st2 = st1; st1 = 0;
         wg_barrier();
         const char* buf = smem + (gc % NBUF) * BUF;
@@ -733,6 +735,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
 #undef CH_TICK
 }
 
+#ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py) only
 unsigned long long* g_chain_prof = nullptr;
 void chain_prof_dump() {
     unsigned long long h[10];
@@ -745,6 +748,7 @@ void chain_prof_dump() {
             getenv("EFFCONF_CHAIN_PHASES"), h[9], (double)tot / h[9]);
     for (int i = 0; i < 9; ++i) fprintf(stderr, "[chain phases]   %-12s %10.0f cyc/wave  %5.1f%%\n", names[i], (double)h[i] / h[9], 100.0 * h[i] / tot);
 }
+#endif
 
 }  // namespace
 
@@ -803,6 +807,7 @@ int launch_chain_t(const ChainParams& p, hipStream_t s) {
     static LdsAttr attr;
     ensure_dynamic_lds(reinterpret_cast<const void*>(&chain_kernel<KS, NW, NBUF, KIND, false>), lds, attr);
     const int rows_per_wg = NW * 32;
+#ifdef EFFCONF_PHASE_PROF
     if constexpr ((KS == 8 && KIND == CHAIN_A_FULL) || (KS == 16 && (KIND == CHAIN_A_HEAD || KIND == CHAIN_A_TAIL))) {
         // EFFCONF_CHAIN_PHASES = "<KS><kind>": 81 = the KS = 8 full chain, 162 / 163 = the KS = 16 head / tail (one instance per process)
         static const bool prof = getenv("EFFCONF_CHAIN_PHASES") != nullptr && atoi(getenv("EFFCONF_CHAIN_PHASES")) == KS * 10 + KIND;
@@ -816,6 +821,7 @@ int launch_chain_t(const ChainParams& p, hipStream_t s) {
             return hipGetLastError() == hipSuccess ? 0 : -1;
         }
     }
+#endif
     hipLaunchKernelGGL((chain_kernel<KS, NW, NBUF, KIND, false>), dim3((p.M + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64), lds, s, cd, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -837,7 +843,7 @@ int launch_chain_kind(const ChainParams& p, hipStream_t s) {
     const bool small = p.small_m > 0 && p.M <= p.small_m;
     if (ks <= 2) return launch_chain_t<2, 4, 4, KIND>(p, s);
     if (ks <= 4) return small ? launch_chain_t<4, 2, 4, KIND>(p, s) : launch_chain_t<4, 8, 4, KIND>(p, s);
-    if (ks <= 8) return small ? launch_chain_t<8, 2, 4, KIND>(p, s) : (p.variant == 1 ? launch_chain_t<8, 4, 2, KIND>(p, s) : launch_chain_t<8, 8, 4, KIND>(p, s));
+    if (ks <= 8) return small ? launch_chain_t<8, 2, 4, KIND>(p, s) : launch_chain_t<8, 4, 2, KIND>(p, s);        // 4-wave workgroups, two per CU
     if (ks <= 12) return small ? launch_chain_t<12, 2, 3, KIND>(p, s) : launch_chain_t<12, 8, 3, KIND>(p, s);
     return launch_chain_t<16, 4, 3, KIND>(p, s);          // D = 240 / 256 already runs one wave per SIMD (4 waves); its 2-wave shape measured slower (84 against 79 us)
 }
@@ -858,9 +864,7 @@ bool chain_full_supported(int D, int dmax) { return chain_head_supported(D) && D
 int launch_chain(const ChainParams& p, int kind, hipStream_t s) {
     if (p.M <= 0) return 0;
     if (!chain_supported(p.D)) return -2;
-    if (p.pair >= 5 && kind != CHAIN_B && chain3_supported(p.D) && p.D >= p.pair_min_d && !(p.pair_small_max >= 0 && p.M <= p.pair_small_max) &&
-        (kind == CHAIN_A_HEAD || p.f[0].w2cm) && (kind == CHAIN_A_TAIL || p.f[1].w2cm)) return launch_chain3(p, kind, s);
-    if (p.pair && chain2_supported(p.D) && p.D >= p.pair_min_d && !(p.pair_small_max >= 0 && p.M <= p.pair_small_max)) return launch_chain2(p, kind, s);
+    if (p.pair && chain3_supported(p.D)) return kind == CHAIN_B ? launch_chain2(p, s) : launch_chain3(p, kind, s);      // padded width 256
     switch (kind) {
         case CHAIN_B: return launch_chain_kind<CHAIN_B>(p, s);
         case CHAIN_A_FULL: return launch_chain_kind<CHAIN_A_FULL>(p, s);

@@ -32,7 +32,7 @@ namespace {
 constexpr int NW3 = 12, NBUF3 = 3, NB3 = 8;                  // waves; ring buffers; waves that issue the ring (the B waves)
 constexpr int S3_ROW = 144;                                  // staging window: 32 rows x (128 + 16) bytes
 constexpr int S3_WIN = 32 * S3_ROW;                          // 4608: one window per B wave; [0, 4096) also carries hf slots / fragment exchanges
-constexpr int S3_TILE = 2 * S3_WIN + 512 + 256;              // per row tile: window 0, window 1, LayerNorm hand-off slots, the sink of wave A's L2 prefetches
+constexpr int S3_TILE = 2 * S3_WIN + 512;                    // per row tile: window 0, window 1, LayerNorm hand-off slots
 
 template <int KS>
 struct Geo3 {
@@ -96,7 +96,7 @@ __device__ __forceinline__ void s3_store(const char* stg, char* base, size_t pit
 //   FFN stage: 4 (statistics)  XB  n + 2 advances                  (PRE: ffn0, POST: ffn1)
 //   block norm: 4                                                  (PRE)
 //   Q/K/V:     4  XB  n_g1 advances  2 (drain)                     (POST)
-// PROF (tuning only, EFFCONF_CHAIN3_PHASES=<kind>): s_memtime per phase, the three waves of every 8th workgroup's first row tile
+// PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN3_PHASES=<kind>): s_memtime per phase, the three waves of every 8th workgroup's first row tile
 template <int KS, int KIND, bool PROF = false>
 __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd, unsigned long long* prof = nullptr) {
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
@@ -254,46 +254,14 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     if (role == 0) {
         // =================================================================== role A: first GEMM + Swish of every hidden chunk
         int gc = 0;
-        // L2 prefetch.  Every weight chunk is a FIRST touch for the XCD's L2 (the workgroups of a launch walk the weight stream in step, nothing is reused
-        // later, and the activation traffic of the launch evicts it before the next one): with two chunks of LDS prefetch the ring fill waited for memory-side
-        // latency in every iteration (vmcnt wait = 1/3 of a B wave's life, profiles/r5_10_*).  Wave A, which idles at the barriers more than half of its
-        // life, touches every 128-byte line of chunk gc + PFD once per iteration: one 4-byte LDS-DMA per lane (4 A waves x 64 lanes = the chunk's 256 lines)
-        // into a sink nobody reads - no destination register, nothing to wait for until the kernel ends
-        const int PFD = (p.nt >> 4) & 15;                    // tuning (option chain_nt, bits 4..7): prefetch distance in chunks, 0 = off
-        char* sink = win0 + 2 * S3_WIN + 512;
-        const uint32_t pf_off = (uint32_t)(((pr * 64 + lane) & 127) * 128);
-        auto prefetch = [&](int c) __attribute__((always_inline)) {
-            if (!(PFD > 0 && c < total)) return;
-            const bool ffn = c >= e0 && c < e2;
-            const bool second = c >= e1;
-            const int cf = c - (second ? e1 : e0);
-            const int nh = second ? n_f1 : n_f0;
-            int c1 = cf < nh ? cf : nh - 1, c2 = cf - 2;
-            c1 = c1 > 0 ? c1 : 0; c2 = c2 > 0 ? c2 : 0;
-            const bf16_t* fw1 = second ? p.f[1].w1 : p.f[0].w1;
-            const bf16_t* fw2 = second ? p.f[1].w2cm : p.f[0].w2cm;
-            const bool first_g = c < e0;
-            const bf16_t* gw = first_g ? p.g0.w : p.g1.w;
-            const int cg = first_g ? c : c - e2;
-            const char* w1 = reinterpret_cast<const char*>(fw1 + (size_t)c1 * CH * cd.ldr);
-            const char* w2 = reinterpret_cast<const char*>(fw2 + (size_t)c2 * (DP * 32));
-            const char* w = reinterpret_cast<const char*>(gw + (size_t)(cg > 0 ? cg : 0) * 64 * cd.ldr);
-            const char* lo = ffn ? w1 : w;
-            const char* hi = ffn ? w2 : w + (size_t)32 * cd.ldr * 2;
-            const char* base = (pr & 2) ? hi : lo;            // A waves 0, 1: the chunk's first 16 KiB (128 lines), 2, 3: its second
-            const uint32_t l = (uint32_t)(uintptr_t)(lds_void_t*)sink;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2" ::"s"(l), "v"(pf_off), "s"(base) : "memory", "m0");
-        };
         auto advanceA = [&]() __attribute__((always_inline)) -> const char* {
             wg_barrier();
             C3_TICK(0);
             const char* buf = smem + (gc % NBUF3) * BUF;
             ++gc;
-            prefetch(gc + NBUF3 - 2 + PFD);
             return buf;
         };
         auto no_rf = []() {};
-        for (int c = NBUF3 - 1; c < NBUF3 - 1 + PFD; ++c) prefetch(c);
         bf16x8 xf[KS];
         if constexpr (PRE) {
 #pragma unroll
@@ -348,7 +316,6 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
 #pragma unroll 1
             for (int i = 1; i < n; ++i) {
                 const char* buf = advanceA();
-                if (p.nt & 256) continue;                    // timing-only ablation (option chain_nt bit 8): no first GEMM / Swish
                 const f32x16 hn = gemm1(buf, sb1 + i * CH + 4 * half, [](int) {});
                 swish_out(hp, ((i - 1) & 1) ? win1 : win0);
                 hp = hn;
@@ -382,13 +349,15 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             qkv_stage(xf, advanceA, no_rf, st, gc % 3);
             C3_TICK(8);
         }
-        wait_vmcnt<0>();                                      // the prefetches write LDS: nothing may be in flight when the workgroup's LDS is handed on
         C3_DUMP();
         return;
     }
 
     // ======================================================================= role B: residual / accumulator tiles of one column half, the weight ring
     const int cw = role - 1, bidx = wave - 4;
+    // bidx < NB3 makes `i < KS` below compile-time for the first PER / 2 offsets (off_f[k] = off_r[k] there): without the hint the two
+    // extra offset registers were spilled, and their reloads inside the FFN loop waited behind the ring's DMAs (chain A at D = 240: +39 %)
+    __builtin_assume(bidx < NB3);
     const int ct0 = cw * NTH;
     char* stg = cw ? win1 : win0;                            // this wave's window
     float* my = cw ? slot1 : slot0;
@@ -431,7 +400,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         const int rem = ahead;
         ahead = ahead < 0 ? 0 : (ahead > MAXC ? MAXC : ahead);
         if (st1 + st2 == 0) wait_chunks<PER, MAXC>(rem);
-        else wait_vmcnt_dyn(PER * ahead + (p.count_stores ? st1 + st2 : 0));               // without the stores since: they may retire before an older DMA (chain.hip, advance())
+        else wait_vmcnt_dyn(PER * ahead);                      // without the stores since: they may retire before an older DMA (chain.hip, advance())
         C3_TICK(1);
         st2 = st1; st1 = 0;
         wg_barrier();
@@ -642,20 +611,18 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             publish(own, xnone, false);
         }
         add_cvec(sb2);
-        // iteration i: second GEMM of hidden chunk i - 2 (hf from window (i - 2) & 1, published by A in iteration i - 1), and the refill
-        const bool rf_first = (p.nt & 4) == 0;               // tuning (option chain_nt, bit 4): the refill behind the second GEMM instead of in front of it
+        // iteration i: the refill, then the second GEMM of hidden chunk i - 2 (hf from window (i - 2) & 1, published by A in iteration i - 1)
 #pragma unroll 1
         for (int i = 0; i < n + 2; ++i) {
             const char* buf = advance();
-            if (rf_first && !(p.nt & 1024)) refill();          // bit 10 (timing-only ablation): no weight stream
-            if (i >= 2 && !(p.nt & 512)) {                   // bit 9 (timing-only ablation): no second GEMM
+            refill();
+            if (i >= 2) {
                 const char* slot = ((i - 2) & 1) ? win1 : win0;
                 const bf16x8 h0 = *reinterpret_cast<const bf16x8*>(slot + lane * 16), h1 = *reinterpret_cast<const bf16x8*>(slot + 1024 + lane * 16);
                 gemm2(buf + HALF, h0, h1);
                 if constexpr (PROF) asm volatile("s_nop 0" :: "v"(xc[0][0]), "v"(xc[NTH - 1][15]));
             }
             C3_TICK(2);
-            if (!rf_first) refill();
         }
     };
     if constexpr (PRE) {
@@ -700,6 +667,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
 #undef C3_DUMP
 }
 
+#ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py) only
 unsigned long long* g_chain3_prof = nullptr;
 void chain3_prof_dump() {
     unsigned long long h[64];
@@ -717,6 +685,7 @@ void chain3_prof_dump() {
         for (int i = 0; i < 10; ++i) if (q[i]) fprintf(stderr, "[chain3 phases]   %-26s %10.0f cyc/wave  %5.1f%%\n", names[i], (double)q[i] / q[15], 100.0 * q[i] / tot);
     }
 }
+#endif
 
 template <int KS, int KIND>
 int launch_chain3_t(const ChainParams& p, hipStream_t s) {
@@ -742,11 +711,8 @@ int launch_chain3_t(const ChainParams& p, hipStream_t s) {
     if (lds > 160 * 1024) return -4;
     static LdsAttr attr;
     ensure_dynamic_lds(reinterpret_cast<const void*>(&chain3_kernel<KS, KIND, false>), lds, attr);
-#ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py); the product has neither the getenv nor the profiling instantiation
+#ifdef EFFCONF_PHASE_PROF
     static const bool prof = getenv("EFFCONF_CHAIN3_PHASES") != nullptr && atoi(getenv("EFFCONF_CHAIN3_PHASES")) == KIND;
-#else
-    constexpr bool prof = false;
-#endif
     if (prof) {
         if (!g_chain3_prof) {
             if (hipMalloc(&g_chain3_prof, 512) != hipSuccess || hipMemset(g_chain3_prof, 0, 512) != hipSuccess) return -1;
@@ -756,6 +722,7 @@ int launch_chain3_t(const ChainParams& p, hipStream_t s) {
         hipLaunchKernelGGL((chain3_kernel<KS, KIND, true>), dim3((p.M + 127) / 128), dim3(NW3 * 64), lds, s, cd, g_chain3_prof);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
+#endif
     hipLaunchKernelGGL((chain3_kernel<KS, KIND, false>), dim3((p.M + 127) / 128), dim3(NW3 * 64), lds, s, cd, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

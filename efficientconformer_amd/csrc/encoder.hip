@@ -58,7 +58,7 @@ struct BlockW {
     // fused row-local chains (chain.hip): every weight with its K index permuted per 16; FFN second weight / bias pre-scaled by 1/2
     bool chain_in = false, chain_out = false;          // chain-packed weights exist for the D-wide / De-wide parts of the block
     PackedLinear c_outp, c_pw1, c_pw2, c_qkv, c_f1a, c_f2a;
-    const bf16_t *c_f1b_cm = nullptr, *c_f2b_cm = nullptr;      // the same second weights chunk-major (chain2.hip): every 32-hidden-unit slab contiguous, in LDS slot order
+    const bf16_t *c_f1b_cm = nullptr, *c_f2b_cm = nullptr;      // the same second weights chunk-major (chain3.hip, padded width 256 only): every 32-hidden-unit slab contiguous, in LDS slot order
     const bf16_t *c_f1b = nullptr, *c_f2b = nullptr; const float *c_f1b2 = nullptr, *c_f2b2 = nullptr;
     int c_qkv_chunks = 0, c_pw1_chunks = 0;
     std::vector<float> h_ln_out_g, h_ln_out_b, h_u, h_v, h_f1b2, h_f2b2;     // host copies for the chains' constant blocks
@@ -99,13 +99,11 @@ struct EcEncoder {
     int ctc_mfma = 2;                        // CTC head: 2 split-bf16 operands on the bf16 MFMA (bf16 path; fp32 mode falls back to 1), 1 fp32 MFMA (bit-identical to 0), 0 the VALU kernel
     int attention_v2 = 1;                    // 0: attention.hip; 1 (default) / 2: attention2.hip variants where they support the head width (padded <= 160)
     // tuning / test options that used to be process-global environment switches (effconf_encoder_set_option)
-    int chain_count_stores = 0;              // measurement only: the unsafe counted waits of rounds 3 - 6 (kernels.h: ChainParams::count_stores)
-    int chain_variant = 1, chain_full_max = 192, attn_waves = 4, rs_variant = 0, ffn_variant = 0;
-    int chain_pair_min_d = 193, chain_nt = 0, chain_w2cm = 1;   // round 5 defaults: the column-pair kernels at padded width 256 (D = 240: 147 -> 119 us per tail + head; at 192 they cost more per row than chain.hip's 256-row workgroups)
+    int chain_full_max = 192;
     int dwconv_mfma = 1;                         // stride-1 depthwise convolutions on the matrix pipe (conv.hip dwconv_mfma_kernel): 1 = kernel size 15 (the Efficient Conformer
                                                  // family), 2 = also 31 / 7 (equally accurate, profiles/r5_35_dw_accuracy.txt, but ConformerCTC-Small's 5-frame test utterance sits ON the
                                                  // stated tolerance with either kernel and crosses it with this one's rounding: 0.0608 against 0.06), 0 = dwconv_kernel (VALU) everywhere
-    int chain_pair = 5, chain_pair_min_m = 0;   // chain2.hip (column-pair chains at padded width 192 / 256): 0 off, 1 burst refills, 2 hooked; launches below chain_pair_min_m rows stay on chain.hip
+    int chain_pair = 5;                      // 5: chain3.hip (chain A) / chain2.hip (chain B) at padded width 256 (D = 240: 147 -> 119 us per tail + head); 0: chain.hip everywhere (the reference the tests compare against)
     int chain_small_m = 4096;                // chain launches of at most this many rows run as 2-wave workgroups (small-batch latency; bit-identical rows)
     int chain_max_dim = 256;                 // fused chains only for stage widths <= this (tuning: wider stages on the per-GEMM / tiled kernels)
     int tiled_auto = 1;                      // wide_gemm = 0: configurations whose widest stage lies in (tiled_min_k, 384] (EfficientConformer Medium: D = 360) send that stage to LayerNorm + the tiled
@@ -567,7 +565,7 @@ int run_ffn(EcEncoder* e, hipStream_t st, const bf16_t* a, int M, int D, const P
         FfnParams p{};
         p.A = a; p.lda = ld8(D); p.X = x; p.ldx = D; p.Y = x; p.ldy = D;
         p.W1 = L1.w; p.ldw1 = L1.ldw; p.b1 = L1.bias; p.W2 = w2p; p.ldw2 = L2.ldw; p.b2 = L2.bias;
-        p.M = M; p.D = D; p.Fp = ec_round_up(F, 32); p.alpha = 0.5f; p.variant = e->ffn_variant;
+        p.M = M; p.D = D; p.Fp = ec_round_up(F, 32); p.alpha = 0.5f;
         if (ln) { p.ln_g = ln->g; p.ln_b = ln->b; }
         return launch_ffn_fused(p, st);
     }
@@ -601,7 +599,6 @@ int run_rs_or_tiled(EcEncoder* e, int cls, hipStream_t st, const bf16_t* A, int 
     GemmParams p{};
     p.A = A; p.lda = lda; p.W = L.w; p.ldw = L.ldw; p.bias = L.bias;
     p.M = M; p.N = L.N; p.K = L.K; p.C = C; p.ldc = ldc; p.R = R; p.ldr = ldr; p.alpha = alpha;
-    p.rs_variant = e->rs_variant;
     if (lnX && ln) { p.X = lnX; p.ldx = L.K; p.ln_g = ln->g; p.ln_b = ln->b; }
     return launch_rs_gemm(p, rs_epi, st);
 }
@@ -651,9 +648,9 @@ int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, int B, 
     return 0;
 }
 
-// chain launches of width D and M rows that go to chain2.hip (launch_chain's rule): there the tail and the next head of chain A are one kernel up to D = 256
 static const void* dw_mfma_table(const EcEncoder* e, const uint16_t* t, int ks) { return (e->dwconv_mfma == 2 || (e->dwconv_mfma == 1 && ks == 15)) ? t : nullptr; }
-static bool pair_on(const EcEncoder* e, int D, int M) { return e->chain_pair && chain2_supported(D) && D >= e->chain_pair_min_d && M >= e->chain_pair_min_m; }
+// chain launches of width D that go to chain2.hip / chain3.hip (launch_chain's rule): there the tail and the next head of chain A are one kernel up to D = 256
+static bool pair_on(const EcEncoder* e, int D) { return e->chain_pair && chain3_supported(D); }
 
 // Ragged batches (s.ragged): every utterance runs at its own length in one concatenated row space (kernels.h: RaggedRows) - the row-local
 // kernels (chains, GEMMs, LayerNorms) just see M rows; the frame-mixing ones (subsampling, attention, depthwise conv, conv_res decimation)
@@ -775,12 +772,12 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         p.T = qT; p.G = rg ? 1 : G; p.H = H; p.D = D; p.d = d; p.dpad = dpad; p.Tg = rg ? M : Tg; p.Tgp = Tgp;
         p.qu = reinterpret_cast<bf16_t*>(ws + w.qu);
         p.kh = reinterpret_cast<bf16_t*>(ws + w.kh); p.vt = reinterpret_cast<bf16_t*>(ws + w.vt);
-        p.u = W.u; p.v = W.v; p.rs_variant = e->rs_variant;
+        p.u = W.u; p.v = W.v;
         if (head_done) {
             // FFN1 and the Q/K/V projection of this block already ran inside the previous block's tail chain
         } else if (chain_head) {
             ChainParams cp{};
-            cp.variant = e->chain_variant; cp.count_stores = e->chain_count_stores; cp.small_m = e->chain_small_m; cp.pair = e->chain_pair; cp.pair_small_max = e->chain_pair_min_m - 1; cp.pair_min_d = e->chain_pair_min_d; cp.nt = e->chain_nt; cp.w2cm = e->chain_w2cm;
+            cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
             fill_chain_head(cp, W, D, F1c(b), qT, qTp, p);
             cp.M = M; cp.X = x; cp.ldx = D; cp.Y = x; cp.ldy = D; cp.consts = W.cc_head;
             PROF(PC_GEMM_FFN, 2.0 * M * (double)D * (2.0 * D * b.ff_ratio + 3.0 * D), (double)M * D * 16 + 22.0 * D * D);
@@ -831,7 +828,7 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             if (nat) { ap.q_bstride = (long long)Tp * D; ap.q_hstride = d; ap.q_rowstride = G * D; ap.e_hstride = d; ap.e_rowstride = G * D; }
             else { ap.q_bstride = (long long)H * Tg * dpad; ap.q_hstride = (long long)Tg * dpad; ap.q_rowstride = dpad;
                    ap.e_hstride = (long long)(2 * Tg - 1) * dpad; ap.e_rowstride = dpad; }
-            ap.out = o; ap.ldo = ld8(D); ap.scale = 1.0f / std::sqrt((float)d); ap.force_waves = e->attn_waves;
+            ap.out = o; ap.ldo = ld8(D); ap.scale = 1.0f / std::sqrt((float)d);
             // streaming mask of this block: built after the subsampling, sliced ::stride after every strided block before this one and ::G in
             // grouped attention (encoders.py:132-136, attentions.py:698): grouped positions compare (mask_stride * G) * (j - i) with the contexts
             const long long unit = (long long)mask_stride * G;
@@ -857,7 +854,7 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             snprintf(nm, sizeof(nm), "blocks.%d.att_o", k); trace_add(e, st, nm, o, M, D, ld8(D), 1);
             if (chain_b) {
                 ChainParams cp{};
-                cp.variant = e->chain_variant; cp.count_stores = e->chain_count_stores; cp.small_m = e->chain_small_m; cp.pair = e->chain_pair; cp.pair_small_max = e->chain_pair_min_m - 1; cp.pair_min_d = e->chain_pair_min_d; cp.nt = e->chain_nt; cp.w2cm = e->chain_w2cm;
+                cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
                 cp.M = M; cp.D = D; cp.X = x; cp.ldx = D; cp.Y = x; cp.ldy = D; cp.A = o; cp.lda = ld8(D);
                 cp.g0 = ChainGemm{W.c_outp.w, W.c_outp.ldw, W.c_outp.bias, 0};
                 cp.ln[0] = ChainLn{W.ln_conv.g, W.ln_conv.b};
@@ -898,10 +895,10 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             bool next_head = false;
             if (!last) {
                 const EcBlock& nbk = e->blocks[k + 1];
-                next_head = W.cc_full && nbk.dim_model <= e->chain_max_dim && e->bw[k + 1].chain_in && chain_full_supported(De, pair_on(e, De, Mo) ? 256 : e->chain_full_max) && (((nbk.group_size * nbk.dim_model / nbk.num_heads) % 2) == 0 || !head_major_odd) && nbk.dim_model == De;
+                next_head = W.cc_full && nbk.dim_model <= e->chain_max_dim && e->bw[k + 1].chain_in && chain_full_supported(De, pair_on(e, De) ? 256 : e->chain_full_max) && (((nbk.group_size * nbk.dim_model / nbk.num_heads) % 2) == 0 || !head_major_odd) && nbk.dim_model == De;
             }
             ChainParams cp{};
-            cp.variant = e->chain_variant; cp.count_stores = e->chain_count_stores; cp.small_m = e->chain_small_m; cp.pair = e->chain_pair; cp.pair_small_max = e->chain_pair_min_m - 1; cp.pair_min_d = e->chain_pair_min_d; cp.nt = e->chain_nt; cp.w2cm = e->chain_w2cm;
+            cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
             cp.M = Mo; cp.D = De; cp.X = x; cp.ldx = De; cp.Y = xo; cp.ldy = De; cp.A = cbuf; cp.lda = ld8(De);
             cp.g0 = ChainGemm{W.c_pw2.w, W.c_pw2.ldw, W.c_pw2.bias, 0};
             cp.ln[0] = ChainLn{W.ln_ffn2.g, W.ln_ffn2.b};
@@ -1644,10 +1641,10 @@ int effconf_encoder_finalize(EcEncoder* e) {
             if (!b2 || !pack_named_linear(e, p + ".feed_forward_module1.layers.1", F1, D, &W.c_f1a, &err, true, p + ".feed_forward_module1.layers.0") ||
                 !pack_named_linear(e, m + ".mhsa.output_layer", D, D, &W.c_outp, &err, true)) return fail("chain packing failed: " + err);
             W.c_f1b = pack_ffn2_permuted(e, p + ".feed_forward_module1.layers.4", D, F1, 0.5f);
-            if (chain2_supported(D)) W.c_f1b_cm = pack_ffn2_chunkmajor(e, p + ".feed_forward_module1.layers.4", D, F1, 0.5f, chain_padded_width(D));
+            if (chain3_supported(D)) W.c_f1b_cm = pack_ffn2_chunkmajor(e, p + ".feed_forward_module1.layers.4", D, F1, 0.5f, chain_padded_width(D));
             std::vector<float> hb(b2->data); for (float& x : hb) x *= 0.5f;
             W.c_f1b2 = upload(e, hb); W.h_f1b2 = hb;
-            if (!W.c_f1b || !W.c_f1b2) return fail("upload failed");
+            if (!W.c_f1b || !W.c_f1b2 || (chain3_supported(D) && !W.c_f1b_cm)) return fail("upload failed");
             W.chain_in = true;
         }
         if (chain_supported(De)) {     // De-wide part: pointwise-2, FFN2
@@ -1655,13 +1652,13 @@ int effconf_encoder_finalize(EcEncoder* e) {
             if (!b2 || !pack_named_linear(e, p + ".feed_forward_module2.layers.1", F2, De, &W.c_f2a, &err, true, p + ".feed_forward_module2.layers.0") ||
                 !pack_named_linear(e, p + ".convolution_module.layers.7", De, De, &W.c_pw2, &err, true)) return fail("chain packing failed: " + err);
             W.c_f2b = pack_ffn2_permuted(e, p + ".feed_forward_module2.layers.4", De, F2, 0.5f);
-            if (chain2_supported(De)) W.c_f2b_cm = pack_ffn2_chunkmajor(e, p + ".feed_forward_module2.layers.4", De, F2, 0.5f, chain_padded_width(De));
+            if (chain3_supported(De)) W.c_f2b_cm = pack_ffn2_chunkmajor(e, p + ".feed_forward_module2.layers.4", De, F2, 0.5f, chain_padded_width(De));
             std::vector<float> hb(b2->data); for (float& x : hb) x *= 0.5f;
             W.c_f2b2 = upload(e, hb); W.h_f2b2 = hb;
             const HostTensor *og = find(e, p + ".norm.weight"), *ob = find(e, p + ".norm.bias");
             if (!og || !ob) return fail("missing " + p + ".norm");
             W.h_ln_out_g = og->data; W.h_ln_out_b = ob->data;
-            if (!W.c_f2b || !W.c_f2b2) return fail("upload failed");
+            if (!W.c_f2b || !W.c_f2b2 || (chain3_supported(De) && !W.c_f2b_cm)) return fail("upload failed");
             W.chain_out = true;
         }
         if (!pack_named_linear(e, m + ".mhsa.pos_layer", D, D, &W.pos, &err)) return fail(err);
@@ -1765,7 +1762,7 @@ int effconf_encoder_finalize(EcEncoder* e) {
         }
         if (W.chain_out && chain_tail_supported(De)) {
             W.cc_tail = build(CHAIN_A_TAIL, De, &W, nullptr, &b, nullptr);
-            if (chain_full_supported(De, std::max(e->chain_full_max, chain2_supported(De) ? 256 : 0)) && k + 1 < e->blocks.size() && e->bw[k + 1].chain_in && e->blocks[k + 1].dim_model == De)
+            if (chain_full_supported(De, std::max(e->chain_full_max, chain3_supported(De) ? 256 : 0)) && k + 1 < e->blocks.size() && e->bw[k + 1].chain_in && e->blocks[k + 1].dim_model == De)
                 W.cc_full = build(CHAIN_A_FULL, De, &W, &e->bw[k + 1], &b, &e->blocks[k + 1]);
         }
     }
@@ -2502,22 +2499,13 @@ int effconf_encoder_set_option(EcEncoder* e, const char* name, int32_t value) {
     if (!strcmp(name, "wide_gemm")) { if (value < 0 || (value > 3 && value < 16)) return fail("wide_gemm: 0 (by shape), 1 (never), 2 (256-column tile), 3 (128-column tile), >= 16 (by shape with this many 256 x 256 tiles as the threshold)"); e->wide_gemm = value; return 0; }
     if (!strcmp(name, "attention_v2")) { if (value != 0 && value != 1 && value != 2) return fail("attention_v2: 0, 1 or 2"); e->attention_v2 = value; return 0; }
     // former EFFCONF_* environment switches (process-global statics): per-handle options now
-    if (!strcmp(name, "chain_variant")) { if (value != 0 && value != 1) return fail("chain_variant: 0 (8-wave chain workgroups) or 1 (4-wave, two per CU, at 65..128-wide stages)"); e->chain_variant = value; return 0; }
     if (!strcmp(name, "chain_full_max")) { if (value < 0 || value > 256) return fail("chain_full_max: widest stage (0..256) that runs chain A as ONE kernel"); e->chain_full_max = value; return 0; }   // widening takes effect at the next finalize (the combined constant blocks are built there)
-    if (!strcmp(name, "attn_waves")) { if (value != 4 && value != 8 && value != 2) return fail("attn_waves: 4 or 8 (attention.hip workgroup size); 2: attention2.hip with two staging sets at head widths 64 / 96 (two workgroups per CU at 64: tuning)"); e->attn_waves = value; return 0; }
-    if (!strcmp(name, "rs_variant")) { if (value != 0 && value != 1) return fail("rs_variant: 0 or 1 (8-wave row-stationary GEMM workgroups)"); e->rs_variant = value; return 0; }
     if (!strcmp(name, "chain_max_dim")) { e->chain_max_dim = value; return 0; }
     if (!strcmp(name, "chain_small_m")) { e->chain_small_m = value; return 0; }
-    if (!strcmp(name, "chain_pair")) { if (value < 0 || value > 5) return fail("chain_pair: 0 (chain.hip everywhere), 5 (chain3.hip for chain A at padded width 256, chain2.hip mode 4 elsewhere), 1 .. 4 (chain2.hip's column-pair kernels at padded width 192 / 256; refill modes, see launch_chain2_kind)"); e->chain_pair = value; return 0; }
-    if (!strcmp(name, "chain_pair_min_m")) { e->chain_pair_min_m = value; return 0; }
+    if (!strcmp(name, "chain_pair")) { if (value != 0 && value != 5) return fail("chain_pair: 0 (chain.hip everywhere) or 5 (chain3.hip for chain A, chain2.hip for chain B at padded width 256)"); e->chain_pair = value; return 0; }
     if (!strcmp(name, "dwconv_mfma")) { if (value < 0 || value > 2) return fail("dwconv_mfma: 0, 1 (kernel size 15) or 2 (15 / 31 / 7)"); e->dwconv_mfma = value; return 0; }
-    if (!strcmp(name, "chain_pair_min_d")) { e->chain_pair_min_d = value; return 0; }
-    if (!strcmp(name, "chain_nt")) { e->chain_nt = value; return 0; }
-    if (!strcmp(name, "chain_w2cm")) { e->chain_w2cm = value; return 0; }
     if (!strcmp(name, "tiled_min_k")) { e->tiled_min_k = value; return 0; }
-    if (!strcmp(name, "chain_count_stores")) { e->chain_count_stores = value != 0; return 0; }
     if (!strcmp(name, "tiled_auto")) { e->tiled_auto = value; return 0; }      // 2: every layer with K in (tiled_min_k, 384] whatever the widest stage (tuning)
-    if (!strcmp(name, "ffn_variant")) { if (value < 0 || value > 2) return fail("ffn_variant: 0, 1 or 2 (fused-FFN workgroup shapes)"); e->ffn_variant = value; return 0; }
     if (!strcmp(name, "head_major_odd")) { e->head_major_odd = value != 0; return 0; }
     if (!strcmp(name, "split_ffn")) { e->split_ffn = value != 0; return 0; }
     if (!strcmp(name, "split_sublin")) { e->split_sublin = value != 0; return 0; }

@@ -52,7 +52,6 @@ struct GemmParams {
     // computed in the prologue from the fp32 residual stream instead of being read from A
     const float* X; int ldx; const float *ln_g, *ln_b;
     int wide;                          // launch_gemm only: 0 pick by shape, 1 never gemm256.hip, 2 / 3 force its 256- / 128-column tile
-    int rs_variant;                    // launch_rs_gemm only (option "rs_variant"): 1 = 8-wave workgroups (256 rows) at KS = 8 / 16
 };
 int launch_gemm(const GemmParams& p, int epi, hipStream_t s);
 // gemm256.hip: 256 x bn x 64 tiles, both operands by LDS-DMA (bn = 256 or 128); the same operands and epilogues as launch_gemm
@@ -72,7 +71,6 @@ struct FfnParams {
     int M, D, Fp;
     float alpha;
     const float *ln_g, *ln_b;          // if non-null: a = LayerNorm(X) computed in the prologue (A is ignored)
-    int variant;                       // option "ffn_variant": workgroup shape overrides (tuning)
 };
 // single row-stationary GEMM (K <= 384); epi: 0 residual fp32, 1 fp32, 2 GLU bf16 (N = packed a|b rows), 3 QKV head-major
 // scatter, 4 QKV natural layout (weight rows permuted inside every 32-row chunk, see pack_linear_chunkperm)
@@ -88,7 +86,7 @@ int launch_ffn_fused(const FfnParams& p, hipStream_t s);
 // One kernel runs a whole row-local stretch of the Conformer block on a 32-row tile per wave, the fp32 residual row staying in
 // registers between GEMMs (see chain.hip).  All weights are K-permuted per 16 (pack_linear_kperm), rows padded to 64.
 struct ChainGemm { const bf16_t* w; int ldw; const float* bias; int nchunks; };        // nchunks = 64-row chunks
-struct ChainFfn { const bf16_t* w1; int ldw1; const float* b1; const bf16_t* w2; int ldw2; const float* b2; int Fp; const bf16_t* w2cm; };   // w2cm: w2 chunk-major (chain2.hip; may be null)   // w2, b2 pre-scaled by 1/2
+struct ChainFfn { const bf16_t* w1; int ldw1; const float* b1; const bf16_t* w2; int ldw2; const float* b2; int Fp; const bf16_t* w2cm; };   // w2cm: w2 chunk-major (chain3.hip; null below padded width 256)   // w2, b2 pre-scaled by 1/2
 struct ChainLn { const float* g; const float* b; };
 struct ChainParams {
     int M, D;
@@ -102,15 +100,8 @@ struct ChainParams {
     bf16_t *qu, *kh, *vt; const float *u, *v; int T, Tp;          // QKV outputs (Q + u, K, V): rows (b, t) -> (b*Tp + t)*D
     bf16_t* glu; int ldg, Ng;           // GLU output [M][ldg], Ng channels
     const float* consts;                // biases / block-norm gamma, beta / u, v as ONE zero padded block laid out by chain_const_layout
-    int variant;                        // option "chain_variant": 1 = 4-wave workgroups (two per CU) at KS = 8
-    int count_stores;                   // option "chain_count_stores" (measurement only, default 0): 1 = the counted ring waits of rounds 3 - 6 that also allow the global stores
-                                        // since the last barrier to stay outstanding - UNSAFE: a store can retire before an older LDS-DMA (chain.hip, advance())
     int small_m;                        // option "chain_small_m": launches of at most this many rows use 2-wave workgroups (64 rows): see launch_chain_kind
-    int pair_min_d;                     // option "chain_pair_min_d": narrower stages stay on chain.hip
-    int w2cm;                           // option "chain_w2cm": chain2.hip streams the FFN second weights from their chunk-major images
-    int nt;                             // option "chain_nt": non-temporal hints on the activation loads (1) / stores (2) of chain2.hip (3 = both)
-    int pair_small_max;                 // option "chain_pair_min_m" - 1: launches of at most this many rows stay on chain.hip's shapes (-1: none)
-    int pair;                           // option "chain_pair": != 0 = the column-pair kernels of chain2.hip where they exist (padded width 192 / 256); 1 = burst refills, 2 = hooked
+    int pair;                           // option "chain_pair": 5 = chain3.hip (chain A) / chain2.hip (chain B) at padded width 256; 0 = chain.hip everywhere
 };
 enum { CHAIN_B = 0, CHAIN_A_FULL = 1, CHAIN_A_HEAD = 2, CHAIN_A_TAIL = 3 };   // HEAD: first block (no previous tail); TAIL: last block (no next head)
 bool chain_supported(int D);
@@ -120,9 +111,9 @@ bool chain_head_supported(int D);   // FFN1 + Q/K/V half (chain A head / full)
 bool chain_tail_supported(int D);   // pointwise-2 + FFN2 + block norm half
 bool chain_full_supported(int D, int dmax = 192);   // tail + next block's head in one kernel (dmax: option "chain_full_max")
 int launch_chain(const ChainParams& p, int kind, hipStream_t s);
-// chain2.hip: the same chains with a PAIR of waves per 32 rows (column halves), 8-wave 128-row workgroups at two waves per SIMD; rows bit-identical to chain.hip's
-bool chain2_supported(int D);
-int launch_chain2(const ChainParams& p, int kind, hipStream_t s);
+// chain2.hip: chain B at padded width 256 with a PAIR of waves per 32 rows (column halves), 8-wave 128-row workgroups at two waves per SIMD; rows
+// bit-identical to chain.hip's
+int launch_chain2(const ChainParams& p, hipStream_t s);
 // chain3.hip: chain A at padded width 256 with the row tile spread over THREE waves (first GEMM + Swish | second GEMM on a column half + the weight stream,
 // twice): 12-wave 128-row workgroups, three waves per SIMD; needs the chunk-major second FFN weights (ChainFfn::w2cm); rows bit-identical to chain.hip's
 bool chain3_supported(int D);
@@ -156,7 +147,6 @@ struct AttnParams {
     int B, H, T, G, D, d, dpad, Tg, Tgp;
     bf16_t* out; int ldo;                   // [B*T][ldo] un-grouped attention output (rows t >= T dropped)
     float scale;                            // 1/sqrt(d)
-    int force_waves;                        // attention.hip only (option "attn_waves"): 8 = one 128-query workgroup per CU where LDS allows
     // ragged batch (attention2.hip, natural layout): rag_off [B + 1] first row of every utterance in the Q / K / V / out row space (rows
     // padded to the group size per utterance), lens[b] = its frames (all valid), rag_wg [B + 1] prefix sums of H x ceil(Tg_b / 64)
     // workgroups in the kernel's utterance order (0, 8, 16, .. | 1, 9, ..), rag_nwg their total, rag_tgmax = Tg of the longest utterance

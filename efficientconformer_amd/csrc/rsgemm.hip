@@ -158,7 +158,7 @@ struct FfnStage {
 };
 
 // KS: k16-steps over D (D <= 16*KS), NT2 = KS/2: 32-col tiles over D, RT: 32-row tiles per wave, NW: waves, NBUF: ring depth
-// PROF: per-phase s_memtime accounting (tuning only, EFFCONF_FFN_PHASES=1): 0 prologue, 1 chunk wait + barrier, 2 DMA issue,
+// PROF: per-phase s_memtime accounting (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_FFN_PHASES=1): 0 prologue, 1 chunk wait + barrier, 2 DMA issue,
 // 3 GEMM1, 4 bias + Swish + pack, 5 GEMM2, 6 epilogue, 7 waves
 template <int KS, int NT2, int RT, int NW, int NBUF, bool PROF = false>
 __global__ __launch_bounds__(NW * 64) void ffn_fused_kernel(const FfnParams p, unsigned long long* prof = nullptr) {
@@ -341,6 +341,7 @@ __global__ __launch_bounds__(NW * 64) void ffn_fused_kernel(const FfnParams p, u
 #undef FFN_TICK
 }
 
+#ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py) only
 unsigned long long* g_ffn_prof = nullptr;     // EFFCONF_FFN_PHASES=1: device counters, dumped at exit
 void ffn_prof_dump() {
     unsigned long long all[8 * 8];
@@ -355,6 +356,7 @@ void ffn_prof_dump() {
         for (int i = 0; i < 7; ++i) fprintf(stderr, "[ffn phases]   %-13s %10.0f cyc/wave  %5.1f%%\n", names[i], (double)h[i] / h[7], 100.0 * h[i] / tot);
     }
 }
+#endif
 
 template <int KS, int NT2, int RT, int NW, int NBUF>
 int launch_ffn_t(const FfnParams& p, hipStream_t s) {
@@ -362,10 +364,12 @@ int launch_ffn_t(const FfnParams& p, hipStream_t s) {
     using ST = FfnStage<KS, NT2, NW, NBUF>;
     const int lds = SM::RING + p.Fp * 4 + NT2 * 32 * 4 + KS * 32 * 4 + (ST::ALIAS ? 0 : ST::BYTES);
     if (lds > 160 * 1024) return -4;
-    static LdsAttr attr, attr_prof;
+    static LdsAttr attr;
     ensure_dynamic_lds(reinterpret_cast<const void*>(&ffn_fused_kernel<KS, NT2, RT, NW, NBUF, false>), lds, attr);
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&ffn_fused_kernel<KS, NT2, RT, NW, NBUF, true>), lds, attr_prof);
     const int rows_per_wg = NW * RT * 32;
+#ifdef EFFCONF_PHASE_PROF
+    static LdsAttr attr_prof;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&ffn_fused_kernel<KS, NT2, RT, NW, NBUF, true>), lds, attr_prof);
     static const bool prof = getenv("EFFCONF_FFN_PHASES") != nullptr;
     if (prof) {
         if (!g_ffn_prof) {
@@ -376,6 +380,7 @@ int launch_ffn_t(const FfnParams& p, hipStream_t s) {
                            dim3(NW * 64), lds, s, p, g_ffn_prof + 8 * ((KS / 4) & 7));
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
+#endif
     hipLaunchKernelGGL((ffn_fused_kernel<KS, NT2, RT, NW, NBUF, false>), dim3((p.M + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64),
                        lds, s, p, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -398,8 +403,9 @@ enum { RS_RESID = 0, RS_F32 = 1, RS_GLU = 2, RS_QKV = 3, RS_QKV_NAT = 4 };
 struct RsDev { GemmParams p; int nchunks; FastDiv32 fD, fd; };
 
 // G = output tiles (32 columns each) accumulated in registers before they are flushed.  Flushes of the QKV / GLU
-// variants contain only stores and sit at the FRONT of an iteration (before the next DMA issue), so the counted vmcnt
-// never under-waits (memory ops retire in order; extra stores in the FIFO can only make the wait stricter).  The
+// variants contain only stores and sit at the FRONT of an iteration (before the next DMA issue).  The counted vmcnt never
+// under-waits because it allows only the DMAs of the chunks ahead, never the stores: stores may retire before an older DMA,
+// but loads retire in order, so vmcnt <= (DMAs ahead) means the waited chunk has landed whatever the stores do.  The
 // residual variants read R, so they keep the whole row (G >= N/32) and flush once after the loop.
 // second launch-bounds argument = minimum waves per SIMD: small workgroups want several co-resident per CU so that one
 // workgroup's prologue / flush memory phases overlap another's MFMA phase
@@ -693,27 +699,26 @@ int launch_rs_t(const RsDev& gd, hipStream_t s) {
 
 // configuration class from max(K, N_resident): KS k-steps; residual variants keep KS/2 output tiles, the others 4
 // Shape heuristics (tuned on MI355X, see profiles/): small-N GEMMs are dominated by per-workgroup fixed latency, so
-// they use 4-wave workgroups (128 rows) at several workgroups per CU; variant 1 = 8 waves (256 rows).
+// they use 4-wave workgroups (128 rows) at several workgroups per CU.
 template <int EPI>
 int launch_rs_ks(const RsDev& gd, hipStream_t s) {
     constexpr bool whole = (EPI == RS_RESID || EPI == RS_F32);
     const int width = whole ? (gd.p.K > gd.p.N ? gd.p.K : gd.p.N) : gd.p.K;
     const int ks = (width + 15) / 16;
-    const bool big = gd.p.rs_variant == 1;
     if constexpr (whole) {      // KS/2 resident output tiles per row
         if (ks <= 2) return launch_rs_t<2, 1, 2, 2, 4, EPI>(gd, s);
         if (ks <= 4) return launch_rs_t<4, 2, 2, 4, 4, EPI>(gd, s);
-        if (ks <= 8) return big ? launch_rs_t<8, 4, 1, 8, 4, EPI>(gd, s) : launch_rs_t<8, 4, 1, 4, 4, EPI>(gd, s);
+        if (ks <= 8) return launch_rs_t<8, 4, 1, 4, 4, EPI>(gd, s);
         if (ks <= 12) return launch_rs_t<12, 6, 1, 4, 4, EPI>(gd, s);
-        if (ks <= 16) return big ? launch_rs_t<16, 8, 1, 8, 4, EPI>(gd, s) : launch_rs_t<16, 8, 1, 4, 4, EPI>(gd, s);
+        if (ks <= 16) return launch_rs_t<16, 8, 1, 4, 4, EPI>(gd, s);
         if (ks <= 20) return launch_rs_t<20, 10, 1, 4, 4, EPI>(gd, s);
         return launch_rs_t<24, 12, 1, 4, 4, EPI>(gd, s);
     } else {                    // QKV / GLU: groups of 4 tiles, stores only
         if (ks <= 2) return launch_rs_t<2, 2, 1, 2, 4, EPI>(gd, s);
         if (ks <= 4) return launch_rs_t<4, 4, 1, 4, 4, EPI>(gd, s);
-        if (ks <= 8) return big ? launch_rs_t<8, 4, 1, 8, 4, EPI>(gd, s) : launch_rs_t<8, 4, 1, 4, 4, EPI>(gd, s);
+        if (ks <= 8) return launch_rs_t<8, 4, 1, 4, 4, EPI>(gd, s);
         if (ks <= 12) return launch_rs_t<12, 4, 1, 4, 4, EPI>(gd, s);
-        if (ks <= 16) return big ? launch_rs_t<16, 4, 1, 8, 4, EPI>(gd, s) : launch_rs_t<16, 4, 1, 4, 4, EPI>(gd, s);
+        if (ks <= 16) return launch_rs_t<16, 4, 1, 4, 4, EPI>(gd, s);
         if (ks <= 20) return launch_rs_t<20, 4, 1, 4, 4, EPI>(gd, s);
         return launch_rs_t<24, 4, 1, 8, 4, EPI>(gd, s);
     }
@@ -727,19 +732,11 @@ int launch_ffn_fused(const FfnParams& p, hipStream_t s) {
     if (p.M <= 0) return 0;
     if (!ffn_fused_supported(p.D) || p.Fp % CH || p.lda % 8 || p.ldw1 % 8 || p.ldw2 % 8) return -2;
     const int ks = (p.D + 15) / 16;
-    // rows per workgroup / waves per SIMD trade-offs, selected per width class (option "ffn_variant" overrides for tuning)
-    const int var = p.variant;
+    // rows per workgroup / waves per SIMD trade-offs, selected per width class
     if (ks <= 2) return launch_ffn_t<2, 1, 1, 4, 4>(p, s);
     if (ks <= 4) return launch_ffn_t<4, 2, 1, 8, 4>(p, s);
-    if (ks <= 8) {
-        if (var == 1) return launch_ffn_t<8, 4, 1, 4, 3>(p, s);      // 128 rows, 3 workgroups per CU
-        if (var == 2) return launch_ffn_t<8, 4, 1, 4, 4>(p, s);
-        return launch_ffn_t<8, 4, 1, 8, 4>(p, s);
-    }
-    if (ks <= 12) {
-        if (var == 1) return launch_ffn_t<12, 6, 1, 4, 4>(p, s);
-        return launch_ffn_t<12, 6, 1, 8, 3>(p, s);                   // 2 waves per SIMD, 256 rows; ring of 3 leaves room for the staging region
-    }
+    if (ks <= 8) return launch_ffn_t<8, 4, 1, 8, 4>(p, s);
+    if (ks <= 12) return launch_ffn_t<12, 6, 1, 8, 3>(p, s);         // 2 waves per SIMD, 256 rows; ring of 3 leaves room for the staging region
     if (ks <= 16) return launch_ffn_t<16, 8, 1, 4, 3>(p, s);
     if (ks <= 20) return launch_ffn_t<20, 10, 1, 4, 3>(p, s);
     return launch_ffn_t<24, 12, 1, 4, 3>(p, s);

@@ -227,8 +227,6 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
  *   split; falls back to 1 where the shape is not supported; front ends wider than 128 channels / columns - EfficientConformer Medium, Large - run
  *   sublinear3.hip instead: option "sub3_auto", default 1), 3 = sublinear3.hip (round 6: the same fusion in chunks of (output frequency, 32 channels), any
  *   channel count / width up to 384; bit-identical to sublinear2.hip where both exist, slower there).
- * "chain_count_stores" (default 0; measurement only): 1 = the weight-ring waits of rounds 3 - 6, which also allowed global stores to stay outstanding - UNSAFE (a store can
- *   retire before an older LDS-DMA; profiles/r6_108_ring_wait_fix.txt): kept to reproduce the finding, never for production.
  * "tiled_auto" (default 1; round 6): with "wide_gemm" = 0, a configuration whose widest stage lies in ("tiled_min_k" = 256, 384] - EfficientConformer Medium's
  *   D = 360 - runs that stage as LayerNorm + tiled GEMMs instead of the row-stationary kernels (+ 2.3 % on Medium; decided per configuration at finalize,
  *   never per batch: one rounding path per handle).  0 = the row-stationary kernels as before.
@@ -248,13 +246,14 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
  * "dwconv_mfma" (default 1; round 5): stride-1 depthwise convolutions on the matrix pipe (csrc/conv.hip dwconv_mfma_kernel: 4 x 4 x 4 Toeplitz blocks, one per
  *   channel, fp32 taps as bf16 hi + lo halves): 1 = kernel size 15, 2 = also 31 / 7, 0 = the VALU kernel everywhere.  Outputs agree with the VALU kernel's
  *   up to the summation order (a bf16 output may move by one ulp).
- * "attn_waves" = 2 (round 5): attention2.hip with two staging sets (two workgroups per CU at head width 64; the default is one set, three workgroups).
- * "chain_pair" (default 5), "chain_pair_min_d", "chain_w2cm", "chain_nt": kernel selection of the chains at padded width 256 (csrc/chain2.hip, chain3.hip; bit-identical).
- * "chain_variant" (0 / 1), "chain_full_max" (widest stage that runs chain A as one kernel; set before finalize to widen), "attn_waves"
- *   (4 / 8, attention.hip), "rs_variant" (0 / 1), "ffn_variant" (0 .. 2), "head_major_odd" (0 / 1), "exact_attention" (0 tiled / 2 tiled with 16-row workgroups / 1 one wave per query row; fp32 mode, bit-identical): tuning / test switches of the kernel launchers that were
- *   process-global EFFCONF_* environment variables until round 2; per handle now.  (Still read from the environment, once, as
- *   profiling / test hooks: EFFCONF_POISON_GUARDS at create, EFFCONF_{CHAIN,ATTN,FFN}_PHASES for the in-kernel phase profilers of chain.hip / attention.hip /
- *   rsgemm.hip.  EFFCONF_CHAIN2_PHASES, EFFCONF_CHAIN3_PHASES and EFFCONF_ATTN_ABLATE exist in the tuning library of tools/build_ablate.py only - round 6.)
+ * "chain_pair" (default 5): kernel selection of the chains at padded width 256: 5 = csrc/chain3.hip for chain A and csrc/chain2.hip for chain B,
+ *   0 = csrc/chain.hip everywhere (the reference; bit-identical).  Any other value is refused.
+ * "chain_full_max" (widest stage that runs chain A as one kernel; set before finalize to widen), "head_major_odd" (0 / 1), "exact_attention" (0 tiled / 2 tiled with 16-row workgroups / 1 one wave per query row; fp32 mode, bit-identical): tuning / test switches of the kernel launchers that were
+ *   process-global EFFCONF_* environment variables until round 2; per handle now.  (Still read from the environment, once: EFFCONF_POISON_GUARDS at
+ *   create.  The in-kernel phase profilers - EFFCONF_{CHAIN,CHAIN2,CHAIN3,ATTN,FFN}_PHASES - and EFFCONF_ATTN_ABLATE exist in the tuning library of
+ *   tools/build_ablate.py only.)
+ * Removed options (tuning-only kernel variants; set_option now fails with "unknown option"): "chain_count_stores", "chain_variant", "chain_pair_min_d",
+ *   "chain_pair_min_m", "chain_nt", "chain_w2cm", "rs_variant", "ffn_variant", "attn_waves".  No exported symbol or struct changed.
  * "exact_fp32" (default 0): fp32-operand precision mode (csrc/exact.hip): every GEMM on fp32 MFMA, fp32 attention / convolutions,
  *   so that greedy CTC label sequences equal the reference's CPU fp32 path (model_ctc.py:99-133) wherever its top-2 logit margins
  *   exceed fp32 summation-order noise; ~10x slower than the default bf16-operand path.  Set to 1 BEFORE effconf_encoder_finalize

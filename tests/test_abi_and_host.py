@@ -384,6 +384,33 @@ def test_no_product_kernel_carries_a_hazardous_packed_fp32_form():
     assert any(v[1] > 0 for k, v in drows.items() if "mel_pk_build" in dnames[k])
 
 
+def test_product_library_has_no_profiling_instance_and_no_tuning_only_option():
+    """The in-kernel phase profilers (PROF = true instances) exist only in the tuning library of tools/build_ablate.py (-DEFFCONF_PHASE_PROF), and
+    the options that only selected tuning variants (among them chain_count_stores: the unsafe counted ring waits of rounds 3 - 6) are unknown
+    to the product library."""
+    from efficientconformer_amd import _isa_guard
+    _lib.load()
+    names = _isa_guard.demangle(list(_isa_guard.scan(_lib.LIB_PATH))).values()
+    fam = re.compile(r"\b(chain_kernel|chain2_kernel|chain3_kernel|relpos_attention_kernel|ffn_fused_kernel)<")
+    kernels = [n for n in names if fam.search(n)]
+    assert {fam.search(n).group(1) for n in kernels} == {"chain_kernel", "chain2_kernel", "chain3_kernel", "relpos_attention_kernel", "ffn_fused_kernel"}
+    assert not [n for n in kernels if re.search(r",\s*true>", n)]
+    lib = _lib.load()
+    cfg, _keep = ModelCTC.from_config(named_config("Tiny")).encoder._make_config()
+    h = lib.effconf_encoder_create(ctypes.byref(cfg))
+    assert h, lib.effconf_last_error()
+    try:
+        for name in ("chain_count_stores", "chain_variant", "chain_pair_min_d", "chain_pair_min_m", "chain_nt", "chain_w2cm", "rs_variant",
+                     "ffn_variant", "attn_waves"):
+            assert lib.effconf_encoder_set_option(h, name.encode(), 0) != 0, name
+            assert b"unknown option" in lib.effconf_last_error(), name
+        for value in (1, 2, 3, 4, 6):
+            assert lib.effconf_encoder_set_option(h, b"chain_pair", value) != 0, value
+        assert lib.effconf_encoder_set_option(h, b"chain_pair", 0) == 0 and lib.effconf_encoder_set_option(h, b"chain_pair", 5) == 0
+    finally:
+        lib.effconf_encoder_destroy(h)
+
+
 SHIPPED = ["ConformerCTCSmall", "ConformerCTCMedium", "ConformerCTCLarge", "ConformerTransducerSmall", "ConformerTransducerMedium",
            "ConformerTransducerLarge", "EfficientConformerCTCSmall", "EfficientConformerCTCMedium", "EfficientConformerCTCLarge",
            "EfficientConformerTransducerSmall", "EfficientConformerTransducerMedium", "EfficientConformerTransducerLarge"]

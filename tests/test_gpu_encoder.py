@@ -561,8 +561,8 @@ def test_row_ranges_on_streams_stay_bit_identical_over_600_forwards():
     forwards with 2 / 3 row ranges in flight differed from the one-stream result in ONE utterance - the last of a row range - by a bf16-rounding-size perturbation) and traced
     (profiles/r6_105 .. r6_108) to the fused chains' weight ring: its counted `s_waitcnt vmcnt(N)` also allowed the global stores issued since the last barrier to stay
     outstanding, on the premise that loads and stores retire in issue order - a store can retire before an older LDS-DMA, the barrier then released readers of a ring slot
-    whose last pieces had not landed (they read the slot's previous weights).  Fixed by not counting the stores (chain.hip advance(); option chain_count_stores = 1 keeps the
-    old waits for measurement: 7 mismatches in 3000 forwards against 0 in 15000).  Here: 600 forwards, alternating 2 and 3 ranges, all bit-identical to one stream."""
+    whose last pieces had not landed (they read the slot's previous weights).  Fixed by not counting the stores (chain.hip advance(); the old waits, measured before they were
+    removed: 7 mismatches in 3000 forwards against 0 in 15000).  Here: 600 forwards, alternating 2 and 3 ranges, all bit-identical to one stream."""
     m, _ = _model("EfficientConformerCTCSmall", 3)
     B = 65
     lens = synth.libri_lengths(B, seed=100 + B)[:B]

@@ -389,8 +389,8 @@ def test_chunked_bf16_front_end_vs_oracle_linear_stage_and_ragged_equals_alone(n
 @pytest.mark.parametrize("precision,iters", [("bf16", 300), ("split", 60)])
 def test_ragged_forward_on_three_streams_reproduces_itself_bit_for_bit(precision, iters):
     """EfficientConformerCTCSmall, B = 256 LibriSpeech-shaped utterances sorted by length, ragged, 3 row ranges on 3 streams (bench.py's configuration): every forward
-    equals the first one bit for bit.  With the weight-ring waits of rounds 3 - 6 (option chain_count_stores = 1: global stores counted into the allowed vmcnt although a
-    store can retire before an older LDS-DMA) 23 % of these forwards carried one or two utterances - the last of a row range - perturbed by ~1e-2
+    equals the first one bit for bit.  With the weight-ring waits of rounds 3 - 6 (global stores counted into the allowed vmcnt although a
+    store can retire before an older LDS-DMA; removed) 23 % of these forwards carried one or two utterances - the last of a row range - perturbed by ~1e-2
     (profiles/r6_108_ring_wait_fix.txt); no parity test could see that, a repetition test does."""
     m, _ = _model("EfficientConformerCTCSmall", 5)
     enc = m.encoder

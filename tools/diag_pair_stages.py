@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Round 5 diagnostics: per-stage trace of the forward with the column-pair chains (chain2.hip) against chain.hip's - first differing stage, and where
-in the row / column space the differences sit.  usage: diag_pair_stages.py <config> <mel frames> <chain_pair> <chain_full_max>"""
+"""Round 5 diagnostics: per-stage trace of the forward with the padded-width-256 chains (chain_pair = 5: chain2.hip / chain3.hip) against chain.hip's
+(chain_pair = 0) - first differing stage, and where in the row / column space the differences sit.
+usage: diag_pair_stages.py <config> <mel frames> <chain_pair> <chain_full_max>"""
 import os
 import sys
 
@@ -14,7 +15,7 @@ from efficientconformer_amd import ModelCTC, named_config, synth  # noqa: E402
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "EfficientConformerCTCSmall"
     tm = int(sys.argv[2]) if len(sys.argv) > 2 else 700
-    pair = int(sys.argv[3]) if len(sys.argv) > 3 else 1
+    pair = int(sys.argv[3]) if len(sys.argv) > 3 else 5
     full = int(sys.argv[4]) if len(sys.argv) > 4 else 192
     extra = [a.split("=") for a in sys.argv[5:]]
     cfg = named_config(name)
