@@ -19,8 +19,7 @@
 // All arithmetic is fp32 (the decisions feed back into the recurrence: one flipped argmax changes every later token,
 // so the head is kept at the reference's precision; softmax().log().argmax() of transducer.py:164 is argmax(logits)).
 // Bound: L2 -> CU bandwidth on the weights (4H*H*4 + J*H*4 bytes per token, V*J*4 per joint pass).
-#include "kernels.h"
-#include "../../include/effconf.h"
+#include "rnnt_common.h"
 
 #include <cmath>
 #include <cstdio>
@@ -32,6 +31,8 @@
 #include <type_traits>
 
 int ec_fail(const char* msg);
+
+using namespace ecrnnt;
 
 namespace {
 
@@ -86,12 +87,16 @@ __global__ __launch_bounds__(256) void sgemm_nt_kernel(const float* __restrict__
     }
 }
 
-int launch_sgemm_nt(const float* A, int lda, const float* Bw, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, hipStream_t s) {
+}  // namespace
+
+int ecrnnt::launch_sgemm_nt(const float* A, int lda, const float* Bw, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, hipStream_t s) {
     if (M <= 0 || N <= 0) return 0;
     if (K % 4 || K < 4) return -2;
     hipLaunchKernelGGL(sgemm_nt_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, s, A, lda, Bw, ldb, bias, C, ldc, M, N, K);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------------
 // mat-vec against a k-major float4 weight image: y[n] = sum_k W[n][k] x[k], W4[(k/4)*N + n] = W[n][k..k+3].
@@ -122,18 +127,6 @@ __device__ __forceinline__ void matvec(const float4* __restrict__ W4, int N, int
     }
 }
 
-struct RnntDev {
-    const float* gin;        // [V][4H]   W_ih emb[y] + b_ih + b_hh
-    const float4* whh4;      // [H/4][4H]
-    const float4* wd4;       // [H/4][J]
-    const float* bd;         // [J]
-    const float4* wj4;       // [J/4][V]
-    const float4 *whh16, *wd16, *wj16;   // the same three in the MFMA order: [K/16][4][N] (kperm16), null if K % 16
-    const float* bj;         // [V]
-    int H, J, V, max_consec;
-};
-
-__device__ __forceinline__ float sigmoid_precise(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // One workgroup = one utterance.  fe: [B][T][J] = linear_encoder(f) incl. bias.
 __global__ __launch_bounds__(NT) void rnnt_greedy_kernel(RnntDev w, const float* __restrict__ fe, const int64_t* __restrict__ lens,
@@ -309,59 +302,6 @@ __device__ __forceinline__ bool cluster_sync(unsigned* cnt, unsigned& epoch, int
     return __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
 }
 
-// ---- the three mat-vec phases on the fp32 matrix pipe -----------------------------------------------------------------------------------
-// A round multiplies a slice of a weight matrix with the CU = 8 (joint: CU * CKF = 16) state vectors of the cluster's utterances.  As VALU
-// code that is 32 FMAs + 8 broadcast LDS reads per weight float4 and thread: the phases were issue-bound (s_memtime: 71k + 37k + 77k of a
-// round's 206k cycles; the three cluster barriers 1.5k each).  v_mfma_f32_16x16x4_f32 takes 16 weight rows x 4 k (A) against 4 k x 16 state
-// vectors (B): one weight float4 and one state float4 per lane feed four MFMAs (4096 MACs).  The k order of every dot product stays
-// ASCENDING: lane group g = lane / 16 is k-slot g of an MFMA, so the float4 a lane loads for 16-block q must hold k = 16q + g, 16q + 4 + g,
-// 16q + 8 + g, 16q + 12 + g (MFMA c of the block then covers k = 16q + 4c .. 16q + 4c + 3) - the weights get a second image in that order
-// (kperm16) and the state vectors sit in LDS with k permuted the same way (kperm).
-__host__ __device__ __forceinline__ int kperm(int k) { return (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); }
-constexpr int CMB = 4;          // 16-blocks of weight loads in flight per tile and lane (8 when a wave owns at most two tiles and K allows)
-
-template <int NTL, int CMB>
-__device__ __forceinline__ void mfma_rows16_t(const float4* __restrict__ W16, int N, int K16, const int (&nrow)[NTL], const float* xs_lane, f32x4 (&acc)[NTL]) {
-    const int g = (threadIdx.x & 63) >> 4;
-    const size_t bs = (size_t)4 * N;                    // float4s per 16-block: [g][n]
-    const float4* wp[NTL];
-    float4 wn[NTL][CMB];
-#pragma unroll
-    for (int i = 0; i < NTL; ++i) {
-        wp[i] = W16 + (size_t)g * N + nrow[i];
-#pragma unroll
-        for (int b = 0; b < CMB; ++b) wn[i][b] = wp[i][b * bs];
-    }
-    for (int q0 = 0; q0 < K16; q0 += CMB) {
-        float4 wv[NTL][CMB];
-#pragma unroll
-        for (int i = 0; i < NTL; ++i)
-#pragma unroll
-            for (int b = 0; b < CMB; ++b) wv[i][b] = wn[i][b];
-        const int qn = q0 + CMB < K16 ? q0 + CMB : q0;                      // last pass: harmless re-load
-#pragma unroll
-        for (int i = 0; i < NTL; ++i)
-#pragma unroll
-            for (int b = 0; b < CMB; ++b) wn[i][b] = wp[i][(size_t)(qn + b) * bs];
-#pragma unroll
-        for (int b = 0; b < CMB; ++b) {
-            const float4 x = *reinterpret_cast<const float4*>(xs_lane + 16 * (q0 + b));
-#pragma unroll
-            for (int i = 0; i < NTL; ++i) {
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i][b].x, x.x, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i][b].y, x.y, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i][b].z, x.z, acc[i], 0, 0, 0);
-                acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i][b].w, x.w, acc[i], 0, 0, 0);
-            }
-        }
-    }
-}
-
-template <int NTL>
-__device__ __forceinline__ void mfma_rows16(const float4* __restrict__ W16, int N, int K16, const int (&nrow)[NTL], const float* xs_lane, f32x4 (&acc)[NTL]) {
-    if (NTL <= 2 && (K16 & 7) == 0) mfma_rows16_t<NTL, 8>(W16, N, K16, nrow, xs_lane, acc);
-    else mfma_rows16_t<NTL, 4>(W16, N, K16, nrow, xs_lane, acc);
-}
 
 // exchange buffers -> registers, three 16-byte loads per lane in flight (sc1: served at the coherent level, as xload; plain loads instead of
 // atomics so that they pipeline - the relaxed atomic loads were issued one at a time, 13k cycles per round for two 20 KB reloads).  The
@@ -625,22 +565,10 @@ struct ClusterShape {
 using ShapeA = ClusterShape<8, 8, 2>;
 using ShapeB = ClusterShape<16, 16, 1>;
 
-struct HostT { std::vector<int64_t> shape; std::vector<float> data; };
+using HostT = EcRnntHostT;
 
 }  // namespace
 
-struct EcRnnt {
-    EcRnntConfig cfg;
-    std::map<std::string, HostT> host;
-    std::vector<void*> allocs;
-    RnntDev dev{};
-    float* we = nullptr;     // linear_encoder.weight [J][De]
-    float* be = nullptr;
-    bool finalized = false;
-    int cluster_by_slice = 1;   // cluster decode: workgroup -> XCD mapping (see rnnt_cluster_kernel)
-    int cluster_mode = -1;   // -1 auto (cluster decode for batches >= 2 x the cluster's utterances), 0 per-utterance kernel, 1 force cluster
-    int cluster_shape = 0;   // 0 <8, 8, 2> (default), 1 <16, 16, 1> where supported (measured: no faster - see the shapes' comment - and a blank costs a round of its own)
-};
 
 namespace {
 
@@ -741,7 +669,7 @@ int effconf_rnnt_finalize(EcRnnt* r) {
     r->dev.wj4 = (const float4*)upload(r, wj4.data(), wj4.size() * 4);
     r->dev.bj = (const float*)upload(r, bj->data.data(), bj->data.size() * 4);
     r->dev.whh16 = r->dev.wd16 = r->dev.wj16 = nullptr;
-    if (ShapeA::supported(r->cfg) || ShapeB::supported(r->cfg)) {
+    if (ShapeA::supported(r->cfg) || ShapeB::supported(r->cfg) || beam_dims_supported(r->cfg)) {
         const std::vector<float> a16 = kperm16(whh->data, 4 * H, H), b16 = kperm16(wd->data, J, H), c16 = kperm16(wj->data, V, J);
         r->dev.whh16 = (const float4*)upload(r, a16.data(), a16.size() * 4);
         r->dev.wd16 = (const float4*)upload(r, b16.data(), b16.size() * 4);
@@ -772,6 +700,11 @@ int effconf_rnnt_set_option(EcRnnt* r, const char* name, int32_t value) {
     if (!strcmp(name, "cluster_decode")) { r->cluster_mode = value; return 0; }
     if (!strcmp(name, "cluster_by_slice")) { r->cluster_by_slice = value != 0; return 0; }
     if (!strcmp(name, "cluster_shape")) { r->cluster_shape = value; return 0; }
+    if (!strcmp(name, "beam_eval_batch")) {
+        if (value < 1 || value > 16) return ec_fail("beam_eval_batch must be 1 .. 16");
+        r->beam_eval_batch = value;
+        return 0;
+    }
     return ec_fail("unknown option");
 }
 

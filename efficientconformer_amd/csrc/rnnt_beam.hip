@@ -1,0 +1,417 @@
+// RNN-T beam search (gfx950): Transducer.beam_search_decoding of the reference (models/transducer.py:188-327) without the
+// neural-LM and n-gram terms (the state of a plain checkpoint load: no LM checkpoint, no n-gram file).
+//
+// Per utterance the reference keeps two hypothesis lists.  For each encoder frame t: A = B, B = [], then until B holds `beam`
+// hypotheses: pop the hypothesis of A with the largest score / len(prediction) (first maximum in list order), run the decoder on
+// (prediction[-1], state), the joint on (f[t], g), logP = (logits / tmp).softmax().log(), and for each of the top `beam` entries
+// append a child: blank -> B (same prediction, the parent's OLD state), any other label -> A (label appended, state = the new one).
+// The answer is the best hypothesis of B after the last frame (transducer.py:319-323).
+//
+// Here ONE persistent workgroup runs one utterance; the reference's pop order is replayed exactly on rows computed ahead of it:
+//   * a hypothesis's logP row is a pure function of (last token, state, t), so up to `beam_eval_batch` not-yet-evaluated hypotheses of
+//     A - the best first, then in pop order (score / len descending, list order on ties) - are evaluated together as the 16 columns of
+//     fp32 MFMA tiles (mfma_rows16, the weight images of effconf_rnnt_finalize): the weights stream once per batch instead of once per
+//     hypothesis.  Every column's arithmetic is independent of the others (k ascending, unused columns zero), so a row does not depend
+//     on what shared its batch: batch 1 and batch 16 give bit-identical results;
+//   * a blank child keeps (last token, state) of its parent, so its decoder output at the next frame IS the parent's: hypotheses carry
+//     their decoder node (h', c', linear_decoder(h')) and only the children that appended a label need an LSTM step;
+//   * predictions are a parent-linked trail of tokens, materialised when a hypothesis is popped (not for every child appended to A).
+// Scores are fp32 sums and score / len an IEEE fp32 division, as in the reference (logp_score is a 0-dim fp32 tensor).
+//
+// Bounds: at most max_expansions pops per frame (status 1 when B is still short: the reference would loop on), at most max_tokens
+// tokens in the answer (status 2); a capped utterance returns no tokens.  All storage is in the caller's workspace, sized by
+// effconf_rnnt_beam_workspace_bytes from (batch, T, beam, max_expansions).
+#include "rnnt_common.h"
+
+#include <cmath>
+#include <cstring>
+
+int ec_fail(const char* msg);
+
+using namespace ecrnnt;
+
+namespace {
+
+constexpr int BT = 512;          // threads per utterance
+constexpr int BNW = BT / 64;     // waves
+constexpr int MAXC = 16;         // columns of an MFMA tile = largest beam and evaluation batch
+constexpr int SLACK = 64;        // evaluated, not yet popped hypotheses per frame (room for evaluating ahead of the pops)
+
+enum : int { H_READY = 1, H_POPPED = 2, H_EVAL = 4 };   // flags; bits 4.. hold the evaluation slot
+
+// One hypothesis.  READY: `node` is its decoder output (a carried blank child); otherwise (pending) `node` is its state (-1: zeros) and
+// y the token the decoder runs on.  After evaluation `node` is the decoder output in both cases.  `lab` >= 0: a label appended to the
+// trail `trail` when the hypothesis is popped (len already counts it).
+struct Hyp { float key; float score; int len; int trail; int lab; int y; int node; int flags; };
+static_assert(sizeof(Hyp) == 32, "Hyp");
+
+struct BeamLayout {
+    int beam, maxexp, ecap, acap, tcap, ns, nnodes;
+    size_t stats, fe, utt, per_utt;                                      // byte offsets / stride
+    size_t nodes, topv, topl, a, b, trail, total;
+};
+
+size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+BeamLayout beam_layout(const EcRnntConfig& c, int batch, int t_out, int beam, int maxexp) {
+    BeamLayout L{};
+    L.beam = beam; L.maxexp = maxexp;
+    L.ecap = maxexp + SLACK;                                             // evaluations per frame: one per pop + the slack
+    L.acap = beam + maxexp * beam;                                       // A: the carried beam + beam children per pop
+    L.tcap = 1 + t_out * maxexp;                                         // trail: the start token + one entry per pop
+    L.ns = 2 * c.dim_decoder + c.dim_joint;                              // node: h', c', linear_decoder(h')
+    L.nnodes = 2 * beam + L.ecap;                                        // two carry sets (previous / next frame) + the frame's arena
+    L.stats = 0;
+    L.fe = al256((size_t)batch * 16);
+    L.utt = L.fe + al256((size_t)batch * t_out * c.dim_joint * 4);
+    size_t o = 0;
+    L.nodes = o; o = al256(o + (size_t)L.nnodes * L.ns * 4);
+    L.topv = o;  o = al256(o + (size_t)L.ecap * beam * 4);
+    L.topl = o;  o = al256(o + (size_t)L.ecap * beam * 4);
+    L.a = o;     o = al256(o + (size_t)L.acap * sizeof(Hyp));
+    L.b = o;     o = al256(o + (size_t)beam * sizeof(Hyp));
+    L.trail = o; o = al256(o + (size_t)L.tcap * 8);
+    L.per_utt = o;
+    L.total = L.utt + (size_t)batch * o + 256;                           // + 256: the caller's pointer is aligned up
+    return L;
+}
+
+size_t beam_lds_bytes(const EcRnntConfig& c) {
+    const int H = c.dim_decoder, J = c.dim_joint, P = H > J ? H : J;
+    return (size_t)MAXC * (P + H + c.vocab_size) * 4;
+}
+
+struct BeamArgs {
+    RnntDev w;
+    const float* fe; const int64_t* lens; int T, B;
+    int nb, max_tok; float tmp;
+    char* utt; int* stats; BeamLayout L;
+    int* tokens; int* counts; float* score; int* status;
+};
+
+// (v, i) before (bv, bi) in pop order: larger value, then smaller index; i < 0 = none
+__device__ __forceinline__ bool before(float v, int i, float bv, int bi) { return i >= 0 && (bi < 0 || v > bv || (v == bv && i < bi)); }
+
+// block-wide first maximum; every thread returns the same (v, i).  Two barriers: callable back to back.
+__device__ __forceinline__ void block_best(float& v, int& i, float* s_rv, int* s_ri) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(v, o); const int oi = __shfl_xor(i, o);
+        if (before(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+    if ((threadIdx.x & 63) == 0) { s_rv[threadIdx.x >> 6] = v; s_ri[threadIdx.x >> 6] = i; }
+    __syncthreads();
+    v = s_rv[0]; i = s_ri[0];
+#pragma unroll
+    for (int q = 1; q < BNW; ++q)
+        if (before(s_rv[q], s_ri[q], v, i)) { v = s_rv[q]; i = s_ri[q]; }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(BT) void rnnt_beam_kernel(const BeamArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const RnntDev& w = a.w;
+    const BeamLayout& L = a.L;
+    const int H = w.H, J = w.J, V = w.V, P = H > J ? H : J, beam = L.beam, ns = L.ns;
+    float* sx = lds;                       // [16][P] LSTM input h, then joint input z (k-permuted, see mfma_rows16)
+    float* sy = sx + MAXC * P;             // [16][H] h' (k-permuted)
+    float* sl = sy + MAXC * H;             // [16][V] logits / tmp
+    __shared__ float s_rv[BNW];
+    __shared__ int s_ri[BNW];
+    __shared__ int s_col[MAXC], s_cy[MAXC], s_cst[MAXC], s_cout[MAXC], s_cpend[MAXC];
+    __shared__ int s_na, s_nb, s_pops, s_used, s_ntrail, s_status;
+    __shared__ float s_pscore;
+    __shared__ int s_plen, s_ptrail, s_pnode, s_pslot;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x;
+    char* base = a.utt + (size_t)b * L.per_utt;
+    float* nodes = reinterpret_cast<float*>(base + L.nodes);
+    float* topv = reinterpret_cast<float*>(base + L.topv);
+    int* topl = reinterpret_cast<int*>(base + L.topl);
+    Hyp* A = reinterpret_cast<Hyp*>(base + L.a);
+    Hyp* Bh = reinterpret_cast<Hyp*>(base + L.b);
+    int2* trail = reinterpret_cast<int2*>(base + L.trail);
+    int Tb = (int)a.lens[b];
+    Tb = Tb < 0 ? 0 : (Tb > a.T ? a.T : Tb);
+    const float* feb = a.fe + (size_t)b * a.T * J;
+    int n_batch = 0, n_eval = 0, n_pop = 0;                              // thread 0's counters (workspace statistics)
+
+    if (tid == 0) {
+        trail[0] = make_int2(0, -1);                                     // prediction [0] (transducer.py:219)
+        A[0] = Hyp{0.f, 0.f, 1, 0, -1, 0, -1, 0};                         // score 0, zero state, pending on token 0
+        s_na = 1; s_nb = 0; s_pops = 0; s_used = 0; s_ntrail = 1; s_status = 0;
+    }
+    __syncthreads();
+
+    for (int t = 0; t < Tb; ++t) {
+        if (t > 0) {
+            // ---- A = B: carry the beam's decoder nodes into this frame's carry set (the other set holds the previous frame's sources)
+            const int par = t & 1;
+            for (int i = tid; i < beam * ns; i += BT) {
+                const int h = i / ns, e = i - h * ns;
+                nodes[(size_t)(par * beam + h) * ns + e] = nodes[(size_t)Bh[h].node * ns + e];
+            }
+            __syncthreads();
+            if (tid < beam) {
+                const Hyp h = Bh[tid];
+                A[tid] = Hyp{h.key, h.score, h.len, h.trail, -1, 0, par * beam + tid, H_READY};
+            }
+            if (tid == 0) { s_na = beam; s_nb = 0; s_pops = 0; s_used = 0; }
+            __syncthreads();
+        }
+        while (true) {
+            const int na = s_na, nbh = s_nb, pops = s_pops, used = s_used;
+            if (nbh >= beam) break;
+            if (pops >= L.maxexp) { if (tid == 0) s_status = 1; break; }
+            // ---- the hypothesis the reference pops next: max score / len over A, first in list order (transducer.py:240)
+            float bv = -INFINITY; int bi = -1;
+            for (int i = tid; i < na; i += BT) {
+                const Hyp& h = A[i];
+                if (!(h.flags & H_POPPED) && before(h.key, i, bv, bi)) { bv = h.key; bi = i; }
+            }
+            block_best(bv, bi, s_rv, s_ri);
+            const int best = bi;
+            if (!(A[best].flags & H_EVAL)) {
+                // ---- evaluation batch: the best, then the next unevaluated hypotheses in pop order, as far as the frame's slots allow
+                int lim = SLACK + 1 + pops - used;
+                lim = lim < a.nb ? lim : a.nb;
+                int nc = 1;
+                if (tid == 0) s_col[0] = best;
+                float pv = bv; int pi = best;
+                while (nc < lim) {
+                    float cv = -INFINITY; int ci = -1;
+                    for (int i = tid; i < na; i += BT) {
+                        const Hyp& h = A[i];
+                        if (!(h.flags & (H_POPPED | H_EVAL)) && (h.key < pv || (h.key == pv && i > pi)) && before(h.key, i, cv, ci)) { cv = h.key; ci = i; }
+                    }
+                    block_best(cv, ci, s_rv, s_ri);
+                    if (ci < 0) break;
+                    if (tid == 0) s_col[nc] = ci;
+                    ++nc;
+                    pv = cv; pi = ci;
+                }
+                __syncthreads();                                         // s_col
+                if (tid < MAXC) {
+                    int pend = 0, y = 0, st = -1, out = 0;
+                    if (tid < nc) {
+                        const Hyp h = A[s_col[tid]];
+                        pend = !(h.flags & H_READY);
+                        y = h.y;
+                        st = pend ? h.node : -1;
+                        out = pend ? 2 * beam + used + tid : h.node;      // a pending hypothesis gets the frame slot's node
+                    }
+                    s_cpend[tid] = pend; s_cy[tid] = y; s_cst[tid] = st; s_cout[tid] = out;
+                }
+                __syncthreads();
+                bool anypend = false;
+#pragma unroll
+                for (int c = 0; c < MAXC; ++c) anypend |= s_cpend[c] != 0;
+                if (anypend) {
+                    // ---- LSTM step of the pending columns: gates = Gin[y] + W_hh h (torch gate order i, f, g, o), 16 units x 4 gates per tile set
+                    for (int i = tid; i < MAXC * H; i += BT) {
+                        const int c = i / H, k = i - c * H;
+                        sx[c * P + kperm(k)] = s_cpend[c] && s_cst[c] >= 0 ? nodes[(size_t)s_cst[c] * ns + k] : 0.f;
+                    }
+                    __syncthreads();
+                    const bool pend = s_cpend[j] != 0;
+                    for (int ub = wave; ub < H / 16; ub += BNW) {
+                        int nrow[4];
+                        f32x4 acc[4];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) { nrow[q] = q * H + 16 * ub + j; acc[q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+                        mfma_rows16_any<4>(w.whh16, 4 * H, H / 16, nrow, sx + j * P + 4 * g, acc);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {                    // row 4 g + e of the tiles = hidden unit, column j = hypothesis
+                            const int unit = 16 * ub + 4 * g + e;
+                            float hv = 0.f;
+                            if (pend) {
+                                const float* gin = w.gin + (size_t)s_cy[j] * 4 * H;
+                                const float ig = sigmoid_precise(acc[0][e] + gin[unit]), fg = sigmoid_precise(acc[1][e] + gin[H + unit]);
+                                const float gg = tanhf(acc[2][e] + gin[2 * H + unit]), og = sigmoid_precise(acc[3][e] + gin[3 * H + unit]);
+                                const float cold = s_cst[j] >= 0 ? nodes[(size_t)s_cst[j] * ns + H + unit] : 0.f;
+                                const float c = fg * cold + ig * gg;
+                                hv = og * tanhf(c);
+                                float* on = nodes + (size_t)s_cout[j] * ns;
+                                on[unit] = hv;
+                                on[H + unit] = c;
+                            }
+                            sy[j * H + kperm(unit)] = hv;
+                        }
+                    }
+                    __syncthreads();
+                    // ---- linear_decoder(h') of the pending columns
+                    for (int tt = wave; tt < J / 16; tt += BNW) {
+                        int nrow[1] = {16 * tt + j};
+                        f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+                        mfma_rows16_any<1>(w.wd16, J, H / 16, nrow, sy + j * H + 4 * g, acc);
+                        if (pend) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const int n = 16 * tt + 4 * g + e;
+                                nodes[(size_t)s_cout[j] * ns + 2 * H + n] = acc[0][e] + w.bd[n];
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+                // ---- joint input z = tanh(linear_encoder(f[t]) + linear_decoder(g)) of every column (unused columns zero)
+                for (int i = tid; i < MAXC * J; i += BT) {
+                    const int c = i / J, k = i - c * J;
+                    sx[c * P + kperm(k)] = c < nc ? tanhf(feb[(size_t)t * J + k] + nodes[(size_t)s_cout[c] * ns + 2 * H + k]) : 0.f;
+                }
+                __syncthreads();
+                // ---- logits = linear_joint(z), divided by the temperature (transducer.py:255)
+                for (int tt = wave; tt < (V + 15) / 16; tt += BNW) {
+                    const int lr = 16 * tt + j;
+                    int nrow[1] = {lr < V ? lr : V - 1};
+                    f32x4 acc[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+                    mfma_rows16_any<1>(w.wj16, V, J / 16, nrow, sx + j * P + 4 * g, acc);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int n = 16 * tt + 4 * g + e;
+                        if (n < V) sl[j * V + n] = (acc[0][e] + w.bj[n]) / a.tmp;
+                    }
+                }
+                __syncthreads();
+                // ---- per column: softmax().log() (transducer.py:258) and the top `beam` entries, one wave per column
+                for (int c = wave; c < nc; c += BNW) {
+                    const float* lc = sl + c * V;
+                    float m = -INFINITY;
+                    for (int v = lane; v < V; v += 64) m = fmaxf(m, lc[v]);
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+                    float s = 0.f;
+                    for (int v = lane; v < V; v += 64) s += expf(lc[v] - m);
+#pragma unroll
+                    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+                    const int slot = used + c;
+                    float pv2 = INFINITY; int pi2 = -1;
+                    for (int r = 0; r < beam; ++r) {                     // descending, lower label first on equal values
+                        float cv = -INFINITY; int ci = -1;
+                        for (int v = lane; v < V; v += 64) {
+                            const float x = lc[v];
+                            if ((x < pv2 || (x == pv2 && v > pi2)) && before(x, v, cv, ci)) { cv = x; ci = v; }
+                        }
+#pragma unroll
+                        for (int o = 32; o >= 1; o >>= 1) {
+                            const float ov = __shfl_xor(cv, o); const int oi = __shfl_xor(ci, o);
+                            if (before(ov, oi, cv, ci)) { cv = ov; ci = oi; }
+                        }
+                        if (lane == 0) { topv[(size_t)slot * beam + r] = logf(expf(cv - m) / s); topl[(size_t)slot * beam + r] = ci; }
+                        pv2 = cv; pi2 = ci;
+                    }
+                }
+                if (tid < nc) {
+                    Hyp* h = A + s_col[tid];
+                    h->node = s_cout[tid];
+                    h->flags |= H_EVAL | ((used + tid) << 4);
+                }
+                if (tid == 0) { s_used = used + nc; ++n_batch; n_eval += nc; }
+                __syncthreads();
+            }
+            // ---- pop: children in top-k order, blank -> B, labels -> A (transducer.py:280-317)
+            if (tid == 0) {
+                Hyp h = A[best];
+                int tr = h.trail;
+                if (h.lab >= 0) { tr = s_ntrail++; trail[tr] = make_int2(h.lab, h.trail); }
+                A[best].flags = h.flags | H_POPPED;
+                s_pscore = h.score; s_plen = h.len; s_ptrail = tr; s_pnode = h.node; s_pslot = h.flags >> 4;
+                ++n_pop;
+            }
+            __syncthreads();
+            if (tid < beam) {
+                const int slot = s_pslot;
+                const int lab = topl[(size_t)slot * beam + tid];
+                const float sc = s_pscore + topv[(size_t)slot * beam + tid];
+                if (lab == 0) {
+                    Bh[nbh] = Hyp{sc / (float)s_plen, sc, s_plen, s_ptrail, -1, 0, s_pnode, 0};
+                } else {
+                    int before_me = 0;
+                    for (int r = 0; r < tid; ++r) before_me += topl[(size_t)slot * beam + r] != 0;
+                    A[na + before_me] = Hyp{sc / (float)(s_plen + 1), sc, s_plen + 1, s_ptrail, lab, lab, s_pnode, 0};
+                }
+            }
+            if (tid == 0) {
+                int blank = 0;
+                for (int r = 0; r < beam; ++r) blank += topl[(size_t)s_pslot * beam + r] == 0;
+                s_na = na + beam - blank; s_nb = nbh + blank; s_pops = pops + 1;
+            }
+            __syncthreads();
+        }
+        __syncthreads();                                                 // s_status
+        if (s_status) break;
+    }
+    __syncthreads();
+    // ---- answer: max over B by score / len, first in list order (transducer.py:320); no frames: the start hypothesis
+    int st = s_status;
+    float sc = 0.f; int len = 1, tr = 0;
+    if (!st && Tb > 0) {
+        float bv = -INFINITY; int bi = -1;
+        for (int i = tid; i < beam; i += BT)
+            if (before(Bh[i].key, i, bv, bi)) { bv = Bh[i].key; bi = i; }
+        block_best(bv, bi, s_rv, s_ri);
+        sc = Bh[bi].score; len = Bh[bi].len; tr = Bh[bi].trail;
+    }
+    int ntok = len - 1;
+    if (!st && ntok > a.max_tok) st = 2;
+    if (st) { ntok = 0; sc = 0.f; }
+    int* out = a.tokens + (size_t)b * a.max_tok;
+    if (tid == 0) {
+        for (int i = ntok - 1; i >= 0; --i) { const int2 e = trail[tr]; out[i] = e.x; tr = e.y; }
+        a.counts[b] = ntok; a.score[b] = sc; a.status[b] = st;
+        a.stats[4 * b + 0] = n_batch; a.stats[4 * b + 1] = n_eval; a.stats[4 * b + 2] = n_pop; a.stats[4 * b + 3] = Tb;
+    }
+    for (int i = ntok + tid; i < a.max_tok; i += BT) out[i] = 0;
+}
+
+const char* beam_check(const EcRnnt* r, int32_t batch, int32_t t_out, int32_t beam, int32_t max_expansions, int32_t max_tokens) {
+    if (!r) return "null handle";
+    if (!beam_dims_supported(r->cfg)) return "beam search: decoder and joint widths must be multiples of 16";
+    if (beam_lds_bytes(r->cfg) > 160 * 1024 - 1024) return "beam search: decoder / joint / vocabulary widths exceed the LDS of one workgroup";
+    if (beam < 1 || beam > MAXC || beam > r->cfg.vocab_size) return "beam search: beam must be in 1 .. min(16, vocab_size)";
+    if (max_expansions < 1 || max_expansions > (1 << 16)) return "beam search: max_expansions must be in 1 .. 65536";
+    if (max_tokens < 1) return "beam search: max_tokens must be >= 1";
+    if (batch < 0 || t_out < 1) return "beam search: bad shape";
+    if ((int64_t)t_out * max_expansions >= (1ll << 30)) return "beam search: t_out * max_expansions too large";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t effconf_rnnt_beam_workspace_bytes(const EcRnnt* r, int32_t batch, int32_t t_out, int32_t beam, int32_t max_expansions, int32_t max_tokens) {
+    if (const char* e = beam_check(r, batch, t_out, beam, max_expansions, max_tokens)) { ec_fail(e); return 0; }
+    return beam_layout(r->cfg, batch, t_out, beam, max_expansions).total;
+}
+
+int effconf_rnnt_beam(EcRnnt* r, const float* enc_out, const int64_t* out_len, int32_t batch, int32_t t_out, int32_t beam, float temperature,
+                      int32_t max_expansions, int32_t* tokens, int32_t* token_len, float* score, int32_t* status, int32_t max_tokens,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (!r || !r->finalized) return ec_fail("rnnt handle not finalized");
+    if (const char* e = beam_check(r, batch, t_out, beam, max_expansions, max_tokens)) return ec_fail(e);
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return ec_fail("beam search: temperature must be > 0");
+    if (batch == 0) return 0;
+    if (!enc_out || !out_len || !tokens || !token_len || !score || !status || !workspace) return ec_fail("null argument");
+    if (!r->dev.whh16 || !r->dev.wd16 || !r->dev.wj16) return ec_fail("beam search: MFMA weight images missing (finalize)");
+    const BeamLayout L = beam_layout(r->cfg, batch, t_out, beam, max_expansions);
+    if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_rnnt_beam_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    const int J = r->cfg.dim_joint, De = r->cfg.dim_encoder;
+    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    float* fe = reinterpret_cast<float*>(ws + L.fe);
+    // linear_encoder(f) for every frame of the batch, once (joint_networks.py:82 recomputes it per decision)
+    if (launch_sgemm_nt(enc_out, De, r->we, De, r->be, fe, J, batch * t_out, J, De, s) != 0) return ec_fail("linear_encoder GEMM launch failed");
+    BeamArgs a{};
+    a.w = r->dev; a.fe = fe; a.lens = out_len; a.T = t_out; a.B = batch;
+    a.nb = r->beam_eval_batch < MAXC ? r->beam_eval_batch : MAXC; a.max_tok = max_tokens; a.tmp = temperature;
+    a.utt = ws + L.utt; a.stats = reinterpret_cast<int*>(ws + L.stats); a.L = L;
+    a.tokens = tokens; a.counts = token_len; a.score = score; a.status = status;
+    const size_t lds = beam_lds_bytes(r->cfg);
+    static LdsAttr attr;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&rnnt_beam_kernel), (int)lds, attr);
+    hipLaunchKernelGGL(rnnt_beam_kernel, dim3(batch), dim3(BT), lds, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : ec_fail("rnnt_beam launch failed");
+}
+
+}  // extern "C"

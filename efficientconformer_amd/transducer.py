@@ -4,8 +4,10 @@
 Keeps the reference's attribute names (``encoder``, ``decoder.embedding``, ``decoder.rnn``, ``joint_network.linear_*``),
 state-dict keys and method names (``gready_search_decoding``, the reference's spelling).  The per-utterance Python loop
 of the reference — one decoder call, one joint call and one ``.argmax()`` host sync per decision — runs as one
-persistent HIP kernel per batch (effconf_rnnt_greedy).  Training (``forward`` over the full (T, U) lattice, RNN-T loss),
-beam search and the LM fusion are out of scope (HISTORY.md).
+persistent HIP kernel per batch (effconf_rnnt_greedy).  ``beam_search_decoding`` (transducer.py:188-327) runs as one persistent
+HIP kernel per batch as well (effconf_rnnt_beam, one workgroup per utterance), with the reference's algorithm, tie rules and fp32
+scores; the neural-LM and n-gram (KenLM) shallow fusion terms are not implemented, which is what the reference computes without an LM
+checkpoint and n-gram file.  Training (``forward`` over the full (T, U) lattice, RNN-T loss) is out of scope (HISTORY.md).
 """
 from __future__ import annotations
 
@@ -65,12 +67,16 @@ class Transducer(nn.Module):
         self.joint_network = JointNetwork(self.encoder.plan.dim_out, decoder_params["dim_model"], decoder_params["vocab_size"],
                                           joint_params)
         self.max_consec_dec_step = decoder_params.get("max_consec_dec_step", 5)      # transducer.py:83
+        decoding_params = decoding_params or {}
+        self.beam_size = int(decoding_params.get("beam_size", 1))                    # model.py:60-61
+        self.tmp = float(decoding_params.get("tmp", 1))
         self._cfg = (self.encoder.plan.dim_out, decoder_params["dim_model"], joint_params["dim_model"],
                      decoder_params["vocab_size"], decoder_params["num_layers"])
         self.tokenizer = tokenizer
         self.name = name
         self._rnnt = None
         self._rnnt_packed = False
+        self._beam_ws = None
         self.eval()
 
     @classmethod
@@ -179,3 +185,76 @@ class Transducer(nn.Module):
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
 
     greedy_search_decoding = gready_search_decoding
+
+    # ------------------------------------------------------------------ beam search
+    def decode_encoded_beam(self, f: torch.Tensor, f_len: Optional[torch.Tensor], beam_size: Optional[int] = None,
+                            max_expansions_per_frame: Optional[int] = None, max_tokens: Optional[int] = None):
+        """Beam search of encoder outputs f (B, T, Denc) fp32 on the GPU (effconf_rnnt_beam) -> (tokens (B, max_tokens) i32,
+        token_len (B) i32, score (B) f32, status (B) i32).  status 1 / 2: the utterance hit the expansion / token cap and has no tokens.
+        Defaults: beam_size = self.beam_size, max_expansions_per_frame = 16 * beam, max_tokens = max(16, beam) * T."""
+        if not f.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        with torch.cuda.device(f.device):
+            return self._decode_encoded_beam(f, f_len, beam_size, max_expansions_per_frame, max_tokens)
+
+    def _decode_encoded_beam(self, f, f_len, beam_size, max_expansions_per_frame, max_tokens):
+        beam = int(self.beam_size if beam_size is None else beam_size)
+        vocab = self._cfg[3]
+        if not 1 <= beam <= min(16, vocab):
+            raise _lib.EffconfError("beam_size must be in 1 .. min(16, vocab_size = %d); got %d" % (vocab, beam))
+        if not self.tmp > 0:
+            raise _lib.EffconfError("decoding_params['tmp'] must be > 0; got %r" % (self.tmp,))
+        self._ensure_rnnt()
+        lib = _lib.load()
+        f = f.contiguous().float()
+        b, t, _ = f.shape
+        if f_len is None:
+            f_len = torch.full((b,), t, dtype=torch.int64, device=f.device)
+        f_len = f_len.to(device=f.device, dtype=torch.int64).contiguous()
+        max_exp = int(16 * beam if max_expansions_per_frame is None else max_expansions_per_frame)
+        max_tok = int(max(16, beam) * max(t, 1) if max_tokens is None else max_tokens)
+        nbytes = int(lib.effconf_rnnt_beam_workspace_bytes(self._rnnt, b, t, beam, max_exp, max_tok))
+        if nbytes == 0:
+            raise _lib.EffconfError("effconf_rnnt_beam_workspace_bytes rejected (batch %d, T %d, beam %d, max_expansions %d, max_tokens %d): %s"
+                                    % (b, t, beam, max_exp, max_tok, lib.effconf_last_error().decode()))
+        tokens = torch.empty(b, max_tok, dtype=torch.int32, device=f.device)
+        token_len = torch.empty(b, dtype=torch.int32, device=f.device)
+        score = torch.empty(b, dtype=torch.float32, device=f.device)
+        status = torch.empty(b, dtype=torch.int32, device=f.device)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+        _lib.check(lib.effconf_rnnt_beam(self._rnnt, f.data_ptr(), f_len.data_ptr(), b, t, beam, float(self.tmp), max_exp, tokens.data_ptr(),
+                                         token_len.data_ptr(), score.data_ptr(), status.data_ptr(), max_tok, ws.data_ptr(), ws.numel(),
+                                         torch.cuda.current_stream(f.device).cuda_stream), "rnnt_beam")
+        self._beam_ws = (ws, b)
+        return tokens, token_len, score, status
+
+    def last_beam_stats(self) -> np.ndarray:
+        """Per-utterance counters of the last decode_encoded_beam call: (B, 4) i32 = evaluation batches, evaluated hypotheses,
+        expansions, frames (the head of the workspace, include/effconf.h)."""
+        ws, b = self._beam_ws
+        off = (-ws.data_ptr()) % 256
+        return ws[off:off + 16 * b].view(torch.int32).view(b, 4).cpu().numpy()
+
+    def beam_tokens(self, x: torch.Tensor, x_len: Optional[torch.Tensor], beam_size: Optional[int] = None,
+                    from_mel: bool = False) -> List[List[int]]:
+        """Beam-search token-id sequences (without the start token), one list per utterance.  Raises EffconfError naming the
+        utterances that hit the expansion or token cap (never a silently truncated result)."""
+        f, f_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+        tokens, token_len, _, status = self.decode_encoded_beam(f, f_len, beam_size)
+        tokens, token_len, status = tokens.cpu(), token_len.cpu(), status.cpu()
+        capped = {1: [i for i in range(len(status)) if int(status[i]) == 1], 2: [i for i in range(len(status)) if int(status[i]) == 2]}
+        if capped[1] or capped[2]:
+            msg = []
+            if capped[1]:
+                msg.append("utterances %s hit the expansion cap (max_expansions_per_frame: B never filled, the reference would not "
+                           "terminate)" % capped[1])
+            if capped[2]:
+                msg.append("utterances %s hit the token cap (max_tokens)" % capped[2])
+            raise _lib.EffconfError("beam search: " + "; ".join(msg))
+        return [tokens[i, :int(token_len[i])].tolist() for i in range(tokens.shape[0])]
+
+    def beam_search_decoding(self, x, x_len, beam_size=None):
+        """Reference name and signature (transducer.py:188).  Decoded strings when a tokenizer is attached
+        (``tokenizer.decode(best_hyp["prediction"][1:])`` per utterance, transducer.py:323), otherwise the id lists."""
+        ids = self.beam_tokens(x, x_len, beam_size)
+        return [self.tokenizer.decode(i) for i in ids] if self.tokenizer is not None else ids

@@ -216,6 +216,21 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
                         int32_t* tokens, int32_t* token_len, int32_t max_tokens, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* RNN-T beam search: Transducer.beam_search_decoding (transducer.py:188-327) without the neural-LM / n-gram terms, one persistent
+ * workgroup per utterance.  1 <= beam <= min(16, vocab_size), temperature > 0 (decoding_params["tmp"]), dim_decoder and dim_joint
+ * multiples of 16.  At most max_expansions hypotheses are expanded per frame and at most max_tokens tokens returned; status dev i32
+ * (batch): 0 ok, 1 expansion cap hit (the reference would keep expanding), 2 token cap hit - a capped utterance returns no tokens.
+ * tokens dev i32 (batch, max_tokens) without the start token, zero-filled tails; token_len dev i32 (batch); score dev f32 (batch): the
+ * fp32 logp_score of the chosen hypothesis.  Option "beam_eval_batch" (effconf_rnnt_set_option, 1 .. 16, default 16): hypotheses
+ * evaluated per pass over the weights; every setting gives bit-identical results.  After the call the first 16 * batch bytes of the
+ * 256-byte aligned workspace hold per-utterance i32 counters (evaluation batches, evaluated hypotheses, expansions, frames).
+ * effconf_rnnt_beam_workspace_bytes returns 0 for arguments effconf_rnnt_beam rejects. */
+size_t effconf_rnnt_beam_workspace_bytes(const EcRnnt* r, int32_t batch, int32_t t_out, int32_t beam, int32_t max_expansions,
+                                         int32_t max_tokens);
+int effconf_rnnt_beam(EcRnnt* r, const float* enc_out, const int64_t* out_len, int32_t batch, int32_t t_out, int32_t beam,
+                      float temperature, int32_t max_expansions, int32_t* tokens, int32_t* token_len, float* score, int32_t* status,
+                      int32_t max_tokens, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Options.  "cache_pos_embeddings" = 1: the positional projections E = pos_layer(R) (reference attentions.py:588, 678)
  * are input independent; they live in the workspace and are recomputed only when that workspace last held a forward of
  * another batch size or number of frames.  The library remembers one tag per workspace pointer (the 16 most recently used),

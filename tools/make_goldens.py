@@ -9,6 +9,7 @@ leave this script: no reference source, bytecode or text is written anywhere.
 It refuses to run where /root/reference is absent (e.g. the GPU box).
 
     python tools/make_goldens.py            # regenerate every fixture
+    python tools/make_goldens.py --only-rnnt-beam   # only tests/golden/rnnt_beam_*.npz (from the stored rnnt_*.npz encoder outputs)
 """
 import os
 import sys
@@ -176,6 +177,49 @@ def rnnt_goldens(enc_mod):
         save("rnnt_" + name, **arrs)
 
 
+def reference_rnnt_beam(f, f_len, dec_params, joint_params, sd, beam_size):
+    """Execute the reference's own Transducer.beam_search_decoding (transducer.py:188-327) on given encoder outputs, in the state of a
+    plain checkpoint load: no n-gram file (ngram_path None) and no LM (lm None, lm_weight 0), temperature 1."""
+    _stub_third_party()
+    import models.transducer as tr
+    import models.decoders as dec
+    import models.joint_networks as jn
+    obj = tr.Transducer.__new__(tr.Transducer)
+    nn.Module.__init__(obj)
+    obj.decoder = dec.RnnDecoder(dec_params).eval()
+    obj.joint_network = jn.JointNetwork(f.shape[-1], dec_params["dim_model"], dec_params["vocab_size"], joint_params).eval()
+    obj.decoder.load_state_dict(to_torch({k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}), strict=True)
+    obj.joint_network.load_state_dict(to_torch({k[len("joint_network."):]: v for k, v in sd.items() if k.startswith("joint_network.")}), strict=True)
+    obj.beam_size, obj.tmp, obj.ngram_path, obj.lm, obj.lm_weight = beam_size, 1, None, None, 0
+
+    class _Ids:                                   # tokenizer.decode(one id list per utterance) -> keep the ids
+        @staticmethod
+        def decode(ids):
+            return list(map(int, ids))
+    obj.tokenizer = _Ids()
+    object.__setattr__(obj, "encoder", lambda x, x_len: (f, f_len, None))
+    obj.eval()
+    with torch.no_grad():
+        return obj.beam_search_decoding(torch.zeros(f.shape[0], 1), f_len)
+
+
+def rnnt_beam_goldens():
+    """RNN-T beam search: the reference's own beam_search_decoding on the encoder outputs stored in rnnt_<name>.npz (blank bias 1.2).
+    Only beams the reference terminates on: Tiny at beam 1 and Medium at beam 4 never see blank in the top of the popped hypothesis
+    in some frame, and the reference's loop (transducer.py:237) runs forever there."""
+    for name, beams in (("TinyTransducer", (4, 16)), ("EfficientConformerTransducerMedium", (16,))):
+        cfg = named_config(name)
+        g = np.load(os.path.join(OUT, "rnnt_%s.npz" % name))
+        f, f_len, seed, bb = torch.from_numpy(g["f"]), torch.from_numpy(g["f_len"]), int(g["weight_seed"]), 1.2
+        sd = synth.make_transducer_state_dict(f.shape[-1], cfg["decoder_params"], cfg["joint_params"], seed, blank_bias=bb)
+        arrs = {"weight_seed": np.int64(seed), "blank_bias": np.float32(bb), "beams": np.asarray(beams, dtype=np.int32)}
+        for beam in beams:
+            toks = reference_rnnt_beam(f, f_len, cfg["decoder_params"], cfg["joint_params"], sd, beam)
+            arrs["tokens_b%d" % beam], arrs["offsets_b%d" % beam] = pack_labels(toks)
+            print("  %s beam %d: tokens per utterance %s (frames %s)" % (name, beam, [len(t) for t in toks], f_len.tolist()))
+        save("rnnt_beam_" + name, **arrs)
+
+
 STREAMING = (("causal", dict(causal=True)), ("ctx_l20_r4", dict(left_context=20, right_context=4)),
              ("causal_l12", dict(causal=True, left_context=12)), ("ctx_l3_r0", dict(left_context=3, right_context=0)))
 
@@ -204,9 +248,12 @@ def main():
     enc_mod, att_mod = import_reference()
     if "--only-rnnt" in sys.argv:
         return rnnt_goldens(enc_mod)
+    if "--only-rnnt-beam" in sys.argv:
+        return rnnt_beam_goldens()
     if "--only-streaming" in sys.argv:
         return streaming_goldens(enc_mod)
     rnnt_goldens(enc_mod)
+    rnnt_beam_goldens()
     streaming_goldens(enc_mod)
 
     # ---- 1. tiny config: every module output, two sequence lengths (T1 % 3 == 0 and != 0)
