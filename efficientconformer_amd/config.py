@@ -236,6 +236,9 @@ def named_config(name: str) -> dict:
         cfg["joint_params"] = {"joint_mode": "sum", "dim_model": d, "act": "tanh"}
         # the beam search part of the shipped configs' decoding_params (the n-gram / LM fusion entries are not implemented)
         cfg["decoding_params"] = {"beam_size": 16, "tmp": 1}
+    else:
+        # the same for the CTC configs (ctcdecode's beam search; the n-gram entries are not implemented)
+        cfg["decoding_params"] = {"beam_size": 16, "tmp": 1}
     return cfg
 
 

@@ -4,12 +4,17 @@
 (``encoder.*``, ``fc.*``) and method names (including the reference's spelling
 ``gready_search_decoding``), but the head and the greedy collapse run as HIP kernels
 (effconf_ctc_greedy) instead of ``nn.Linear`` + a Python loop with ``.item()`` per token.
-Training (losses, optimizer, schedules), beam search and WER scoring are out of scope (HISTORY.md).
+``beam_search_decoding`` (model_ctc.py:138-181) is ctcdecode's CTC prefix beam search without the n-gram scorer: the head's
+fp32 logits go to one persistent HIP kernel per batch (effconf_ctc_beam, one workgroup per utterance) instead of a host copy and
+8 CPU processes.  The n-gram (KenLM) terms (``ngram_path``, ``ngram_alpha``, ``ngram_beta``), neural-LM fusion, probability
+cutoffs below the shipped ones and per-token timesteps are not implemented.  Training (losses, optimizer, schedules) and WER
+scoring are out of scope (HISTORY.md).
 """
 from __future__ import annotations
 
 from typing import List, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -28,8 +33,12 @@ class ModelCTC(nn.Module):
         self.encoder = ConformerEncoder(encoder_params)
         self.fc = nn.Linear(self.encoder.plan.dim_out, tokenizer_params["vocab_size"])
         self.encoder.attach_head(self.fc)
+        decoding_params = decoding_params or {}
+        self.beam_size = int(decoding_params.get("beam_size", 1))                    # model.py:60-61
+        self.tmp = float(decoding_params.get("tmp", 1))
         self.tokenizer = tokenizer
         self.name = name
+        self._beam_ws = None
         self.eval()
 
     @classmethod
@@ -130,3 +139,93 @@ class ModelCTC(nn.Module):
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
 
     greedy_search_decoding = gready_search_decoding
+
+    # ------------------------------------------------------------------ beam search
+    def _check_beam(self, beam: int, vocab: int):
+        if not 1 <= beam <= 32:
+            raise _lib.EffconfError("beam_size must be in 1 .. 32; got %d" % beam)
+        if not 2 <= vocab <= 1024:
+            raise _lib.EffconfError("vocab_size must be in 2 .. 1024 for the CTC beam search; got %d" % vocab)
+        if not 0 < self.tmp < float("inf"):
+            raise _lib.EffconfError("decoding_params['tmp'] must be > 0; got %r" % (self.tmp,))
+
+    def decode_logits_beam(self, logits: torch.Tensor, logits_len: Optional[torch.Tensor], beam_size: Optional[int] = None):
+        """CTC prefix beam search of head logits (B, T, V) fp32 on the GPU (effconf_ctc_beam), temperature ``self.tmp`` ->
+        (tokens (B, beam, T) i32, token_len (B, beam) i32, score (B, beam) f32), ranked best first.  score = log(P_blank + P_nonblank)
+        of the prefix; ranks without a hypothesis have length 0 and score -inf."""
+        beam = int(self.beam_size if beam_size is None else beam_size)
+        if logits.dim() != 3:
+            raise _lib.EffconfError("logits must be (batch, frames, vocab); got shape %s" % (tuple(logits.shape),))
+        b, t, v = logits.shape
+        self._check_beam(beam, v)
+        if not logits.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        lib = _lib.load()
+        nbytes = int(lib.effconf_ctc_beam_workspace_bytes(b, t, v, beam))
+        if nbytes == 0:
+            raise _lib.EffconfError("effconf_ctc_beam_workspace_bytes rejected (batch %d, T %d, vocab %d, beam %d): %s"
+                                    % (b, t, v, beam, lib.effconf_last_error().decode()))
+        with torch.cuda.device(logits.device):
+            logits = logits.contiguous().float()
+            if logits_len is None:
+                logits_len = torch.full((b,), t, dtype=torch.int64, device=logits.device)
+            logits_len = logits_len.to(device=logits.device, dtype=torch.int64).contiguous()
+            tokens = torch.empty(b, beam, t, dtype=torch.int32, device=logits.device)
+            token_len = torch.empty(b, beam, dtype=torch.int32, device=logits.device)
+            score = torch.empty(b, beam, dtype=torch.float32, device=logits.device)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+            _lib.check(lib.effconf_ctc_beam(logits.data_ptr(), logits_len.data_ptr(), b, t, v, beam, float(self.tmp), tokens.data_ptr(),
+                                            token_len.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            torch.cuda.current_stream(logits.device).cuda_stream), "ctc_beam")
+        self._beam_ws = (ws, b, t, beam)
+        return tokens, token_len, score
+
+    def last_beam_trace(self) -> List[dict]:
+        """The workspace of the last decode_logits_beam call (layout: include/effconf.h), one dict per utterance: ``len`` (frames
+        decoded), ``candidates`` (candidates scored, summed over frames), ``node`` (len, beam) i32 and ``pb`` / ``pnb`` / ``score``
+        (len, beam) f32 = the beam after each frame in rank order (node -1: no member), ``parent`` / ``token`` / ``length`` (nodes,)
+        i32 = the prefix trie (node 0: the empty prefix)."""
+        ws, b, t, beam = self._beam_ws
+        raw = ws.cpu().numpy()
+        base = (-ws.data_ptr()) % 256                                  # the library aligns the workspace up to 256 bytes
+
+        def al(x):
+            return (x + 255) // 256 * 256
+        ncap = 1 + beam * t
+        h = 1
+        while h < 2 * ncap:
+            h <<= 1
+        o_nodes = al(16 * t * beam)
+        per_utt = o_nodes + al(16 * ncap) + al(8 * h) + al(4 * h)
+        stats = raw[base:base + 16 * b].view(np.int32).reshape(b, 4)
+        out = []
+        for i in range(b):
+            u = base + al(16 * b) + i * per_utt
+            n, nn = int(stats[i, 0]), int(stats[i, 2])
+            tr = raw[u:u + 16 * t * beam].view(np.int32).reshape(t, beam, 4)[:n]
+            trf = tr.view(np.float32)
+            nd = raw[u + o_nodes:u + o_nodes + 16 * ncap].view(np.int32).reshape(ncap, 4)[:nn]
+            out.append({"len": n, "candidates": int(stats[i, 1]), "node": tr[:, :, 0].copy(), "pb": trf[:, :, 1].copy(),
+                        "pnb": trf[:, :, 2].copy(), "score": trf[:, :, 3].copy(), "parent": nd[:, 0].copy(), "token": nd[:, 1].copy(),
+                        "length": nd[:, 2].copy()})
+        return out
+
+    def beam_labels(self, x: torch.Tensor, x_len: Optional[torch.Tensor], beam_size: Optional[int] = None,
+                    from_mel: bool = False) -> List[List[int]]:
+        """Best CTC beam-search label-id sequence per utterance: encoder, head logits (``_head(want_logits=True)``), effconf_ctc_beam."""
+        beam = int(self.beam_size if beam_size is None else beam_size)
+        self._check_beam(beam, self.fc.out_features)
+        if not x.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        enc, enc_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+        logits, _, _ = self._head(enc, enc_len, want_logits=True)
+        tokens, token_len, _ = self.decode_logits_beam(logits, enc_len, beam)
+        tokens, token_len = tokens[:, 0].cpu(), token_len[:, 0].cpu()          # one D2H copy per batch
+        return [tokens[i, :int(token_len[i])].tolist() for i in range(tokens.shape[0])]
+
+    def beam_search_decoding(self, x, x_len, beam_size=None):
+        """Reference name and signature (model_ctc.py:138).  ``tokenizer.decode(list_of_id_lists)`` of the best beam when a tokenizer
+        is attached (model_ctc.py:181), otherwise the id lists.  Without the n-gram terms: the ``ngram_*`` and ``lm_*`` entries of
+        decoding_params are ignored."""
+        ids = self.beam_labels(x, x_len, beam_size)
+        return self.tokenizer.decode(ids) if self.tokenizer is not None else ids

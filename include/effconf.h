@@ -140,6 +140,28 @@ int effconf_ctc_greedy(EcEncoder* enc, const float* enc_out, const int64_t* out_
 int effconf_ctc_greedy_bf16(EcEncoder* enc, const uint16_t* enc_out_bf16, const int64_t* out_len, int32_t batch, int32_t t_out,
                             int32_t* labels, int32_t* label_len, float* logits, void* workspace, size_t workspace_bytes, void* stream);
 
+/* CTC prefix beam search: ModelCTC.beam_search_decoding (reference model_ctc.py:138-181, ctcdecode's CTCBeamDecoder with blank 0,
+ * cutoff_top_n = vocab, cutoff_prob 1) without the n-gram (KenLM) terms, one persistent workgroup per utterance.  logits dev f32
+ * (batch, t_out, vocab), e.g. the logits output of effconf_ctc_greedy; per frame logP = (logits / temperature).softmax().log() in fp32.
+ * out_len dev i64 (batch), clamped to [0, t_out]; frames at or beyond it are never read.  1 <= beam <= 32, 2 <= vocab <= 1024,
+ * temperature > 0.  Outputs, ranked best first: tokens dev i32 (batch, beam, t_out) with zero-filled tails, token_len dev i32
+ * (batch, beam), score dev f32 (batch, beam) = log(P_blank + P_nonblank) of the prefix (ctcdecode's beam_scores are -score).  Ranks
+ * without a hypothesis have length 0 and score -inf; len 0 gives the empty prefix with score 0.
+ * Workspace (effconf_ctc_beam_workspace_bytes; the library aligns the pointer up to 256 bytes; al(x) = x rounded up to 256):
+ *   [0, 16 batch)            i32 stats[batch][4]: frames decoded, candidates scored (sum over frames), trie nodes used, 0
+ *   al(16 batch) + b * U     utterance b, U = al(16 t_out beam) + al(16 N) + al(8 H) + al(4 H), N = 1 + beam t_out trie nodes,
+ *                            H = smallest power of two >= 2 N:
+ *     trace [t_out][beam]    {i32 node, f32 pb, f32 pnb, f32 score} of the beam after frame t, in rank order (t < len only; a rank
+ *                            without a member has node -1 and -inf values)
+ *     nodes [N]              {i32 parent, i32 token, i32 length, i32 0}; node 0 is the empty prefix (-1, -1, 0); a prefix's node is
+ *                            the same for as long as the call runs (a prefix created again gets its old node)
+ *     hash keys u64 [H], hash nodes i32 [H]   the (parent, token) -> node index
+ * effconf_ctc_beam_workspace_bytes returns 0 for arguments effconf_ctc_beam rejects. */
+size_t effconf_ctc_beam_workspace_bytes(int32_t batch, int32_t t_out, int32_t vocab, int32_t beam);
+int effconf_ctc_beam(const float* logits, const int64_t* out_len, int32_t batch, int32_t t_out, int32_t vocab, int32_t beam,
+                     float temperature, int32_t* tokens, int32_t* token_len, float* score, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* (Grouped)RelPosMultiHeadSelfAttention core alone (reference attentions.py:549-718 between the input projections and the output
  * projection): natural-layout bf16 device buffers qu = Q + u, k, v of (batch * Tp, dim) rows (Tp = frames rounded up to the group
  * size; pad rows: qu = u, k = v = 0), e = pos_layer(R) of (2 Tp - group, dim) rows, dvu = (v - u) per head column as fp32
