@@ -68,7 +68,7 @@ __device__ __forceinline__ void add_cvec(f32x16 (&xc)[NT], const float* sv, int 
             xc[t][4 * q + 0] += v.x; xc[t][4 * q + 1] += v.y; xc[t][4 * q + 2] += v.z; xc[t][4 * q + 3] += v.w;
         }
 }
-// two-pass statistics over the D valid columns (pad columns hold exact zeros); eps 1e-6 (reference modules.py:377, 447; blocks.py:97)
+// two-pass statistics over the D valid columns (pad columns hold exact zeros: nothing to the sum, masked out of the squares); eps 1e-6 (reference modules.py:377, 447; blocks.py:97)
 template <int NT>
 __device__ __forceinline__ void ln_stats(const f32x16 (&xc)[NT], int D, float& mean, float& rstd) {
     float sum = 0.f;
@@ -77,16 +77,21 @@ __device__ __forceinline__ void ln_stats(const f32x16 (&xc)[NT], int D, float& m
 #pragma unroll
         for (int r = 0; r < 16; r += 4) sum += (xc[t][r] + xc[t][r + 1]) + (xc[t][r + 2] + xc[t][r + 3]);
     mean = (sum + __shfl_xor(sum, 32)) / (float)D;
+    // registers r .. r + 3 of tile t are the columns 32 t + 2 r + 4 (lane / 32) + (0..3) (add_cvec); D % 4 == 0: such a piece is valid or pad as a whole.
+    // A pad piece adds nothing: summing its four (0 - mean)^2 and subtracting pad * mean^2 afterwards cancels catastrophically where
+    // |mean| >> std (a stream with an offset of 160 and unit deviation at D = 24: 2e5 + 24 - 2e5 in float32, rstd off by 5e-4).  The pads lie in
+    // the last two tiles (widths 16 .. 32 -> 32, .. 64, 68 .. 128, .. 192, .. 256: at most 60 pad columns)
+    const int lim = D - 4 * (int)((threadIdx.x & 63) >> 5);
     float var = 0.f;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 16; r += 4) {
             const float a = xc[t][r] - mean, b = xc[t][r + 1] - mean, c = xc[t][r + 2] - mean, d = xc[t][r + 3] - mean;
-            var += (a * a + b * b) + (c * c + d * d);
+            const float g = (a * a + b * b) + (c * c + d * d);
+            var += (t < NT - 2 || 32 * t + 2 * r < lim) ? g : 0.f;
         }
     var += __shfl_xor(var, 32);
-    var -= (float)(32 * NT - D) * mean * mean;           // the zero pad columns contributed (0 - mean)^2 each
     rstd = rsqrtf(fmaxf(var, 0.f) / (float)D + 1e-6f);
     // opaque copy: keeps the compiler from carrying all (x - mean) differences of the variance pass into the normalisation
     // (64-128 extra live registers pushed loop-invariant addresses into scratch, and scratch reloads share the vmcnt FIFO with
@@ -864,6 +869,7 @@ bool chain_full_supported(int D, int dmax) { return chain_head_supported(D) && D
 int launch_chain(const ChainParams& p, int kind, hipStream_t s) {
     if (p.M <= 0) return 0;
     if (!chain_supported(p.D)) return -2;
+    if (chain_padded_width(p.D) - p.D >= 64) return -2;      // ln_stats (here, chain2.hip, chain3.hip) masks the pad columns of the LAST TWO 32-column tiles only
     if (p.pair && chain3_supported(p.D)) return kind == CHAIN_B ? launch_chain2(p, s) : launch_chain3(p, kind, s);      // padded width 256
     switch (kind) {
         case CHAIN_B: return launch_chain_kind<CHAIN_B>(p, s);

@@ -265,7 +265,8 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
 #pragma unroll
                 for (int r = 0; r < 16; r += 4) {
                     const float a = xc[t][r] - mu, b = xc[t][r + 1] - mu, c = xc[t][r + 2] - mu, d = xc[t][r + 3] - mu;
-                    var += (a * a + b * b) + (c * c + d * d);
+                    const float g = (a * a + b * b) + (c * c + d * d);
+                    var += (t < NTH - 2 || 32 * (ct0 + t) + 2 * r + 4 * half < D) ? g : 0.f;      // pad pieces add nothing (chain.hip ln_stats)
                 }
             return var;
         };
@@ -279,7 +280,6 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
         if (cw == 1) {
             float var = pvar(*pa, mean);
             var += __shfl_xor(var, 32);
-            var -= (float)(32 * NT - D) * mean * mean;
             rstd = rsqrtf(fmaxf(var, 0.f) / (float)D + 1e-6f);
             *my = rstd;
         }

@@ -194,9 +194,11 @@ int launch_conv2_igemm(const bf16_t* act1, int B, int F1, int T1, int Cp, const 
 // g (B, T, ld) bf16 -> (B, To, ld) bf16: depthwise conv k taps ("same" zero pad), stride s, folded BN, Swish
 int launch_dwconv(const bf16_t* g, int B, int T, int To, int C, int ld, const float* w_kc, const float* bias,
                   int ksize, int stride, bf16_t* out, hipStream_t s, const RaggedConv* rc = nullptr, int causal = 0,
-                  const void* w_mfma = nullptr);      // w_mfma: pack_dwconv_mfma's table -> dwconv_mfma_kernel (stride 1)
+                  const void* w_mfma = nullptr,       // w_mfma: pack_dwconv_mfma's table -> dwconv_mfma_kernel (stride 1)
+                  const void* w_mfma3 = nullptr);     // w_mfma3: pack_dwconv_mfma3's third tap plane (blocks with large folded taps)
 int dwconv_mfma_groups(int ksize);
 bool dwconv_mfma_supported(int ksize, int stride);
+void pack_dwconv_mfma3(const float* w_kc, int ksize, int C, uint16_t* dst);    // dst: C * 4 * dwconv_mfma_groups(ksize) * 4 bf16
 void pack_dwconv_mfma(const float* w_kc, int ksize, int C, uint16_t* dst);     // dst: C * 4 * dwconv_mfma_groups(ksize) * 8 bf16   // causal: pre-padding (k - 1, 0)
 
 // ---------------------------------------------------------------- fp32-operand "exact" mode  (exact.hip)

@@ -136,35 +136,20 @@ def rel_sinusoid_rows_causal(tp: int, dim: int, dtype=torch.float) -> torch.Tens
     return r
 
 
-def relpos_attention(x: torch.Tensor, lens: Optional[torch.Tensor], sd, prefix: str, heads: int, group: int,
-                     return_probs: bool = False, causal: bool = False, left: Optional[int] = None, right: Optional[int] = None,
-                     mask_stride: int = 1):
-    """x: (B, T, D) *already pre-normed*; lens: valid frames per utterance at this stage.
-    Closed form (SURVEY.md section 8a-6): S[b,h,i,j] = (Qu_i.K_j + Qv_i.E[Tg-1+j-i]) / sqrt(d).
-    Streaming contexts (attentions.py:1377-1403, sliced ::s at encoders.py:132-136 and ::G at attentions.py:698): grouped key j is masked
-    for grouped query i iff mask_stride * G * (j - i) > right or < -left.  causal (attentions.py:506-529, 1243-1247): E has Tg rows and the
-    relative-to-absolute shift is the Music-Transformer skew; entries right of the diagonal are whatever the skew wraps in - the causal
-    mask (right = 0) covers them."""
-    bsz, t, dim = x.shape
-    m = prefix + ".mhsa."
-    q = F.linear(x, _t(sd, m + "query_layer.weight"), _t(sd, m + "query_layer.bias"))
-    k = F.linear(x, _t(sd, m + "key_layer.weight"), _t(sd, m + "key_layer.bias"))
-    v = F.linear(x, _t(sd, m + "value_layer.weight"), _t(sd, m + "value_layer.bias"))
-    tp = (t + group - 1) // group * group                 # chunk padding, attentions.py:107-138, 671
+def relpos_scores(qu, qv, k, e, lens, t: int, heads: int, group: int, causal: bool = False, left: Optional[int] = None,
+                  right: Optional[int] = None, mask_stride: int = 1) -> torch.Tensor:
+    """Masked, scaled scores (B, H, Tg, Tg) of relpos_attention from its operands: qu = Q + u, qv = Q + v, k (B, Tp, D) with the chunk
+    padding in place, e (2Tp - G, D; causal: (Tp, D)) the projected positional rows, t the frames before chunk padding.  Split out of
+    relpos_attention (same operations, same order) so that oracle/ref_bf16.py masks and gathers with the same code."""
+    bsz, tp, dim = qu.shape
     pad = tp - t
-    if pad:
-        q, k, v = (F.pad(z, (0, 0, 0, pad)) for z in (q, k, v))    # zeros *after* the projections
-    qu = q + _t(sd, m + "u")                               # attentions.py:674-675 (pad rows become u / v)
-    qv = q + _t(sd, m + "v")
     tg = tp // group
     d = group * dim // heads                               # attentions.py:643
-    ft = x.dtype                                           # float32 unless the whole forward runs in float64
-    rows = rel_sinusoid_rows_causal(tp, dim, ft) if causal else rel_sinusoid_rows(tp, dim, group, ft)
-    e = F.linear(rows, _t(sd, m + "pos_layer.weight"), _t(sd, m + "pos_layer.bias"))
+    ft = qu.dtype
 
     def split(z, rows):                                    # (B, rows*G, D) -> (B, H, rows, d): a pure view + transpose
         return z.reshape(z.shape[0], rows, heads, d).transpose(1, 2)
-    qu, qv, k, v = split(qu, tg), split(qv, tg), split(k, tg), split(v, tg)
+    qu, qv, k = split(qu, tg), split(qv, tg), split(k, tg)
     e = split(e.unsqueeze(0), tg if causal else 2 * tg - 1)[0]               # (H, 2Tg-1, d); causal: (H, Tg, d)
     s_k = qu @ k.transpose(2, 3)                           # (B, H, Tg, Tg)
     s_rel = qv @ e.transpose(1, 2)                         # (B, H, Tg, 2Tg-1); causal: (B, H, Tg, Tg)
@@ -199,6 +184,35 @@ def relpos_attention(x: torch.Tensor, lens: Optional[torch.Tensor], sd, prefix: 
         if band is not None:
             masked = torch.maximum(masked, band[None, None])
         s = s + masked * -1e9
+    return s
+
+
+def relpos_attention(x: torch.Tensor, lens: Optional[torch.Tensor], sd, prefix: str, heads: int, group: int,
+                     return_probs: bool = False, causal: bool = False, left: Optional[int] = None, right: Optional[int] = None,
+                     mask_stride: int = 1):
+    """x: (B, T, D) *already pre-normed*; lens: valid frames per utterance at this stage.
+    Closed form (SURVEY.md section 8a-6): S[b,h,i,j] = (Qu_i.K_j + Qv_i.E[Tg-1+j-i]) / sqrt(d).
+    Streaming contexts (attentions.py:1377-1403, sliced ::s at encoders.py:132-136 and ::G at attentions.py:698): grouped key j is masked
+    for grouped query i iff mask_stride * G * (j - i) > right or < -left.  causal (attentions.py:506-529, 1243-1247): E has Tg rows and the
+    relative-to-absolute shift is the Music-Transformer skew; entries right of the diagonal are whatever the skew wraps in - the causal
+    mask (right = 0) covers them."""
+    bsz, t, dim = x.shape
+    m = prefix + ".mhsa."
+    q = F.linear(x, _t(sd, m + "query_layer.weight"), _t(sd, m + "query_layer.bias"))
+    k = F.linear(x, _t(sd, m + "key_layer.weight"), _t(sd, m + "key_layer.bias"))
+    v = F.linear(x, _t(sd, m + "value_layer.weight"), _t(sd, m + "value_layer.bias"))
+    tp = (t + group - 1) // group * group                 # chunk padding, attentions.py:107-138, 671
+    pad = tp - t
+    if pad:
+        q, k, v = (F.pad(z, (0, 0, 0, pad)) for z in (q, k, v))    # zeros *after* the projections
+    qu = q + _t(sd, m + "u")                               # attentions.py:674-675 (pad rows become u / v)
+    qv = q + _t(sd, m + "v")
+    ft = x.dtype                                           # float32 unless the whole forward runs in float64
+    rows = rel_sinusoid_rows_causal(tp, dim, ft) if causal else rel_sinusoid_rows(tp, dim, group, ft)
+    e = F.linear(rows, _t(sd, m + "pos_layer.weight"), _t(sd, m + "pos_layer.bias"))
+    s = relpos_scores(qu, qv, k, e, lens, t, heads, group, causal, left, right, mask_stride)
+    tg = tp // group
+    v = v.reshape(bsz, tg, heads, group * dim // heads).transpose(1, 2)
     p = s.softmax(dim=-1)
     o = (p @ v).transpose(1, 2).reshape(bsz, tp, dim)[:, :t]      # un-group, drop chunk padding (:710-713)
     o = F.linear(o, _t(sd, m + "output_layer.weight"), _t(sd, m + "output_layer.bias"))
