@@ -1,7 +1,7 @@
 """ORACLE — test infrastructure only: the bf16 path's arithmetic contract, stage by stage, in plain torch on the CPU.
 
 The statement of record of WHERE the bf16 path (efficientconformer_amd/csrc: chain.hip, chain2.hip, chain3.hip, rsgemm.hip, gemm.hip,
-attention2.hip, attention.hip, conv.hip) rounds to bf16.  Every function is one stage between two points of the debug trace
+attention2.hip, attention.hip, conv.hip, conv2.hip, sublinear.hip, sublinear2.hip, sublinear3.hip) rounds to bf16.  Every function is one stage between two points of the debug trace
 (ConformerEncoder.trace_forward_mel), takes that stage's INPUT tensor(s), the float32 reference state dict (keys without ``encoder.``),
 the BlockPlan and ``dtype``, and evaluates the stage in ``dtype`` arithmetic with the one rounding helper ``q`` applied at exactly the
 kernels' rounding points.  ``dtype = torch.float64`` is the reference; ``dtype = torch.float32`` is the noise model (what a correct
@@ -32,9 +32,31 @@ Conventions
   (encoder.hip build_pos_table: h_f2bf(std::sin(a)); launch_gemm(pe, EPI_BF16)).  Scores, softmax and P V are not rounded here; ``round_p``
   rounds exp(s - rowmax) to bf16 before P V - the kernel rounds P against its RUNNING maximum, which cannot be reproduced exactly, so
   ``round_p`` belongs to the noise model only.
-* Front end (sublinear3.hip, sublinear2.hip, conv2.hip + gemm.hip): NOT modelled in this module - the three routes fold and round the
-  convolution taps differently and none has been written down here - so the trace entry ``linear`` keeps the un-rounded oracle test of
-  tests/test_gpu_round6.py only.
+* Front end (conv.hip + gemm.hip, sublinear.hip, sublinear2.hip, sublinear3.hip, conv2.hip + gemm.hip), one contract for all five routes:
+  - Layer 1: BatchNorm2d folded into the nine taps and the bias in float32 - scale = gamma / sqrt(var + 1e-5f), shift = beta - mean * scale (encoder.hip
+    bn_fold), tap = w * scale, bias = b * scale + shift (effconf_encoder_finalize: the ``w9[ch * 9 + j] = w->data[ch * 9 + j] * sc[ch]`` /
+    ``bb[ch] = b->data[ch] * sc[ch] + sh[ch]`` loop) - float32 mel, float32 accumulation, Swish, then ONE rounding to bf16: conv.hip
+    subsample_conv_kernel ``pack_bf2(swishf_(acc[0][tl]), swishf_(acc[1][tl]))``, sublinear.hip ``pa[i] = make_uint4(pack_bf2(r[0], r[1]), ...)``,
+    sublinear2.hip ``y[e] = swishf_(cv[8 * j + e])`` / ``xf[2 * g + j] = ... pack_bf2(y[0], y[1])``, sublinear3.hip ``q.hh[pr] = pack_bf2(q.x[2 * pr], ...)``,
+    conv2.hip subsample_conv_cl_kernel ``pack_bf2(r0, r1)``.  Nothing else is rounded: taps, bias and mel stay float32 numbers.
+  - ``conv="split"`` (sublinear2.hip, sublinear3.hip: the convolution on the matrix pipe): both operands as hi + lo with hi = the float32 number with
+    its low 16 bits cleared (sublinear2.hip split_hi, sublinear3.hip hi_bits, encoder.hip put_tap ``u & 0xFFFF0000u``) and lo = q(x - hi)
+    (``pack_bf2(v[2 * e] - __uint_as_float(h0), ...)``, put_tap ``h_f2bf(v - hf)``), the sum W_hi P_hi + W_hi P_lo + W_lo P_hi - the lo lo term, 2^-14 of a
+    product at most, is dropped - and the folded bias as tap slot 9 against a patch entry of 1.0 (encoder.hip ``tab[ch * 16 + 9] = bb[ch]`` /
+    ``put_tap(ch, 9, bb[ch])``, sublinear2.hip ``tp[1] = 1.0f``).  An evaluation of the same contract to ~2^-14 of sum |w| |p|: it belongs to the noise
+    model only, the float64 reference is the exact convolution.
+  - Time padding: zeros in front of frame 0 and behind the utterance's own last mel frame where lengths are given (ragged batches: conv.hip
+    ``tmb = rag_tm ? rag_tm[b] : Tm``, sublinear3.hip ``Tv = p.mel_len ? p.mel_len[b] : p.Tm``, conv2.hip ``Tmb``); a rectangular batch reads the rectangle as it
+    is, pad frames included.  Frequency padding: zero rows at -1 and n_mels.
+  - Layer 2 of the two-layer subsampler (conv2.hip conv2_igemm_kernel) from the stored bf16 layer-1 image, which a ragged batch zero-fills behind every
+    utterance's own (len - 1) / 2 + 1 frames (subsample_conv_cl_kernel ``t < T1b ? swishf_(a.x) : 0.f``): weight q(float32(w2 * scale2)) (encoder.hip
+    ``h_f2bf(w2->data[...] * sc2[n])``), float32 bias b2 * scale2 + shift2 added after the sum, Swish, bf16 store (``f2bf(swishf_(acc[mi][ni][r] + bz))``).
+  - Linear: act . q(W)^T + b with a float32 bias, float32 out (encoder.hip pack_linear and the ``wf`` / ``wr`` / ``wimg`` loops: h_f2bf(lw->data[...])).
+    The K orders of those images ((fc * Cp + c) * 8 + e; permuted per 16; accumulator order of 32-channel chunks; (f2, c)) are the packers' business:
+    ``front_linear`` contracts in the reference's feature order c * F' + f (modules.py:247) and nothing else, which is what makes a wrong permutation visible.
+  The trace holds ``subsample`` (the last layer's bf16 activation) where separate kernels write it - fuse_subsample = 0, front ends without a fused
+  kernel, ragged batches off the matrix-pipe routes, the two-layer subsampler (whose layer-1 image is ``subsample1``) - and nothing between mel and
+  ``linear`` on the fused routes, where the activation only exists in registers.
 
 Masking, the relative-to-absolute gather, the streaming band and the sinusoid rows are oracle/ref_encoder.py's own code (relpos_scores,
 rel_sinusoid_rows, rel_sinusoid_rows_causal): this module adds roundings, nothing else.
@@ -145,6 +167,99 @@ def ffn(x: torch.Tensor, sd, prefix: str, dtype, folded: bool, rnd: Callable = q
     if prod is None:
         prod = h @ w2.T
     return x + prod + 0.5 * _w(sd, prefix + ".layers.4.bias", dtype)
+
+
+# ------------------------------------------------------------------ front end: Conv2dSubsampling + Linear
+def bn_fold2d(sd, layer: int, ft, eps: float = R.BN_EPS) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(weight, scale, folded bias) of subsampling layer ``layer`` in ``ft`` arithmetic (the kernels: float32): scale = gamma / sqrt(var + eps),
+    bias = b * scale + (beta - mean * scale).  ``eps`` other than BN_EPS: tests only."""
+    p = "subsampling_module.layers.%d" % layer
+    sc = _w(sd, p + ".1.weight", ft) / torch.sqrt(_w(sd, p + ".1.running_var", ft) + eps)
+    sh = _w(sd, p + ".1.bias", ft) - _w(sd, p + ".1.running_mean", ft) * sc
+    return _w(sd, p + ".0.weight", ft), sc, _w(sd, p + ".0.bias", ft) * sc + sh
+
+
+def split_hi_lo(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The matrix-pipe front ends' operand split of float32 numbers: hi = x with its low 16 bits cleared, lo = q(x - hi)."""
+    x = x.float().contiguous()
+    hi = (x.view(torch.int32) & -65536).view(torch.float32)
+    return hi, q(x - hi)
+
+
+def mask_time(x: torch.Tensor, lens: Optional[torch.Tensor]) -> torch.Tensor:
+    """x (..., T) with zeros behind every utterance's own ``lens[b]`` frames (None: as it is)."""
+    if lens is None:
+        return x
+    keep = torch.arange(x.shape[-1])[None, :] < torch.as_tensor(lens).reshape(-1, 1)
+    return x * keep.reshape([x.shape[0]] + [1] * (x.dim() - 2) + [x.shape[-1]]).to(x.dtype)
+
+
+def front_conv(mel: torch.Tensor, mel_len: Optional[torch.Tensor], sd, plan, dtype, rnd: Callable = q, conv: str = "fp32") -> torch.Tensor:
+    """mel (B, n_mels, Tm) -> layer 1 of the subsampler (B, C, n_mels / 2, (Tm - 1) / 2 + 1) before its bf16 store: the 3 x 3 stride-2 pad-1 convolution
+    with the BatchNorm folded in float32, Swish.  ``mel_len``: the time-side zero padding starts behind each utterance's own frames (frames behind
+    (len - 1) / 2 + 1 of the result are then the convolution of zeros: callers take the utterance's own).  ``conv="split"``: the matrix-pipe formula
+    (module docstring), float32 operands - noise model only."""
+    x = mask_time(mel.to(dtype), mel_len).unsqueeze(1)
+    if rnd is ident:
+        p = "subsampling_module.layers.0"
+        h = F.conv2d(x, _w(sd, p + ".0.weight", dtype), _w(sd, p + ".0.bias", dtype), stride=2, padding=1)
+        h = F.batch_norm(h, _w(sd, p + ".1.running_mean", dtype), _w(sd, p + ".1.running_var", dtype), _w(sd, p + ".1.weight", dtype),
+                         _w(sd, p + ".1.bias", dtype), False, 0.0, R.BN_EPS)
+        return swish(h)
+    w, sc, bias = bn_fold2d(sd, 0, torch.float32)
+    w9 = w * sc[:, None, None, None]
+    if conv == "fp32":
+        return swish(F.conv2d(x, w9.to(dtype), bias.to(dtype), stride=2, padding=1))
+    assert conv == "split", conv
+    bsz, _, f, t = x.shape
+    pt = F.unfold(x.float(), 3, padding=1, stride=2)                                         # (B, 9, F1 * T1)
+    pt = torch.cat([pt, torch.ones_like(pt[:, :1])], 1)                                      # slot 9: the bias's 1.0
+    wt = torch.cat([w9.reshape(-1, 9), bias[:, None]], 1)                                    # (C, 10)
+    (whi, wlo), (phi, plo) = split_hi_lo(wt), split_hi_lo(pt)
+    mm = lambda a, b: torch.einsum("cj,bjl->bcl", a.to(dtype), b.to(dtype))
+    h = mm(whi, phi) + mm(whi, plo) + mm(wlo, phi)
+    return swish(h.reshape(bsz, -1, (f - 1) // 2 + 1, (t - 1) // 2 + 1))
+
+
+def front_conv2(act1: torch.Tensor, sd, plan, dtype, rnd: Callable = q) -> torch.Tensor:
+    """act1 (B, C, F1, T1): the STORED bf16 layer-1 image (zero behind an utterance's own frames in ragged batches) -> layer 2 of the two-layer
+    subsampler (B, C1, F1 / 2, (T1 - 1) / 2 + 1) before its bf16 store: weight q(float32(w2 * scale2)), float32 bias, zero rows outside the image, Swish."""
+    x = act1.to(dtype)
+    if rnd is ident:
+        p = "subsampling_module.layers.1"
+        h = F.conv2d(x, _w(sd, p + ".0.weight", dtype), _w(sd, p + ".0.bias", dtype), stride=2, padding=1)
+        h = F.batch_norm(h, _w(sd, p + ".1.running_mean", dtype), _w(sd, p + ".1.running_var", dtype), _w(sd, p + ".1.weight", dtype),
+                         _w(sd, p + ".1.bias", dtype), False, 0.0, R.BN_EPS)
+        return swish(h)
+    w, sc, bias = bn_fold2d(sd, 1, torch.float32)
+    return swish(F.conv2d(x, rnd((w * sc[:, None, None, None]).to(dtype)), bias.to(dtype), stride=2, padding=1))
+
+
+def feature_rows(act: torch.Tensor) -> torch.Tensor:
+    """(B, C, F', T) -> (B, T, C * F') in the reference's feature order c * F' + f (modules.py:247, encoders.py:113)."""
+    b, c, f, t = act.shape
+    return act.reshape(b, c * f, t).transpose(1, 2)
+
+
+def front_linear(act: torch.Tensor, sd, plan, dtype, rnd: Callable = q) -> torch.Tensor:
+    """act (..., K): the STORED bf16 subsampler output in the reference's feature order -> act . q(W)^T + b, float32 rows (..., D0)."""
+    return act.to(dtype) @ rnd(_w(sd, "linear.weight", dtype)).T + _w(sd, "linear.bias", dtype)
+
+
+def front_end(mel: torch.Tensor, mel_len: Optional[torch.Tensor], sd, plan, dtype, rnd: Callable = q, conv: str = "fp32",
+              trace: Optional[dict] = None) -> torch.Tensor:
+    """mel (B, n_mels, Tm) -> the trace entry ``linear`` (B, T1, D0): the stages above chained, every bf16-stored intermediate rounded.  ``mel_len``
+    (ragged batches): padding at the utterance's own length; rows behind an utterance's own frames are not part of the contract.  ``trace`` receives
+    ``subsample`` (B, T1, K), the stored activation in the reference's feature order."""
+    a = rnd(front_conv(mel, mel_len, sd, plan, dtype, rnd, conv))
+    if plan.sub_layers == 2:
+        if mel_len is not None:
+            a = mask_time(a, torch.div(torch.as_tensor(mel_len) - 1, 2, rounding_mode="floor") + 1)
+        a = rnd(front_conv2(a, sd, plan, dtype, rnd))
+    a = feature_rows(a)
+    if trace is not None:
+        trace["subsample"] = a
+    return front_linear(a, sd, plan, dtype, rnd)
 
 
 # ------------------------------------------------------------------ attention side

@@ -4,7 +4,8 @@ tests/test_ref_bf16_host.py (traces made on the CPU) run."""
 import numpy as np
 import torch
 
-from oracle.ref_bf16 import (attention, chain_a, conv_res, depthwise, f32_runs, glu, out_proj, pos_e, q, qkv, rel, stage_ratios, worst_element)
+from oracle import ref_bf16 as Q
+from oracle.ref_bf16 import (attention, chain_a, conv_res, depthwise, f32_runs, ffn, glu, out_proj, pos_e, q, qkv, rel, stage_ratios, worst_element)
 
 F64, F32 = torch.float64, torch.float32
 
@@ -68,12 +69,144 @@ def _misses(x: torch.Tensor, r64: torch.Tensor) -> str:
     return "%d of %d elements off q(r64) in %d rows" % (int(m.sum()), m.numel(), int(m.reshape(-1, m.shape[-1]).any(-1).sum()))
 
 
+def chain_route(fuse, width):
+    """The fused chains serve this stage width (encoder.hip: chain_max_dim = 256; chain.hip chain_supported) and are on (option fuse_chain)."""
+    return bool(fuse) and width % 4 == 0 and 16 <= width <= 256
+
+
+def front_route(plan, opts, ragged):
+    """What run_subsample_linear / the ragged branch of forward_core (encoder.hip) choose for this configuration and these options:
+    {"conv": "fp32" | "split" - the convolution's form, "subsample": the activation is in the trace (separate kernels write it), "fuse_chain": the option}."""
+    fuse, auto = opts.get("fuse_subsample", 2), opts.get("sub3_auto", 1)
+    C0, D0, F = plan.sub_filters[0], plan.blocks[0].dim_model, plan.n_mels
+    route = {"fuse_chain": opts.get("fuse_chain", 1)}
+    if plan.sub_layers == 2:                                                  # conv2.hip + gemm.hip; the ragged form runs on the rectangle and gathers
+        return dict(route, conv="fp32", subsample=True)
+    sub3 = D0 % 4 == 0 and D0 <= 384 and (fuse == 3 or (fuse == 2 and auto and (C0 > 128 or D0 > 128)))          # use_sublinear3, sublinear3_tiles
+    sub2 = fuse >= 2 and F == 80 and D0 % 4 == 0 and ((C0 <= 128 and D0 <= 128) or (C0 <= 192 and D0 <= 192))      # sublinear2_groups
+    if sub3 or sub2:
+        return dict(route, conv="split", subsample=False)
+    sub1 = fuse >= 1 and F == 80 and D0 <= 256 and not ragged                 # sublinear_fused_supported; ragged batches: conv.hip writes the ragged rows
+    return dict(route, conv="fp32", subsample=not sub1)
+
+
+def _bf16_ulp(x: torch.Tensor) -> torch.Tensor:
+    """The distance between neighbouring bf16 numbers at |x| (8 significant bits; never below the smallest normal's)."""
+    _, e = torch.frexp(x.double().abs().clamp_min(2.0 ** -126))
+    return torch.ldexp(torch.ones_like(x, dtype=torch.float64), e - 8)
+
+
+def check_front(got, plan, sd, mel, ln, tm, ragged, route, rep):
+    """The front end and block 0's first FFN of one traced forward against oracle/ref_bf16.py, into the _Report ``rep`` (block number 0).
+    mel (B, n_mels, tm) float32 as the GPU got it, ``ln`` the mel lengths; ``route``: what front_route expects - asserted.
+    Where separate kernels write the activation (``subsample`` in the trace), every stage from its own traced input: ``conv`` - layer 1 from the mel
+    (K = 9; the two-layer subsampler's layer-1 image is the trace entry ``subsample1``) - and ``conv2`` - layer 2 from that image (K = 9 C) - with
+    stage_ratios (bf16 output: the share of correctly rounded outputs included) and the element-wise bound one bf16 ulp of r64 +
+    2 K 2^-23 (sum |w| |p| + |b|) 1.1 (float32 summation through the Swish, whose slope is at most 1.1); ``linear`` from the traced activation with the
+    out-projection's element-wise summation bound.  Fused routes: one stage mel -> ``linear`` (stage ``front``).  Then ``ffn1_0``: blocks.0.x_ffn1 from the
+    traced ``linear``.  Rectangular batches count every frame of the rectangle; ragged batches every utterance's own frames, the reference padding the time
+    axis at the utterance's own length.  Excluded: the group-padding rows of the ragged row space (counted against the lengths; finite in ``linear``, zero in
+    ``subsample``) and, in the two-layer subsampler's rectangular images of a ragged batch, the frames behind an utterance's own (layer 1: asserted zero)."""
+    mel = torch.as_tensor(mel).float()
+    B = len(ln)
+    lens0 = [int(v) for v in ln]
+    lens1, t1 = lens0, tm
+    half = lambda v: (v - 1) // 2 + 1
+    for _ in range(plan.sub_layers):
+        lens1, t1 = [half(v) for v in lens1], half(t1)
+    b0 = plan.blocks[0]
+    sp = _Space(ragged, lens1, t1, b0.group_size)
+    D0 = b0.dim_model
+    K = plan.sub_filters[plan.sub_layers - 1] * (plan.n_mels >> plan.sub_layers)
+    mlen = torch.as_tensor(lens0) if ragged else None
+    lin = got["linear"]
+    assert lin.shape == (sp.rows, D0), (lin.shape, sp.rows, D0)
+    npad = sp.rows - len(sp.xidx)
+    assert npad == (sum(_up(v, b0.group_size) - v for v in lens1) if ragged else 0)
+    pad_rows = torch.ones(sp.rows, dtype=torch.bool)
+    pad_rows[sp.xidx] = False
+    assert int(pad_rows.sum()) == npad and bool(torch.isfinite(lin[pad_rows]).all()), "group-padding rows of ``linear``: count / not finite"
+    assert ("subsample" in got) == bool(route["subsample"]), ("subsample", "expected in the trace" if route["subsample"] else "expected to stay in registers", route)
+    assert ("subsample1" in got) == (plan.sub_layers == 2), "the two-layer subsampler's layer-1 image"
+
+    def own(x, live=None):      # (B, T, columns) -> the valid frames' rows, utterance after utterance
+        live = sp.live if live is None else live
+        return torch.cat([x[b, :live[b]] for b in range(B)])
+
+    def conv_stage(stage, gv, fn, kc, wabs, babs, xabs, rows):
+        """One convolution with a bf16 output: gv the GPU's rows, fn(dtype) the reference's rows before the rounding; |w|, |b|, |input| and the map image -> rows for the bound."""
+        c64, c32 = fn(F64), f32_runs(lambda: fn(F32))
+        rep.add(stage, 0, stage_ratios(gv, c64, c32, kc, True), lambda: "gpu %s, float32 runs %s; %s" % (_misses(gv, c64), [_misses(q(r), c64).split(" of")[0] for r in c32], worst_element(gv, c64)))
+        bound = _bf16_ulp(c64) + 2.0 * kc * 2.0 ** -23 * 1.1 * rows(torch.nn.functional.conv2d(xabs, wabs, babs, stride=2, padding=1))
+        rep.elementwise(stage, 0, "ulp+sum", (gv.double() - c64).abs(), bound, gv, c64)
+
+    gl = lin[sp.xidx]
+    if route["subsample"]:
+        sub = got["subsample"]
+        w, sc, bias = Q.bn_fold2d(sd, 0, F32)
+        w9 = (w * sc[:, None, None, None]).double()
+        mel_own = Q.mask_time(mel, mlen)
+        if plan.sub_layers == 1:
+            assert sub.shape == (sp.rows, K), (sub.shape, sp.rows, K)          # the Linear's rows: rectangular, or the ragged row space (conv.hip writes it)
+            assert float(sub[pad_rows].abs().sum()) == 0.0, "group-padding rows of ``subsample`` are not zero"
+            sub = sub[sp.xidx]
+            rows = lambda x: own(Q.feature_rows(x))
+            conv_stage("conv", sub, lambda dt: rows(Q.front_conv(mel, mlen, sd, plan, dt)), 9, w9.abs(), bias.double().abs(), mel_own.double().abs().unsqueeze(1), rows)
+        else:
+            c0, c1, f1 = plan.sub_filters[0], plan.sub_filters[1], plan.n_mels // 2
+            tl1, live1 = half(tm), ([half(v) for v in lens0] if ragged else [half(tm)] * B)
+            t1r = half(tl1)                                                    # both images are rectangular, ragged batch or not (forward_core gathers the Linear's rows)
+            img = got["subsample1"]
+            assert img.shape == (B * f1 * tl1, c0) and sub.shape == (B * t1r, K), (img.shape, sub.shape)
+            img = img.reshape(B, f1, tl1, c0).permute(0, 3, 1, 2)              # conv2.hip subsample_conv_cl_kernel: rows (b, f, t), channel-last
+            assert float(Q.mask_time(img, live1).sub(img).abs().sum()) == 0.0, "layer-1 image behind an utterance's own frames is not zero"
+            rows = lambda x: own(Q.feature_rows(x), live1)
+            conv_stage("conv", rows(img), lambda dt: rows(Q.front_conv(mel, mlen, sd, plan, dt)), 9, w9.abs(), bias.double().abs(), mel_own.double().abs().unsqueeze(1), rows)
+            sub = sub.reshape(B, t1r, K // c1, c1).transpose(2, 3).reshape(B, t1r, K)        # conv2_igemm_kernel writes (f2, c); the reference's order is c * F2 + f2
+            sub = own(sub)
+            w2, sc2, bias2 = Q.bn_fold2d(sd, 1, F32)
+            rows = lambda x: own(Q.feature_rows(x))
+            conv_stage("conv2", sub, lambda dt: rows(Q.front_conv2(img, sd, plan, dt)), 9 * c0, q(w2 * sc2[:, None, None, None]).double().abs(), bias2.double().abs(), img.double().abs(), rows)
+        l64, l32 = Q.front_linear(sub, sd, plan, F64), Q.front_linear(sub, sd, plan, F32)
+        rep.add("linear", 0, stage_ratios(gl, l64, l32, K, False), lambda: worst_element(gl, l64))
+        w_, b_ = q(torch.from_numpy(np.asarray(sd["linear.weight"])).double()), torch.from_numpy(np.asarray(sd["linear.bias"])).double()
+        cls = 2.0 * K * 2.0 ** -23 * (sub.double().abs() @ w_.abs().T + b_.abs())
+        rep.elementwise("linear", 0, "summation", (gl.double() - l64).abs(), cls + 1e-30, gl, l64)
+    else:
+        fe = lambda dt, cv: own(Q.front_end(mel, mlen, sd, plan, dt, conv=cv))
+        r64 = fe(F64, "fp32")
+        runs = {"fp32": f32_runs(lambda: fe(F32, "fp32"))}
+        if route["conv"] == "split":
+            runs["split"] = f32_runs(lambda: fe(F32, "split"))
+        pool = [r for v in runs.values() for r in v]
+        rep.add("front", 0, stage_ratios(gl, r64, pool, K, False), lambda: worst_element(gl, r64))
+        if plan.sub_layers == 1:
+            # the convolution's form leaves no trace entry: asserted through the data - the other form's float32 run must fit the GPU's numbers worse
+            if "split" not in runs:
+                runs["split"] = [fe(F32, "split")]
+            other = "fp32" if route["conv"] == "split" else "split"
+            fit, misfit = rel(gl, runs[route["conv"]][0])[1], rel(gl, runs[other][0])[1]
+            rep.form = (fit, misfit)
+            if not fit < misfit:
+                rep.fails.append("block 0 front route: expected the %s convolution, mean distance to its float32 run %.3g, to the other form's %.3g" % (route["conv"], fit, misfit))
+
+    # ---- block 0's first FFN: the chain head (chain.hip) / rs_gemm FFN on the front end's output
+    fold = chain_route(route["fuse_chain"], D0)
+    x1 = got["blocks.0.x_ffn1"]
+    assert x1.shape[0] == sp.rows, (x1.shape, sp.rows)
+    g1 = x1[sp.xidx]
+    pf = "blocks.0.feed_forward_module1"
+    f64, f32 = ffn(gl, sd, pf, F64, fold), f32_runs(lambda: ffn(gl, sd, pf, F32, fold))
+    rep.add("ffn1_0", 0, stage_ratios(g1, f64, f32, b0.dim_ffn1, False), lambda: worst_element(g1, f64))
+    return rep
+
+
 def check_trace(got, out_len, plan, sd, ln, tm, ragged, fuse, label):
     """Every stage of every block of one traced forward (``got``: trace name -> float tensor of (rows, columns)) against the reference computed
     from the trace's own inputs of that stage.  Returns the _Report (``finish`` prints the worst ratios and asserts).  ``fuse``: the fused chains
     are on (option fuse_chain), so the widths they support take the folded-LayerNorm route."""
     nb, B = len(plan.blocks), len(ln)
-    chained = lambda width: bool(fuse) and width % 4 == 0 and 16 <= width <= 256          # encoder.hip: chain_max_dim = 256; chain.hip chain_supported
+    chained = lambda width: chain_route(fuse, width)
     rep = _Report(label)
 
     # lengths and the row map of every block's input (and of the output)

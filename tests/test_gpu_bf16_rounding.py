@@ -24,7 +24,17 @@ per-module kernels (fuse_chain = 0 and Medium's D = 360 stage), attention.hip an
 always), one causal and one streaming configuration, synthetic and `trained` weights.  The Q / K / V and GLU route (folded or per-module) leaves no trace
 entry: it is asserted through the data (the other route's reference must fit worse; tests/bf16_parity.py).
 
-What the first runs found (measured before the fixes; all inside the un-rounded 0.02 / 0.003 tests): (1) `trained` profile, block 0 (stream mean 160,
+The front end and block 0's first FFN (tests/bf16_parity.py check_front, run by every case of both tests): where separate kernels write the subsampler's
+activation (`subsample`, `subsample1`) the convolution(s) and the Linear each from their own traced input - `conv` / `conv2`: the bf16 statistics plus element-wise
+one bf16 ulp + 2 K 2^-23 (sum |w| |p| + |b|) 1.1, `linear`: the float32 statistics plus the out-projection's summation bound; on the fused routes one stage
+mel -> `linear` (`front`) whose noise is the float32 runs of ref_bf16.front_end with the float32 convolution and, on sublinear2.hip / sublinear3.hip, with their split
+formula as well; `ffn1_0`: blocks.0.x_ffn1 from the traced `linear`.  The route is asserted (`subsample` present or absent; the convolution's form through the data).
+The second test walks the routes (Tiny, EfficientConformerCTC-Small with fuse_subsample 0 / 1 / 2 / 3, Medium with and without sub3_auto, Large with the fused kernel
+and with conv.hip + GEMM, the two-layer subsampler of ConformerCTC-Small / -Large; rectangular and ragged), the frame-tile edges (1, 2, 31, 32, 33, 127, 128, 129,
+257 output frames at both parities of the mel length; a 1-frame and a 3-frame utterance next to a 700-frame one) and the inputs (synth.silence_floor_mel on
+`trained` weights, whose calibrated BatchNorm folds to large taps and biases).  Its first run found every route inside every bound.
+
+What the first runs of the block stages found (measured before the fixes; all inside the un-rounded 0.02 / 0.003 tests): (1) `trained` profile, block 0 (stream mean 160,
 deviation 1): 8 % of the Q / K / V outputs and 2.4 % of the GLU outputs not the correctly rounded number, 2.1 - 2.6 x the share bound - the chains' LayerNorm
 variance summed the pad columns' (0 - mean)^2 and subtracted pad * mean^2 afterwards (chain.hip ln_stats; fixed by masking the pad pieces).  (2) `trained`
 profile, EfficientConformerCTC-Small: the matrix-pipe depthwise kernel up to 1.84 x the element-wise 2^-8 |r| + 2e-5 (bf16 hi + lo tap pairs on folded taps of
@@ -35,7 +45,7 @@ import pytest
 import torch
 
 from efficientconformer_amd import ModelCTC, named_config, synth
-from bf16_parity import check_trace
+from bf16_parity import _Report, check_front, check_trace, front_route
 from oracle import ref_bf16 as Q
 
 pytestmark = pytest.mark.gpu
@@ -103,4 +113,69 @@ def test_every_bf16_stage_vs_the_rounding_aware_reference(case):
     mel, ln = synth.make_mel(len(lens), plan.n_mels, tm, lens, seed=5021 + tm)
     out, out_len, got = enc.trace_forward_mel(torch.from_numpy(mel).cuda(), torch.from_numpy(ln).cuda(), arena_bytes=1 << 29)
     rep = check_trace(got, out_len.cpu().tolist(), plan, sd, ln, tm, ragged, opts.get("fuse_chain", 1), _id(case))
+    check_front(got, plan, sd, mel, ln, tm, ragged, front_route(plan, opts, ragged), rep)
+    rep.finish()
+
+
+# ------------------------------------------------------------------ the front end's routes and edges
+def _odd(t1):       # mel frames that give t1 output frames with the last patch's third column behind the end / inside
+    return 2 * t1 - 1
+
+
+def _even(t1):
+    return 2 * t1
+
+
+_EDGE_T1 = (257, 129, 128, 127, 33, 32, 31, 2, 1)
+_EDGE_A = [_even(t) if i % 2 == 0 else _odd(t) for i, t in enumerate(_EDGE_T1)]          # 514, 257, 256, 253, 66, 63, 62, 3, 1
+_EDGE_B = [_odd(t) if i % 2 == 0 else _even(t) for i, t in enumerate(_EDGE_T1)]          # 513, 258, 255, 254, 65, 64, 61, 4, 2
+_SHORT = [1400, 5, 1]                                                                    # 700 frames next to a 3-frame and a 1-frame utterance
+_M4 = [520, 401, 263, 97]
+_SM, _MD, _LG = "EfficientConformerCTCSmall", "EfficientConformerCTCMedium", "EfficientConformerCTCLarge"
+# name, mel frames, lengths, ragged, options, weight profile, mel ("mel": synth.make_mel, "floor": synth.silence_floor_mel)
+FRONT_CASES = (
+    # every route, rectangular and ragged, at a width it ships on (Tiny: 24 channels, a partly filled 32-channel block)
+    [("Tiny", 1201, _T12, rg, o, "synthetic", "mel") for rg in (False, True) for o in ({}, {"fuse_subsample": 3}, {"fuse_subsample": 1}, {"fuse_subsample": 0})]
+    + [(_SM, 700, _L4, rg, {"fuse_subsample": f}, "synthetic", "mel") for rg in (False, True) for f in (0, 1, 2, 3)]
+    + [(_MD, 520, _M4, rg, o, "synthetic", "mel") for rg in (False, True) for o in ({}, {"sub3_auto": 0})]
+    + [(_LG, 520, _M4, rg, o, "synthetic", "mel") for rg in (False, True) for o in ({}, {"fuse_subsample": 0})]
+    + [(n, 520, _M4, rg, {}, "synthetic", "mel") for rg in (False, True) for n in ("ConformerCTCSmall", "ConformerCTCLarge")]
+    # frame-tile edges: 1, 2, 31, 32, 33, 127, 128, 129 and 257 output frames per utterance, both parities of the mel length at every one
+    + [(_SM, max(e), e, True, {"fuse_subsample": f}, "synthetic", "mel") for e in (_EDGE_A, _EDGE_B) for f in (0, 2, 3)]
+    + [("Tiny", max(e), e, True, {}, "synthetic", "mel") for e in (_EDGE_A, _EDGE_B)]
+    + [(_LG, max(e), e, True, o, "synthetic", "mel") for e in (_EDGE_A, _EDGE_B) for o in ({}, {"fuse_subsample": 0})]
+    + [("ConformerCTCSmall", max(e), e, True, {}, "synthetic", "mel") for e in (_EDGE_A, _EDGE_B)]
+    + [(_SM, tm, [tm, tm - 7, 5], False, {"fuse_subsample": f}, "synthetic", "mel") for tm in (63, 65, 66, 257, 513) for f in (1, 2)]
+    + [(n, 1400, _SHORT, True, o, "synthetic", "mel") for n, o in (("Tiny", {}), (_SM, {}), (_SM, {"fuse_subsample": 3}), (_SM, {"fuse_subsample": 0}), (_LG, {}),
+                                                                 ("ConformerCTCSmall", {}))]
+    # inputs: silent runs at the log floor and loud frames; `trained` weights (calibrated BatchNorm: large folded taps and biases)
+    + [(_SM, 700, _L4, rg, {"fuse_subsample": f}, "trained", "floor") for rg in (False, True) for f in (0, 1, 2, 3)]
+    + [("Tiny", 700, _L4, True, {}, "trained", "floor"), (_MD, 520, _M4, False, {}, "trained", "floor"), (_LG, 520, _M4, True, {}, "trained", "floor"),
+       (_LG, 520, _M4, True, {"fuse_subsample": 0}, "trained", "floor"), ("ConformerCTCSmall", 520, _M4, False, {}, "trained", "floor"),
+       ("ConformerCTCSmall", 520, _M4, True, {}, "trained", "floor"), (_SM, 700, _L4, False, {}, "synthetic", "floor")]
+)
+
+
+def _fid(c):
+    return "-".join([c[0], "ragged" if c[3] else "rect", "T%d" % c[1], "L%d" % len(c[2])] + ["%s=%d" % kv for kv in sorted(c[4].items())] + [c[5], c[6]])
+
+
+@pytest.mark.parametrize("case", FRONT_CASES, ids=_fid)
+def test_front_end_routes_and_edges_vs_the_rounding_aware_reference(case):
+    """The front end (every route of run_subsample_linear and of forward_core's ragged branch, asserted) and block 0's first FFN against
+    ref_bf16.front_* / ffn (tests/bf16_parity.py check_front); on Tiny's twelve-utterance batch, where it is cheap, the block stages as well."""
+    name, tm, lens, ragged, opts, profile, kind = case
+    torch.set_num_threads(16)
+    m, sd = _model(name, profile, {})
+    enc, plan = m.encoder, m.encoder.plan
+    for k, v in opts.items():
+        enc.set_option(k, v)
+    enc.ragged = ragged
+    mel, ln = (synth.make_mel if kind == "mel" else synth.silence_floor_mel)(len(lens), plan.n_mels, tm, lens, seed=5021 + tm)
+    out, out_len, got = enc.trace_forward_mel(torch.from_numpy(mel).cuda(), torch.from_numpy(ln).cuda(), arena_bytes=1 << 29)
+    if name == "Tiny" and len(lens) == len(_T12):          # the block stages' share statistics need the rows of the twelve-utterance batch (see _T12)
+        rep = check_trace(got, out_len.cpu().tolist(), plan, sd, ln, tm, ragged, 1, _fid(case))
+    else:
+        rep = _Report(_fid(case))
+    check_front(got, plan, sd, mel, ln, tm, ragged, front_route(plan, opts, ragged), rep)
     rep.finish()

@@ -230,3 +230,199 @@ def test_the_bound_sees_every_injected_fault_and_passes_reference_and_controls()
         if not inside and not listed and not ratio > 1.0:
             bad.append((stage, blk, nme, width, ratio))
     assert not bad, bad
+
+
+# ------------------------------------------------------------------ the front end (ref_bf16.front_*) and block 0's first FFN
+from bf16_parity import _Report, check_front, chain_route          # noqa: E402
+
+
+@pytest.mark.parametrize("name,tm,lens", [("Tiny", 333, [333, 250, 97, 12]), ("EfficientConformerCTCSmall", 201, [201, 120, 3]),
+                                          ("ConformerCTCSmall", 150, [150, 97, 6])])
+def test_front_end_without_roundings_is_the_float64_oracle(name, tm, lens):
+    """rnd = ident, float64: front_end is ref_encoder's subsampler + Linear, and front_end + encoder_from_linear is ref_encoder.encoder_from_mel, to
+    float64 rounding, on one-layer and two-layer subsamplers.  Rectangular: the whole batch.  With lengths: the contract pads at the utterance's own
+    length, so every utterance's own frames equal the oracle run on that utterance alone, cut to its length."""
+    plan, sd, mel, ln = _setup(name, tm, lens)
+    with torch.no_grad():
+        want = {}
+        ref, _ = R.encoder_from_mel(mel, ln, sd, plan, want, dtype=F64)
+        x = Q.front_end(mel, None, sd, plan, F64, rnd=Q.ident)
+        assert Q.rel(x, want["linear"])[0] < 1e-12, Q.rel(x, want["linear"])
+        out = Q.encoder_from_linear(x, _lens_after_subsampling(plan, ln), sd, plan, F64, rnd=Q.ident)
+        assert Q.rel(out, ref)[0] < 1e-11, Q.rel(out, ref)
+        xl = Q.front_end(mel, ln, sd, plan, F64, rnd=Q.ident)
+        for b, n in enumerate(ln.tolist()):
+            alone = {}
+            ref_b, _ = R.encoder_from_mel(mel[b:b + 1, :, :n], None, sd, plan, alone, dtype=F64)
+            t1 = alone["linear"].shape[1]
+            assert t1 == int(_lens_after_subsampling(plan, ln)[b])
+            assert Q.rel(xl[b:b + 1, :t1], alone["linear"])[0] < 1e-12, (b, Q.rel(xl[b:b + 1, :t1], alone["linear"]))
+            out_b = Q.encoder_from_linear(xl[b:b + 1, :t1], None, sd, plan, F64, rnd=Q.ident)
+            assert Q.rel(out_b, ref_b)[0] < 1e-11, (b, Q.rel(out_b, ref_b))
+
+
+def _trunc16(x):
+    return (x.float().contiguous().view(torch.int32) & -65536).view(torch.float32)
+
+
+def _standin(mel, mlen, sd, plan, form, fold, fault=None, traced=False):
+    """A CPU stand-in of a correct front-end kernel + chain head in float32 arithmetic with the kernels' summation orders, not the noise runs': the
+    convolution tap by tap on the accumulator that starts at the bias (conv.hip) or, ``form = "split"``, three products per tap slot with the bias in
+    slot 9 (sublinear2.hip / sublinear3.hip); the Linear one output frequency after the other (the fused kernels' K order).  ``fault``: one of the
+    injected faults of FRONT_FAULTS.  Returns the trace check_front reads (rectangular layout; ``subsample`` if ``traced``)."""
+    assert plan.sub_layers == 1
+    mel = mel.float()
+    B, F, tm = mel.shape
+    if fault == "patch one mel frame late":
+        mel = torch.cat([mel[:, :, 1:], torch.zeros(B, F, 1)], 2)
+    x = Q.mask_time(mel, None if fault == "time padding at the batch's last frame" else mlen)
+    w, sc, bias = Q.bn_fold2d(sd, 0, F32, eps=0.0 if fault == "BatchNorm folded without eps" else R.BN_EPS)
+    w9 = (w * sc[:, None, None, None]).reshape(-1, 9)
+    if fault == "folded bias missing from tap slot 9":
+        bias = torch.zeros_like(bias)
+    C, F1, T1 = w9.shape[0], F // 2, (tm - 1) // 2 + 1
+    xp = torch.nn.functional.pad(x, (1, 2, 1, 2))
+    tap = lambda i, j: xp[:, i: i + 2 * F1: 2, j: j + 2 * T1: 2][:, None]                   # (B, 1, F1, T1)
+    if form == "fp32":
+        acc = bias[None, :, None, None].expand(B, C, F1, T1).clone()
+        for j in range(9):
+            acc = torch.addcmul(acc, w9[None, :, j, None, None], tap(j // 3, j % 3))
+    else:
+        whi, wlo = Q.split_hi_lo(torch.cat([w9, bias[:, None]], 1))
+        if fault == "lo tap plane dropped":
+            whi, wlo = Q.q(torch.cat([w9, bias[:, None]], 1)), torch.zeros_like(wlo)
+        acc = torch.zeros(B, C, F1, T1)
+        for j in reversed(range(10)):
+            p = tap(j // 3, j % 3) if j < 9 else torch.ones(B, 1, F1, T1)
+            phi, plo = Q.split_hi_lo(p)
+            cw = lambda v: v[None, :, j, None, None]
+            acc = acc + (cw(whi) * phi + (cw(whi) * plo + cw(wlo) * phi))
+    act = Q.swish(acc)
+    act = _trunc16(act) if fault == "activation truncated to bf16" else Q.q(act)
+    wq = Q.q(torch.from_numpy(np.asarray(sd["linear.weight"])).float()).reshape(-1, C, F1).clone()        # (D0, C, F1)
+    if fault == "K-slot swap in one 16-group":
+        wq[:, [5, 9], 3] = wq[:, [9, 5], 3].clone()
+    if fault == "stale 32-channel weight chunk":
+        c0 = 32 if C > 32 else 0
+        wq[:, c0: c0 + 32, 7] = wq[:, c0: c0 + 32, 6].clone()
+    rows = act.permute(0, 3, 1, 2).reshape(B * T1, C, F1)
+    if fault == "(c, f) order transposed in one channel block":
+        cb = min(C, 32)
+        rows = rows.clone()
+        rows[:, :cb] = rows[:, :cb].clone().reshape(-1, F1, cb).transpose(1, 2)
+    y = torch.from_numpy(np.asarray(sd["linear.bias"])).float()[None, :].expand(B * T1, -1).clone()
+    for f in range(F1):
+        y = y + rows[:, :, f] @ wq[:, :, f].T
+    got = {"linear": y}
+    if traced:
+        got["subsample"] = rows.reshape(B * T1, C * F1)
+    with Q.hardware_like(1):
+        got["blocks.0.x_ffn1"] = Q.ffn(y, sd, "blocks.0.feed_forward_module1", F32, fold != (fault == "FFN1 on the wrong LayerNorm route"))
+    return got
+
+
+def _ragged_layout(got, lens1, t1, g):
+    """The rectangular stand-in trace as the ragged row space lays it out: every utterance's own frames, then rows up to the group size (``subsample``: zeros; else a copy of a live row: finite)."""
+    out = {}
+    for k, v in got.items():
+        v = v.reshape(len(lens1), t1, -1)
+        pad = lambda b: torch.zeros_like(v[b, :1]) if k == "subsample" else v[b, :1]
+        out[k] = torch.cat([torch.cat([v[b, :n], pad(b).expand((n + g - 1) // g * g - n, -1)]) for b, n in enumerate(lens1)])
+    return out
+
+
+FRONT_FAULTS = ("K-slot swap in one 16-group", "stale 32-channel weight chunk", "(c, f) order transposed in one channel block", "lo tap plane dropped",
+                "folded bias missing from tap slot 9", "activation truncated to bf16", "patch one mel frame late", "time padding at the batch's last frame",
+                "BatchNorm folded without eps", "FFN1 on the wrong LayerNorm route")
+# (fault, convolution form, weight profile) the bound does not see, with the measured ratio printed by the test and recorded in DESIGN.md section 2b.
+# The eps changes a folded tap by 1e-5 / (2 var): 5e-6 of it on the synthetic weights (var ~ 1).  The split convolution's own dropped lo lo term is up to
+# 2^-14 = 6e-5 of a product, so on the routes whose noise model holds the split runs the fault is below the noise itself (0.24 - 0.25 x the bound, the
+# correct stand-in's own figure; no margin over the fp32 runs separates them either: the fault is at 40 - 62 x their mean noise, the correct split
+# stand-in at 48 - 76 x).  On the `trained` profile (calibrated BatchNorm, small variances) it is 1.7 x the bound, on the fp32 routes 2.2 - 11 x.
+FRONT_UNSEEN = {("BatchNorm folded without eps", "split", "synthetic")}
+
+
+def _front_over(rep):
+    return max([v for (s, st), (v, _) in rep.worst.items() if not st.startswith(("noise", "single"))] + [0.0])
+
+
+@pytest.mark.parametrize("profile", ["synthetic", "trained"])
+@pytest.mark.parametrize("name,tm,lens", [("Tiny", 259, [259, 130, 5, 1]), ("EfficientConformerCTCSmall", 259, [259, 130, 5])])
+def test_check_front_passes_stand_ins_and_sees_the_injected_faults(name, tm, lens, profile):
+    """check_front (the checker of the GPU test) on CPU stand-ins of the three kinds of route - separate kernels with the activation traced, fused with the
+    float32 convolution, fused with the split convolution - rectangular and ragged: the correct stand-ins pass, the route assertion tells the two
+    convolution forms apart, and every injected fault of FRONT_FAULTS fails the checker on every route it applies to, except what FRONT_UNSEEN lists
+    (reported with its ratio, not asserted)."""
+    plan, sd, mel, ln = _setup(name, tm, lens, profile)
+    if profile == "trained":
+        mel = torch.from_numpy(synth.silence_floor_mel(len(lens), plan.n_mels, tm, lens, seed=5021 + tm)[0])
+    b0 = plan.blocks[0]
+    fold = chain_route(1, b0.dim_model)
+    lens1, t1 = [(int(v) - 1) // 2 + 1 for v in ln], (tm - 1) // 2 + 1
+    routes = [("separate", "fp32", True, False), ("fused fp32", "fp32", False, False), ("fused split", "split", False, False), ("ragged split", "split", False, True),
+              ("ragged fp32", "fp32", False, True), ("ragged separate", "fp32", True, True)]
+    bad = []
+    with torch.no_grad():
+        for tag, form, traced, ragged in routes:
+            route = {"conv": form, "subsample": traced, "fuse_chain": 1}
+
+            def run(fault):
+                got = _standin(mel, ln if ragged else None, sd, plan, form, fold, fault, traced)
+                if ragged:
+                    got = _ragged_layout(got, lens1, t1, b0.group_size)
+                rep = _Report("%s %s %s" % (name, profile, tag))
+                check_front(got, plan, sd, mel, ln.tolist(), tm, ragged, route, rep)
+                return rep, _front_over(rep)
+            rep, over = run(None)
+            rep.finish()
+            print("%-28s %-9s %-13s %-46s ratio to the bound %10.3g  must stay inside; conv form fit / misfit %s" % (
+                name, profile, tag, "none (stand-in)", over, getattr(rep, "form", None)))
+            for fault in FRONT_FAULTS:
+                if (fault == "lo tap plane dropped" and form != "split") or (fault == "time padding at the batch's last frame" and not ragged):
+                    continue
+                rep, over = run(fault)
+                listed = (fault, form, profile) in FRONT_UNSEEN
+                print("%-28s %-9s %-13s %-46s ratio to the bound %10.3g  %s" % (name, profile, tag, fault, over, "NOT DETECTABLE here (listed)" if listed else "must exceed"))
+                if not listed and not (rep.fails or over > 1.0):
+                    bad.append((tag, fault, over))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("ragged", [False, True])
+def test_check_front_on_a_two_layer_reference_trace_and_two_faults(ragged):
+    """ConformerCTC-Small's two-layer subsampler: a trace made by the float32-arithmetic reference on the kernels' own float32 formulas, laid out as the
+    kernels lay it out (layer-1 image rows (b, f, t) channel-last and zero behind an utterance's own frames, layer-2 rows in (f2, c) order, both
+    rectangular; ``linear`` gathered into the ragged row space) passes every stage - conv, conv2, linear, ffn1_0; layer 2 left in the reference's
+    (c, f2) order, and layer-2 weights that missed their bf16 rounding, fail."""
+    name, tm, lens = "ConformerCTCSmall", 150, [150, 97, 6]
+    plan, sd, mel, ln = _setup(name, tm, lens)
+    b0, B = plan.blocks[0], len(lens)
+    half = lambda v: (v - 1) // 2 + 1
+    lens2, t2 = [half(half(v)) for v in lens], half(half(tm))
+    c1 = plan.sub_filters[1]
+
+    def trace(fault):
+        with torch.no_grad(), Q.hardware_like(1):
+            mlen = ln if ragged else None
+            a1 = Q.q(Q.front_conv(mel, mlen, sd, plan, F32))
+            if ragged:
+                a1 = Q.mask_time(a1, torch.tensor([half(v) for v in lens]))
+            a2 = Q.q(Q.front_conv2(a1, sd, plan, F32, rnd=Q.ident if fault == "weights" else Q.q))
+            got = {"subsample1": a1.permute(0, 2, 3, 1).reshape(-1, a1.shape[1])}
+            k = a2.shape[1] * a2.shape[2]
+            got["subsample"] = (a2.permute(0, 3, 1, 2) if fault == "order" else a2.permute(0, 3, 2, 1)).reshape(B * t2, k)
+            x = Q.front_linear(Q.feature_rows(a2), sd, plan, F32)
+            rest = {"linear": x.reshape(B * t2, -1), "blocks.0.x_ffn1": Q.ffn(x, sd, "blocks.0.feed_forward_module1", F32, True).reshape(B * t2, -1)}
+            got.update(_ragged_layout(rest, lens2, t2, b0.group_size) if ragged else rest)
+        return got
+    route = {"conv": "fp32", "subsample": True, "fuse_chain": 1}
+    for fault in (None, "order", "weights"):
+        rep = _Report("%s two-layer %s fault %s" % (name, "ragged" if ragged else "rect", fault))
+        with torch.no_grad():
+            check_front(trace(fault), plan, sd, mel, ln.tolist(), tm, ragged, route, rep)
+        print("two-layer %s fault %-8s ratio to the bound %.3g" % ("ragged" if ragged else "rect", fault, _front_over(rep)))
+        if fault is None:
+            rep.finish()
+        else:
+            # (the mis-ordered activation also disagrees with the ``linear`` this trace computed from the right one; conv and ffn1_0 stay inside)
+            assert any(f.startswith("block 0 conv2 ") for f in rep.fails) and all(f.startswith(("block 0 conv2 ", "block 0 linear ")) for f in rep.fails), rep.fails[:3]
