@@ -127,6 +127,16 @@ def build_plan(params: dict) -> EncoderPlan:
     stride = int(p.get("stride", 2))
     hop = int(p["sample_rate"] * p["hop_length_ms"]) // 1000
     win = int(p["sample_rate"] * p["win_length_ms"]) // 1000
+    # the front end's geometry, checked before anything is sized from it (csrc/encoder.hip: mel_config_error holds the same rules)
+    n_fft, n_mels = int(p["n_fft"]), int(p["n_mels"])
+    if n_fft != 512:
+        raise NotImplementedError("n_fft=%d: only n_fft = 512 is native" % n_fft)
+    if win <= 0 or win > n_fft:
+        raise ValueError("win_length_ms=%r gives win_length = %d samples: must be in 1..n_fft (%d)" % (p["win_length_ms"], win, n_fft))
+    if hop <= 0:
+        raise ValueError("hop_length_ms=%r gives hop_length = %d samples: must be >= 1" % (p["hop_length_ms"], hop))
+    if not 1 <= n_mels <= 128:
+        raise ValueError("n_mels=%d: must be in 1..128" % n_mels)
     layers = int(p["subsampling_layers"])
     filters = list(p["subsampling_filters"])
     plan = EncoderPlan(

@@ -323,9 +323,21 @@ const bf16_t* build_pos_table(EcEncoder* e, int max_pos, int D) {
     return upload(e, t);
 }
 
+// The front end's geometry: "" or the reason it cannot run, naming the field.  Checked by effconf_encoder_create and again in front of the tables:
+// win_length > n_fft would write the window in front of its vector, hop_length <= 0 divides by zero in every frame count.
+std::string mel_config_error(const EcConfig& c) {
+    if (c.n_fft != 512) return "n_fft = " + std::to_string(c.n_fft) + ": only n_fft = 512 is native";
+    if (c.win_length <= 0 || c.win_length > c.n_fft) return "win_length = " + std::to_string(c.win_length) + ": must be in 1..n_fft (" + std::to_string(c.n_fft) + ")";
+    if (c.hop_length <= 0) return "hop_length = " + std::to_string(c.hop_length) + ": must be >= 1";
+    if (c.n_mels < 1 || c.n_mels > 128) return "n_mels = " + std::to_string(c.n_mels) + ": must be in 1..128";
+    if (c.sample_rate < 2) return "sample_rate = " + std::to_string(c.sample_rate) + ": must be >= 2";
+    return "";
+}
+
 bool build_mel_tables(EcEncoder* e, std::string* err) {
     const EcConfig& c = e->cfg;
-    if (c.n_fft != 512) { *err = "only n_fft = 512 is native"; return false; }
+    *err = mel_config_error(c);
+    if (!err->empty()) return false;
     // Hann(win_length, periodic) centred in n_fft (torch.stft pads the window on both sides)
     std::vector<float> win(c.n_fft, 0.f);
     const int off = (c.n_fft - c.win_length) / 2;
@@ -1442,7 +1454,8 @@ EcEncoder* effconf_encoder_create(const EcConfig* cfg) {
     if (!cfg || cfg->num_blocks <= 0 || !cfg->blocks) { fail("null / empty config"); return nullptr; }
     if (cfg->sub_layers < 1 || cfg->sub_layers > 2) { fail("Conv2dSubsampling with 1 or 2 layers is native"); return nullptr; }
     if (cfg->sub_layers == 2 && (cfg->sub_filters[0] % 8 || cfg->sub_filters[1] % 8 || cfg->n_mels % 16)) { fail("two-layer subsampler needs filters % 8 == 0, n_mels % 16 == 0"); return nullptr; }
-    if (cfg->n_mels % 4 || cfg->n_mels > 128) { fail("n_mels must be a multiple of 4, <= 128"); return nullptr; }
+    { const std::string merr = mel_config_error(*cfg); if (!merr.empty()) { fail(merr); return nullptr; } }
+    if (cfg->n_mels % 4) { fail("n_mels = " + std::to_string(cfg->n_mels) + ": must be a multiple of 4 (16-byte rows of the mel image)"); return nullptr; }
     for (int i = 0; i < cfg->num_blocks; ++i) {
         const EcBlock& b = cfg->blocks[i];
         if (b.dim_model % 4 || b.dim_expand % 4 || b.kernel_size > 31 || !(b.kernel_size & 1) || !(b.group_size & 1) ||
@@ -2250,6 +2263,8 @@ int effconf_encoder_forward_ragged(EcEncoder* e, const float* x, const int64_t* 
 
 int effconf_mel_frontend(EcEncoder* e, const float* audio, int32_t batch, int32_t n_samples, float* mel, void* stream) {
     if (!e || !e->finalized) return fail("encoder not finalized");
+    if (!audio || !mel) return fail("mel_frontend: null argument");
+    if (batch > 0 && n_samples <= e->cfg.n_fft / 2) return fail("mel_frontend: n_samples must exceed n_fft / 2 (reflect padding)");
     const int Tm = n_samples / e->cfg.hop_length + 1;
     EC_TRY(launch_mel(audio, batch, n_samples, e->mel, e->cfg.n_fft, e->cfg.hop_length, e->cfg.n_mels, Tm,
                       e->cfg.normalize, e->cfg.mean, e->cfg.std, mel, (hipStream_t)stream));

@@ -520,12 +520,19 @@ class ConformerEncoder(nn.Module):
     # ------------------------------------------------------------------ test instrumentation
     def trace_forward_mel(self, mel: torch.Tensor, mel_len: torch.Tensor, arena_bytes: int = 1 << 28):
         """Run forward_mel with the debug trace enabled; returns (out, out_len, {name: tensor})."""
+        return self._trace_forward(self.forward_mel, mel, mel_len, arena_bytes)
+
+    def trace_forward(self, x: torch.Tensor, x_len: torch.Tensor, arena_bytes: int = 1 << 28):
+        """The same from audio: the trace then starts with "mel", the front end's image as rows (b, m) of the batch's frame pitch."""
+        return self._trace_forward(self.forward, x, x_len, arena_bytes)
+
+    def _trace_forward(self, fwd, mel: torch.Tensor, mel_len: torch.Tensor, arena_bytes: int):
         lib = _lib.load()
         self._ensure_packed()
         arena = torch.zeros(arena_bytes, dtype=torch.uint8, device=mel.device)
         _lib.check(lib.effconf_encoder_set_trace(self._handle, arena.data_ptr(), arena.numel()), "set_trace")
         try:
-            out, out_len, _ = self.forward_mel(mel, mel_len)
+            out, out_len, _ = fwd(mel, mel_len)
             torch.cuda.synchronize()
             res = {}
             name = C.create_string_buffer(64)

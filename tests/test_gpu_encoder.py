@@ -3,7 +3,7 @@ Runs on a real MI355X only (-m gpu).  Tolerances are for the bf16-operand / fp32
   * encoder output (LayerNorm-ed, O(1) values): max |err| <= 0.06, mean |err| <= 0.010 (round 4: 1.5x the worst measured 0.039 / 0.008; was 0.10 / 0.012)
   * greedy CTC labels: identical at every frame whose reference top-2 logit margin exceeds 0.15
     (random-weight logits have tiny margins; bf16 flips only frames inside that band)
-  * fp32 kernels (mel frontend, CTC head on identical input): 2e-4 abs / bit-exact labels.
+  * fp32 kernels (mel frontend on spectrally flat input, CTC head on identical input): 2e-4 abs / bit-exact labels.
 """
 import os
 
@@ -14,6 +14,7 @@ import torch
 from efficientconformer_amd import ModelCTC, named_config, synth
 from efficientconformer_amd.config import build_plan
 from oracle import ref_encoder as R
+from mel_ref import mel_fp64
 
 pytestmark = pytest.mark.gpu
 
@@ -117,6 +118,8 @@ def test_ctc_head_is_exact_fp32_and_collapse_bit_exact(golden_dir):
 
 
 def test_mel_frontend_vs_oracle():
+    """Against the oracle's torch.stft restatement on white noise of amplitude 0.1: the flat 4e-4 / 2e-6 is a statement about spectrally flat input
+    (both sides float32, each within 2e-4 of the float64 restatement THERE); tests/test_gpu_mel.py holds every other signal class."""
     m, _ = _model("Tiny", 7)
     lens = np.array([48000, 31337, 16000], dtype=np.int64)
     audio = synth.make_audio(lens, seed=11)
@@ -130,36 +133,15 @@ def test_mel_frontend_vs_oracle():
     assert torch.allclose(mel[2, :, 110:].cpu(), torch.full_like(mel[2, :, 110:].cpu(), float(np.log(np.float32(1e-9)))), atol=1e-5)
 
 
-def _mel_fp64(audio, n_fft=512, win=400, hop=160, n_mels=80, sr=16000):
-    """Independent float64 restatement of Spectrogram(power=2) + MelScale(htk, norm=None) + log(x + 1e-9): explicit framing,
-    numpy rfft in float64 (no torch.stft, no fp32 anywhere)."""
-    a = np.asarray(audio, dtype=np.float64)
-    pad = n_fft // 2
-    a = np.pad(a, ((0, 0), (pad, pad)), mode="reflect")
-    tm = (a.shape[1] - n_fft) // hop + 1
-    idx = np.arange(n_fft)[None, :] + hop * np.arange(tm)[:, None]
-    w = np.zeros(n_fft)
-    off = (n_fft - win) // 2
-    w[off:off + win] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win) / win)
-    spec = np.fft.rfft(a[:, idx] * w, axis=-1)
-    power = spec.real ** 2 + spec.imag ** 2                                   # (B, Tm, 257)
-    freqs = np.linspace(0.0, sr / 2, n_fft // 2 + 1)
-    mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)
-    m_pts = np.linspace(mel(0.0), mel(8000.0), n_mels + 2)
-    f_pts = 700.0 * (10.0 ** (m_pts / 2595.0) - 1.0)
-    down = (freqs[:, None] - f_pts[None, :-2]) / (f_pts[1:-1] - f_pts[:-2])[None, :]
-    up = (f_pts[None, 2:] - freqs[:, None]) / (f_pts[2:] - f_pts[1:-1])[None, :]
-    fb = np.maximum(0.0, np.minimum(down, up))                                # (257, n_mels)
-    return np.log(power @ fb + 1e-9).transpose(0, 2, 1)                       # (B, n_mels, Tm)
-
-
 def test_mel_frontend_vs_float64_dft():
-    """The mel kernel is all fp32: against an independent float64 DFT restatement it must hold 2e-4 abs in the log domain
-    (the fp32 oracle itself is within 2e-4 of the same float64 restatement: tests/test_oracle_golden.py)."""
+    """The mel kernel is all fp32: against an independent float64 DFT restatement (tests/mel_ref.py) it must hold 2e-4 abs in the log domain
+    ON SPECTRALLY FLAT INPUT - this white noise (the fp32 oracle itself is within 2e-4 of the same restatement there: tests/test_oracle_golden.py).
+    A flat number cannot hold for tones, steps or silence next to loud frames in any float32 front end; those are held to the energy-aware
+    per-element bound of tests/test_gpu_mel.py."""
     m, _ = _model("Tiny", 7)
     lens = np.array([48000, 31337, 16000, 2000], dtype=np.int64)
     audio = synth.make_audio(lens, seed=11)
-    ref = _mel_fp64(audio)
+    ref = mel_fp64(audio)
     mel, _ = m.encoder.mel_frontend(torch.from_numpy(audio).cuda(), torch.from_numpy(lens).cuda())
     d = np.abs(mel.cpu().numpy().astype(np.float64) - ref)
     print("mel vs float64 DFT: max %.2e mean %.2e" % (d.max(), d.mean()))

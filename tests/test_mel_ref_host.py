@@ -1,0 +1,215 @@
+"""Host checks of tests/mel_ref.py (no GPU): the float64 restatement equals the definitions it replaces, both float32 stand-ins sit inside the
+energy-aware bound on the whole signal zoo, every injected front-end fault is seen on at least one zoo class, and a front-end geometry that
+cannot run is refused by name in build_plan and through the C ABI."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import mel_ref as M
+from efficientconformer_amd import ModelCTC, _lib, named_config, synth
+from efficientconformer_amd.config import build_plan
+
+NORM = M.Settings(normalize=True, mean=M.SHIPPED_MEAN, std=M.SHIPPED_STD)
+HELD_OUT_SEEDS = (100, 101)
+
+
+def _old_mel_fp64(audio, n_fft=512, win=400, hop=160, n_mels=80, sr=16000):
+    """The restatement tests/test_gpu_encoder.py carried before it moved to mel_ref.py, kept verbatim as the yardstick of the move."""
+    a = np.asarray(audio, dtype=np.float64)
+    pad = n_fft // 2
+    a = np.pad(a, ((0, 0), (pad, pad)), mode="reflect")
+    tm = (a.shape[1] - n_fft) // hop + 1
+    idx = np.arange(n_fft)[None, :] + hop * np.arange(tm)[:, None]
+    w = np.zeros(n_fft)
+    off = (n_fft - win) // 2
+    w[off:off + win] = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win) / win)
+    spec = np.fft.rfft(a[:, idx] * w, axis=-1)
+    power = spec.real ** 2 + spec.imag ** 2
+    freqs = np.linspace(0.0, sr / 2, n_fft // 2 + 1)
+    mel = lambda f: 2595.0 * np.log10(1.0 + f / 700.0)
+    m_pts = np.linspace(mel(0.0), mel(8000.0), n_mels + 2)
+    f_pts = 700.0 * (10.0 ** (m_pts / 2595.0) - 1.0)
+    down = (freqs[:, None] - f_pts[None, :-2]) / (f_pts[1:-1] - f_pts[:-2])[None, :]
+    up = (f_pts[None, 2:] - freqs[:, None]) / (f_pts[2:] - f_pts[1:-1])[None, :]
+    fb = np.maximum(0.0, np.minimum(down, up))
+    return np.log(power @ fb + 1e-9).transpose(0, 2, 1)
+
+
+def test_restatement_with_defaults_equals_the_definitions_it_replaces():
+    lens = np.array([4000, 2560, 31337 % 5000 + 300], dtype=np.int64)
+    audio = synth.make_audio(lens, seed=9)
+    new = M.mel_fp64(audio)
+    assert new.shape == (3, 80, 26) and np.isfinite(new).all()
+    assert np.abs(new - _old_mel_fp64(audio)).max() < 1e-12
+    # the frame-by-frame definition of tests/test_oracle_golden.py::test_mel_frontend_against_independent_dft
+    win = np.zeros(512)
+    win[56:456] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(400) / 400)
+    fb = M.filterbank(512, 80, 16000)
+    for b in range(2):
+        xp = np.pad(audio[b].astype(np.float64), (256, 256), mode="reflect")
+        for t in (0, 1, 7, 16, 25):
+            ref = np.log(np.abs(np.fft.rfft(xp[t * 160:t * 160 + 512] * win)) ** 2 @ fb + 1e-9)
+            assert np.abs(new[b, :, t] - ref).max() < 1e-12
+    # per-utterance lengths: row b is the restatement of that utterance ALONE, and nothing exists past its own last frame
+    rag = M.mel_fp64(audio, lens)
+    for b, n in enumerate(lens.tolist()):
+        tb = n // 160 + 1
+        alone = M.mel_fp64(audio[b:b + 1, :n])
+        assert alone.shape[2] == tb and np.array_equal(rag[b, :, :tb], alone[0]) and np.isnan(rag[b, :, tb:]).all()
+    # other settings against the old function (it took n_fft / win / hop / n_mels / sr already)
+    for kw in (dict(win=320), dict(win=512), dict(hop=200), dict(n_mels=40), dict(n_mels=128), dict(sr=32000)):
+        assert np.abs(M.mel_fp64(audio, **kw) - _old_mel_fp64(audio, **kw)).max() < 1e-12, kw
+    z = M.mel_fp64(audio, normalize=True, mean=-5.6501, std=4.2280)
+    assert np.abs(z - (new + 5.6501) / 4.2280).max() < 1e-12
+    # 8 kHz: filters above Nyquist hold no bin, the definition gives the floor there
+    low = M.mel_fp64(audio, sr=8000)
+    dead = np.nonzero(M.filterbank(512, 80, 8000).sum(0) == 0)[0]
+    assert len(dead) > 10 and np.array_equal(low[:, dead], np.full_like(low[:, dead], np.log(1e-9)))
+
+
+def test_restatement_does_not_lean_on_stft_or_the_oracle():
+    import ast
+    tree = ast.parse(open(M.__file__).read())
+    names = {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute)} | {n.id for n in ast.walk(tree) if isinstance(n, ast.Name)}
+    imports = {a.name for n in ast.walk(tree) if isinstance(n, ast.Import) for a in n.names} | \
+              {n.module for n in ast.walk(tree) if isinstance(n, ast.ImportFrom)}
+    assert not names & {"stft", "istft", "ref_encoder", "mel_frontend", "mel_filterbank"}
+    assert imports <= {"__future__", "functools", "dataclasses", "typing", "numpy", "torch"}, imports
+
+
+def test_reference_refuses_what_it_cannot_frame_and_counts_every_element():
+    with pytest.raises(ValueError, match="n_fft / 2"):
+        M.mel_fp64(np.zeros((1, 256), dtype=np.float32))
+    audio, lens = M.make_signal("noise_0.1", 0)
+    ref = M.reference(audio, lens)
+    assert ref.valid.sum() == sum(n // 160 + 1 for n in lens.tolist())
+    got = np.where(np.isnan(ref.mel), 0.0, ref.mel)
+    assert M.ratios(got, ref)[0] == 0.0
+    bad = got.copy()
+    bad[2, 79, int(lens[2]) // 160] = np.nan           # one NaN in the last valid frame of the shortest row
+    assert M.ratios(bad, ref)[0] == np.inf
+    bad = got.copy()
+    bad[2, 0, int(lens[2]) // 160 + 1] = 7.0           # past the row's own last frame: not the kernel's to define, not compared
+    assert M.ratios(bad, ref)[0] == 0.0
+
+
+def test_zoo_puts_loud_frames_next_to_silent_partners_on_both_parities():
+    """The step classes are built from frame geometry: check against the frames themselves that the loud side is alone in its parity."""
+    for name, loud_parity in (("step_even_silent", 0), ("step_odd_silent", 1)):
+        audio, _ = M.make_signal(name, 0)
+        fr, _ = M.frames64(audio[:1])
+        e = np.sqrt((fr[0] ** 2).sum(-1))
+        t = np.arange(len(e))
+        quiet = e[(t % 4 == (1 if loud_parity == 0 else 0)) & (t > 1) & (t < len(e) - 2)]
+        loud = e[(t % 4 == (0 if loud_parity == 0 else 1)) & (t > 1) & (t < len(e) - 2)]
+        assert (quiet == 0).all() and loud.min() > 1.0, (name, quiet.max(), loud.min())
+    audio, lens = M.make_signal("ends_loud", 0)
+    fr, _ = M.frames64(audio)
+    e = np.sqrt((fr ** 2).sum(-1))
+    first_silent = [int(np.nonzero(e[b] == 0)[0][0]) for b in (1, 2)]
+    assert first_silent[0] % 2 == 0 and first_silent[1] % 2 == 1 and e[2, first_silent[1] - 1] > 0.01
+    assert [int(n) // 160 % 2 for n in lens[1:]] == [0, 1]          # ragged: an even (unpaired) and an odd last frame
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["rectangular", "ragged"])
+def test_both_standins_pass_the_bound_on_the_whole_zoo(ragged):
+    """The class constants come from CAL_SEEDS; on seeds they have not seen both stand-ins must sit inside the margins the kernel gets, and the
+    bound must have teeth: the stand-ins' own worst element uses more than 1 / 50 of it."""
+    lines = []
+    for name in M.ZOO:
+        const = M.class_constant(name, M.DEFAULT, ragged)
+        used = 0.0
+        for seed in HELD_OUT_SEEDS:
+            audio, ln, ref_p, ref_s = M.zoo_case(name, seed, M.DEFAULT, ragged)
+            for tag, fn, ref in (("single", M.standin_single, ref_s), ("paired", M.standin_paired, ref_p)):
+                v = M.verdict(fn(audio, ln), ref, const)
+                lines.append(M.report_line("%s/%s/seed%d" % (name, tag, seed), const, v))
+                assert v["ok"], lines[-1]
+                used = max(used, v["fill"])
+        assert used > 1.0 / 50.0, (name, used)
+    print("\n".join(lines))
+
+
+def _fault_run(fault, st):
+    paired = fault.startswith("pair_sign_leak")
+    seen, best = [], (0.0, None)
+    for name in M.ZOO:
+        audio, ln, ref_p, ref_s = M.zoo_case(name, 0, st, False)
+        got = (M.standin_paired if paired else M.standin_single)(audio, ln, st, fault=fault)
+        v = M.verdict(got, ref_p if paired else ref_s, M.class_constant(name, st, False))
+        if not v["ok"]:
+            seen.append(name)
+        if v["fill"] > best[0]:
+            best = (v["fill"], name)
+    return seen, best
+
+
+# faults the bound is NOT expected to see, with the reason; reported with their ratio like the bf16 host tests do
+# (a leak of 1e-7 - one eps32 - of the partner's amplitude is still seen, on the tones, the impulses and the loud ending, at 1.7x the bound)
+UNSEEN = {"pair_sign_leak_1e-8": "a leak below eps32 of the partner's amplitude is under the cross-talk the two-for-one transform has by design"}
+
+
+@pytest.mark.parametrize("fault", M.FAULTS + tuple(UNSEEN))
+def test_injected_fault_is_seen_on_at_least_one_zoo_class(fault):
+    st = NORM if fault in ("std_for_inv_std", "mean_dropped") else M.DEFAULT
+    seen, (worst, where) = _fault_run(fault, st)
+    print("fault %-26s seen on %2d of %d classes; worst use of the bound %.3g on %s; first: %s"
+          % (fault, len(seen), len(M.ZOO), worst, where, seen[:3]))
+    if fault in UNSEEN:
+        assert not seen, "the bound sees %s now (on %s): move it to the seen list" % (fault, seen)
+        print("UNSEEN %s: worst use of the bound %.3g on %s - %s" % (fault, worst, where, UNSEEN[fault]))
+    else:
+        assert seen, "no zoo class sees %s: worst use of the bound %.3g on %s" % (fault, worst, where)
+
+
+def test_silent_frame_fault_is_seen_where_the_partner_is_loud():
+    """The class built for it: a stand-in whose all-zero frames read 1e-2 off the floor fails on the silent partners of loud frames."""
+    for name in ("step_even_silent", "step_odd_silent", "ends_loud"):
+        audio, ln, ref_p, _ = M.zoo_case(name, 0, M.DEFAULT, False)
+        v = M.verdict(M.standin_paired(audio, ln, fault="silent_frame_1e-2_off"), ref_p, M.class_constant(name))
+        assert not v["ok"], name
+
+
+# ------------------------------------------------------------------------------------------------------------------ config validation
+def _params(**kw):
+    p = dict(named_config("Tiny")["encoder_params"])
+    p.update(kw)
+    return p
+
+
+@pytest.mark.parametrize("kw,field", [(dict(win_length_ms=33), "win_length"), (dict(win_length_ms=0), "win_length"), (dict(win_length_ms=-25), "win_length"),
+                                      (dict(hop_length_ms=0), "hop_length"), (dict(hop_length_ms=0.05), "hop_length"), (dict(hop_length_ms=-10), "hop_length"),
+                                      (dict(n_mels=0), "n_mels"), (dict(n_mels=129), "n_mels"), (dict(n_mels=-80), "n_mels"), (dict(n_fft=1024), "n_fft")])
+def test_build_plan_refuses_a_front_end_that_cannot_run_and_names_the_field(kw, field):
+    with pytest.raises((ValueError, NotImplementedError), match=field):
+        build_plan(_params(**kw))
+
+
+def test_build_plan_accepts_the_front_end_settings_the_kernel_runs():
+    for kw in (dict(win_length_ms=32), dict(win_length_ms=20), dict(hop_length_ms=5), dict(hop_length_ms=12.5), dict(n_mels=40), dict(n_mels=128),
+               dict(n_mels=1), dict(sample_rate=8000), dict(sample_rate=32000, win_length_ms=10, hop_length_ms=5), dict(normalize=True)):
+        plan = build_plan(_params(**kw))
+        assert 0 < plan.win_length <= plan.n_fft and plan.hop_length > 0 and 1 <= plan.n_mels <= 128, kw
+
+
+@pytest.mark.parametrize("kw,field", [(dict(win_length=513), b"win_length"), (dict(win_length=0), b"win_length"), (dict(win_length=-400), b"win_length"),
+                                      (dict(hop_length=0), b"hop_length"), (dict(hop_length=-160), b"hop_length"),
+                                      (dict(n_mels=0), b"n_mels"), (dict(n_mels=132), b"n_mels"), (dict(n_mels=-4), b"n_mels"),
+                                      (dict(n_mels=81), b"n_mels"), (dict(n_mels=65), b"n_mels"), (dict(n_fft=256), b"n_fft")])
+def test_library_refuses_the_same_settings_through_the_abi_before_any_table_is_built(kw, field):
+    """effconf_encoder_create holds the rules of build_mel_tables (one function, csrc/encoder.hip: mel_config_error): a caller of the C ABI that never
+    went through build_plan gets no handle and an error string naming the field - win_length > n_fft used to write in front of a host vector."""
+    lib = _lib.load()
+    cfg, _keep = ModelCTC.from_config(named_config("Tiny")).encoder._make_config()
+    h = lib.effconf_encoder_create(ctypes.byref(cfg))
+    assert h, lib.effconf_last_error()
+    lib.effconf_encoder_destroy(h)
+    for k, v in kw.items():
+        setattr(cfg, k, v)
+    h = lib.effconf_encoder_create(ctypes.byref(cfg))
+    if h:
+        lib.effconf_encoder_destroy(h)
+    assert not h, kw
+    assert field in lib.effconf_last_error(), lib.effconf_last_error()
