@@ -178,6 +178,15 @@ class ConformerEncoder(nn.Module):
         else:
             self._packed = False
 
+    @property
+    def frame_seconds(self) -> float:
+        """Seconds of audio per encoder output frame: the mel hop times the subsampling (2 per layer) times the stride of every strided
+        block (0.08 for the Efficient Conformers, 0.04 for ConformerCTC)."""
+        f = float(self.params["hop_length_ms"]) / 1000.0 * 2 ** self.plan.sub_layers
+        for b in self.plan.blocks:
+            f *= b.conv_stride
+        return f
+
     def _param_device(self):
         return self.linear.weight.device
 

@@ -7,12 +7,15 @@
 ``beam_search_decoding`` (model_ctc.py:138-181) is ctcdecode's CTC prefix beam search without the n-gram scorer: the head's
 fp32 logits go to one persistent HIP kernel per batch (effconf_ctc_beam, one workgroup per utterance) instead of a host copy and
 8 CPU processes.  The n-gram (KenLM) terms (``ngram_path``, ``ngram_alpha``, ``ngram_beta``), neural-LM fusion, probability
-cutoffs below the shipped ones and per-token timesteps are not implemented.  Training (losses, optimizer, schedules) and WER
-scoring are out of scope (HISTORY.md).
+cutoffs below the shipped ones are not implemented.  Token timestamps and transcript scores come from the forced alignment instead:
+``align`` / ``greedy_alignment`` (Viterbi over the CTC trellis: which frames each token covers) and ``score_labels`` (the CTC forward
+algorithm: log P(y | x), -ctc_loss without the host copy) run on the same logits in csrc/ctc_align.hip (effconf_ctc_align).  Training
+(losses with gradients, optimizer, schedules), WER scoring and word-level (SentencePiece-merging) timestamps are out of scope (HISTORY.md).
 """
 from __future__ import annotations
 
-from typing import List, Optional
+import os
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -21,6 +24,22 @@ import torch.nn as nn
 from . import _lib
 from .config import load_config
 from .encoders import ConformerEncoder
+
+
+class Alignment(NamedTuple):
+    """Forced alignment of one utterance (``ModelCTC.align``): token u covers the encoder frames start_frame[u] .. end_frame[u] - 1, i.e. the
+    seconds start_time[u] .. end_time[u] (frame x ``ConformerEncoder.frame_seconds``); token_logp[u] is the log-probability summed over these
+    frames, ``score`` the log-probability of the whole best path, ``log_likelihood`` log P(tokens | audio) over all paths.  status: 0 ok,
+    1 too few frames for the tokens, 2 a token id outside 1 .. vocab - 1 (then the spans are -1 and both scores -inf)."""
+    tokens: List[int]
+    start_frame: List[int]
+    end_frame: List[int]
+    start_time: List[float]
+    end_time: List[float]
+    token_logp: List[float]
+    score: float
+    log_likelihood: float
+    status: int
 
 
 class ModelCTC(nn.Module):
@@ -229,3 +248,119 @@ class ModelCTC(nn.Module):
         decoding_params are ignored."""
         ids = self.beam_labels(x, x_len, beam_size)
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
+
+    # ------------------------------------------------------------------ forced alignment, transcript scoring
+    def _targets(self, y, y_len, device):
+        """(targets (B, U) i32, target_len (B,) i64) on `device` from a padded integer tensor + lengths, a list of id lists, or a list of
+        strings (needs a tokenizer).  A list is padded on the host and copied once."""
+        if isinstance(y, torch.Tensor):
+            if y.dim() != 2:
+                raise _lib.EffconfError("targets must be (batch, tokens); got shape %s" % (tuple(y.shape),))
+            tg = y.to(device=device, dtype=torch.int32).contiguous()
+            if y_len is None:
+                y_len = torch.full((y.shape[0],), y.shape[1], dtype=torch.int64)
+            return tg, torch.as_tensor(y_len).to(device=device, dtype=torch.int64).contiguous()
+        rows = [[int(c) for c in r] for r in self._ids(y)]
+        lens = [len(r) for r in rows] if y_len is None else [int(v) for v in (y_len.tolist() if hasattr(y_len, "tolist") else y_len)]
+        host = np.zeros((len(rows), max([len(r) for r in rows] + [0])), dtype=np.int32)
+        for i, r in enumerate(rows):
+            host[i, :len(r)] = r
+        return torch.from_numpy(host).to(device), torch.tensor(lens, dtype=torch.int64).to(device)
+
+    def _ids(self, y):
+        """Strings -> id lists through the tokenizer; anything else as it is."""
+        if not isinstance(y, torch.Tensor) and len(y) and isinstance(y[0], str):
+            if self.tokenizer is None:
+                raise _lib.EffconfError("string targets need a tokenizer (tokenizer.encode)")
+            return [self.tokenizer.encode(r) for r in y]
+        return y
+
+    def align_logits(self, logits: torch.Tensor, logits_len: Optional[torch.Tensor], targets, target_len=None, scores_only: bool = False):
+        """Forced alignment of head logits (B, T, V) fp32 to `targets` ((B, U) integers + `target_len`, or a list of id lists) on the GPU
+        (effconf_ctc_align), temperature ``self.tmp`` -> dict of device tensors: ``log_likelihood`` (B,) f32 = log P(target | logits),
+        ``status`` (B,) i32 and, unless `scores_only`, ``score`` (B,) f32 = log-probability of the best path, ``frame_token`` (B, T) i32
+        (target index per frame, -1 blank / beyond the length), ``token_start`` / ``token_end`` (B, U) i32 (first frame, last frame + 1) and
+        ``token_logp`` (B, U) f32.  include/effconf.h has the details."""
+        if logits.dim() != 3:
+            raise _lib.EffconfError("logits must be (batch, frames, vocab); got shape %s" % (tuple(logits.shape),))
+        b, t, v = logits.shape
+        if not 2 <= v <= 1024:
+            raise _lib.EffconfError("vocab_size must be in 2 .. 1024 for the CTC alignment; got %d" % v)
+        if not 0 < self.tmp < float("inf"):
+            raise _lib.EffconfError("decoding_params['tmp'] must be > 0; got %r" % (self.tmp,))
+        if not logits.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        dev = logits.device
+        tg, tl = self._targets(targets, target_len, dev)
+        if tg.shape[0] != b or tl.shape[0] != b:
+            raise _lib.EffconfError("targets: %d rows for %d utterances" % (tg.shape[0], b))
+        u = int(tg.shape[1])
+        if u > 2047:
+            raise _lib.EffconfError("at most 2047 target tokens per utterance; got %d" % u)
+        lib = _lib.load()
+        nbytes = int(lib.effconf_ctc_align_workspace_bytes(b, t, v, u))
+        if nbytes == 0:
+            raise _lib.EffconfError("effconf_ctc_align_workspace_bytes rejected (batch %d, T %d, vocab %d, U %d): %s"
+                                    % (b, t, v, u, lib.effconf_last_error().decode()))
+        with torch.cuda.device(dev):
+            logits = logits.contiguous().float()
+            if logits_len is None:
+                logits_len = torch.full((b,), t, dtype=torch.int64, device=dev)
+            logits_len = logits_len.to(device=dev, dtype=torch.int64).contiguous()
+            out = {"log_likelihood": torch.empty(b, dtype=torch.float32, device=dev), "status": torch.empty(b, dtype=torch.int32, device=dev)}
+            if not scores_only:
+                out["score"] = torch.empty(b, dtype=torch.float32, device=dev)
+                out["frame_token"] = torch.empty(b, t, dtype=torch.int32, device=dev)
+                out["token_start"] = torch.empty(b, u, dtype=torch.int32, device=dev)
+                out["token_end"] = torch.empty(b, u, dtype=torch.int32, device=dev)
+                out["token_logp"] = torch.empty(b, u, dtype=torch.float32, device=dev)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            fill = os.environ.get("EFFCONF_POISON_WORKSPACE", "")
+            if fill:                # test hook (include/effconf.h): the byte a fresh workspace is filled with
+                ws.fill_(int(fill))
+            ptr = lambda k: out[k].data_ptr() if k in out else None
+            _lib.check(lib.effconf_ctc_align(logits.data_ptr(), logits_len.data_ptr(), b, t, v, tg.data_ptr(), tl.data_ptr(), u, float(self.tmp),
+                                             ptr("log_likelihood"), ptr("score"), ptr("status"), ptr("frame_token"), ptr("token_start"),
+                                             ptr("token_end"), ptr("token_logp"), ws.data_ptr(), ws.numel(),
+                                             torch.cuda.current_stream(dev).cuda_stream), "ctc_align")
+        return out
+
+    def _logits(self, x, x_len, from_mel):
+        if not x.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        enc, enc_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+        return self._head(enc, enc_len, want_logits=True) + (enc_len,)
+
+    def _records(self, out, tg, tl) -> List[Alignment]:
+        fs = self.encoder.frame_seconds
+        host = {k: v.cpu() for k, v in out.items()}                     # one D2H copy per batch (per output tensor)
+        tg, tl = tg.cpu(), tl.cpu()
+        recs = []
+        for i in range(tg.shape[0]):
+            n = max(0, min(int(tl[i]), tg.shape[1]))
+            st, en = host["token_start"][i, :n].tolist(), host["token_end"][i, :n].tolist()
+            recs.append(Alignment(tg[i, :n].tolist(), st, en, [f * fs for f in st], [f * fs for f in en], host["token_logp"][i, :n].tolist(),
+                                  float(host["score"][i]), float(host["log_likelihood"][i]), int(host["status"][i])))
+        return recs
+
+    def align(self, x: torch.Tensor, x_len: Optional[torch.Tensor], y, y_len=None, from_mel: bool = False) -> List[Alignment]:
+        """Token timestamps of known transcripts: encoder, head logits, effconf_ctc_align -> one ``Alignment`` per utterance.  `y`: a padded
+        (B, U) integer tensor (+ `y_len`), a list of id lists, or a list of strings when a tokenizer is attached."""
+        y = self._ids(y)
+        logits, _, _, enc_len = self._logits(x, x_len, from_mel)
+        tg, tl = self._targets(y, y_len, logits.device)
+        return self._records(self.align_logits(logits, enc_len, tg, tl), tg, tl)
+
+    def score_labels(self, x: torch.Tensor, x_len: Optional[torch.Tensor], y, y_len=None, from_mel: bool = False) -> torch.Tensor:
+        """log P(y | x) of every utterance, (B,) fp32 on the device (-inf where the transcript cannot be aligned): the CTC forward algorithm
+        alone (no Viterbi pass, no backpointers), = -ctc_loss(log_softmax(logits / tmp)) without the copy of the logits to the host."""
+        y = self._ids(y)
+        logits, _, _, enc_len = self._logits(x, x_len, from_mel)
+        return self.align_logits(logits, enc_len, y, y_len, scores_only=True)["log_likelihood"]
+
+    def greedy_alignment(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_mel: bool = False) -> List[Alignment]:
+        """The greedy labels with their timestamps: ``align`` on the greedy labels of the same logits (one encoder pass, one head pass)."""
+        logits, labels, label_len, enc_len = self._logits(x, x_len, from_mel)
+        u = min(int(labels.shape[1]), 2047)
+        tg, tl = labels[:, :u].contiguous(), label_len.to(torch.int64)
+        return self._records(self.align_logits(logits, enc_len, tg, tl), tg, tl)

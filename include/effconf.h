@@ -162,6 +162,35 @@ int effconf_ctc_beam(const float* logits, const int64_t* out_len, int32_t batch,
                      float temperature, int32_t* tokens, int32_t* token_len, float* score, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* CTC forced alignment and transcript scoring: for every utterance the best alignment (Viterbi) of a given target to the frames and the
+ * total CTC log-likelihood log P(target | audio) (-torch.nn.functional.ctc_loss of the log_softmax), one trellis of t_out frames and
+ * 2 U + 1 states, blank 0.  logits dev f32 (batch, t_out, vocab), e.g. the logits output of effconf_ctc_greedy; per frame
+ * lp = log_softmax(logits / temperature) in fp32 (finite where the beam search's softmax().log() is -inf).  out_len dev i64 (batch), clamped
+ * to [0, t_out]; target_len dev i64 (batch), clamped to [0, u_max]; targets dev i32 (batch, u_max).  Frames at or beyond out_len and
+ * target slots at or beyond target_len are never read.  2 <= vocab <= 1024, 0 <= u_max <= 2047, temperature > 0.
+ * Outputs (dev): log_likelihood f32 (batch); score f32 (batch) = the sum of lp along the best path; status i32 (batch):
+ *   0 ok;  1 infeasible: out_len < U + (number of adjacent equal target pairs);  2 a target id outside 1 .. vocab - 1 (wins over 1).
+ *   With status 1 / 2 both scores are -inf, frame_token and the token spans are -1 and token_logp is 0.  out_len 0 with U 0 is ok: scores 0.
+ * frame_token i32 (batch, t_out): the target INDEX u emitted at frame t, -1 for a blank and at or beyond out_len; token_start / token_end
+ * i32 (batch, u_max): first frame and last frame + 1 of token u, -1 at or beyond target_len; token_logp f32 (batch, u_max): the sum of lp
+ * over the token's frames, 0 at or beyond target_len.  Ties: the smaller step wins (stay, +1, +2), the path ends in the last blank when both
+ * ends are equal.  frame_token, token_start, token_end and token_logp may each be NULL; when all four are NULL the Viterbi half is skipped
+ * (scoring only: score may be NULL and is not written; log_likelihood is bit-identical to the full call's).  An utterance's results do not
+ * depend on the batch, on t_out / u_max beyond its own lengths, or on the run.
+ * Workspace (effconf_ctc_align_workspace_bytes; the library aligns the pointer up to 256 bytes; al(x) = x rounded up to 256):
+ *   [0, al(4 batch t_out (u_max + 1)))   f32 emit[batch][t_out][u_max + 1]: lp[blank], lp[target[0]], ... of every frame below out_len
+ *   + al(4 batch t_out)                  i32 path[batch][t_out]: the state (2 u + 1: token u, even: a blank) of the best path per frame
+ *   + batch * al(t_out R)                backpointers of utterances too long for LDS: per frame 64 w ceil(n / 4) bytes, n = ceil((2 U + 1) / 256)
+ *                                        states per thread, w = ceil((2 U + 1) / (64 n)) waves; thread i's byte j holds the steps (2 bits each,
+ *                                        0 stay / 1 / 2) into its states i n + 4 j .. i n + 4 j + 3;  R = 256 ceil(n_max / 4) with n_max =
+ *                                        ceil((2 u_max + 1) / 256) rounded up to a power of two
+ * effconf_ctc_align_workspace_bytes returns 0 for arguments effconf_ctc_align rejects. */
+size_t effconf_ctc_align_workspace_bytes(int32_t batch, int32_t t_out, int32_t vocab, int32_t u_max);
+int effconf_ctc_align(const float* logits, const int64_t* out_len, int32_t batch, int32_t t_out, int32_t vocab, const int32_t* targets,
+                      const int64_t* target_len, int32_t u_max, float temperature, float* log_likelihood, float* score, int32_t* status,
+                      int32_t* frame_token, int32_t* token_start, int32_t* token_end, float* token_logp, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* (Grouped)RelPosMultiHeadSelfAttention core alone (reference attentions.py:549-718 between the input projections and the output
  * projection): natural-layout bf16 device buffers qu = Q + u, k, v of (batch * Tp, dim) rows (Tp = frames rounded up to the group
  * size; pad rows: qu = u, k = v = 0), e = pos_layer(R) of (2 Tp - group, dim) rows, dvu = (v - u) per head column as fp32
