@@ -116,6 +116,7 @@ struct EcEncoder {
     int sub3_auto = 1;                       // with fuse_subsample = 2: front ends wider than 128 channels / columns on sublinear3.hip (0: sublinear2.hip / conv + GEMM as before round 6)
     int split_sublin = 1;                    // split mode: Conv2dSubsampling + Linear as one kernel (sxf_sub.hip) for the one-layer subsampler; 0 = conv kernel + GEMM [+ row gather] (tests)
     int split_ffn = 1;                       // split mode: the feed-forward modules as one kernel each (sxf_ffn.hip) where the width is built; 0 = LayerNorm + two GEMMs (tests)
+    bool trace_fused = false;                // split mode: a debug trace keeps the fused kernels (sxf_sub.hip, sxf_chain.hip) and records what THEY write; 0 = a trace selects the per-module kernels
     int exact_attention = 0;                 // fp32 mode: 0 tiled attention kernel (2: its 16-row shape), 1 one wave per query row (round 2's); bit-identical
     bool head_major_odd = false;             // odd grouped head widths on the head-major Q/K/V layout (tests; the default reads the natural layout unaligned)
     // two-layer subsampler (plain Conformer configs): layer-2 implicit-GEMM weight [N][9*Cp] (tap, c_in), folded bias, Cp
@@ -1237,8 +1238,9 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
     int Fl = c.n_mels, Cl = C0;
     int T1r = s.Tm; for (int i = 0; i < c.sub_layers; ++i) T1r = (T1r - 1) / 2 + 1;
     // one-layer subsampler: convolution + Swish + Linear as ONE kernel on the frames that exist (sxf_sub.hip) - the (frames, C F') activation stays in registers.
-    // A debug trace wants that activation ("subsample"): per-module kernels then
-    const bool sublin = e->split_sublin && e->xsub_wimg && c.sub_layers == 1 && !e->trace_arena;
+    // A debug trace wants that activation ("subsample"): per-module kernels then, unless option trace_fused keeps the forward as it runs untraced
+    const bool tr_modules = e->trace_arena && !e->trace_fused;
+    const bool sublin = e->split_sublin && e->xsub_wimg && c.sub_layers == 1 && !tr_modules;
     if (sublin) {
         const int D0 = e->blocks[0].dim_model;
         SxfSubParams sp{};
@@ -1270,6 +1272,7 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
         // x holds the rows already
     } else if (rg) {
         float* xrect = F32(w.xrect);
+        trace_add(e, st, "subsample", sub, (int64_t)B * T1r, Ksub, Ksub, 0);      // the rectangular image: rows (b, t) at the batch's pitch, zeros read behind an utterance's own mel frames
         EC_TRY(xgemm(e, st, sub, Ksub, B * T1r, "linear", D0, Ksub, xrect, D0));
         PROF(PC_MISC, 0, (double)s.Min[0] * D0 * 8);
         EC_TRY(launch_gather_rows(xrect, D0, T1r, rows_at(0), x, st));
@@ -1288,8 +1291,8 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
         return launch_layernorm(in, rows, dim, ln.g, ln.b, dst, nullptr, 0, nullptr, nullptr, st);
     };
     // the row-local work between attention and the depthwise convolution as two kernels per block (sxf_chain.hip); a debug trace wants the intermediate
-    // states, which the chains never write: per-module kernels then
-    const bool chains = e->split_chain && e->split_ffn && !e->trace_arena;
+    // states, which the chains never write: per-module kernels then (option trace_fused: the chains stay, and the trace holds what they write to memory)
+    const bool chains = e->split_chain && e->split_ffn && !tr_modules;
     bool head_done = false;                    // this block's FFN1 + Q / K / V projections ran at the end of the previous block's chain A
     for (int k = 0; k < nb; ++k) {
         const EcBlock& b = e->blocks[k];
@@ -1303,12 +1306,14 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
         const bool chain_in = chains && W.xc_in, chain_out = chains && W.xc_out;
         if (head_done) {
             // nothing: x is the stream after FFN1, Q / K / V are written
+            snprintf(nm, sizeof(nm), "blocks.%d.x_ffn1", k); trace_add(e, st, nm, x, M, D, D, 0);
         } else if (chain_in) {
             SxcAParams cp{};
             cp.head = 1; cp.y = x; cp.M = M; cp.D = D; cp.w_f1 = W.xc_f[0]; cp.nch_f1 = W.xf_nch[0]; cp.b_f1 = W.xf_b2[0]; cp.w_qkv = W.xc_qkv;
             cp.q = q; cp.qkv_stride = w.qkv_stride; cp.q_rows = qr; cp.q_pitch = qp; cp.qkv_bytes = (2 * w.qkv_stride + (size_t)s.Mq[k] * D) * 4;
             PROF(PC_GEMM_FFN, M * (double)D * D * (4.0 * b.ff_ratio + 6.0), (double)M * D * 24 + D * (double)D * (16.0 * b.ff_ratio + 12.0));
             EC_TRY(launch_sxc_a(cp, st));
+            snprintf(nm, sizeof(nm), "blocks.%d.x_ffn1", k); trace_add(e, st, nm, x, M, D, D, 0);
         } else {
         // ---- x += 1/2 FFN1(LN(x))   (blocks.py:122; modules.py:385-392): one kernel where the width is built (sxf_ffn.hip), else LayerNorm + two GEMMs
         if (W.xf_img[0] && e->split_ffn) {
@@ -1346,6 +1351,7 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
         uint16_t* epk = reinterpret_cast<uint16_t*>(ws + w.ep_blk[k]);
         if (!e_cached) {
             EC_TRY(xgemm(e, st, tab + (size_t)(b.max_pos - Tp + (c.causal ? 0 : G / 2)) * D, D, erows, m + ".mhsa.pos_layer", D, D, eb, D));
+            snprintf(nm, sizeof(nm), "blocks.%d.e", k); trace_add(e, st, nm, eb, erows, D, D, 0);      // the fp32 projection, before sxf_pack_e
             PROF(PC_MISC, 0, (double)erows * D * 8); EC_TRY(launch_sxf_pack_e(eb, W.u, W.v, erows / G, H, G, D, d, epk, st));
         }
         SxfAttnParams ap{};
@@ -1368,6 +1374,8 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
             cp.w_o = W.xc_wo; cp.b_o = W.xc_bo; cp.w_p1 = W.xc_p1; cp.nch_p1 = W.xc_nch_p1;
             PROF(PC_GEMM_OTHER, 2.0 * M * D * ((double)D + 2.0 * De), (double)M * (D * 12.0 + De * 4.0) + 4.0 * D * ((double)D + 2.0 * De));
             EC_TRY(launch_sxc_b(cp, st));
+            snprintf(nm, sizeof(nm), "blocks.%d.x_mhsa", k); trace_add(e, st, nm, x, M, D, D, 0);
+            snprintf(nm, sizeof(nm), "blocks.%d.glu", k); trace_add(e, st, nm, g, M, De, De, 0);
         } else {
         EC_TRY(xgemm(e, st, o, D, M, m + ".mhsa.output_layer", D, D, x, D, 2, x, 1.0f, qr, qp, 1));
         snprintf(nm, sizeof(nm), "blocks.%d.x_mhsa", k); trace_add(e, st, nm, x, M, D, D, 0);
@@ -1375,6 +1383,7 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
         EC_TRY(layernorm(x, M, D, W.ln_conv, a));
         EC_TRY(xgemm(e, st, a, D, M, cm + ".2", 2 * De, D, p1, 2 * De));
         { PROF(PC_MISC, 0, (double)M * De * 12); EC_TRY(launch_sxf_glu(p1, M, De, g, st)); }
+        snprintf(nm, sizeof(nm), "blocks.%d.glu", k); trace_add(e, st, nm, g, M, De, De, 0);
         }
         RaggedConv rc{};
         int tcap = To;
@@ -1393,6 +1402,7 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
                 EC_TRY(xgemm(e, st, x, D, Mo, p + ".conv_res.1", De, D, xalt, De, 0, nullptr, 1.f, To, T, b.conv_stride));
             }
             std::swap(x, xalt);
+            snprintf(nm, sizeof(nm), "blocks.%d.conv_res", k); trace_add(e, st, nm, x, Mo, De, De, 0);      // the residual rows chain A's tail / pointwise-2 adds to
         } else if (b.conv_stride > 1) {
             return fail("strided block without expansion is not native (no shipped config uses it)");
         }
@@ -1431,7 +1441,7 @@ int forward_core_split(EcEncoder* e, const float* mel, const int64_t* in_len, in
         }
         }
         if (!(k == nb - 1 && !rg)) std::swap(x, xalt);
-        snprintf(nm, sizeof(nm), "blocks.%d.out", k); trace_add(e, st, nm, xo, Mo, De, De, 0);
+        if (!head_done) { snprintf(nm, sizeof(nm), "blocks.%d.out", k); trace_add(e, st, nm, xo, Mo, De, De, 0); }      // a merged head has already made xo the next block's x_ffn1
     }
     if (!capturing && !e->trace_arena) e->e_cache_put(ws, B, e_tag, e_layout);
     if (rg) {
@@ -2558,6 +2568,7 @@ int effconf_encoder_set_option(EcEncoder* e, const char* name, int32_t value) {
     if (!strcmp(name, "split_sublin")) { e->split_sublin = value != 0; return 0; }
     if (!strcmp(name, "sub3_auto")) { e->sub3_auto = value != 0; return 0; }
     if (!strcmp(name, "split_chain")) { e->split_chain = value != 0; return 0; }
+    if (!strcmp(name, "trace_fused")) { e->trace_fused = value != 0; return 0; }
     if (!strcmp(name, "exact_attention")) { if (value < 0 || value > 2) return fail("exact_attention: 0 (tiled), 2 (tiled, 16-row workgroups) or 1 (one wave per query row)"); e->exact_attention = value; return 0; }
     if (!strcmp(name, "cache_pos_embeddings")) { e->e_cache_on = value != 0; e->e_cache.clear(); return 0; }
     if (!strcmp(name, "exact_fp32")) {

@@ -333,6 +333,10 @@ int effconf_rnnt_beam(EcRnnt* r, const float* enc_out, const int64_t* out_len, i
  * "split_chain" (default 1), "split_ffn" (default 1): split mode on the fused row-local kernels (csrc/sxf_chain.hip; csrc/sxf_ffn.hip when split_chain = 0);
  *   0 / 0 = LayerNorm, split GEMM, GLU kernels per module (tests: the same results within a few 1e-6, another summation order).  A debug trace
  *   (effconf_encoder_trace_*) runs the per-module kernels: the chains never write the intermediate states.
+ * "trace_fused" (default 0; tests): 1 = a debug trace of the split mode keeps the fused kernels an untraced forward runs (csrc/sxf_sub.hip, csrc/sxf_chain.hip;
+ *   the output is bit-identical to the untraced forward's) and records what THEY write to memory: "linear", per block "x_ffn1" (after a head launch or a merged
+ *   tail + head), "q" / "k" / "v" (Q without u; chunk-padding rows are never written), "e" (the fp32 positional projection), "att_o", "x_mhsa", "glu", "dw",
+ *   "conv_res" (transition blocks) and "out" only where no head is merged into chain A's tail.  "subsample" / "x_conv" exist on the per-module route only.
  * "split_sublin" (default 1; round 6, csrc/sxf_sub.hip): split mode, one-layer subsampler (the EfficientConformer configurations): Conv2d + BatchNorm + Swish + flatten
  *   + Linear as ONE kernel whose (frames, C F') activation stays in registers (the conv as a 16-tap MFMA product whose accumulators are the B fragments of the
  *   Linear's product), ragged batches on the frames that exist; 0 = fp32 VALU convolution + split GEMM (+ row gather) - the same results within a few 1e-6.

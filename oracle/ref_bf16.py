@@ -60,6 +60,9 @@ Conventions
 
 Masking, the relative-to-absolute gather, the streaming band and the sinusoid rows are oracle/ref_encoder.py's own code (relpos_scores,
 rel_sinusoid_rows, rel_sinusoid_rows_causal): this module adds roundings, nothing else.
+
+Two hooks serve the split mode's noise model (oracle/ref_split.py) and change nothing unless set: every matrix product of a stage goes through ``_mm``
+(``product_like``: another evaluation of a . w^T, e. g. fp16 operand pairs) and front_conv(conv="split") takes its operand splitters from ``_SPLIT_OPS``.
 """
 from __future__ import annotations
 
@@ -111,6 +114,40 @@ class hardware_like:
         _HW = self.prev
 
 
+_MM = None      # None: the plain product.  A function (a, w, kind) -> a . w^T: another evaluation of the same product (oracle/ref_split.py, noise models only)
+
+
+class product_like:
+    """``with product_like(fn):`` every matrix product of the stages below is evaluated by fn(a, w, kind) - a (..., K), w (N, K), ``kind`` the name of the
+    product ("ffn1", "ffn2", "qkv", "pw1", "pos", "out", "res", "pw2", "linear") - instead of a @ w.T.  oracle/ref_split.py: the split mode's operand pairs."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __enter__(self):
+        global _MM
+        self.prev, _MM = _MM, self.fn
+
+    def __exit__(self, *a):
+        global _MM
+        _MM = self.prev
+
+
+def _mm(a: torch.Tensor, w: torch.Tensor, kind: str) -> torch.Tensor:
+    return a @ w.T if _MM is None else _MM(a, w, kind)
+
+
+def _exp(x: torch.Tensor) -> torch.Tensor:
+    """exp of the softmax; under hardware_like(s) in float32: sx_common.h sx_expf (two-part x log2(e), exp2, first-order correction) moved by s ulps."""
+    if _HW is not None and x.dtype == torch.float32:
+        l2e, l2e_lo = 1.44269502162933349609375, 1.925963033500011e-08
+        t = x * l2e
+        c = (x.double() * l2e - t.double()).float() + x * l2e_lo          # fmaf(x, L2E, -t): the exact residual of the rounded product
+        e = torch.exp2(t) * (1.0 + _HW * 2.0 ** -23)
+        return e * (c * 0.693147180559945) + e
+    return torch.exp(x)
+
+
 def ln_plain(x: torch.Tensor) -> torch.Tensor:
     """(x - mean) * rstd, two-pass statistics, eps 1e-6 (chain.hip ln_stats)."""
     if _HW is not None and x.dtype == torch.float32:
@@ -129,13 +166,13 @@ def sigmoid(x: torch.Tensor) -> torch.Tensor:
     return torch.sigmoid(x)
 
 
-def ln_linear(x: torch.Tensor, sd, wkey: str, bkey: str, ln: str, dtype, folded: bool, rnd: Callable = q, conv1x1: bool = False) -> torch.Tensor:
+def ln_linear(x: torch.Tensor, sd, wkey: str, bkey: str, ln: str, dtype, folded: bool, rnd: Callable = q, conv1x1: bool = False, kind: str = "") -> torch.Tensor:
     """Linear(LayerNorm(x)) with the LayerNorm ``ln`` (.weight / .bias) folded into the weight (``folded``) or applied to the operand."""
     x = x.to(dtype)
     wsel = (lambda t: t[:, :, 0]) if conv1x1 else (lambda t: t)
     if rnd is ident:
         a = ln_plain(x) * _w(sd, ln + ".weight", dtype) + _w(sd, ln + ".bias", dtype)
-        return a @ wsel(_w(sd, wkey, dtype)).T + _w(sd, bkey, dtype)
+        return _mm(a, wsel(_w(sd, wkey, dtype)), kind) + _w(sd, bkey, dtype)
     w32, b32 = wsel(_w(sd, wkey, torch.float32)), _w(sd, bkey, torch.float32)
     g32, be32 = _w(sd, ln + ".weight", torch.float32), _w(sd, ln + ".bias", torch.float32)
     if folded:
@@ -146,7 +183,7 @@ def ln_linear(x: torch.Tensor, sd, wkey: str, bkey: str, ln: str, dtype, folded:
         w = rnd(w32.to(dtype))
         b = b32.to(dtype)
         a = rnd(ln_plain(x) * g32.to(dtype) + be32.to(dtype))
-    return a @ w.T + b
+    return _mm(a, w, kind) + b
 
 
 def swish(h):
@@ -157,7 +194,7 @@ def ffn(x: torch.Tensor, sd, prefix: str, dtype, folded: bool, rnd: Callable = q
     """x + 1/2 FFN(x) on float32 residual rows (..., D).  ``fault`` (tests only): a hook (name, value) -> replacement or None, called with
     "hidden" (swish(h) before its rounding -> the rounded hidden) and "product" ((hidden, q(W2 / 2), W2) -> hidden . W2^T)."""
     x = x.to(dtype)
-    h = ln_linear(x, sd, prefix + ".layers.1.weight", prefix + ".layers.1.bias", prefix + ".layers.0", dtype, folded, rnd)
+    h = ln_linear(x, sd, prefix + ".layers.1.weight", prefix + ".layers.1.bias", prefix + ".layers.0", dtype, folded, rnd, kind="ffn1")
     h = swish(h)
     hq = fault("hidden", h) if fault else None
     h = rnd(h) if hq is None else hq
@@ -165,7 +202,7 @@ def ffn(x: torch.Tensor, sd, prefix: str, dtype, folded: bool, rnd: Callable = q
     w2 = rnd(0.5 * w2raw)
     prod = fault("product", (h, w2, w2raw)) if fault else None
     if prod is None:
-        prod = h @ w2.T
+        prod = _mm(h, w2, "ffn2")
     return x + prod + 0.5 * _w(sd, prefix + ".layers.4.bias", dtype)
 
 
@@ -184,6 +221,9 @@ def split_hi_lo(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     x = x.float().contiguous()
     hi = (x.view(torch.int32) & -65536).view(torch.float32)
     return hi, q(x - hi)
+
+
+_SPLIT_OPS = None      # None: split_hi_lo for both operands of front_conv(conv="split").  (weight splitter, patch splitter): oracle/ref_split.py's fp16 pairs
 
 
 def mask_time(x: torch.Tensor, lens: Optional[torch.Tensor]) -> torch.Tensor:
@@ -215,7 +255,8 @@ def front_conv(mel: torch.Tensor, mel_len: Optional[torch.Tensor], sd, plan, dty
     pt = F.unfold(x.float(), 3, padding=1, stride=2)                                         # (B, 9, F1 * T1)
     pt = torch.cat([pt, torch.ones_like(pt[:, :1])], 1)                                      # slot 9: the bias's 1.0
     wt = torch.cat([w9.reshape(-1, 9), bias[:, None]], 1)                                    # (C, 10)
-    (whi, wlo), (phi, plo) = split_hi_lo(wt), split_hi_lo(pt)
+    wsplit, psplit = _SPLIT_OPS or (split_hi_lo, split_hi_lo)
+    (whi, wlo), (phi, plo) = wsplit(wt), psplit(pt)
     mm = lambda a, b: torch.einsum("cj,bjl->bcl", a.to(dtype), b.to(dtype))
     h = mm(whi, phi) + mm(whi, plo) + mm(wlo, phi)
     return swish(h.reshape(bsz, -1, (f - 1) // 2 + 1, (t - 1) // 2 + 1))
@@ -243,7 +284,7 @@ def feature_rows(act: torch.Tensor) -> torch.Tensor:
 
 def front_linear(act: torch.Tensor, sd, plan, dtype, rnd: Callable = q) -> torch.Tensor:
     """act (..., K): the STORED bf16 subsampler output in the reference's feature order -> act . q(W)^T + b, float32 rows (..., D0)."""
-    return act.to(dtype) @ rnd(_w(sd, "linear.weight", dtype)).T + _w(sd, "linear.bias", dtype)
+    return _mm(act.to(dtype), rnd(_w(sd, "linear.weight", dtype)), "linear") + _w(sd, "linear.bias", dtype)
 
 
 def front_end(mel: torch.Tensor, mel_len: Optional[torch.Tensor], sd, plan, dtype, rnd: Callable = q, conv: str = "fp32",
@@ -268,7 +309,7 @@ def qkv(x_ffn1: torch.Tensor, sd, bp, dtype, folded: bool, rnd: Callable = q) ->
     pm = "blocks.%d.multi_head_self_attention_module" % bp.index
     out = []
     for nm in ("query_layer", "key_layer", "value_layer"):
-        out.append(ln_linear(x_ffn1, sd, pm + ".mhsa." + nm + ".weight", pm + ".mhsa." + nm + ".bias", pm + ".norm", dtype, folded, rnd))
+        out.append(ln_linear(x_ffn1, sd, pm + ".mhsa." + nm + ".weight", pm + ".mhsa." + nm + ".bias", pm + ".norm", dtype, folded, rnd, kind="qkv"))
     return out[0] + _w(sd, pm + ".mhsa.u", dtype), out[1], out[2]
 
 
@@ -299,7 +340,7 @@ def pos_rows(tp: int, bp, dtype, causal: bool = False, rnd: Callable = q, shift:
 def pos_e(tp: int, sd, bp, dtype, causal: bool = False, rnd: Callable = q, shift: int = 0) -> torch.Tensor:
     """E before its bf16 store: q(rows) . q(Wpos)^T + bpos, (2Tp - G, D); causal (Tp, D)."""
     m = "blocks.%d.multi_head_self_attention_module.mhsa.pos_layer" % bp.index
-    return pos_rows(tp, bp, dtype, causal, rnd, shift) @ rnd(_w(sd, m + ".weight", dtype)).T + _w(sd, m + ".bias", dtype)
+    return _mm(pos_rows(tp, bp, dtype, causal, rnd, shift), rnd(_w(sd, m + ".weight", dtype)), "pos") + _w(sd, m + ".bias", dtype)
 
 
 def attention(qu: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: torch.Tensor, lens: Optional[torch.Tensor], t: int, sd, bp, dtype,
@@ -326,7 +367,7 @@ def attention(qu: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: torch.Tenso
     s = R.relpos_scores(qu, qv, k, e, ml, t, h, g, **ctx)
     tg, d = tp // g, g * dim // h
     vh = v.reshape(bsz, tg, h, d).transpose(1, 2)
-    pr = torch.exp(s - s.amax(-1, keepdim=True))
+    pr = _exp(s - s.amax(-1, keepdim=True))
     den = pr.sum(-1, keepdim=True)
     if round_p and rnd is not ident:
         pr = rnd(pr)
@@ -339,14 +380,14 @@ def attention(qu: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: torch.Tenso
 def out_proj(x_ffn1: torch.Tensor, att_o: torch.Tensor, sd, bp, dtype, rnd: Callable = q) -> torch.Tensor:
     """x_mhsa = x_ffn1 + att_o . q(Wo)^T + bo  (att_o: the stored bf16 attention output)."""
     m = "blocks.%d.multi_head_self_attention_module.mhsa.output_layer" % bp.index
-    return x_ffn1.to(dtype) + att_o.to(dtype) @ rnd(_w(sd, m + ".weight", dtype)).T + _w(sd, m + ".bias", dtype)
+    return x_ffn1.to(dtype) + _mm(att_o.to(dtype), rnd(_w(sd, m + ".weight", dtype)), "out") + _w(sd, m + ".bias", dtype)
 
 
 # ------------------------------------------------------------------ convolution side
 def glu(x_mhsa: torch.Tensor, sd, bp, dtype, folded: bool, rnd: Callable = q) -> torch.Tensor:
     """a * sigmoid(b) of the pointwise-1 product, before its bf16 store (..., De)."""
     p = "blocks.%d.convolution_module.layers" % bp.index
-    h = ln_linear(x_mhsa, sd, p + ".2.weight", p + ".2.bias", p + ".0", dtype, folded, rnd, conv1x1=True)
+    h = ln_linear(x_mhsa, sd, p + ".2.weight", p + ".2.bias", p + ".0", dtype, folded, rnd, conv1x1=True, kind="pw1")
     a, b = h.chunk(2, dim=-1)
     return a * sigmoid(b)
 
@@ -374,7 +415,7 @@ def conv_res(x_mhsa: torch.Tensor, sd, bp, dtype, rnd: Callable = q) -> torch.Te
     if not bp.transition:
         return x[:, ::bp.conv_stride]
     m = "blocks.%d.conv_res.1" % bp.index
-    return rnd(x[:, ::bp.conv_stride]) @ rnd(_w(sd, m + ".weight", dtype)[:, :, 0]).T + _w(sd, m + ".bias", dtype)
+    return _mm(rnd(x[:, ::bp.conv_stride]), rnd(_w(sd, m + ".weight", dtype)[:, :, 0]), "res") + _w(sd, m + ".bias", dtype)
 
 
 def chain_a(res: torch.Tensor, dw: torch.Tensor, sd, bp, next_bp, dtype, folded: bool, folded_next: Optional[bool] = None, rnd: Callable = q,
@@ -384,7 +425,7 @@ def chain_a(res: torch.Tensor, dw: torch.Tensor, sd, bp, next_bp, dtype, folded:
     ``fault`` (tests only): the hook of ``ffn`` for FFN2, also called with "ln_out" (the block LayerNorm's input -> its output)."""
     p = "blocks.%d" % bp.index
     c = p + ".convolution_module.layers.7"
-    x = res.to(dtype) + dw.to(dtype) @ rnd(_w(sd, c + ".weight", dtype)[:, :, 0]).T + _w(sd, c + ".bias", dtype)
+    x = res.to(dtype) + _mm(dw.to(dtype), rnd(_w(sd, c + ".weight", dtype)[:, :, 0]), "pw2") + _w(sd, c + ".bias", dtype)
     out = {"x_conv": x}
     x = ffn(x, sd, p + ".feed_forward_module2", dtype, folded, rnd, fault)
     y = fault("ln_out", x) if fault else None
