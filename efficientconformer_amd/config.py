@@ -127,7 +127,7 @@ def build_plan(params: dict) -> EncoderPlan:
     stride = int(p.get("stride", 2))
     hop = int(p["sample_rate"] * p["hop_length_ms"]) // 1000
     win = int(p["sample_rate"] * p["win_length_ms"]) // 1000
-    # the front end's geometry, checked before anything is sized from it (csrc/encoder.hip: mel_config_error holds the same rules)
+    # the front end's geometry, checked before anything is sized from it (csrc/pack.hip: mel_config_error holds the same rules)
     n_fft, n_mels = int(p["n_fft"]), int(p["n_mels"])
     if n_fft != 512:
         raise NotImplementedError("n_fft=%d: only n_fft = 512 is native" % n_fft)

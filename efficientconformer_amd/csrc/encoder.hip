@@ -1,11 +1,11 @@
-// libeffconf host side: weight packing, workspace layout, the encoder forward schedule and the C ABI
-// declared in include/effconf.h.  Everything the forward path does is "enqueue kernels on the
+// libeffconf host side: workspace layout, the encoder forward schedules and the C ABI declared in include/effconf.h (the handle's state:
+// encoder_state.h; weight packing: pack.h / pack.hip).  Everything the forward path does is "enqueue kernels on the
 // caller's stream": no allocation, no synchronisation, no host<->device copies (graph-capturable).
 //
 // The forward schedule follows ConformerEncoder.forward (reference models/encoders.py:97-142) and
 // ConformerBlock.forward (models/blocks.py:119-137); see DESIGN.md for the kernel map.
-#include "kernels.h"
-#include "../../include/effconf.h"
+#include "encoder_state.h"
+#include "pack.h"
 #ifdef EFFCONF_DEBUG_ABI
 #include "../../include/effconf_debug.h"
 #endif
@@ -21,10 +21,6 @@
 namespace {
 
 thread_local std::string g_err;
-int fail(const std::string& m) { g_err = m; return -1; }
-#define EC_TRY(expr) do { int _rc = (expr); if (_rc != 0) return fail(std::string(#expr) + " failed rc=" + std::to_string(_rc)); } while (0)
-
-inline int ld8(int d) { return ec_round_up(d, 8); }
 
 // Timing-only ablation build (tools/build_ablate.py: -DEFFCONF_ABLATE into a SEPARATE library, never the product): EFFCONF_SKIP = bit mask of kernel
 // families whose launches are dropped (1 attention, 2 chain A, 4 chain B, 8 depthwise conv, 16 mel, 32 subsampling, 64 glue) - what a family costs the
@@ -36,354 +32,37 @@ static int ablate_mask() { static const int m = getenv("EFFCONF_SKIP") ? atoi(ge
 #define EC_ABL(bit, stmt) do { stmt; } while (0)
 #endif
 
-uint16_t h_f2bf(float f) {
-    uint32_t u; memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
-
-struct PackedLinear { const bf16_t* w = nullptr; const float* bias = nullptr; int N = 0, K = 0, ldw = 0; std::vector<float> hbias; /* host copy of the padded bias */ };
-struct LNp { const float* g = nullptr; const float* b = nullptr; };
-
-struct BlockW {
-    LNp ln_ffn1, ln_att, ln_conv, ln_ffn2, ln_out;
-    PackedLinear ffn1_a, ffn1_b, qkv, qkv_nat, pos, outp, pw1, pw2, res, ffn2_a, ffn2_b;
-    const bf16_t *ffn1_bp = nullptr, *ffn2_bp = nullptr;   // W2 with the hidden index permuted per 16 (rsgemm.hip)
-    const float *u = nullptr, *v = nullptr, *dw_w = nullptr, *dw_b = nullptr;
-    const uint16_t* dw_a3 = nullptr;             // pack_dwconv_mfma3: third tap plane, only where the folded taps are large (finalize)
-    const uint16_t* dw_a = nullptr;              // pack_dwconv_mfma: Toeplitz rows of the depthwise taps for dwconv_mfma_kernel (stride-1 layers)
-    const float* dvu = nullptr; int dvu_ld = 0;   // (v - u) per head column [H][dvu_ld], zero beyond d (attention derives Q + v from Q + u)
-    const bf16_t* pos_table = nullptr;   // [2*max_pos-1][ld8(D)], row r <-> position max_pos-1-r
-    // fused row-local chains (chain.hip): every weight with its K index permuted per 16; FFN second weight / bias pre-scaled by 1/2
-    bool chain_in = false, chain_out = false;          // chain-packed weights exist for the D-wide / De-wide parts of the block
-    PackedLinear c_outp, c_pw1, c_pw2, c_qkv, c_f1a, c_f2a;
-    const bf16_t *c_f1b_cm = nullptr, *c_f2b_cm = nullptr;      // the same second weights chunk-major (chain3.hip, padded width 256 only): every 32-hidden-unit slab contiguous, in LDS slot order
-    const bf16_t *c_f1b = nullptr, *c_f2b = nullptr; const float *c_f1b2 = nullptr, *c_f2b2 = nullptr;
-    int c_qkv_chunks = 0, c_pw1_chunks = 0;
-    std::vector<float> h_ln_out_g, h_ln_out_b, h_u, h_v, h_f1b2, h_f2b2;     // host copies for the chains' constant blocks
-    // split mode (sxf_ffn.hip): weight images of the two feed-forward modules, b2 / 2, hidden chunks
-    const uint16_t *xf_img[2] = {nullptr, nullptr}; const float* xf_b2[2] = {nullptr, nullptr}; int xf_nch[2] = {0, 0};
-    // split mode (sxf_chain.hip): images in the accumulator layout's k order - out-proj / pointwise-2 (F2), pointwise-1 with GLU row pairs / Q | K | V (F1, pre-norm
-    // folded), the two feed-forward modules; biases of the F2 products
-    const uint16_t *xc_wo = nullptr, *xc_p1 = nullptr, *xc_p2 = nullptr, *xc_qkv = nullptr, *xc_f[2] = {nullptr, nullptr};
-    const float *xc_bo = nullptr, *xc_bp2 = nullptr; int xc_nch_p1 = 0;
-    bool xc_in = false, xc_out = false;          // the D-wide (out-proj, pointwise-1, FFN1, Q K V) / De-wide (pointwise-2, FFN2) images exist
-    const float *cc_b = nullptr, *cc_head = nullptr, *cc_tail = nullptr, *cc_full = nullptr;   // constant blocks (chain_const_layout)
-};
-
-struct TraceEntry { char name[64]; int64_t offset, rows, cols, ld; int32_t dtype; };
-struct ProfRec { int cls; double flops, bytes; };
-
 }  // namespace
 
-int ec_fail(const char* msg) { return fail(msg ? msg : "error"); }   // shared with rnnt.hip
+int ec_fail(const char* msg) { g_err = msg ? msg : "error"; return -1; }   // shared with pack.hip and rnnt.hip
 
-
-struct EcEncoder {
-    EcConfig cfg;
-    std::vector<EcBlock> blocks;
-    std::map<std::string, HostTensor> host;
-    bool finalized = false;
-    std::vector<void*> allocs;
-    int wide_gemm = 0;                    // option "wide_gemm": GemmParams::wide of every tiled GEMM (0 by shape, 1 never, 2 / 3 forced)
-    size_t guard_bytes = 0;               // EFFCONF_POISON_GUARDS (test hook): NaN-filled guard regions around every parameter buffer
-    // packed
-    const float *sub_w9 = nullptr, *sub_b = nullptr;
-    PackedLinear lin;
-    const bf16_t* lin_fused = nullptr; int lin_fused_ld = 0;   // Linear weight in the fused kernel's K order (sublinear.hip)
-    const uint16_t *sub3_cimg = nullptr, *sub3_wimg = nullptr; const float* sub3_bias = nullptr; int sub3_ncb = 0, sub3_fo = 0;   // sublinear3.hip (kernels.h: SubLin3Params)
-    const bf16_t* lin_rs = nullptr; const float* conv_tab = nullptr;   // sublinear2.hip: Linear weight [F/2][32 NT][32 CG] (K-permuted per 16), conv taps [32 CG][16]
-    int fuse_subsample = 2;                  // 0: separate conv + GEMM kernels, 1: sublinear.hip, 2: sublinear2.hip where it supports the shape (else 1; wide front ends: sublinear3.hip, option sub3_auto), 3: sublinear3.hip
-    bool fuse_chain = true;                  // row-local chains (chain.hip) where supported
-    int ctc_mfma = 2;                        // CTC head: 2 split-bf16 operands on the bf16 MFMA (bf16 path; fp32 mode falls back to 1), 1 fp32 MFMA (bit-identical to 0), 0 the VALU kernel
-    int attention_v2 = 1;                    // 0: attention.hip; 1 (default) / 2: attention2.hip variants where they support the head width (padded <= 160)
-    // tuning / test options that used to be process-global environment switches (effconf_encoder_set_option)
-    int chain_full_max = 192;
-    int dwconv_mfma = 1;                         // stride-1 depthwise convolutions on the matrix pipe (conv.hip dwconv_mfma_kernel): 1 = kernel size 15 (the Efficient Conformer
-                                                 // family), 2 = also 31 / 7 (equally accurate, profiles/r5_35_dw_accuracy.txt, but ConformerCTC-Small's 5-frame test utterance sits ON the
-                                                 // stated tolerance with either kernel and crosses it with this one's rounding: 0.0608 against 0.06), 0 = dwconv_kernel (VALU) everywhere
-    int chain_pair = 5;                      // 5: chain3.hip (chain A) / chain2.hip (chain B) at padded width 256 (D = 240: 147 -> 119 us per tail + head); 0: chain.hip everywhere (the reference the tests compare against)
-    int chain_small_m = 4096;                // chain launches of at most this many rows run as 2-wave workgroups (small-batch latency; bit-identical rows)
-    int chain_max_dim = 256;                 // fused chains only for stage widths <= this (tuning: wider stages on the per-GEMM / tiled kernels)
-    int tiled_auto = 1;                      // wide_gemm = 0: configurations whose widest stage lies in (tiled_min_k, 384] (EfficientConformer Medium: D = 360) send that stage to LayerNorm + the tiled
-                                             // GEMMs (+ 2.3 % on Medium, profiles/r6_100_*; neutral where wider stages exist - Large - which keep the row-stationary kernels there); 0 = as before round 6's last session
-    bool tiled_auto_on = false;              // the rule's outcome for this configuration (finalize)
-    int tiled_min_k = 256;                   // with wide_gemm >= 2: layers with K > this leave the row-stationary kernels for LayerNorm + tiled GEMMs
-    std::vector<float*> att_out;             // per block: device buffer [B][H][Tg][Tg] for the softmax maps of the next forward, or null
-    int split_chain = 1;                     // split mode: the row-local work of a block as two kernels (sxf_chain.hip) where the width is built; 0 = per-module kernels (tests)
-    int sub3_auto = 1;                       // with fuse_subsample = 2: front ends wider than 128 channels / columns on sublinear3.hip (0: sublinear2.hip / conv + GEMM as before round 6)
-    int split_sublin = 1;                    // split mode: Conv2dSubsampling + Linear as one kernel (sxf_sub.hip) for the one-layer subsampler; 0 = conv kernel + GEMM [+ row gather] (tests)
-    int split_ffn = 1;                       // split mode: the feed-forward modules as one kernel each (sxf_ffn.hip) where the width is built; 0 = LayerNorm + two GEMMs (tests)
-    bool trace_fused = false;                // split mode: a debug trace keeps the fused kernels (sxf_sub.hip, sxf_chain.hip) and records what THEY write; 0 = a trace selects the per-module kernels
-    int exact_attention = 0;                 // fp32 mode: 0 tiled attention kernel (2: its 16-row shape), 1 one wave per query row (round 2's); bit-identical
-    bool head_major_odd = false;             // odd grouped head widths on the head-major Q/K/V layout (tests; the default reads the natural layout unaligned)
-    // two-layer subsampler (plain Conformer configs): layer-2 implicit-GEMM weight [N][9*Cp] (tap, c_in), folded bias, Cp
-    const bf16_t* sub2_w = nullptr; const float* sub2_b = nullptr; int sub2_cp = 0;
-    std::vector<BlockW> bw;
-    const float *fc_wt = nullptr, *fc_b = nullptr;
-    const bf16_t *fc_hi = nullptr, *fc_lo = nullptr;      // fc.weight as split-bf16 MFMA B fragments (launch_ctc_split)
-    const int* block_stride = nullptr;
-    const int *block_group = nullptr, *block_heads = nullptr;     // ragged batches: attention group size / heads per block (device)
-    MelTables mel{};
-    // trace
-    char* trace_arena = nullptr; size_t trace_bytes = 0, trace_used = 0;
-    std::vector<TraceEntry> trace;
-    // positional-embedding cache: E = pos_layer(R) depends only on (block, T); when the caller keeps the SAME workspace
-    // untouched between forwards (opt-in), the 15-18 small E projections are skipped for an unchanged T
-    // One tag per workspace: callers that alternate workspaces (one per stream) keep every one of them warm.
-    bool e_cache_on = false;
-    struct ECacheTag { const void* ws; int batch, tm; size_t layout; };   // layout: offset of the first E buffer (ragged batches: it moves with the row totals)
-    std::vector<ECacheTag> e_cache;          // most recently used last; at most E_CACHE_MAX entries
-    static constexpr size_t E_CACHE_MAX = 16;
-    bool e_cache_hit(const void* ws, int batch, int tm, size_t layout) const {   // the workspace layout depends on (batch, tm) [+ the row totals]
-        for (const ECacheTag& t : e_cache) if (t.ws == ws) return t.batch == batch && t.tm == tm && t.layout == layout;
-        return false;
+const void* ec_upload(EcEncoder* e, const void* src, size_t used) {
+    if (e->dry) {
+        // dry run: hash (length, contents) instead of copying; the per-buffer hashes add up, so the digest does not depend on the order of the uploads
+        static const char nowhere[16] = {0};
+        const unsigned char* p = static_cast<const unsigned char*>(src);
+        uint64_t h = 0xcbf29ce484222325ull ^ used;
+        size_t i = 0;
+        for (; i + 8 <= used; i += 8) { uint64_t w; memcpy(&w, p + i, 8); h = (h ^ w) * 0x100000001b3ull; h ^= h >> 29; }
+        for (; i < used; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+        e->dry->sum += h * 0x9E3779B97F4A7C15ull + 1; e->dry->buffers += 1; e->dry->bytes += (int64_t)used;
+        return nowhere;
     }
-    void e_cache_put(const void* ws, int batch, int tm, size_t layout) {
-        e_cache_drop(ws);
-        if (e_cache.size() >= E_CACHE_MAX) e_cache.erase(e_cache.begin());
-        e_cache.push_back({ws, batch, tm, layout});
-    }
-    void e_cache_drop(const void* ws) {
-        for (size_t i = 0; i < e_cache.size(); ++i) if (e_cache[i].ws == ws) { e_cache.erase(e_cache.begin() + i); break; }
-    }
-    // fp32-operand "exact" mode (exact.hip): raw fp32 state-dict tensors on the device by key, fp32 sinusoid tables,
-    // per-layer BatchNorm scale / shift of the subsampling convs
-    bool exact_pack = false, exact_on = false;
-    // exact_fp32 = 2: the same schedule with every GEMM / the attention products on the fp16 matrix pipe with split operands (split.hip)
-    bool exact_split = false;
-    struct SplitW { const uint16_t *hi, *lo; int ldh; };
-    std::map<std::string, SplitW> xsplit;    // Linear / 1x1 conv weights by state-dict prefix (+ the stacked "...mhsa.qkv_layer")
-    std::map<std::string, const float*> xw;
-    std::map<std::pair<int, int>, const float*> xtab;
-    const float *xsub_scale[2] = {nullptr, nullptr}, *xsub_shift[2] = {nullptr, nullptr};
-    // split mode: images of the fused front end (sxf_sub.hip; kernels.h: SxfSubParams) - one-layer subsampler only
-    const uint16_t *xsub_cimg = nullptr, *xsub_wimg = nullptr; const float* xsub_bias = nullptr; int xsub_ncb = 0, xsub_fo = 0;
-    // per-launch event profiler (bench / tuning only; off by default)
-    bool prof_on = false;
-    std::vector<hipEvent_t> prof_ev;          // pairs
-    std::vector<ProfRec> prof_rec;
-    size_t prof_next = 0;
-};
-
-namespace {
-
-template <class T>
-const T* upload(EcEncoder* e, const std::vector<T>& v) {
     // guard > 0 (EFFCONF_POISON_GUARDS, a test hook read once at create): every parameter buffer sits between two guard regions of 0xFF
     // bytes (NaN as bf16 and as fp32), so a read past either end of a packed weight shows up in the output instead of depending on
     // what the allocator happened to place next to it
-    const size_t guard = e->guard_bytes, used = v.size() * sizeof(T);
+    const size_t guard = e->guard_bytes;
     void* d = nullptr;
     size_t bytes = std::max<size_t>((used + 15) / 16 * 16, 16);
     if (hipMalloc(&d, bytes + 2 * guard) != hipSuccess) return nullptr;
     e->allocs.push_back(d);
     char* base = static_cast<char*>(d) + guard;
     if (guard && (hipMemset(d, 0xFF, guard) != hipSuccess || hipMemset(base + used, 0xFF, bytes - used + guard) != hipSuccess)) return nullptr;
-    if (!v.empty() && hipMemcpy(base, v.data(), used, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return reinterpret_cast<const T*>(base);
+    if (used && hipMemcpy(base, src, used, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    return base;
 }
 
-const HostTensor* find(EcEncoder* e, const std::string& k) {
-    auto it = e->host.find(k);
-    return it == e->host.end() ? nullptr : &it->second;
-}
-
-// [N][K] fp32 (row-major, possibly a gather of rows given by `rows`) -> padded bf16 + padded bias
-// kperm: K index permuted inside every group of 16 (packed position 8h+e holds column 4h + 8(e>>2) + (e&3)): the B fragments of
-// chain.hip are LayerNorm-ed accumulator registers in MFMA C order
-// ln_g / ln_b: a LayerNorm in front of this linear layer folded in: W diag(gamma), b + W beta (fp32, before the bf16 rounding)
-bool pack_linear(EcEncoder* e, const std::vector<const float*>& row_ptr, const std::vector<float>& bias, int K, PackedLinear* out,
-                 bool kperm = false, const float* ln_g = nullptr, const float* ln_b = nullptr, int min_ldw = 0) {
-    const int N = (int)row_ptr.size();
-    const int Np = ec_round_up(N, 128), Kp = ec_round_up(K > min_ldw ? K : min_ldw, 64);
-    std::vector<uint16_t> w((size_t)Np * Kp, 0);
-    std::vector<float> b(Np, 0.f);
-    for (int n = 0; n < N && n < (int)bias.size(); ++n) b[n] = bias[n];
-    for (int n = 0; n < N; ++n) {
-        if (!row_ptr[n]) continue;
-        for (int k = 0; k < Kp; ++k) {
-            int src = k;
-            if (kperm) { const int g = k / 16, pp = k % 16, hh = pp >> 3, ee = pp & 7; src = g * 16 + 4 * hh + 8 * (ee >> 2) + (ee & 3); }
-            if (src < K) w[(size_t)n * Kp + k] = h_f2bf(row_ptr[n][src] * (ln_g ? ln_g[src] : 1.0f));
-        }
-        if (ln_b) {
-            double acc = 0.0;
-            for (int k = 0; k < K; ++k) acc += (double)row_ptr[n][k] * ln_b[k];
-            b[n] += (float)acc;
-        }
-    }
-    out->w = upload(e, w);
-    out->bias = upload(e, b);
-    out->hbias = b;
-    out->N = N; out->K = K; out->ldw = Kp;
-    return out->w && out->bias;
-}
-
-// min_ldw: row pitch floor in elements.  The whole-row kernels of rsgemm.hip (RS_F32 / RS_RESID) pick their k-step class from
-// max(K, N) and DMA that many columns of every weight row: an expanding layer (K < N) must be packed at least N wide, or the last
-// row's DMA runs past the buffer (found with EFFCONF_POISON_GUARDS: conv_res 180 -> 256 of EfficientConformer Medium)
-bool pack_named_linear(EcEncoder* e, const std::string& prefix, int N, int K, PackedLinear* out, std::string* err, bool kperm = false,
-                       const std::string& fold_ln = "", int min_ldw = 0) {
-    const HostTensor* w = find(e, prefix + ".weight");
-    const HostTensor* b = find(e, prefix + ".bias");
-    if (!w || !b) { *err = "missing tensor " + prefix + ".weight/.bias"; return false; }
-    if ((int64_t)w->data.size() != (int64_t)N * K || (int)b->data.size() != N) { *err = "shape mismatch for " + prefix; return false; }
-    std::vector<const float*> rows(N);
-    for (int n = 0; n < N; ++n) rows[n] = w->data.data() + (size_t)n * K;
-    const HostTensor *lg = fold_ln.empty() ? nullptr : find(e, fold_ln + ".weight"), *lb = fold_ln.empty() ? nullptr : find(e, fold_ln + ".bias");
-    if (!fold_ln.empty() && (!lg || !lb || (int)lg->data.size() != K || (int)lb->data.size() != K)) { *err = "missing LayerNorm " + fold_ln; return false; }
-    return pack_linear(e, rows, b->data, K, out, kperm, lg ? lg->data.data() : nullptr, lb ? lb->data.data() : nullptr, min_ldw);
-}
-
-// second FFN weight [D][F] with the hidden (K) index permuted inside every group of 16 so that the first GEMM's
-// accumulator registers are directly the second GEMM's B fragments: position 8h+e <-> 4h + 8(e>>2) + (e&3)
-const bf16_t* pack_ffn2_permuted(EcEncoder* e, const std::string& prefix, int D, int F, float scale = 1.0f) {
-    const HostTensor* w = find(e, prefix + ".weight");
-    if (!w || (int64_t)w->data.size() != (int64_t)D * F) return nullptr;
-    const int Np = ec_round_up(D, 128), Kp = ec_round_up(F, 64);
-    std::vector<uint16_t> out((size_t)Np * Kp, 0);
-    for (int n = 0; n < D; ++n)
-        for (int k = 0; k < Kp; ++k) {
-            const int g = k / 16, pp = k % 16, hh = pp >> 3, ee = pp & 7;
-            const int src = g * 16 + 4 * hh + 8 * (ee >> 2) + (ee & 3);
-            if (src < F) out[(size_t)n * Kp + k] = h_f2bf(scale * w->data[(size_t)n * F + src]);
-        }
-    return upload(e, out);
-}
-
-// The same weight chunk-major for chain2.hip: slab c (hidden units 32c .. 32c + 31 of all DP output rows, 64 B per row) is contiguous and already in
-// the LDS image's slot order (piece pc of row n at slot 4n + ((pc + (n >> 2)) & 3), rowstat.h dma_w2_off), so a wave-DMA reads 1 KiB of consecutive
-// bytes (row-major: sixteen 64-byte half lines per wave-DMA, the other half of every line belonging to the next slab)
-const bf16_t* pack_ffn2_chunkmajor(EcEncoder* e, const std::string& prefix, int D, int F, float scale, int DP) {
-    const HostTensor* w = find(e, prefix + ".weight");
-    if (!w || (int64_t)w->data.size() != (int64_t)D * F) return nullptr;
-    const int nch = ec_round_up(F, 32) / 32;
-    std::vector<uint16_t> out((size_t)nch * DP * 32, 0);
-    for (int c = 0; c < nch; ++c)
-        for (int n = 0; n < DP; ++n)
-            for (int pc = 0; pc < 4; ++pc) {
-                const int slot = 4 * n + ((pc + (n >> 2)) & 3);
-                for (int i = 0; i < 8; ++i) {
-                    const int k = 32 * c + 8 * pc + i;
-                    const int g = k / 16, pp = k % 16, hh = pp >> 3, ee = pp & 7;
-                    const int src = g * 16 + 4 * hh + 8 * (ee >> 2) + (ee & 3);
-                    if (n < D && src < F) out[((size_t)c * DP * 4 + slot) * 8 + i] = h_f2bf(scale * w->data[(size_t)n * F + src]);
-                }
-            }
-    return upload(e, out);
-}
-
-bool get_ln(EcEncoder* e, const std::string& prefix, int D, LNp* out, std::string* err) {
-    const HostTensor* g = find(e, prefix + ".weight");
-    const HostTensor* b = find(e, prefix + ".bias");
-    if (!g || !b || (int)g->data.size() != D || (int)b->data.size() != D) { *err = "missing/mis-shaped LayerNorm " + prefix; return false; }
-    out->g = upload(e, g->data);
-    out->b = upload(e, b->data);
-    return out->g && out->b;
-}
-
-// Largest |value x 2^10| the fused split images (sxf_sub / sxf_ffn / sxf_chain) hold as two fp16 halves (fp16 max 65504): |w| < 63.48 after
-// folding.  An image with a value beyond it is not built - that block / the front end runs the per-module split kernels - and the per-module
-// images (h = fp16(w)) refuse |w| >= kSplitImgMax itself (split-mode operand envelopes).  Nothing is clamped.
-constexpr float kSplitImgMax = 65000.f;
-// Largest per-channel L2 norm of the BatchNorm-folded depthwise taps the matrix-pipe kernel runs on two bf16 tap planes (hi + lo); above it a third; see finalize
-constexpr float kDwMfmaTwoPlaneNorm = 6.0f;
-
-// BatchNorm(eval) fold: y = (x - mean) / sqrt(var + 1e-5) * gamma + beta  -> per-channel scale / shift
-bool bn_fold(EcEncoder* e, const std::string& prefix, int C, std::vector<float>* scale, std::vector<float>* shift, std::string* err) {
-    const HostTensor *g = find(e, prefix + ".weight"), *b = find(e, prefix + ".bias");
-    const HostTensor *m = find(e, prefix + ".running_mean"), *v = find(e, prefix + ".running_var");
-    if (!g || !b || !m || !v || (int)g->data.size() != C) { *err = "missing/mis-shaped BatchNorm " + prefix; return false; }
-    scale->resize(C); shift->resize(C);
-    for (int c = 0; c < C; ++c) {
-        const float s = g->data[c] / std::sqrt(v->data[c] + 1e-5f);
-        (*scale)[c] = s;
-        (*shift)[c] = b->data[c] - m->data[c] * s;
-    }
-    return true;
-}
-
-// Relative sinusoid table, fp32 operation order of the reference (attentions.py:1219-1226 / 1275-1284):
-// angle = pos / 10000^(2i/D) in fp32, row r <-> position max_pos-1-r, even cols sin, odd cols cos.
-const bf16_t* build_pos_table(EcEncoder* e, int max_pos, int D) {
-    const int rows = 2 * max_pos - 1, ld = ld8(D);
-    std::vector<uint16_t> t((size_t)rows * ld, 0);
-    std::vector<float> denom(D / 2);
-    for (int i = 0; i < D / 2; ++i) denom[i] = std::pow(10000.0f, (2.0f * (float)i) / (float)D);
-    for (int r = 0; r < rows; ++r) {
-        const float pos = (float)(max_pos - 1 - r);
-        for (int i = 0; i < D / 2; ++i) {
-            const float a = pos / denom[i];
-            t[(size_t)r * ld + 2 * i] = h_f2bf(std::sin(a));
-            t[(size_t)r * ld + 2 * i + 1] = h_f2bf(std::cos(a));
-        }
-    }
-    return upload(e, t);
-}
-
-// The front end's geometry: "" or the reason it cannot run, naming the field.  Checked by effconf_encoder_create and again in front of the tables:
-// win_length > n_fft would write the window in front of its vector, hop_length <= 0 divides by zero in every frame count.
-std::string mel_config_error(const EcConfig& c) {
-    if (c.n_fft != 512) return "n_fft = " + std::to_string(c.n_fft) + ": only n_fft = 512 is native";
-    if (c.win_length <= 0 || c.win_length > c.n_fft) return "win_length = " + std::to_string(c.win_length) + ": must be in 1..n_fft (" + std::to_string(c.n_fft) + ")";
-    if (c.hop_length <= 0) return "hop_length = " + std::to_string(c.hop_length) + ": must be >= 1";
-    if (c.n_mels < 1 || c.n_mels > 128) return "n_mels = " + std::to_string(c.n_mels) + ": must be in 1..128";
-    if (c.sample_rate < 2) return "sample_rate = " + std::to_string(c.sample_rate) + ": must be >= 2";
-    return "";
-}
-
-bool build_mel_tables(EcEncoder* e, std::string* err) {
-    const EcConfig& c = e->cfg;
-    *err = mel_config_error(c);
-    if (!err->empty()) return false;
-    // Hann(win_length, periodic) centred in n_fft (torch.stft pads the window on both sides)
-    std::vector<float> win(c.n_fft, 0.f);
-    const int off = (c.n_fft - c.win_length) / 2;
-    for (int n = 0; n < c.win_length; ++n) win[off + n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * n / c.win_length));
-    std::vector<float2> tw(c.n_fft / 2);
-    for (int k = 0; k < c.n_fft / 2; ++k) {
-        const double a = -2.0 * M_PI * k / c.n_fft;
-        tw[k] = make_float2((float)std::cos(a), (float)std::sin(a));
-    }
-    // HTK triangular filterbank, f in [0, 8000], no area normalisation (torchaudio melscale_fbanks, modules.py:82)
-    const int nf = c.n_fft / 2 + 1, nm = c.n_mels;
-    const double fmin = 0.0, fmax = 8000.0;
-    auto hz2mel = [](double f) { return 2595.0 * std::log10(1.0 + f / 700.0); };
-    auto mel2hz = [](double m) { return 700.0 * (std::pow(10.0, m / 2595.0) - 1.0); };
-    std::vector<double> fpts(nm + 2);
-    for (int i = 0; i < nm + 2; ++i) fpts[i] = mel2hz(hz2mel(fmin) + (hz2mel(fmax) - hz2mel(fmin)) * i / (nm + 1));
-    std::vector<int> start(nm), count(nm), offs(nm);
-    std::vector<float> wts;
-    for (int m = 0; m < nm; ++m) {
-        int s0 = -1, cnt = 0;
-        std::vector<float> row;
-        for (int k = 0; k < nf; ++k) {
-            const double f = (double)(c.sample_rate / 2) * k / (nf - 1);
-            const double down = (f - fpts[m]) / (fpts[m + 1] - fpts[m]);
-            const double up = (fpts[m + 2] - f) / (fpts[m + 2] - fpts[m + 1]);
-            const double w = std::max(0.0, std::min(down, up));
-            if (w > 0.0) {
-                if (s0 < 0) s0 = k;
-                row.resize(k - s0 + 1, 0.f);
-                row[k - s0] = (float)w;
-                cnt = k - s0 + 1;
-            }
-        }
-        start[m] = s0 < 0 ? 0 : s0; count[m] = cnt; offs[m] = (int)wts.size();
-        wts.insert(wts.end(), row.begin(), row.begin() + cnt);
-    }
-    e->mel.window = upload(e, win);
-    e->mel.twiddle = upload(e, tw);
-    e->mel.fb_start = upload(e, start);
-    e->mel.fb_count = upload(e, count);
-    e->mel.fb_offset = upload(e, offs);
-    e->mel.fb_nnz = (int)wts.size();
-    e->mel.fb_weight = upload(e, wts);
-    return e->mel.window && e->mel.twiddle && e->mel.fb_weight;
-}
+namespace {
 
 // ------------------------------------------------------------------ shapes + workspace layout
 struct Shapes {
@@ -1504,636 +1183,7 @@ int effconf_encoder_finalize(EcEncoder* e) {
     if (!e) return fail("null encoder");
     for (void* p : e->allocs) (void)hipFree(p);
     e->allocs.clear();
-    e->bw.assign(e->blocks.size(), BlockW());
-    std::string err;
-    const EcConfig& c = e->cfg;
-    // ---- subsampling conv (C,1,3,3) + BatchNorm2d fold
-    {
-        const int C = c.sub_filters[0];
-        const HostTensor* w = find(e, "subsampling_module.layers.0.0.weight");
-        const HostTensor* b = find(e, "subsampling_module.layers.0.0.bias");
-        std::vector<float> sc, sh;
-        if (!w || !b || (int)w->data.size() != C * 9) return fail("missing subsampling conv weights");
-        if (!bn_fold(e, "subsampling_module.layers.0.1", C, &sc, &sh, &err)) return fail(err);
-        std::vector<float> w9(C * 9), bb(C);
-        for (int ch = 0; ch < C; ++ch) {
-            for (int j = 0; j < 9; ++j) w9[ch * 9 + j] = w->data[ch * 9 + j] * sc[ch];
-            bb[ch] = b->data[ch] * sc[ch] + sh[ch];
-        }
-        e->sub_w9 = upload(e, w9); e->sub_b = upload(e, bb);
-        if (c.sub_layers == 1) {
-            if (!pack_named_linear(e, "linear", e->blocks[0].dim_model, C * (c.n_mels / 2), &e->lin, &err)) return fail(err);
-        } else {
-            // ---- layer 2: (C1, C, 3, 3) conv + BatchNorm2d fold -> implicit-GEMM weight [C1][9*Cp], K order (tap, c_in)
-            const int C1 = c.sub_filters[1], Cp = ec_round_up(C, 64), F2 = c.n_mels / 4;
-            const HostTensor* w2 = find(e, "subsampling_module.layers.1.0.weight");
-            const HostTensor* b2 = find(e, "subsampling_module.layers.1.0.bias");
-            std::vector<float> sc2, sh2;
-            if (!w2 || !b2 || (int64_t)w2->data.size() != (int64_t)C1 * C * 9) return fail("missing subsampling layer-2 conv weights");
-            if (!bn_fold(e, "subsampling_module.layers.1.1", C1, &sc2, &sh2, &err)) return fail(err);
-            const int Np = ec_round_up(C1, 128);
-            std::vector<uint16_t> wp((size_t)Np * 9 * Cp, 0);
-            std::vector<float> bp(Np, 0.f);
-            for (int n = 0; n < C1; ++n) {
-                for (int ci = 0; ci < C; ++ci)
-                    for (int tap = 0; tap < 9; ++tap)
-                        wp[(size_t)n * 9 * Cp + (size_t)tap * Cp + ci] = h_f2bf(w2->data[((size_t)n * C + ci) * 9 + tap] * sc2[n]);
-                bp[n] = b2->data[n] * sc2[n] + sh2[n];
-            }
-            e->sub2_w = upload(e, wp); e->sub2_b = upload(e, bp); e->sub2_cp = Cp;
-            // ---- Linear with its K axis in (f2, c) order (reference feature index c*F2 + f2, modules.py:247)
-            const HostTensor* lw = find(e, "linear.weight");
-            const HostTensor* lb = find(e, "linear.bias");
-            const int N = e->blocks[0].dim_model, K = C1 * F2;
-            if (!lw || !lb || (int64_t)lw->data.size() != (int64_t)N * K) return fail("missing / mis-shaped linear.weight");
-            std::vector<float> perm((size_t)N * K);
-            for (int n = 0; n < N; ++n)
-                for (int f2 = 0; f2 < F2; ++f2)
-                    for (int ch = 0; ch < C1; ++ch) perm[(size_t)n * K + (size_t)f2 * C1 + ch] = lw->data[(size_t)n * K + (size_t)ch * F2 + f2];
-            std::vector<const float*> rows(N);
-            for (int n = 0; n < N; ++n) rows[n] = perm.data() + (size_t)n * K;
-            if (!pack_linear(e, rows, lb->data, K, &e->lin)) return fail("upload failed");
-        }
-        if (c.sub_layers == 1 && sublinear_fused_supported(c.n_mels, e->blocks[0].dim_model)) {
-            // K' = (fc*Cp + ch)*8 + e  <->  reference feature ch*(F/2) + 8*fc + e   (sublinear.hip)
-            const HostTensor* lw = find(e, "linear.weight");
-            const int N = e->blocks[0].dim_model, F2 = c.n_mels / 2, Cp = ec_round_up(C, 8), Kp = (F2 / 8) * Cp * 8;
-            const int Np = ec_round_up(N, 128);
-            std::vector<uint16_t> wf((size_t)Np * Kp, 0);
-            for (int n = 0; n < N; ++n)
-                for (int fc = 0; fc < F2 / 8; ++fc)
-                    for (int ch = 0; ch < C; ++ch)
-                        for (int ee = 0; ee < 8; ++ee)
-                            wf[(size_t)n * Kp + ((size_t)fc * Cp + ch) * 8 + ee] = h_f2bf(lw->data[(size_t)n * (C * F2) + ch * F2 + fc * 8 + ee]);
-            e->lin_fused = upload(e, wf); e->lin_fused_ld = Kp;
-        }
-        e->lin_rs = nullptr; e->conv_tab = nullptr;
-        if (c.sub_layers == 1) {
-            const int N = e->blocks[0].dim_model, F2 = c.n_mels / 2;
-            const int CGr = sublinear2_groups(c.n_mels, C, N);
-            if (CGr > 0) {
-                // sublinear2.hip: per output frequency f a slab [32 NT rows n][32 CG columns]: natural column = channel c (reference feature
-                // c*(F/2) + f, modules.py:247), K index permuted inside every group of 16 (packed position 8h+e <-> column 4h + 8(e>>2) + (e&3)):
-                // the Swish-ed accumulator registers of the conv MFMA are the B fragments directly (chain.hip's register hand-off)
-                const HostTensor* lw = find(e, "linear.weight");
-                const int NT = CGr, Cp = 32 * CGr, rows = 32 * NT;
-                std::vector<uint16_t> wr((size_t)F2 * rows * Cp, 0);
-                for (int f = 0; f < F2; ++f)
-                    for (int n = 0; n < N; ++n)
-                        for (int k = 0; k < Cp; ++k) {
-                            const int g16 = k / 16, pp = k % 16, hh = pp >> 3, ee = pp & 7;
-                            const int ch = g16 * 16 + 4 * hh + 8 * (ee >> 2) + (ee & 3);
-                            if (ch < C) wr[((size_t)f * rows + n) * Cp + k] = h_f2bf(lw->data[(size_t)n * (C * F2) + (size_t)ch * F2 + f]);
-                        }
-                std::vector<float> tab((size_t)Cp * 16, 0.f);
-                for (int ch = 0; ch < C; ++ch) {
-                    for (int j = 0; j < 9; ++j) tab[(size_t)ch * 16 + j] = w9[ch * 9 + j];
-                    tab[(size_t)ch * 16 + 9] = bb[ch];
-                }
-                e->lin_rs = upload(e, wr); e->conv_tab = upload(e, tab);
-            }
-            // sublinear3.hip: chunks of (output frequency, 32 channels), any channel count / width up to 384: conv taps as bf16 hi (truncation) + lo, the
-            // Linear's weight [chunk][32 nt rows][32 k] with the k order of the accumulator layout
-            e->sub3_cimg = e->sub3_wimg = nullptr; e->sub3_bias = nullptr;
-            const int nt3 = sublinear3_tiles(N);
-            const HostTensor *lw3 = find(e, "linear.weight"), *lb3 = find(e, "linear.bias");
-            if (nt3 && lw3 && lb3 && (int64_t)lw3->data.size() == (int64_t)N * C * F2 && (int)lb3->data.size() == N) {
-                const int ncb = (C + 31) / 32, DP2 = 32 * nt3;
-                std::vector<uint16_t> cimg((size_t)ncb * 2 * 32 * 16, 0), wimg((size_t)F2 * ncb * DP2 * 32, 0);
-                auto put_tap = [&](int ch, int tap, float v) {
-                    uint32_t u; memcpy(&u, &v, 4);
-                    const uint32_t hb = u & 0xFFFF0000u; float hf; memcpy(&hf, &hb, 4);
-                    const size_t base = (size_t)(ch / 32) * 2 * 32 * 16 + (size_t)(ch % 32) * 16 + tap;
-                    cimg[base] = (uint16_t)(hb >> 16); cimg[base + 32 * 16] = h_f2bf(v - hf);
-                };
-                for (int ch = 0; ch < C; ++ch) {
-                    for (int j = 0; j < 9; ++j) put_tap(ch, j, w9[ch * 9 + j]);
-                    put_tap(ch, 9, bb[ch]);
-                }
-                for (int f = 0; f < F2; ++f)
-                    for (int cb = 0; cb < ncb; ++cb) {
-                        const size_t base = (size_t)(f * ncb + cb) * DP2 * 32;
-                        for (int n = 0; n < N; ++n)
-                            for (int pos = 0; pos < 32; ++pos) {
-                                const int sstep = pos >> 4, khh = (pos >> 3) & 1, ee = pos & 7;
-                                const int ch = 32 * cb + 16 * sstep + 8 * (ee >> 2) + 4 * khh + (ee & 3);      // accumulator register 8 s + e of lane half kh holds this channel
-                                if (ch < C) wimg[base + (size_t)n * 32 + pos] = h_f2bf(lw3->data[(size_t)n * (C * F2) + (size_t)ch * F2 + f]);
-                            }
-                    }
-                std::vector<float> bp(DP2, 0.f);
-                for (int n = 0; n < N; ++n) bp[n] = lb3->data[n];
-                e->sub3_cimg = upload(e, cimg); e->sub3_wimg = upload(e, wimg); e->sub3_bias = upload(e, bp); e->sub3_ncb = ncb; e->sub3_fo = F2;
-            }
-        }
-    }
-    std::map<std::pair<int, int>, const bf16_t*> tables;
-    std::vector<int> strides;
-    for (size_t k = 0; k < e->blocks.size(); ++k) {
-        const EcBlock& b = e->blocks[k];
-        BlockW& W = e->bw[k];
-        const int D = b.dim_model, De = b.dim_expand, F1 = D * b.ff_ratio, F2 = De * b.ff_ratio;
-        const std::string p = "blocks." + std::to_string(k);
-        strides.push_back(b.conv_stride);
-        bool ok = get_ln(e, p + ".feed_forward_module1.layers.0", D, &W.ln_ffn1, &err) &&
-                  pack_named_linear(e, p + ".feed_forward_module1.layers.1", F1, D, &W.ffn1_a, &err) &&
-                  pack_named_linear(e, p + ".feed_forward_module1.layers.4", D, F1, &W.ffn1_b, &err) &&
-                  get_ln(e, p + ".feed_forward_module2.layers.0", De, &W.ln_ffn2, &err) &&
-                  pack_named_linear(e, p + ".feed_forward_module2.layers.1", F2, De, &W.ffn2_a, &err) &&
-                  pack_named_linear(e, p + ".feed_forward_module2.layers.4", De, F2, &W.ffn2_b, &err) &&
-                  get_ln(e, p + ".norm", De, &W.ln_out, &err);
-        if (!ok) return fail(err);
-        W.ffn1_bp = pack_ffn2_permuted(e, p + ".feed_forward_module1.layers.4", D, F1);
-        W.ffn2_bp = pack_ffn2_permuted(e, p + ".feed_forward_module2.layers.4", De, F2);
-        if (!W.ffn1_bp || !W.ffn2_bp) return fail("upload failed");
-        const std::string m = p + ".multi_head_self_attention_module";
-        if (!get_ln(e, m + ".norm", D, &W.ln_att, &err)) return fail(err);
-        {   // Q, K, V stacked into one [3D][D] weight
-            std::vector<const float*> rows; std::vector<float> bias;
-            for (const char* n : {"query_layer", "key_layer", "value_layer"}) {
-                const HostTensor* w = find(e, m + ".mhsa." + n + ".weight");
-                const HostTensor* bb = find(e, m + ".mhsa." + n + ".bias");
-                if (!w || !bb || (int)w->data.size() != D * D) return fail("missing " + m + ".mhsa." + n);
-                for (int r = 0; r < D; ++r) rows.push_back(w->data.data() + (size_t)r * D);
-                bias.insert(bias.end(), bb->data.begin(), bb->data.end());
-            }
-            if (!pack_linear(e, rows, bias, D, &W.qkv)) return fail("upload failed");
-            // natural-layout variant for the row-stationary kernel: rows permuted inside every chunk of 32 so that a lane's
-            // accumulators are row-contiguous runs of 8 columns (chunk row j <-> column 16(j>>4) + 8((j>>2)&1) + 4((j>>3)&1) + (j&3))
-            const int np = ec_round_up(3 * D, 32);
-            std::vector<const float*> prow(np, nullptr); std::vector<float> pbias(np, 0.f);
-            for (int n = 0; n < np; ++n) {
-                const int c = n / 32, j = n % 32;
-                const int src = c * 32 + 16 * (j >> 4) + 8 * ((j >> 2) & 1) + 4 * ((j >> 3) & 1) + (j & 3);
-                if (src < 3 * D) { prow[n] = rows[src]; pbias[n] = bias[src]; }
-            }
-            if (!pack_linear(e, prow, pbias, D, &W.qkv_nat)) return fail("upload failed");
-            W.qkv_nat.N = 3 * D;
-            if (chain_supported(D)) {
-                const HostTensor *lg = find(e, m + ".norm.weight"), *lb = find(e, m + ".norm.bias");      // attention pre-norm folded in
-                if (!lg || !lb || !pack_linear(e, prow, pbias, D, &W.c_qkv, true, lg->data.data(), lb->data.data())) return fail("upload failed");
-                W.c_qkv_chunks = ec_cdiv(3 * D, 64);
-            }
-        }
-        if (chain_supported(D)) {      // D-wide part of the block: FFN1, attention output projection (pointwise-1 below)
-            const HostTensor* b2 = find(e, p + ".feed_forward_module1.layers.4.bias");
-            if (!b2 || !pack_named_linear(e, p + ".feed_forward_module1.layers.1", F1, D, &W.c_f1a, &err, true, p + ".feed_forward_module1.layers.0") ||
-                !pack_named_linear(e, m + ".mhsa.output_layer", D, D, &W.c_outp, &err, true)) return fail("chain packing failed: " + err);
-            W.c_f1b = pack_ffn2_permuted(e, p + ".feed_forward_module1.layers.4", D, F1, 0.5f);
-            if (chain3_supported(D)) W.c_f1b_cm = pack_ffn2_chunkmajor(e, p + ".feed_forward_module1.layers.4", D, F1, 0.5f, chain_padded_width(D));
-            std::vector<float> hb(b2->data); for (float& x : hb) x *= 0.5f;
-            W.c_f1b2 = upload(e, hb); W.h_f1b2 = hb;
-            if (!W.c_f1b || !W.c_f1b2 || (chain3_supported(D) && !W.c_f1b_cm)) return fail("upload failed");
-            W.chain_in = true;
-        }
-        if (chain_supported(De)) {     // De-wide part: pointwise-2, FFN2
-            const HostTensor* b2 = find(e, p + ".feed_forward_module2.layers.4.bias");
-            if (!b2 || !pack_named_linear(e, p + ".feed_forward_module2.layers.1", F2, De, &W.c_f2a, &err, true, p + ".feed_forward_module2.layers.0") ||
-                !pack_named_linear(e, p + ".convolution_module.layers.7", De, De, &W.c_pw2, &err, true)) return fail("chain packing failed: " + err);
-            W.c_f2b = pack_ffn2_permuted(e, p + ".feed_forward_module2.layers.4", De, F2, 0.5f);
-            if (chain3_supported(De)) W.c_f2b_cm = pack_ffn2_chunkmajor(e, p + ".feed_forward_module2.layers.4", De, F2, 0.5f, chain_padded_width(De));
-            std::vector<float> hb(b2->data); for (float& x : hb) x *= 0.5f;
-            W.c_f2b2 = upload(e, hb); W.h_f2b2 = hb;
-            const HostTensor *og = find(e, p + ".norm.weight"), *ob = find(e, p + ".norm.bias");
-            if (!og || !ob) return fail("missing " + p + ".norm");
-            W.h_ln_out_g = og->data; W.h_ln_out_b = ob->data;
-            if (!W.c_f2b || !W.c_f2b2 || (chain3_supported(De) && !W.c_f2b_cm)) return fail("upload failed");
-            W.chain_out = true;
-        }
-        if (!pack_named_linear(e, m + ".mhsa.pos_layer", D, D, &W.pos, &err)) return fail(err);
-        if (!pack_named_linear(e, m + ".mhsa.output_layer", D, D, &W.outp, &err)) return fail(err);
-        const HostTensor *u = find(e, m + ".mhsa.u"), *v = find(e, m + ".mhsa.v");
-        if (!u || !v || (int)u->data.size() != D) return fail("missing " + m + ".mhsa.u/v");
-        W.u = upload(e, u->data); W.v = upload(e, v->data);
-        W.h_u = u->data; W.h_v = v->data;
-        {   // head column x of head h is feature (h*d + x) % D of the un-grouped row (group = view, attentions.py:677-686)
-            const int H = b.num_heads, d = b.group_size * D / H;
-            W.dvu_ld = ec_round_up(d, 32);
-            std::vector<float> t((size_t)H * W.dvu_ld, 0.f);
-            for (int h = 0; h < H; ++h)
-                for (int x = 0; x < d; ++x) { const int n = (h * d + x) % D; t[(size_t)h * W.dvu_ld + x] = v->data[n] - u->data[n]; }
-            W.dvu = upload(e, t);
-        }
-        auto key = std::make_pair(b.max_pos, D);
-        if (!tables.count(key)) tables[key] = build_pos_table(e, b.max_pos, D);
-        W.pos_table = tables[key];
-        // ---- convolution module
-        const std::string cm = p + ".convolution_module.layers";
-        if (!get_ln(e, cm + ".0", D, &W.ln_conv, &err)) return fail(err);
-        {   // pointwise-1 (2De, D, 1): GLU halves interleaved in blocks of 32 output channels (a | b)
-            const HostTensor* w = find(e, cm + ".2.weight");
-            const HostTensor* bb = find(e, cm + ".2.bias");
-            if (!w || !bb || (int)w->data.size() != 2 * De * D) return fail("missing " + cm + ".2");
-            const int nblk = ec_cdiv(De, 32);
-            std::vector<const float*> rows(nblk * 64, nullptr); std::vector<float> bias(nblk * 64, 0.f);
-            for (int j = 0; j < De; ++j) {
-                const int jb = j / 32, jj = j % 32;
-                rows[jb * 64 + jj] = w->data.data() + (size_t)j * D;            bias[jb * 64 + jj] = bb->data[j];
-                rows[jb * 64 + 32 + jj] = w->data.data() + (size_t)(De + j) * D; bias[jb * 64 + 32 + jj] = bb->data[De + j];
-            }
-            if (!pack_linear(e, rows, bias, D, &W.pw1)) return fail("upload failed");
-            if (chain_supported(D)) {
-                const HostTensor *lg = find(e, cm + ".0.weight"), *lb = find(e, cm + ".0.bias");          // conv-module pre-norm folded in
-                if (!lg || !lb || !pack_linear(e, rows, bias, D, &W.c_pw1, true, lg->data.data(), lb->data.data())) return fail("upload failed");
-                W.c_pw1_chunks = nblk;
-            }
-        }
-        {   // depthwise (De, 1, k) + BatchNorm1d fold -> [k][De] fp32
-            const int ks = b.kernel_size;
-            const HostTensor* w = find(e, cm + ".4.weight");
-            const HostTensor* bb = find(e, cm + ".4.bias");
-            std::vector<float> sc, sh;
-            if (!w || !bb || (int)w->data.size() != De * ks) return fail("missing " + cm + ".4");
-            if (!bn_fold(e, cm + ".5", De, &sc, &sh, &err)) return fail(err);
-            std::vector<float> wk((size_t)ks * De), bz(De);
-            for (int ch = 0; ch < De; ++ch) {
-                for (int j = 0; j < ks; ++j) wk[(size_t)j * De + ch] = w->data[(size_t)ch * ks + j] * sc[ch];
-                bz[ch] = bb->data[ch] * sc[ch] + sh[ch];
-            }
-            W.dw_w = upload(e, wk); W.dw_b = upload(e, bz);
-            // The matrix-pipe kernel holds every folded tap as a bf16 hi + lo pair: 2^-18 of the tap is lost, sigma = 2^-18 / sqrt(3) * |taps|_2 * rms(x) on the
-            // pre-activation.  The stage's contract (oracle/ref_bf16.py, tests/test_gpu_bf16_rounding.py) leaves 2e-5 absolute on the output, 4e-5 on the
-            // pre-activation where Swish has slope 1/2; five sigma inside that at rms(GLU) = 0.6 means |taps|_2 <= 6 per channel.  Initialised and synthetic
-            // weights sit at 1.5 - 2.4; BatchNorm statistics of a trained-like profile fold to 12 - 800: those blocks get a third tap plane (one more MFMA per
-            // tap group on the same kernel; taps exact to 2^-27)
-            float tap_norm = 0.f;
-            for (int ch = 0; ch < De; ++ch) {
-                double n2 = 0.0;
-                for (int j = 0; j < ks; ++j) n2 += (double)wk[(size_t)j * De + ch] * wk[(size_t)j * De + ch];
-                tap_norm = std::max(tap_norm, (float)std::sqrt(n2));
-            }
-            if (dwconv_mfma_supported(ks, b.conv_stride)) {
-                std::vector<uint16_t> ta((size_t)De * 4 * dwconv_mfma_groups(ks) * 8);
-                pack_dwconv_mfma(wk.data(), ks, De, ta.data());
-                if (tap_norm > kDwMfmaTwoPlaneNorm) {
-                    std::vector<uint16_t> t3((size_t)De * 4 * dwconv_mfma_groups(ks) * 4);
-                    pack_dwconv_mfma3(wk.data(), ks, De, t3.data());
-                    W.dw_a3 = upload(e, t3);
-                    if (!W.dw_a3) return fail("upload failed");
-                }
-                W.dw_a = upload(e, ta);
-                if (!W.dw_a) return fail("upload failed");
-            }
-        }
-        if (!pack_named_linear(e, cm + ".7", De, De, &W.pw2, &err)) return fail(err);
-        if (D != De && !pack_named_linear(e, p + ".conv_res.1", De, D, &W.res, &err, false, "", De)) return fail(err);
-    }
-    // ---- constant blocks of the fused chains (one LDS-DMA per workgroup instead of a dozen small strided copies)
-    for (size_t k = 0; k < e->blocks.size(); ++k) {
-        BlockW& W = e->bw[k];
-        const EcBlock& b = e->blocks[k];
-        const int D = b.dim_model, De = b.dim_expand;
-        auto build = [&](int kind, int dim, const BlockW* pre, const BlockW* post, const EcBlock* pb, const EcBlock* qb) -> const float* {
-            ChainParams cp{};
-            cp.D = dim;
-            const bool isb = kind == CHAIN_B;
-            if (pre && !isb) cp.f[0].Fp = ec_round_up(pb->dim_expand * pb->ff_ratio, 32);
-            if (post) cp.f[1].Fp = ec_round_up(qb->dim_model * qb->ff_ratio, 32);
-            cp.g1.nchunks = isb ? pre->c_pw1_chunks : (post ? post->c_qkv_chunks : 0);
-            int nf[8];
-            const int nfl = chain_const_layout(cp, kind, nf);
-            const int DP = chain_padded_width(dim);
-            std::vector<float> blk(nfl, 0.f);
-            auto put = [&](int off, const std::vector<float>& src, int n) { for (int i = 0; i < n && i < (int)src.size(); ++i) blk[off + i] = src[i]; };
-            if (isb) {
-                put(nf[0], pre->c_outp.hbias, dim);
-                put(nf[6], pre->c_pw1.hbias, 64 * cp.g1.nchunks);
-            } else {
-                if (pre) {
-                    put(nf[0], pre->c_pw2.hbias, dim);
-                    put(nf[1], pre->h_ln_out_g, dim); put(nf[1] + DP, pre->h_ln_out_b, dim);
-                    put(nf[2], pre->c_f2a.hbias, cp.f[0].Fp); put(nf[3], pre->h_f2b2, dim);
-                }
-                if (post) {
-                    put(nf[4], post->c_f1a.hbias, cp.f[1].Fp); put(nf[5], post->h_f1b2, dim);
-                    put(nf[6], post->c_qkv.hbias, 64 * cp.g1.nchunks);
-                    put(nf[7], post->h_u, dim); put(nf[7] + DP, post->h_v, dim);
-                }
-            }
-            return upload(e, blk);
-        };
-        if (W.chain_in) {
-            W.cc_b = build(CHAIN_B, D, &W, nullptr, &b, nullptr);
-            if (chain_head_supported(D)) W.cc_head = build(CHAIN_A_HEAD, D, nullptr, &W, nullptr, &b);
-        }
-        if (W.chain_out && chain_tail_supported(De)) {
-            W.cc_tail = build(CHAIN_A_TAIL, De, &W, nullptr, &b, nullptr);
-            if (chain_full_supported(De, std::max(e->chain_full_max, chain3_supported(De) ? 256 : 0)) && k + 1 < e->blocks.size() && e->bw[k + 1].chain_in && e->blocks[k + 1].dim_model == De)
-                W.cc_full = build(CHAIN_A_FULL, De, &W, &e->bw[k + 1], &b, &e->blocks[k + 1]);
-        }
-    }
-    e->block_stride = upload(e, strides);
-    {
-        std::vector<int> gs, hs;
-        for (const EcBlock& b : e->blocks) { gs.push_back(b.group_size); hs.push_back(b.num_heads); }
-        e->block_group = upload(e, gs); e->block_heads = upload(e, hs);
-    }
-    if (c.vocab_size > 0) {
-        const HostTensor *w = find(e, "fc.weight"), *b = find(e, "fc.bias");
-        const int D = e->blocks.back().dim_expand, V = c.vocab_size;
-        if (w && b) {
-            if ((int)w->data.size() != V * D) return fail("fc.weight shape mismatch");
-            std::vector<float> wt((size_t)D * V);
-            for (int v = 0; v < V; ++v) for (int k = 0; k < D; ++k) wt[(size_t)k * V + v] = w->data[(size_t)v * D + k];
-            e->fc_wt = upload(e, wt); e->fc_b = upload(e, b->data);
-            // split-bf16 images: W = hi + lo (hi = bf16(W), lo = bf16(W - hi)), fragment (k-step s, column v, k-half h) = W[v][16 s + 8 h .. + 7]
-            const int Kp = ec_round_up(D, 16), Vp = ec_round_up(V, 256);   // whole 256-column passes of ctc_argmax_bf16x3_kernel (4 waves x 64): every wave's fragment loads stay inside the image
-            std::vector<uint16_t> hi((size_t)(Kp / 16) * Vp * 16, 0), lo(hi.size(), 0);
-            for (int v = 0; v < V; ++v)
-                for (int k = 0; k < D; ++k) {
-                    const float wv = w->data[(size_t)v * D + k];
-                    const uint16_t h = h_f2bf(wv);
-                    uint32_t hb = (uint32_t)h << 16; float hf; memcpy(&hf, &hb, 4);
-                    const size_t idx = (((size_t)(k / 16) * Vp + v) * 2 + (k % 16) / 8) * 8 + k % 8;
-                    hi[idx] = h; lo[idx] = h_f2bf(wv - hf);
-                }
-            e->fc_hi = upload(e, hi); e->fc_lo = upload(e, lo);
-        }
-    }
-    if (!build_mel_tables(e, &err)) return fail(err);
-    e->xw.clear(); e->xtab.clear();
-    if (e->exact_pack) {       // fp32-operand mode: the reference-layout fp32 tensors themselves, fp32 sinusoid tables, BatchNorm scale / shift
-        for (auto& kv : e->host) e->xw[kv.first] = upload(e, kv.second.data);
-        std::vector<float> sub_sc0, sub_sh0;
-        for (int l = 0; l < c.sub_layers; ++l) {
-            const std::string sp = "subsampling_module.layers." + std::to_string(l);
-            const int C = c.sub_filters[l];
-            const HostTensor* cbias = find(e, sp + ".0.bias");
-            std::vector<float> sc, sh;
-            if (!cbias || (int)cbias->data.size() != C || !bn_fold(e, sp + ".1", C, &sc, &sh, &err)) return fail("exact mode: " + err);
-            for (int ch = 0; ch < C; ++ch) sh[ch] += cbias->data[ch] * sc[ch];
-            e->xsub_scale[l] = upload(e, sc); e->xsub_shift[l] = upload(e, sh);
-            if (l == 0) { sub_sc0 = sc; sub_sh0 = sh; }
-        }
-        e->xsplit.clear();
-        e->xsub_cimg = e->xsub_wimg = nullptr; e->xsub_bias = nullptr;
-        if (e->exact_split && c.sub_layers == 1) {
-            // images of the fused front end (sxf_sub.hip): conv taps with the BatchNorm scale folded in (shift + scaled conv bias in tap 9), the Linear's weight in
-            // chunks of (output frequency f', 32 channels) with the k order of the accumulator layout; same-scale halves at 2^10 as for the other fused kernels
-            const int Co = c.sub_filters[0], Fo = (c.n_mels - 1) / 2 + 1, N = e->blocks[0].dim_model, nt = sxf_sublin_tiles(N);
-            const HostTensor *cw = find(e, "subsampling_module.layers.0.0.weight"), *lw = find(e, "linear.weight"), *lb = find(e, "linear.bias");
-            if (nt && cw && lw && lb && (int64_t)cw->data.size() == (int64_t)Co * 9 && (int64_t)lw->data.size() == (int64_t)N * Co * Fo && (int)lb->data.size() == N) {
-                auto half_bits = [](float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; };
-                bool over = false;                     // a folded value the image cannot hold: no fused front end (per-module kernels)
-                auto put = [&](std::vector<uint16_t>& img, size_t hi_at, size_t lo_at, double wv) {
-                    const float ws = (float)(wv * 1024.0);
-                    if (!(std::fabs(ws) < kSplitImgMax)) { over = true; return; }
-                    const _Float16 hh = (_Float16)ws;
-                    img[hi_at] = half_bits((float)hh);
-                    img[lo_at] = half_bits(ws - (float)hh);
-                };
-                const int ncb = (Co + 31) / 32, DP2 = 32 * nt;
-                std::vector<uint16_t> cimg((size_t)ncb * 2 * 32 * 16, 0), wimg((size_t)Fo * ncb * 2 * DP2 * 32, 0);
-                for (int co = 0; co < Co; ++co) {
-                    const size_t base = (size_t)(co / 32) * 2 * 32 * 16 + (size_t)(co % 32) * 16;
-                    for (int tap = 0; tap < 9; ++tap) put(cimg, base + tap, base + 32 * 16 + tap, (double)cw->data[(size_t)co * 9 + tap] * sub_sc0[co]);
-                    put(cimg, base + 9, base + 32 * 16 + 9, sub_sh0[co]);
-                }
-                for (int fo = 0; fo < Fo; ++fo)
-                    for (int cb = 0; cb < ncb; ++cb) {
-                        const size_t base = (size_t)(fo * ncb + cb) * 2 * DP2 * 32;
-                        for (int n = 0; n < N; ++n)
-                            for (int pos = 0; pos < 32; ++pos) {
-                                const int sstep = pos >> 4, khh = (pos >> 3) & 1, ee = pos & 7;
-                                const int co = 32 * cb + 16 * sstep + 8 * (ee >> 2) + 4 * khh + (ee & 3);      // accumulator register 8 s + e of lane half kh holds this channel
-                                if (co >= Co) continue;
-                                put(wimg, base + (size_t)n * 32 + pos, base + (size_t)DP2 * 32 + (size_t)n * 32 + pos, lw->data[(size_t)n * Co * Fo + (size_t)co * Fo + fo]);
-                            }
-                    }
-                std::vector<float> bp(DP2, 0.f);
-                for (int n = 0; n < N; ++n) bp[n] = lb->data[n];
-                if (!over) { e->xsub_cimg = upload(e, cimg); e->xsub_wimg = upload(e, wimg); e->xsub_bias = upload(e, bp); e->xsub_ncb = ncb; e->xsub_fo = Fo; }
-            }
-        }
-        if (e->exact_split) {
-            // every 2-D weight (nn.Linear [N][K], 1x1 Conv1d [N][K][1]) as two fp16 images h = fp16(w), l = fp16((w - h) * 2048), K padded
-            // with zeros to whole 32-wide k-tiles and stored k-tile major; the three attention projections of a block additionally stacked (q | k | v)
-            auto half_bits = [](float f) { _Float16 h = (_Float16)f; uint16_t u; memcpy(&u, &h, 2); return u; };
-            std::string range_err;                 // the first tensor with an element the per-module images cannot hold: finalize fails
-            auto add_split = [&](const std::string& prefix, const std::vector<const float*>& rows, int K) {
-                const int N = (int)rows.size(), ldh = ec_round_up(K, 32);
-                std::vector<uint16_t> hi((size_t)N * ldh, 0), lo(hi.size(), 0);
-                for (int n = 0; n < N; ++n)
-                    for (int k = 0; k < K; ++k) {
-                        const float wv = rows[n][k];
-                        if (!(std::fabs(wv) < kSplitImgMax)) {
-                            if (range_err.empty())
-                                range_err = "split mode: " + prefix + ".weight[" + std::to_string(n) + "][" + std::to_string(k) + "] = " + std::to_string(wv) +
-                                            " is outside the split images' range |w| < 65000";
-                            return;
-                        }
-                        const _Float16 h = (_Float16)wv;
-                        const size_t at = ((size_t)(k / 32) * N + n) * 32 + k % 32;       // k-tile major (kernels.h: SxGemmParams)
-                        hi[at] = half_bits((float)h);
-                        lo[at] = half_bits((wv - (float)h) * 2048.0f);                      // |w - h| <= 2^-11 |w|: |l| < 2^15
-                    }
-                e->xsplit[prefix] = EcEncoder::SplitW{upload(e, hi), upload(e, lo), ldh};
-            };
-            for (auto& kv : e->host) {
-                const std::string& key = kv.first;
-                const HostTensor& t = kv.second;
-                if (key.size() < 8 || key.compare(key.size() - 7, 7, ".weight") != 0) continue;
-                const bool lin = t.shape.size() == 2, pw = t.shape.size() == 3 && t.shape[2] == 1 && key.find("subsampling") == std::string::npos;
-                if (!lin && !pw) continue;
-                const int N = (int)t.shape[0], K = (int)t.shape[1];
-                if (K % 4 || key == "fc.weight") continue;
-                std::vector<const float*> rows(N);
-                for (int n = 0; n < N; ++n) rows[n] = t.data.data() + (size_t)n * K;
-                add_split(key.substr(0, key.size() - 7), rows, K);
-            }
-            for (size_t k = 0; k < e->blocks.size(); ++k) {
-                const std::string m = "blocks." + std::to_string(k) + ".multi_head_self_attention_module.mhsa.";
-                const int D = e->blocks[k].dim_model;
-                std::vector<const float*> rows;
-                std::vector<float> bias;
-                bool ok = true;
-                for (const char* nm : {"query_layer", "key_layer", "value_layer"}) {
-                    const HostTensor *w = find(e, m + nm + ".weight"), *b = find(e, m + nm + ".bias");
-                    if (!w || !b || (int)w->data.size() != D * D || (int)b->data.size() != D) { ok = false; break; }
-                    for (int n = 0; n < D; ++n) rows.push_back(w->data.data() + (size_t)n * D);
-                    bias.insert(bias.end(), b->data.begin(), b->data.end());
-                }
-                if (!ok) continue;
-                add_split(m + "qkv_layer", rows, D);
-                e->xw[m + "qkv_layer.bias"] = upload(e, bias);
-            }
-            if (!range_err.empty()) return fail(range_err);
-            // weight images of the fused FFN kernel (sxf_ffn.hip; kernels.h: SxfFfnParams)
-            for (size_t k = 0; k < e->blocks.size(); ++k)
-                for (int which = 0; which < 2; ++which) {
-                    const int D = which ? e->blocks[k].dim_expand : e->blocks[k].dim_model, F = D * e->blocks[k].ff_ratio;
-                    if (!sxf_ffn_supported(D)) continue;
-                    const std::string pf = "blocks." + std::to_string(k) + (which ? ".feed_forward_module2.layers." : ".feed_forward_module1.layers.");
-                    const HostTensor *g = find(e, pf + "0.weight"), *bt = find(e, pf + "0.bias"), *w1 = find(e, pf + "1.weight"), *b1 = find(e, pf + "1.bias"),
-                                     *w2 = find(e, pf + "4.weight"), *b2 = find(e, pf + "4.bias");
-                    if (!g || !bt || !w1 || !b1 || !w2 || !b2 || (int64_t)w1->data.size() != (int64_t)F * D || (int64_t)w2->data.size() != (int64_t)F * D ||
-                        (int)g->data.size() != D || (int)bt->data.size() != D || (int)b1->data.size() != F || (int)b2->data.size() != D) continue;
-                    int ks1, nt2; sxf_ffn_shape(D, &ks1, &nt2);
-                    const int DP1 = 16 * ks1, DP2 = 32 * nt2, nch = (F + 31) / 32;
-                    const size_t per = (size_t)64 * (DP1 + DP2);
-                    std::vector<uint16_t> img((size_t)nch * per, 0);
-                    bool over = false;                 // a folded value the image cannot hold: this FFN (and the chains using it) runs per-module
-                    auto put = [&](size_t hi_at, size_t lo_at, float wv) {      // same-scale halves at the weight scale 2^10 (sx_common.h split2s; sxf_ffn.hip SW)
-                        const float ws = wv * 1024.0f;
-                        if (!(std::fabs(ws) < kSplitImgMax)) { over = true; return; }
-                        const _Float16 hh = (_Float16)ws;
-                        img[hi_at] = half_bits((float)hh);
-                        img[lo_at] = half_bits(ws - (float)hh);
-                    };
-                    for (int c = 0; c < nch; ++c) {
-                        const size_t base = (size_t)c * per;
-                        for (int r = 0; r < 32; ++r) {
-                            const int hrow = 32 * c + r;
-                            if (hrow >= F) continue;
-                            double bias = b1->data[hrow];
-                            for (int kk = 0; kk < D; ++kk) {
-                                const double wv = w1->data[(size_t)hrow * D + kk];
-                                bias += wv * bt->data[kk];                                       // W1 beta folded into the bias column
-                                put(base + (size_t)r * DP1 + kk, base + (size_t)32 * DP1 + (size_t)r * DP1 + kk, (float)(wv * g->data[kk]));
-                            }
-                            put(base + (size_t)r * DP1 + D, base + (size_t)32 * DP1 + (size_t)r * DP1 + D, (float)bias);
-                        }
-                        for (int n = 0; n < D; ++n)
-                            for (int pos = 0; pos < 32; ++pos) {
-                                const int sstep = pos >> 4, khh = (pos >> 3) & 1, ee = pos & 7;
-                                const int hid = 32 * c + 16 * sstep + 8 * (ee >> 2) + 4 * khh + (ee & 3);      // accumulator register 8 s + e of lane half kh holds this hidden unit
-                                if (hid >= F) continue;
-                                put(base + (size_t)64 * DP1 + (size_t)n * 32 + pos, base + (size_t)64 * DP1 + (size_t)32 * DP2 + (size_t)n * 32 + pos,
-                                    0.5f * w2->data[(size_t)n * F + hid]);
-                            }
-                    }
-                    if (over) continue;
-                    std::vector<float> b2h(DP2, 0.f);
-                    for (int n = 0; n < D; ++n) b2h[n] = 0.5f * b2->data[n];
-                    e->bw[k].xf_img[which] = upload(e, img); e->bw[k].xf_b2[which] = upload(e, b2h); e->bw[k].xf_nch[which] = nch;
-                }
-            // weight images of the split chains (sxf_chain.hip; kernels.h: SxcBParams / SxcAParams).  ONE k order everywhere - the accumulator layout's: inside a
-            // 16-block, position 8 kh + e holds feature 8 (e >> 2) + 4 kh + (e & 3) - because every operand of a product is a converted accumulator tile.
-            {
-                auto perm16 = [](int pos) { const int khh = pos >> 3, ee = pos & 7; return 8 * (ee >> 2) + 4 * khh + (ee & 3); };
-                bool over = false;                     // set by put: a folded value the image being built cannot hold (that chain is not built)
-                auto put = [&](std::vector<uint16_t>& img, size_t hi_at, size_t lo_at, double wv) {
-                    const float ws = (float)(wv * 1024.0);
-                    if (!(std::fabs(ws) < kSplitImgMax)) { over = true; return; }
-                    const _Float16 hh = (_Float16)ws;
-                    img[hi_at] = half_bits((float)hh);
-                    img[lo_at] = half_bits(ws - (float)hh);
-                };
-                // F1 chunk at `base`: 32 output rows (null = padding) x DP1 columns, h plane then l plane; gamma folded into the weights, W beta + bias in column D
-                auto f1_chunk = [&](std::vector<uint16_t>& img, size_t base, int DP1, int K, const float* const* wrow, const float* bias, const float* g, const float* beta) {
-                    for (int r = 0; r < 32; ++r) {
-                        if (!wrow[r]) continue;
-                        double bsum = bias[r];
-                        for (int col = 0; col < DP1; ++col) {
-                            const int f = (col & ~15) + perm16(col & 15);
-                            if (f < K) {
-                                const double wv = wrow[r][f];
-                                if (beta) bsum += wv * beta[f];
-                                put(img, base + (size_t)r * DP1 + col, base + (size_t)32 * DP1 + (size_t)r * DP1 + col, g ? wv * g[f] : wv);
-                            }
-                        }
-                        for (int col = 0; col < DP1; ++col)
-                            if ((col & ~15) + perm16(col & 15) == K) put(img, base + (size_t)r * DP1 + col, base + (size_t)32 * DP1 + (size_t)r * DP1 + col, bsum);
-                    }
-                };
-                // F2 chunk c at `base`: DP2 output rows x 32 input positions (inputs 32 c ..), h plane then l plane
-                auto f2_chunk = [&](std::vector<uint16_t>& img, size_t base, int DP2, int c, const float* Wm, int N, int K, int ldw, double scale) {
-                    for (int n = 0; n < N; ++n)
-                        for (int pos = 0; pos < 32; ++pos) {
-                            const int kk = 32 * c + (pos & ~15) + perm16(pos & 15);
-                            if (kk < K) put(img, base + (size_t)n * 32 + pos, base + (size_t)32 * DP2 + (size_t)n * 32 + pos, scale * Wm[(size_t)n * ldw + kk]);
-                        }
-                };
-                auto padded = [&](const std::vector<float>& v, int n, float scale) { std::vector<float> o(n, 0.f); for (size_t i = 0; i < v.size() && (int)i < n; ++i) o[i] = scale * v[i]; return o; };
-                for (size_t k = 0; k < e->blocks.size(); ++k) {
-                    const EcBlock& b = e->blocks[k];
-                    BlockW& W = e->bw[k];
-                    const int D = b.dim_model, De = b.dim_expand;
-                    const std::string pb = "blocks." + std::to_string(k);
-                    const std::string mh = pb + ".multi_head_self_attention_module.", cm = pb + ".convolution_module.layers.";
-                    auto ffn_image = [&](int which, int Dw) -> const uint16_t* {       // FeedForwardModule `which` at width Dw: per 32 hidden units an F1 chunk + an F2 chunk
-                        const int F = Dw * b.ff_ratio;
-                        const std::string pf = pb + (which ? ".feed_forward_module2.layers." : ".feed_forward_module1.layers.");
-                        const HostTensor *g = find(e, pf + "0.weight"), *bt = find(e, pf + "0.bias"), *w1 = find(e, pf + "1.weight"), *b1 = find(e, pf + "1.bias"),
-                                         *w2 = find(e, pf + "4.weight");
-                        if (!g || !bt || !w1 || !b1 || !w2 || (int64_t)w1->data.size() != (int64_t)F * Dw || (int64_t)w2->data.size() != (int64_t)F * Dw ||
-                            (int)g->data.size() != Dw || (int)bt->data.size() != Dw || (int)b1->data.size() != F || !W.xf_b2[which]) return nullptr;
-                        int ks, nt; sxf_ffn_shape(Dw, &ks, &nt);
-                        const int DP1 = 16 * ks, DP2 = 32 * nt, nch = (F + 31) / 32;
-                        const size_t per = (size_t)64 * (DP1 + DP2);
-                        std::vector<uint16_t> img((size_t)nch * per, 0);
-                        for (int c = 0; c < nch; ++c) {
-                            const float* rows[32]; float bias[32];
-                            for (int r = 0; r < 32; ++r) { const int h = 32 * c + r; rows[r] = h < F ? w1->data.data() + (size_t)h * Dw : nullptr; bias[r] = h < F ? b1->data[h] : 0.f; }
-                            f1_chunk(img, (size_t)c * per, DP1, Dw, rows, bias, g->data.data(), bt->data.data());
-                            f2_chunk(img, (size_t)c * per + (size_t)64 * DP1, DP2, c, w2->data.data(), Dw, F, F, 0.5);
-                        }
-                        return over ? nullptr : upload(e, img);
-                    };
-                    if (sxc_supported(D) && sxf_ffn_supported(D)) {
-                        int ks, nt; sxf_ffn_shape(D, &ks, &nt);
-                        const int DP1 = 16 * ks, DP2 = 32 * nt, nte = (De + 31) / 32;
-                        const HostTensor *wo = find(e, mh + "mhsa.output_layer.weight"), *bo = find(e, mh + "mhsa.output_layer.bias"), *lg = find(e, cm + "0.weight"), *lb = find(e, cm + "0.bias"),
-                                         *w1 = find(e, cm + "2.weight"), *b1 = find(e, cm + "2.bias"), *ag = find(e, mh + "norm.weight"), *ab = find(e, mh + "norm.bias");
-                        const HostTensor *wq[3] = {find(e, mh + "mhsa.query_layer.weight"), find(e, mh + "mhsa.key_layer.weight"), find(e, mh + "mhsa.value_layer.weight")};
-                        const HostTensor *bq[3] = {find(e, mh + "mhsa.query_layer.bias"), find(e, mh + "mhsa.key_layer.bias"), find(e, mh + "mhsa.value_layer.bias")};
-                        bool ok = wo && bo && lg && lb && w1 && b1 && ag && ab && (int)wo->data.size() == D * D && (int)bo->data.size() == D && (int)lg->data.size() == D && (int)lb->data.size() == D &&
-                                  (int64_t)w1->data.size() == (int64_t)2 * De * D && (int)b1->data.size() == 2 * De && (int)ag->data.size() == D && (int)ab->data.size() == D;
-                        for (int i = 0; i < 3; ++i) ok = ok && wq[i] && bq[i] && (int)wq[i]->data.size() == D * D && (int)bq[i]->data.size() == D;
-                        if (ok) {
-                            over = false;
-                            std::vector<uint16_t> io((size_t)nt * 64 * DP2, 0);
-                            for (int c = 0; c < nt; ++c) f2_chunk(io, (size_t)c * 64 * DP2, DP2, c, wo->data.data(), D, D, D, 1.0);
-                            std::vector<uint16_t> ip((size_t)2 * nte * 64 * DP1, 0);
-                            for (int c = 0; c < 2 * nte; ++c) {          // chunk 2 j: value rows 32 j .., chunk 2 j + 1: their gate rows De + 32 j ..
-                                const float* rows[32]; float bias[32];
-                                for (int r = 0; r < 32; ++r) { const int f = 32 * (c >> 1) + r, n = (c & 1) * De + f; rows[r] = f < De ? w1->data.data() + (size_t)n * D : nullptr; bias[r] = f < De ? b1->data[n] : 0.f; }
-                                f1_chunk(ip, (size_t)c * 64 * DP1, DP1, D, rows, bias, lg->data.data(), lb->data.data());
-                            }
-                            std::vector<uint16_t> iq((size_t)3 * nt * 64 * DP1, 0);
-                            for (int c = 0; c < 3 * nt; ++c) {
-                                const int which = c / nt, cc = c % nt;
-                                const float* rows[32]; float bias[32];
-                                for (int r = 0; r < 32; ++r) { const int n = 32 * cc + r; rows[r] = n < D ? wq[which]->data.data() + (size_t)n * D : nullptr; bias[r] = n < D ? bq[which]->data[n] : 0.f; }
-                                f1_chunk(iq, (size_t)c * 64 * DP1, DP1, D, rows, bias, ag->data.data(), ab->data.data());
-                            }
-                            if (!over) {
-                            W.xc_wo = upload(e, io); W.xc_bo = upload(e, padded(bo->data, DP2, 1.f)); W.xc_p1 = upload(e, ip); W.xc_nch_p1 = 2 * nte; W.xc_qkv = upload(e, iq);
-                            W.xc_f[0] = ffn_image(0, D);
-                            W.xc_in = W.xc_f[0] != nullptr;
-                            }
-                        }
-                    }
-                    if (sxc_supported(De) && sxf_ffn_supported(De)) {
-                        int ks, nt; sxf_ffn_shape(De, &ks, &nt);
-                        const int DP2 = 32 * nt;
-                        const HostTensor *w2 = find(e, cm + "7.weight"), *b2 = find(e, cm + "7.bias");
-                        if (w2 && b2 && (int64_t)w2->data.size() == (int64_t)De * De && (int)b2->data.size() == De) {
-                            over = false;
-                            std::vector<uint16_t> i2((size_t)nt * 64 * DP2, 0);
-                            for (int c = 0; c < nt; ++c) f2_chunk(i2, (size_t)c * 64 * DP2, DP2, c, w2->data.data(), De, De, De, 1.0);
-                            if (!over) {
-                                W.xc_p2 = upload(e, i2); W.xc_bp2 = upload(e, padded(b2->data, DP2, 1.f));
-                                W.xc_f[1] = ffn_image(1, De);
-                                W.xc_out = W.xc_f[1] != nullptr;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        for (const EcBlock& b : e->blocks) {
-            auto key = std::make_pair(b.max_pos, b.dim_model);
-            if (e->xtab.count(key)) continue;
-            const int rows = 2 * b.max_pos - 1, D = b.dim_model;
-            std::vector<float> t((size_t)rows * D, 0.f), denom(D / 2);
-            for (int i = 0; i < D / 2; ++i) denom[i] = std::pow(10000.0f, (2.0f * (float)i) / (float)D);
-            for (int r = 0; r < rows; ++r) {
-                const float pos = (float)(b.max_pos - 1 - r);
-                for (int i = 0; i < D / 2; ++i) { const float a = pos / denom[i]; t[(size_t)r * D + 2 * i] = std::sin(a); t[(size_t)r * D + 2 * i + 1] = std::cos(a); }
-            }
-            e->xtab[key] = upload(e, t);
-        }
-    }
+    if (int rc = pack_encoder(e)) return rc;
     for (void* p : e->allocs) if (!p) return fail("device allocation failed");
     if (hipDeviceSynchronize() != hipSuccess) return fail("upload failed");
     e->host.clear();
@@ -2146,6 +1196,28 @@ int effconf_encoder_finalize(EcEncoder* e) {
     e->finalized = true;
     return 0;
 }
+
+#ifdef EFFCONF_DEBUG_ABI        // libeffconf_debug.so only (include/effconf_debug.h)
+int effconf_debug_pack_digest(EcEncoder* e, uint64_t* digest, int64_t* buffers, int64_t* bytes) {
+    if (!e) return fail("null encoder");
+    // The packing runs on a scratch copy of the handle that borrows the host tensors, so e itself never holds a packed pointer: it stays not finalized, and a
+    // later effconf_encoder_finalize works as if this had not run.  No HIP call: the copy owns no device buffer and upload only hashes.
+    std::map<std::string, HostTensor> host = std::move(e->host);
+    e->host.clear();
+    EcEncoder t(*e);
+    t.host = std::move(host);
+    t.cfg.blocks = t.blocks.data();
+    t.allocs.clear();
+    EcEncoder::PackDigest d;
+    t.dry = &d;
+    const int rc = pack_encoder(&t);
+    e->host = std::move(t.host);
+    if (digest) *digest = d.sum;
+    if (buffers) *buffers = d.buffers;
+    if (bytes) *bytes = d.bytes;
+    return rc;
+}
+#endif
 
 size_t effconf_encoder_workspace_bytes(const EcEncoder* e, int32_t batch, int32_t n, int32_t from_audio) {
     if (!e || batch <= 0 || n <= 0) return 0;

@@ -113,7 +113,7 @@ def make_audio(lengths, seed: int = 1234) -> np.ndarray:
 # Stressed parameter sets: statistics of trained checkpoints and values at the split-precision images' limits
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 
-SPLIT_IMG_LIMIT = 65000.0 / 1024.0   # largest |folded value| the fused split images hold (encoder.hip: w * 2^10 as two fp16 halves, kSplitImgMax)
+SPLIT_IMG_LIMIT = 65000.0 / 1024.0   # largest |folded value| the fused split images hold (csrc/pack.h: w * 2^10 as two fp16 halves, kSplitImgMax)
 STRESS_PROFILES = ("trained", "boundary")
 
 
@@ -135,13 +135,13 @@ def silence_floor_mel(batch: int, n_mels: int, tm: int, lengths: List[int] | Non
 
 
 def fold_bn(sd: Dict[str, np.ndarray], prefix: str):
-    """BatchNorm(eval) as per-channel (scale, shift) in float32 - the fold of encoder.hip bn_fold."""
+    """BatchNorm(eval) as per-channel (scale, shift) in float32 - the fold of csrc/pack.hip bn_fold."""
     s = (sd[prefix + ".weight"] / np.sqrt(sd[prefix + ".running_var"] + np.float32(1e-5))).astype(np.float32)
     return s, (sd[prefix + ".bias"] - sd[prefix + ".running_mean"] * s).astype(np.float32)
 
 
 def split_image_values(plan: EncoderPlan, sd: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-    """Every value the fused split images hold, folded as encoder.hip folds them at finalize (before the 2^10 scale), by image:
+    """Every value the fused split images hold, folded as csrc/pack.hip folds them at finalize (before the 2^10 scale), by image:
     ``sub.taps`` (conv tap x BN scale), ``sub.shift`` (BN shift + conv bias x BN scale, tap 9), ``linear``; per block k ``ffn{1,2}.w1`` (gamma W1),
     ``ffn{1,2}.bias`` (b1 + W1 beta), ``ffn{1,2}.w2`` (W2 / 2), ``pw1.w`` / ``pw1.bias`` (conv LayerNorm folded), ``qkv.w`` / ``qkv.bias``
     (attention LayerNorm folded), ``wo``, ``pw2``."""
@@ -174,7 +174,7 @@ def split_image_values(plan: EncoderPlan, sd: Dict[str, np.ndarray]) -> Dict[str
 
 def _boundary(plan: EncoderPlan, sd: Dict[str, np.ndarray]) -> None:
     """Profile ``boundary``: synthetic weights except for one folded value of each fused split image moved ACROSS the images' limit
-    (|w| < 65000 / 1024 = 63.48 after folding; encoder.hip kSplitImgMax) to ~100, and one moved just below it.  Targets the fused images of
+    (|w| < 65000 / 1024 = 63.48 after folding; csrc/pack.h kSplitImgMax) to ~100, and one moved just below it.  Targets the fused images of
     sxf_sub.hip (conv tap x BN scale, BN shift), sxf_ffn.hip / sxf_chain.hip (gamma W1, the bias column b1 + W1 beta) and sxf_chain.hip's
     pointwise-1 (gamma W, conv-module LayerNorm folded).  The values below the limit are as close to it as the ACTIVATION envelopes allow on
     the tests' inputs: 60 for biases / shifts and for the pointwise-1 gate row (sigmoid input); 40 for gamma W1 (the Swish operand, |x| < 255,

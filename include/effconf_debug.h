@@ -58,6 +58,12 @@ int effconf_debug_spin(double microseconds, void* stream);
  * out (dev, 2 * blocks uint64): {cycles, bytes} per workgroup. */
 int effconf_debug_lds_fill(int32_t mode, int32_t blocks, int32_t waves, const void* src, size_t window, int32_t kib_per_wave, int32_t passes, uint64_t* out, void* stream);
 
+/* HOST function (no GPU, no HIP call): a dry run of effconf_encoder_finalize on the tensors loaded into `enc` (csrc/pack.hip: every packing step), with the copy
+ * to the device replaced by a hash of each buffer (length + contents; the per-buffer hashes are combined order-independently).  Returns what finalize would
+ * return (effconf_last_error carries the same text) and the digest, the number of buffers and their bytes.  `enc` itself is left as it was - not finalized, no
+ * packed pointer, the host tensors kept - so a later effconf_encoder_finalize works as if this had not run.  The sinusoid and mel tables go through libm:
+ * compare digests within one machine only (tools/pack_digest.py, tests/test_pack_host.py). */
+int effconf_debug_pack_digest(EcEncoder* enc, uint64_t* digest, int64_t* buffers, int64_t* bytes);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

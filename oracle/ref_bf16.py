@@ -13,45 +13,45 @@ Conventions
   stored number is ``q`` of it.  Their bf16 inputs are taken as they are (already bf16 numbers in the trace).
 * ``folded``: how the LayerNorm in front of a Linear is applied.
   True  (fused chains): weight q(float32(W * gamma)) - product in float32, then rounded - bias b + float32(sum_k W[n][k] beta[k]) with the sum
-        in double, operand q((x - mean) * rstd) without gamma / beta.  encoder.hip pack_linear ("W diag(gamma), b + W beta (fp32, before the
-        bf16 rounding)", the h_f2bf(row_ptr[n][src] * ln_g[src]) line and the double accumulator below it); chain.hip ln_stats (two-pass, eps
+        in double, operand q((x - mean) * rstd) without gamma / beta.  pack.hip pack_linear ("W diag(gamma), b + W beta (fp32, before the
+        bf16 rounding)", the bf16_rn(rows[n][src] * ln_g[src]) line and the double accumulator below it); chain.hip ln_stats (two-pass, eps
         1e-6, pad-column correction of the variance) and norm_frags (pack_bf2(fmaf(x, rstd, -mean * rstd))).
   False (per-module kernels: norm.hip launch_layernorm, the prologue LayerNorm of rsgemm.hip): operand q(LN(x) * gamma + beta), weight q(W).
-* FFN: hidden q(swish(.)) (chain.hip ffn_stage: pack_bf2(swishf_(h[r]), ...)), second weight q(W2 / 2) and bias b2 / 2 (encoder.hip
+* FFN: hidden q(swish(.)) (chain.hip ffn_stage: pack_bf2(swishf_(h[r]), ...)), second weight q(W2 / 2) and bias b2 / 2 (pack.hip
   pack_ffn2_permuted(..., 0.5f) and the ``hb`` vectors next to it; the per-module kernel multiplies by alpha = 0.5 after the product, which is
   the same number), accumulated onto the float32 residual row.  Block-final LayerNorm: float32, affine, not rounded (ChainParams::ln[1],
   chain.hip ln_inplace).
 * Chain B: x += att_o . q(Wo)^T + bo, then glu = q(a * sigmoid(b)) of the pointwise-1 product on the (folded) conv-module LayerNorm (chain.hip:
   "a * sigmoid(b) for channels ..." / pack_bf2(o[0], o[1])).
-* Depthwise convolution: BatchNorm folded into taps and bias in float32 (encoder.hip bn_fold and the "[k][De] fp32" table), bf16 input, output
+* Depthwise convolution: BatchNorm folded into taps and bias in float32 (pack.hip bn_fold, conv_bn_fold and the "[k][De] fp32" table), bf16 input, output
   q(swish(.)).  conv_res of transition blocks: q(x[::s]) (norm.hip launch_cast_rows) times q(W), float32 out.
 * Q / K / V: qu = q(Q + b + u), k = q(K + b), v = q(V + b) (chain.hip: pack_bf2(acc + ua.x, ...) with the bias as the accumulator's initial value;
   gemm.hip EPI_QKV_NAT: "if (which == 0) add += p.u[nc]"); chunk-padding rows qu = q(u), k = v = 0 (attention.hip attn_pad_rows_nat_kernel /
   attn_pad_rows_ragged_kernel).  In the attention kernel qv = q(float(qu) + float32(v - u)) - a second rounding (attention2.hip, the
-  pack_bf2(... + da.x ...) lines; the table v - u is built in float32 in encoder.hip, ``W.dvu``).  E = q(q(sinusoid rows) . q(Wpos)^T + bpos)
-  (encoder.hip build_pos_table: h_f2bf(std::sin(a)); launch_gemm(pe, EPI_BF16)).  Scores, softmax and P V are not rounded here; ``round_p``
+  pack_bf2(... + da.x ...) lines; the table v - u is built in float32 in pack.hip, dvu_table -> ``W.dvu``).  E = q(q(sinusoid rows) . q(Wpos)^T + bpos)
+  (pack.hip build_pos_table: bf16_rn(std::sin(a)); launch_gemm(pe, EPI_BF16)).  Scores, softmax and P V are not rounded here; ``round_p``
   rounds exp(s - rowmax) to bf16 before P V - the kernel rounds P against its RUNNING maximum, which cannot be reproduced exactly, so
   ``round_p`` belongs to the noise model only.
 * Front end (conv.hip + gemm.hip, sublinear.hip, sublinear2.hip, sublinear3.hip, conv2.hip + gemm.hip), one contract for all five routes:
-  - Layer 1: BatchNorm2d folded into the nine taps and the bias in float32 - scale = gamma / sqrt(var + 1e-5f), shift = beta - mean * scale (encoder.hip
-    bn_fold), tap = w * scale, bias = b * scale + shift (effconf_encoder_finalize: the ``w9[ch * 9 + j] = w->data[ch * 9 + j] * sc[ch]`` /
-    ``bb[ch] = b->data[ch] * sc[ch] + sh[ch]`` loop) - float32 mel, float32 accumulation, Swish, then ONE rounding to bf16: conv.hip
+  - Layer 1: BatchNorm2d folded into the nine taps and the bias in float32 - scale = gamma / sqrt(var + 1e-5f), shift = beta - mean * scale (pack.hip
+    bn_fold), tap = w * scale, bias = b * scale + shift (pack.hip conv_bn_fold: ``(double)w[...] * sc[ch]``, exact, rounded once to float32 /
+    ``b[ch] * sc[ch] + sh[ch]``) - float32 mel, float32 accumulation, Swish, then ONE rounding to bf16: conv.hip
     subsample_conv_kernel ``pack_bf2(swishf_(acc[0][tl]), swishf_(acc[1][tl]))``, sublinear.hip ``pa[i] = make_uint4(pack_bf2(r[0], r[1]), ...)``,
     sublinear2.hip ``y[e] = swishf_(cv[8 * j + e])`` / ``xf[2 * g + j] = ... pack_bf2(y[0], y[1])``, sublinear3.hip ``q.hh[pr] = pack_bf2(q.x[2 * pr], ...)``,
     conv2.hip subsample_conv_cl_kernel ``pack_bf2(r0, r1)``.  Nothing else is rounded: taps, bias and mel stay float32 numbers.
   - ``conv="split"`` (sublinear2.hip, sublinear3.hip: the convolution on the matrix pipe): both operands as hi + lo with hi = the float32 number with
-    its low 16 bits cleared (sublinear2.hip split_hi, sublinear3.hip hi_bits, encoder.hip put_tap ``u & 0xFFFF0000u``) and lo = q(x - hi)
-    (``pack_bf2(v[2 * e] - __uint_as_float(h0), ...)``, put_tap ``h_f2bf(v - hf)``), the sum W_hi P_hi + W_hi P_lo + W_lo P_hi - the lo lo term, 2^-14 of a
-    product at most, is dropped - and the folded bias as tap slot 9 against a patch entry of 1.0 (encoder.hip ``tab[ch * 16 + 9] = bb[ch]`` /
-    ``put_tap(ch, 9, bb[ch])``, sublinear2.hip ``tp[1] = 1.0f``).  An evaluation of the same contract to ~2^-14 of sum |w| |p|: it belongs to the noise
+    its low 16 bits cleared (sublinear2.hip split_hi, sublinear3.hip hi_bits, pack.h bf16_pair_trunc ``u >> 16``) and lo = q(x - hi)
+    (``pack_bf2(v[2 * e] - __uint_as_float(h0), ...)``, bf16_pair_trunc ``bf16_rn(f - bf16_value(*hi))``), the sum W_hi P_hi + W_hi P_lo + W_lo P_hi - the lo lo term, 2^-14 of a
+    product at most, is dropped - and the folded bias as tap slot 9 against a patch entry of 1.0 (pack.hip ``(*tab)[(size_t)ch * 16 + 9] = tbias[ch]`` /
+    ``tap_enc(tbias[ch], at + 9, ...)``, sublinear2.hip ``tp[1] = 1.0f``).  An evaluation of the same contract to ~2^-14 of sum |w| |p|: it belongs to the noise
     model only, the float64 reference is the exact convolution.
   - Time padding: zeros in front of frame 0 and behind the utterance's own last mel frame where lengths are given (ragged batches: conv.hip
     ``tmb = rag_tm ? rag_tm[b] : Tm``, sublinear3.hip ``Tv = p.mel_len ? p.mel_len[b] : p.Tm``, conv2.hip ``Tmb``); a rectangular batch reads the rectangle as it
     is, pad frames included.  Frequency padding: zero rows at -1 and n_mels.
   - Layer 2 of the two-layer subsampler (conv2.hip conv2_igemm_kernel) from the stored bf16 layer-1 image, which a ragged batch zero-fills behind every
-    utterance's own (len - 1) / 2 + 1 frames (subsample_conv_cl_kernel ``t < T1b ? swishf_(a.x) : 0.f``): weight q(float32(w2 * scale2)) (encoder.hip
-    ``h_f2bf(w2->data[...] * sc2[n])``), float32 bias b2 * scale2 + shift2 added after the sum, Swish, bf16 store (``f2bf(swishf_(acc[mi][ni][r] + bz))``).
-  - Linear: act . q(W)^T + b with a float32 bias, float32 out (encoder.hip pack_linear and the ``wf`` / ``wr`` / ``wimg`` loops: h_f2bf(lw->data[...])).
+    utterance's own (len - 1) / 2 + 1 frames (subsample_conv_cl_kernel ``t < T1b ? swishf_(a.x) : 0.f``): weight q(float32(w2 * scale2)) (pack.hip
+    conv_bn_fold + sub2_conv_image ``bf16_rn((float)wf[...])``), float32 bias b2 * scale2 + shift2 added after the sum, Swish, bf16 store (``f2bf(swishf_(acc[mi][ni][r] + bz))``).
+  - Linear: act . q(W)^T + b with a float32 bias, float32 out (pack.hip pack_linear, sublinear_image, sublinear2_images and front_chunks: bf16_rn(lw[...])).
     The K orders of those images ((fc * Cp + c) * 8 + e; permuted per 16; accumulator order of 32-channel chunks; (f2, c)) are the packers' business:
     ``front_linear`` contracts in the reference's feature order c * F' + f (modules.py:247) and nothing else, which is what makes a wrong permutation visible.
   The trace holds ``subsample`` (the last layer's bf16 activation) where separate kernels write it - fuse_subsample = 0, front ends without a fused
@@ -325,7 +325,7 @@ def pad_rows(qu: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sd, bp, rnd: Ca
 
 def pos_rows(tp: int, bp, dtype, causal: bool = False, rnd: Callable = q, shift: int = 0) -> torch.Tensor:
     """The sinusoid rows the positional projection reads: ref_encoder's rows in ``dtype`` arithmetic, rounded.  The kernels' table is built in
-    float32 (encoder.hip build_pos_table): an angle of up to ~1000 rad carries 6e-5 of float32 error, which moves a few of the rounded sines to
+    float32 (pack.hip build_pos_table): an angle of up to ~1000 rad carries 6e-5 of float32 error, which moves a few of the rounded sines to
     the neighbouring bf16 number - a difference the float32 run of this function has too, so the noise model contains it.
     ``shift`` (tests only): the fault "positional rows shifted by one"."""
     ft = dtype

@@ -11,17 +11,17 @@ The kernels' arithmetic
   Scales, per operand class (split-mode operand envelopes): SA = 2^8 LayerNorm-ed rows and Swish outputs (sxf_ffn.hip:27, sxf_chain.hip:32 -
   acc_to_frags(acc, mean, rstd * SA, SA, ...), swish_frags ``(z * SA) * rcp``; sxf_sub.hip:25 hidden activation), SR = 2^6 operands that are not LayerNorm-ed - the
   attention output and the depthwise output (sxf_chain.hip:33, acc_to_frags(acc, 0.f, SR, SR, ...)), SP = 2^6 the mel patch (sxf_sub.hip:25), SQK = SV_ = 2^8
-  Q + u, K, E, V and SP_ = 2^10 the probabilities (sxf.hip:26), SW = 2^10 every weight image (encoder.hip ``put``: ws = float(w 1024), h = (_Float16)ws - round to
+  Q + u, K, E, V and SP_ = 2^10 the probabilities (sxf.hip:26), SW = 2^10 every weight image (pack.h f16_pair_s10: ws = float(w 1024), h = (_Float16)ws - round to
   nearest -, l = fp16(ws - h)).
 * Product = a_h w_h + a_h w_l + a_l w_h, fp32 accumulation (sxf_chain.hip g1: one accumulator per product kind, summed ``(h1 + h2) + h3``), the scale undone by
   one exact multiply (UNS = 1 / (SA SW), UNS_R = 1 / (SR SW)).  The l l' term is dropped.
 * Per-module form (split.hip sx_gemm_kernel; sx_common.h split2): x = h + l / 2048 with h = fp16 toward zero of the UNSCALED value, l = fp16((x - h) 2048)
-  clamped to +-65000; weights h = fp16(w), l = fp16((w - h) 2048) (encoder.hip "every 2-D weight ... as two fp16 images"); two accumulators acc = a_h w_h and
+  clamped to +-65000; weights h = fp16(w), l = fp16((w - h) 2048) (pack.h f16_pair_2048, pack.hip split_pair_image); two accumulators acc = a_h w_h and
   acx = a_h w_l + a_l w_h, result fmaf(acx, 1 / 2048, acc) (split.hip:135-137, 189).  It runs the positional projection and conv_res on every route, and every
   product where the fused kernels are off or not built (D = 360 .. 720).
 * LayerNorm: sxf_chain.hip row_stats (mean = sum / D, rstd = rsqrtf(sum (x - mean)^2 / D + 1e-6)) and apply_ln / acc_to_frags ((x - mean) rstd): the float32
   formulas ref_bf16.hardware_like already evaluates, with the rsqrt moved by s ulps.  gamma / beta of a pre-norm are folded into the weight image and its bias
-  column (encoder.hip f1_chunk: ``g ? wv * g[f] : wv``, ``bsum += wv * beta[f]`` in double) - ref_bf16.ln_linear's ``folded`` form, taken here with
+  column (pack.hip f1_chunk: ``g ? wv * g[f] : wv``, ``bsum += wv * beta[f]`` in double) - ref_bf16.ln_linear's ``folded`` form, taken here with
   ``rnd = keep`` (an identity that is not ``ident``).  The bias column is itself a split pair against the operand 1.0: 2^-23 of the bias, not modelled.
 * exp / reciprocal: sx_common.h sx_expf (x log2(e) in two parts, v_exp_f32, first-order correction) and sx_rcp (v_rcp_f32 + one Newton step) in the GLU, the
   depthwise Swish (sxf.hip:459, 485) and chain B's GLU (sxf_chain.hip:588); the FFN Swish of the chains uses the same exp without the constant's low part and a
@@ -99,14 +99,14 @@ def split2(x: torch.Tensor):
 
 
 def weight_same(w: torch.Tensor):
-    """encoder.hip ``put`` of the fused images: ws = float(w 1024), h = fp16(ws), l = fp16(ws - h)."""
+    """pack.h f16_pair_s10, the element of the fused images: ws = float(w 1024), h = fp16(ws), l = fp16(ws - h)."""
     ws = (w.double() * SW).float()
     h = rn16(ws)
     return h, rn16(ws - h)
 
 
 def weight_module(w: torch.Tensor):
-    """encoder.hip, per-module images: h = fp16(w), l = fp16((w - h) 2048)."""
+    """pack.h f16_pair_2048, per-module images: h = fp16(w), l = fp16((w - h) 2048)."""
     w = w.float()
     h = rn16(w)
     return h, rn16((w - h) * LO_SCALE)

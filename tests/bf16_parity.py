@@ -70,7 +70,7 @@ def _misses(x: torch.Tensor, r64: torch.Tensor) -> str:
 
 
 def chain_route(fuse, width):
-    """The fused chains serve this stage width (encoder.hip: chain_max_dim = 256; chain.hip chain_supported) and are on (option fuse_chain)."""
+    """The fused chains serve this stage width (encoder_state.h: chain_max_dim = 256; chain.hip chain_supported) and are on (option fuse_chain)."""
     return bool(fuse) and width % 4 == 0 and 16 <= width <= 256
 
 
@@ -252,7 +252,7 @@ def check_trace(got, out_len, plan, sd, ln, tm, ragged, fuse, label):
             u = q(torch.from_numpy(np.asarray(sd["blocks.%d.multi_head_self_attention_module.mhsa.u" % k])).float())
             assert torch.equal(qu[si.qpad], u.expand(len(si.qpad), -1)) and float(kk[si.qpad].abs().sum()) == 0.0 and float(vv[si.qpad].abs().sum()) == 0.0, (k, "chunk-padding rows")
 
-        # ---- positional rows E (gemm.hip on the table of encoder.hip build_pos_table); the table's own float32 angles are part of the noise model
+        # ---- positional rows E (gemm.hip on the table of pack.hip build_pos_table); the table's own float32 angles are part of the noise model
         tpmax = max(si.tp)
         assert ee.shape[0] == (tpmax if plan.causal else 2 * tpmax - bp.group_size), (k, ee.shape)
         e64, e32 = pos_e(tpmax, sd, bp, F64, plan.causal), pos_e(tpmax, sd, bp, F32, plan.causal)

@@ -151,7 +151,7 @@ def check_split_trace(got, out_len, plan, sd, ln, tm, ragged, route, label, only
             gv = g[si.qidx].double() + (u.double() if i == 0 else 0.0)
             rep.add("qkv", k, stage_ratios(gv, r64[i], [r[i] for r in runs], D, False), lambda gv=gv, i=i, nme=nme: nme + " " + worst_element(gv, r64[i]))
 
-        # ---- positional projection (split.hip on the float32 sinusoid table of encoder.hip)
+        # ---- positional projection (split.hip on the float32 sinusoid table of pack.hip build_pos_table)
         tpmax = max(si.tp)
         assert ee.shape == ((tpmax if plan.causal else 2 * tpmax - bp.group_size), D), (k, ee.shape)
         fe = lambda dt, rnd: Q.pos_e(tpmax, sd, bp, dt, plan.causal, rnd)

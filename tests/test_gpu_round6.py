@@ -122,7 +122,7 @@ def test_depthwise_conv_kernels_alone_vs_the_oracle_depthwise_stage(ksize, chann
     h = F.batch_norm(h, torch.from_numpy(mean).double(), torch.from_numpy(var).double(), torch.from_numpy(gamma).double(), torch.from_numpy(beta).double(),
                      False, 0.0, R.BN_EPS)
     want = (h * torch.sigmoid(h)).transpose(1, 2).numpy()                                       # (B, T, C) float64
-    # what finalize hands the kernels: BatchNorm folded into the taps / bias in fp32 (encoder.hip; SURVEY.md 8a closed form)
+    # what finalize hands the kernels: BatchNorm folded into the taps / bias in fp32 (pack.hip; SURVEY.md 8a closed form)
     sc = (gamma / np.sqrt(var + np.float32(1e-5))).astype(np.float32)
     w_kc = np.ascontiguousarray((w[:, 0, :] * sc[:, None]).T.astype(np.float32))                 # [k][C]
     bias = (cb * sc + beta - mean * sc).astype(np.float32)

@@ -199,7 +199,7 @@ def test_build_plan_accepts_the_front_end_settings_the_kernel_runs():
                                       (dict(n_mels=0), b"n_mels"), (dict(n_mels=132), b"n_mels"), (dict(n_mels=-4), b"n_mels"),
                                       (dict(n_mels=81), b"n_mels"), (dict(n_mels=65), b"n_mels"), (dict(n_fft=256), b"n_fft")])
 def test_library_refuses_the_same_settings_through_the_abi_before_any_table_is_built(kw, field):
-    """effconf_encoder_create holds the rules of build_mel_tables (one function, csrc/encoder.hip: mel_config_error): a caller of the C ABI that never
+    """effconf_encoder_create holds the rules of build_mel_tables (one function, csrc/pack.hip: mel_config_error): a caller of the C ABI that never
     went through build_plan gets no handle and an error string naming the field - win_length > n_fft used to write in front of a host vector."""
     lib = _lib.load()
     cfg, _keep = ModelCTC.from_config(named_config("Tiny")).encoder._make_config()

@@ -1,5 +1,5 @@
 """CPU: the stressed parameter generator (synth.make_stressed_state_dict) - deterministic, leaves make_state_dict alone, and puts its values
-exactly where its profiles say relative to the fused split images' limit (|w| < 65000 / 1024 after folding, encoder.hip kSplitImgMax)."""
+exactly where its profiles say relative to the fused split images' limit (|w| < 65000 / 1024 after folding, csrc/pack.h kSplitImgMax)."""
 import zlib
 
 import numpy as np
@@ -44,7 +44,7 @@ def test_stressed_generator_is_deterministic(profile):
 
 @pytest.mark.parametrize("name", ["Tiny", "EfficientConformerCTCSmall", "EfficientConformerCTCMedium", "ConformerCTCSmall"])
 def test_boundary_crosses_exactly_the_intended_limits(name):
-    """Folded in numpy as encoder.hip folds them (bn_fold, gamma W, b1 + W beta): the subsampler tap x BN scale and BN shift (one-layer subsampler),
+    """Folded in numpy as pack.hip folds them (bn_fold, gamma W, b1 + W beta): the subsampler tap x BN scale and BN shift (one-layer subsampler),
     block 0's gamma W1 / bias column (FFN1) and pointwise-1 at ~100; nothing else at or beyond the limit; the below-limit values present in the last
     block (FFN2 bias column and pointwise-1 at 60, gamma W1 at 40)."""
     plan = _plan(name)
