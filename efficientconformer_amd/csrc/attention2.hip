@@ -51,6 +51,15 @@ __device__ __forceinline__ void wave_sync() {                   // per-wave LDS 
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// The lane id, computed again where it is asked for (two VALU instructions).  The compiler cannot rematerialise what it derives from threadIdx.x (an argument
+// register), so per-thread addresses that are affine in the lane id and used once per key block were kept in scratch across the block's MFMAs, and their
+// reloads made the loop wait for the K / V / E loads it had just issued.  A volatile statement is neither merged with another one nor hoisted out of the loop.
+__device__ __forceinline__ int lane_now() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 lds_tr16(const char* p) {      // ds_read_b64_tr_b16
     const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
@@ -82,7 +91,8 @@ __global__ __launch_bounds__(NWV * 64, (QT == 1 && NWV == 4 && DP <= 96) ? ((DP 
     char* sE = sV + SM::V_BYTES;
     float* sS = reinterpret_cast<float*>(sE + SM::E_BYTES);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform, and known to be: what is built on it (band rows, skew buffer, first query) lives in SGPRs
     const int c = lane & 15, g = lane >> 4;
     int qtiles = (p.Tg + BI - 1) / BI;
     // utterance b on XCD b % 8: all heads / query tiles of an utterance share one L2, and a length-sorted batch spreads evenly over
@@ -157,9 +167,16 @@ __global__ __launch_bounds__(NWV * 64, (QT == 1 && NWV == 4 && DP <= 96) ? ((DP 
     // the tail paths, i.e. to the loads that can run past the END of a buffer (last rows of the last head), where the bytes are not
     // the library's own and may be NaN patterns.
     uint32_t koffs[NK];                                          // K, V and E share the row stride (launch check), so one offset serves all three
-    auto chunk_row = [&](int n) { int q = tid + NTHR * n; q = q < BJ * CPR ? q : BJ * CPR - 1; return q / CPR; };
-    auto tail_mask = [&](uint4 a, int n) {                      // tail paths only: recomputed there instead of living in registers
-        int q = tid + NTHR * n; q = q < BJ * CPR ? q : BJ * CPR - 1;
+    // tail paths only: everything per-thread is recomputed there (from `t`, a thread id taken inside the path) instead of living in registers
+    auto tid_now = [&]() { return wave * 64 + lane_now(); };
+    auto chunk_row = [&](int t, int n) { int q = t + NTHR * n; q = q < BJ * CPR ? q : BJ * CPR - 1; return q / CPR; };
+    auto chunk_col2 = [&](int t, int n) {                       // byte offset of the chunk inside its row (koffs[n] without the row)
+        int q = t + NTHR * n; q = q < BJ * CPR ? q : BJ * CPR - 1;
+        const int x = (q - (q / CPR) * CPR) * 8;
+        return (uint32_t)(x < dceil ? x : 0) * 2u;
+    };
+    auto tail_mask = [&](uint4 a, int t, int n) {
+        int q = t + NTHR * n; q = q < BJ * CPR ? q : BJ * CPR - 1;
         return mask_chunk(a, p.d - (q - (q / CPR) * CPR) * 8);
     };
 #pragma unroll
@@ -181,11 +198,12 @@ __global__ __launch_bounds__(NWV * 64, (QT == 1 && NWV == 4 && DP <= 96) ? ((DP 
 #pragma unroll
             for (int n = 0; n < NK; ++n) { st_.lk[n] = ld16b(kb + koffs[n]); st_.lv[n] = ld16b(vb + koffs[n]); }
         } else {
+            const int t = tid_now();
 #pragma unroll
             for (int n = 0; n < NK; ++n) {
-                const int kr = chunk_row(n), j = jn + kr;
-                const size_t o = (size_t)(j < Tg ? j : Tg - 1) * RS * 2 + (koffs[n] - (uint32_t)(kr * RS) * 2u);
-                st_.lk[n] = tail_mask(ld16b(reinterpret_cast<const char*>(Kh) + o), n); st_.lv[n] = tail_mask(ld16b(reinterpret_cast<const char*>(Vh) + o), n);
+                const int j = jn + chunk_row(t, n);
+                const size_t o = (size_t)(j < Tg ? j : Tg - 1) * RS * 2 + chunk_col2(t, n);
+                st_.lk[n] = tail_mask(ld16b(reinterpret_cast<const char*>(Kh) + o), t, n); st_.lv[n] = tail_mask(ld16b(reinterpret_cast<const char*>(Vh) + o), t, n);
             }
         }
         if (jn > kbeg) {
@@ -195,12 +213,12 @@ __global__ __launch_bounds__(NWV * 64, (QT == 1 && NWV == 4 && DP <= 96) ? ((DP 
 #pragma unroll
                 for (int n = 0; n < NK; ++n) st_.le[n] = ld16b(eb + koffs[n]);
             } else {
+                const int t = tid_now();
 #pragma unroll
                 for (int n = 0; n < NK; ++n) {
-                    const int er = chunk_row(n);
-                    int r = rnew + er;
+                    int r = rnew + chunk_row(t, n);
                     r = r < 0 ? 0 : (r >= erows ? erows - 1 : r);
-                    st_.le[n] = tail_mask(ld16b(reinterpret_cast<const char*>(Eh) + (size_t)r * ERS * 2 + (koffs[n] - (uint32_t)(er * RS) * 2u)), n);
+                    st_.le[n] = tail_mask(ld16b(reinterpret_cast<const char*>(Eh) + (size_t)r * ERS * 2 + chunk_col2(t, n)), t, n);
                 }
             }
         }
@@ -267,26 +285,20 @@ __global__ __launch_bounds__(NWV * 64, (QT == 1 && NWV == 4 && DP <= 96) ? ((DP 
     // LDS byte offsets of the thread's chunks: K / V tile rows, and the ring rows of a new-row batch for even / odd key blocks
     // (ring row = band row + key offset mod 2 BI = 128: the batch starts at row BI - 1 + 64 * parity)
     static_assert(BI == 64, "ring phases: two (BI == BJ)");
-    uint32_t ldk[NK], ldv[NK], lde[2][NK];
-#pragma unroll
-    for (int n = 0; n < NK; ++n) {
-        int q = tid + NTHR * n;
-        q = q < BJ * CPR ? q : BJ * CPR - 1;
-        const int r = q / CPR, ch = q - r * CPR;
-        ldk[n] = (uint32_t)SM::koff(r, ch);
-        ldv[n] = (uint32_t)(r * SM::VP + ch * 16);
-        lde[0][n] = (uint32_t)SM::koff((BI - 1 + r) & (ERING - 1), ch);
-        lde[1][n] = (uint32_t)SM::koff((BI - 1 + r + 64) & (ERING - 1), ch);
-    }
+    // Computed per block from a fresh thread id (shifts, one xor, one multiply-add per chunk): 4 NK registers that would otherwise live across the block
     constexpr bool FULL = (BJ * CPR) % NTHR == 0;                // every thread owns NK real chunks
     auto publish = [&](const Stage& st_, int j0, int par) __attribute__((always_inline)) {
         __syncthreads();                                         // the previous block's LDS reads are done
+        const int t = tid_now();
 #pragma unroll
         for (int n = 0; n < NK; ++n) {
-            if (FULL || tid + NTHR * n < BJ * CPR) {
-                *reinterpret_cast<uint4*>(sK + ldk[n]) = st_.lk[n];
-                *reinterpret_cast<uint4*>(sV + ldv[n]) = st_.lv[n];
-                if (j0 > kbeg) *reinterpret_cast<uint4*>(sE + lde[par][n]) = st_.le[n];
+            if (FULL || t + NTHR * n < BJ * CPR) {
+                int q = t + NTHR * n;
+                q = q < BJ * CPR ? q : BJ * CPR - 1;
+                const int r = q / CPR, ch = q - r * CPR;
+                *reinterpret_cast<uint4*>(sK + SM::koff(r, ch)) = st_.lk[n];
+                *reinterpret_cast<uint4*>(sV + r * SM::VP + ch * 16) = st_.lv[n];
+                if (j0 > kbeg) *reinterpret_cast<uint4*>(sE + SM::koff((BI - 1 + r + 64 * par) & (ERING - 1), ch)) = st_.le[n];
             }
         }
         __syncthreads();

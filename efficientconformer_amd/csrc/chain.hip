@@ -57,6 +57,15 @@ struct ChainDev {
     int ldr, ld2;         // row pitch (elements) shared by every row-shaped weight of the chain / by the FFN second weights
 };
 
+// The lane id, computed again where it is asked for (two VALU instructions; a volatile statement is neither merged with another one nor hoisted).  For lane
+// constants that two distant stages share: the compiler cannot rematerialise what derives from threadIdx.x (an argument register) and parks it in scratch between
+// the stages - and a scratch reload waits on the vmcnt queue the ring's DMAs are in.
+__device__ __forceinline__ int lane_now() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
 // ---- C-layout helpers -----------------------------------------------------------------------------------------------------
 template <int NT>
 __device__ __forceinline__ void add_cvec(f32x16 (&xc)[NT], const float* sv, int half) {    // xc[t][r] += sv[column]
@@ -581,6 +590,16 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
         float mean, rstd;
         ln_stats<NT>(xc, D, mean, rstd);
         norm_frags<KS>(xc, mean, rstd, xf);
+        // the slab reader's lane constants, made again for this loop: the g0 stage's copies (q0, w1row and the KS wrap-around terms the compiler derives from
+        // q0) were spilled behind that stage and reloaded here, each reload draining the two ring chunks in flight
+        const int lane = lane_now(), lr = lane & 31, half = lane >> 5;
+        const int q0 = (half + lr) % P1;
+        const int w1row = lr * (P1 * 16);
+        auto wfrag = [&](const char* slab, int s) __attribute__((always_inline)) {
+            int q = q0 + 2 * s;
+            q -= q >= P1 ? P1 : 0;
+            return *reinterpret_cast<const bf16x8*>(slab + w1row + q * 16);
+        };
         for (int c = 0; c < n_g1; ++c) {
             const char* buf = advance();
             refill();
@@ -729,7 +748,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
         }
     }
     // ---- residual rows out
-    if constexpr (!POST) store_x<NT, 0>(reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D, m_base, p.M, stg, lane, xc);
+    // chain B takes a fresh lane id here: with the kernel's own, the window offsets of the loads at the top are kept (in scratch) for these stores
+    if constexpr (ISB) store_x<NT, 0>(reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D, m_base, p.M, stg, lane_now(), xc);
+    else if constexpr (!POST) store_x<NT, 0>(reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D, m_base, p.M, stg, lane, xc);
     if constexpr (PROF) {
         CH_TICK(8);
         if (lane == 0 && (blockIdx.x & 7) == 0) {      // a 1/8 sample of the workgroups reports (keeps the atomics out of the measurement)

@@ -60,6 +60,17 @@ struct ChainDev3 {
 #define C3_PIN_TILE(ofs, tile) ((void)0)
 #endif
 
+// The lane id, computed again where it is asked for.  Everything a lane derives from threadIdx.x is affine in this value, but the compiler cannot
+// rematerialise a kernel argument register: lane / lr / half and the addresses built from them were kept in scratch across the stages, and their reloads
+// share the in-order vmcnt queue with the ring's DMAs.  A volatile statement is neither merged with another one nor hoisted: each phase below takes its
+// own copy, whose live range ends with the phase.
+__device__ __forceinline__ int lane_now() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+#define C3_LANE() const int lane = lane_now(), lr = lane & 31, half = lane >> 5; (void)lr; (void)half
+
 template <int V> using ic3 = std::integral_constant<int, V>;
 template <int I, int N, class F> __device__ __forceinline__ void static_for3(F&& f) {
     if constexpr (I < N) { f(ic3<I>{}); static_for3<I + 1, N>(f); }
@@ -102,7 +113,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
     if constexpr (PROF) t0 = __builtin_readcyclecounter();
 #define C3_TICK(i) do { if constexpr (PROF) { asm volatile("" ::: "memory"); const unsigned long long t1_ = __builtin_readcyclecounter(); ph[i] += t1_ - t0; t0 = t1_; } } while (0)
-#define C3_DUMP() do { if constexpr (PROF) { C3_TICK(9); if (lane == 0 && pr == 0 && (blockIdx.x & 7) == 0) { for (int i = 0; i < 10; ++i) atomicAdd(prof + 16 * role + i, ph[i]); atomicAdd(prof + 16 * role + 15, 1ull); } } } while (0)
+#define C3_DUMP() do { if constexpr (PROF) { C3_TICK(9); if (lane_now() == 0 && pr == 0 && (blockIdx.x & 7) == 0) { for (int i = 0; i < 10; ++i) atomicAdd(prof + 16 * role + i, ph[i]); atomicAdd(prof + 16 * role + 15, 1ull); } } } while (0)
     if constexpr (PROF) {          // which SIMD does wave w of a 12-wave workgroup run on?  (HW_REG_HW_ID bits 5:4; workgroup 0 reports)
         unsigned hwid;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
@@ -117,14 +128,12 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* tile_base = smem + NBUF3 * BUF;
     float* sf = reinterpret_cast<float*>(tile_base + 4 * S3_TILE);
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int pr = wave & 3, role = wave >> 2;               // row tile; 0 = A, 1 / 2 = B0 / B1 (waves w, w + 4, w + 8 share a SIMD)
-    const int lr = lane & 31, half = lane >> 5;
     const int m_base = (blockIdx.x * 4 + pr) * 32;
     char* win0 = tile_base + pr * S3_TILE;                   // the row tile's two windows and its hand-off slots
     char* win1 = win0 + S3_WIN;
-    float* slot0 = reinterpret_cast<float*>(win0 + 2 * S3_WIN) + lane;       // B0's hand-off slot, B1's
+    float* slot0 = reinterpret_cast<float*>(win0 + 2 * S3_WIN);              // B0's hand-off slot, B1's (one float per lane)
     float* slot1 = slot0 + 64;
     const int D = p.D;
 
@@ -144,15 +153,20 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     const float* s_g1b = sf + cd.nf[6];
     const float* s_uv = sf + cd.nf[7];
 
-    const int q0 = (half + lr) % P1;
-    const int w1row = lr * (P1 * 16);
-    auto wfrag = [&](const char* slab, int s) __attribute__((always_inline)) {
-        int q = q0 + 2 * s;
-        q -= q >= P1 ? P1 : 0;
-        return *reinterpret_cast<const bf16x8*>(slab + w1row + q * 16);
+    // reader of a [32 rows][P1 pieces] weight slab; made once per stage, so that its two lane constants live no longer than the stage's loop
+    auto make_wfrag = [&]() __attribute__((always_inline)) {
+        C3_LANE();
+        const int q0 = (half + lr) % P1;
+        const int w1row = lr * (P1 * 16);
+        return [q0, w1row](const char* slab, int s) __attribute__((always_inline)) {
+            int q = q0 + 2 * s;
+            q -= q >= P1 ? P1 : 0;
+            return *reinterpret_cast<const bf16x8*>(slab + w1row + q * 16);
+        };
     };
     // every wave reads the published fragments of a round: fragments r0 .. r0 + 3 from window 0, KSH + r0 .. from window 1
     auto read_round = [&](bf16x8 (&xf)[KS], auto r0c) __attribute__((always_inline)) {
+        C3_LANE();
         constexpr int r0 = decltype(r0c)::value;
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -164,6 +178,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     // destination rows of the Q/K/V write-out: (b, t) -> (b * Tp + t) * D for the 2 rows a lane stores per half-tile instruction pair
     // bias of the two 32-row slabs of ring chunk c -> accumulators; the MFMAs of a Q/K/V chunk
     auto acc_bias = [&](f32x16 (&acc)[2], int c) __attribute__((always_inline)) {
+        C3_LANE();
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -172,7 +187,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
                 acc[j][4 * q + 0] = v.x; acc[j][4 * q + 1] = v.y; acc[j][4 * q + 2] = v.z; acc[j][4 * q + 3] = v.w;
             }
     };
-    auto g1_mfma = [&](f32x16 (&acc)[2], const bf16x8 (&xf)[KS], const char* buf) __attribute__((always_inline)) {
+    auto g1_mfma = [&](f32x16 (&acc)[2], const bf16x8 (&xf)[KS], const char* buf, auto wfrag) __attribute__((always_inline)) {
         constexpr int FB = 2;
 #pragma unroll
         for (int s0 = 0; s0 < KS; s0 += FB) {
@@ -189,6 +204,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     // tile j (32 columns) of Q/K/V chunk c out through window `stg`: registers r = 8g .. 8g + 7 of the tile are the columns 64c + 32j + 16g + 8 half + (0..7)
     // of the stacked [Q | K | V] (row permutation of pack_linear_chunkperm); Q columns get + u.  Returns the number of store instructions
     auto qkv_out_tile = [&](const f32x16& a, int c, int j, char* stg) __attribute__((always_inline)) -> int {
+        C3_LANE();
         wave_sync();
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -237,12 +253,13 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         int mine = (role + 3 - op) % 3;                      // first chunk of this wave
+        const auto wfrag = make_wfrag();
 #pragma unroll 1
         for (int c = 0; c < n_g1 + 2; ++c) {
             const char* buf = nullptr;
             if (c < n_g1) buf = adv(); else wg_barrier();
             const int ph = c - mine;                         // 0: MFMAs of chunk `mine`, 1 / 2: its column tiles out
-            if (ph == 0 && c < n_g1) { acc_bias(acc, c); g1_mfma(acc, xf, buf); rf(); }
+            if (ph == 0 && c < n_g1) { acc_bias(acc, c); g1_mfma(acc, xf, buf, wfrag); rf(); }
             else {
                 rf();
                 if (ph == 1 && mine < n_g1) st += qkv_out_tile(acc[0], mine, 0, win0);
@@ -262,6 +279,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             return buf;
         };
         auto no_rf = []() {};
+        const auto wfrag = make_wfrag();
         bf16x8 xf[KS];
         if constexpr (PRE) {
 #pragma unroll
@@ -291,6 +309,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             return h;
         };
         auto swish_out = [&](const f32x16& h, char* slot) __attribute__((always_inline)) {
+            C3_LANE();
             uint32_t w[8];
 #pragma unroll
             for (int r = 0; r < 16; r += 2) w[r >> 1] = pack_bf2(swishf_(h[r]), swishf_(h[r + 1]));
@@ -311,12 +330,12 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             f32x16 hp;
             {   // i = 0
                 const char* buf = advanceA();
-                hp = gemm1(buf, sb1 + 4 * half, [](int) {});
+                hp = gemm1(buf, sb1 + 4 * (lane_now() >> 5), [](int) {});
             }
 #pragma unroll 1
             for (int i = 1; i < n; ++i) {
                 const char* buf = advanceA();
-                const f32x16 hn = gemm1(buf, sb1 + i * CH + 4 * half, [](int) {});
+                const f32x16 hn = gemm1(buf, sb1 + i * CH + 4 * (lane_now() >> 5), [](int) {});
                 swish_out(hp, ((i - 1) & 1) ? win1 : win0);
                 hp = hn;
                 if constexpr (PROF) asm volatile("s_nop 0" :: "v"(hp[0]), "v"(hp[15]));
@@ -360,12 +379,11 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     __builtin_assume(bidx < NB3);
     const int ct0 = cw * NTH;
     char* stg = cw ? win1 : win0;                            // this wave's window
-    float* my = cw ? slot1 : slot0;
-    const float* pa = cw ? slot0 : slot1;
     uint32_t off_r[PER], off_f[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const int i = bidx + NB3 * k;
+        const int lane = lane_now();
         off_r[k] = i < KS ? dma_rows32_off<P1>(cd.ldr, i, lane) : dma_rows32_off<P1>(cd.ldr, i - KS, lane) + (uint32_t)(32 * cd.ldr) * 2u;
         off_f[k] = i < KS ? off_r[k] : (uint32_t)((i - KS) * 1024 + lane * 16);        // second FFN weights: chunk-major images (contiguous slabs)
     }
@@ -413,7 +431,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         if (gc + NBUF3 - 2 < total) issue(gc + NBUF3 - 2);
         C3_TICK(3);
     };
-    for (int i = bidx; i < cd.nfl_kb; i += NB3) glds16(reinterpret_cast<const char*>(p.consts) + (size_t)i * 1024 + lane * 16, reinterpret_cast<char*>(sf) + i * 1024);
+    for (int i = bidx; i < cd.nfl_kb; i += NB3) glds16(reinterpret_cast<const char*>(p.consts) + (size_t)i * 1024, (uint32_t)(lane_now() * 16), reinterpret_cast<char*>(sf) + i * 1024);
 #pragma unroll
     for (int c = 0; c < NBUF3 - 1; ++c)
         if (c < total) issue(c);
@@ -421,6 +439,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     f32x16 xc[NTH];
     // own fragments -> window (4 per round); `reader` waves read both windows
     auto publish = [&](const bf16x8 (&own)[KSH], bf16x8 (&xf)[KS], bool reader) __attribute__((always_inline)) {
+        C3_LANE();
         static_for3<0, XR>([&](auto I) {
             constexpr int r = decltype(I)::value;
             if (r > 0) wg_barrier();
@@ -433,6 +452,9 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         wg_barrier();
     };
     auto ln_stats = [&](float& mean, float& rstd) __attribute__((always_inline)) {
+        C3_LANE();
+        float* my = (cw ? slot1 : slot0) + lane;
+        const float* pa = (cw ? slot0 : slot1) + lane;
         auto psum = [&](float sum) __attribute__((always_inline)) {
 #pragma unroll
             for (int t = 0; t < NTH; ++t)
@@ -480,6 +502,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         }
     };
     auto add_cvec = [&](const float* sv) __attribute__((always_inline)) {
+        C3_LANE();
         int ofs = 32 * ct0 + 4 * half;
 #pragma unroll
         for (int tt = 0; tt < NTH; ++tt) {
@@ -494,6 +517,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         }
     };
     auto store_x = [&]() __attribute__((always_inline)) {
+        C3_LANE();
 #pragma unroll
         for (int tt = 0; tt < NTH; ++tt) {
             wave_sync();
@@ -508,6 +532,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
 
     // ---- rows in
     {
+        C3_LANE();
         const char* xb = reinterpret_cast<const char*>(p.X);
         u32x4 vx[4 * NTH] = {};
         static_for3<0, NTH>([&](auto I) { constexpr int tt = decltype(I)::value; s3_load<4 * tt>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane, vx); });
@@ -529,6 +554,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         // ---- x += g0(A): the bf16 operand rows (each B wave loads half of the k-steps, both end up with all of them), then the wave's own column tiles
         bf16x8 xa[KS];
         {
+        C3_LANE();
             // one exchange round per 128-byte window (4 k-steps) of the wave's half of the operand row: load, fragments, window, barrier, both halves back.
             // Window by window (not all loads first): with xc and the growing xa live, a second set of staging registers does not fit 168
             static_assert(XR == (KSH + 3) / 4, "one round per window");
@@ -564,6 +590,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         if (total >= NBUF3) wait_vmcnt<PER * (NBUF3 - 2)>(); else wait_vmcnt<0>();
         wg_barrier();
         add_cvec(s_b0);
+        const auto wfrag = make_wfrag();
 #pragma unroll
         for (int c = 0; c < (NT + 1) / 2; ++c) {
             const char* buf = advance();
@@ -590,9 +617,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         wg_barrier();
     }
 
-    const int k2 = (half + (lr >> 2)) & 3;
-    const int w2off0 = lr * 64 + k2 * 16 + ct0 * 2048, w2off1 = lr * 64 + (k2 ^ 2) * 16 + ct0 * 2048;
-    auto gemm2 = [&](const char* w2, const bf16x8 hf0, const bf16x8 hf1) __attribute__((always_inline)) {
+    auto gemm2 = [&](const char* w2, int w2off0, int w2off1, const bf16x8 hf0, const bf16x8 hf1) __attribute__((always_inline)) {
 #pragma unroll
         for (int tt = 0; tt < NTH; ++tt) {
             const bf16x8 wb0 = *reinterpret_cast<const bf16x8*>(w2 + tt * 2048 + w2off0);
@@ -611,6 +636,9 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             publish(own, xnone, false);
         }
         add_cvec(sb2);
+        C3_LANE();                                            // the loop's lane constants: made here, dead after the loop
+        const int k2 = (half + (lr >> 2)) & 3;
+        const int w2off0 = lr * 64 + k2 * 16 + ct0 * 2048, w2off1 = lr * 64 + (k2 ^ 2) * 16 + ct0 * 2048;
         // iteration i: the refill, then the second GEMM of hidden chunk i - 2 (hf from window (i - 2) & 1, published by A in iteration i - 1)
 #pragma unroll 1
         for (int i = 0; i < n + 2; ++i) {
@@ -619,7 +647,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             if (i >= 2) {
                 const char* slot = ((i - 2) & 1) ? win1 : win0;
                 const bf16x8 h0 = *reinterpret_cast<const bf16x8*>(slot + lane * 16), h1 = *reinterpret_cast<const bf16x8*>(slot + 1024 + lane * 16);
-                gemm2(buf + HALF, h0, h1);
+                gemm2(buf + HALF, w2off0, w2off1, h0, h1);
                 if constexpr (PROF) asm volatile("s_nop 0" :: "v"(xc[0][0]), "v"(xc[NTH - 1][15]));
             }
             C3_TICK(2);
@@ -629,6 +657,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         ffn_stage_b(s_f0b2, n_f0);
         float mean, rstd;
         ln_stats(mean, rstd);
+        C3_LANE();
         const float* sg = s_ln + 32 * ct0 + 4 * half;
         const float* sb = s_ln + DP + 32 * ct0 + 4 * half;
         int ofs = 0;

@@ -1,0 +1,82 @@
+"""Compile-time resources of the stage-2 / stage-3 chain kernels and of the head-width-64 attention kernel (no GPU: hipcc cross-compiles for gfx950).
+
+A scratch reload inside one of these kernels waits on the vmcnt queue its own prefetches are in (LDS-DMAs of the weight ring, the K / V / E loads one key block
+ahead): the reload of a spilled lane constant drains what was just issued.  The kernels are kept free of scratch altogether; their occupancy (waves per SIMD) is
+what the launch shapes were chosen for and may not be traded for registers.  Only the compiler's kernel-resource-usage remarks are read."""
+import os
+import re
+import shutil
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+
+import pytest
+
+from efficientconformer_amd import _build
+
+
+def _hipcc():
+    for c in (os.environ.get("HIPCC"), "/opt/rocm/bin/hipcc", shutil.which("hipcc")):
+        if c and os.path.exists(c):
+            return c
+    return None
+
+
+pytestmark = pytest.mark.skipif(_hipcc() is None, reason="hipcc not found")
+
+_REMARKS = {}
+
+
+def _compile(source):
+    cmd = [_hipcc()] + _build.FLAGS + _build.NO_PACKED_FP32 + _build.PER_SOURCE.get(source, []) + \
+          ["--cuda-device-only", "-c", os.path.join(_build.CSRC, source), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rows, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = rows.setdefault(m.group(1), {})
+            continue
+        for key, pat in (("vgpr", r" VGPRs: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"), ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)")):
+            m = re.search(pat, line)
+            if m and cur is not None:
+                cur[key] = int(m.group(1))
+    names = subprocess.run(["c++filt"], input="\n".join(rows), capture_output=True, text=True).stdout.split("\n")
+    return {re.sub(r"\(anonymous namespace\)::", "", n).split("(")[0].replace("void ", ""): v for n, v in zip(names, rows.values())}
+
+
+def _resources(source):
+    """{demangled kernel name: {"vgpr", "occupancy", "scratch"}} of one source under the product flags (the sources are compiled once, side by side)."""
+    if not _REMARKS:
+        sources = sorted({s for s, _, _, _ in BROUGHT_TO_ZERO + STAY_AT_ZERO})
+        with ThreadPoolExecutor(max_workers=len(sources)) as ex:
+            _REMARKS.update(zip(sources, ex.map(_compile, sources)))
+    return _REMARKS[source]
+
+
+# (source, kernel, waves per SIMD, scratch bytes per lane).  Every kernel of this list is at zero scratch: none needs a bound of its own.
+BROUGHT_TO_ZERO = [
+    ("chain3.hip", "chain3_kernel<16, 1, false>", 3, 0),
+    ("chain3.hip", "chain3_kernel<16, 2, false>", 3, 0),
+    ("chain3.hip", "chain3_kernel<16, 3, false>", 3, 0),
+    ("attention2.hip", "relpos_attention2_kernel<64, 4, 1, 1>", 3, 0),
+    ("chain.hip", "chain_kernel<12, 8, 3, 0, false>", 2, 0),
+]
+# kernels of the flagship step that had no scratch before: they keep none (and their occupancy)
+STAY_AT_ZERO = [
+    ("chain.hip", "chain_kernel<8, 4, 2, 0, false>", 2, 0),
+    ("chain.hip", "chain_kernel<8, 4, 2, 1, false>", 2, 0),
+    ("chain2.hip", "chain2_kernel<16, false>", 2, 0),
+    ("attention2.hip", "relpos_attention2_kernel<96, 4, 1, 1>", 2, 0),
+]
+
+
+@pytest.mark.parametrize("source,kernel,occupancy,scratch", BROUGHT_TO_ZERO + STAY_AT_ZERO, ids=[k for _, k, _, _ in BROUGHT_TO_ZERO + STAY_AT_ZERO])
+def test_kernel_keeps_its_occupancy_and_uses_no_scratch(source, kernel, occupancy, scratch):
+    res = _resources(source)
+    assert kernel in res, (kernel, sorted(res))
+    got = res[kernel]
+    print("%s: %d VGPRs, %d waves/SIMD, %d scratch bytes/lane" % (kernel, got["vgpr"], got["occupancy"], got["scratch"]))
+    assert got["occupancy"] == occupancy, got
+    assert got["scratch"] == scratch, got
+    assert got["vgpr"] <= 512 // occupancy, got
