@@ -66,6 +66,10 @@ SIGNATURES = {
     "effconf_rnnt_greedy": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _P, _I32, _P, _SZ, _P]),
     "effconf_rnnt_beam_workspace_bytes": (_SZ, [_P, _I32, _I32, _I32, _I32, _I32]),
     "effconf_rnnt_beam": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _F32P, _P, _I32, _P, _SZ, _P]),
+    "effconf_rnnt_lattice_workspace_bytes": (_SZ, [_P, _I32, _I32, _I32]),
+    "effconf_rnnt_lattice": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _I64P, _I32, C.c_float, _F32P, _F32P, _P, _P, _SZ, _P]),
+    "effconf_rnnt_align_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "effconf_rnnt_align": (C.c_int, [_F32P, _F32P, _I64P, _I64P, _I32, _I32, _I32, _F32P, _F32P, _P, _F32P, _P, _P, _SZ, _P]),
     "effconf_encoder_set_option": (C.c_int, [_P, C.c_char_p, _I32]),
     "effconf_profile_enable": (C.c_int, [_P, _I32]),
     "effconf_profile_read": (C.c_int, [_P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),

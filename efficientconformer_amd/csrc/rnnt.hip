@@ -678,7 +678,8 @@ int effconf_rnnt_finalize(EcRnnt* r) {
     }
     r->we = (float*)upload(r, we->data.data(), we->data.size() * 4);
     r->be = (float*)upload(r, be->data.data(), be->data.size() * 4);
-    if (!d_emb || !d_wih || !d_bsum || !d_gin || !r->dev.whh4 || !r->dev.wd4 || !r->dev.bd || !r->dev.wj4 || !r->dev.bj || !r->we || !r->be)
+    r->wd = (float*)upload(r, wd->data.data(), wd->data.size() * 4);
+    if (!d_emb || !d_wih || !d_bsum || !d_gin || !r->dev.whh4 || !r->dev.wd4 || !r->dev.bd || !r->dev.wj4 || !r->dev.bj || !r->we || !r->be || !r->wd)
         return ec_fail("device allocation / upload failed");
     // Gin[y] = W_ih emb[y] + (b_ih + b_hh)   for every token id (Embedding rows are the only LSTM inputs, decoders.py:55)
     if (launch_sgemm_nt(d_emb, H, d_wih, H, d_bsum, d_gin, 4 * H, V, 4 * H, H, nullptr) != 0) return ec_fail("Gin GEMM launch failed");

@@ -102,6 +102,7 @@ struct EcRnnt {
     ecrnnt::RnntDev dev{};
     float* we = nullptr;     // linear_encoder.weight [J][De]
     float* be = nullptr;
+    float* wd = nullptr;     // linear_decoder.weight [J][H], row-major (the lattice's GEMM over all (b, u) rows)
     bool finalized = false;
     int cluster_by_slice = 1;   // cluster decode: workgroup -> XCD mapping (see rnnt_cluster_kernel)
     int cluster_mode = -1;   // -1 auto (cluster decode for batches >= 2 x the cluster's utterances), 0 per-utterance kernel, 1 force cluster

@@ -7,12 +7,16 @@ of the reference — one decoder call, one joint call and one ``.argmax()`` host
 persistent HIP kernel per batch (effconf_rnnt_greedy).  ``beam_search_decoding`` (transducer.py:188-327) runs as one persistent
 HIP kernel per batch as well (effconf_rnnt_beam, one workgroup per utterance), with the reference's algorithm, tie rules and fp32
 scores; the neural-LM and n-gram (KenLM) shallow fusion terms are not implemented, which is what the reference computes without an LM
-checkpoint and n-gram file.  Training (``forward`` over the full (T, U) lattice, RNN-T loss) is out of scope (HISTORY.md).
+checkpoint and n-gram file.  For a KNOWN transcript, ``lattice`` gives the two log-probabilities per (t, u) cell the RNN-T loss sees
+(csrc/rnnt_lattice.hip: the (B, T, U + 1, V) logits of transducer.py:88-107 never reach memory), ``score_labels`` log P(y | x) = -rnnt_loss
+and ``align`` the frame at which each token is emitted (csrc/rnnt_align.hip: forward recursion and Viterbi over the lattice).  Training
+(``forward`` with gradients, the RNN-T loss' backward) is out of scope (HISTORY.md).
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional
+import os
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -24,6 +28,20 @@ from .encoders import ConformerEncoder
 
 _JOINT_MODES = {"sum": 0}
 _JOINT_ACTS = {"tanh": 0}
+
+
+class TransducerAlignment(NamedTuple):
+    """Forced alignment of one utterance (``Transducer.align``): token u is emitted at encoder frame frame[u], i.e. at second time[u]
+    (frame x ``ConformerEncoder.frame_seconds``); token_logp[u] is its log-probability at that lattice cell, ``score`` the log-probability
+    of the whole best path (its blanks included), ``log_likelihood`` log P(tokens | audio) over all paths.  status: 0 ok, 1 tokens but no
+    frames, 2 a token id outside 1 .. vocab - 1 (then frame is -1 and both scores -inf)."""
+    tokens: List[int]
+    frame: List[int]
+    time: List[float]
+    token_logp: List[float]
+    score: float
+    log_likelihood: float
+    status: int
 
 
 class RnnDecoder(nn.Module):
@@ -107,8 +125,9 @@ class Transducer(nn.Module):
         return load_checkpoint(self, path)
 
     def forward(self, batch):
-        raise NotImplementedError("Transducer.forward builds the (B, T, U+1, V) training lattice (transducer.py:88-107): "
-                                  "training is out of scope of the native inference path; use greedy_tokens / gready_search_decoding")
+        raise NotImplementedError("Transducer.forward returns the (B, T, U+1, V) training logits (transducer.py:88-107): training is out of "
+                                  "scope of the native inference path; lattice() gives the per-cell blank / label log-probabilities of a "
+                                  "transcript, score_labels() its log-likelihood, align() its token frames")
 
     # ------------------------------------------------------------------ native handle
     def _ensure_rnnt(self):
@@ -258,3 +277,149 @@ class Transducer(nn.Module):
         (``tokenizer.decode(best_hyp["prediction"][1:])`` per utterance, transducer.py:323), otherwise the id lists."""
         ids = self.beam_tokens(x, x_len, beam_size)
         return [self.tokenizer.decode(i) for i in ids] if self.tokenizer is not None else ids
+
+    # ------------------------------------------------------------------ lattice scoring, forced alignment
+    def _ids(self, y):
+        """Strings -> id lists through the tokenizer; anything else as it is."""
+        if not isinstance(y, torch.Tensor) and len(y) and isinstance(y[0], str):
+            if self.tokenizer is None:
+                raise _lib.EffconfError("string targets need a tokenizer (tokenizer.encode)")
+            return [self.tokenizer.encode(r) for r in y]
+        return y
+
+    def _targets(self, y, y_len, device):
+        """(targets (B, U) i32, target_len (B,) i64) on `device` from a padded integer tensor + lengths, a list of id lists, or a list of
+        strings (needs a tokenizer).  A list is padded on the host and copied once."""
+        if isinstance(y, torch.Tensor):
+            if y.dim() != 2:
+                raise _lib.EffconfError("targets must be (batch, tokens); got shape %s" % (tuple(y.shape),))
+            tg = y.to(device=device, dtype=torch.int32).contiguous()
+            if y_len is None:
+                y_len = torch.full((y.shape[0],), y.shape[1], dtype=torch.int64)
+            return tg, torch.as_tensor(y_len).to(device=device, dtype=torch.int64).contiguous()
+        rows = [[int(c) for c in r] for r in self._ids(y)]
+        lens = [len(r) for r in rows] if y_len is None else [int(v) for v in (y_len.tolist() if hasattr(y_len, "tolist") else y_len)]
+        host = np.zeros((len(rows), max([len(r) for r in rows] + [0])), dtype=np.int32)
+        for i, r in enumerate(rows):
+            host[i, :len(r)] = r
+        return torch.from_numpy(host).to(device), torch.tensor(lens, dtype=torch.int64).to(device)
+
+    @staticmethod
+    def _workspace(nbytes: int, device):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        fill = os.environ.get("EFFCONF_POISON_WORKSPACE", "")
+        if fill:                    # test hook (include/effconf.h): the byte a fresh workspace is filled with
+            ws.fill_(int(fill))
+        return ws
+
+    def lattice(self, f: torch.Tensor, f_len: Optional[torch.Tensor], y, y_len=None):
+        """The RNN-T lattice of encoder outputs f (B, T, Denc) fp32 and transcripts `y` ((B, U) integers + `y_len`, or a list of id lists) on
+        the GPU (effconf_rnnt_lattice), temperature ``self.tmp`` -> (lp_blank, lp_label (B, T, U + 1) f32, status (B,) i32).  For t < f_len[b],
+        u <= y_len[b]: lp_blank = log P(blank | t, u), lp_label = log P(y[u] | t, u) (-inf at u = y_len[b]); 0 outside.  With tmp = 1 these
+        are the entries of log_softmax(joint logits) the RNN-T loss reads.  include/effconf.h has the details."""
+        if f.dim() != 3:
+            raise _lib.EffconfError("encoder outputs must be (batch, frames, dim); got shape %s" % (tuple(f.shape),))
+        if not f.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        if not 0 < self.tmp < float("inf"):
+            raise _lib.EffconfError("decoding_params['tmp'] must be > 0; got %r" % (self.tmp,))
+        dev = f.device
+        tg, tl = self._targets(y, y_len, dev)
+        b, t, _ = f.shape
+        if tg.shape[0] != b or tl.shape[0] != b:
+            raise _lib.EffconfError("targets: %d rows for %d utterances" % (tg.shape[0], b))
+        u = int(tg.shape[1])
+        with torch.cuda.device(dev):
+            self._ensure_rnnt()
+            lib = _lib.load()
+            nbytes = int(lib.effconf_rnnt_lattice_workspace_bytes(self._rnnt, b, t, u))
+            if nbytes == 0:
+                raise _lib.EffconfError("effconf_rnnt_lattice_workspace_bytes rejected (batch %d, T %d, U %d): %s"
+                                        % (b, t, u, lib.effconf_last_error().decode()))
+            f = f.contiguous().float()
+            if f_len is None:
+                f_len = torch.full((b,), t, dtype=torch.int64, device=dev)
+            f_len = f_len.to(device=dev, dtype=torch.int64).contiguous()
+            lp_blank = torch.empty(b, t, u + 1, dtype=torch.float32, device=dev)
+            lp_label = torch.empty(b, t, u + 1, dtype=torch.float32, device=dev)
+            status = torch.empty(b, dtype=torch.int32, device=dev)
+            ws = self._workspace(nbytes, dev)
+            _lib.check(lib.effconf_rnnt_lattice(self._rnnt, f.data_ptr(), f_len.data_ptr(), b, t, tg.data_ptr(), tl.data_ptr(), u, float(self.tmp),
+                                                lp_blank.data_ptr(), lp_label.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                torch.cuda.current_stream(dev).cuda_stream), "rnnt_lattice")
+        return lp_blank, lp_label, status
+
+    def align_lattice(self, lp_blank: torch.Tensor, lp_label: torch.Tensor, f_len: Optional[torch.Tensor], y_len, scores_only: bool = False,
+                      status: Optional[torch.Tensor] = None):
+        """The lattice's dynamic programs on the GPU (effconf_rnnt_align) -> dict of device tensors: ``log_likelihood`` (B,) f32 =
+        log P(y | x) over all paths, ``status`` (B,) i32 (starts from `status`, the lattice's, when given) and, unless `scores_only`,
+        ``score`` (B,) f32 = log-probability of the best path, ``token_frame`` (B, U) i32 (the frame token u is emitted at, -1 at or beyond
+        y_len) and ``token_logp`` (B, U) f32."""
+        if lp_blank.dim() != 3 or lp_blank.shape != lp_label.shape:
+            raise _lib.EffconfError("planes must be two (batch, frames, tokens + 1) tensors; got %s and %s" % (tuple(lp_blank.shape), tuple(lp_label.shape)))
+        b, t, e = lp_blank.shape
+        if e < 1:
+            raise _lib.EffconfError("planes need at least the column u = 0")
+        u = e - 1
+        dev = lp_blank.device
+        lib = _lib.load()
+        nbytes = int(lib.effconf_rnnt_align_workspace_bytes(b, t, u))
+        if nbytes == 0:
+            raise _lib.EffconfError("effconf_rnnt_align_workspace_bytes rejected (batch %d, T %d, U %d): %s"
+                                    % (b, t, u, lib.effconf_last_error().decode()))
+        if not lp_blank.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        with torch.cuda.device(dev):
+            lp_blank, lp_label = lp_blank.contiguous().float(), lp_label.contiguous().float()
+            if f_len is None:
+                f_len = torch.full((b,), t, dtype=torch.int64, device=dev)
+            f_len = torch.as_tensor(f_len).to(device=dev, dtype=torch.int64).contiguous()
+            y_len = torch.as_tensor(y_len).to(device=dev, dtype=torch.int64).contiguous()
+            if f_len.shape[0] != b or y_len.shape[0] != b:
+                raise _lib.EffconfError("lengths: %d / %d entries for %d utterances" % (f_len.shape[0], y_len.shape[0], b))
+            st = torch.zeros(b, dtype=torch.int32, device=dev) if status is None else status.to(device=dev, dtype=torch.int32).clone()
+            out = {"log_likelihood": torch.empty(b, dtype=torch.float32, device=dev), "status": st}
+            if not scores_only:
+                out["score"] = torch.empty(b, dtype=torch.float32, device=dev)
+                out["token_frame"] = torch.empty(b, u, dtype=torch.int32, device=dev)
+                out["token_logp"] = torch.empty(b, u, dtype=torch.float32, device=dev)
+            ws = self._workspace(nbytes, dev)
+            ptr = lambda k: out[k].data_ptr() if k in out else None
+            _lib.check(lib.effconf_rnnt_align(lp_blank.data_ptr(), lp_label.data_ptr(), f_len.data_ptr(), y_len.data_ptr(), b, t, u,
+                                              ptr("log_likelihood"), ptr("score"), ptr("token_frame"), ptr("token_logp"), ptr("status"),
+                                              ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "rnnt_align")
+        return out
+
+    def _encode(self, x, x_len, from_mel):
+        if not x.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        f, f_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+        return f, f_len
+
+    def align(self, x: torch.Tensor, x_len: Optional[torch.Tensor], y, y_len=None, from_mel: bool = False) -> List[TransducerAlignment]:
+        """Token timestamps of known transcripts: encoder, ``lattice``, ``align_lattice`` -> one ``TransducerAlignment`` per utterance.
+        `y`: a padded (B, U) integer tensor (+ `y_len`), a list of id lists, or a list of strings when a tokenizer is attached."""
+        y = self._ids(y)
+        f, f_len = self._encode(x, x_len, from_mel)
+        tg, tl = self._targets(y, y_len, f.device)
+        lp_blank, lp_label, status = self.lattice(f, f_len, tg, tl)
+        out = self.align_lattice(lp_blank, lp_label, f_len, tl, status=status)
+        fs = self.encoder.frame_seconds
+        host = {k: v.cpu() for k, v in out.items()}                     # one D2H copy per batch (per output tensor)
+        tg, tl = tg.cpu(), tl.cpu()
+        recs = []
+        for i in range(tg.shape[0]):
+            n = max(0, min(int(tl[i]), tg.shape[1]))
+            fr = host["token_frame"][i, :n].tolist()
+            recs.append(TransducerAlignment(tg[i, :n].tolist(), fr, [k * fs for k in fr], host["token_logp"][i, :n].tolist(),
+                                            float(host["score"][i]), float(host["log_likelihood"][i]), int(host["status"][i])))
+        return recs
+
+    def score_labels(self, x: torch.Tensor, x_len: Optional[torch.Tensor], y, y_len=None, from_mel: bool = False) -> torch.Tensor:
+        """log P(y | x) of every utterance, (B,) fp32 on the device (-inf where the transcript cannot be scored): the lattice and its
+        forward recursion alone (no Viterbi pass, no back-pointers), = -rnnt_loss at tmp = 1."""
+        y = self._ids(y)
+        f, f_len = self._encode(x, x_len, from_mel)
+        tg, tl = self._targets(y, y_len, f.device)
+        lp_blank, lp_label, status = self.lattice(f, f_len, tg, tl)
+        return self.align_lattice(lp_blank, lp_label, f_len, tl, scores_only=True, status=status)["log_likelihood"]

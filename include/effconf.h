@@ -282,6 +282,31 @@ int effconf_rnnt_beam(EcRnnt* r, const float* enc_out, const int64_t* out_len, i
                       float temperature, int32_t max_expansions, int32_t* tokens, int32_t* token_len, float* score, int32_t* status,
                       int32_t max_tokens, void* workspace, size_t workspace_bytes, void* stream);
 
+/* RNN-T lattice (csrc/rnnt_lattice.hip): for a known transcript, the two log-probabilities per lattice cell the RNN-T loss and a forced
+ * alignment need, without the (batch, T, U + 1, vocab) logits of transducer.py:88-107.  targets dev i32 (batch, u_max), blank excluded,
+ * target_len dev i64 (batch).  For t < out_len[b] and u <= target_len[b], with logits(t, u) = linear_joint(tanh(linear_encoder(f[t]) +
+ * linear_decoder(g_u))) and g_u the prediction network's output after [0, y_1 .. y_u]:
+ *   lp_blank[b][t][u] = log_softmax(logits / temperature)[0],  lp_label[b][t][u] = log_softmax(logits / temperature)[y_b[u]] (-inf at
+ *   u = target_len[b]);  both dev f32 (batch, t_out, u_max + 1), 0 outside the utterance's rectangle.  fp32 operands on the fp32 matrix
+ * pipe; a cell depends on its own utterance only.  status dev i32 (batch): 0 ok, 1 tokens but no frames, 2 a token outside 1 .. vocab - 1
+ * or target_len outside 0 .. u_max (the utterance's rows of both planes are 0).  u_max <= 1023, batch * t_out * (u_max + 1) < 2^31,
+ * dim_decoder and dim_joint multiples of 16; effconf_rnnt_lattice_workspace_bytes returns 0 for arguments effconf_rnnt_lattice rejects. */
+size_t effconf_rnnt_lattice_workspace_bytes(const EcRnnt* r, int32_t batch, int32_t t_out, int32_t u_max);
+int effconf_rnnt_lattice(EcRnnt* r, const float* enc_out, const int64_t* out_len, int32_t batch, int32_t t_out, const int32_t* targets,
+                         const int64_t* target_len, int32_t u_max, float temperature, float* lp_blank, float* lp_label, int32_t* status,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* RNN-T lattice dynamic programs (csrc/rnnt_align.hip) on such planes (any planes of that shape): log_likelihood dev f32 (batch) =
+ * log P(y | x) over all monotone paths (= -rnnt_loss), and - unless score is NULL (then token_frame / token_logp must be NULL too: the
+ * forward recursion alone, bit-identical log_likelihood) - score dev f32 (batch) = the best path's log-probability including its blanks,
+ * token_frame dev i32 (batch, u_max) = the frame at which token u is emitted, token_logp dev f32 (batch, u_max) = lp_label at that cell;
+ * rows at or beyond target_len[b] are -1 / 0.  Ties take the blank (time) move.  status dev i32 (batch) is read (the lattice's status,
+ * or zeros) and written: a non-zero status is kept, 1 = tokens but no frames, 2 = target_len outside 0 .. u_max; such an utterance has both
+ * scores -inf, token_frame -1 and token_logp 0.  No frames and no tokens: status 0, both scores 0. */
+size_t effconf_rnnt_align_workspace_bytes(int32_t batch, int32_t t_out, int32_t u_max);
+int effconf_rnnt_align(const float* lp_blank, const float* lp_label, const int64_t* out_len, const int64_t* target_len, int32_t batch,
+                       int32_t t_out, int32_t u_max, float* log_likelihood, float* score, int32_t* token_frame, float* token_logp,
+                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Options.  "cache_pos_embeddings" = 1: the positional projections E = pos_layer(R) (reference attentions.py:588, 678)
  * are input independent; they live in the workspace and are recomputed only when that workspace last held a forward of
  * another batch size or number of frames.  The library remembers one tag per workspace pointer (the 16 most recently used),

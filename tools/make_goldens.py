@@ -10,6 +10,7 @@ It refuses to run where /root/reference is absent (e.g. the GPU box).
 
     python tools/make_goldens.py            # regenerate every fixture
     python tools/make_goldens.py --only-rnnt-beam   # only tests/golden/rnnt_beam_*.npz (from the stored rnnt_*.npz encoder outputs)
+    python tools/make_goldens.py --only-rnnt-lattice   # only tests/golden/rnnt_lattice_*.npz (from the stored rnnt_*.npz encoder outputs)
 """
 import os
 import sys
@@ -220,6 +221,55 @@ def rnnt_beam_goldens():
         save("rnnt_beam_" + name, **arrs)
 
 
+RNNT_LATTICE = (("TinyTransducer", (5, 0, 9, 3), 501), ("EfficientConformerTransducerMedium", (17, 30), 502))
+
+
+def rnnt_lattice_targets(name):
+    """The fixed transcripts of the lattice goldens: token ids 1 .. V - 1 from a seeded generator, padded with 0."""
+    cfg = named_config(name)
+    lens, seed = next((l, s) for n, l, s in RNNT_LATTICE if n == name)
+    rng = np.random.default_rng(seed)
+    y = np.zeros((len(lens), max(lens)), dtype=np.int32)
+    for i, u in enumerate(lens):
+        y[i, :u] = rng.integers(1, cfg["decoder_params"]["vocab_size"], u)
+    return y, np.asarray(lens, dtype=np.int64), seed
+
+
+def rnnt_lattice_goldens():
+    """RNN-T lattice: the reference's own RnnDecoder and JointNetwork run as Transducer.forward runs them (transducer.py:96-104: y padded
+    with the start token, the decoder over the packed (B, U + 1) batch, the joint network's (B, T, U + 1, V) logits) on the encoder outputs
+    stored in rnnt_<name>.npz (blank bias 1.2), reduced with log_softmax to the two fp32 planes the RNN-T loss reads: column 0 and column
+    y[u] of every cell.  Outside an utterance's rectangle the planes are 0; lp_label is -inf at u = U."""
+    _stub_third_party()
+    import models.decoders as dec
+    import models.joint_networks as jn
+    for name, _, _ in RNNT_LATTICE:
+        cfg = named_config(name)
+        g = np.load(os.path.join(OUT, "rnnt_%s.npz" % name))
+        f, f_len, seed, bb = torch.from_numpy(g["f"]), torch.from_numpy(g["f_len"]), int(g["weight_seed"]), 1.2
+        sd = synth.make_transducer_state_dict(f.shape[-1], cfg["decoder_params"], cfg["joint_params"], seed, blank_bias=bb)
+        decoder = dec.RnnDecoder(cfg["decoder_params"]).eval()
+        joint = jn.JointNetwork(f.shape[-1], cfg["decoder_params"]["dim_model"], cfg["decoder_params"]["vocab_size"], cfg["joint_params"]).eval()
+        decoder.load_state_dict(to_torch({k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}), strict=True)
+        joint.load_state_dict(to_torch({k[len("joint_network."):]: v for k, v in sd.items() if k.startswith("joint_network.")}), strict=True)
+        y, y_len, tseed = rnnt_lattice_targets(name)
+        with torch.no_grad():
+            yp = torch.nn.functional.pad(torch.from_numpy(y).long(), pad=(1, 0, 0, 0), value=0)
+            gg, _ = decoder(yp, None, torch.from_numpy(y_len) + 1)
+            lp = torch.log_softmax(joint(f, gg), dim=-1)                      # (B, T, U + 1, V)
+        b, t, e = lp.shape[:3]
+        lpb, lpl = np.zeros((b, t, e), dtype=np.float32), np.zeros((b, t, e), dtype=np.float32)
+        for i in range(b):
+            n, u = int(f_len[i]), int(y_len[i])
+            lpb[i, :n, :u + 1] = lp[i, :n, :u + 1, 0].numpy()
+            lpl[i, :n, u] = -np.inf
+            for k in range(u):
+                lpl[i, :n, k] = lp[i, :n, k, int(y[i, k])].numpy()
+        print("  %s: frames %s, tokens %s" % (name, f_len.tolist(), y_len.tolist()))
+        save("rnnt_lattice_" + name, weight_seed=np.int64(seed), blank_bias=np.float32(bb), target_seed=np.int64(tseed), targets=y,
+             target_len=y_len, f_len=f_len.numpy(), lp_blank=lpb, lp_label=lpl)
+
+
 STREAMING = (("causal", dict(causal=True)), ("ctx_l20_r4", dict(left_context=20, right_context=4)),
              ("causal_l12", dict(causal=True, left_context=12)), ("ctx_l3_r0", dict(left_context=3, right_context=0)))
 
@@ -250,10 +300,13 @@ def main():
         return rnnt_goldens(enc_mod)
     if "--only-rnnt-beam" in sys.argv:
         return rnnt_beam_goldens()
+    if "--only-rnnt-lattice" in sys.argv:
+        return rnnt_lattice_goldens()
     if "--only-streaming" in sys.argv:
         return streaming_goldens(enc_mod)
     rnnt_goldens(enc_mod)
     rnnt_beam_goldens()
+    rnnt_lattice_goldens()
     streaming_goldens(enc_mod)
 
     # ---- 1. tiny config: every module output, two sequence lengths (T1 % 3 == 0 and != 0)
