@@ -1,0 +1,121 @@
+// The effconf_debug_* entries of include/effconf_debug.h: libeffconf_debug.so only (tests and tools), never linked into libeffconf.so.
+#include "encoder_state.h"
+#include "pack.h"
+#include "../../include/effconf_debug.h"
+
+extern "C" {
+
+int effconf_debug_pack_digest(EcEncoder* e, uint64_t* digest, int64_t* buffers, int64_t* bytes) {
+    if (!e) return fail("null encoder");
+    // The packing runs on a scratch copy of the handle that borrows the host tensors, so e itself never holds a packed pointer: it stays not finalized, and a
+    // later effconf_encoder_finalize works as if this had not run.  No HIP call: the copy owns no device buffer and upload only hashes.
+    std::map<std::string, HostTensor> host = std::move(e->host);
+    e->host.clear();
+    EcEncoder t(*e);
+    t.host = std::move(host);
+    t.cfg.blocks = t.blocks.data();
+    t.allocs.clear();
+    EcEncoder::PackDigest d;
+    t.dry = &d;
+    const int rc = pack_encoder(&t);
+    e->host = std::move(t.host);
+    if (digest) *digest = d.sum;
+    if (buffers) *buffers = d.buffers;
+    if (bytes) *bytes = d.bytes;
+    return rc;
+}
+
+int effconf_debug_mel(EcEncoder* e, int32_t variant, int32_t extra_lds, const float* audio, int32_t batch, int32_t n_samples, float* mel,
+                      uint32_t* counters, void* stream) {
+    if (!e || !e->finalized) return fail("encoder not finalized");
+    const int Tm = n_samples / e->cfg.hop_length + 1;
+    EC_TRY(launch_mel_debug(variant, extra_lds, audio, batch, n_samples, e->mel, e->cfg.n_fft, e->cfg.hop_length, e->cfg.n_mels, Tm,
+                            e->cfg.normalize, e->cfg.mean, e->cfg.std, mel, counters, (hipStream_t)stream));
+    return 0;
+}
+
+int effconf_debug_neighbour(int32_t kind, int32_t blocks, int32_t lds_bytes, int32_t iters, float* buf, size_t n_floats, void* stream) {
+    EC_TRY(launch_debug_neighbour(kind, blocks, lds_bytes, iters, buf, n_floats, (hipStream_t)stream));
+    return 0;
+}
+
+int effconf_debug_gemm(const uint16_t* a, int32_t lda, const uint16_t* w, int32_t ldw, const float* bias, int32_t m, int32_t n, int32_t k,
+                       int32_t epi, int32_t wide, void* c, int32_t ldc, const float* r, int32_t ldr, float alpha, void* stream) {
+    if (!a || !w || !bias || !c) return fail("null argument");
+    if (epi < EPI_F32 || epi > EPI_GLU_BF16 || (epi == EPI_RESID_F32 && !r)) return fail("epilogue: 0 f32, 1 bf16, 2 swish bf16, 3 residual f32, 4 GLU bf16");
+    if (wide < 0 || wide > 3) return fail("wide: 0 .. 3");
+    GemmParams p{};
+    p.A = a; p.lda = lda; p.W = w; p.ldw = ldw; p.bias = bias; p.M = m; p.N = n; p.K = k;
+    p.C = c; p.ldc = ldc; p.R = r; p.ldr = ldr; p.alpha = alpha; p.wide = wide;
+    if (wide >= 2 && !gemm256_supported(p, epi)) return fail("gemm256 does not take this shape / alignment");
+    EC_TRY(launch_gemm(p, epi, (hipStream_t)stream));
+    return 0;
+}
+
+int effconf_debug_sx_gemm(const float* a, int32_t lda, const uint16_t* w_hi, const uint16_t* w_lo, int32_t ldh, const float* bias, int32_t m, int32_t n,
+                          int32_t k, int32_t epi, float* c, int32_t ldc, const float* r, int32_t ldr, float alpha, void* stream) {
+    SxGemmParams q{};
+    q.g.A = a; q.g.lda = lda; q.g.bias = bias; q.g.M = m; q.g.N = n; q.g.K = k; q.g.C = c; q.g.ldc = ldc; q.g.R = r; q.g.ldr = ldr; q.g.alpha = alpha; q.g.epi = epi;
+    q.Whi = w_hi; q.Wlo = w_lo; q.ldh = ldh;
+    const int rc = launch_sx_gemm(q, reinterpret_cast<hipStream_t>(stream));
+    return rc ? fail("sx_gemm launch failed rc=" + std::to_string(rc)) : 0;
+}
+
+int effconf_debug_pack_dwconv_mfma(const float* w_kc, int32_t ksize, int32_t channels, uint16_t* dst, size_t dst_elems) {
+    if (!w_kc || !dst || channels <= 0) return fail("null argument");
+    if (!dwconv_mfma_supported(ksize, 1)) return fail("kernel size: 15, 31 or 7");
+    if (dst_elems != (size_t)channels * 4 * dwconv_mfma_groups(ksize) * 8) return fail("dst: channels * 4 * groups * 8 bf16");
+    pack_dwconv_mfma(w_kc, ksize, channels, dst);          // host memory in, host memory out
+    return 0;
+}
+
+int effconf_debug_dwconv(const uint16_t* g, int32_t batch, int32_t frames, int32_t channels, int32_t ld, const float* w_kc_host, const float* bias_host,
+                         int32_t ksize, int32_t stride, int32_t use_mfma, int32_t causal, uint16_t* out, void* stream) {
+    if (!g || !w_kc_host || !bias_host || !out || batch <= 0 || frames <= 0 || channels <= 0 || ld < channels || ld % 8) return fail("bad argument");
+    if (use_mfma && !dwconv_mfma_supported(ksize, stride)) return fail("dwconv_mfma_kernel: stride 1, kernel size 15, 31 or 7");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    float *dw = nullptr, *db = nullptr; uint16_t* dt = nullptr;
+    std::vector<uint16_t> tab;
+    if (use_mfma) { tab.resize((size_t)channels * 4 * dwconv_mfma_groups(ksize) * 8); pack_dwconv_mfma(w_kc_host, ksize, channels, tab.data()); }
+    // test-only entry: temporary device copies of the taps, synchronous
+    if (hipMalloc(&dw, (size_t)ksize * channels * 4) != hipSuccess || hipMalloc(&db, (size_t)channels * 4) != hipSuccess ||
+        (use_mfma && hipMalloc(&dt, tab.size() * 2) != hipSuccess)) return fail("hipMalloc failed");
+    (void)hipMemcpy(dw, w_kc_host, (size_t)ksize * channels * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(db, bias_host, (size_t)channels * 4, hipMemcpyHostToDevice);
+    if (use_mfma) (void)hipMemcpy(dt, tab.data(), tab.size() * 2, hipMemcpyHostToDevice);
+    const int to = (frames - 1) / stride + 1;
+    const int rc = launch_dwconv(g, batch, frames, to, channels, ld, dw, db, ksize, stride, out, st, nullptr, causal, use_mfma ? dt : nullptr);
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(dw); (void)hipFree(db); if (dt) (void)hipFree(dt);
+    return rc ? fail("launch_dwconv failed rc=" + std::to_string(rc)) : 0;
+}
+
+int effconf_debug_sxf_ffn(EcEncoder* e, int32_t block, int32_t which, const float* x, int32_t rows, float* y, int32_t with_norm, int32_t ablate, void* stream) {
+    if (!e || !e->finalized || block < 0 || block >= (int)e->blocks.size() || which < 1 || which > 2 || !x || !y || rows <= 0) return fail("bad argument");
+    const BlockW& W = e->bw[block];
+    if (!W.xf_img[which - 1]) return fail("no fused split FFN image for this block (finalize with exact_fp32 = 2; width not built, or a folded weight beyond the image's range)");
+    SxfFfnParams fp{};
+    const int D = which == 2 ? e->blocks[block].dim_expand : e->blocks[block].dim_model;
+    fp.X = x; fp.ldx = D; fp.Y = y; fp.ldy = D; fp.wimg = W.xf_img[which - 1]; fp.b2 = W.xf_b2[which - 1]; fp.M = rows; fp.D = D; fp.nchunk = W.xf_nch[which - 1];
+    if (with_norm) { fp.ln_g = W.ln_out.g; fp.ln_b = W.ln_out.b; }
+    fp.ablate = ablate;
+    EC_TRY(launch_sxf_ffn(fp, reinterpret_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int effconf_debug_spin(double microseconds, void* stream) {
+    if (launch_debug_spin(microseconds, reinterpret_cast<hipStream_t>(stream)) != 0) return fail("spin launch failed");
+    return 0;
+}
+
+int effconf_debug_lds_fill(int32_t mode, int32_t blocks, int32_t waves, const void* src, size_t window, int32_t kib_per_wave, int32_t passes, uint64_t* out, void* stream) {
+    EC_TRY(launch_debug_lds_fill(mode, blocks, waves, reinterpret_cast<const char*>(src), window, kib_per_wave, passes, reinterpret_cast<unsigned long long*>(out), (hipStream_t)stream));
+    return 0;
+}
+
+int effconf_debug_victim(int32_t kind, int32_t blocks, int32_t iters, float* out, void* stream) {
+    EC_TRY(launch_debug_victim(kind, blocks, iters, out, (hipStream_t)stream));
+    return 0;
+}
+
+}  // extern "C"

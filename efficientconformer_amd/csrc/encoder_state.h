@@ -1,4 +1,4 @@
-// State of an encoder handle shared by encoder.hip (shapes, workspaces, the forward schedules, the C ABI) and pack.hip (the packing steps of
+// State of an encoder handle shared by encoder.hip (the C ABI), forward_*.hip (the forward schedules) and pack.hip (the packing steps of
 // effconf_encoder_finalize): the handle, its per-block packed weights, the host tensors loaded before finalize, and the error helpers.  Internal to libeffconf.
 #pragma once
 #include "kernels.h"

@@ -1,0 +1,587 @@
+// The bf16 forward schedule: bf16 activations between kernels, an fp32 residual stream, fused row-local chains where the stage width allows.  Follows
+// ConformerEncoder.forward (reference models/encoders.py:97-142) and ConformerBlock.forward (models/blocks.py:119-137); see DESIGN.md for the kernel map.
+// Also the per-module entries of the C ABI, which exist only on this file's helpers.
+#include "forward_common.h"
+
+#include <cmath>
+
+Workspace make_workspace(const EcEncoder* e, const Shapes& s, bool from_audio) {
+    Workspace w;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
+    const size_t B = s.B;
+    size_t mx = 0, ma = 0, mh = 0, mq = 0, mvt = 0, me = 0, mg = 0, mc = 0;
+    std::vector<size_t> esz;
+    for (size_t k = 0; k < e->blocks.size(); ++k) {
+        const EcBlock& b = e->blocks[k];
+        const size_t T = s.Tin[k], D = b.dim_model, De = b.dim_expand;
+        const size_t Tp = ec_round_up((int)T, b.group_size), Tg = Tp / b.group_size;
+        const size_t d = (size_t)b.group_size * D / b.num_heads, dpad = ec_round_up((int)d, 32);
+        const size_t Mi = (size_t)s.Min[k], Mo = (size_t)s.Mout[k], Mqk = (size_t)s.Mq[k];     // rows in, rows out, Q / K / V rows
+        mx = std::max(mx, std::max(Mi * D, Mo * De) * 4);
+        ma = std::max(ma, std::max(Mi * ld8(D), Mo * ld8(De)) * 2);
+        mh = std::max(mh, std::max(Mi * D, Mo * De) * b.ff_ratio * 2);
+        // Q / K / V: natural layout Mq rows x D; the head-major test layout needs B * H * Tg * dpad (rectangular batches only)
+        const size_t qkv = std::max(Mqk * D, s.ragged ? (size_t)0 : B * b.num_heads * Tg * dpad);
+        mq = std::max(mq, qkv * 2 + 512);     // + slack: 16-byte chunk loads may run past a row's head span
+        mvt = std::max(mvt, qkv * 2 + 512);
+        me = std::max(me, (size_t)b.num_heads * (2 * Tg - 1) * dpad * 2);
+        esz.push_back((size_t)b.num_heads * (2 * Tg - 1) * dpad * 2 + 512);
+        mg = std::max(mg, Mi * ld8(De) * 2);
+        mc = std::max(mc, Mo * ld8(De) * 2);
+    }
+    w.mel = take(from_audio ? B * e->cfg.n_mels * s.Tm * 4 : 0);
+    const int C = e->cfg.sub_filters[e->cfg.sub_layers - 1];
+    int F = e->cfg.n_mels; for (int i = 0; i < e->cfg.sub_layers; ++i) F /= 2;
+    const bool rag_unfused = s.ragged && !(e->fuse_subsample == 2 && e->lin_rs);        // (s.Tm = the input's row pitch in ragged batches)
+    size_t T1r = (size_t)s.T1;
+    if (s.ragged) { T1r = (size_t)s.Tm; for (int i = 0; i < e->cfg.sub_layers; ++i) T1r = (T1r - 1) / 2 + 1; }      // rows per utterance of the rectangular image
+    // scratch of the unfused front ends; ragged rows: every utterance's frames rounded up to the first block's group size
+    w.sub = take(s.ragged && !rag_unfused ? 0 : B * (T1r + (s.ragged ? e->blocks[0].group_size - 1 : 0)) * C * F * 2);
+    w.xrect = take(rag_unfused ? B * T1r * e->blocks[0].dim_model * 4 : 0);
+    {   // two-layer subsampler: channel-last layer-1 activation [B][F/2][T after layer 1][Cp]
+        const size_t tl1 = (s.Tm - 1) / 2 + 1;
+        w.sub1 = take(e->cfg.sub_layers == 2 ? B * (e->cfg.n_mels / 2) * tl1 * ec_round_up(e->cfg.sub_filters[0], 64) * 2 : 0);
+    }
+    w.x0 = take(mx); w.x1 = take(mx);
+    w.a = take(ma); w.hbuf = take(mh);
+    w.qu = take(mq); w.kh = take(mq); w.vt = take(mvt); w.eh = take(me);
+    w.o = take(ma); w.gbuf = take(mg); w.cbuf = take(mc); w.xs = take(ma);
+    w.lens = take((e->blocks.size() + 1) * B * 4);
+    if (s.ragged) {
+        const size_t nbk = e->blocks.size();
+        w.mel_len = take(B * 4);
+        w.row_off = take((nbk + 1) * (B + 1) * 4);
+        w.wg_off = take(nbk * (B + 1) * 4);
+        w.tile_off = take(nbk * (B + 1) * 4);
+    }
+    for (size_t k = 0; k < esz.size(); ++k) w.eh_blk.push_back(take(esz[k]));
+    w.preds = take(0);
+    w.total = off;
+    return w;
+}
+
+namespace {
+
+int run_gemm(EcEncoder* e, int cls, hipStream_t st, const bf16_t* A, int lda, int M, const PackedLinear& L, int epi, void* C, int ldc,
+             const float* R = nullptr, int ldr = 0, float alpha = 1.f) {
+    const double out_b = (epi == EPI_F32) ? 4.0 : (epi == EPI_RESID_F32 ? 8.0 : 2.0);
+    PROF(cls, 2.0 * M * (double)L.N * L.K, (double)M * L.K * 2 + (double)L.N * L.K * 2 + (double)M * L.N * out_b);
+    GemmParams p{};
+    p.A = A; p.lda = lda; p.W = L.w; p.ldw = L.ldw; p.bias = L.bias;
+    p.M = M; p.N = L.N; p.K = L.K; p.C = C; p.ldc = ldc; p.R = R; p.ldr = ldr; p.alpha = alpha;
+    p.wide = e->wide_gemm;
+    return launch_gemm(p, epi, st);
+}
+
+// x += alpha * FFN(a)  — fused row-stationary kernel when the width allows, else two tiled GEMMs
+// ln != null: the pre-norm is computed inside the fused kernel's prologue (a is not read); the tiled fallback needs `a`
+inline int F1c(const EcBlock& b) { return ec_round_up(b.dim_model * b.ff_ratio, 32); }
+
+// POST half of a chain A: the block's FFN1 (pre-norm ln[2]), attention pre-norm ln[3] and stacked Q/K/V projection
+void fill_chain_head(ChainParams& cp, const BlockW& W, int D, int Fp, int T, int Tp, const GemmParams& q) {
+    cp.D = D;
+    cp.ln[2] = ChainLn{W.ln_ffn1.g, W.ln_ffn1.b};
+    cp.ln[3] = ChainLn{W.ln_att.g, W.ln_att.b};
+    cp.f[1] = ChainFfn{W.c_f1a.w, W.c_f1a.ldw, W.c_f1a.bias, W.c_f1b, W.ffn1_b.ldw, W.c_f1b2, Fp, W.c_f1b_cm};
+    cp.g1 = ChainGemm{W.c_qkv.w, W.c_qkv.ldw, W.c_qkv.bias, W.c_qkv_chunks};
+    cp.qu = q.qu; cp.kh = q.kh; cp.vt = q.vt; cp.u = W.u; cp.v = W.v; cp.T = T; cp.Tp = Tp;
+}
+
+bool prefer_tiled(const EcEncoder* e, int M, int N, int K);
+
+int run_ffn(EcEncoder* e, hipStream_t st, const bf16_t* a, int M, int D, const PackedLinear& L1, const PackedLinear& L2,
+            const bf16_t* w2p, float* x, bf16_t* hbuf, const LNp* ln = nullptr) {
+    const int F = L1.N;
+    if (ffn_fused_supported(D) && !(prefer_tiled(e, M, F, D) && !ln)) {
+        PROF(PC_GEMM_FFN, 4.0 * M * (double)D * F, (double)M * D * 10 + 4.0 * D * F);
+        FfnParams p{};
+        p.A = a; p.lda = ld8(D); p.X = x; p.ldx = D; p.Y = x; p.ldy = D;
+        p.W1 = L1.w; p.ldw1 = L1.ldw; p.b1 = L1.bias; p.W2 = w2p; p.ldw2 = L2.ldw; p.b2 = L2.bias;
+        p.M = M; p.D = D; p.Fp = ec_round_up(F, 32); p.alpha = 0.5f;
+        if (ln) { p.ln_g = ln->g; p.ln_b = ln->b; }
+        return launch_ffn_fused(p, st);
+    }
+    int rc = run_gemm(e, PC_GEMM_FFN, st, a, ld8(D), M, L1, EPI_SWISH_BF16, hbuf, F);
+    if (rc) return rc;
+    return run_gemm(e, PC_GEMM_FFN, st, hbuf, F, M, L2, EPI_RESID_F32, x, D, x, D, 0.5f);
+}
+
+// Widths 257 .. 384 (EfficientConformer Large stage 1, Medium stage 3) fit the row-stationary kernels, but at 24 k-steps those run one
+// wave per SIMD and stream every weight per 32-row tile: 60 - 200 TFLOP/s (profiles/r2_03_large_kernel_stats.txt).  `wide_gemm` 2 / 3
+// sends these layers to LayerNorm + the tiled GEMMs instead.  Only when forced: chosen by row count (gemm256.hip's tiles filling the
+// chip) it was -3 % kernel time on Large and wall-neutral, and it made a forward's bits depend on how the batch is split into row ranges
+// (the two paths round differently; tools/robustness_sweep.py) - the gemm.hip / gemm256.hip choice does not (bit-identical kernels).
+bool prefer_tiled(const EcEncoder* e, int M, int N, int K) {
+    (void)M; (void)N;
+    return (e->wide_gemm == 2 || e->wide_gemm == 3 || (e->wide_gemm == 0 && (e->tiled_auto == 2 || (e->tiled_auto && e->tiled_auto_on)))) && K > e->tiled_min_k && K % 8 == 0;
+}
+
+// row-stationary single GEMM when K <= 384, else the tiled kernel
+int run_rs_or_tiled(EcEncoder* e, int cls, hipStream_t st, const bf16_t* A, int lda, int M, const PackedLinear& L, int rs_epi,
+                    int tiled_epi, void* C, int ldc, const float* R = nullptr, int ldr = 0, float alpha = 1.f,
+                    const float* lnX = nullptr, const LNp* ln = nullptr) {
+    const bool ok = (rs_epi == 0 || rs_epi == 1) ? rs_gemm_resident_supported(L.K, L.N) : rs_gemm_supported(L.K);
+    if (!ok) return run_gemm(e, cls, st, A, lda, M, L, tiled_epi, C, ldc, R, ldr, alpha);
+    if (prefer_tiled(e, M, L.N, L.K)) {
+        if (lnX && ln) { PROF(PC_LAYERNORM, 0, (double)M * L.K * 6); EC_TRY(launch_layernorm(lnX, M, L.K, ln->g, ln->b, nullptr, const_cast<bf16_t*>(A), lda, nullptr, nullptr, st)); }
+        return run_gemm(e, cls, st, A, lda, M, L, tiled_epi, C, ldc, R, ldr, alpha);
+    }
+    const double out_b = (tiled_epi == EPI_F32) ? 4.0 : (tiled_epi == EPI_RESID_F32 ? 8.0 : 2.0);
+    PROF(cls, 2.0 * M * (double)L.N * L.K, (double)M * L.K * 2 + (double)L.N * L.K * 2 + (double)M * L.N * out_b);
+    GemmParams p{};
+    p.A = A; p.lda = lda; p.W = L.w; p.ldw = L.ldw; p.bias = L.bias;
+    p.M = M; p.N = L.N; p.K = L.K; p.C = C; p.ldc = ldc; p.R = R; p.ldr = ldr; p.alpha = alpha;
+    if (lnX && ln) { p.X = lnX; p.ldx = L.K; p.ln_g = ln->g; p.ln_b = ln->b; }
+    return launch_rs_gemm(p, rs_epi, st);
+}
+
+// Conv2dSubsampling (modules.py:232-249) + transpose + Linear (encoders.py:113-116): mel (B, n_mels, Tm) -> x fp32 (B * T1, D0).
+// sub / act1: bf16 scratch of the unfused variants (the subsampler's output rows / the two-layer subsampler's layer-1 image).
+// sublinear3.hip: option fuse_subsample = 3 (every one-layer front end it is built for) or 2 = the default where sublinear2.hip has no instance or runs one workgroup per
+// CU (channel counts / widths above 128); a debug trace keeps the kernels that write the "subsample" activation only when fuse_subsample = 0
+bool use_sublinear3(const EcEncoder* e) {
+    if (!e->sub3_wimg || e->cfg.sub_layers != 1) return false;
+    if (e->fuse_subsample == 3) return true;
+    return e->fuse_subsample == 2 && e->sub3_auto && (e->cfg.sub_filters[0] > 128 || e->blocks[0].dim_model > 128);
+}
+
+int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, int B, int Tm, int T1, bf16_t* sub, bf16_t* act1, float* x) {
+    const EcConfig& c = e->cfg;
+    const int C0 = c.sub_filters[0], F2 = c.n_mels / 2, Ksub = C0 * F2;
+    if (c.sub_layers == 2) {
+        const int Tl1 = (Tm - 1) / 2 + 1, F1 = c.n_mels / 2, F2q = c.n_mels / 4, C1 = c.sub_filters[1];
+        { PROF(PC_SUBCONV, 2.0 * 9 * B * Tl1 * (double)C0 * F1, (double)B * c.n_mels * Tm * 4 + (double)B * Tl1 * F1 * e->sub2_cp * 2);
+          EC_TRY(launch_subsample_conv_cl(mel, B, c.n_mels, Tm, Tl1, e->sub_w9, e->sub_b, C0, e->sub2_cp, act1, st)); }
+        trace_add(e, st, "subsample1", act1, (int64_t)B * F1 * Tl1, C0, e->sub2_cp, 1);       // layer-1 image, rows (b, f, t), channel-last
+        { PROF(PC_GEMM_OTHER, 2.0 * 9 * (double)B * F2q * T1 * C0 * C1, (double)B * Tl1 * F1 * e->sub2_cp * 2 + (double)B * T1 * F2q * C1 * 2);
+          EC_TRY(launch_conv2_igemm(act1, B, F1, Tl1, e->sub2_cp, e->sub2_w, 9 * e->sub2_cp, e->sub2_b, C1, F2q, T1, sub, st)); }
+        trace_add(e, st, "subsample", sub, (int64_t)B * T1, F2q * C1, F2q * C1, 1);
+        EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, F2q * C1, B * T1, e->lin, EPI_F32, x, e->lin.N));
+    } else if (use_sublinear3(e)) {
+        PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub + 2.0 * B * T1 * (double)Ksub * e->lin.N,
+             (double)B * c.n_mels * Tm * 4 + (double)B * T1 * e->lin.N * 4);
+        SubLin3Params sp{};
+        sp.mel = mel; sp.B = B; sp.F = c.n_mels; sp.Tm = Tm; sp.To = T1; sp.rows_max = T1;
+        sp.cimg = e->sub3_cimg; sp.wimg = e->sub3_wimg; sp.bias = e->sub3_bias; sp.y = x; sp.ldy = e->lin.N; sp.N = e->lin.N; sp.ncb = e->sub3_ncb; sp.Fo = e->sub3_fo;
+        EC_TRY(launch_sublinear3(sp, st));
+    } else if (e->fuse_subsample >= 2 && e->lin_rs) {
+        PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub + 2.0 * B * T1 * (double)Ksub * e->lin.N,
+             (double)B * c.n_mels * Tm * 4 + (double)B * T1 * e->lin.N * 4);
+        EC_TRY(launch_sublinear2(mel, B, c.n_mels, Tm, T1, e->conv_tab, e->lin_rs, e->lin.bias, C0, e->lin.N, x, e->lin.N, st));
+    } else if (e->fuse_subsample && e->lin_fused) {
+        PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub + 2.0 * B * T1 * (double)Ksub * e->lin.N,
+             (double)B * c.n_mels * Tm * 4 + (double)B * T1 * e->lin.N * 4);
+        EC_TRY(launch_sublinear_fused(mel, B, c.n_mels, Tm, T1, e->sub_w9, e->sub_b, C0, e->lin_fused, e->lin_fused_ld,
+                                      e->lin.bias, e->lin.N, x, e->lin.N, st));
+    } else {
+        { PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub, (double)B * c.n_mels * Tm * 4 + (double)B * T1 * Ksub * 2); EC_TRY(launch_subsample_conv(mel, B, c.n_mels, Tm, T1, e->sub_w9, e->sub_b, C0, sub, Ksub, st)); }
+        trace_add(e, st, "subsample", sub, (int64_t)B * T1, Ksub, Ksub, 1);
+        EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, Ksub, B * T1, e->lin, EPI_F32, x, e->lin.N));
+    }
+    return 0;
+}
+
+static const void* dw_mfma_table(const EcEncoder* e, const uint16_t* t, int ks) { return (e->dwconv_mfma == 2 || (e->dwconv_mfma == 1 && ks == 15)) ? t : nullptr; }
+// chain launches of width D that go to chain2.hip / chain3.hip (launch_chain's rule): there the tail and the next head of chain A are one kernel up to D = 256
+static bool pair_on(const EcEncoder* e, int D) { return e->chain_pair && chain3_supported(D); }
+
+}  // namespace
+
+// Ragged batches (s.ragged): every utterance runs at its own length in one concatenated row space (kernels.h: RaggedRows) - the row-local
+// kernels (chains, GEMMs, LayerNorms) just see M rows; the frame-mixing ones (subsampling, attention, depthwise conv, conv_res decimation)
+// index utterances through the descriptor arrays lengths_ragged_kernel leaves in the workspace.  out: (B, out_frames, D_last), zero filled
+// behind every utterance's own last frame.
+int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from_audio, const Shapes& s, const Workspace& w,
+                 char* ws, float* out, int64_t* out_len, hipStream_t st, int out_frames) {
+    const EcConfig& c = e->cfg;
+    const int B = s.B, nb = (int)e->blocks.size();
+    const bool rg = s.ragged;
+    BatchRows br;
+    EC_TRY(begin_forward(e, st, s, w, ws, mel, in_len, from_audio, out_len, &br));
+    const int* mel_len = br.mel_len;
+
+    // ---- Conv2dSubsampling (modules.py:232-249) + transpose + Linear (encoders.py:113-116)
+    float* x = reinterpret_cast<float*>(ws + w.x0);
+    float* xalt = reinterpret_cast<float*>(ws + w.x1);
+    if (rg) {
+        const int C0 = c.sub_filters[0], Ksub = C0 * (c.n_mels / 2);
+        const RaggedRows r0 = br.rows_at(0);
+        if (c.sub_layers == 2) {
+            // two-layer subsampler (the plain Conformer configurations): both convolutions and the Linear on the RECTANGULAR image - layer 1
+            // zero-fills every utterance's image behind its own last frame, so layer 2 sees the zero padding of the utterance run alone -
+            // then the valid rows are gathered into the ragged row space
+            bf16_t* sub = reinterpret_cast<bf16_t*>(ws + w.sub);
+            bf16_t* act1 = reinterpret_cast<bf16_t*>(ws + w.sub1);
+            float* xrect = reinterpret_cast<float*>(ws + w.xrect);
+            const int Tl1 = (s.Tm - 1) / 2 + 1, T1r = (Tl1 - 1) / 2 + 1, F1 = c.n_mels / 2, F2q = c.n_mels / 4, C1 = c.sub_filters[1];
+            { PROF(PC_SUBCONV, 2.0 * 9 * B * Tl1 * (double)C0 * F1, (double)B * c.n_mels * s.Tm * 4 + (double)B * Tl1 * F1 * e->sub2_cp * 2);
+              EC_TRY(launch_subsample_conv_cl(mel, B, c.n_mels, s.Tm, Tl1, e->sub_w9, e->sub_b, C0, e->sub2_cp, act1, st, mel_len)); }
+            trace_add(e, st, "subsample1", act1, (int64_t)B * F1 * Tl1, C0, e->sub2_cp, 1);
+            { PROF(PC_GEMM_OTHER, 2.0 * 9 * (double)B * F2q * T1r * C0 * C1, (double)B * Tl1 * F1 * e->sub2_cp * 2 + (double)B * T1r * F2q * C1 * 2);
+              EC_TRY(launch_conv2_igemm(act1, B, F1, Tl1, e->sub2_cp, e->sub2_w, 9 * e->sub2_cp, e->sub2_b, C1, F2q, T1r, sub, st)); }
+            trace_add(e, st, "subsample", sub, (int64_t)B * T1r, F2q * C1, F2q * C1, 1);       // the RECTANGULAR image's rows (b, t)
+            EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, F2q * C1, B * T1r, e->lin, EPI_F32, xrect, e->lin.N));
+            { PROF(PC_MISC, 0, (double)s.Min[0] * e->lin.N * 8); EC_TRY(launch_gather_rows(xrect, e->lin.N, T1r, r0, x, st)); }
+        } else if (use_sublinear3(e)) {                            // sublinear3.hip: workgroup = (utterance, 128 frames)
+            PROF(PC_SUBCONV, 2.0 * 9 * (double)s.Min[0] * Ksub + 2.0 * (double)s.Min[0] * Ksub * e->lin.N, (double)B * c.n_mels * s.Tm * 4 + (double)s.Min[0] * e->lin.N * 4);
+            SubLin3Params sp{};
+            sp.mel = mel; sp.B = B; sp.F = c.n_mels; sp.Tm = s.Tm; sp.mel_len = mel_len; sp.off = r0.off; sp.len = r0.len;
+            sp.rows_max = ec_round_up(s.Tin[0], e->blocks[0].group_size);
+            sp.cimg = e->sub3_cimg; sp.wimg = e->sub3_wimg; sp.bias = e->sub3_bias; sp.y = x; sp.ldy = e->lin.N; sp.N = e->lin.N; sp.ncb = e->sub3_ncb; sp.Fo = e->sub3_fo;
+            EC_TRY(launch_sublinear3(sp, st));
+        } else if (e->fuse_subsample >= 2 && e->lin_rs) {        // sublinear2.hip indexes the ragged rows itself
+            PROF(PC_SUBCONV, 2.0 * 9 * (double)s.Min[0] * Ksub + 2.0 * (double)s.Min[0] * Ksub * e->lin.N, (double)B * c.n_mels * s.Tm * 4 + (double)s.Min[0] * e->lin.N * 4);
+            EC_ABL(32, EC_TRY(launch_sublinear2(mel, B, c.n_mels, s.Tm, s.T1, e->conv_tab, e->lin_rs, e->lin.bias, C0, e->lin.N, x, e->lin.N, st, &r0, mel_len)));
+        } else {
+            // wide front ends (Large: 360 filters): conv (zero padding at every utterance's own last mel frame) + Linear on the RECTANGULAR
+            // (B, T1 of the longest) rows, then the valid rows are gathered into the ragged row space (pad rows are computed and dropped:
+            // the subsampler is a few percent of the step)
+            // Round 4: the conv writes the RAGGED rows itself (tiles behind an utterance's own end exit; group-padding rows = zeros) and the
+            // Linear runs on those rows only - until round 3 both ran on the (B, longest) rectangle (24 % padding on the bench batch) and a
+            // gather pass copied the valid rows.  Group-padding rows of x = the Linear's bias (finite; no kernel mixes them into valid rows).
+            bf16_t* sub = reinterpret_cast<bf16_t*>(ws + w.sub);
+            const int T1r = (s.Tm - 1) / 2 + 1;            // rows per utterance of the rectangular image (pitch of the input)
+            const int Tcover = T1r + e->blocks[0].group_size - 1;      // >= every utterance's frames rounded up to the group size
+            { PROF(PC_SUBCONV, 2.0 * 9 * (double)s.Min[0] * Ksub, (double)B * c.n_mels * s.Tm * 4 + (double)s.Min[0] * Ksub * 2);
+              EC_TRY(launch_subsample_conv(mel, B, c.n_mels, s.Tm, Tcover, e->sub_w9, e->sub_b, C0, sub, Ksub, st, mel_len, &r0)); }
+            trace_add(e, st, "subsample", sub, s.Min[0], Ksub, Ksub, 1);                       // the RAGGED rows
+            EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, Ksub, (int)s.Min[0], e->lin, EPI_F32, x, e->lin.N));
+        }
+    } else {
+        EC_TRY(run_subsample_linear(e, st, mel, B, s.Tm, s.T1, reinterpret_cast<bf16_t*>(ws + w.sub), reinterpret_cast<bf16_t*>(ws + w.sub1), x));
+    }
+    trace_add(e, st, "linear", x, s.Min[0], e->lin.N, e->lin.N, 0);
+
+    bf16_t* a = reinterpret_cast<bf16_t*>(ws + w.a);
+    bf16_t* hbuf = reinterpret_cast<bf16_t*>(ws + w.hbuf);
+    bf16_t* o = reinterpret_cast<bf16_t*>(ws + w.o);
+    bf16_t* gbuf = reinterpret_cast<bf16_t*>(ws + w.gbuf);
+    bf16_t* cbuf = reinterpret_cast<bf16_t*>(ws + w.cbuf);
+    bf16_t* xs = reinterpret_cast<bf16_t*>(ws + w.xs);
+    bool have_a = false, head_done = false;
+    const ECache ec = e_cache_begin(e, st, ws, s, w.eh_blk[0], true);
+    const bool e_cached = ec.hit;
+
+    int mask_stride = 1;                       // product of the strides of the blocks before block k
+    for (int k = 0; k < nb; ++k) {
+        const EcBlock& b = e->blocks[k];
+        const BlockW& W = e->bw[k];
+        const int T = s.Tin[k], To = s.Tout[k], D = b.dim_model, De = b.dim_expand;      // ragged: the LONGEST utterance's frames
+        const int M = (int)s.Min[k], Mo = (int)s.Mout[k];
+        const int G = b.group_size, H = b.num_heads;
+        const int Tp = ec_round_up(T, G), Tg = Tp / G, Tgp = ec_round_up(Tg, 8);
+        const int d = G * D / H, dpad = ec_round_up(d, 32);
+        // Q/K/V/E layout: "natural" row-major [B*Tp][D] (16-byte row stores from the GEMM, head split = pointer arithmetic in
+        // the attention kernel).  An odd grouped head width (d = 135: Medium / Large stage 0) makes the head spans only 2-byte
+        // aligned; gfx950 global loads are alignment-free, so the attention kernel reads them as they are - the head-major
+        // fallback (a scatter epilogue of 2-byte stores, 9 % of Medium's step) is kept behind the option "head_major_odd" for tests.
+        const bool head_major_odd = e->head_major_odd;
+        const bool nat = (d % 2) == 0 || !head_major_odd;
+        if (rg && !nat) return fail("ragged batches use the natural Q / K / V layout (option head_major_odd = 0)");
+        // rows (b, t) -> Q / K / V rows b * Tp + t; a ragged batch keeps every utterance's rows group-padded in the residual stream itself,
+        // so the map is the identity: ONE "utterance" of M rows
+        const int qT = rg ? M : T, qTp = rg ? M : Tp;
+        const bool chain_head = e->fuse_chain && W.chain_in && nat && chain_head_supported(D) && D <= e->chain_max_dim;          // FFN1 + QKV of this block as a fused chain
+        const bool chain_b = e->fuse_chain && W.chain_in && D <= e->chain_max_dim;                      // out-proj + LN + pointwise-1/GLU
+        const bool chain_tail = e->fuse_chain && W.chain_out && chain_tail_supported(De) && De <= e->chain_max_dim;                  // pointwise-2 + FFN2 + block norm (+ next block's head)
+        GemmParams p{};
+        p.A = a; p.lda = ld8(D); p.W = W.qkv.w; p.ldw = W.qkv.ldw; p.bias = W.qkv.bias;
+        p.M = M; p.N = 3 * D; p.K = D;
+        p.T = qT; p.G = rg ? 1 : G; p.H = H; p.D = D; p.d = d; p.dpad = dpad; p.Tg = rg ? M : Tg; p.Tgp = Tgp;
+        p.qu = reinterpret_cast<bf16_t*>(ws + w.qu);
+        p.kh = reinterpret_cast<bf16_t*>(ws + w.kh); p.vt = reinterpret_cast<bf16_t*>(ws + w.vt);
+        p.u = W.u; p.v = W.v;
+        if (head_done) {
+            // FFN1 and the Q/K/V projection of this block already ran inside the previous block's tail chain
+        } else if (chain_head) {
+            ChainParams cp{};
+            cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
+            fill_chain_head(cp, W, D, F1c(b), qT, qTp, p);
+            cp.M = M; cp.X = x; cp.ldx = D; cp.Y = x; cp.ldy = D; cp.consts = W.cc_head;
+            PROF(PC_GEMM_FFN, 2.0 * M * (double)D * (2.0 * D * b.ff_ratio + 3.0 * D), (double)M * D * 16 + 22.0 * D * D);
+            EC_ABL(2, EC_TRY(launch_chain(cp, CHAIN_A_HEAD, st)));
+        } else {
+            // ---- x += 1/2 FFN1(x)   (blocks.py:122; modules.py:385-392)
+            { PROF(PC_LAYERNORM, 0, (double)M * D * 6); if (!have_a) EC_TRY(launch_layernorm(x, M, D, W.ln_ffn1.g, W.ln_ffn1.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
+            EC_TRY(run_ffn(e, st, a, M, D, W.ffn1_a, W.ffn1_b, W.ffn1_bp, x, hbuf));
+            // ---- Q/K/V of LN(x)   (modules.py:472-488; attentions.py:651-686)
+            const bool qkv_tiled = nat && prefer_tiled(e, M, 3 * D, D);
+            const bool ln_fused = rs_gemm_supported(D) && !qkv_tiled;      // pre-norm computed in the QKV kernel's prologue
+            if (!ln_fused) { PROF(PC_LAYERNORM, 0, (double)M * D * 6); EC_TRY(launch_layernorm(x, M, D, W.ln_att.g, W.ln_att.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
+            { PROF(PC_GEMM_OTHER, 2.0 * M * 3.0 * D * D, (double)M * D * 2 + 3.0 * D * D * 2 + (double)M * D * 8);
+              if (ln_fused) {
+                  if (nat) { p.W = W.qkv_nat.w; p.ldw = W.qkv_nat.ldw; p.bias = W.qkv_nat.bias; }
+                  p.X = x; p.ldx = D; p.ln_g = W.ln_att.g; p.ln_b = W.ln_att.b;
+                  EC_TRY(launch_rs_gemm(p, nat ? 4 : 3, st));
+              } else {
+                  p.wide = e->wide_gemm;
+                  EC_TRY(launch_gemm(p, nat ? EPI_QKV_NAT : EPI_QKV, st));
+              } }
+        }
+        trace_block(e, st, k, "x_ffn1", x, M, D, D, 0);
+
+        // ---- x += MHSA(LN(x))   (blocks.py:125-126; attentions.py:549-718)
+        {
+            { PROF(PC_MISC, 0, 0);
+              if (rg) EC_ABL(64, EC_TRY(launch_attn_pad_rows_ragged(p.qu, p.kh, p.vt, W.u, D, G, br.rows_at(k), st)));
+              else EC_TRY(nat ? launch_attn_pad_rows_nat(p, B, st) : launch_attn_pad_rows(p, B, st)); }
+            // positional embeddings E = pos_layer(R) (attentions.py:588 / 678): input independent, tiny (2Tp-G rows)
+            GemmParams pe{};
+            // relative tables: R[m] = sinusoid(Tp - 1 - G/2 - m), m < 2 Tp - G; causal: R[m] = sinusoid(Tp - 1 - m), m < Tp (attentions.py:1243-1251, 1296-1309)
+            const int erows = c.causal ? Tp : 2 * Tp - G;
+            pe.A = W.pos_table + (size_t)(b.max_pos - Tp + (c.causal ? 0 : G / 2)) * ld8(D); pe.lda = ld8(D);
+            pe.W = W.pos.w; pe.ldw = W.pos.ldw; pe.bias = W.pos.bias;
+            pe.M = erows; pe.N = D; pe.K = D;
+            pe.T = erows; pe.G = G; pe.H = H; pe.D = D; pe.d = d; pe.dpad = dpad; pe.Tg = c.causal ? Tg : 2 * Tg - 1; pe.Tgp = 0;
+            pe.kh = reinterpret_cast<bf16_t*>(ws + w.eh_blk[k]);
+            pe.C = pe.kh; pe.ldc = D;
+            if (Tp > b.max_pos) return fail("sequence longer than max_pos_encoding");
+            if (!e_cached) { PROF(PC_GEMM_OTHER, 2.0 * erows * (double)D * D, (double)erows * D * 4 + (double)D * D * 2);
+                             EC_TRY(launch_gemm(pe, nat ? EPI_BF16 : EPI_HEADS, st)); }
+            if (e->trace_arena && nat) {    // the attention kernel's operands, natural layout: rows b Tp + t (ragged: the group-padded row space), pad rows filled; E rows m < erows
+                const int64_t qrows = rg ? (int64_t)M : (int64_t)B * Tp;
+                trace_block(e, st, k, "qu", p.qu, qrows, D, D, 1);
+                trace_block(e, st, k, "k", p.kh, qrows, D, D, 1);
+                trace_block(e, st, k, "v", p.vt, qrows, D, D, 1);
+                trace_block(e, st, k, "e", pe.kh, erows, D, D, 1);
+            }
+            AttnParams ap{};
+            ap.qu = p.qu; ap.kh = p.kh; ap.vt = p.vt; ap.eh = pe.kh;
+            ap.dvu = W.dvu; ap.dvu_ld = W.dvu_ld;
+            ap.lens = br.lens_at(k);
+            ap.B = B; ap.H = H; ap.T = T; ap.G = G; ap.D = D; ap.d = d; ap.dpad = dpad; ap.Tg = Tg; ap.Tgp = Tgp;
+            if (nat) { ap.q_bstride = (long long)Tp * D; ap.q_hstride = d; ap.q_rowstride = G * D; ap.e_hstride = d; ap.e_rowstride = G * D; }
+            else { ap.q_bstride = (long long)H * Tg * dpad; ap.q_hstride = (long long)Tg * dpad; ap.q_rowstride = dpad;
+                   ap.e_hstride = (long long)(2 * Tg - 1) * dpad; ap.e_rowstride = dpad; }
+            ap.out = o; ap.ldo = ld8(D); ap.scale = 1.0f / std::sqrt((float)d);
+            const Band bd = band(c, mask_stride, G);
+            ap.band_l = bd.l; ap.band_r = bd.r;
+            ap.causal = c.causal;
+            const bool streaming = c.causal || ap.band_l < Tg || ap.band_r < Tg;
+            if (streaming && !(nat && relpos_attention2_supported(dpad) && e->attention_v2))
+                return fail("streaming contexts / causal attention run on attention2.hip (natural layout, padded head width <= 160, option attention_v2 != 0)");
+            if (rg) {
+                if (!relpos_attention2_supported(dpad)) return fail("ragged batches need attention2.hip (padded head width <= 160)");
+                ap.rag_off = br.off_at(k); ap.rag_wg = br.wg_off + (size_t)k * (B + 1); ap.rag_nwg = s.wgs[k]; ap.rag_tgmax = Tg;
+            }
+            { PROF(PC_ATTENTION, 2.0 * H * (rg ? s.tg2[k] : (double)B * Tg * Tg) * d * 3.0, (double)M * D * 2 * 5);
+              if (rg || streaming) EC_ABL(1, EC_TRY(launch_relpos_attention2(ap, 1, st))); else
+              // attention2.hip reads the natural layout only (its column masks assume the next head's finite data behind a head span); the
+              // head-major test layout of odd head widths (EFFCONF_HEAD_MAJOR_ODD) stays on attention.hip
+              if (e->attention_v2 && nat && relpos_attention2_supported(dpad)) EC_TRY(launch_relpos_attention2(ap, e->attention_v2, st));
+              else EC_TRY(launch_relpos_attention(ap, st)); }
+            if ((int)e->att_out.size() == nb && e->att_out[k]) {       // opt-in: the reference's att_w of this block (encoders.py:129)
+                // ragged batches: (B, H, Tg of the LONGEST utterance, same) per block, an utterance's own Tg x Tg block = its map run alone, zeros elsewhere
+                EC_TRY(launch_attention_probs(ap, e->att_out[k], st));
+            }
+            trace_block(e, st, k, "att_o", o, M, D, ld8(D), 1);
+            if (chain_b) {
+                ChainParams cp{};
+                cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
+                cp.M = M; cp.D = D; cp.X = x; cp.ldx = D; cp.Y = x; cp.ldy = D; cp.A = o; cp.lda = ld8(D);
+                cp.g0 = ChainGemm{W.c_outp.w, W.c_outp.ldw, W.c_outp.bias, 0};
+                cp.ln[0] = ChainLn{W.ln_conv.g, W.ln_conv.b};
+                cp.g1 = ChainGemm{W.c_pw1.w, W.c_pw1.ldw, W.c_pw1.bias, W.c_pw1_chunks};
+                cp.glu = gbuf; cp.ldg = ld8(De); cp.Ng = De; cp.T = qT; cp.Tp = qTp; cp.consts = W.cc_b;
+                PROF(PC_GEMM_OTHER, 2.0 * M * (double)D * (D + 2.0 * De), (double)M * D * 10 + (double)M * De * 2 + 2.0 * D * (D + 2.0 * De));
+                EC_ABL(4, EC_TRY(launch_chain(cp, CHAIN_B, st)));
+            } else {
+                EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, o, ld8(D), M, W.outp, 0, EPI_RESID_F32, x, D, x, D, 1.0f));
+            }
+            trace_block(e, st, k, "x_mhsa", x, M, D, D, 0);
+        }
+
+        // ---- x = conv_res(x) + ConvModule(x)   (blocks.py:129; modules.py:511-522)
+        if (chain_b) {
+        } else if (rs_gemm_supported(D)) {
+            EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De), nullptr, 0, 1.f, x, &W.ln_conv));
+        } else {
+            { PROF(PC_LAYERNORM, 0, (double)M * D * 6); EC_TRY(launch_layernorm(x, M, D, W.ln_conv.g, W.ln_conv.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
+            EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De)));
+        }
+        trace_block(e, st, k, "glu", gbuf, M, De, ld8(De), 1);
+        const RaggedConv rc = rg ? br.conv_at(k, Mo, true) : RaggedConv{};
+        { PROF(PC_DWCONV, 2.0 * Mo * (double)De * b.kernel_size, (double)M * De * 2 + (double)Mo * De * 2); EC_ABL(8, EC_TRY(launch_dwconv(gbuf, B, T, To, De, ld8(De), W.dw_w, W.dw_b, b.kernel_size, b.conv_stride, cbuf, st, rg ? &rc : nullptr, c.causal, dw_mfma_table(e, W.dw_a, b.kernel_size), W.dw_a3))); }
+        mask_stride *= b.conv_stride;
+        trace_block(e, st, k, "dw", cbuf, Mo, De, ld8(De), 1);
+        if (D != De) {   // 1x1 strided conv on frames 0, s, 2s, ...  (blocks.py:106-110)
+            { PROF(PC_MISC, 0, (double)Mo * D * 6); EC_ABL(64, EC_TRY(launch_cast_rows(x, D, T, b.conv_stride, To, B, xs, ld8(D), st, rg ? &rc : nullptr))); }
+            EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, xs, ld8(D), Mo, W.res, 1, EPI_F32, xalt, De));
+            std::swap(x, xalt);
+        } else if (b.conv_stride > 1) {
+            return fail("strided block without expansion is not native (no shipped config uses it)");
+        }
+        const bool last = (k == nb - 1);
+        float* xo = (last && !rg) ? out : x;        // ragged: the last block writes its rows in place; emit_rows pads them into `out` below
+        if (chain_tail) {
+            bool next_head = false;
+            if (!last) {
+                const EcBlock& nbk = e->blocks[k + 1];
+                next_head = W.cc_full && nbk.dim_model <= e->chain_max_dim && e->bw[k + 1].chain_in && chain_full_supported(De, pair_on(e, De) ? 256 : e->chain_full_max) && (((nbk.group_size * nbk.dim_model / nbk.num_heads) % 2) == 0 || !head_major_odd) && nbk.dim_model == De;
+            }
+            ChainParams cp{};
+            cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
+            cp.M = Mo; cp.D = De; cp.X = x; cp.ldx = De; cp.Y = xo; cp.ldy = De; cp.A = cbuf; cp.lda = ld8(De);
+            cp.g0 = ChainGemm{W.c_pw2.w, W.c_pw2.ldw, W.c_pw2.bias, 0};
+            cp.ln[0] = ChainLn{W.ln_ffn2.g, W.ln_ffn2.b};
+            cp.ln[1] = ChainLn{W.ln_out.g, W.ln_out.b};
+            cp.f[0] = ChainFfn{W.c_f2a.w, W.c_f2a.ldw, W.c_f2a.bias, W.c_f2b, W.ffn2_b.ldw, W.c_f2b2, ec_round_up(De * b.ff_ratio, 32), W.c_f2b_cm};
+            double fl = 2.0 * Mo * (double)De * (De + 2.0 * De * b.ff_ratio), by = (double)Mo * De * 10 + 2.0 * De * De * (1 + 2.0 * b.ff_ratio);
+            if (next_head) {
+                const EcBlock& nbk = e->blocks[k + 1];
+                const int Gn = nbk.group_size;
+                const int Tn = rg ? Mo : s.Tin[k + 1], Tpn = rg ? Mo : ec_round_up(Tn, Gn);
+                GemmParams pn{};
+                pn.qu = reinterpret_cast<bf16_t*>(ws + w.qu);
+                pn.kh = reinterpret_cast<bf16_t*>(ws + w.kh); pn.vt = reinterpret_cast<bf16_t*>(ws + w.vt);
+                fill_chain_head(cp, e->bw[k + 1], De, F1c(nbk), Tn, Tpn, pn);
+                fl += 2.0 * Mo * (double)De * (2.0 * De * nbk.ff_ratio + 3.0 * De); by += (double)Mo * De * 8 + 2.0 * De * De * (3 + 2.0 * nbk.ff_ratio);
+            }
+            cp.consts = next_head ? W.cc_full : W.cc_tail;
+            { PROF(PC_GEMM_FFN, fl, by); EC_ABL(2, EC_TRY(launch_chain(cp, next_head ? CHAIN_A_FULL : CHAIN_A_TAIL, st))); }
+            head_done = next_head;
+            have_a = false;
+            if (last) { trace_block(e, st, k, "out", xo, Mo, De, De, 0); }
+            continue;
+        }
+        head_done = false;
+        EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, cbuf, ld8(De), Mo, W.pw2, 0, EPI_RESID_F32, x, De, x, De, 1.0f));
+        trace_block(e, st, k, "x_conv", x, Mo, De, De, 0);
+
+        // ---- x += 1/2 FFN2(x); x = LN(x)   (blocks.py:132-135)
+        if (ffn_fused_supported(De) && !prefer_tiled(e, Mo, De * b.ff_ratio, De)) {
+            EC_TRY(run_ffn(e, st, a, Mo, De, W.ffn2_a, W.ffn2_b, W.ffn2_bp, x, hbuf, &W.ln_ffn2));
+        } else {
+            { PROF(PC_LAYERNORM, 0, (double)Mo * De * 6); EC_TRY(launch_layernorm(x, Mo, De, W.ln_ffn2.g, W.ln_ffn2.b, nullptr, a, ld8(De), nullptr, nullptr, st)); }
+            EC_TRY(run_ffn(e, st, a, Mo, De, W.ffn2_a, W.ffn2_b, W.ffn2_bp, x, hbuf));
+        }
+        // block-final norm fused with the next block's FFN1 pre-norm (both read the same rows)
+        { PROF(PC_LAYERNORM, 0, (double)Mo * De * 10); EC_TRY(launch_layernorm(x, Mo, De, W.ln_out.g, W.ln_out.b, xo, last ? nullptr : a, ld8(De),
+                                last ? nullptr : e->bw[k + 1].ln_ffn1.g, last ? nullptr : e->bw[k + 1].ln_ffn1.b, st)); }
+        have_a = !last;
+        trace_block(e, st, k, "out", xo, Mo, De, De, 0);
+    }
+    e_cache_end(e, ws, s, ec);
+    if (rg) EC_TRY(emit_ragged(e, st, br, x, out_frames, out));
+    return 0;
+}
+
+// =================================================================== C ABI: one module on the product kernels
+extern "C" {
+
+int effconf_relpos_attention(const uint16_t* qu, const uint16_t* k, const uint16_t* v, const uint16_t* e, const float* dvu, int32_t dvu_ld,
+                             const int32_t* lens, int32_t batch, int32_t heads, int32_t frames, int32_t group, int32_t dim, uint16_t* out,
+                             int32_t ld_out, int32_t variant, void* stream) {
+    if (!qu || !k || !v || !e || !dvu || !lens || !out) return fail("null argument");
+    if (batch <= 0 || heads <= 0 || frames <= 0 || group <= 0 || !(group & 1) || dim <= 0 || (group * dim) % heads) return fail("bad attention shape");
+    AttnParams ap{};
+    const int Tp = ec_round_up(frames, group), Tg = Tp / group, d = group * dim / heads, dpad = ec_round_up(d, 32);
+    if (dpad > 192 || dvu_ld < dpad || ld_out < dim) return fail("unsupported head width / leading dimension");
+    ap.qu = qu; ap.kh = k; ap.vt = v; ap.eh = e; ap.dvu = dvu; ap.dvu_ld = dvu_ld; ap.lens = lens;
+    ap.B = batch; ap.H = heads; ap.T = frames; ap.G = group; ap.D = dim; ap.d = d; ap.dpad = dpad; ap.Tg = Tg; ap.Tgp = ec_round_up(Tg, 8);
+    ap.q_bstride = (long long)Tp * dim; ap.q_hstride = d; ap.q_rowstride = group * dim; ap.e_hstride = d; ap.e_rowstride = group * dim;
+    ap.out = out; ap.ldo = ld_out; ap.scale = 1.0f / std::sqrt((float)d);
+    ap.band_l = ap.band_r = 1 << 30;          // full context (the streaming variants are tested end to end against the reference goldens)
+    if (variant == 0) { EC_TRY(launch_relpos_attention(ap, (hipStream_t)stream)); return 0; }
+    if ((variant != 1 && variant != 2) || !relpos_attention2_supported(dpad)) return fail("attention variant not available for this head width");
+    EC_TRY(launch_relpos_attention2(ap, variant, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- per-kernel entry points: one module of a block on the product kernels, unit-testable against the reference's
+// per-module outputs (tests/golden/tiny_*.npz: trace/blocks.N.ffn1 | conv | out, trace/linear)
+size_t effconf_module_workspace_bytes(const EcEncoder* e, int32_t batch, int32_t frames) {
+    if (!e || batch <= 0 || frames <= 0) return 0;
+    size_t mx = 0;
+    for (const EcBlock& b : e->blocks) {
+        const size_t D = (size_t)std::max(b.dim_model, b.dim_expand);
+        mx = std::max(mx, D * ((size_t)b.ff_ratio + 4) * 2 + 64);
+    }
+    const size_t rows = (size_t)batch * frames;
+    size_t sub = 0;
+    {   // subsampler scratch: frames = mel frames here
+        const int L = e->cfg.sub_layers, C = e->cfg.sub_filters[L - 1];
+        int F = e->cfg.n_mels; for (int i = 0; i < L; ++i) F /= 2;
+        const size_t t1 = (frames - 1) / 2 + 1;
+        sub = al((size_t)batch * t1 * C * F * 2) + (L == 2 ? al((size_t)batch * (e->cfg.n_mels / 2) * t1 * ec_round_up(e->cfg.sub_filters[0], 64) * 2) : 0);
+    }
+    return std::max(al(rows * mx) + 4 * 256, sub + 256);
+}
+
+int effconf_ffn(EcEncoder* e, int32_t block, int32_t which, const float* x, int32_t rows, float* y, void* workspace, size_t workspace_bytes,
+                void* stream) {
+    if (!e || !e->finalized) return fail("encoder not finalized");
+    if (block < 0 || block >= (int)e->blocks.size() || (which != 1 && which != 2) || !x || !y || rows <= 0 || !workspace) return fail("bad argument");
+    const EcBlock& b = e->blocks[block];
+    const BlockW& W = e->bw[block];
+    const int D = which == 1 ? b.dim_model : b.dim_expand, F = D * b.ff_ratio;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    const size_t a_bytes = al((size_t)rows * ld8(D) * 2), h_bytes = al((size_t)rows * F * 2);
+    if (workspace_bytes < a_bytes + h_bytes) return fail("workspace too small");
+    bf16_t* a = reinterpret_cast<bf16_t*>(ws);
+    bf16_t* hbuf = reinterpret_cast<bf16_t*>(ws + a_bytes);
+    if (y != x && hipMemcpyAsync(y, x, (size_t)rows * D * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail("copy failed");
+    const LNp& ln = which == 1 ? W.ln_ffn1 : W.ln_ffn2;
+    const PackedLinear &L1 = which == 1 ? W.ffn1_a : W.ffn2_a, &L2 = which == 1 ? W.ffn1_b : W.ffn2_b;
+    const bf16_t* w2p = which == 1 ? W.ffn1_bp : W.ffn2_bp;
+    if (ffn_fused_supported(D)) return run_ffn(e, st, a, rows, D, L1, L2, w2p, y, hbuf, &ln);       // pre-norm in the kernel's prologue
+    EC_TRY(launch_layernorm(y, rows, D, ln.g, ln.b, nullptr, a, ld8(D), nullptr, nullptr, st));
+    return run_ffn(e, st, a, rows, D, L1, L2, w2p, y, hbuf);
+}
+
+int effconf_conv_module(EcEncoder* e, int32_t block, const float* x, int32_t batch, int32_t frames, float* y, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (!e || !e->finalized) return fail("encoder not finalized");
+    if (block < 0 || block >= (int)e->blocks.size() || !x || !y || batch <= 0 || frames <= 0 || !workspace) return fail("bad argument");
+    const EcBlock& b = e->blocks[block];
+    const BlockW& W = e->bw[block];
+    const int D = b.dim_model, De = b.dim_expand, T = frames, To = (T - 1) / b.conv_stride + 1, M = batch * T, Mo = batch * To;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = reinterpret_cast<char*>(workspace);
+    const size_t a_bytes = al((size_t)M * ld8(D) * 2), g_bytes = al((size_t)M * ld8(De) * 2), c_bytes = al((size_t)Mo * ld8(De) * 2);
+    if (workspace_bytes < a_bytes + g_bytes + c_bytes) return fail("workspace too small");
+    bf16_t* a = reinterpret_cast<bf16_t*>(ws);
+    bf16_t* gbuf = reinterpret_cast<bf16_t*>(ws + a_bytes);
+    bf16_t* cbuf = reinterpret_cast<bf16_t*>(ws + a_bytes + g_bytes);
+    // LayerNorm -> pointwise-1 + GLU (modules.py:511-514)
+    if (rs_gemm_supported(D)) {
+        EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De), nullptr, 0, 1.f, x, &W.ln_conv));
+    } else {
+        EC_TRY(launch_layernorm(x, M, D, W.ln_conv.g, W.ln_conv.b, nullptr, a, ld8(D), nullptr, nullptr, st));
+        EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De)));
+    }
+    // depthwise conv + BatchNorm + Swish (modules.py:516-518), pointwise-2 (modules.py:519)
+    EC_TRY(launch_dwconv(gbuf, batch, T, To, De, ld8(De), W.dw_w, W.dw_b, b.kernel_size, b.conv_stride, cbuf, st, nullptr, e->cfg.causal, dw_mfma_table(e, W.dw_a, b.kernel_size), W.dw_a3));
+    return run_rs_or_tiled(e, PC_GEMM_OTHER, st, cbuf, ld8(De), Mo, W.pw2, 1, EPI_F32, y, De);
+}
+
+int effconf_subsample(EcEncoder* e, const float* mel, int32_t batch, int32_t n_frames, float* y, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    if (!e || !e->finalized) return fail("encoder not finalized");
+    if (!mel || !y || batch <= 0 || n_frames <= 0 || !workspace) return fail("bad argument");
+    const Shapes s = make_shapes(e, batch, n_frames);
+    const int L = e->cfg.sub_layers, C = e->cfg.sub_filters[L - 1];
+    int F = e->cfg.n_mels; for (int i = 0; i < L; ++i) F /= 2;
+    const size_t sub_bytes = al((size_t)batch * s.T1 * C * F * 2);
+    const size_t tl1 = (n_frames - 1) / 2 + 1;
+    const size_t act_bytes = L == 2 ? al((size_t)batch * (e->cfg.n_mels / 2) * tl1 * ec_round_up(e->cfg.sub_filters[0], 64) * 2) : 0;
+    if (workspace_bytes < sub_bytes + act_bytes) return fail("workspace too small");
+    char* ws = reinterpret_cast<char*>(workspace);
+    return run_subsample_linear(e, (hipStream_t)stream, mel, batch, n_frames, s.T1, reinterpret_cast<bf16_t*>(ws), reinterpret_cast<bf16_t*>(ws + sub_bytes), y);
+}
+
+int effconf_layernorm_residual(EcEncoder* e, int32_t block, int32_t which, const float* x, const float* r, float alpha, int32_t rows, float* y,
+                               void* stream) {
+    if (!e || !e->finalized) return fail("encoder not finalized");
+    if (block < 0 || block >= (int)e->blocks.size() || which < 0 || which > 4 || !x || !y || rows <= 0) return fail("bad argument");
+    const EcBlock& b = e->blocks[block];
+    const BlockW& W = e->bw[block];
+    const LNp* ln[5] = {&W.ln_ffn1, &W.ln_att, &W.ln_conv, &W.ln_ffn2, &W.ln_out};
+    const int D = which >= 3 ? b.dim_expand : b.dim_model;
+    EC_TRY(launch_layernorm_residual(x, r, alpha, rows, D, ln[which]->g, ln[which]->b, y, (hipStream_t)stream));
+    return 0;
+}
+
+}  // extern "C"

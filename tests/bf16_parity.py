@@ -75,7 +75,7 @@ def chain_route(fuse, width):
 
 
 def front_route(plan, opts, ragged):
-    """What run_subsample_linear / the ragged branch of forward_core (encoder.hip) choose for this configuration and these options:
+    """What run_subsample_linear / the ragged branch of forward_core (forward_bf16.hip) choose for this configuration and these options:
     {"conv": "fp32" | "split" - the convolution's form, "subsample": the activation is in the trace (separate kernels write it), "fuse_chain": the option}."""
     fuse, auto = opts.get("fuse_subsample", 2), opts.get("sub3_auto", 1)
     C0, D0, F = plan.sub_filters[0], plan.blocks[0].dim_model, plan.n_mels

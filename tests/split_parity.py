@@ -10,7 +10,7 @@ error of at most ds_i in every score of row i moves every p_ij by a factor withi
 ds_i = (2 (d + 1) 2^-23 + 2^-20 + 2^-22) max_j (|q + u| |k_j| + |q + v| |e_ij|) / sqrt(d) (float32 summation of the d + 1 products, the split term, the two
 roundings of the scale multiply) and c_v = 2 Tg 2^-23 + 2^-20 + 8 2^-23 (P V summation, its split term, exp / sum / reciprocal).
 
-Trace layout of the split mode (encoder.hip forward_core_split): ``q`` is Q + b WITHOUT u (the attention kernel adds u), q / k / v / att_o live in the
+Trace layout of the split mode (forward_exact.hip forward_exact, fused kernel family): ``q`` is Q + b WITHOUT u (the attention kernel adds u), q / k / v / att_o live in the
 projections' row space (rectangular: b Tp + t; ragged: the group-padded stream rows) whose chunk-padding rows are never written and are ignored here;
 ``e`` is the float32 positional projection; ``conv_res`` exists on transition blocks, ``x_conv`` on the per-module route only, ``out`` wherever no head is merged into chain A's tail."""
 import numpy as np
@@ -29,7 +29,7 @@ EPS = 2.0 ** -23
 
 
 def split_route(plan, opts):
-    """What forward_core_split chooses for these options: {"chain": the row-local chains (split_chain and split_ffn), "ffn": sxf_ffn.hip where no chain runs,
+    """What forward_exact (fused kernel family) chooses for these options: {"chain": the row-local chains (split_chain and split_ffn), "ffn": sxf_ffn.hip where no chain runs,
     "sublin": sxf_sub.hip}.  A traced forward takes this route only with trace_fused = 1; otherwise chain = sublin = False."""
     fused = bool(opts.get("trace_fused", 0))
     ffn = bool(opts.get("split_ffn", 1))

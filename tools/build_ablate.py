@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing-only library for tools/ablate_bench.py: the product objects with encoder.hip and attention2.hip recompiled under -DEFFCONF_ABLATE (EFFCONF_SKIP =
+"""Timing-only library for tools/ablate_bench.py: the product objects with the forward entries and schedules (encoder.hip, forward_bf16.hip) and attention2.hip recompiled under -DEFFCONF_ABLATE (EFFCONF_SKIP =
 bit mask of kernel families whose launches are dropped; EFFCONF_ATTN_ABLATE = bit mask of the attention kernel's parts - the product kernel has no such branches),
 and the kernels with in-kernel phase profilers recompiled under -DEFFCONF_PHASE_PROF (EFFCONF_{CHAIN,CHAIN2,CHAIN3,ATTN,FFN}_PHASES).  Written to
 efficientconformer_amd/build/libeffconf_ablate.so; never loaded by the package (EFFCONF_ABLATE_LIB=<path> points the tools at it)."""
@@ -14,7 +14,7 @@ from efficientconformer_amd import _build as B  # noqa: E402
 B.build()
 objdir = os.path.join(B.HERE, "build")
 # chain / chain2 / chain3 / attention / rsgemm: their in-kernel phase profilers (EFFCONF_{CHAIN,CHAIN2,CHAIN3,ATTN,FFN}_PHASES) exist in this library only
-REBUILT = ("encoder.hip", "attention2.hip", "chain.hip", "chain2.hip", "chain3.hip", "attention.hip", "rsgemm.hip")
+REBUILT = ("encoder.hip", "forward_bf16.hip", "attention2.hip", "chain.hip", "chain2.hip", "chain3.hip", "attention.hip", "rsgemm.hip")
 abl = []
 for src in REBUILT:
     obj = os.path.join(objdir, src.replace(".hip", "_ablate.o"))
