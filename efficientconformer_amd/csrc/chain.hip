@@ -109,12 +109,13 @@ __device__ __forceinline__ void ln_stats(const f32x16 (&xc)[NT], int D, float& m
 }
 // xf = bf16((xc - mean) * rstd) as the K-permuted B fragments of the next GEMM.  The LayerNorm's gamma / beta are folded into that
 // GEMM at pack time (W diag(gamma), b + W beta), so the pre-norms cost no loads; pad columns become -mean*rstd but meet zero
-// weight columns
+// weight columns.  skip_last: the last k-step is all pad and no GEMM reads its fragment (ks_skip_last) - it is not built
 template <int KS>
-__device__ __forceinline__ void norm_frags(const f32x16 (&xc)[KS / 2], float mean, float rstd, bf16x8 (&xf)[KS]) {
+__device__ __forceinline__ void norm_frags(const f32x16 (&xc)[KS / 2], float mean, float rstd, bf16x8 (&xf)[KS], bool skip_last) {
     const float nm = -mean * rstd;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
+        if (s == KS - 1 && skip_last) continue;
         const int r = 8 * (s & 1);
         xf[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
                                      pack_bf2(fmaf(xc[s >> 1][r + 2], rstd, nm), fmaf(xc[s >> 1][r + 3], rstd, nm)),
@@ -198,16 +199,17 @@ __device__ __forceinline__ void store_x(char* yb, size_t pitch, int D, int m_bas
     }
 }
 // bf16 rows (natural column order) -> K-permuted B fragments: k-step s of half h = columns 16s + 4h + {0..3} and 16s + 8 + 4h + {0..3}
-template <int KS, int W>
-__device__ __forceinline__ void take_a(char* stg, int lane, int D, int m_base, int M, const u32x4 (&v)[8], bf16x8 (&xf)[KS]) {
+// (skip_last: the last k-step is all pad and its fragment is not built, see norm_frags)
+template <int KS, int W, int OFF, int N>
+__device__ __forceinline__ void take_a(char* stg, int lane, int D, int m_base, int M, const u32x4 (&v)[N], bf16x8 (&xf)[KS], bool skip_last) {
     const int lr = lane & 31, half = lane >> 5;
     wave_sync();
-    stage_put<0>(stg, lane, v);
+    stage_put<OFF>(stg, lane, v);
     wave_sync();
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int s = 8 * W + j;
-        if (s < KS) {
+        if (s < KS && !(s == KS - 1 && skip_last)) {
             const char* src = stg + lr * STG_ROW + (16 * j + 4 * half) * 2;
             uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 16);
             const int c0 = 16 * s + 4 * half;           // D % 4 == 0: each 4-column piece is valid or not as a whole
@@ -217,21 +219,16 @@ __device__ __forceinline__ void take_a(char* stg, int lane, int D, int m_base, i
         }
     }
 }
-template <int KS, int W>
-__device__ __forceinline__ void load_a(const char* ab, size_t pitch, int row_bytes, int D, int m_base, int M, char* stg, int lane, bf16x8 (&xf)[KS]) {
-    constexpr int NWIN = (KS + 7) / 8;                  // 128 columns per window
-    if constexpr (W < NWIN) {
-        u32x4 v[8] = {};
-        stage_load<0>(ab, pitch, row_bytes, m_base, M, 256 * W, lane, v);
-        take_a<KS, W>(stg, lane, D, m_base, M, v, xf);
-        load_a<KS, W + 1>(ab, pitch, row_bytes, D, m_base, M, stg, lane, xf);
-    }
+// compile-time loop (window indices select registers of the staging arrays)
+template <int I, int N, class F> __device__ __forceinline__ void static_for1(F&& f) {
+    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for1<I + 1, N>(f); }
 }
 
 // PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN_PHASES=81 | 162 | 163: KS = 8 full chain, KS = 16 head / tail): s_memtime per phase of the FFN stages -
 // 0 advance (DMA wait + barrier + refill), 1 GEMM1, 2 Swish, 3 GEMM2, 4 everything else, 5 waves
-template <int KS, int NW, int NBUF, int KIND, bool PROF = false>
-__global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_kernel(const ChainDev cd, unsigned long long* prof = nullptr) {
+// KPAD: the last k-step holds pad columns only and is left out of every product over the model width (rowstat.h, ks_skip_last)
+template <int KS, int NW, int NBUF, int KIND, bool PROF, bool KPAD>
+__device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long long* prof) {
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
     if constexpr (PROF) t0 = __builtin_readcyclecounter();
 #define CH_TICK(i) do { if constexpr (PROF) { asm volatile("" ::: "memory"); const unsigned long long t1_ = __builtin_readcyclecounter(); ph[i] += t1_ - t0; t0 = t1_; } } while (0)
@@ -253,6 +250,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
     const int m_base = (blockIdx.x * NW + wave) * 32;
     char* stg = stg_base + wave * STG_BYTES;
     const int D = p.D;
+    // k-step s takes part in the products over the model width: all but the last one of a KPAD instance.  Compile-time in every (fully unrolled) loop: the
+    // dropped step costs no fragment read, no MFMA and no registers for its activation fragment
+    constexpr bool skip_last = KPAD;
+    auto kstep = [](int s) __attribute__((always_inline)) { return s < KS - 1 || !KPAD; };
 
     // ---- chunk schedule: [g0] [ffn0] [ffn1] [g1]
     const int n_g0 = (ISB || PRE) ? (NT + 1) / 2 : 0;
@@ -402,19 +403,20 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
     f32x16 xc[NT];
     bf16x8 xf[KS];
     if constexpr (ISB || PRE) {
-        // first windows of x and A fetched together (one HBM latency instead of two), the rest by the generic loaders
+        // Every window of x (64 fp32 columns each) and of A (128 bf16 columns each) is requested before the first one is consumed: ONE HBM round trip
+        // for the wave's rows.  (Window by window, every later request sat behind the wave_sync() fences of the previous take_*: three dependent round
+        // trips at KS = 12, in a one-round launch whose CU has nothing else to run.)  The staging registers are at their peak here (8 per window: 40 at
+        // KS = 12) while xc / xf are still dead, and die window by window as take_* fills the tiles in the former order, through the same staging path.
+        // The ring's priming DMAs above are OLDER than these loads and the counted wait below still allows exactly the chunks ahead: loads retire in order,
+        // so the argument above advance() is untouched.
         const char* xb = reinterpret_cast<const char*>(p.X);
         const char* ab = reinterpret_cast<const char*>(p.A);
-        constexpr int NWX = (NT + 1) / 2;
-        u32x4 vx[16] = {}, va[8] = {};
-        stage_load<0>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 0, lane, vx);
-        if constexpr (NWX > 1) stage_load<8>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 256, lane, vx);
-        stage_load<0>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, 0, lane, va);
-        take_x<NT, 0, 0>(stg, lane, D, vx, xc);
-        if constexpr (NWX > 1) take_x<NT, 1, 8>(stg, lane, D, vx, xc);
-        take_a<KS, 0>(stg, lane, D, m_base, p.M, va, xf);
-        load_x<NT, 2>(xb, (size_t)p.ldx * 4, D, m_base, p.M, stg, lane, xc);
-        load_a<KS, 1>(ab, (size_t)p.lda * 2, p.lda * 2, D, m_base, p.M, stg, lane, xf);
+        constexpr int NWX = (NT + 1) / 2, NWA = (KS + 7) / 8;
+        u32x4 vx[8 * NWX] = {}, va[8 * NWA] = {};
+        static_for1<0, NWX>([&](auto W) { constexpr int w = decltype(W)::value; stage_load<8 * w>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 256 * w, lane, vx); });
+        static_for1<0, NWA>([&](auto W) { constexpr int w = decltype(W)::value; stage_load<8 * w>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, 256 * w, lane, va); });
+        static_for1<0, NWX>([&](auto W) { constexpr int w = decltype(W)::value; take_x<NT, w, 8 * w>(stg, lane, D, vx, xc); });
+        static_for1<0, NWA>([&](auto W) { constexpr int w = decltype(W)::value; take_a<KS, w, 8 * w>(stg, lane, D, m_base, p.M, va, xf, skip_last); });
     } else {
         load_x<NT, 0>(reinterpret_cast<const char*>(p.X), (size_t)p.ldx * 4, D, m_base, p.M, stg, lane, xc);
     }
@@ -449,9 +451,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
                     for (int s0 = 0; s0 < KS; s0 += FB) {
                         bf16x8 wa[FB];
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) wa[i] = wfrag(buf + j * HALF, s0 + i);
+                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) xc[2 * c + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[2 * c + j], 0, 0, 0);
+                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) xc[2 * c + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[2 * c + j], 0, 0, 0);
                     }
                 }
             }
@@ -483,9 +485,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
         for (int s0 = 0; s0 < KS; s0 += FB) {
             bf16x8 wa[FB];
 #pragma unroll
-            for (int i = 0; i < FB; ++i) wa[i] = wfrag(buf, s0 + i);
+            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf, s0 + i);
 #pragma unroll
-            for (int i = 0; i < FB; ++i) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
+            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
             after(s0 / FB);
         }
         return h;
@@ -511,7 +513,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
     auto ffn_stage = [&](const float* sb1, const float* sb2, int nchunks) __attribute__((always_inline)) {
         float mean, rstd;
         ln_stats<NT>(xc, D, mean, rstd);
-        norm_frags<KS>(xc, mean, rstd, xf);
+        norm_frags<KS>(xc, mean, rstd, xf, skip_last);
         add_cvec<NT>(xc, sb2, half);
         if constexpr (PIPE) {
             CH_TICK(4);
@@ -589,7 +591,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
         // ---- conv-module pre-norm, pointwise-1 + GLU -> bf16 rows (modules.py:512-514)
         float mean, rstd;
         ln_stats<NT>(xc, D, mean, rstd);
-        norm_frags<KS>(xc, mean, rstd, xf);
+        norm_frags<KS>(xc, mean, rstd, xf, skip_last);
         // the slab reader's lane constants, made again for this loop: the g0 stage's copies (q0, w1row and the KS wrap-around terms the compiler derives from
         // q0) were spilled behind that stage and reloaded here, each reload draining the two ring chunks in flight
         const int lane = lane_now(), lr = lane & 31, half = lane >> 5;
@@ -616,9 +618,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
             for (int s0 = 0; s0 < KS; s0 += FB) {
                 bf16x8 wa[2][FB];
 #pragma unroll
-                for (int i = 0; i < FB; ++i) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
+                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
 #pragma unroll
-                for (int i = 0; i < FB; ++i) {
+                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
                     acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
                 }
@@ -653,7 +655,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
             ffn_stage(s_f1b1, s_f1b2, n_f1);                                        // FFN1 of this block
             float mean, rstd;
             ln_stats<NT>(xc, D, mean, rstd);
-            norm_frags<KS>(xc, mean, rstd, xf);                                     // attention pre-norm
+            norm_frags<KS>(xc, mean, rstd, xf, skip_last);                                     // attention pre-norm
             CH_TICK(4);
             // x is final here (the Q/K/V projection only reads it): store it now so that its registers are free during the last stage
             store_x<NT, 0>(reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D, m_base, p.M, stg, lane, xc);
@@ -690,9 +692,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
                 for (int s0 = 0; s0 < KS; s0 += FB) {
                     bf16x8 wa[2][FB];
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
+                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) {
+                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
                         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
                         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
                     }
@@ -759,6 +761,17 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_k
         }
     }
 #undef CH_TICK
+}
+
+template <int KS, int NW, int NBUF, int KIND, bool PROF = false>
+__global__ __launch_bounds__(NW * 64, (NW == 4 && KS <= 8) ? 2 : 1) void chain_kernel(const ChainDev cd, unsigned long long* prof = nullptr) {
+    chain_body<KS, NW, NBUF, KIND, PROF, false>(cd, prof);
+}
+// the same chain for a width whose last k-step is all pad (D = 168 at KS = 12, D = 240 at KS = 16)
+template <int KS, int NW, int NBUF, int KIND>
+__global__ __launch_bounds__(NW * 64, 1) void chain_kpad_kernel(const ChainDev cd) {
+    static_assert(KS >= 12, "see ks_skip_last");
+    chain_body<KS, NW, NBUF, KIND, false, true>(cd, nullptr);
 }
 
 #ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py) only
@@ -848,6 +861,14 @@ int launch_chain_t(const ChainParams& p, hipStream_t s) {
         }
     }
 #endif
+    if constexpr (KS >= 12) {
+        if (ks_skip_last<KS>((p.D + 15) / 16)) {
+            static LdsAttr attr_kpad;
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&chain_kpad_kernel<KS, NW, NBUF, KIND>), lds, attr_kpad);
+            hipLaunchKernelGGL((chain_kpad_kernel<KS, NW, NBUF, KIND>), dim3((p.M + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64), lds, s, cd);
+            return hipGetLastError() == hipSuccess ? 0 : -1;
+        }
+    }
     hipLaunchKernelGGL((chain_kernel<KS, NW, NBUF, KIND, false>), dim3((p.M + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64), lds, s, cd, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

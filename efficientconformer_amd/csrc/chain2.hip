@@ -81,8 +81,9 @@ __device__ __forceinline__ void s2_store(const char* stg, char* base, size_t pit
 }
 
 // PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN2_PHASES=1): s_memtime per phase, wave A and wave B of every 8th workgroup's first pair
-template <int KS, bool PROF = false>
-__global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd, unsigned long long* prof = nullptr) {
+// KPAD: the last k-step holds pad columns only and is left out of every product over the model width (rowstat.h, ks_skip_last)
+template <int KS, bool PROF, bool KPAD>
+__device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long long* prof) {
     unsigned long long ph[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
     if constexpr (PROF) t0 = __builtin_readcyclecounter();
 #define C2_TICK(i) do { if constexpr (PROF) { asm volatile("" ::: "memory"); const unsigned long long t1_ = __builtin_readcyclecounter(); ph[i] += t1_ - t0; t0 = t1_; } } while (0)
@@ -100,6 +101,10 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
     char* stg = stg_base + wave * S2_BYTES;                   // this wave's staging region
     const char* stgp = stg_base + (wave ^ 4) * S2_BYTES;      // the partner's (read only)
     const int D = p.D;
+    // k-step s takes part in the products over the model width: all but the last one of a KPAD instance (compile-time in every unrolled loop).  The dropped
+    // k-step is wave B's last own fragment: not built (zeros travel through the exchange in its place), not read back, no weight fragment, no MFMA
+    auto kstep = [](int s) __attribute__((always_inline)) { return s < KS - 1 || !KPAD; };
+    const bool own_pad = KPAD && cw == 1;                     // this wave's own[KSH - 1] is the dropped k-step
 
     // ---- chunk schedule: [g0] [g1]
     const int n_g0 = (NT + 1) / 2;
@@ -175,7 +180,7 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
             for (int i = 0; i < 4; ++i)
                 if (r0 + i < KSH) {
                     xf[r0 + i] = *reinterpret_cast<const bf16x8*>(stgA + i * 1024 + lane * 16);
-                    xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(stgB + i * 1024 + lane * 16);
+                    if (kstep(KSH + r0 + i)) xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(stgB + i * 1024 + lane * 16);
                 }
         }
         wg_barrier();                                        // the staging regions are private again
@@ -211,7 +216,8 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
             wave_sync();
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if constexpr (true) if (4 * w + j < KSH) {
+                if (4 * w + j == KSH - 1 && own_pad) own[4 * w + j] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u));
+                else if (4 * w + j < KSH) {
                     const int s = cw * KSH + 4 * w + j;
                     const char* src = stg + lr * S2_ROW + (16 * j + 4 * half) * 2;
                     uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 16);
@@ -295,7 +301,8 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
 #pragma unroll
         for (int s = 0; s < KSH; ++s) {
             const int r = 8 * (s & 1);
-            own[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
+            if (s == KSH - 1 && own_pad) own[s] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u));
+            else own[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
                                           pack_bf2(fmaf(xc[s >> 1][r + 2], rstd, nm), fmaf(xc[s >> 1][r + 3], rstd, nm)),
                                           pack_bf2(fmaf(xc[s >> 1][r + 4], rstd, nm), fmaf(xc[s >> 1][r + 5], rstd, nm)),
                                           pack_bf2(fmaf(xc[s >> 1][r + 6], rstd, nm), fmaf(xc[s >> 1][r + 7], rstd, nm))));
@@ -332,9 +339,9 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
                 for (int s0 = 0; s0 < KS; s0 += FB) {
                     bf16x8 wa[FB];
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) wa[i] = wfrag(buf + j * HALF, s0 + i);
+                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[tt], 0, 0, 0);
+                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[tt], 0, 0, 0);
                 }
             }
         }
@@ -358,9 +365,9 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
         for (int s0 = 0; s0 < KS; s0 += FB) {
             bf16x8 wa[2][FB];
 #pragma unroll
-            for (int i = 0; i < FB; ++i) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
+            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
 #pragma unroll
-            for (int i = 0; i < FB; ++i) {
+            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
             }
@@ -417,6 +424,16 @@ __global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd,
 #undef C2_TICK
 }
 
+template <int KS, bool PROF = false>
+__global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd, unsigned long long* prof = nullptr) {
+    chain2_body<KS, PROF, false>(cd, prof);
+}
+// the same chain for a width whose last k-step is all pad (D = 240)
+template <int KS>
+__global__ __launch_bounds__(NW2 * 64, 1) void chain2_kpad_kernel(const ChainDev2 cd) {
+    chain2_body<KS, false, true>(cd, nullptr);
+}
+
 #ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py) only
 unsigned long long* g_chain2_prof = nullptr;
 void chain2_prof_dump() {
@@ -464,6 +481,12 @@ int launch_chain2(const ChainParams& p, hipStream_t s) {
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
 #endif
+    if (ks_skip_last<KS>((p.D + 15) / 16)) {
+        static LdsAttr attr_kpad;
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&chain2_kpad_kernel<KS>), lds, attr_kpad);
+        hipLaunchKernelGGL((chain2_kpad_kernel<KS>), dim3((p.M + 127) / 128), dim3(NW2 * 64), lds, s, cd);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     hipLaunchKernelGGL((chain2_kernel<KS, false>), dim3((p.M + 127) / 128), dim3(NW2 * 64), lds, s, cd, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -108,8 +108,9 @@ __device__ __forceinline__ void s3_store(const char* stg, char* base, size_t pit
 //   block norm: 4                                                  (PRE)
 //   Q/K/V:     4  XB  n_g1 advances  2 (drain)                     (POST)
 // PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN3_PHASES=<kind>): s_memtime per phase, the three waves of every 8th workgroup's first row tile
-template <int KS, int KIND, bool PROF = false>
-__global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd, unsigned long long* prof = nullptr) {
+// KPAD: the last k-step holds pad columns only and is left out of every product over the model width (rowstat.h, ks_skip_last)
+template <int KS, int KIND, bool PROF, bool KPAD>
+__device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long long* prof) {
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
     if constexpr (PROF) t0 = __builtin_readcyclecounter();
 #define C3_TICK(i) do { if constexpr (PROF) { asm volatile("" ::: "memory"); const unsigned long long t1_ = __builtin_readcyclecounter(); ph[i] += t1_ - t0; t0 = t1_; } } while (0)
@@ -136,6 +137,10 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     float* slot0 = reinterpret_cast<float*>(win0 + 2 * S3_WIN);              // B0's hand-off slot, B1's (one float per lane)
     float* slot1 = slot0 + 64;
     const int D = p.D;
+    // k-step s takes part in the products over the model width: all but the last one of a KPAD instance (compile-time in every unrolled loop).  The dropped
+    // k-step is wave B1's last own fragment: not built (zeros travel through the exchange in its place), not read back, no weight fragment, no MFMA - wave A's
+    // dependency chain per hidden chunk is 15 MFMAs instead of 16
+    auto kstep = [](int s) __attribute__((always_inline)) { return s < KS - 1 || !KPAD; };
 
     const int n_g0 = PRE ? (NT + 1) / 2 : 0;
     const int n_f0 = PRE ? p.f[0].Fp / CH : 0;
@@ -172,7 +177,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         for (int i = 0; i < 4; ++i)
             if (r0 + i < KSH) {
                 xf[r0 + i] = *reinterpret_cast<const bf16x8*>(win0 + i * 1024 + lane * 16);
-                xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(win1 + i * 1024 + lane * 16);
+                if (kstep(KSH + r0 + i)) xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(win1 + i * 1024 + lane * 16);
             }
     };
     // destination rows of the Q/K/V write-out: (b, t) -> (b * Tp + t) * D for the 2 rows a lane stores per half-tile instruction pair
@@ -193,9 +198,9 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
         for (int s0 = 0; s0 < KS; s0 += FB) {
             bf16x8 wa[2][FB];
 #pragma unroll
-            for (int i = 0; i < FB; ++i) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
+            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
 #pragma unroll
-            for (int i = 0; i < FB; ++i) {
+            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
                 acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
             }
@@ -301,9 +306,9 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
             for (int s0 = 0; s0 < KS; s0 += FB) {
                 bf16x8 wa[FB];
 #pragma unroll
-                for (int i = 0; i < FB; ++i) wa[i] = wfrag(buf, s0 + i);
+                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf, s0 + i);
 #pragma unroll
-                for (int i = 0; i < FB; ++i) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
+                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
                 between(s0 / FB);
             }
             return h;
@@ -378,6 +383,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
     // extra offset registers were spilled, and their reloads inside the FFN loop waited behind the ring's DMAs (chain A at D = 240: +39 %)
     __builtin_assume(bidx < NB3);
     const int ct0 = cw * NTH;
+    const bool own_pad = KPAD && cw == 1;                    // this wave's own fragment KSH - 1 is the dropped k-step
     char* stg = cw ? win1 : win0;                            // this wave's window
     uint32_t off_r[PER], off_f[PER];
 #pragma unroll
@@ -495,7 +501,8 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
 #pragma unroll
         for (int s = 0; s < KSH; ++s) {
             const int r = 8 * (s & 1);
-            own[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
+            if (s == KSH - 1 && own_pad) own[s] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u));
+            else own[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
                                           pack_bf2(fmaf(xc[s >> 1][r + 2], rstd, nm), fmaf(xc[s >> 1][r + 3], rstd, nm)),
                                           pack_bf2(fmaf(xc[s >> 1][r + 4], rstd, nm), fmaf(xc[s >> 1][r + 5], rstd, nm)),
                                           pack_bf2(fmaf(xc[s >> 1][r + 6], rstd, nm), fmaf(xc[s >> 1][r + 7], rstd, nm))));
@@ -571,6 +578,7 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int s = cw * KSH + 4 * w + j;
+                    if (4 * w + j == KSH - 1 && own_pad) { own4[j] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u)); continue; }
                     const char* src = stg + lr * S3_ROW + (16 * j + 4 * half) * 2;
                     uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 16);
                     const int c0 = 16 * s + 4 * half;
@@ -605,9 +613,9 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
                     for (int s0 = 0; s0 < KS; s0 += FB) {
                         bf16x8 wa[FB];
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) wa[i] = wfrag(buf + j * HALF, s0 + i);
+                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xa[s0 + i], xc[tt], 0, 0, 0);
+                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xa[s0 + i], xc[tt], 0, 0, 0);
                     }
                 }
             }
@@ -696,6 +704,16 @@ __global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd,
 #undef C3_DUMP
 }
 
+template <int KS, int KIND, bool PROF = false>
+__global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd, unsigned long long* prof = nullptr) {
+    chain3_body<KS, KIND, PROF, false>(cd, prof);
+}
+// the same chain for a width whose last k-step is all pad (D = 240)
+template <int KS, int KIND>
+__global__ __launch_bounds__(NW3 * 64, 1) void chain3_kpad_kernel(const ChainDev3 cd) {
+    chain3_body<KS, KIND, false, true>(cd, nullptr);
+}
+
 #ifdef EFFCONF_PHASE_PROF    // in-kernel phase profiles: a tuning build (tools/build_ablate.py) only
 unsigned long long* g_chain3_prof = nullptr;
 void chain3_prof_dump() {
@@ -752,6 +770,12 @@ int launch_chain3_t(const ChainParams& p, hipStream_t s) {
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
 #endif
+    if (ks_skip_last<KS>((p.D + 15) / 16)) {
+        static LdsAttr attr_kpad;
+        ensure_dynamic_lds(reinterpret_cast<const void*>(&chain3_kpad_kernel<KS, KIND>), lds, attr_kpad);
+        hipLaunchKernelGGL((chain3_kpad_kernel<KS, KIND>), dim3((p.M + 127) / 128), dim3(NW3 * 64), lds, s, cd);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     hipLaunchKernelGGL((chain3_kernel<KS, KIND, false>), dim3((p.M + 127) / 128), dim3(NW3 * 64), lds, s, cd, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -181,6 +181,18 @@ __device__ __forceinline__ void fetch_row_bf16(const bf16_t* A, int lda, int m_b
 }
 
 
+// Valid k-steps of a product whose K is the model width D, padded to KS k-steps of 16 columns: ks_valid = ceil(D / 16), a run-time value of the launch.
+// A k-step s >= ks_valid holds pad columns only - exact zeros in the packed weights, -mean * rstd (norm_frags) or zeros (take_a) in the activation fragments -
+// so its MFMAs add +-0 to their accumulators.  The chains drop the LAST k-step when it is such a one (D = 168 and 176 at KS = 12, D = 240 at KS = 16; not
+// D = 184 or 248, whose last k-step is half valid): no weight fragment read, no MFMA, no activation fragment built.  The launcher applies the rule and picks
+// between two instances of the kernel (*_kpad_kernel: KS - 1 k-steps in the fully unrolled loops).  A wave-uniform branch around the last step inside ONE
+// instance was tried first: in the register-bound D = 168 shapes it cost 20 - 90 bytes of NEW scratch (the accumulator tuple of the conditional MFMA is no
+// longer coalesced), and two forms of each loop behind one branch cost more.  Only the widths of 12 and 16 k-steps take part: no shipped narrower width has an
+// all-pad k-step (D = 120: eight valid columns in k-step 7).  A width with several all-pad k-steps (D = 132 at KS = 12) keeps the others: correct, not minimal.
+// The remaining k-steps keep their order.  Values: an accumulator loses additions of +-0 only; one that is exactly -0.0 could become +0.0, which compares
+// equal (torch.equal, np.array_equal) and which no consumer divides by.
+template <int KS> __host__ __device__ constexpr bool ks_skip_last(int ks_valid) { return KS >= 12 && ks_valid < KS; }
+
 struct FastDiv32 {   // exact for n * d < 2^32
     uint32_t mul, d;
     __host__ __device__ FastDiv32() : mul(0), d(1) {}
