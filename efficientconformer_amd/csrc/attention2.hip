@@ -51,15 +51,6 @@ __device__ __forceinline__ void wave_sync() {                   // per-wave LDS 
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// The lane id, computed again where it is asked for (two VALU instructions).  The compiler cannot rematerialise what it derives from threadIdx.x (an argument
-// register), so per-thread addresses that are affine in the lane id and used once per key block were kept in scratch across the block's MFMAs, and their
-// reloads made the loop wait for the K / V / E loads it had just issued.  A volatile statement is neither merged with another one nor hoisted out of the loop.
-__device__ __forceinline__ int lane_now() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 lds_tr16(const char* p) {      // ds_read_b64_tr_b16
     const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));

@@ -25,8 +25,7 @@
 //     bf16 products (Q+u, Q+v, K, V rows, or the GLU output) out.
 // HBM bytes per row: chain A 4D (x) + 2D (A) in, 4D (x) + 8D (Q+u, Q+v, K, V) out; chain B 6D in, 4D + 2D out — against
 // ~74D for the unfused block.
-#include "kernels.h"
-#include "rowstat.h"
+#include "chain_common.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -49,23 +48,6 @@ struct Geo {
     static constexpr int BUF = 2 * HALF;
 };
 
-struct ChainDev {
-    ChainParams p;
-    FastDiv32 fT, fD;
-    int nf[8];            // float offsets of the LDS constant arrays (see chain_const_layout)
-    int nfl_kb;           // size of the constant block in KiB (LDS-DMA pieces)
-    int ldr, ld2;         // row pitch (elements) shared by every row-shaped weight of the chain / by the FFN second weights
-};
-
-// The lane id, computed again where it is asked for (two VALU instructions; a volatile statement is neither merged with another one nor hoisted).  For lane
-// constants that two distant stages share: the compiler cannot rematerialise what derives from threadIdx.x (an argument register) and parks it in scratch between
-// the stages - and a scratch reload waits on the vmcnt queue the ring's DMAs are in.
-__device__ __forceinline__ int lane_now() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
 // ---- C-layout helpers -----------------------------------------------------------------------------------------------------
 template <int NT>
 __device__ __forceinline__ void add_cvec(f32x16 (&xc)[NT], const float* sv, int half) {    // xc[t][r] += sv[column]
@@ -77,6 +59,7 @@ __device__ __forceinline__ void add_cvec(f32x16 (&xc)[NT], const float* sv, int 
             xc[t][4 * q + 0] += v.x; xc[t][4 * q + 1] += v.y; xc[t][4 * q + 2] += v.z; xc[t][4 * q + 3] += v.w;
         }
 }
+// Local code, not chain_common.h's row_psum / row_pvar: as calls (same arithmetic) they cost chain_kernel<16, 4, 3, 1> 4 and chain_kpad_kernel<12, 2, 3, 2> 8 bytes of new scratch.
 // two-pass statistics over the D valid columns (pad columns hold exact zeros: nothing to the sum, masked out of the squares); eps 1e-6 (reference modules.py:377, 447; blocks.py:97)
 template <int NT>
 __device__ __forceinline__ void ln_stats(const f32x16 (&xc)[NT], int D, float& mean, float& rstd) {
@@ -107,20 +90,14 @@ __device__ __forceinline__ void ln_stats(const f32x16 (&xc)[NT], int D, float& m
     // the weight DMAs: every reload in a chunk loop waited for the whole prefetch queue)
     asm volatile("" : "+v"(mean));
 }
-// xf = bf16((xc - mean) * rstd) as the K-permuted B fragments of the next GEMM.  The LayerNorm's gamma / beta are folded into that
-// GEMM at pack time (W diag(gamma), b + W beta), so the pre-norms cost no loads; pad columns become -mean*rstd but meet zero
-// weight columns.  skip_last: the last k-step is all pad and no GEMM reads its fragment (ks_skip_last) - it is not built
+// xf = bf16((xc - mean) * rstd) as the K-permuted B fragments of the next GEMM (chain_common.h, norm_frag).  skip_last: the last k-step is all pad and no GEMM reads its fragment (ks_skip_last) - it is not built
 template <int KS>
 __device__ __forceinline__ void norm_frags(const f32x16 (&xc)[KS / 2], float mean, float rstd, bf16x8 (&xf)[KS], bool skip_last) {
     const float nm = -mean * rstd;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
         if (s == KS - 1 && skip_last) continue;
-        const int r = 8 * (s & 1);
-        xf[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
-                                     pack_bf2(fmaf(xc[s >> 1][r + 2], rstd, nm), fmaf(xc[s >> 1][r + 3], rstd, nm)),
-                                     pack_bf2(fmaf(xc[s >> 1][r + 4], rstd, nm), fmaf(xc[s >> 1][r + 5], rstd, nm)),
-                                     pack_bf2(fmaf(xc[s >> 1][r + 6], rstd, nm), fmaf(xc[s >> 1][r + 7], rstd, nm))));
+        xf[s] = norm_frag(xc, s, rstd, nm);
     }
 }
 template <int NT>
@@ -219,11 +196,6 @@ __device__ __forceinline__ void take_a(char* stg, int lane, int D, int m_base, i
         }
     }
 }
-// compile-time loop (window indices select registers of the staging arrays)
-template <int I, int N, class F> __device__ __forceinline__ void static_for1(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for1<I + 1, N>(f); }
-}
-
 // PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN_PHASES=81 | 162 | 163: KS = 8 full chain, KS = 16 head / tail): s_memtime per phase of the FFN stages -
 // 0 advance (DMA wait + barrier + refill), 1 GEMM1, 2 Swish, 3 GEMM2, 4 everything else, 5 waves
 // KPAD: the last k-step holds pad columns only and is left out of every product over the model width (rowstat.h, ks_skip_last)
@@ -250,10 +222,8 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
     const int m_base = (blockIdx.x * NW + wave) * 32;
     char* stg = stg_base + wave * STG_BYTES;
     const int D = p.D;
-    // k-step s takes part in the products over the model width: all but the last one of a KPAD instance.  Compile-time in every (fully unrolled) loop: the
-    // dropped step costs no fragment read, no MFMA and no registers for its activation fragment
+    // KPAD: the dropped k-step (rowstat.h, kstep)
     constexpr bool skip_last = KPAD;
-    auto kstep = [](int s) __attribute__((always_inline)) { return s < KS - 1 || !KPAD; };
 
     // ---- chunk schedule: [g0] [ffn0] [ffn1] [g1]
     const int n_g0 = (ISB || PRE) ? (NT + 1) / 2 : 0;
@@ -413,10 +383,10 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
         const char* ab = reinterpret_cast<const char*>(p.A);
         constexpr int NWX = (NT + 1) / 2, NWA = (KS + 7) / 8;
         u32x4 vx[8 * NWX] = {}, va[8 * NWA] = {};
-        static_for1<0, NWX>([&](auto W) { constexpr int w = decltype(W)::value; stage_load<8 * w>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 256 * w, lane, vx); });
-        static_for1<0, NWA>([&](auto W) { constexpr int w = decltype(W)::value; stage_load<8 * w>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, 256 * w, lane, va); });
-        static_for1<0, NWX>([&](auto W) { constexpr int w = decltype(W)::value; take_x<NT, w, 8 * w>(stg, lane, D, vx, xc); });
-        static_for1<0, NWA>([&](auto W) { constexpr int w = decltype(W)::value; take_a<KS, w, 8 * w>(stg, lane, D, m_base, p.M, va, xf, skip_last); });
+        static_for<0, NWX>([&](auto W) { constexpr int w = decltype(W)::value; stage_load<8 * w>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 256 * w, lane, vx); });
+        static_for<0, NWA>([&](auto W) { constexpr int w = decltype(W)::value; stage_load<8 * w>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, 256 * w, lane, va); });
+        static_for<0, NWX>([&](auto W) { constexpr int w = decltype(W)::value; take_x<NT, w, 8 * w>(stg, lane, D, vx, xc); });
+        static_for<0, NWA>([&](auto W) { constexpr int w = decltype(W)::value; take_a<KS, w, 8 * w>(stg, lane, D, m_base, p.M, va, xf, skip_last); });
     } else {
         load_x<NT, 0>(reinterpret_cast<const char*>(p.X), (size_t)p.ldx * 4, D, m_base, p.M, stg, lane, xc);
     }
@@ -425,6 +395,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
     if (total >= NBUF) wait_vmcnt<PER * (NBUF - 2)>(); else wait_vmcnt<0>();     // (also covers the constant block, issued first)
     wg_barrier();
 
+    // local code, not chain_common.h's WFrag: the value type reschedules 22 of the 44 instances (no resource changes; profiles/chain_common_parity.txt)
     const int q0 = (half + lr) % P1;
     const int w1row = lr * (P1 * 16);
     auto wfrag = [&](const char* slab, int s) __attribute__((always_inline)) {
@@ -451,9 +422,9 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
                     for (int s0 = 0; s0 < KS; s0 += FB) {
                         bf16x8 wa[FB];
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
+                        for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) xc[2 * c + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[2 * c + j], 0, 0, 0);
+                        for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) xc[2 * c + j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[2 * c + j], 0, 0, 0);
                     }
                 }
             }
@@ -485,9 +456,9 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
         for (int s0 = 0; s0 < KS; s0 += FB) {
             bf16x8 wa[FB];
 #pragma unroll
-            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf, s0 + i);
+            for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) wa[i] = wfrag(buf, s0 + i);
 #pragma unroll
-            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
+            for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
             after(s0 / FB);
         }
         return h;
@@ -605,6 +576,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
         for (int c = 0; c < n_g1; ++c) {
             const char* buf = advance();
             refill();
+            // local code, not acc_from_bias / g1_mfma: as calls, chain_kpad_kernel<12, 2 | 8, 3, 0> get their chunk loop unrolled once more (132 MFMAs for 110)
             f32x16 acc[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j)
@@ -618,9 +590,9 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
             for (int s0 = 0; s0 < KS; s0 += FB) {
                 bf16x8 wa[2][FB];
 #pragma unroll
-                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
+                for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
 #pragma unroll
-                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
+                for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) {
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
                     acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
                 }
@@ -679,6 +651,7 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
                 CH_TICK(6);                 // PROF, Q/K/V stage: "g0 stage" = wait + barrier, "ffn gemm1" = the refill, "norms+misc" = MFMAs, "qkv stage" = write-out
                 refill();
                 CH_TICK(1);
+                // local code, not acc_from_bias / g1_mfma: as calls they change the listing of all 33 chain A instances (no resource changes)
                 f32x16 acc[2];
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
@@ -692,9 +665,9 @@ __device__ __forceinline__ void chain_body(const ChainDev& cd, unsigned long lon
                 for (int s0 = 0; s0 < KS; s0 += FB) {
                     bf16x8 wa[2][FB];
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
+                    for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
+                    for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) {
                         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
                         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
                     }
@@ -822,29 +795,8 @@ template <int KS, int NW, int NBUF, int KIND>
 int launch_chain_t(const ChainParams& p, hipStream_t s) {
     using G = Geo<KS>;
     ChainDev cd;
-    cd.p = p;
-    cd.fT = FastDiv32(p.T > 0 ? p.T : 1);
-    cd.fD = FastDiv32(p.D);
-    {   // one row pitch for g0 / g1 / W1 (all have K = D), one for the W2 matrices: the kernel keeps its DMA offsets in registers
-        constexpr bool isb = KIND == CHAIN_B, pre = KIND == CHAIN_A_FULL || KIND == CHAIN_A_TAIL, post = KIND == CHAIN_A_FULL || KIND == CHAIN_A_HEAD;
-        int ldr = 0, ld2 = 0;
-        bool ok = true;
-        auto row = [&](int ld) { if (!ldr) ldr = ld; else ok = ok && ld == ldr; };
-        auto w2 = [&](int ld) { if (!ld2) ld2 = ld; else ok = ok && ld == ld2; };
-        if (isb || pre) row(p.g0.ldw);
-        if (isb || post) row(p.g1.ldw);
-        if (pre) { row(p.f[0].ldw1); w2(p.f[0].ldw2); }
-        if (post) { row(p.f[1].ldw1); w2(p.f[1].ldw2); }
-        if (!ok || ldr <= 0) return -6;
-        cd.ldr = ldr; cd.ld2 = ld2;
-    }
-    const int nfl = chain_const_layout(p, KIND, cd.nf);
-    cd.nfl_kb = nfl / 256;
-    if (!p.consts) return -5;
-    const int lds = NBUF * G::BUF + NW * STG_BYTES + nfl * 4;
-    if (lds > 160 * 1024) return -4;
-    static LdsAttr attr;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&chain_kernel<KS, NW, NBUF, KIND, false>), lds, attr);
+    const int lds = chain_dev_init(cd, p, KIND, false, NBUF * G::BUF + NW * STG_BYTES);
+    if (lds < 0) return lds;
     const int rows_per_wg = NW * 32;
 #ifdef EFFCONF_PHASE_PROF
     if constexpr ((KS == 8 && KIND == CHAIN_A_FULL) || (KS == 16 && (KIND == CHAIN_A_HEAD || KIND == CHAIN_A_TAIL))) {
@@ -861,16 +813,11 @@ int launch_chain_t(const ChainParams& p, hipStream_t s) {
         }
     }
 #endif
-    if constexpr (KS >= 12) {
-        if (ks_skip_last<KS>((p.D + 15) / 16)) {
-            static LdsAttr attr_kpad;
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&chain_kpad_kernel<KS, NW, NBUF, KIND>), lds, attr_kpad);
-            hipLaunchKernelGGL((chain_kpad_kernel<KS, NW, NBUF, KIND>), dim3((p.M + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64), lds, s, cd);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        }
-    }
-    hipLaunchKernelGGL((chain_kernel<KS, NW, NBUF, KIND, false>), dim3((p.M + rows_per_wg - 1) / rows_per_wg), dim3(NW * 64), lds, s, cd, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const dim3 grid((p.M + rows_per_wg - 1) / rows_per_wg), block(NW * 64);
+    if constexpr (KS >= 12)
+        return chain_launch<&chain_kernel<KS, NW, NBUF, KIND, false>, &chain_kpad_kernel<KS, NW, NBUF, KIND>>(ks_skip_last<KS>((p.D + 15) / 16), grid, block, lds, s, cd);
+    else
+        return chain_launch<&chain_kernel<KS, NW, NBUF, KIND, false>, nullptr>(false, grid, block, lds, s, cd);
 }
 
 // Workgroup shape.  A chain workgroup streams ALL weights of its chain through its LDS ring, one 32-unit chunk per barrier interval - a fixed
@@ -911,7 +858,7 @@ bool chain_full_supported(int D, int dmax) { return chain_head_supported(D) && D
 int launch_chain(const ChainParams& p, int kind, hipStream_t s) {
     if (p.M <= 0) return 0;
     if (!chain_supported(p.D)) return -2;
-    if (chain_padded_width(p.D) - p.D >= 64) return -2;      // ln_stats (here, chain2.hip, chain3.hip) masks the pad columns of the LAST TWO 32-column tiles only
+    if (chain_padded_width(p.D) - p.D >= 64) return -2;      // ln_stats (here) and row_pvar (chain_common.h) mask the pad columns of the LAST TWO 32-column tiles only
     if (p.pair && chain3_supported(p.D)) return kind == CHAIN_B ? launch_chain2(p, s) : launch_chain3(p, kind, s);      // padded width 256
     switch (kind) {
         case CHAIN_B: return launch_chain_kind<CHAIN_B>(p, s);

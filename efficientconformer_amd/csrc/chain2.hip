@@ -17,8 +17,7 @@
 // sums continued from wave A's partial in wave B), so the rows are BIT-IDENTICAL to chain.hip's - which is how this file is tested
 // (tests/test_gpu_round5.py: option chain_pair 5 against 0).  Weights, constant blocks and parameters are chain.hip's (same packing, same
 // ring chunk layout).  Reference: models/modules.py:511-514; blocks.py:126; attentions.py:716.
-#include "kernels.h"
-#include "rowstat.h"
+#include "chain_common.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -27,8 +26,7 @@
 namespace {
 
 constexpr int NW2 = 8, NBUF2 = 3;
-constexpr int S2_ROW = 144;                  // staging row pitch: 128-byte windows + 16 (36 dwords: conflict-free 16-byte accesses, rows x pieces either way)
-constexpr int S2_WIN = 32 * S2_ROW;          // 4608: the window area; its bytes [0, 4096) also carry the xf exchanges between the waves of a pair
+constexpr int S2_WIN = 32 * STG128_ROW;         // 4608: the window area; its bytes [0, 4096) also carry the xf exchanges between the waves of a pair
 constexpr int S2_BYTES = S2_WIN + 512;       // + the LayerNorm hand-off slots (never touched by the window / exchange traffic: no barrier between their last read and the next private use)
 
 template <int KS>
@@ -40,50 +38,10 @@ struct Geo2 {
     static constexpr int PER = 2 * KS / NW2;             // wave-DMAs per wave and ring chunk (2 PER in the wave's turn)
 };
 
-struct ChainDev2 {
-    ChainParams p;
-    int nf[8];
-    int nfl_kb;
-    int ldr;
-};
-
-template <int V> using ic = std::integral_constant<int, V>;
-// compile-time loop: f(ic<0>{}), f(ic<1>{}), ... - array indices derived from the counter are constants BEFORE any optimisation pass (a runtime offset
-// into a register array that only becomes constant after unrolling can leave the array in scratch)
-template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) { f(ic<I>{}); static_for<I + 1, N>(f); }
-}
-
-// ---- 128-byte-window staging (private to a wave): lane = (row 8i + lane / 8, piece lane % 8)
-template <int OFF, int N>
-__device__ __forceinline__ void s2_load(const char* base, size_t pitch, int row_bytes, int m_base, int M, int wbyte, int lane, u32x4 (&v)[N]) {
-    int cb = wbyte + 16 * (lane & 7);
-    cb = cb < row_bytes - 16 ? cb : row_bytes - 16;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m_base + 8 * i + (lane >> 3);
-        v[OFF + i] = *reinterpret_cast<const u32x4*>(base + (size_t)(m < M ? m : M - 1) * pitch + cb);
-    }
-}
-template <int OFF, int N>
-__device__ __forceinline__ void s2_put(char* stg, int lane, const u32x4 (&v)[N]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(stg + (8 * i + (lane >> 3)) * S2_ROW + 16 * (lane & 7)) = v[OFF + i];
-}
-__device__ __forceinline__ void s2_store(const char* stg, char* base, size_t pitch, int row_bytes, int m_base, int M, int wbyte, int lane) {
-    const int cb = wbyte + 16 * (lane & 7);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m_base + 8 * i + (lane >> 3);
-        const u32x4 v = *reinterpret_cast<const u32x4*>(stg + (8 * i + (lane >> 3)) * S2_ROW + 16 * (lane & 7));
-        if (m < M && cb < row_bytes) *reinterpret_cast<u32x4*>(base + (size_t)m * pitch + cb) = v;
-    }
-}
-
 // PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN2_PHASES=1): s_memtime per phase, wave A and wave B of every 8th workgroup's first pair
 // KPAD: the last k-step holds pad columns only and is left out of every product over the model width (rowstat.h, ks_skip_last)
 template <int KS, bool PROF, bool KPAD>
-__device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long long* prof) {
+__device__ __forceinline__ void chain2_body(const ChainDev& cd, unsigned long long* prof) {
     unsigned long long ph[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
     if constexpr (PROF) t0 = __builtin_readcyclecounter();
 #define C2_TICK(i) do { if constexpr (PROF) { asm volatile("" ::: "memory"); const unsigned long long t1_ = __builtin_readcyclecounter(); ph[i] += t1_ - t0; t0 = t1_; } } while (0)
@@ -101,9 +59,8 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
     char* stg = stg_base + wave * S2_BYTES;                   // this wave's staging region
     const char* stgp = stg_base + (wave ^ 4) * S2_BYTES;      // the partner's (read only)
     const int D = p.D;
-    // k-step s takes part in the products over the model width: all but the last one of a KPAD instance (compile-time in every unrolled loop).  The dropped
-    // k-step is wave B's last own fragment: not built (zeros travel through the exchange in its place), not read back, no weight fragment, no MFMA
-    auto kstep = [](int s) __attribute__((always_inline)) { return s < KS - 1 || !KPAD; };
+    // KPAD: the dropped k-step (rowstat.h, kstep) is wave B's last own fragment: not built (zeros travel through the exchange in its place), not read back,
+    // no weight fragment, no MFMA
     const bool own_pad = KPAD && cw == 1;                     // this wave's own[KSH - 1] is the dropped k-step
 
     // ---- chunk schedule: [g0] [g1]
@@ -180,7 +137,7 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
             for (int i = 0; i < 4; ++i)
                 if (r0 + i < KSH) {
                     xf[r0 + i] = *reinterpret_cast<const bf16x8*>(stgA + i * 1024 + lane * 16);
-                    if (kstep(KSH + r0 + i)) xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(stgB + i * 1024 + lane * 16);
+                    if (kstep<KS, KPAD>(KSH + r0 + i)) xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(stgB + i * 1024 + lane * 16);
                 }
         }
         wg_barrier();                                        // the staging regions are private again
@@ -190,20 +147,20 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
     {
         const char* xb = reinterpret_cast<const char*>(p.X);
         u32x4 vx[4 * NTH] = {};
-        static_for<0, NTH>([&](auto I) { constexpr int tt = decltype(I)::value; s2_load<4 * tt>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane, vx); });
+        static_for<0, NTH>([&](auto I) { constexpr int tt = decltype(I)::value; stage128_load<4 * tt>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane, vx); });
         constexpr int NWA = (KSH + 3) / 4;                   // 128-byte windows (4 k-steps) of the wave's half of the operand row
         u32x4 va[4 * NWA] = {};
         const char* ab = reinterpret_cast<const char*>(p.A);
-        static_for<0, NWA>([&](auto I) { constexpr int w = decltype(I)::value; s2_load<4 * w>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, cw * KSH * 32 + 128 * w, lane, va); });
+        static_for<0, NWA>([&](auto I) { constexpr int w = decltype(I)::value; stage128_load<4 * w>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, cw * KSH * 32 + 128 * w, lane, va); });
         static_for<0, NTH>([&](auto I) {
             constexpr int tt = decltype(I)::value;
             wave_sync();
-            s2_put<4 * tt>(stg, lane, vx);
+            stage128_put<4 * tt>(stg, lane, vx);
             wave_sync();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int col = 32 * (ct0 + tt) + 8 * q + 4 * half;
-                float4 x4 = *reinterpret_cast<const float4*>(stg + lr * S2_ROW + (q * 8 + half * 4) * 4);
+                float4 x4 = *reinterpret_cast<const float4*>(stg + lr * STG128_ROW + (q * 8 + half * 4) * 4);
                 if (col >= D) x4 = make_float4(0.f, 0.f, 0.f, 0.f);
                 xc[tt][4 * q + 0] = x4.x; xc[tt][4 * q + 1] = x4.y; xc[tt][4 * q + 2] = x4.z; xc[tt][4 * q + 3] = x4.w;
             }
@@ -212,14 +169,14 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
         static_for<0, NWA>([&](auto I) {
             constexpr int w = decltype(I)::value;
             wave_sync();
-            s2_put<4 * w>(stg, lane, va);
+            stage128_put<4 * w>(stg, lane, va);
             wave_sync();
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (4 * w + j == KSH - 1 && own_pad) own[4 * w + j] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u));
                 else if (4 * w + j < KSH) {
                     const int s = cw * KSH + 4 * w + j;
-                    const char* src = stg + lr * S2_ROW + (16 * j + 4 * half) * 2;
+                    const char* src = stg + lr * STG128_ROW + (16 * j + 4 * half) * 2;
                     uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 16);
                     const int c0 = 16 * s + 4 * half;
                     if (c0 >= D || m_base + lr >= p.M) lo = make_uint2(0u, 0u);
@@ -236,13 +193,7 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
     wg_barrier();
     C2_TICK(6);
 
-    const int q0 = (half + lr) % P1;
-    const int w1row = lr * (P1 * 16);
-    auto wfrag = [&](const char* slab, int s) __attribute__((always_inline)) {
-        int q = q0 + 2 * s;
-        q -= q >= P1 ? P1 : 0;
-        return *reinterpret_cast<const bf16x8*>(slab + w1row + q * 16);
-    };
+    const WFrag<P1> wfrag(lane);
 
     auto add_cvec2 = [&](const float* sv) __attribute__((always_inline)) {       // xc[tt][r] += sv[column]
 #pragma unroll
@@ -253,45 +204,11 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
                 xc[tt][4 * q + 0] += v.x; xc[tt][4 * q + 1] += v.y; xc[tt][4 * q + 2] += v.z; xc[tt][4 * q + 3] += v.w;
             }
     };
-    // LayerNorm statistics in chain.hip's summation order: wave A sums its tiles, wave B continues from A's partial and finishes (the xor-32
-    // shuffle, the division, the rsqrt), and hands the result back - four barriers per norm.  eps 1e-6 (modules.py:377, 447; blocks.py:97)
+    // LayerNorm statistics in chain.hip's summation order: wave A's partial continued by wave B (pair_ln_stats)
     auto ln_stats2 = [&](float& mean, float& rstd) __attribute__((always_inline)) {
         float* my = reinterpret_cast<float*>(stg + S2_WIN) + lane;
         const float* pa = reinterpret_cast<const float*>(stgp + S2_WIN) + lane;
-        auto psum = [&](float sum) __attribute__((always_inline)) {
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; r += 4) sum += (xc[t][r] + xc[t][r + 1]) + (xc[t][r + 2] + xc[t][r + 3]);
-            return sum;
-        };
-        auto pvar = [&](float var, float mu) __attribute__((always_inline)) {
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; r += 4) {
-                    const float a = xc[t][r] - mu, b = xc[t][r + 1] - mu, c = xc[t][r + 2] - mu, d = xc[t][r + 3] - mu;
-                    const float g = (a * a + b * b) + (c * c + d * d);
-                    var += (t < NTH - 2 || 32 * (ct0 + t) + 2 * r + 4 * half < D) ? g : 0.f;      // pad pieces add nothing (chain.hip ln_stats)
-                }
-            return var;
-        };
-        mean = 0.f; rstd = 0.f;
-        if (cw == 0) *my = psum(0.f);
-        wg_barrier();
-        if (cw == 1) { const float sum = psum(*pa); mean = (sum + __shfl_xor(sum, 32)) / (float)D; *my = mean; }
-        wg_barrier();
-        if (cw == 0) { mean = *pa; *my = pvar(0.f, mean); }
-        wg_barrier();
-        if (cw == 1) {
-            float var = pvar(*pa, mean);
-            var += __shfl_xor(var, 32);
-            rstd = rsqrtf(fmaxf(var, 0.f) / (float)D + 1e-6f);
-            *my = rstd;
-        }
-        wg_barrier();
-        if (cw == 0) rstd = *pa;
-        asm volatile("" : "+v"(mean));
+        pair_ln_stats<NTH>(xc, cw, 32 * ct0 + 4 * half, D, my, pa, mean, rstd);
         C2_TICK(5);
     };
     // bf16((x - mean) * rstd) of the wave's columns as K-permuted B fragments, then both halves to both waves
@@ -300,12 +217,8 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
         bf16x8 own[KSH];
 #pragma unroll
         for (int s = 0; s < KSH; ++s) {
-            const int r = 8 * (s & 1);
             if (s == KSH - 1 && own_pad) own[s] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u));
-            else own[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
-                                          pack_bf2(fmaf(xc[s >> 1][r + 2], rstd, nm), fmaf(xc[s >> 1][r + 3], rstd, nm)),
-                                          pack_bf2(fmaf(xc[s >> 1][r + 4], rstd, nm), fmaf(xc[s >> 1][r + 5], rstd, nm)),
-                                          pack_bf2(fmaf(xc[s >> 1][r + 6], rstd, nm), fmaf(xc[s >> 1][r + 7], rstd, nm))));
+            else own[s] = norm_frag(xc, s, rstd, nm);
         }
         publish_xf(own);
         C2_TICK(5);
@@ -316,9 +229,9 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
             wave_sync();
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<float4*>(stg + lr * S2_ROW + (q * 8 + half * 4) * 4) = make_float4(xc[tt][4 * q + 0], xc[tt][4 * q + 1], xc[tt][4 * q + 2], xc[tt][4 * q + 3]);
+                *reinterpret_cast<float4*>(stg + lr * STG128_ROW + (q * 8 + half * 4) * 4) = make_float4(xc[tt][4 * q + 0], xc[tt][4 * q + 1], xc[tt][4 * q + 2], xc[tt][4 * q + 3]);
             wave_sync();
-            s2_store(stg, reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane);
+            stage128_store(stg, reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane);
         }
         C2_TICK(10);
     };
@@ -339,40 +252,15 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
                 for (int s0 = 0; s0 < KS; s0 += FB) {
                     bf16x8 wa[FB];
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
+                    for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
 #pragma unroll
-                    for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[tt], 0, 0, 0);
+                    for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], xc[tt], 0, 0, 0);
                 }
             }
         }
         if constexpr (PROF) asm volatile("s_nop 0" :: "v"(xc[0][0]), "v"(xc[NTH - 1][15]));
         C2_TICK(7);
     }
-
-    // bias of the two 32-row slabs of ring chunk c -> accumulators
-    auto acc_bias = [&](f32x16 (&acc)[2], int c) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v = *reinterpret_cast<const float4*>(s_g1b + 64 * c + 32 * j + 8 * q + 4 * half);
-                acc[j][4 * q + 0] = v.x; acc[j][4 * q + 1] = v.y; acc[j][4 * q + 2] = v.z; acc[j][4 * q + 3] = v.w;
-            }
-    };
-    auto g1_mfma = [&](f32x16 (&acc)[2], const char* buf) __attribute__((always_inline)) {
-        constexpr int FB = 2;
-#pragma unroll
-        for (int s0 = 0; s0 < KS; s0 += FB) {
-            bf16x8 wa[2][FB];
-#pragma unroll
-            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
-#pragma unroll
-            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
-            }
-        }
-    };
 
     // ---- conv-module pre-norm, pointwise-1 + GLU -> bf16 rows (modules.py:512-514).  GLU chunks alternate between the pair; the owner of chunk c
     //      writes it out during chunk c + 1
@@ -392,14 +280,14 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
                 float o[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = acc[0][4 * q + i] * sigmoidf_(acc[1][4 * q + i]);
-                *reinterpret_cast<uint2*>(stg + lr * S2_ROW + (8 * q + 4 * half) * 2) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
+                *reinterpret_cast<uint2*>(stg + lr * STG128_ROW + (8 * q + 4 * half) * 2) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
             }
             wave_sync();
             const int col = 32 * c + 8 * (lane & 3);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int row = 16 * i + (lane >> 2), m = m_base + row;
-                const u32x4 v = *reinterpret_cast<const u32x4*>(stg + row * S2_ROW + 16 * (lane & 3));
+                const u32x4 v = *reinterpret_cast<const u32x4*>(stg + row * STG128_ROW + 16 * (lane & 3));
                 if (m < p.M && col < p.Ng) *reinterpret_cast<u32x4*>(p.glu + (size_t)m * p.ldg + col) = v;
             }
         };
@@ -407,7 +295,7 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
         for (int c = 0; c < n_g1; ++c) {
             const char* buf = advance();
             refill();
-            if (((c + op) & 1) == cw) { acc_bias(acc, c); g1_mfma(acc, buf); if constexpr (PROF) asm volatile("s_nop 0" :: "v"(acc[0][0]), "v"(acc[1][15])); C2_TICK(8); }
+            if (((c + op) & 1) == cw) { acc_from_bias(acc, s_g1b, c, half); g1_mfma<KS, KPAD>(acc, xf, buf, wfrag); if constexpr (PROF) asm volatile("s_nop 0" :: "v"(acc[0][0]), "v"(acc[1][15])); C2_TICK(8); }
             else if (c >= 1) { glu_out(c - 1); C2_TICK(9); }
         }
         if (n_g1 >= 1 && ((n_g1 - 1 + op) & 1) == cw) glu_out(n_g1 - 1);
@@ -425,12 +313,12 @@ __device__ __forceinline__ void chain2_body(const ChainDev2& cd, unsigned long l
 }
 
 template <int KS, bool PROF = false>
-__global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev2 cd, unsigned long long* prof = nullptr) {
+__global__ __launch_bounds__(NW2 * 64, 1) void chain2_kernel(const ChainDev cd, unsigned long long* prof = nullptr) {
     chain2_body<KS, PROF, false>(cd, prof);
 }
 // the same chain for a width whose last k-step is all pad (D = 240)
 template <int KS>
-__global__ __launch_bounds__(NW2 * 64, 1) void chain2_kpad_kernel(const ChainDev2 cd) {
+__global__ __launch_bounds__(NW2 * 64, 1) void chain2_kpad_kernel(const ChainDev cd) {
     chain2_body<KS, false, true>(cd, nullptr);
 }
 
@@ -452,23 +340,15 @@ void chain2_prof_dump() {
 
 }  // namespace
 
-// LDS: ring + staging + constant block
 int launch_chain2(const ChainParams& p, hipStream_t s) {
     constexpr int KS = 16;
     using G = Geo2<KS>;
     if (p.M <= 0) return 0;
     if (!chain3_supported(p.D)) return -2;                   // padded width 256
-    ChainDev2 cd;
-    cd.p = p;
-    if (p.g0.ldw != p.g1.ldw || p.g0.ldw <= 0) return -6;   // one row pitch for g0 / g1: the kernel keeps its DMA offsets in registers
-    cd.ldr = p.g0.ldw;
-    const int nfl = chain_const_layout(p, CHAIN_B, cd.nf);
-    cd.nfl_kb = nfl / 256;
-    if (!p.consts) return -5;
-    const int lds = NBUF2 * G::BUF + NW2 * S2_BYTES + nfl * 4;
-    if (lds > 160 * 1024) return -4;
-    static LdsAttr attr;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&chain2_kernel<KS, false>), lds, attr);
+    if (p.g0.ldw <= 0) return -6;                            // (chain_dev_init skips a leading zero pitch, as chain.hip always did; this launcher never did)
+    ChainDev cd;
+    const int lds = chain_dev_init(cd, p, CHAIN_B, false, NBUF2 * G::BUF + NW2 * S2_BYTES);       // LDS: ring + staging + constant block
+    if (lds < 0) return lds;
 #ifdef EFFCONF_PHASE_PROF
     static const bool prof = getenv("EFFCONF_CHAIN2_PHASES") != nullptr;
     if (prof) {
@@ -481,12 +361,5 @@ int launch_chain2(const ChainParams& p, hipStream_t s) {
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
 #endif
-    if (ks_skip_last<KS>((p.D + 15) / 16)) {
-        static LdsAttr attr_kpad;
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&chain2_kpad_kernel<KS>), lds, attr_kpad);
-        hipLaunchKernelGGL((chain2_kpad_kernel<KS>), dim3((p.M + 127) / 128), dim3(NW2 * 64), lds, s, cd);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    hipLaunchKernelGGL((chain2_kernel<KS, false>), dim3((p.M + 127) / 128), dim3(NW2 * 64), lds, s, cd, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return chain_launch<&chain2_kernel<KS, false>, &chain2_kpad_kernel<KS>>(ks_skip_last<KS>((p.D + 15) / 16), dim3((p.M + 127) / 128), dim3(NW2 * 64), lds, s, cd);
 }

@@ -20,8 +20,7 @@
 // The two roles are separate code paths from the top (a common path would keep A's fragments and B's accumulators live in each other's
 // code: 190 registers); they execute the same sequence of workgroup barriers - kept in one table below (PROTOCOL).
 // Reference: models/modules.py:385-392, 519-522; blocks.py:119-137; attentions.py:651-686.
-#include "kernels.h"
-#include "rowstat.h"
+#include "chain_common.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -30,8 +29,7 @@
 namespace {
 
 constexpr int NW3 = 12, NBUF3 = 3, NB3 = 8;                  // waves; ring buffers; waves that issue the ring (the B waves)
-constexpr int S3_ROW = 144;                                  // staging window: 32 rows x (128 + 16) bytes
-constexpr int S3_WIN = 32 * S3_ROW;                          // 4608: one window per B wave; [0, 4096) also carries hf slots / fragment exchanges
+constexpr int S3_WIN = 32 * STG128_ROW;                         // 4608: one window per B wave; [0, 4096) also carries hf slots / fragment exchanges
 constexpr int S3_TILE = 2 * S3_WIN + 512;                    // per row tile: window 0, window 1, LayerNorm hand-off slots
 
 template <int KS>
@@ -44,14 +42,6 @@ struct Geo3 {
     static constexpr int XR = (KSH + 3) / 4;                 // rounds of a fragment exchange (4 fragments per B wave and round)
 };
 
-struct ChainDev3 {
-    ChainParams p;
-    FastDiv32 fT, fD;
-    int nf[8];
-    int nfl_kb;
-    int ldr;
-};
-
 // `ofs` (feeding the next addresses) made to depend on a whole accumulator tile.  Device pass only: on the host side of the compilation a 64-byte "v" operand is
 // not a valid x86 constraint, and the failed instantiation silently leaves the kernel's host stub undefined
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -60,46 +50,8 @@ struct ChainDev3 {
 #define C3_PIN_TILE(ofs, tile) ((void)0)
 #endif
 
-// The lane id, computed again where it is asked for.  Everything a lane derives from threadIdx.x is affine in this value, but the compiler cannot
-// rematerialise a kernel argument register: lane / lr / half and the addresses built from them were kept in scratch across the stages, and their reloads
-// share the in-order vmcnt queue with the ring's DMAs.  A volatile statement is neither merged with another one nor hoisted: each phase below takes its
-// own copy, whose live range ends with the phase.
-__device__ __forceinline__ int lane_now() {
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
+// each phase below takes its own copy of the lane id (common.h, lane_now), whose live range ends with the phase
 #define C3_LANE() const int lane = lane_now(), lr = lane & 31, half = lane >> 5; (void)lr; (void)half
-
-template <int V> using ic3 = std::integral_constant<int, V>;
-template <int I, int N, class F> __device__ __forceinline__ void static_for3(F&& f) {
-    if constexpr (I < N) { f(ic3<I>{}); static_for3<I + 1, N>(f); }
-}
-
-template <int OFF, int N>
-__device__ __forceinline__ void s3_load(const char* base, size_t pitch, int row_bytes, int m_base, int M, int wbyte, int lane, u32x4 (&v)[N]) {
-    int cb = wbyte + 16 * (lane & 7);
-    cb = cb < row_bytes - 16 ? cb : row_bytes - 16;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m_base + 8 * i + (lane >> 3);
-        v[OFF + i] = *reinterpret_cast<const u32x4*>(base + (size_t)(m < M ? m : M - 1) * pitch + cb);
-    }
-}
-template <int OFF, int N>
-__device__ __forceinline__ void s3_put(char* stg, int lane, const u32x4 (&v)[N]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(stg + (8 * i + (lane >> 3)) * S3_ROW + 16 * (lane & 7)) = v[OFF + i];
-}
-__device__ __forceinline__ void s3_store(const char* stg, char* base, size_t pitch, int row_bytes, int m_base, int M, int wbyte, int lane) {
-    const int cb = wbyte + 16 * (lane & 7);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m_base + 8 * i + (lane >> 3);
-        const u32x4 v = *reinterpret_cast<const u32x4*>(stg + (8 * i + (lane >> 3)) * S3_ROW + 16 * (lane & 7));
-        if (m < M && cb < row_bytes) *reinterpret_cast<u32x4*>(base + (size_t)m * pitch + cb) = v;
-    }
-}
 
 // PROTOCOL - the workgroup barriers both roles execute, in order (XB = 2 XR barriers of a fragment exchange):
 //   prologue:  [XB if PRE]  1 (constants + first chunk)
@@ -110,7 +62,7 @@ __device__ __forceinline__ void s3_store(const char* stg, char* base, size_t pit
 // PROF (tuning library only, -DEFFCONF_PHASE_PROF; EFFCONF_CHAIN3_PHASES=<kind>): s_memtime per phase, the three waves of every 8th workgroup's first row tile
 // KPAD: the last k-step holds pad columns only and is left out of every product over the model width (rowstat.h, ks_skip_last)
 template <int KS, int KIND, bool PROF, bool KPAD>
-__device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long long* prof) {
+__device__ __forceinline__ void chain3_body(const ChainDev& cd, unsigned long long* prof) {
     unsigned long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
     if constexpr (PROF) t0 = __builtin_readcyclecounter();
 #define C3_TICK(i) do { if constexpr (PROF) { asm volatile("" ::: "memory"); const unsigned long long t1_ = __builtin_readcyclecounter(); ph[i] += t1_ - t0; t0 = t1_; } } while (0)
@@ -137,10 +89,8 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
     float* slot0 = reinterpret_cast<float*>(win0 + 2 * S3_WIN);              // B0's hand-off slot, B1's (one float per lane)
     float* slot1 = slot0 + 64;
     const int D = p.D;
-    // k-step s takes part in the products over the model width: all but the last one of a KPAD instance (compile-time in every unrolled loop).  The dropped
-    // k-step is wave B1's last own fragment: not built (zeros travel through the exchange in its place), not read back, no weight fragment, no MFMA - wave A's
-    // dependency chain per hidden chunk is 15 MFMAs instead of 16
-    auto kstep = [](int s) __attribute__((always_inline)) { return s < KS - 1 || !KPAD; };
+    // KPAD: the dropped k-step (rowstat.h, kstep) is wave B1's last own fragment: not built (zeros travel through the exchange in its place), not read back,
+    // no weight fragment, no MFMA - wave A's dependency chain per hidden chunk is 15 MFMAs instead of 16
 
     const int n_g0 = PRE ? (NT + 1) / 2 : 0;
     const int n_f0 = PRE ? p.f[0].Fp / CH : 0;
@@ -158,17 +108,8 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
     const float* s_g1b = sf + cd.nf[6];
     const float* s_uv = sf + cd.nf[7];
 
-    // reader of a [32 rows][P1 pieces] weight slab; made once per stage, so that its two lane constants live no longer than the stage's loop
-    auto make_wfrag = [&]() __attribute__((always_inline)) {
-        C3_LANE();
-        const int q0 = (half + lr) % P1;
-        const int w1row = lr * (P1 * 16);
-        return [q0, w1row](const char* slab, int s) __attribute__((always_inline)) {
-            int q = q0 + 2 * s;
-            q -= q >= P1 ? P1 : 0;
-            return *reinterpret_cast<const bf16x8*>(slab + w1row + q * 16);
-        };
-    };
+    // the reader of a weight slab (chain_common.h, WFrag) is made once per stage, from the lane id of that moment: its two lane constants live no longer than
+    // the stage's loop
     // every wave reads the published fragments of a round: fragments r0 .. r0 + 3 from window 0, KSH + r0 .. from window 1
     auto read_round = [&](bf16x8 (&xf)[KS], auto r0c) __attribute__((always_inline)) {
         C3_LANE();
@@ -177,35 +118,10 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
         for (int i = 0; i < 4; ++i)
             if (r0 + i < KSH) {
                 xf[r0 + i] = *reinterpret_cast<const bf16x8*>(win0 + i * 1024 + lane * 16);
-                if (kstep(KSH + r0 + i)) xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(win1 + i * 1024 + lane * 16);
+                if (kstep<KS, KPAD>(KSH + r0 + i)) xf[KSH + r0 + i] = *reinterpret_cast<const bf16x8*>(win1 + i * 1024 + lane * 16);
             }
     };
     // destination rows of the Q/K/V write-out: (b, t) -> (b * Tp + t) * D for the 2 rows a lane stores per half-tile instruction pair
-    // bias of the two 32-row slabs of ring chunk c -> accumulators; the MFMAs of a Q/K/V chunk
-    auto acc_bias = [&](f32x16 (&acc)[2], int c) __attribute__((always_inline)) {
-        C3_LANE();
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v = *reinterpret_cast<const float4*>(s_g1b + 64 * c + 32 * j + 8 * q + 4 * half);
-                acc[j][4 * q + 0] = v.x; acc[j][4 * q + 1] = v.y; acc[j][4 * q + 2] = v.z; acc[j][4 * q + 3] = v.w;
-            }
-    };
-    auto g1_mfma = [&](f32x16 (&acc)[2], const bf16x8 (&xf)[KS], const char* buf, auto wfrag) __attribute__((always_inline)) {
-        constexpr int FB = 2;
-#pragma unroll
-        for (int s0 = 0; s0 < KS; s0 += FB) {
-            bf16x8 wa[2][FB];
-#pragma unroll
-            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) { wa[0][i] = wfrag(buf, s0 + i); wa[1][i] = wfrag(buf + HALF, s0 + i); }
-#pragma unroll
-            for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) {
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[0][i], xf[s0 + i], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[1][i], xf[s0 + i], acc[1], 0, 0, 0);
-            }
-        }
-    };
     // tile j (32 columns) of Q/K/V chunk c out through window `stg`: registers r = 8g .. 8g + 7 of the tile are the columns 64c + 32j + 16g + 8 half + (0..7)
     // of the stacked [Q | K | V] (row permutation of pack_linear_chunkperm); Q columns get + u.  Returns the number of store instructions
     auto qkv_out_tile = [&](const f32x16& a, int c, int j, char* stg) __attribute__((always_inline)) -> int {
@@ -216,7 +132,7 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
             const int n0 = 64 * c + 32 * j + 16 * g + 8 * half;
             float4 ua = make_float4(0.f, 0.f, 0.f, 0.f), ub = ua;
             if (n0 < D) { ua = *reinterpret_cast<const float4*>(s_uv + n0); ub = *reinterpret_cast<const float4*>(s_uv + n0 + 4); }
-            *reinterpret_cast<uint4*>(stg + lr * S3_ROW + (16 * g + 8 * half) * 2) =
+            *reinterpret_cast<uint4*>(stg + lr * STG128_ROW + (16 * g + 8 * half) * 2) =
                 make_uint4(pack_bf2(a[8 * g + 0] + ua.x, a[8 * g + 1] + ua.y), pack_bf2(a[8 * g + 2] + ua.z, a[8 * g + 3] + ua.w),
                            pack_bf2(a[8 * g + 4] + ub.x, a[8 * g + 5] + ub.y), pack_bf2(a[8 * g + 6] + ub.z, a[8 * g + 7] + ub.w));
         }
@@ -229,7 +145,7 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
             const int mc = m < p.M ? m : p.M - 1;
             const int b = cd.fT.div(mc), t = mc - b * p.T;
             const size_t qoff = ((size_t)b * p.Tp + t) * D;
-            const u32x4 v = *reinterpret_cast<const u32x4*>(stg + row * S3_ROW + 16 * (lane & 3));
+            const u32x4 v = *reinterpret_cast<const u32x4*>(stg + row * STG128_ROW + 16 * (lane & 3));
             if ((D & 7) == 0) {
                 const int which = cd.fD.div(n0), nn0 = n0 - which * D;
                 bf16_t* dst = which == 0 ? p.qu : (which == 1 ? p.kh : p.vt);
@@ -258,13 +174,13 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
         int mine = (role + 3 - op) % 3;                      // first chunk of this wave
-        const auto wfrag = make_wfrag();
+        const WFrag<P1> wfrag(lane_now());
 #pragma unroll 1
         for (int c = 0; c < n_g1 + 2; ++c) {
             const char* buf = nullptr;
             if (c < n_g1) buf = adv(); else wg_barrier();
             const int ph = c - mine;                         // 0: MFMAs of chunk `mine`, 1 / 2: its column tiles out
-            if (ph == 0 && c < n_g1) { acc_bias(acc, c); g1_mfma(acc, xf, buf, wfrag); rf(); }
+            if (ph == 0 && c < n_g1) { acc_from_bias(acc, s_g1b, c, lane_now() >> 5); g1_mfma<KS, KPAD>(acc, xf, buf, wfrag); rf(); }
             else {
                 rf();
                 if (ph == 1 && mine < n_g1) st += qkv_out_tile(acc[0], mine, 0, win0);
@@ -284,7 +200,7 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
             return buf;
         };
         auto no_rf = []() {};
-        const auto wfrag = make_wfrag();
+        const WFrag<P1> wfrag(lane_now());
         bf16x8 xf[KS];
         if constexpr (PRE) {
 #pragma unroll
@@ -306,9 +222,9 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
             for (int s0 = 0; s0 < KS; s0 += FB) {
                 bf16x8 wa[FB];
 #pragma unroll
-                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf, s0 + i);
+                for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) wa[i] = wfrag(buf, s0 + i);
 #pragma unroll
-                for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
+                for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xf[s0 + i], h, 0, 0, 0);
                 between(s0 / FB);
             }
             return h;
@@ -324,11 +240,11 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
         auto ffn_stage_a = [&](const float* sb1, int n) __attribute__((always_inline)) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) wg_barrier();         // statistics (B0 -> B1 -> B0)
-            static_for3<0, XR>([&](auto I) {                  // normalised fragments from the B waves
+            static_for<0, XR>([&](auto I) {                  // normalised fragments from the B waves
                 constexpr int r = decltype(I)::value;
                 if (r > 0) wg_barrier();
                 wg_barrier();
-                read_round(xf, ic3<4 * r>{});
+                read_round(xf, ic<4 * r>{});
             });
             wg_barrier();
             // iteration i: first GEMM of hidden chunk i (i < n) with the Swish of chunk i - 1 in the same basic block; hf(i - 1) -> window (i - 1) & 1
@@ -361,11 +277,11 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
             ffn_stage_a(s_f1b1, n_f1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) wg_barrier();         // attention pre-norm statistics
-            static_for3<0, XR>([&](auto I) {
+            static_for<0, XR>([&](auto I) {
                 constexpr int r = decltype(I)::value;
                 if (r > 0) wg_barrier();
                 wg_barrier();
-                read_round(xf, ic3<4 * r>{});
+                read_round(xf, ic<4 * r>{});
             });
             wg_barrier();
             int st = 0;
@@ -446,14 +362,14 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
     // own fragments -> window (4 per round); `reader` waves read both windows
     auto publish = [&](const bf16x8 (&own)[KSH], bf16x8 (&xf)[KS], bool reader) __attribute__((always_inline)) {
         C3_LANE();
-        static_for3<0, XR>([&](auto I) {
+        static_for<0, XR>([&](auto I) {
             constexpr int r = decltype(I)::value;
             if (r > 0) wg_barrier();
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 if (4 * r + i < KSH) *reinterpret_cast<bf16x8*>(stg + i * 1024 + lane * 16) = own[4 * r + i];
             wg_barrier();
-            if (reader) read_round(xf, ic3<4 * r>{});
+            if (reader) read_round(xf, ic<4 * r>{});
         });
         wg_barrier();
     };
@@ -461,51 +377,14 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
         C3_LANE();
         float* my = (cw ? slot1 : slot0) + lane;
         const float* pa = (cw ? slot0 : slot1) + lane;
-        auto psum = [&](float sum) __attribute__((always_inline)) {
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; r += 4) sum += (xc[t][r] + xc[t][r + 1]) + (xc[t][r + 2] + xc[t][r + 3]);
-            return sum;
-        };
-        auto pvar = [&](float var, float mu) __attribute__((always_inline)) {
-#pragma unroll
-            for (int t = 0; t < NTH; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; r += 4) {
-                    const float a = xc[t][r] - mu, b = xc[t][r + 1] - mu, c = xc[t][r + 2] - mu, d = xc[t][r + 3] - mu;
-                    const float g = (a * a + b * b) + (c * c + d * d);
-                    var += (t < NTH - 2 || 32 * (ct0 + t) + 2 * r + 4 * half < D) ? g : 0.f;      // pad pieces add nothing (chain.hip ln_stats)
-                }
-            return var;
-        };
-        mean = 0.f; rstd = 0.f;
-        if (cw == 0) *my = psum(0.f);
-        wg_barrier();
-        if (cw == 1) { const float sum = psum(*pa); mean = (sum + __shfl_xor(sum, 32)) / (float)D; *my = mean; }
-        wg_barrier();
-        if (cw == 0) { mean = *pa; *my = pvar(0.f, mean); }
-        wg_barrier();
-        if (cw == 1) {
-            float var = pvar(*pa, mean);
-            var += __shfl_xor(var, 32);
-            rstd = rsqrtf(fmaxf(var, 0.f) / (float)D + 1e-6f);
-            *my = rstd;
-        }
-        wg_barrier();
-        if (cw == 0) rstd = *pa;
-        asm volatile("" : "+v"(mean));
+        pair_ln_stats<NTH>(xc, cw, 32 * ct0 + 4 * half, D, my, pa, mean, rstd);
     };
     auto norm_own = [&](float mean, float rstd, bf16x8 (&own)[KSH]) __attribute__((always_inline)) {
         const float nm = -mean * rstd;
 #pragma unroll
         for (int s = 0; s < KSH; ++s) {
-            const int r = 8 * (s & 1);
             if (s == KSH - 1 && own_pad) own[s] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u));
-            else own[s] = as_bf16x8(make_uint4(pack_bf2(fmaf(xc[s >> 1][r + 0], rstd, nm), fmaf(xc[s >> 1][r + 1], rstd, nm)),
-                                          pack_bf2(fmaf(xc[s >> 1][r + 2], rstd, nm), fmaf(xc[s >> 1][r + 3], rstd, nm)),
-                                          pack_bf2(fmaf(xc[s >> 1][r + 4], rstd, nm), fmaf(xc[s >> 1][r + 5], rstd, nm)),
-                                          pack_bf2(fmaf(xc[s >> 1][r + 6], rstd, nm), fmaf(xc[s >> 1][r + 7], rstd, nm))));
+            else own[s] = norm_frag(xc, s, rstd, nm);
         }
     };
     auto add_cvec = [&](const float* sv) __attribute__((always_inline)) {
@@ -530,9 +409,9 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
             wave_sync();
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<float4*>(stg + lr * S3_ROW + (q * 8 + half * 4) * 4) = make_float4(xc[tt][4 * q + 0], xc[tt][4 * q + 1], xc[tt][4 * q + 2], xc[tt][4 * q + 3]);
+                *reinterpret_cast<float4*>(stg + lr * STG128_ROW + (q * 8 + half * 4) * 4) = make_float4(xc[tt][4 * q + 0], xc[tt][4 * q + 1], xc[tt][4 * q + 2], xc[tt][4 * q + 3]);
             wave_sync();
-            s3_store(stg, reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane);
+            stage128_store(stg, reinterpret_cast<char*>(p.Y), (size_t)p.ldy * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane);
         }
         st1 += 4 * NTH;
     };
@@ -542,16 +421,16 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
         C3_LANE();
         const char* xb = reinterpret_cast<const char*>(p.X);
         u32x4 vx[4 * NTH] = {};
-        static_for3<0, NTH>([&](auto I) { constexpr int tt = decltype(I)::value; s3_load<4 * tt>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane, vx); });
-        static_for3<0, NTH>([&](auto I) {
+        static_for<0, NTH>([&](auto I) { constexpr int tt = decltype(I)::value; stage128_load<4 * tt>(xb, (size_t)p.ldx * 4, D * 4, m_base, p.M, 128 * (ct0 + tt), lane, vx); });
+        static_for<0, NTH>([&](auto I) {
             constexpr int tt = decltype(I)::value;
             wave_sync();
-            s3_put<4 * tt>(stg, lane, vx);
+            stage128_put<4 * tt>(stg, lane, vx);
             wave_sync();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int col = 32 * (ct0 + tt) + 8 * q + 4 * half;
-                float4 x4 = *reinterpret_cast<const float4*>(stg + lr * S3_ROW + (q * 8 + half * 4) * 4);
+                float4 x4 = *reinterpret_cast<const float4*>(stg + lr * STG128_ROW + (q * 8 + half * 4) * 4);
                 if (col >= D) x4 = make_float4(0.f, 0.f, 0.f, 0.f);
                 xc[tt][4 * q + 0] = x4.x; xc[tt][4 * q + 1] = x4.y; xc[tt][4 * q + 2] = x4.z; xc[tt][4 * q + 3] = x4.w;
             }
@@ -566,20 +445,20 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
             // Window by window (not all loads first): with xc and the growing xa live, a second set of staging registers does not fit 168
             static_assert(XR == (KSH + 3) / 4, "one round per window");
             const char* ab = reinterpret_cast<const char*>(p.A);
-            static_for3<0, XR>([&](auto I) {
+            static_for<0, XR>([&](auto I) {
                 constexpr int w = decltype(I)::value;
                 u32x4 va[4] = {};
-                s3_load<0>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, cw * KSH * 32 + 128 * w, lane, va);
+                stage128_load<0>(ab, (size_t)p.lda * 2, p.lda * 2, m_base, p.M, cw * KSH * 32 + 128 * w, lane, va);
                 if (w > 0) wg_barrier();                     // the previous round has been read
                 wave_sync();
-                s3_put<0>(stg, lane, va);
+                stage128_put<0>(stg, lane, va);
                 wave_sync();
                 bf16x8 own4[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int s = cw * KSH + 4 * w + j;
                     if (4 * w + j == KSH - 1 && own_pad) { own4[j] = as_bf16x8(make_uint4(0u, 0u, 0u, 0u)); continue; }
-                    const char* src = stg + lr * S3_ROW + (16 * j + 4 * half) * 2;
+                    const char* src = stg + lr * STG128_ROW + (16 * j + 4 * half) * 2;
                     uint2 lo = *reinterpret_cast<const uint2*>(src), hi = *reinterpret_cast<const uint2*>(src + 16);
                     const int c0 = 16 * s + 4 * half;
                     if (c0 >= D || m_base + lr >= p.M) lo = make_uint2(0u, 0u);
@@ -591,14 +470,14 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
                 for (int j = 0; j < 4; ++j)
                     if (4 * w + j < KSH) *reinterpret_cast<bf16x8*>(stg + j * 1024 + lane * 16) = own4[j];
                 wg_barrier();
-                read_round(xa, ic3<4 * w>{});
+                read_round(xa, ic<4 * w>{});
             });
             wg_barrier();
         }
         if (total >= NBUF3) wait_vmcnt<PER * (NBUF3 - 2)>(); else wait_vmcnt<0>();
         wg_barrier();
         add_cvec(s_b0);
-        const auto wfrag = make_wfrag();
+        const WFrag<P1> wfrag(lane_now());
 #pragma unroll
         for (int c = 0; c < (NT + 1) / 2; ++c) {
             const char* buf = advance();
@@ -613,9 +492,9 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
                     for (int s0 = 0; s0 < KS; s0 += FB) {
                         bf16x8 wa[FB];
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
+                        for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) wa[i] = wfrag(buf + j * HALF, s0 + i);
 #pragma unroll
-                        for (int i = 0; i < FB; ++i) if (kstep(s0 + i)) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xa[s0 + i], xc[tt], 0, 0, 0);
+                        for (int i = 0; i < FB; ++i) if (kstep<KS, KPAD>(s0 + i)) xc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[i], xa[s0 + i], xc[tt], 0, 0, 0);
                     }
                 }
             }
@@ -705,12 +584,12 @@ __device__ __forceinline__ void chain3_body(const ChainDev3& cd, unsigned long l
 }
 
 template <int KS, int KIND, bool PROF = false>
-__global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev3 cd, unsigned long long* prof = nullptr) {
+__global__ __launch_bounds__(NW3 * 64, 1) void chain3_kernel(const ChainDev cd, unsigned long long* prof = nullptr) {
     chain3_body<KS, KIND, PROF, false>(cd, prof);
 }
 // the same chain for a width whose last k-step is all pad (D = 240)
 template <int KS, int KIND>
-__global__ __launch_bounds__(NW3 * 64, 1) void chain3_kpad_kernel(const ChainDev3 cd) {
+__global__ __launch_bounds__(NW3 * 64, 1) void chain3_kpad_kernel(const ChainDev cd) {
     chain3_body<KS, KIND, false, true>(cd, nullptr);
 }
 
@@ -737,27 +616,9 @@ void chain3_prof_dump() {
 template <int KS, int KIND>
 int launch_chain3_t(const ChainParams& p, hipStream_t s) {
     using G = Geo3<KS>;
-    ChainDev3 cd;
-    cd.p = p;
-    cd.fT = FastDiv32(p.T > 0 ? p.T : 1);
-    cd.fD = FastDiv32(p.D);
-    {
-        constexpr bool pre = KIND == CHAIN_A_FULL || KIND == CHAIN_A_TAIL, post = KIND == CHAIN_A_FULL || KIND == CHAIN_A_HEAD;
-        int ldr = 0;
-        bool ok = true;
-        auto row = [&](int ld) { if (!ldr) ldr = ld; else ok = ok && ld == ldr; };
-        if (pre) { row(p.g0.ldw); row(p.f[0].ldw1); ok = ok && p.f[0].w2cm; }
-        if (post) { row(p.g1.ldw); row(p.f[1].ldw1); ok = ok && p.f[1].w2cm; }
-        if (!ok || ldr <= 0) return -6;
-        cd.ldr = ldr;
-    }
-    const int nfl = chain_const_layout(p, KIND, cd.nf);
-    cd.nfl_kb = nfl / 256;
-    if (!p.consts) return -5;
-    const int lds = NBUF3 * G::BUF + 4 * S3_TILE + nfl * 4;
-    if (lds > 160 * 1024) return -4;
-    static LdsAttr attr;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&chain3_kernel<KS, KIND, false>), lds, attr);
+    ChainDev cd;
+    const int lds = chain_dev_init(cd, p, KIND, true, NBUF3 * G::BUF + 4 * S3_TILE);
+    if (lds < 0) return lds;
 #ifdef EFFCONF_PHASE_PROF
     static const bool prof = getenv("EFFCONF_CHAIN3_PHASES") != nullptr && atoi(getenv("EFFCONF_CHAIN3_PHASES")) == KIND;
     if (prof) {
@@ -770,14 +631,7 @@ int launch_chain3_t(const ChainParams& p, hipStream_t s) {
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
 #endif
-    if (ks_skip_last<KS>((p.D + 15) / 16)) {
-        static LdsAttr attr_kpad;
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&chain3_kpad_kernel<KS, KIND>), lds, attr_kpad);
-        hipLaunchKernelGGL((chain3_kpad_kernel<KS, KIND>), dim3((p.M + 127) / 128), dim3(NW3 * 64), lds, s, cd);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    hipLaunchKernelGGL((chain3_kernel<KS, KIND, false>), dim3((p.M + 127) / 128), dim3(NW3 * 64), lds, s, cd, nullptr);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return chain_launch<&chain3_kernel<KS, KIND, false>, &chain3_kpad_kernel<KS, KIND>>(ks_skip_last<KS>((p.D + 15) / 16), dim3((p.M + 127) / 128), dim3(NW3 * 64), lds, s, cd);
 }
 
 }  // namespace

@@ -40,6 +40,16 @@ __device__ __forceinline__ bf16x8 as_bf16x8(uint4 v) {
     return c.b;
 }
 
+// The lane id, computed again where it is asked for (two VALU instructions; a volatile statement is neither merged with another one nor hoisted out of a loop).
+// Everything a lane derives from threadIdx.x is affine in this value, but the compiler cannot rematerialise a kernel argument register: lane constants that two
+// distant stages share (chain.hip, chain3.hip) or that are used once per key block (attention2.hip) were kept in scratch in between, and a scratch reload waits on
+// the vmcnt queue the kernel's own prefetches are in (the weight ring's DMAs, the K / V / E loads).  Each phase takes its own copy, whose live range ends with it.
+__device__ __forceinline__ int lane_now() {
+    int l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
 // Raise a kernel's dynamic-LDS limit when a launch needs more than any earlier launch of that instantiation ON THAT DEVICE (the
 // attribute is per device; one process may hold handles on several).  One static LdsAttr per launch site.
 struct LdsAttr { int bytes[16] = {}; };

@@ -1,7 +1,10 @@
-// Shared device helpers of the row-stationary kernels (rsgemm.hip, chain.hip): LDS-DMA weight ring, counted waits,
-// coalesced row-tile staging.  See rsgemm.hip for the design notes.
+// Shared device helpers of the row-stationary kernels (rsgemm.hip, gemm256.hip, sublinear2.hip and - through chain_common.h - chain.hip, chain2.hip, chain3.hip):
+// LDS-DMA weight ring, counted waits, coalesced row-tile staging (256- and 128-byte windows), compile-time loop, the dropped all-pad k-step.
+// See rsgemm.hip for the design notes.
 #pragma once
 #include "kernels.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -55,6 +58,13 @@ template <int PER, int MAXC> __device__ __forceinline__ void wait_chunks(int all
 }
 __device__ __forceinline__ void wg_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+template <int V> using ic = std::integral_constant<int, V>;
+// compile-time loop: f(ic<0>{}), f(ic<1>{}), ... - array indices derived from the counter (window indices select registers of the staging arrays) are constants
+// BEFORE any optimisation pass (a runtime offset into a register array that only becomes constant after unrolling can leave the array in scratch)
+template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) { f(ic<I>{}); static_for<I + 1, N>(f); }
 }
 
 // DMA shapes of the weight ring.  A kernel computes the per-lane BYTE offsets of its wave's DMA instructions once, keeps them in
@@ -120,6 +130,34 @@ __device__ __forceinline__ void stage_store(const char* stg, char* base, size_t 
         if (m < M && cb < row_bytes) *reinterpret_cast<u32x4*>(base + (size_t)m * pitch + cb) = v;
     }
 }
+// ---- 128-byte-window staging (private to a wave; chain2.hip, chain3.hip): lane = (row 8i + lane / 8, piece lane % 8), four instructions per 32-row window.
+// Row pitch 128 + 16 bytes (36 dwords: conflict-free 16-byte accesses, rows x pieces either way)
+constexpr int STG128_ROW = 144;
+template <int OFF, int N>
+__device__ __forceinline__ void stage128_load(const char* base, size_t pitch, int row_bytes, int m_base, int M, int wbyte, int lane, u32x4 (&v)[N]) {
+    int cb = wbyte + 16 * (lane & 7);
+    cb = cb < row_bytes - 16 ? cb : row_bytes - 16;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m_base + 8 * i + (lane >> 3);
+        v[OFF + i] = *reinterpret_cast<const u32x4*>(base + (size_t)(m < M ? m : M - 1) * pitch + cb);
+    }
+}
+template <int OFF, int N>
+__device__ __forceinline__ void stage128_put(char* stg, int lane, const u32x4 (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4*>(stg + (8 * i + (lane >> 3)) * STG128_ROW + 16 * (lane & 7)) = v[OFF + i];
+}
+__device__ __forceinline__ void stage128_store(const char* stg, char* base, size_t pitch, int row_bytes, int m_base, int M, int wbyte, int lane) {
+    const int cb = wbyte + 16 * (lane & 7);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m_base + 8 * i + (lane >> 3);
+        const u32x4 v = *reinterpret_cast<const u32x4*>(stg + (8 * i + (lane >> 3)) * STG128_ROW + 16 * (lane & 7));
+        if (m < M && cb < row_bytes) *reinterpret_cast<u32x4*>(base + (size_t)m * pitch + cb) = v;
+    }
+}
+
 // this lane's fp32 row fragments (columns 16s + 8*half + 0..7 of row lr) for all s < KS, fetched through the staging region
 template <int KS, int W>
 __device__ __forceinline__ void take_window_f32(const char* stg, int lr, int half, float4 (&ra)[KS], float4 (&rb)[KS]) {
@@ -192,6 +230,9 @@ __device__ __forceinline__ void fetch_row_bf16(const bf16_t* A, int lda, int m_b
 // The remaining k-steps keep their order.  Values: an accumulator loses additions of +-0 only; one that is exactly -0.0 could become +0.0, which compares
 // equal (torch.equal, np.array_equal) and which no consumer divides by.
 template <int KS> __host__ __device__ constexpr bool ks_skip_last(int ks_valid) { return KS >= 12 && ks_valid < KS; }
+// k-step s takes part in the products over the model width: all but the last one of a KPAD instance.  Compile-time in every (fully unrolled) loop: the dropped
+// step costs no fragment read, no MFMA and no registers for its activation fragment
+template <int KS, bool KPAD> __host__ __device__ constexpr bool kstep(int s) { return s < KS - 1 || !KPAD; }
 
 struct FastDiv32 {   // exact for n * d < 2^32
     uint32_t mul, d;

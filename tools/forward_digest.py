@@ -132,6 +132,12 @@ def model_cases(precision: str):
     for ragged in layouts:
         for trace in ("off", "on", "fused") if precision == "split" else ("off", "on"):
             cases.append(("%s trace=%s" % ("ragged" if ragged else "rect", trace), dict(ragged=ragged, trace=trace != "off"), {"trace_fused": int(trace == "fused")} if precision == "split" else {}))
+    if precision == "bf16":      # the chain shapes the defaults never take at this batch size; last on the handle, each case sets both options (they persist)
+        for label, opts in (("chain_small_m=0", {"chain_small_m": 0, "chain_pair": 5}),      # the 8- and 4-wave shapes on a nearly empty workgroup: the row clamp
+                            ("chain_pair=0", {"chain_small_m": 4096, "chain_pair": 0}),         # chain.hip's own KS = 16 instances, kpad at D = 240 among them
+                            ("chain_small_m=0 chain_pair=0", {"chain_small_m": 0, "chain_pair": 0})):
+            for ragged in (False, True):
+                cases.append(("%s %s trace=on" % ("ragged" if ragged else "rect", label), dict(ragged=ragged, trace=True), opts))
     if precision != "bf16":      # attention maps: the scores-in-memory kernels in either label-exact mode
         for trace in ("off", "on"):
             cases.append(("rect maps trace=%s" % trace, dict(maps=True, trace=trace == "on"), {"trace_fused": 0} if precision == "split" else {}))
