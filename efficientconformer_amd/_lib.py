@@ -52,6 +52,7 @@ SIGNATURES = {
     "effconf_host_pack_rows": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), _I32, C.c_void_p, C.c_int64, _I32, _I32]),
     "effconf_ctc_greedy": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _P, _F32P, _P, _SZ, _P]),
     "effconf_ctc_greedy_bf16": (C.c_int, [_P, _P, _I64P, _I32, _I32, _P, _P, _F32P, _P, _SZ, _P]),
+    "effconf_ctc_greedy_margin": (C.c_int, [_P, _P, _I32, _I64P, _I32, _I32, _P, _P, _F32P, _F32P, _F32P, _P, _P, _SZ, _P]),
     "effconf_ctc_beam_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
     "effconf_ctc_beam": (C.c_int, [_F32P, _I64P, _I32, _I32, _I32, _I32, C.c_float, _P, _P, _F32P, _P, _SZ, _P]),
     "effconf_ctc_align_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),

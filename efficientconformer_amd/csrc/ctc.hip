@@ -7,6 +7,8 @@
 //                           0.2 % of the FLOPs, so it stays exact fp32 to keep greedy labels stable.
 //  * ctc_collapse_kernel — drop blanks (id 0), collapse repeats not separated by a blank, stop at len[b]
 //                           (the reference's Python loop with .item() per token, model_ctc.py:105-133).
+//  * MARGIN instances      — the same kernels with every frame's top-2 logit margin and its minimum per utterance (effconf_ctc_greedy_margin:
+//                           which utterances margin-gated label-exact decoding runs again in the split mode).
 #include "kernels.h"
 
 namespace {
@@ -98,14 +100,19 @@ __global__ __launch_bounds__(1024) void lengths_ragged_kernel(const int64_t* __r
 // One workgroup = CTC_ROWS frames x the whole vocabulary (thread = vocabulary column).  Every workgroup reads all of fc^T from L2, so
 // the rows per workgroup set the L2 traffic (8 rows: 3200 workgroups x 245 KB = 0.8 GB per launch, the whole 150 us of the first
 // version); the frame tile sits in LDS and is read as float4 broadcasts along k (one LDS read per 4 FMAs).
-template <int CTC_ROWS>
+// MARGIN = true (every head kernel of this file): the frame's top-2 margin as well - the scan keeps (best, first index, second), two triples merge
+// as second = max(min(b1, b2), s1, s2), margin = best - second in fp32 (= topk(logits, 2) differenced; a duplicated maximum: second = best, 0).
+// A template parameter: the MARGIN = false instances are the kernels of effconf_ctc_greedy / _bf16, instruction for instruction.
+template <int CTC_ROWS, bool MARGIN = false>
 __global__ __launch_bounds__(256) void ctc_argmax_kernel(const float* __restrict__ x, int M, int D,
                                                          const float* __restrict__ Wt, const float* __restrict__ bias,
-                                                         int V, int* __restrict__ preds, float* __restrict__ logits) {
+                                                         int V, int* __restrict__ preds, float* __restrict__ logits,
+                                                         float* __restrict__ margin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* sx = reinterpret_cast<float*>(smem);                         // [CTC_ROWS][D]   (D % 4 == 0)
     float* sbest = sx + CTC_ROWS * D;                                   // [CTC_ROWS][4]
     int* sidx = reinterpret_cast<int*>(sbest + CTC_ROWS * 4);           // [CTC_ROWS][4]
+    float* ssec = reinterpret_cast<float*>(sidx + CTC_ROWS * 4);        // [CTC_ROWS][4]   (MARGIN only)
     const int m0 = blockIdx.x * CTC_ROWS;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int i = tid * 4; i < CTC_ROWS * D; i += 256 * 4) {
@@ -116,8 +123,13 @@ __global__ __launch_bounds__(256) void ctc_argmax_kernel(const float* __restrict
     __syncthreads();
     float best[CTC_ROWS];
     int bidx[CTC_ROWS];
+    [[maybe_unused]] float second[MARGIN ? CTC_ROWS : 1];
 #pragma unroll
     for (int r = 0; r < CTC_ROWS; ++r) { best[r] = -INFINITY; bidx[r] = 0x7fffffff; }
+    if constexpr (MARGIN) {
+#pragma unroll
+        for (int r = 0; r < CTC_ROWS; ++r) second[r] = -INFINITY;
+    }
     for (int v0 = 0; v0 < V; v0 += 256) {
         const int v = v0 + tid, vc = v < V ? v : V - 1;
         float acc[CTC_ROWS];
@@ -136,6 +148,12 @@ __global__ __launch_bounds__(256) void ctc_argmax_kernel(const float* __restrict
         for (int r = 0; r < CTC_ROWS; ++r) {
             const float val = acc[r] + bz;
             if (logits && v < V && m0 + r < M) logits[(size_t)(m0 + r) * V + v] = val;
+            if constexpr (MARGIN) {
+                if (v < V) {
+                    if (val > best[r]) { second[r] = best[r]; best[r] = val; bidx[r] = v; }
+                    else if (val > second[r]) second[r] = val;
+                }
+            } else
             if (v < V && val > best[r]) { best[r] = val; bidx[r] = v; }   // strictly greater: first max wins
         }
     }
@@ -143,21 +161,26 @@ __global__ __launch_bounds__(256) void ctc_argmax_kernel(const float* __restrict
 #pragma unroll
     for (int r = 0; r < CTC_ROWS; ++r) {
         float bv = best[r]; int bi = bidx[r];
+        [[maybe_unused]] float sv = MARGIN ? second[MARGIN ? r : 0] : 0.f;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
+            if constexpr (MARGIN) sv = fmaxf(fminf(bv, ov), fmaxf(sv, __shfl_xor(sv, o)));
             if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
         }
-        if (lane == 0) { sbest[r * 4 + wave] = bv; sidx[r * 4 + wave] = bi; }
+        if (lane == 0) { sbest[r * 4 + wave] = bv; sidx[r * 4 + wave] = bi; if constexpr (MARGIN) ssec[r * 4 + wave] = sv; }
     }
     __syncthreads();
     if (tid < CTC_ROWS && m0 + tid < M) {
         float bv = sbest[tid * 4]; int bi = sidx[tid * 4];
+        [[maybe_unused]] float sv = MARGIN ? ssec[tid * 4] : 0.f;
         for (int w = 1; w < 4; ++w) {
             const float ov = sbest[tid * 4 + w]; const int oi = sidx[tid * 4 + w];
+            if constexpr (MARGIN) sv = fmaxf(fminf(bv, ov), fmaxf(sv, ssec[tid * 4 + w]));
             if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
         }
         preds[m0 + tid] = bi;
+        if constexpr (MARGIN) margin[m0 + tid] = bv - sv;
     }
 }
 
@@ -166,10 +189,10 @@ __global__ __launch_bounds__(256) void ctc_argmax_kernel(const float* __restrict
 // LDS (row pitch D + 1 floats: conflict-free column reads), fc^T streams from L2 as MFMA B fragments (two rows of 32 consecutive
 // floats per load).  The logits tile goes back through LDS for the per-row argmax (first maximum wins) and the optional row-major
 // logits output.  6.3 GFLOP per 256 x 201 frames: 222 us on the VALU kernel above, fp32-MFMA bound here.
-template <int ROWS>
+template <int ROWS, bool MARGIN = false>
 __global__ __launch_bounds__(256) void ctc_argmax_mfma_kernel(const float* __restrict__ x, int M, int D, const float* __restrict__ Wt,
                                                               const float* __restrict__ bias, int V, int* __restrict__ preds,
-                                                              float* __restrict__ logits, int tile_off) {
+                                                              float* __restrict__ logits, int tile_off, float* __restrict__ margin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int RT = ROWS / 32, TPR = 256 / ROWS, CPT = 256 / TPR, LDT = 257;
     float* sx = reinterpret_cast<float*>(smem);                         // [ROWS][D + 1]
@@ -188,6 +211,7 @@ __global__ __launch_bounds__(256) void ctc_argmax_mfma_kernel(const float* __res
     const int prow = tid / TPR, part = tid - prow * TPR;                // argmax: TPR adjacent threads per row, CPT columns each
     float best = -INFINITY;
     int bidx = 0x7fffffff;
+    [[maybe_unused]] float second = -INFINITY;
     const int kh = lane >> 5, lc = lane & 31;
     for (int v0 = 0; v0 < V; v0 += 256) {
         f32x16 acc[RT][2];
@@ -232,15 +256,23 @@ __global__ __launch_bounds__(256) void ctc_argmax_mfma_kernel(const float* __res
         for (int j = 0; j < CPT; ++j) {
             const int cc = part * CPT + j;
             const float val = st[prow * LDT + cc];
+            if constexpr (MARGIN) {
+                if (v0 + cc < V) {
+                    if (val > best) { second = best; best = val; bidx = v0 + cc; }
+                    else if (val > second) second = val;
+                }
+            } else
             if (v0 + cc < V && val > best) { best = val; bidx = v0 + cc; }   // ascending columns, strictly greater: first maximum wins
         }
     }
 #pragma unroll
     for (int o = 1; o < TPR; o <<= 1) {
         const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bidx, o);
+        if constexpr (MARGIN) second = fmaxf(fminf(best, ov), fmaxf(second, __shfl_xor(second, o)));
         if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
     }
     if (part == 0 && m0 + prow < M) preds[m0 + prow] = bidx;
+    if constexpr (MARGIN) { if (part == 0 && m0 + prow < M) margin[m0 + prow] = best - second; }
 }
 
 // fc + argmax with SPLIT-bf16 operands on the bf16 matrix pipe (the default of the bf16 path): x = x_hi + x_lo, W = W_hi + W_lo (two bf16 each:
@@ -253,10 +285,10 @@ __global__ __launch_bounds__(256) void ctc_argmax_mfma_kernel(const float* __res
 // XBF = true (round 4): the frame rows arrive as bf16 (the gathered encoder outputs of the multi-rank path, bf16 wire): x_hi is the input itself,
 // x_lo = 0, so the x_lo W_hi term and the lo image of the frame tile vanish (2 MFMAs per 16 k, no conversion pass over the gathered chunk, half
 // the input bytes) - and the logits equal, bit for bit, those of the fp32-input kernel fed with the same values widened to fp32.
-template <int ROWS, bool XBF = false>
+template <int ROWS, bool XBF = false, bool MARGIN = false>
 __global__ __launch_bounds__(256) void ctc_argmax_bf16x3_kernel(const float* __restrict__ x, int M, int D, int Kp, const bf16_t* __restrict__ Whi,
                                                                 const bf16_t* __restrict__ Wlo, const float* __restrict__ bias, int V, int Vp,
-                                                                int* __restrict__ preds, float* __restrict__ logits) {
+                                                                int* __restrict__ preds, float* __restrict__ logits, float* __restrict__ margin) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int RT = ROWS / 32, TPR = 256 / ROWS, CPT = 256 / TPR, LDT = 257;
     const int pitch = Kp * 2 + 16;                                       // bytes per frame row of one half
@@ -284,6 +316,7 @@ __global__ __launch_bounds__(256) void ctc_argmax_bf16x3_kernel(const float* __r
     const int prow = tid / TPR, part = tid - prow * TPR;
     float best = -INFINITY;
     int bidx = 0x7fffffff;
+    [[maybe_unused]] float second = -INFINITY;
     const int kh = lane >> 5, lc = lane & 31;
     const int nks = Kp / 16;
     for (int v0 = 0; v0 < V; v0 += 256) {
@@ -339,29 +372,51 @@ __global__ __launch_bounds__(256) void ctc_argmax_bf16x3_kernel(const float* __r
         for (int j = 0; j < CPT; ++j) {
             const int cc = part * CPT + j;
             const float val = st[prow * LDT + cc];
+            if constexpr (MARGIN) {
+                if (v0 + cc < V) {
+                    if (val > best) { second = best; best = val; bidx = v0 + cc; }
+                    else if (val > second) second = val;
+                }
+            } else
             if (v0 + cc < V && val > best) { best = val; bidx = v0 + cc; }
         }
     }
 #pragma unroll
     for (int o = 1; o < TPR; o <<= 1) {
         const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(bidx, o);
+        if constexpr (MARGIN) second = fmaxf(fminf(best, ov), fmaxf(second, __shfl_xor(second, o)));
         if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
     }
     if (part == 0 && m0 + prow < M) preds[m0 + prow] = bidx;
+    if constexpr (MARGIN) { if (part == 0 && m0 + prow < M) margin[m0 + prow] = best - second; }
 }
 
 // one wave per utterance: 64 frames per step, keep = (c != 0 && c != previous frame's c), output position = running count +
 // prefix popcount of the keep ballot
+// MARGIN = true: the utterance's smallest frame margin over its valid frames and the first frame that holds it as well (+inf, -1 for no frames;
+// a NaN margin counts as smaller than every number, so it reaches the caller)
+template <bool MARGIN = false>
 __global__ __launch_bounds__(64) void ctc_collapse_kernel(const int* __restrict__ preds, const int64_t* __restrict__ lens, int B, int T,
-                                                          int* __restrict__ labels, int* __restrict__ label_len) {
+                                                          int* __restrict__ labels, int* __restrict__ label_len,
+                                                          const float* __restrict__ margin, float* __restrict__ min_margin,
+                                                          int* __restrict__ min_frame) {
     const int b = blockIdx.x, lane = threadIdx.x;
     long long len = lens[b];
     if (len > T) len = T;
     if (len < 0) len = 0;
     int n = 0, carry = 0;                                      // carry = prediction of the frame before this step (0 at the start)
+    [[maybe_unused]] float mv = INFINITY;
+    [[maybe_unused]] int mt = 0x7fffffff;
+    [[maybe_unused]] auto below = [](float a, int at, float c, int ct) {          // (a, at) before (c, ct): smaller margin (NaN first), then earlier frame
+        const bool an = a != a, cn = c != c;
+        return an != cn ? an : ((!an && a < c) || ((an || a == c) && at < ct));
+    };
     for (int t0 = 0; t0 < (int)len; t0 += 64) {
         const int t = t0 + lane;
         const int c = t < (int)len ? preds[(size_t)b * T + t] : 0;
+        if constexpr (MARGIN) {
+            if (t < (int)len) { const float g = margin[(size_t)b * T + t]; if (below(g, t, mv, mt)) { mv = g; mt = t; } }
+        }
         int prev = __shfl_up(c, 1);
         if (lane == 0) prev = carry;
         const bool keep = t < (int)len && c != 0 && c != prev;
@@ -372,6 +427,14 @@ __global__ __launch_bounds__(64) void ctc_collapse_kernel(const int* __restrict_
     }
     if (lane == 0) label_len[b] = n;
     for (int t = n + lane; t < T; t += 64) labels[(size_t)b * T + t] = 0;
+    if constexpr (MARGIN) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(mv, o); const int ot = __shfl_xor(mt, o);
+            if (below(ov, ot, mv, mt)) { mv = ov; mt = ot; }
+        }
+        if (lane == 0) { min_margin[b] = mv; min_frame[b] = mt == 0x7fffffff ? -1 : mt; }
+    }
 }
 
 }  // namespace
@@ -394,72 +457,79 @@ int launch_lengths(const int64_t* x_len, int B, int from_audio, int hop, int sub
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-template <int ROWS>
-int launch_ctc_mfma(const float* x, int M, int D, const float* Wt, const float* bias, int V, int* preds, float* logits, hipStream_t s) {
+template <int ROWS, bool MARGIN>
+int launch_ctc_mfma(const float* x, int M, int D, const float* Wt, const float* bias, int V, int* preds, float* logits, float* margin, hipStream_t s) {
     const size_t frame = (size_t)ROWS * (D + 1) * 4, tile = (size_t)ROWS * 257 * 4;
     const bool alias = V <= 256;                                       // one pass: the logits tile may reuse the frame tile
     const size_t lds = alias ? (frame > tile ? frame : tile) : frame + tile;
     if (lds > 160 * 1024) return -2;
     static LdsAttr attr;
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&ctc_argmax_mfma_kernel<ROWS>), (int)lds, attr);
-    hipLaunchKernelGGL((ctc_argmax_mfma_kernel<ROWS>), dim3((M + ROWS - 1) / ROWS), dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits,
-                       alias ? 0 : (int)(frame / 4));
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&ctc_argmax_mfma_kernel<ROWS, MARGIN>), (int)lds, attr);
+    hipLaunchKernelGGL((ctc_argmax_mfma_kernel<ROWS, MARGIN>), dim3((M + ROWS - 1) / ROWS), dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits,
+                       alias ? 0 : (int)(frame / 4), margin);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// one launch site (one LdsAttr) per instance
+template <int ROWS, bool XBF, bool MARGIN>
+void launch_ctc_bf16x3(const float* x, int M, int D, int Kp, const bf16_t* Whi, const bf16_t* Wlo, const float* bias, int V, int Vp, int* preds,
+                       float* logits, float* margin, size_t lds, hipStream_t s) {
+    static LdsAttr attr;
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&ctc_argmax_bf16x3_kernel<ROWS, XBF, MARGIN>), (int)lds, attr);
+    hipLaunchKernelGGL((ctc_argmax_bf16x3_kernel<ROWS, XBF, MARGIN>), dim3((M + ROWS - 1) / ROWS), dim3(256), lds, s, x, M, D, Kp, Whi, Wlo, bias, V, Vp,
+                       preds, logits, margin);
+}
+
+template <bool XBF, bool MARGIN>
+int launch_ctc_split_as(const float* x, int M, int D, const bf16_t* Whi, const bf16_t* Wlo, const float* bias, int V, int* preds, float* logits,
+                        float* margin, hipStream_t s) {
+    const int Kp = (D + 15) / 16 * 16, Vp = (V + 255) / 256 * 256;     // = finalize's packing (pack.hip): a pass covers 256 columns
+    // bf16 rows keep the layout (the lo image stays unused)
+    auto lds_for = [&](int rows) { return (size_t)2 * rows * (Kp * 2 + 16) + (size_t)rows * 257 * 4; };
+    if (lds_for(64) <= 160 * 1024) launch_ctc_bf16x3<64, XBF, MARGIN>(x, M, D, Kp, Whi, Wlo, bias, V, Vp, preds, logits, margin, lds_for(64), s);
+    else if (lds_for(32) <= 160 * 1024) launch_ctc_bf16x3<32, XBF, MARGIN>(x, M, D, Kp, Whi, Wlo, bias, V, Vp, preds, logits, margin, lds_for(32), s);   // wide last stages (D = 720: Large)
+    else return -2;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_ctc_split(const float* x, int M, int D, const bf16_t* Whi, const bf16_t* Wlo, const float* bias, int V, int* preds, float* logits,
-                     hipStream_t s, int x_is_bf16) {
+                     hipStream_t s, int x_is_bf16, float* margin) {
     if (M <= 0) return 0;
     if (D % 4 || !Whi || !Wlo) return -2;
-    if (x_is_bf16) {
-        const int Kp = (D + 15) / 16 * 16, Vp = (V + 255) / 256 * 256;
-        auto lds_b = [&](int rows) { return (size_t)2 * rows * (Kp * 2 + 16) + (size_t)rows * 257 * 4; };      // same layout (the lo image stays unused)
-        static LdsAttr b64, b32;
-        if (lds_b(64) <= 160 * 1024) {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&ctc_argmax_bf16x3_kernel<64, true>), (int)lds_b(64), b64);
-            hipLaunchKernelGGL((ctc_argmax_bf16x3_kernel<64, true>), dim3((M + 63) / 64), dim3(256), lds_b(64), s, x, M, D, Kp, Whi, Wlo, bias, V, Vp, preds, logits);
-        } else if (lds_b(32) <= 160 * 1024) {
-            ensure_dynamic_lds(reinterpret_cast<const void*>(&ctc_argmax_bf16x3_kernel<32, true>), (int)lds_b(32), b32);
-            hipLaunchKernelGGL((ctc_argmax_bf16x3_kernel<32, true>), dim3((M + 31) / 32), dim3(256), lds_b(32), s, x, M, D, Kp, Whi, Wlo, bias, V, Vp, preds, logits);
-        } else {
-            return -2;
-        }
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    const int Kp = (D + 15) / 16 * 16, Vp = (V + 255) / 256 * 256;     // = finalize's packing (encoder.hip): a pass covers 256 columns
-    auto lds_for = [&](int rows) { return (size_t)2 * rows * (Kp * 2 + 16) + (size_t)rows * 257 * 4; };
-    static LdsAttr attr64, attr32;
-    if (lds_for(64) <= 160 * 1024) {
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&ctc_argmax_bf16x3_kernel<64>), (int)lds_for(64), attr64);
-        hipLaunchKernelGGL((ctc_argmax_bf16x3_kernel<64>), dim3((M + 63) / 64), dim3(256), lds_for(64), s, x, M, D, Kp, Whi, Wlo, bias, V, Vp, preds, logits);
-    } else if (lds_for(32) <= 160 * 1024) {          // wide last stages (D = 720: Large)
-        ensure_dynamic_lds(reinterpret_cast<const void*>(&ctc_argmax_bf16x3_kernel<32>), (int)lds_for(32), attr32);
-        hipLaunchKernelGGL((ctc_argmax_bf16x3_kernel<32>), dim3((M + 31) / 32), dim3(256), lds_for(32), s, x, M, D, Kp, Whi, Wlo, bias, V, Vp, preds, logits);
-    } else {
-        return -2;
-    }
+    if (margin) return x_is_bf16 ? launch_ctc_split_as<true, true>(x, M, D, Whi, Wlo, bias, V, preds, logits, margin, s)
+                                 : launch_ctc_split_as<false, true>(x, M, D, Whi, Wlo, bias, V, preds, logits, margin, s);
+    return x_is_bf16 ? launch_ctc_split_as<true, false>(x, M, D, Whi, Wlo, bias, V, preds, logits, nullptr, s)
+                     : launch_ctc_split_as<false, false>(x, M, D, Whi, Wlo, bias, V, preds, logits, nullptr, s);
+}
+
+template <bool MARGIN>
+int launch_ctc_argmax_as(const float* x, int M, int D, const float* Wt, const float* bias, int V, int* preds, float* logits_or_null, float* margin,
+                         hipStream_t s, int use_mfma) {
+    if (use_mfma && D <= 256) return launch_ctc_mfma<64, MARGIN>(x, M, D, Wt, bias, V, preds, logits_or_null, margin, s);
+    if (use_mfma && D <= 1024 && V <= 256) return launch_ctc_mfma<32, MARGIN>(x, M, D, Wt, bias, V, preds, logits_or_null, margin, s);
+    // rows per workgroup: as many as keep the frame tile within the default 64 KB of dynamic LDS
+    const int rows = D <= 384 ? 32 : (D <= 768 ? 16 : 8);
+    const size_t lds = (size_t)rows * D * sizeof(float) + rows * 4 * (sizeof(float) + sizeof(int) + (MARGIN ? sizeof(float) : 0));
+    if (lds > 64 * 1024) return -2;
+    const dim3 grid((M + rows - 1) / rows);
+    if (rows == 32) hipLaunchKernelGGL((ctc_argmax_kernel<32, MARGIN>), grid, dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits_or_null, margin);
+    else if (rows == 16) hipLaunchKernelGGL((ctc_argmax_kernel<16, MARGIN>), grid, dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits_or_null, margin);
+    else hipLaunchKernelGGL((ctc_argmax_kernel<8, MARGIN>), grid, dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits_or_null, margin);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 int launch_ctc_argmax(const float* x, int M, int D, const float* Wt, const float* bias, int V,
-                      int* preds, float* logits_or_null, hipStream_t s, int use_mfma) {
+                      int* preds, float* logits_or_null, hipStream_t s, int use_mfma, float* margin) {
     if (M <= 0) return 0;
     if (D % 4) return -2;
-    if (use_mfma && D <= 256) return launch_ctc_mfma<64>(x, M, D, Wt, bias, V, preds, logits_or_null, s);
-    if (use_mfma && D <= 1024 && V <= 256) return launch_ctc_mfma<32>(x, M, D, Wt, bias, V, preds, logits_or_null, s);
-    // rows per workgroup: as many as keep the frame tile within the default 64 KB of dynamic LDS
-    const int rows = D <= 384 ? 32 : (D <= 768 ? 16 : 8);
-    const size_t lds = (size_t)rows * D * sizeof(float) + rows * 4 * (sizeof(float) + sizeof(int));
-    if (lds > 64 * 1024) return -2;
-    const dim3 grid((M + rows - 1) / rows);
-    if (rows == 32) hipLaunchKernelGGL(ctc_argmax_kernel<32>, grid, dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits_or_null);
-    else if (rows == 16) hipLaunchKernelGGL(ctc_argmax_kernel<16>, grid, dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits_or_null);
-    else hipLaunchKernelGGL(ctc_argmax_kernel<8>, grid, dim3(256), lds, s, x, M, D, Wt, bias, V, preds, logits_or_null);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return margin ? launch_ctc_argmax_as<true>(x, M, D, Wt, bias, V, preds, logits_or_null, margin, s, use_mfma)
+                  : launch_ctc_argmax_as<false>(x, M, D, Wt, bias, V, preds, logits_or_null, nullptr, s, use_mfma);
 }
 
-int launch_ctc_collapse(const int* preds, const int64_t* lens, int B, int T, int* labels, int* label_len, hipStream_t s) {
+int launch_ctc_collapse(const int* preds, const int64_t* lens, int B, int T, int* labels, int* label_len, hipStream_t s,
+                        const float* margin, float* min_margin, int* min_frame) {
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(ctc_collapse_kernel, dim3(B), dim3(64), 0, s, preds, lens, B, T, labels, label_len);
+    if (margin) hipLaunchKernelGGL(ctc_collapse_kernel<true>, dim3(B), dim3(64), 0, s, preds, lens, B, T, labels, label_len, margin, min_margin, min_frame);
+    else hipLaunchKernelGGL(ctc_collapse_kernel<false>, dim3(B), dim3(64), 0, s, preds, lens, B, T, labels, label_len, nullptr, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

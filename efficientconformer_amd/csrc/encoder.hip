@@ -248,6 +248,34 @@ int effconf_ctc_greedy_bf16(EcEncoder* e, const uint16_t* enc_out_bf16, const in
     return 0;
 }
 
+int effconf_ctc_greedy_margin(EcEncoder* e, const void* enc_out, int32_t enc_is_bf16, const int64_t* out_len, int32_t batch, int32_t t_out,
+                              int32_t* labels, int32_t* label_len, float* logits, float* frame_margin, float* min_margin, int32_t* min_frame,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (!e || !e->finalized) return fail("encoder not finalized");
+    if (!e->fc_wt) return fail("no CTC head (fc.weight / fc.bias) loaded");
+    if (enc_is_bf16 && e->exact_on) return fail("effconf_ctc_greedy_margin: bf16 rows belong to the bf16 path (the label-exact modes keep fp32 rows and the fp32 head)");
+    if (enc_is_bf16 && (!e->fc_hi || !e->fc_lo)) return fail("no CTC head (fc.weight / fc.bias) loaded");
+    if (batch < 0 || t_out < 0) return fail("effconf_ctc_greedy_margin: negative batch / t_out");
+    if (!min_margin || !min_frame) return fail("effconf_ctc_greedy_margin: min_margin and min_frame are outputs, not optional");
+    if (workspace_bytes < (size_t)batch * t_out * 8) return fail("workspace too small");
+    int* preds = reinterpret_cast<int*>(workspace);
+    float* margin = frame_margin ? frame_margin : reinterpret_cast<float*>(preds + (size_t)batch * t_out);
+    hipStream_t st = (hipStream_t)stream;
+    const int D = e->blocks.back().dim_expand, V = e->cfg.vocab_size;
+    // the head kernel of effconf_ctc_greedy / effconf_ctc_greedy_bf16 for the same handle state, in its margin instance
+    if (enc_is_bf16) {
+        EC_TRY(launch_ctc_split(reinterpret_cast<const float*>(enc_out), batch * t_out, D, e->fc_hi, e->fc_lo, e->fc_b, V, preds, logits, st, 1, margin));
+    } else {
+        const float* x = reinterpret_cast<const float*>(enc_out);
+        const int mode = e->exact_on && e->ctc_mfma == 2 ? 1 : e->ctc_mfma;
+        if (mode == 2 && e->fc_hi && launch_ctc_split(x, batch * t_out, D, e->fc_hi, e->fc_lo, e->fc_b, V, preds, logits, st, 0, margin) == 0) {
+        } else
+        EC_TRY(launch_ctc_argmax(x, batch * t_out, D, e->fc_wt, e->fc_b, V, preds, logits, st, mode != 0, margin));
+    }
+    EC_TRY(launch_ctc_collapse(preds, out_len, batch, t_out, labels, label_len, st, margin, min_margin, min_frame));
+    return 0;
+}
+
 /* Attention maps (reference encoders.py:126-142): maps[k] = device buffer of batch x heads[k] x tg[k] x tg[k] floats for block k, or null. */
 int effconf_encoder_attention_dims(EcEncoder* e, int32_t n, int32_t from_audio, int32_t* heads, int32_t* tg) {
     if (!e || !e->finalized || !heads || !tg) return fail("effconf_encoder_attention_dims: null argument / encoder not finalized");

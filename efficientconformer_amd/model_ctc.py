@@ -42,6 +42,32 @@ class Alignment(NamedTuple):
     status: int
 
 
+class HeadMargins(NamedTuple):
+    """``ModelCTC.head_margins``: the greedy labels with the top-2 logit margins they were taken at, all on the device.  labels (B, T) i32 with a zero
+    tail, label_len (B,) i32, frame_margin (B, T) f32 (largest minus second largest logit of every frame of the rectangle), min_margin (B,) f32 / min_frame
+    (B,) i32: the smallest margin over an utterance's valid frames and the first frame that holds it (+inf / -1 without frames), logits (B, T, V) or None."""
+    labels: torch.Tensor
+    label_len: torch.Tensor
+    frame_margin: torch.Tensor
+    min_margin: torch.Tensor
+    min_frame: torch.Tensor
+    logits: Optional[torch.Tensor]
+
+
+# Default band of ``ModelCTC.greedy_exact``: twice the largest per-frame spread max_v d_v - min_v d_v, d = bf16-mode logits - split-mode logits, measured
+# over tools/label_exact_band.py's grid (profiles/label_exact_band.txt; DESIGN.md 6f), rounded up to two digits: the worst spread, 2.97, comes from the
+# "trained" weight recipe of synth.make_stressed_state_dict on EfficientConformerCTCLarge (make_state_dict alone: 0.084).
+LABEL_EXACT_BAND = 6.0
+
+
+def select_rerun(min_margin: torch.Tensor, band: float) -> torch.Tensor:
+    """The rows of a batch that margin-gated decoding runs again in the split mode: those whose smallest top-2 margin is not known to be at least
+    `band` - ``not (min_margin >= band)``, so a NaN margin is selected, +inf (an utterance without frames) never, a margin equal to the band is kept.
+    Returns their indices, ascending, int64, on `min_margin`'s device.  Pure: no model, no GPU."""
+    mm = torch.as_tensor(min_margin)
+    return torch.nonzero(~(mm >= float(band)), as_tuple=False).reshape(-1)
+
+
 class ModelCTC(nn.Module):
 
     def __init__(self, encoder_params: dict, tokenizer_params: dict, training_params: Optional[dict] = None,
@@ -55,6 +81,7 @@ class ModelCTC(nn.Module):
         decoding_params = decoding_params or {}
         self.beam_size = int(decoding_params.get("beam_size", 1))                    # model.py:60-61
         self.tmp = float(decoding_params.get("tmp", 1))
+        self.label_exact_band = float(decoding_params.get("label_exact_band", LABEL_EXACT_BAND))
         self.tokenizer = tokenizer
         self.name = name
         self._beam_ws = None
@@ -118,6 +145,131 @@ class ModelCTC(nn.Module):
                           ws.numel(), torch.cuda.current_stream(enc.device).cuda_stream), "ctc_greedy")
         return logits, labels, label_len
 
+    def _margin_call(self, rows: torch.Tensor, as_bf16: bool, lens: torch.Tensor, b: int, t: int, labels, label_len, logits, frame_margin, min_margin,
+                     min_frame):
+        """effconf_ctc_greedy_margin on `b` utterances of `t` frames starting at the given tensors' first elements, on the current stream."""
+        ws = torch.empty(b * t * 8, dtype=torch.uint8, device=rows.device)
+        _lib.check(_lib.load().effconf_ctc_greedy_margin(self.encoder._handle, rows.data_ptr(), int(as_bf16), lens.data_ptr(), b, t, labels.data_ptr(),
+                                                         label_len.data_ptr(), None if logits is None else logits.data_ptr(),
+                                                         None if frame_margin is None else frame_margin.data_ptr(), min_margin.data_ptr(),
+                                                         min_frame.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                         torch.cuda.current_stream(rows.device).cuda_stream), "ctc_greedy_margin")
+
+    def head_margins(self, enc: torch.Tensor, enc_len: Optional[torch.Tensor], want_logits: bool = False) -> HeadMargins:
+        """``_head`` with the top-2 logit margin of every frame and its minimum per utterance (effconf_ctc_greedy_margin): the same head kernel as
+        ``_head`` takes for this handle and row type, so labels, label counts and logits are bit-identical to its; frame_margin is the fp32 difference
+        of the two largest logits of a frame (0 for a duplicated maximum)."""
+        if not enc.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        as_bf16 = enc.dtype == torch.bfloat16 and self.encoder.precision == "bf16" and self.encoder._options.get("ctc_mfma", 2) == 2
+        enc = enc.contiguous() if as_bf16 else enc.contiguous().float()
+        b, t, _ = enc.shape
+        dev = enc.device
+        if enc_len is None:
+            enc_len = torch.full((b,), t, dtype=torch.int64, device=dev)
+        enc_len = enc_len.to(dev, torch.int64).contiguous()
+        out = HeadMargins(torch.empty(b, t, dtype=torch.int32, device=dev), torch.empty(b, dtype=torch.int32, device=dev),
+                          torch.empty(b, t, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev),
+                          torch.empty(b, dtype=torch.int32, device=dev),
+                          torch.empty(b, t, self.fc.out_features, dtype=torch.float32, device=dev) if want_logits else None)
+        with torch.cuda.device(dev):          # the C library launches on the current device
+            self.encoder._ensure_packed()
+            self._margin_call(enc, as_bf16, enc_len, b, t, out.labels, out.label_len, out.logits, out.frame_margin, out.min_margin, out.min_frame)
+        return out
+
+    def _encode_margins(self, x, x_len, from_mel, x_len_host):
+        """Encoder + margin head, the head per row range on that range's stream as in ``encode_greedy`` -> (labels, label_len, min_margin, min_frame)."""
+        state = {}
+
+        def hook(lo, hi, out, out_len):
+            b, t = out.shape[0], out.shape[1]
+            if not state:
+                state["labels"] = torch.empty(b, t, dtype=torch.int32, device=out.device)
+                state["label_len"] = torch.empty(b, dtype=torch.int32, device=out.device)
+                state["min_margin"] = torch.empty(b, dtype=torch.float32, device=out.device)
+                state["min_frame"] = torch.empty(b, dtype=torch.int32, device=out.device)
+            self._margin_call(out[lo:], False, out_len[lo:], hi - lo, t, state["labels"][lo:], state["label_len"][lo:], None, None,
+                              state["min_margin"][lo:], state["min_frame"][lo:])
+            st = torch.cuda.current_stream(out.device)
+            for tns in state.values():
+                tns.record_stream(st)
+
+        (self.encoder.forward_mel if from_mel else self.encoder)(x, x_len, range_hook=hook, x_len_host=x_len_host)
+        return state["labels"], state["label_len"], state["min_margin"], state["min_frame"]
+
+    def greedy_exact(self, x: torch.Tensor, x_len: torch.Tensor, band: Optional[float] = None, from_mel: bool = False, x_len_host=None):
+        """Margin-gated label-exact greedy decoding: the bf16 ragged forward with the margin head; every utterance whose smallest top-2
+        logit margin over its valid frames is not at least `band` runs again - all of them as ONE ragged ``precision = "split"`` batch, trimmed to
+        their longest - and takes the split mode's labels.  If `band` is at least the per-frame spread of (bf16 logit - split logit), the result is the
+        split mode's labels for the whole batch: with a the bf16 argmax of a frame and m its margin, split[a] - split[v] >= m - spread > 0 for every
+        other v.  `band` None: ``decoding_params["label_exact_band"]``, else ``LABEL_EXACT_BAND`` (measured, not proven: profiles/label_exact_band.txt).
+        0 runs nothing again, inf everything.
+
+        Returns (labels (B, T) i32 with zero tails, label_len (B,) i32, report); report: ``band``; ``min_margin`` (B,) f32 on the HOST and
+        ``min_frame`` (B,) i32 on the device, of the bf16 pass; ``rerun``: the row indices that ran again (host, int64, ascending); ``changed``: (B,) bool
+        on the device, the rows whose labels moved; ``exact_min_margin``: the split pass's smallest margins of the rows in ``rerun`` (device).
+
+        Needs ``encoder.ragged`` - the only batch semantics in which an utterance's labels do not depend on its neighbours, so that running a subset
+        again reproduces them - and ``encoder.precision == "bf16"``.  One synchronisation (the copy of min_margin to the host, plus that of `x_len` when
+        `x_len_host` is not given), so it refuses to run while a stream is being captured.  The handle is packed for the split mode once (it serves
+        the bf16 path as well); ``precision`` is "bf16" again on return, also after an error."""
+        enc = self.encoder
+        if not x.is_cuda:
+            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        if not enc.ragged:
+            raise RuntimeError("greedy_exact needs encoder.ragged = True: only a ragged forward gives an utterance the same labels in every batch")
+        if enc.precision != "bf16":
+            raise RuntimeError("greedy_exact gates the bf16 path: encoder.precision is %r (that mode's greedy_labels are already what it computes)" % enc.precision)
+        if x_len is None:
+            raise ValueError("greedy_exact needs x_len (a ragged batch)")
+        band = float(self.label_exact_band if band is None else band)
+        if band != band or band < 0:
+            raise ValueError("band must be >= 0; got %r" % band)
+        with torch.cuda.device(x.device):
+            if enc._capturing(x.device):
+                raise RuntimeError("greedy_exact synchronises (min_margin goes to the host): not while a stream is being captured")
+            if not (enc._packed and enc._exact_packed == 2):
+                try:                               # pack for the split mode: that handle serves both passes
+                    enc.precision = "split"
+                    enc._ensure_packed()
+                finally:
+                    enc.precision = "bf16"
+            host = x_len_host if x_len_host is not None else x_len.cpu()
+            host = np.ascontiguousarray(np.asarray(host.cpu() if torch.is_tensor(host) else host, dtype=np.int64))
+            check = enc.check_host_lengths
+            try:
+                enc.check_host_lengths = check and x_len_host is not None      # a copy made here needs no comparison with its source
+                labels, label_len, min_margin, min_frame = self._encode_margins(x, x_len, from_mel, host)
+            finally:
+                enc.check_host_lengths = check
+            mm = min_margin.cpu()                  # the one D2H copy the gate needs
+            rerun = select_rerun(mm, band)
+            report = {"band": band, "min_margin": mm, "min_frame": min_frame, "rerun": rerun,
+                      "changed": torch.zeros(x.shape[0], dtype=torch.bool, device=x.device),
+                      "exact_min_margin": torch.empty(0, dtype=torch.float32, device=x.device)}
+            if rerun.numel() == 0:
+                return labels, label_len, report
+            idx = rerun.to(x.device)
+            sub_host = host[rerun.numpy()]
+            n = int(sub_host.max())
+            xs = (x[idx, :, :n] if from_mel else x[idx, :n]).contiguous()
+            ls = x_len.to(x.device, torch.int64)[idx].contiguous()
+            try:
+                enc.precision = "split"
+                enc.check_host_lengths = False     # both gathered from lengths the first pass has compared
+                lab2, len2, mm2, _ = self._encode_margins(xs, ls, from_mel, sub_host)
+            finally:
+                enc.precision = "bf16"
+                enc.check_host_lengths = check
+            t2 = lab2.shape[1]                     # <= labels.shape[1]: the selected rows' own longest output
+            new = torch.zeros(idx.numel(), labels.shape[1], dtype=torch.int32, device=x.device)
+            new[:, :t2] = lab2
+            report["changed"][idx] = (new != labels[idx]).any(dim=1) | (len2 != label_len[idx])
+            report["exact_min_margin"] = mm2
+            labels[idx] = new
+            label_len[idx] = len2
+        return labels, label_len, report
+
     def encode_greedy(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_mel: bool = False, **encoder_kwargs):
         """Encoder + CTC head with the head launched PER ROW RANGE on that range's stream (``ConformerEncoder.sub_batches``): the
         fc + argmax + collapse of range i overlaps the other ranges' encoder kernels instead of running after the join
@@ -144,17 +296,25 @@ class ModelCTC(nn.Module):
             enc, enc_len, _ = (self.encoder.forward_mel if from_mel else self.encoder)(x, x_len, range_hook=hook, **encoder_kwargs)
         return enc, enc_len, state["labels"], state["label_len"]
 
-    def greedy_labels(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_mel: bool = False) -> List[List[int]]:
-        """Greedy CTC label-id sequences (blank 0 removed, repeats collapsed), one list per utterance."""
-        enc, enc_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
-        _, labels, label_len = self._head(enc, enc_len)
+    def greedy_labels(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_mel: bool = False, *, label_exact: Optional[str] = None,
+                      band: Optional[float] = None) -> List[List[int]]:
+        """Greedy CTC label-id sequences (blank 0 removed, repeats collapsed), one list per utterance.  `label_exact`: None - one forward in
+        ``encoder.precision``; "auto" - ``greedy_exact`` (utterances with a top-2 margin under `band` run again in the split mode); "always" - every
+        utterance runs again (band = inf)."""
+        if label_exact not in (None, "auto", "always"):
+            raise ValueError("label_exact must be None, 'auto' or 'always'; got %r" % (label_exact,))
+        if label_exact is not None:
+            labels, label_len, _ = self.greedy_exact(x, x_len, float("inf") if label_exact == "always" else band, from_mel)
+        else:
+            enc, enc_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+            _, labels, label_len = self._head(enc, enc_len)
         labels, label_len = labels.cpu(), label_len.cpu()          # one D2H copy per batch, not one per token
         return [labels[b, :int(label_len[b])].tolist() for b in range(labels.shape[0])]
 
-    def gready_search_decoding(self, x, x_len):
+    def gready_search_decoding(self, x, x_len, label_exact: Optional[str] = None):
         """Reference spelling (model_ctc.py:90).  Returns decoded strings when a tokenizer is attached
-        (``tokenizer.decode(list_of_id_lists)``, model_ctc.py:136), otherwise the id lists."""
-        ids = self.greedy_labels(x, x_len)
+        (``tokenizer.decode(list_of_id_lists)``, model_ctc.py:136), otherwise the id lists.  `label_exact`: as ``greedy_labels``."""
+        ids = self.greedy_labels(x, x_len, label_exact=label_exact)
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
 
     greedy_search_decoding = gready_search_decoding

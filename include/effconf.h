@@ -139,6 +139,20 @@ int effconf_ctc_greedy(EcEncoder* enc, const float* enc_out, const int64_t* out_
  * widened to fp32. */
 int effconf_ctc_greedy_bf16(EcEncoder* enc, const uint16_t* enc_out_bf16, const int64_t* out_len, int32_t batch, int32_t t_out,
                             int32_t* labels, int32_t* label_len, float* logits, void* workspace, size_t workspace_bytes, void* stream);
+/* The same head with the top-2 logit margin of every frame, for margin-gated label-exact decoding (ModelCTC.greedy_exact: an utterance whose
+ * smallest bf16 margin is at least a band >= the per-frame spread of (bf16 logit - split logit) keeps its bf16 labels).
+ * enc_out: dev f32 rows, or dev bf16 rows with enc_is_bf16 != 0 (then as effconf_ctc_greedy_bf16: bf16 path only).  The head kernel is chosen as in
+ * the two entries above (option ctc_mfma, the label-exact modes, the row type); labels, label_len and logits are bit-identical to theirs.
+ *   frame_margin dev f32 (batch, t_out), may be NULL: largest minus second largest logit of the frame, the fp32 subtraction of the values `logits`
+ *                holds (= topk(logits, 2) differenced); 0 for a duplicated maximum (the label stays the first index).  Every frame of the
+ *                rectangle is written, valid or not.
+ *   min_margin   dev f32 (batch): the smallest frame_margin over frames < out_len[b] (clamped to [0, t_out]); +inf for out_len 0.  A NaN margin
+ *                (a frame of NaN logits) wins over every number.
+ *   min_frame    dev i32 (batch): the first frame that holds min_margin; -1 for out_len 0.
+ * logits may be NULL.  Needs batch*T_out*8 bytes of workspace. */
+int effconf_ctc_greedy_margin(EcEncoder* enc, const void* enc_out, int32_t enc_is_bf16, const int64_t* out_len, int32_t batch, int32_t t_out,
+                              int32_t* labels, int32_t* label_len, float* logits, float* frame_margin, float* min_margin, int32_t* min_frame,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* CTC prefix beam search: ModelCTC.beam_search_decoding (reference model_ctc.py:138-181, ctcdecode's CTCBeamDecoder with blank 0,
  * cutoff_top_n = vocab, cutoff_prob 1) without the n-gram (KenLM) terms, one persistent workgroup per utterance.  logits dev f32
