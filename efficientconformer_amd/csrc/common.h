@@ -50,6 +50,9 @@ __device__ __forceinline__ int lane_now() {
     return l;
 }
 
+// Workgroup barrier that waits for this wave's LDS traffic only (lgkmcnt): the global loads a ring has in flight (vmcnt) stay in flight across it
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 // Raise a kernel's dynamic-LDS limit when a launch needs more than any earlier launch of that instantiation ON THAT DEVICE (the
 // attribute is per device; one process may hold handles on several).  One static LdsAttr per launch site.
 struct LdsAttr { int bytes[16] = {}; };

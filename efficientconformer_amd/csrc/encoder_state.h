@@ -17,6 +17,7 @@ inline int ld8(int d) { return ec_round_up(d, 8); }
 struct HostTensor { std::vector<float> data; std::vector<int64_t> shape; };
 
 struct PackedLinear { const bf16_t* w = nullptr; const float* bias = nullptr; int N = 0, K = 0, ldw = 0; std::vector<float> hbias; /* host copy of the padded bias */ };
+struct SubChunkImg { const uint16_t *cimg = nullptr, *wimg = nullptr; const float* bias = nullptr; int ncb = 0, fo = 0; };   // kernels.h: SubChunkParams (null wimg: not built)
 struct LNp { const float* g = nullptr; const float* b = nullptr; };
 
 struct BlockW {
@@ -62,7 +63,7 @@ struct EcEncoder {
     const float *sub_w9 = nullptr, *sub_b = nullptr;
     PackedLinear lin;
     const bf16_t* lin_fused = nullptr; int lin_fused_ld = 0;   // Linear weight in the fused kernel's K order (sublinear.hip)
-    const uint16_t *sub3_cimg = nullptr, *sub3_wimg = nullptr; const float* sub3_bias = nullptr; int sub3_ncb = 0, sub3_fo = 0;   // sublinear3.hip (kernels.h: SubLin3Params)
+    SubChunkImg sub3, xsub;               // images of the chunked front end (one-layer subsampler only): bf16 (sublinear3.hip) and split mode (sxf_sub.hip)
     const bf16_t* lin_rs = nullptr; const float* conv_tab = nullptr;   // sublinear2.hip: Linear weight [F/2][32 NT][32 CG] (K-permuted per 16), conv taps [32 CG][16]
     int fuse_subsample = 2;                  // 0: separate conv + GEMM kernels, 1: sublinear.hip, 2: sublinear2.hip where it supports the shape (else 1; wide front ends: sublinear3.hip, option sub3_auto), 3: sublinear3.hip
     bool fuse_chain = true;                  // row-local chains (chain.hip) where supported
@@ -128,8 +129,6 @@ struct EcEncoder {
     std::map<std::string, const float*> xw;
     std::map<std::pair<int, int>, const float*> xtab;
     const float *xsub_scale[2] = {nullptr, nullptr}, *xsub_shift[2] = {nullptr, nullptr};
-    // split mode: images of the fused front end (sxf_sub.hip; kernels.h: SxfSubParams) - one-layer subsampler only
-    const uint16_t *xsub_cimg = nullptr, *xsub_wimg = nullptr; const float* xsub_bias = nullptr; int xsub_ncb = 0, xsub_fo = 0;
     // per-launch event profiler (bench / tuning only; off by default)
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;          // pairs

@@ -136,48 +136,55 @@ int run_rs_or_tiled(EcEncoder* e, int cls, hipStream_t st, const bf16_t* A, int 
     return launch_rs_gemm(p, rs_epi, st);
 }
 
-// Conv2dSubsampling (modules.py:232-249) + transpose + Linear (encoders.py:113-116): mel (B, n_mels, Tm) -> x fp32 (B * T1, D0).
-// sub / act1: bf16 scratch of the unfused variants (the subsampler's output rows / the two-layer subsampler's layer-1 image).
+// Conv2dSubsampling (modules.py:232-249) + transpose + Linear (encoders.py:113-116): mel (B, n_mels, s.Tm) -> x fp32 (s.Min[0] rows, D0).  The one list of the bf16
+// schedule's front-end routes, for rectangular batches (rg = null: rows (b, t), B * T1) and ragged ones (rg: the batch's descriptors; x = the ragged row space).
+// sub / act1: bf16 scratch of the unfused variants (the subsampler's output rows / the two-layer subsampler's layer-1 image); xrect: ragged two-layer route only.
 // sublinear3.hip: option fuse_subsample = 3 (every one-layer front end it is built for) or 2 = the default where sublinear2.hip has no instance or runs one workgroup per
 // CU (channel counts / widths above 128); a debug trace keeps the kernels that write the "subsample" activation only when fuse_subsample = 0
 bool use_sublinear3(const EcEncoder* e) {
-    if (!e->sub3_wimg || e->cfg.sub_layers != 1) return false;
+    if (!e->sub3.wimg || e->cfg.sub_layers != 1) return false;
     if (e->fuse_subsample == 3) return true;
     return e->fuse_subsample == 2 && e->sub3_auto && (e->cfg.sub_filters[0] > 128 || e->blocks[0].dim_model > 128);
 }
 
-int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, int B, int Tm, int T1, bf16_t* sub, bf16_t* act1, float* x) {
+int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, const Shapes& s, const BatchRows* rg, bf16_t* sub, bf16_t* act1, float* xrect, float* x) {
     const EcConfig& c = e->cfg;
-    const int C0 = c.sub_filters[0], F2 = c.n_mels / 2, Ksub = C0 * F2;
+    const int B = s.B, Tm = s.Tm, C0 = c.sub_filters[0], F2 = c.n_mels / 2, Ksub = C0 * F2, N = e->lin.N;
+    const RaggedRows r0 = rg ? rg->rows_at(0) : RaggedRows{};
+    const int* mel_len = rg ? rg->mel_len : nullptr;
+    const double Mr = (double)s.Min[0];                            // rows of x
+    const int Tl1 = (Tm - 1) / 2 + 1;                              // frames after one layer, at the input's pitch
     if (c.sub_layers == 2) {
-        const int Tl1 = (Tm - 1) / 2 + 1, F1 = c.n_mels / 2, F2q = c.n_mels / 4, C1 = c.sub_filters[1];
+        // two-layer subsampler (the plain Conformer configurations).  Ragged: both convolutions and the Linear on the RECTANGULAR image at the input's pitch - layer 1
+        // zero-fills every utterance's image behind its own last frame, so layer 2 sees the zero padding of the utterance run alone - then the valid rows are gathered
+        // into the ragged row space
+        const int T2 = (Tl1 - 1) / 2 + 1, F1 = c.n_mels / 2, F2q = c.n_mels / 4, C1 = c.sub_filters[1];
         { PROF(PC_SUBCONV, 2.0 * 9 * B * Tl1 * (double)C0 * F1, (double)B * c.n_mels * Tm * 4 + (double)B * Tl1 * F1 * e->sub2_cp * 2);
-          EC_TRY(launch_subsample_conv_cl(mel, B, c.n_mels, Tm, Tl1, e->sub_w9, e->sub_b, C0, e->sub2_cp, act1, st)); }
+          EC_TRY(launch_subsample_conv_cl(mel, B, c.n_mels, Tm, Tl1, e->sub_w9, e->sub_b, C0, e->sub2_cp, act1, st, mel_len)); }
         trace_add(e, st, "subsample1", act1, (int64_t)B * F1 * Tl1, C0, e->sub2_cp, 1);       // layer-1 image, rows (b, f, t), channel-last
-        { PROF(PC_GEMM_OTHER, 2.0 * 9 * (double)B * F2q * T1 * C0 * C1, (double)B * Tl1 * F1 * e->sub2_cp * 2 + (double)B * T1 * F2q * C1 * 2);
-          EC_TRY(launch_conv2_igemm(act1, B, F1, Tl1, e->sub2_cp, e->sub2_w, 9 * e->sub2_cp, e->sub2_b, C1, F2q, T1, sub, st)); }
-        trace_add(e, st, "subsample", sub, (int64_t)B * T1, F2q * C1, F2q * C1, 1);
-        EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, F2q * C1, B * T1, e->lin, EPI_F32, x, e->lin.N));
-    } else if (use_sublinear3(e)) {
-        PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub + 2.0 * B * T1 * (double)Ksub * e->lin.N,
-             (double)B * c.n_mels * Tm * 4 + (double)B * T1 * e->lin.N * 4);
-        SubLin3Params sp{};
-        sp.mel = mel; sp.B = B; sp.F = c.n_mels; sp.Tm = Tm; sp.To = T1; sp.rows_max = T1;
-        sp.cimg = e->sub3_cimg; sp.wimg = e->sub3_wimg; sp.bias = e->sub3_bias; sp.y = x; sp.ldy = e->lin.N; sp.N = e->lin.N; sp.ncb = e->sub3_ncb; sp.Fo = e->sub3_fo;
-        EC_TRY(launch_sublinear3(sp, st));
-    } else if (e->fuse_subsample >= 2 && e->lin_rs) {
-        PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub + 2.0 * B * T1 * (double)Ksub * e->lin.N,
-             (double)B * c.n_mels * Tm * 4 + (double)B * T1 * e->lin.N * 4);
-        EC_TRY(launch_sublinear2(mel, B, c.n_mels, Tm, T1, e->conv_tab, e->lin_rs, e->lin.bias, C0, e->lin.N, x, e->lin.N, st));
-    } else if (e->fuse_subsample && e->lin_fused) {
-        PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub + 2.0 * B * T1 * (double)Ksub * e->lin.N,
-             (double)B * c.n_mels * Tm * 4 + (double)B * T1 * e->lin.N * 4);
-        EC_TRY(launch_sublinear_fused(mel, B, c.n_mels, Tm, T1, e->sub_w9, e->sub_b, C0, e->lin_fused, e->lin_fused_ld,
-                                      e->lin.bias, e->lin.N, x, e->lin.N, st));
+        { PROF(PC_GEMM_OTHER, 2.0 * 9 * (double)B * F2q * T2 * C0 * C1, (double)B * Tl1 * F1 * e->sub2_cp * 2 + (double)B * T2 * F2q * C1 * 2);
+          EC_TRY(launch_conv2_igemm(act1, B, F1, Tl1, e->sub2_cp, e->sub2_w, 9 * e->sub2_cp, e->sub2_b, C1, F2q, T2, sub, st)); }
+        trace_add(e, st, "subsample", sub, (int64_t)B * T2, F2q * C1, F2q * C1, 1);           // the RECTANGULAR image's rows (b, t)
+        EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, F2q * C1, B * T2, e->lin, EPI_F32, rg ? xrect : x, N));
+        if (rg) { PROF(PC_MISC, 0, Mr * N * 8); EC_TRY(launch_gather_rows(xrect, N, T2, r0, x, st)); }
+    } else if (use_sublinear3(e)) {                                // sublinear3.hip: workgroup = (utterance, 128 frames)
+        PROF(PC_SUBCONV, 2.0 * 9 * Mr * Ksub + 2.0 * Mr * Ksub * N, (double)B * c.n_mels * Tm * 4 + Mr * N * 4);
+        EC_TRY(launch_sublinear3(sub_chunk_params(e, e->sub3, mel, s, rg, x), st));
+    } else if (e->fuse_subsample >= 2 && e->lin_rs) {              // sublinear2.hip indexes the ragged rows itself
+        PROF(PC_SUBCONV, 2.0 * 9 * Mr * Ksub + 2.0 * Mr * Ksub * N, (double)B * c.n_mels * Tm * 4 + Mr * N * 4);
+        EC_ABL(rg ? 32 : 0, EC_TRY(launch_sublinear2(mel, B, c.n_mels, Tm, s.T1, e->conv_tab, e->lin_rs, e->lin.bias, C0, N, x, N, st, rg ? &r0 : nullptr, mel_len)));
+    } else if (!rg && e->fuse_subsample && e->lin_fused) {         // sublinear.hip: rectangular batches only
+        PROF(PC_SUBCONV, 2.0 * 9 * Mr * Ksub + 2.0 * Mr * Ksub * N, (double)B * c.n_mels * Tm * 4 + Mr * N * 4);
+        EC_TRY(launch_sublinear_fused(mel, B, c.n_mels, Tm, s.T1, e->sub_w9, e->sub_b, C0, e->lin_fused, e->lin_fused_ld, e->lin.bias, N, x, N, st));
     } else {
-        { PROF(PC_SUBCONV, 2.0 * 9 * B * T1 * (double)Ksub, (double)B * c.n_mels * Tm * 4 + (double)B * T1 * Ksub * 2); EC_TRY(launch_subsample_conv(mel, B, c.n_mels, Tm, T1, e->sub_w9, e->sub_b, C0, sub, Ksub, st)); }
-        trace_add(e, st, "subsample", sub, (int64_t)B * T1, Ksub, Ksub, 1);
-        EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, Ksub, B * T1, e->lin, EPI_F32, x, e->lin.N));
+        // conv + GEMM (wide front ends: Large with sub3_auto = 0).  Ragged: the conv (zero padding at every utterance's own last mel frame) writes the RAGGED rows
+        // itself (tiles behind an utterance's own end exit; group-padding rows = zeros) and the Linear runs on those rows only.  Group-padding rows of x = the Linear's
+        // bias (finite; no kernel mixes them into valid rows).  Tcover >= every utterance's frames rounded up to the group size
+        const int Tcover = rg ? Tl1 + e->blocks[0].group_size - 1 : s.T1;
+        { PROF(PC_SUBCONV, 2.0 * 9 * Mr * Ksub, (double)B * c.n_mels * Tm * 4 + Mr * Ksub * 2);
+          EC_TRY(launch_subsample_conv(mel, B, c.n_mels, Tm, Tcover, e->sub_w9, e->sub_b, C0, sub, Ksub, st, mel_len, rg ? &r0 : nullptr)); }
+        trace_add(e, st, "subsample", sub, s.Min[0], Ksub, Ksub, 1);
+        EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, Ksub, (int)s.Min[0], e->lin, EPI_F32, x, N));
     }
     return 0;
 }
@@ -204,53 +211,8 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
     // ---- Conv2dSubsampling (modules.py:232-249) + transpose + Linear (encoders.py:113-116)
     float* x = reinterpret_cast<float*>(ws + w.x0);
     float* xalt = reinterpret_cast<float*>(ws + w.x1);
-    if (rg) {
-        const int C0 = c.sub_filters[0], Ksub = C0 * (c.n_mels / 2);
-        const RaggedRows r0 = br.rows_at(0);
-        if (c.sub_layers == 2) {
-            // two-layer subsampler (the plain Conformer configurations): both convolutions and the Linear on the RECTANGULAR image - layer 1
-            // zero-fills every utterance's image behind its own last frame, so layer 2 sees the zero padding of the utterance run alone -
-            // then the valid rows are gathered into the ragged row space
-            bf16_t* sub = reinterpret_cast<bf16_t*>(ws + w.sub);
-            bf16_t* act1 = reinterpret_cast<bf16_t*>(ws + w.sub1);
-            float* xrect = reinterpret_cast<float*>(ws + w.xrect);
-            const int Tl1 = (s.Tm - 1) / 2 + 1, T1r = (Tl1 - 1) / 2 + 1, F1 = c.n_mels / 2, F2q = c.n_mels / 4, C1 = c.sub_filters[1];
-            { PROF(PC_SUBCONV, 2.0 * 9 * B * Tl1 * (double)C0 * F1, (double)B * c.n_mels * s.Tm * 4 + (double)B * Tl1 * F1 * e->sub2_cp * 2);
-              EC_TRY(launch_subsample_conv_cl(mel, B, c.n_mels, s.Tm, Tl1, e->sub_w9, e->sub_b, C0, e->sub2_cp, act1, st, mel_len)); }
-            trace_add(e, st, "subsample1", act1, (int64_t)B * F1 * Tl1, C0, e->sub2_cp, 1);
-            { PROF(PC_GEMM_OTHER, 2.0 * 9 * (double)B * F2q * T1r * C0 * C1, (double)B * Tl1 * F1 * e->sub2_cp * 2 + (double)B * T1r * F2q * C1 * 2);
-              EC_TRY(launch_conv2_igemm(act1, B, F1, Tl1, e->sub2_cp, e->sub2_w, 9 * e->sub2_cp, e->sub2_b, C1, F2q, T1r, sub, st)); }
-            trace_add(e, st, "subsample", sub, (int64_t)B * T1r, F2q * C1, F2q * C1, 1);       // the RECTANGULAR image's rows (b, t)
-            EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, F2q * C1, B * T1r, e->lin, EPI_F32, xrect, e->lin.N));
-            { PROF(PC_MISC, 0, (double)s.Min[0] * e->lin.N * 8); EC_TRY(launch_gather_rows(xrect, e->lin.N, T1r, r0, x, st)); }
-        } else if (use_sublinear3(e)) {                            // sublinear3.hip: workgroup = (utterance, 128 frames)
-            PROF(PC_SUBCONV, 2.0 * 9 * (double)s.Min[0] * Ksub + 2.0 * (double)s.Min[0] * Ksub * e->lin.N, (double)B * c.n_mels * s.Tm * 4 + (double)s.Min[0] * e->lin.N * 4);
-            SubLin3Params sp{};
-            sp.mel = mel; sp.B = B; sp.F = c.n_mels; sp.Tm = s.Tm; sp.mel_len = mel_len; sp.off = r0.off; sp.len = r0.len;
-            sp.rows_max = ec_round_up(s.Tin[0], e->blocks[0].group_size);
-            sp.cimg = e->sub3_cimg; sp.wimg = e->sub3_wimg; sp.bias = e->sub3_bias; sp.y = x; sp.ldy = e->lin.N; sp.N = e->lin.N; sp.ncb = e->sub3_ncb; sp.Fo = e->sub3_fo;
-            EC_TRY(launch_sublinear3(sp, st));
-        } else if (e->fuse_subsample >= 2 && e->lin_rs) {        // sublinear2.hip indexes the ragged rows itself
-            PROF(PC_SUBCONV, 2.0 * 9 * (double)s.Min[0] * Ksub + 2.0 * (double)s.Min[0] * Ksub * e->lin.N, (double)B * c.n_mels * s.Tm * 4 + (double)s.Min[0] * e->lin.N * 4);
-            EC_ABL(32, EC_TRY(launch_sublinear2(mel, B, c.n_mels, s.Tm, s.T1, e->conv_tab, e->lin_rs, e->lin.bias, C0, e->lin.N, x, e->lin.N, st, &r0, mel_len)));
-        } else {
-            // wide front ends (Large: 360 filters): conv (zero padding at every utterance's own last mel frame) + Linear on the RECTANGULAR
-            // (B, T1 of the longest) rows, then the valid rows are gathered into the ragged row space (pad rows are computed and dropped:
-            // the subsampler is a few percent of the step)
-            // Round 4: the conv writes the RAGGED rows itself (tiles behind an utterance's own end exit; group-padding rows = zeros) and the
-            // Linear runs on those rows only - until round 3 both ran on the (B, longest) rectangle (24 % padding on the bench batch) and a
-            // gather pass copied the valid rows.  Group-padding rows of x = the Linear's bias (finite; no kernel mixes them into valid rows).
-            bf16_t* sub = reinterpret_cast<bf16_t*>(ws + w.sub);
-            const int T1r = (s.Tm - 1) / 2 + 1;            // rows per utterance of the rectangular image (pitch of the input)
-            const int Tcover = T1r + e->blocks[0].group_size - 1;      // >= every utterance's frames rounded up to the group size
-            { PROF(PC_SUBCONV, 2.0 * 9 * (double)s.Min[0] * Ksub, (double)B * c.n_mels * s.Tm * 4 + (double)s.Min[0] * Ksub * 2);
-              EC_TRY(launch_subsample_conv(mel, B, c.n_mels, s.Tm, Tcover, e->sub_w9, e->sub_b, C0, sub, Ksub, st, mel_len, &r0)); }
-            trace_add(e, st, "subsample", sub, s.Min[0], Ksub, Ksub, 1);                       // the RAGGED rows
-            EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, Ksub, (int)s.Min[0], e->lin, EPI_F32, x, e->lin.N));
-        }
-    } else {
-        EC_TRY(run_subsample_linear(e, st, mel, B, s.Tm, s.T1, reinterpret_cast<bf16_t*>(ws + w.sub), reinterpret_cast<bf16_t*>(ws + w.sub1), x));
-    }
+    EC_TRY(run_subsample_linear(e, st, mel, s, rg ? &br : nullptr, reinterpret_cast<bf16_t*>(ws + w.sub), reinterpret_cast<bf16_t*>(ws + w.sub1),
+                                reinterpret_cast<float*>(ws + w.xrect), x));
     trace_add(e, st, "linear", x, s.Min[0], e->lin.N, e->lin.N, 0);
 
     bf16_t* a = reinterpret_cast<bf16_t*>(ws + w.a);
@@ -569,7 +531,7 @@ int effconf_subsample(EcEncoder* e, const float* mel, int32_t batch, int32_t n_f
     const size_t act_bytes = L == 2 ? al((size_t)batch * (e->cfg.n_mels / 2) * tl1 * ec_round_up(e->cfg.sub_filters[0], 64) * 2) : 0;
     if (workspace_bytes < sub_bytes + act_bytes) return fail("workspace too small");
     char* ws = reinterpret_cast<char*>(workspace);
-    return run_subsample_linear(e, (hipStream_t)stream, mel, batch, n_frames, s.T1, reinterpret_cast<bf16_t*>(ws), reinterpret_cast<bf16_t*>(ws + sub_bytes), y);
+    return run_subsample_linear(e, (hipStream_t)stream, mel, s, nullptr, reinterpret_cast<bf16_t*>(ws), reinterpret_cast<bf16_t*>(ws + sub_bytes), nullptr, y);
 }
 
 int effconf_layernorm_residual(EcEncoder* e, int32_t block, int32_t which, const float* x, const float* r, float alpha, int32_t rows, float* y,

@@ -174,6 +174,18 @@ struct BatchRows {
     }
 };
 
+// Parameter block of the chunked front end (sub_chunked.h) in either format: image `im`, mel (B, n_mels, s.Tm) -> y (s.Min[0] rows, D0); rg = null: rectangular
+// rows (b, t), else the batch's ragged descriptors
+inline SubChunkParams sub_chunk_params(const EcEncoder* e, const SubChunkImg& im, const float* mel, const Shapes& s, const BatchRows* rg, float* y) {
+    SubChunkParams sp{};
+    sp.mel = mel; sp.B = s.B; sp.F = e->cfg.n_mels; sp.Tm = s.Tm;
+    if (rg) { const RaggedRows r0 = rg->rows_at(0); sp.mel_len = rg->mel_len; sp.off = r0.off; sp.len = r0.len; sp.rows_max = ec_round_up(s.Tin[0], e->blocks[0].group_size); }
+    else { sp.To = s.T1; sp.rows_max = s.T1; }
+    sp.cimg = im.cimg; sp.wimg = im.wimg; sp.bias = im.bias; sp.ncb = im.ncb; sp.Fo = im.fo;
+    sp.y = y; sp.ldy = sp.N = e->blocks[0].dim_model;
+    return sp;
+}
+
 // Start of every forward: empties the trace, enqueues the lengths kernel (out_len = the lengths leaving the encoder) and records the mel image of an audio forward
 template <class W>
 int begin_forward(EcEncoder* e, hipStream_t st, const Shapes& s, const W& w, char* ws, const float* mel, const int64_t* in_len, int from_audio, int64_t* out_len,

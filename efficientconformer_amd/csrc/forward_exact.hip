@@ -178,16 +178,11 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
     // one-layer subsampler: convolution + Swish + Linear as ONE kernel on the frames that exist (sxf_sub.hip) - the (frames, C F') activation stays in registers.
     // A debug trace wants that activation ("subsample"): per-module kernels then, unless option trace_fused keeps the forward as it runs untraced
     const bool tr_modules = e->trace_arena && !e->trace_fused;
-    const bool sublin = fused && e->split_sublin && e->xsub_wimg && c.sub_layers == 1 && !tr_modules;
+    const bool sublin = fused && e->split_sublin && e->xsub.wimg && c.sub_layers == 1 && !tr_modules;
     if (sublin) {
-        SxfSubParams sp{};
-        sp.mel = mel; sp.B = B; sp.F = c.n_mels; sp.Tm = s.Tm; sp.mel_len = br.mel_len;
-        if (rg) { const RaggedRows r0 = br.rows_at(0); sp.off = r0.off; sp.len = r0.len; sp.rows_max = ec_round_up(s.Tin[0], e->blocks[0].group_size); }
-        else { sp.To = T1r; sp.rows_max = T1r; }
-        sp.cimg = e->xsub_cimg; sp.wimg = e->xsub_wimg; sp.bias = e->xsub_bias; sp.y = x; sp.N = D0; sp.ncb = e->xsub_ncb; sp.Fo = e->xsub_fo;
-        const double Mr = (double)s.Min[0], Ks = (double)C0 * e->xsub_fo;
+        const double Mr = (double)s.Min[0], Ks = (double)C0 * e->xsub.fo;
         PROF(PC_SUBCONV, 2.0 * Mr * Ks * (9.0 + D0), (double)B * c.n_mels * s.Tm * 4 + Mr * D0 * 4);
-        EC_TRY(launch_sxf_sublin(sp, st));
+        EC_TRY(launch_sxf_sublin(sub_chunk_params(e, e->xsub, mel, s, rg ? &br : nullptr, x), st));
     } else {
         int Fl = (c.n_mels - 1) / 2 + 1, Cl = C0;
         {

@@ -463,11 +463,11 @@ int pack_front_end(EcEncoder* e) {
         e->lin_rs = upload(e, wr); e->conv_tab = upload(e, tab);
     }
     // sublinear3.hip: any channel count / width up to 384
-    e->sub3_cimg = e->sub3_wimg = nullptr; e->sub3_bias = nullptr;
-    if (const int nt3 = sublinear3_tiles(N)) {
+    e->sub3 = SubChunkImg{};
+    if (const int nt3 = sub_chunked_tiles(N)) {
         Img cimg, wimg; std::vector<float> bp;
         front_chunks(taps, tbias, fdata(lw), fdata(lb), C, F2, N, nt3, bf16_pair_trunc, bf16_single, 1, &cimg, &wimg, &bp);
-        e->sub3_cimg = upload(e, cimg); e->sub3_wimg = upload(e, wimg); e->sub3_bias = upload(e, bp); e->sub3_ncb = (C + 31) / 32; e->sub3_fo = F2;
+        e->sub3 = SubChunkImg{upload(e, cimg), upload(e, wimg), upload(e, bp), (C + 31) / 32, F2};
     }
     return 0;
 }
@@ -696,18 +696,18 @@ int pack_split_modules(EcEncoder* e) {
     return range_err.empty() ? 0 : fail(range_err);
 }
 
-// split mode: images of the fused front end (sxf_sub.hip; kernels.h: SxfSubParams) - one-layer subsampler only; a folded value the image cannot hold: no fused
+// split mode: images of the fused front end (sxf_sub.hip; kernels.h: SubChunkParams) - one-layer subsampler only; a folded value the image cannot hold: no fused
 // front end (per-module kernels)
 int pack_split_front_end(EcEncoder* e) {
     const EcConfig& c = e->cfg;
     if (c.sub_layers != 1) return 0;
-    const int Co = c.sub_filters[0], Fo = (c.n_mels - 1) / 2 + 1, N = e->blocks[0].dim_model, nt = sxf_sublin_tiles(N);
+    const int Co = c.sub_filters[0], Fo = (c.n_mels - 1) / 2 + 1, N = e->blocks[0].dim_model, nt = sub_chunked_tiles(N);
     const HostTensor *lw = find(e, "linear.weight"), *lb = find(e, "linear.bias");
     std::vector<double> taps; std::vector<float> tbias, bp; std::string err;
     Img cimg, wimg;
     if (!nt || !sized(lw, (int64_t)N * Co * Fo) || !sized(lb, N) || !fold_front_conv(e, &taps, &tbias, &err)) return 0;
     if (!front_chunks(taps, tbias, fdata(lw), fdata(lb), Co, Fo, N, nt, f16_pair_s10, f16_pair_s10, 2, &cimg, &wimg, &bp)) return 0;
-    e->xsub_cimg = upload(e, cimg); e->xsub_wimg = upload(e, wimg); e->xsub_bias = upload(e, bp); e->xsub_ncb = (Co + 31) / 32; e->xsub_fo = Fo;
+    e->xsub = SubChunkImg{upload(e, cimg), upload(e, wimg), upload(e, bp), (Co + 31) / 32, Fo};
     return 0;
 }
 
@@ -790,7 +790,7 @@ int pack_encoder(EcEncoder* e) {
     if (!e->exact_pack) return 0;
     if ((rc = pack_fp32_tensors(e))) return rc;
     e->xsplit.clear();
-    e->xsub_cimg = e->xsub_wimg = nullptr; e->xsub_bias = nullptr;
+    e->xsub = SubChunkImg{};
     if (e->exact_split && ((rc = pack_split_front_end(e)) || (rc = pack_split_modules(e)) || (rc = pack_split_ffn(e)) || (rc = pack_split_chains(e)))) return rc;
     return pack_fp32_tables(e);
 }

@@ -36,7 +36,6 @@ __device__ __forceinline__ void wave_sync() {
 
 // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding GLOBAL load (s_waitcnt vmcnt(0)), i.e. for the next
 // tile's prefetch the moment it was issued
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int KS, int NT>
 struct AttnLds {

@@ -27,8 +27,6 @@ namespace {
 
 using namespace sx;
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 constexpr float SA = 256.0f, SW = 1024.0f, UNS = 1.0f / (256.0f * 1024.0f);      // LayerNorm-ed operands | weights (the scales of sxf_ffn.hip)
 constexpr float SR = 64.0f, UNS_R = 1.0f / (64.0f * 1024.0f);                    // operands that are NOT LayerNorm-ed (attention output, conv-module activations): range 1023
 constexpr int ROW2 = 80;                                                         // bytes per F2 image row in LDS: 32 inputs (64 B) + 16

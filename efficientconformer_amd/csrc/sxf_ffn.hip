@@ -22,8 +22,6 @@ namespace {
 
 using namespace sx;
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 constexpr float SA = 256.0f, SW = 1024.0f, UNSCALE = 1.0f / (256.0f * 1024.0f);      // operand scales (activations, weights; encoder.hip packs the images with SW)
 constexpr int ROW2 = 80;                                         // bytes per W2 image row in LDS: 32 hidden units (64 B) + 16
 

@@ -82,7 +82,7 @@ def front_route(plan, opts, ragged):
     route = {"fuse_chain": opts.get("fuse_chain", 1)}
     if plan.sub_layers == 2:                                                  # conv2.hip + gemm.hip; the ragged form runs on the rectangle and gathers
         return dict(route, conv="fp32", subsample=True)
-    sub3 = D0 % 4 == 0 and D0 <= 384 and (fuse == 3 or (fuse == 2 and auto and (C0 > 128 or D0 > 128)))          # use_sublinear3, sublinear3_tiles
+    sub3 = D0 % 4 == 0 and D0 <= 384 and (fuse == 3 or (fuse == 2 and auto and (C0 > 128 or D0 > 128)))          # use_sublinear3, sub_chunked_tiles
     sub2 = fuse >= 2 and F == 80 and D0 % 4 == 0 and ((C0 <= 128 and D0 <= 128) or (C0 <= 192 and D0 <= 192))      # sublinear2_groups
     if sub3 or sub2:
         return dict(route, conv="split", subsample=False)

@@ -68,6 +68,15 @@ STAY_AT_ZERO = [
     ("chain.hip", "chain_kernel<8, 4, 2, 1, false>", 2, 0),
     ("chain2.hip", "chain2_kernel<16, false>", 2, 0),
     ("attention2.hip", "relpos_attention2_kernel<96, 4, 1, 1>", 2, 0),
+    # the chunked front end (sub_chunked.h) in its two formats: the occupancies the 1 / 4 / 6 / 12-tile instances had as two separate kernels
+    ("sublinear3.hip", "sublinear3_kernel<1>", 5, 0),
+    ("sublinear3.hip", "sublinear3_kernel<4>", 3, 0),
+    ("sublinear3.hip", "sublinear3_kernel<6>", 2, 0),
+    ("sublinear3.hip", "sublinear3_kernel<12>", 1, 0),
+    ("sxf_sub.hip", "sxf_sublin_kernel<1>", 4, 0),
+    ("sxf_sub.hip", "sxf_sublin_kernel<4>", 2, 0),
+    ("sxf_sub.hip", "sxf_sublin_kernel<6>", 1, 0),
+    ("sxf_sub.hip", "sxf_sublin_kernel<12>", 1, 0),
 ]
 # instances that carry scratch today, or are newer than the lists above: their occupancy and an upper bound on their scratch (a bound, not an equality: less is
 # welcome).  The bounds are the ones set when the chains' shared pieces moved into chain_common.h; measured at that commit, before and after alike

@@ -4,6 +4,7 @@ requested and - with a trace arena attached - the ordered list of trace entries 
     python tools/forward_digest.py                    # the whole table
     python tools/forward_digest.py --compact          # the trace list folded into its count and one SHA-256 (the form kept in profiles/)
     python tools/forward_digest.py Tiny               # the cases of one model
+    python tools/forward_digest.py --front-end        # only the front-end cases (front_end_cases)
 
 Checking a change of the host side (csrc/encoder.hip, forward_*.hip): run this on the tree before and on the tree after ON THE SAME GPU and compare the lines; a
 forward that enqueues the same kernels with the same arguments in the same order gives the same bytes.  Weights: the recipe of tools/pack_digest.py; inputs:
@@ -160,6 +161,19 @@ def context_cases():
     return out
 
 
+def front_end_cases():
+    """(model, precision, [(label, options)]): every route of the bf16 front-end dispatcher and all four tile counts (1 / 4 / 6 / 12) of both chunked front-end
+    kernels (sublinear3.hip, sxf_sub.hip); each case runs rectangular and ragged with a trace (split: trace_fused, so the fused kernel is what runs)."""
+    sub = lambda fuse, auto=1: {"fuse_subsample": fuse, "sub3_auto": auto}
+    out = [("EfficientConformerCTCSmall", "bf16", [("fuse_subsample=%d" % f, sub(f)) for f in (0, 1, 2, 3)]),
+           ("EfficientConformerCTCMedium", "bf16", [("sub3_auto=%d" % a, sub(2, a)) for a in (0, 1)]),
+           ("EfficientConformerCTCLarge", "bf16", [("defaults", {})]),
+           ("Tiny", "bf16", [("fuse_subsample=3", sub(3))]),
+           ("ConformerCTCSmall", "bf16", [("two layers", {})])]
+    out += [(m, "split", [("fused front end", {"trace_fused": 1})]) for m in ("Tiny", "EfficientConformerCTCSmall", "EfficientConformerCTCMedium", "EfficientConformerCTCLarge")]
+    return out
+
+
 def emit(compact: bool, head: dict, res: dict):
     if compact and "trace" in res:
         t = res.pop("trace")
@@ -172,7 +186,7 @@ def main(argv):
     only = [a for a in argv if not a.startswith("--")]
     lib = _lib.load()
     for model in MODELS:
-        if only and model not in only:
+        if "--front-end" in argv or (only and model not in only):
             continue
         for precision in pack_digest.PRECISIONS:
             hd = Handle(lib, model, precision)
@@ -183,7 +197,19 @@ def main(argv):
                     emit(compact, {"model": model, "precision": precision, "case": label}, forward(hd, **kw))
             finally:
                 hd.close()
-    if not only or CONTEXT_MODEL in only:
+    for model, precision, cases in front_end_cases():
+        if only and model not in only:
+            continue
+        hd = Handle(lib, model, precision)
+        try:
+            for label, opts in cases:
+                for k, v in opts.items():
+                    hd.option(k, v)
+                for ragged in (False, True):
+                    emit(compact, {"model": model, "precision": precision, "case": "front end, %s, %s" % (label, "ragged" if ragged else "rect")}, forward(hd, ragged=ragged, trace=True))
+        finally:
+            hd.close()
+    if "--front-end" not in argv and (not only or CONTEXT_MODEL in only):
         for label, precision, ctx, kw, opts in context_cases():
             hd = Handle(lib, CONTEXT_MODEL, precision, **ctx)
             try:
