@@ -6,9 +6,10 @@ csrc/.  See DESIGN.md / INTEGRATION.md.
 """
 from .config import build_plan, load_config, named_config  # noqa: F401
 from .encoders import ConformerEncoder  # noqa: F401
-from .model_ctc import Alignment, HeadMargins, ModelCTC, select_rerun  # noqa: F401
+from .model_ctc import Alignment, HeadMargins, ModelCTC, select_nbest, select_rerun  # noqa: F401
 from .transducer import Transducer, TransducerAlignment  # noqa: F401
+from .lm import LanguageModel  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .batching import FrontDoor, bucket_batches, collate_fn_pad  # noqa: F401
 
-__all__ = ["ConformerEncoder", "ModelCTC", "Alignment", "HeadMargins", "select_rerun", "Transducer", "TransducerAlignment", "load_checkpoint", "save_checkpoint", "FrontDoor", "bucket_batches", "collate_fn_pad", "build_plan", "load_config", "named_config"]
+__all__ = ["ConformerEncoder", "ModelCTC", "Alignment", "HeadMargins", "select_rerun", "select_nbest", "Transducer", "TransducerAlignment", "LanguageModel", "load_checkpoint", "save_checkpoint", "FrontDoor", "bucket_batches", "collate_fn_pad", "build_plan", "load_config", "named_config"]

@@ -31,6 +31,10 @@ class EcRnntConfig(C.Structure):
                                             "max_consec_dec_step", "joint_mode", "joint_act")]
 
 
+class EcLmConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("vocab_size", "dim_model", "num_layers")]
+
+
 # name -> (restype, argtypes); the symbol list tests/test_abi.py checks against include/effconf.h
 _P, _I32, _I64P, _F32P, _SZ = C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t
 SIGNATURES = {
@@ -71,6 +75,13 @@ SIGNATURES = {
     "effconf_rnnt_lattice": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _I64P, _I32, C.c_float, _F32P, _F32P, _P, _P, _SZ, _P]),
     "effconf_rnnt_align_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "effconf_rnnt_align": (C.c_int, [_F32P, _F32P, _I64P, _I64P, _I32, _I32, _I32, _F32P, _F32P, _P, _F32P, _P, _P, _SZ, _P]),
+    "effconf_lm_create": (_P, [C.POINTER(EcLmConfig)]),
+    "effconf_lm_destroy": (None, [_P]),
+    "effconf_lm_load_tensor": (C.c_int, [_P, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), _I32]),
+    "effconf_lm_finalize": (C.c_int, [_P]),
+    "effconf_lm_workspace_bytes": (_SZ, [_P, _I32, _I32]),
+    "effconf_lm_score": (C.c_int, [_P, _P, _I64P, _I32, _I32, C.c_float, _F32P, _F32P, _P, _P, _SZ, _P]),
+    "effconf_lm_step": (C.c_int, [_P, _P, _F32P, _F32P, _I32, _F32P, _F32P, _F32P, _P, _SZ, _P]),
     "effconf_encoder_set_option": (C.c_int, [_P, C.c_char_p, _I32]),
     "effconf_profile_enable": (C.c_int, [_P, _I32]),
     "effconf_profile_read": (C.c_int, [_P, _I32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),

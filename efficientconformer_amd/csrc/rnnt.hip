@@ -589,16 +589,6 @@ std::vector<float> kmajor4(const std::vector<float>& W, int N, int K) {
     return o;
 }
 
-// W [N][K] row-major -> float4 image [K/16][4][N]: entry (q, g, n) = W[n][16q + g], W[n][16q + 4 + g], W[n][16q + 8 + g], W[n][16q + 12 + g]
-std::vector<float> kperm16(const std::vector<float>& W, int N, int K) {
-    std::vector<float> o((size_t)N * K);
-    for (int q = 0; q < K / 16; ++q)
-        for (int g = 0; g < 4; ++g)
-            for (int n = 0; n < N; ++n)
-                for (int e = 0; e < 4; ++e) o[(((size_t)q * 4 + g) * N + n) * 4 + e] = W[(size_t)n * K + 16 * q + 4 * e + g];
-    return o;
-}
-
 const HostT* need(EcRnnt* r, const char* key, std::initializer_list<int64_t> shape, std::string& err) {
     auto it = r->host.find(key);
     if (it == r->host.end()) { err = std::string("missing tensor ") + key; return nullptr; }

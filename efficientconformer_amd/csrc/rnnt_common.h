@@ -85,6 +85,17 @@ __device__ __forceinline__ void mfma_rows16_any(const float4* __restrict__ W16, 
     else mfma_rows16_t<NTL, 1>(W16, N, K16, nrow, xs_lane, acc);
 }
 
+// W [N][K] row-major -> float4 image [K/16][4][N]: entry (q, g, n) = W[n][16q + g], W[n][16q + 4 + g], W[n][16q + 8 + g], W[n][16q + 12 + g]
+// (host; rnnt.hip and lm.hip build their MFMA weight images with it at finalize)
+inline std::vector<float> kperm16(const std::vector<float>& W, int N, int K) {
+    std::vector<float> o((size_t)N * K);
+    for (int q = 0; q < K / 16; ++q)
+        for (int g = 0; g < 4; ++g)
+            for (int n = 0; n < N; ++n)
+                for (int e = 0; e < 4; ++e) o[(((size_t)q * 4 + g) * N + n) * 4 + e] = W[(size_t)n * K + 16 * q + 4 * e + g];
+    return o;
+}
+
 // fp32 GEMM  C[m][n] = sum_k A[m][k] * B[n][k] + bias[n]   (nn.Linear semantics), K % 4 == 0 (rnnt.hip)
 int launch_sgemm_nt(const float* A, int lda, const float* Bw, int ldb, const float* bias, float* C, int ldc, int M, int N, int K, hipStream_t s);
 

@@ -6,8 +6,9 @@
 (effconf_ctc_greedy) instead of ``nn.Linear`` + a Python loop with ``.item()`` per token.
 ``beam_search_decoding`` (model_ctc.py:138-181) is ctcdecode's CTC prefix beam search without the n-gram scorer: the head's
 fp32 logits go to one persistent HIP kernel per batch (effconf_ctc_beam, one workgroup per utterance) instead of a host copy and
-8 CPU processes.  The n-gram (KenLM) terms (``ngram_path``, ``ngram_alpha``, ``ngram_beta``), neural-LM fusion, probability
-cutoffs below the shipped ones are not implemented.  Token timestamps and transcript scores come from the forced alignment instead:
+8 CPU processes.  The n-gram (KenLM) terms (``ngram_path``, ``ngram_alpha``, ``ngram_beta``), neural-LM fusion inside the search,
+probability cutoffs below the shipped ones are not implemented; a ``LanguageModel`` attached as ``lm`` rescores the search's ranked n-best after
+it (``rescore_nbest``, ``beam_labels_rescored``, ``beam_search_rescored``; csrc/lm.hip).  Token timestamps and transcript scores come from the forced alignment instead:
 ``align`` / ``greedy_alignment`` (Viterbi over the CTC trellis: which frames each token covers) and ``score_labels`` (the CTC forward
 algorithm: log P(y | x), -ctc_loss without the host copy) run on the same logits in csrc/ctc_align.hip (effconf_ctc_align).  Training
 (losses with gradients, optimizer, schedules), WER scoring and word-level (SentencePiece-merging) timestamps are out of scope (HISTORY.md).
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _targets
 from .config import load_config
 from .encoders import ConformerEncoder
 
@@ -68,6 +69,25 @@ def select_rerun(min_margin: torch.Tensor, band: float) -> torch.Tensor:
     return torch.nonzero(~(mm >= float(band)), as_tuple=False).reshape(-1)
 
 
+def select_nbest(am_score: torch.Tensor, lm_score: torch.Tensor, token_len: torch.Tensor, lm_weight: float, length_bonus: float = 0.0):
+    """The selection rule of ``ModelCTC.rescore_nbest`` on (B, beam) scores: total = am_score + lm_weight * lm_score + length_bonus * token_len
+    in fp32 (the LM term is left out at lm_weight == 0, so an LM score of -inf cannot turn it into NaN); ranks whose am_score is -inf take no
+    part; the best total wins, ties go to the lower rank (also when every rank is excluded: rank 0).  Returns (best_rank (B,) i64, total).
+    Pure torch ops on the scores' device: no model, no GPU needed."""
+    am = torch.as_tensor(am_score).float()
+    total = am.clone()
+    if lm_weight:
+        total = total + float(lm_weight) * torch.as_tensor(lm_score).to(am.device).float()
+    if length_bonus:
+        total = total + float(length_bonus) * torch.as_tensor(token_len).to(am.device).float()
+    key = torch.where(torch.isneginf(am) | torch.isnan(total), torch.full_like(total, float("-inf")), total)
+    top = key.max(dim=1, keepdim=True).values
+    beam = key.shape[1]
+    rank = torch.arange(beam, device=key.device).expand_as(key)
+    best = torch.where(key == top, rank, torch.full_like(rank, beam)).min(dim=1).values      # the first rank that holds the maximum
+    return best.clamp(max=beam - 1), total
+
+
 class ModelCTC(nn.Module):
 
     def __init__(self, encoder_params: dict, tokenizer_params: dict, training_params: Optional[dict] = None,
@@ -85,6 +105,11 @@ class ModelCTC(nn.Module):
         self.tokenizer = tokenizer
         self.name = name
         self._beam_ws = None
+        # the reference's attribute and decoding_params (model.py:70-72): a LanguageModel attached by the caller; rescoring only.  Assigning one
+        # registers it as a submodule, as in the reference: state_dict() then carries its tensors under ``lm.``
+        self.lm = None
+        self.lm_weight = float(decoding_params.get("lm_weight", 0))
+        self.lm_tmp = float(decoding_params.get("lm_tmp", 1))
         self.eval()
 
     @classmethod
@@ -409,31 +434,62 @@ class ModelCTC(nn.Module):
         ids = self.beam_labels(x, x_len, beam_size)
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
 
+    # ------------------------------------------------------------------ n-best rescoring with a neural LM
+    def rescore_nbest(self, tokens: torch.Tensor, token_len: torch.Tensor, am_score: torch.Tensor, lm=None, lm_weight: Optional[float] = None,
+                      length_bonus: float = 0.0):
+        """Rescore the ranked n-best of ``decode_logits_beam`` (tokens (B, beam, T) i32, token_len (B, beam) i32, am_score (B, beam) f32) with a
+        ``LanguageModel`` (`lm`, else ``self.lm``): all B * beam hypotheses go through csrc/lm.hip together ->
+        (best_rank (B,) i64, total (B, beam) f32, lm_score (B, beam) f32) on the device, total = am_score + lm_weight * lm_score +
+        length_bonus * token_len in fp32.  Ranks with am_score = -inf (no hypothesis) are excluded; ties go to the lower rank.  With no LM or
+        lm_weight == 0 the LM is not run: lm_score is 0 and total = am_score + length_bonus * token_len.  `lm_weight` None:
+        ``decoding_params["lm_weight"]``; the LM's temperature is ``decoding_params["lm_tmp"]``.  The hypotheses go to the LM at their
+        padded width T without a copy of the lengths to the host: positions at or beyond the longest hypothesis cost launches whose waves return
+        at once (csrc/lm.hip), no weight or state traffic."""
+        lm = self.lm if lm is None else lm
+        w = float(self.lm_weight if lm_weight is None else lm_weight)
+        if tokens.dim() != 3 or token_len.shape != tokens.shape[:2] or am_score.shape != tokens.shape[:2]:
+            raise _lib.EffconfError("n-best: tokens (B, beam, T), token_len (B, beam), am_score (B, beam); got %s, %s, %s"
+                                    % (tuple(tokens.shape), tuple(token_len.shape), tuple(am_score.shape)))
+        b, beam, t = tokens.shape
+        am = am_score.float()
+        if lm is None or w == 0.0:
+            lm_score = torch.zeros_like(am)
+        else:
+            lm_score = lm.score(tokens.reshape(b * beam, t), token_len.reshape(b * beam), lm_tmp=self.lm_tmp).reshape(b, beam)
+        best, total = select_nbest(am, lm_score, token_len, w, length_bonus)
+        return best, total, lm_score
+
+    def beam_labels_rescored(self, x: torch.Tensor, x_len: Optional[torch.Tensor], beam_size: Optional[int] = None, from_mel: bool = False,
+                             lm=None, lm_weight: Optional[float] = None, length_bonus: float = 0.0) -> List[List[int]]:
+        """``beam_labels`` with the n-best rescored by the attached LanguageModel (``rescore_nbest``): the label-id sequence of the best total
+        score per utterance.  With no LM attached or lm_weight == 0: exactly ``beam_labels``' result."""
+        lm = self.lm if lm is None else lm
+        w = float(self.lm_weight if lm_weight is None else lm_weight)
+        if lm is None or w == 0.0:
+            return self.beam_labels(x, x_len, beam_size, from_mel)
+        beam = int(self.beam_size if beam_size is None else beam_size)
+        self._check_beam(beam, self.fc.out_features)
+        logits, _, _, enc_len = self._logits(x, x_len, from_mel)
+        tokens, token_len, score = self.decode_logits_beam(logits, enc_len, beam)
+        best, _, _ = self.rescore_nbest(tokens, token_len, score, lm, w, length_bonus)
+        idx = torch.arange(tokens.shape[0], device=tokens.device)
+        tokens, token_len = tokens[idx, best].cpu(), token_len[idx, best].cpu()      # one D2H copy per batch
+        return [tokens[i, :int(token_len[i])].tolist() for i in range(tokens.shape[0])]
+
+    def beam_search_rescored(self, x, x_len, beam_size=None):
+        """``beam_search_decoding`` through ``beam_labels_rescored``: strings when a tokenizer is attached, otherwise the id lists."""
+        ids = self.beam_labels_rescored(x, x_len, beam_size)
+        return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
+
     # ------------------------------------------------------------------ forced alignment, transcript scoring
     def _targets(self, y, y_len, device):
         """(targets (B, U) i32, target_len (B,) i64) on `device` from a padded integer tensor + lengths, a list of id lists, or a list of
         strings (needs a tokenizer).  A list is padded on the host and copied once."""
-        if isinstance(y, torch.Tensor):
-            if y.dim() != 2:
-                raise _lib.EffconfError("targets must be (batch, tokens); got shape %s" % (tuple(y.shape),))
-            tg = y.to(device=device, dtype=torch.int32).contiguous()
-            if y_len is None:
-                y_len = torch.full((y.shape[0],), y.shape[1], dtype=torch.int64)
-            return tg, torch.as_tensor(y_len).to(device=device, dtype=torch.int64).contiguous()
-        rows = [[int(c) for c in r] for r in self._ids(y)]
-        lens = [len(r) for r in rows] if y_len is None else [int(v) for v in (y_len.tolist() if hasattr(y_len, "tolist") else y_len)]
-        host = np.zeros((len(rows), max([len(r) for r in rows] + [0])), dtype=np.int32)
-        for i, r in enumerate(rows):
-            host[i, :len(r)] = r
-        return torch.from_numpy(host).to(device), torch.tensor(lens, dtype=torch.int64).to(device)
+        return _targets.targets(self.tokenizer, y, y_len, device)
 
     def _ids(self, y):
         """Strings -> id lists through the tokenizer; anything else as it is."""
-        if not isinstance(y, torch.Tensor) and len(y) and isinstance(y[0], str):
-            if self.tokenizer is None:
-                raise _lib.EffconfError("string targets need a tokenizer (tokenizer.encode)")
-            return [self.tokenizer.encode(r) for r in y]
-        return y
+        return _targets.ids(self.tokenizer, y)
 
     def align_logits(self, logits: torch.Tensor, logits_len: Optional[torch.Tensor], targets, target_len=None, scores_only: bool = False):
         """Forced alignment of head logits (B, T, V) fp32 to `targets` ((B, U) integers + `target_len`, or a list of id lists) on the GPU

@@ -77,6 +77,17 @@ def head_specs(plan: EncoderPlan, vocab: int) -> List[Spec]:
     return _lin("fc", vocab, plan.dim_out)
 
 
+def lm_specs(lm_params: dict) -> List[Spec]:
+    """LanguageModel state_dict (reference lm.py:39-47: ``decoder`` = RnnDecoder -> ``decoder.embedding`` / ``decoder.rnn`` of num_layers layers,
+    ``fc``), arch "RNN"."""
+    v, h = int(lm_params["vocab_size"]), int(lm_params["dim_model"])
+    out: List[Spec] = [("decoder.embedding.weight", (v, h), EMB)]
+    for l in range(int(lm_params["num_layers"])):
+        out += [("decoder.rnn.weight_ih_l%d" % l, (4 * h, h), W), ("decoder.rnn.weight_hh_l%d" % l, (4 * h, h), W),
+                ("decoder.rnn.bias_ih_l%d" % l, (4 * h,), B), ("decoder.rnn.bias_hh_l%d" % l, (4 * h,), B)]
+    return out + _lin("fc", v, h)
+
+
 def transducer_specs(dim_encoder: int, decoder_params: dict, joint_params: dict) -> List[Spec]:
     """Prediction + joint network state_dict (reference decoders.py:46-47 -> ``decoder.embedding`` / ``decoder.rnn``;
     joint_networks.py:41-52 -> ``joint_network.linear_{encoder,decoder,joint}``), RNN decoder, one layer."""

@@ -80,6 +80,16 @@ def make_transducer_state_dict(dim_encoder: int, decoder_params: dict, joint_par
     return sd
 
 
+def make_lm_state_dict(lm_params: dict, seed: int = 0, bias=None) -> Dict[str, np.ndarray]:
+    """Key-seeded LanguageModel weights (keys ``decoder.embedding.weight``, ``decoder.rnn.*_l{k}``, ``fc.*``).  The embedding row of id 0 is zero
+    (padding_idx = 0, decoders.py:46).  ``bias``: None, or a (vocab,) array added to ``fc.bias`` - the unigram preference a trained LM has and
+    purely random weights lack (tests choose one under which rescoring moves some winners and keeps others)."""
+    sd = {key: make_tensor("lm." + key, shape, kind, seed) for key, shape, kind in P.lm_specs(lm_params)}
+    if bias is not None:
+        sd["fc.bias"] = (sd["fc.bias"] + np.asarray(bias, dtype=np.float32)).astype(np.float32)
+    return sd
+
+
 def make_mel(batch: int, n_mels: int, tm: int, lengths: List[int] | None = None, seed: int = 4321):
     """Seeded mel batch (B, n_mels, Tm) float32 + int64 mel lengths (sorted descending)."""
     g = np.random.Generator(np.random.PCG64(seed))

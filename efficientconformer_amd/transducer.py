@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _targets
 from .config import load_config
 from .encoders import ConformerEncoder
 
@@ -281,28 +281,12 @@ class Transducer(nn.Module):
     # ------------------------------------------------------------------ lattice scoring, forced alignment
     def _ids(self, y):
         """Strings -> id lists through the tokenizer; anything else as it is."""
-        if not isinstance(y, torch.Tensor) and len(y) and isinstance(y[0], str):
-            if self.tokenizer is None:
-                raise _lib.EffconfError("string targets need a tokenizer (tokenizer.encode)")
-            return [self.tokenizer.encode(r) for r in y]
-        return y
+        return _targets.ids(self.tokenizer, y)
 
     def _targets(self, y, y_len, device):
         """(targets (B, U) i32, target_len (B,) i64) on `device` from a padded integer tensor + lengths, a list of id lists, or a list of
         strings (needs a tokenizer).  A list is padded on the host and copied once."""
-        if isinstance(y, torch.Tensor):
-            if y.dim() != 2:
-                raise _lib.EffconfError("targets must be (batch, tokens); got shape %s" % (tuple(y.shape),))
-            tg = y.to(device=device, dtype=torch.int32).contiguous()
-            if y_len is None:
-                y_len = torch.full((y.shape[0],), y.shape[1], dtype=torch.int64)
-            return tg, torch.as_tensor(y_len).to(device=device, dtype=torch.int64).contiguous()
-        rows = [[int(c) for c in r] for r in self._ids(y)]
-        lens = [len(r) for r in rows] if y_len is None else [int(v) for v in (y_len.tolist() if hasattr(y_len, "tolist") else y_len)]
-        host = np.zeros((len(rows), max([len(r) for r in rows] + [0])), dtype=np.int32)
-        for i, r in enumerate(rows):
-            host[i, :len(r)] = r
-        return torch.from_numpy(host).to(device), torch.tensor(lens, dtype=torch.int64).to(device)
+        return _targets.targets(self.tokenizer, y, y_len, device)
 
     @staticmethod
     def _workspace(nbytes: int, device):

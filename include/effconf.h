@@ -321,6 +321,46 @@ int effconf_rnnt_align(const float* lp_blank, const float* lp_label, const int64
                        int32_t t_out, int32_t u_max, float* log_likelihood, float* score, int32_t* token_frame, float* token_logp,
                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LSTM language model (csrc/lm.hip): n-best rescoring and the decode step ------------------------------------------ */
+/* The reference's LanguageModel (models/lm.py:33-81, configs/LM-RNN.json): RnnDecoder = Embedding + num_layers LSTM layers of width dim_model
+ * (models/decoders.py:41-70; torch gate order i, f, g, o; b_ih + b_hh), then fc (dim_model -> vocab_size).  All arithmetic fp32 on the fp32
+ * matrix pipe.  dim_model a multiple of 16 in 16 .. 4096, 1 <= num_layers <= 4, vocab_size >= 2: anything else is refused at create. */
+typedef struct EcLmConfig {
+    int32_t vocab_size;           /* lm_params["vocab_size"] = tokenizer_params["vocab_size"]; token 0 = blank / start (lm.py:71) */
+    int32_t dim_model;            /* lm_params["dim_model"]: embedding = LSTM hidden width                                        */
+    int32_t num_layers;           /* lm_params["num_layers"]                                                                      */
+} EcLmConfig;
+
+typedef struct EcLm EcLm;
+
+EcLm* effconf_lm_create(const EcLmConfig* cfg);
+void effconf_lm_destroy(EcLm* lm);
+/* state_dict tensors (HOST fp32) by reference key: "decoder.embedding.weight", "decoder.rnn.{weight,bias}_{ih,hh}_l{k}", "fc.{weight,bias}". */
+int effconf_lm_load_tensor(EcLm* lm, const char* key, const float* host, const int64_t* shape, int32_t ndim);
+/* Builds the layer-0 input table Gin0[y] = W_ih0 emb[y] + b_ih0 + b_hh0 (the embedding row of id 0 as the checkpoint holds it) and the
+ * k-permuted weight images (W_hh0; [W_ih_l | W_hh_l] for l >= 1; fc); uploads.  A missing or mis-shaped tensor is reported before any
+ * device call. */
+int effconf_lm_finalize(EcLm* lm);
+/* Workspace of effconf_lm_score and effconf_lm_step (the latter: any u_max, e.g. 0): 256 + al(4 n) + num_layers * 3 * Np * dim_model * 4 bytes,
+ * Np = n rounded up to 64, al(x) = x rounded up to 256.  After the 256-byte aligned pointer: i32 ulen[n]; at al(4 n) per layer l the blocks
+ * h[2][Np][dim_model] (k permuted within every 16: position (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); step u reads buffer u & 1 and
+ * writes the other one for the column groups that still hold an unfinished sequence) and c[Np][dim_model].  Returns 0 for arguments the calls
+ * reject: n outside 0 .. 2^21, u_max outside 0 .. 4096, n * u_max >= 2^31. */
+size_t effconf_lm_workspace_bytes(const EcLm* lm, int32_t n, int32_t u_max);
+/* Scores n token sequences: tokens dev i32 (n, u_max), token_len dev i64 (n).  With x = [0, y_0 .. y_{U-1}] and h_u the top layer's output after
+ * x_0 .. x_u from zero state: token_logp[u] = log_softmax(fc(h_u) / lm_tmp)[y_u] for u < U (0 at or beyond U), score = their fp32 sum in
+ * ascending u (U = 0: 0).  status dev i32 (n): 0 ok; 2 a token among the first U outside 1 .. vocab_size - 1 or token_len outside 0 .. u_max -
+ * then score and the row of token_logp are -inf and the rest of the batch is untouched.  token_logp dev f32 (n, u_max) may be NULL.  Token slots
+ * at or beyond token_len never influence a result.  Step-major: per position one launch per layer and one head launch, no (n, u_max, vocab)
+ * tensor; a sequence's results are bit-identical in any batch, order, u_max and on any workspace content.  lm_tmp > 0. */
+int effconf_lm_score(EcLm* lm, const int32_t* tokens, const int64_t* token_len, int32_t n, int32_t u_max, float lm_tmp, float* token_logp,
+                     float* score, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* LanguageModel.decode(x, hidden) (lm.py:55-63): one token per sequence, tokens dev i32 (n) in 0 .. vocab_size - 1 (ids outside are clamped),
+ * h_in / c_in dev f32 (num_layers, n, dim_model) or NULL = zeros -> logits dev f32 (n, vocab_size): the raw fc outputs, no temperature;
+ * h_out / c_out (num_layers, n, dim_model), may be NULL, may alias h_in / c_in.  The same kernels as effconf_lm_score. */
+int effconf_lm_step(EcLm* lm, const int32_t* tokens, const float* h_in, const float* c_in, int32_t n, float* logits, float* h_out, float* c_out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* Options.  "cache_pos_embeddings" = 1: the positional projections E = pos_layer(R) (reference attentions.py:588, 678)
  * are input independent; they live in the workspace and are recomputed only when that workspace last held a forward of
  * another batch size or number of frames.  The library remembers one tag per workspace pointer (the 16 most recently used),

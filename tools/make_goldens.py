@@ -11,6 +11,7 @@ It refuses to run where /root/reference is absent (e.g. the GPU box).
     python tools/make_goldens.py            # regenerate every fixture
     python tools/make_goldens.py --only-rnnt-beam   # only tests/golden/rnnt_beam_*.npz (from the stored rnnt_*.npz encoder outputs)
     python tools/make_goldens.py --only-rnnt-lattice   # only tests/golden/rnnt_lattice_*.npz (from the stored rnnt_*.npz encoder outputs)
+    python tools/make_goldens.py --only-lm             # only tests/golden/lm_*.npz (LSTM language model; TinyLM's rescoring bias from tiny_T*.npz)
 """
 import os
 import sys
@@ -270,6 +271,101 @@ def rnnt_lattice_goldens():
              target_len=y_len, f_len=f_len.numpy(), lp_blank=lpb, lp_label=lpl)
 
 
+LM_MODELS = (("TinyLM", dict(arch="RNN", vocab_size=40, dim_model=32, num_layers=2), 11, (12, 0, 1, 2, 7, 12), 601),
+             ("LM257", dict(arch="RNN", vocab_size=257, dim_model=48, num_layers=3), 12, (9, 0, 1, 2, 5), 602))
+LM_RESCORE_WEIGHT = 0.5          # lm_weight of the rescoring test (tests/test_gpu_lm.py)
+
+
+def reference_lm(lm_params, sd, double):
+    """The reference's LanguageModel around its own RnnDecoder and an nn.Linear (without Model.__init__: no tokenizer file, optimizer or loss
+    here); its real ``forward`` and ``decode`` methods are called."""
+    _stub_third_party()
+    import models.decoders as dec
+    import models.lm as lm
+    obj = lm.LanguageModel.__new__(lm.LanguageModel)
+    nn.Module.__init__(obj)
+    obj.decoder = dec.RnnDecoder(lm_params)
+    obj.fc = nn.Linear(lm_params["dim_model"], lm_params["vocab_size"])
+    if sd is not None:
+        obj.load_state_dict(to_torch(sd), strict=True)
+    obj.eval()
+    return obj.double() if double else obj
+
+
+def _lm_rescore_bias(lm_params, seed):
+    """An fc bias for TinyLM under which n-best rescoring of the Tiny CTC goldens' logits (beam 16, lm_weight LM_RESCORE_WEIGHT) moves the winner of at
+    least two utterances and keeps rank 0 in at least two, every decision by more than 0.05: tests/ctc_beam_ref.py + tests/lm_ref.py on the CPU."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ctc_beam_ref
+    import lm_ref
+    nbest = []
+    for tm in (100, 47):
+        g = np.load(os.path.join(OUT, "tiny_T%d.npz" % tm))
+        for i in range(g["logits"].shape[0]):
+            r = ctc_beam_ref.beam_search(ctc_beam_ref.logp32(g["logits"][i]), int(g["out_len"][i]), 16)
+            nbest.append((r["prefixes"], r["score"]))
+    for trial in range(200):
+        rng = np.random.Generator(np.random.PCG64(7000 + trial))
+        bias = (2.0 * rng.standard_normal(lm_params["vocab_size"])).astype(np.float32)
+        sd = synth.make_lm_state_dict(lm_params, seed, bias=bias)
+        best, margin = [], []
+        for prefixes, am in nbest:
+            u = max(len(p) for p in prefixes)
+            y = np.zeros((len(prefixes), max(u, 1)), dtype=np.int64)
+            for k, p in enumerate(prefixes):
+                y[k, :len(p)] = p
+            _, lms, _ = lm_ref.token_logprobs(sd, y, [len(p) for p in prefixes])
+            total = np.where(np.isfinite(am), am + LM_RESCORE_WEIGHT * lms, -np.inf)
+            order = np.argsort(-total, kind="stable")
+            best.append(int(order[0]))
+            margin.append(total[order[0]] - total[order[1]])
+        moved, kept = sum(b != 0 for b in best), sum(b == 0 for b in best)
+        if moved >= 2 and kept >= 2 and min(margin) > 0.05:
+            print("  rescoring bias: trial %d, winners %s, smallest decision %.3f" % (trial, best, min(margin)))
+            return bias, np.asarray(best, dtype=np.int64)
+    sys.exit("make_goldens: no rescoring bias found")
+
+
+def lm_goldens():
+    """LSTM language model: the reference's own RnnDecoder + nn.Linear as LanguageModel.forward and .decode run them (lm.py:55-81), in fp32 and in
+    float64 (.double()), on synthetic weights.  Also the state-dict keys and shapes of the reference's LanguageModel for configs/LM-RNN.json
+    (built on the meta device: no 1.4 GB of weights), as bytes and integers."""
+    import json
+    with torch.device("meta"):
+        big = reference_lm(json.load(open(os.path.join(REF, "configs", "LM-RNN.json")))["lm_params"], None, False)
+    keys = list(big.state_dict().keys())
+    shapes = np.zeros((len(keys), 2), dtype=np.int64)
+    for i, k in enumerate(keys):
+        shp = tuple(big.state_dict()[k].shape)
+        shapes[i, :len(shp)] = shp
+    for name, params, seed, lens, tseed in LM_MODELS:
+        arrs = {"weight_seed": np.int64(seed), "token_seed": np.int64(tseed), "vocab_size": np.int64(params["vocab_size"]),
+                "dim_model": np.int64(params["dim_model"]), "num_layers": np.int64(params["num_layers"]),
+                "lmrnn_keys": np.frombuffer("\n".join(keys).encode(), dtype=np.uint8), "lmrnn_shapes": shapes}
+        bias = None
+        if name == "TinyLM":
+            bias, best = _lm_rescore_bias(params, seed)
+            arrs["fc_bias_extra"], arrs["rescore_best_rank"], arrs["rescore_lm_weight"] = bias, best, np.float64(LM_RESCORE_WEIGHT)
+        sd = synth.make_lm_state_dict(params, seed, bias=bias)
+        rng = np.random.default_rng(tseed)
+        y = np.zeros((len(lens), max(lens)), dtype=np.int64)
+        for i, u in enumerate(lens):
+            y[i, :u] = rng.integers(1, params["vocab_size"], u)
+        walk = rng.integers(0, params["vocab_size"], (5, 3))
+        arrs["tokens"], arrs["token_len"], arrs["walk_tokens"] = y.astype(np.int32), np.asarray(lens, dtype=np.int64), walk.astype(np.int32)
+        for tag, double in (("f32", False), ("f64", True)):
+            m = reference_lm(params, sd, double)
+            with torch.no_grad():
+                arrs["logits_" + tag] = m.forward((torch.from_numpy(y), torch.from_numpy(arrs["token_len"]), None)).numpy()
+                hidden, steps = None, []
+                for k in range(walk.shape[0]):
+                    lg, hidden = m.decode(torch.from_numpy(walk[k])[:, None], hidden)
+                    steps.append(lg[:, 0].numpy())
+            arrs["walk_logits_" + tag] = np.stack(steps)
+            arrs["walk_h_" + tag], arrs["walk_c_" + tag] = hidden[0].numpy(), hidden[1].numpy()
+        save("lm_" + name, **arrs)
+
+
 STREAMING = (("causal", dict(causal=True)), ("ctx_l20_r4", dict(left_context=20, right_context=4)),
              ("causal_l12", dict(causal=True, left_context=12)), ("ctx_l3_r0", dict(left_context=3, right_context=0)))
 
@@ -302,12 +398,15 @@ def main():
         return rnnt_beam_goldens()
     if "--only-rnnt-lattice" in sys.argv:
         return rnnt_lattice_goldens()
+    if "--only-lm" in sys.argv:
+        return lm_goldens()
     if "--only-streaming" in sys.argv:
         return streaming_goldens(enc_mod)
     rnnt_goldens(enc_mod)
     rnnt_beam_goldens()
     rnnt_lattice_goldens()
     streaming_goldens(enc_mod)
+    # lm_goldens() reads tiny_T*.npz: after section 1 below (or --only-lm on stored ones)
 
     # ---- 1. tiny config: every module output, two sequence lengths (T1 % 3 == 0 and != 0)
     for tm, lens in ((47, [47, 40, 23]), (100, [100, 77, 52])):
@@ -321,6 +420,7 @@ def main():
         lab, offs = pack_labels(greedy_reference(logits, out_len))
         arrs["labels"], arrs["label_offsets"] = lab, offs
         save("tiny_T%d" % tm, **arrs)
+    lm_goldens()
 
     # ---- 2. EfficientConformerCTCSmall, B=4, Tm=1001, ragged
     mel, ln = synth.make_mel(4, 80, 1001, [1001, 900, 800, 700], seed=4321)
