@@ -17,7 +17,7 @@
 //     second MFMA straight from registers (the 32-key contraction order is permuted consistently
 //     on both operands instead of shuffling P);
 //   * the key-padding mask is evaluated from lens[b]; fully masked key blocks are skipped;
-//   * group-reshape / head split are index arithmetic (inputs are head-major, output is (B*T, D)).
+//   * group-reshape / head split are index arithmetic (the strides of AttnParams; output is (B*T, D)).
 // All MFMA are v_mfma_f32_16x16x32_bf16, fp32 accumulation.
 #include "kernels.h"
 #include <cstdio>
@@ -35,13 +35,6 @@ __device__ __forceinline__ uint4 ld16(const bf16_t* p) {
     typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(2)));
     const u32x4_a4 v = *reinterpret_cast<const u32x4_a4*>(p);
     return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-// per-wave LDS hand-off: LDS operations of one wave execute in order, only the compiler must not reorder across it
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 
@@ -455,27 +448,9 @@ void attn_prof_dump() {
 }
 #endif
 
-__global__ void attn_pad_rows_kernel(GemmParams p, int B) {
-    // rows t in [T, Tp): Q = 0 -> Qu = u (and Qv = u + (v - u) = v in the attention kernel);  K = V = 0
-    const int Tp = p.Tg * p.G;
-    const int npad = Tp - p.T;
-    const int total = B * npad * p.D;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int nn = idx % p.D;
-        const int rest = idx / p.D;
-        const int t = p.T + rest % npad, b = rest / npad;
-        const int tq = t / p.G, toff = t - tq * p.G;
-        const int flat = toff * p.D + nn;
-        const int h = flat / p.d, x = flat - h * p.d;
-        const size_t i1 = ((size_t)(b * p.H + h) * p.Tg + tq) * p.dpad + x;
-        p.qu[i1] = f2bf(p.u[nn]);
-        p.kh[i1] = 0;
-        p.vt[i1] = 0;
-    }
-}
-
+// rows t in [T, Tp): Q = 0 -> Qu = u (and Qv = u + (v - u) = v in the attention kernel);  K = V = 0
 __global__ void attn_pad_rows_nat_kernel(GemmParams p, int B) {
-    const int Tp = p.Tg * p.G, npad = Tp - p.T;
+    const int Tp = p.Tp, npad = Tp - p.T;
     const int total = B * npad * p.D;
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const int nn = idx % p.D, rest = idx / p.D;
@@ -548,7 +523,7 @@ int launch_relpos_attention(const AttnParams& p, hipStream_t s) {
 }
 
 int launch_attn_pad_rows_nat(const GemmParams& p, int B, hipStream_t s) {
-    const int npad = p.Tg * p.G - p.T;
+    const int npad = p.Tp - p.T;
     if (npad <= 0 || B <= 0) return 0;
     const int total = B * npad * p.D;
     hipLaunchKernelGGL(attn_pad_rows_nat_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p, B);
@@ -559,14 +534,6 @@ int launch_attn_pad_rows_ragged(bf16_t* qu, bf16_t* kh, bf16_t* vt, const float*
     if (G <= 1 || rg.n <= 0) return 0;
     const int total = rg.n * (G - 1) * D;
     hipLaunchKernelGGL(attn_pad_rows_ragged_kernel, dim3((total + 255) / 256), dim3(256), 0, s, qu, kh, vt, u, D, G, rg.off, rg.len, rg.n);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-int launch_attn_pad_rows(const GemmParams& p, int B, hipStream_t s) {
-    const int npad = p.Tg * p.G - p.T;
-    if (npad <= 0 || B <= 0) return 0;
-    const int total = B * npad * p.D;
-    hipLaunchKernelGGL(attn_pad_rows_kernel, dim3((total + 255) / 256), dim3(256), 0, s, p, B);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -45,12 +45,6 @@ __device__ __forceinline__ uint4 ld16(const bf16_t* p) {       // 16-byte global
 
 __device__ __forceinline__ uint4 ld16b(const char* p) { return ld16(reinterpret_cast<const bf16_t*>(p)); }
 
-__device__ __forceinline__ void wave_sync() {                   // per-wave LDS hand-off (LDS operations of one wave execute in order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint2 lds_tr16(const char* p) {      // ds_read_b64_tr_b16
     const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));

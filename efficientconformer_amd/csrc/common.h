@@ -52,6 +52,19 @@ __device__ __forceinline__ int lane_now() {
 
 // Workgroup barrier that waits for this wave's LDS traffic only (lgkmcnt): the global loads a ring has in flight (vmcnt) stay in flight across it
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Per-wave LDS hand-off: LDS operations of one wave execute in order, only the compiler must not reorder across it
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct FastDiv32 {   // n / d by one multiply-high; exact for n * d < 2^32
+    uint32_t mul, d;
+    __host__ __device__ FastDiv32() : mul(0), d(1) {}
+    __host__ explicit FastDiv32(uint32_t dd) : mul(dd > 1 ? (uint32_t)((1ull << 32) / dd + 1) : 0), d(dd) {}
+    __device__ __forceinline__ uint32_t div(uint32_t n) const { return d == 1 ? n : __umulhi(n, mul); }
+};
 
 // Raise a kernel's dynamic-LDS limit when a launch needs more than any earlier launch of that instantiation ON THAT DEVICE (the
 // attribute is per device; one process may hold handles on several).  One static LdsAttr per launch site.

@@ -10,7 +10,7 @@ Workspace make_workspace(const EcEncoder* e, const Shapes& s, bool from_audio) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
     const size_t B = s.B;
-    size_t mx = 0, ma = 0, mh = 0, mq = 0, mvt = 0, me = 0, mg = 0, mc = 0;
+    size_t mx = 0, ma = 0, mh = 0, mq = 0, me = 0, mg = 0, mc = 0;
     std::vector<size_t> esz;
     for (size_t k = 0; k < e->blocks.size(); ++k) {
         const EcBlock& b = e->blocks[k];
@@ -21,10 +21,7 @@ Workspace make_workspace(const EcEncoder* e, const Shapes& s, bool from_audio) {
         mx = std::max(mx, std::max(Mi * D, Mo * De) * 4);
         ma = std::max(ma, std::max(Mi * ld8(D), Mo * ld8(De)) * 2);
         mh = std::max(mh, std::max(Mi * D, Mo * De) * b.ff_ratio * 2);
-        // Q / K / V: natural layout Mq rows x D; the head-major test layout needs B * H * Tg * dpad (rectangular batches only)
-        const size_t qkv = std::max(Mqk * D, s.ragged ? (size_t)0 : B * b.num_heads * Tg * dpad);
-        mq = std::max(mq, qkv * 2 + 512);     // + slack: 16-byte chunk loads may run past a row's head span
-        mvt = std::max(mvt, qkv * 2 + 512);
+        mq = std::max(mq, Mqk * D * 2 + 512);     // Q / K / V: Mq rows x D  + slack: 16-byte chunk loads may run past a row's head span
         me = std::max(me, (size_t)b.num_heads * (2 * Tg - 1) * dpad * 2);
         esz.push_back((size_t)b.num_heads * (2 * Tg - 1) * dpad * 2 + 512);
         mg = std::max(mg, Mi * ld8(De) * 2);
@@ -45,7 +42,7 @@ Workspace make_workspace(const EcEncoder* e, const Shapes& s, bool from_audio) {
     }
     w.x0 = take(mx); w.x1 = take(mx);
     w.a = take(ma); w.hbuf = take(mh);
-    w.qu = take(mq); w.kh = take(mq); w.vt = take(mvt); w.eh = take(me);
+    w.qu = take(mq); w.kh = take(mq); w.vt = take(mq); w.eh = take(me);
     w.o = take(ma); w.gbuf = take(mg); w.cbuf = take(mc); w.xs = take(ma);
     w.lens = take((e->blocks.size() + 1) * B * 4);
     if (s.ragged) {
@@ -234,23 +231,19 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         const int G = b.group_size, H = b.num_heads;
         const int Tp = ec_round_up(T, G), Tg = Tp / G, Tgp = ec_round_up(Tg, 8);
         const int d = G * D / H, dpad = ec_round_up(d, 32);
-        // Q/K/V/E layout: "natural" row-major [B*Tp][D] (16-byte row stores from the GEMM, head split = pointer arithmetic in
+        // Q/K/V/E layout: plain row-major [B*Tp][D] (16-byte row stores from the GEMM, head split = pointer arithmetic in
         // the attention kernel).  An odd grouped head width (d = 135: Medium / Large stage 0) makes the head spans only 2-byte
-        // aligned; gfx950 global loads are alignment-free, so the attention kernel reads them as they are - the head-major
-        // fallback (a scatter epilogue of 2-byte stores, 9 % of Medium's step) is kept behind the option "head_major_odd" for tests.
-        const bool head_major_odd = e->head_major_odd;
-        const bool nat = (d % 2) == 0 || !head_major_odd;
-        if (rg && !nat) return fail("ragged batches use the natural Q / K / V layout (option head_major_odd = 0)");
+        // aligned; gfx950 global loads are alignment-free, so the attention kernel reads them as they are.
         // rows (b, t) -> Q / K / V rows b * Tp + t; a ragged batch keeps every utterance's rows group-padded in the residual stream itself,
         // so the map is the identity: ONE "utterance" of M rows
         const int qT = rg ? M : T, qTp = rg ? M : Tp;
-        const bool chain_head = e->fuse_chain && W.chain_in && nat && chain_head_supported(D) && D <= e->chain_max_dim;          // FFN1 + QKV of this block as a fused chain
+        const bool chain_head = e->fuse_chain && W.chain_in && chain_head_supported(D) && D <= e->chain_max_dim;          // FFN1 + QKV of this block as a fused chain
         const bool chain_b = e->fuse_chain && W.chain_in && D <= e->chain_max_dim;                      // out-proj + LN + pointwise-1/GLU
         const bool chain_tail = e->fuse_chain && W.chain_out && chain_tail_supported(De) && De <= e->chain_max_dim;                  // pointwise-2 + FFN2 + block norm (+ next block's head)
         GemmParams p{};
         p.A = a; p.lda = ld8(D); p.W = W.qkv.w; p.ldw = W.qkv.ldw; p.bias = W.qkv.bias;
         p.M = M; p.N = 3 * D; p.K = D;
-        p.T = qT; p.G = rg ? 1 : G; p.H = H; p.D = D; p.d = d; p.dpad = dpad; p.Tg = rg ? M : Tg; p.Tgp = Tgp;
+        p.T = qT; p.Tp = qTp; p.D = D;
         p.qu = reinterpret_cast<bf16_t*>(ws + w.qu);
         p.kh = reinterpret_cast<bf16_t*>(ws + w.kh); p.vt = reinterpret_cast<bf16_t*>(ws + w.vt);
         p.u = W.u; p.v = W.v;
@@ -268,17 +261,17 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             { PROF(PC_LAYERNORM, 0, (double)M * D * 6); if (!have_a) EC_TRY(launch_layernorm(x, M, D, W.ln_ffn1.g, W.ln_ffn1.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
             EC_TRY(run_ffn(e, st, a, M, D, W.ffn1_a, W.ffn1_b, W.ffn1_bp, x, hbuf));
             // ---- Q/K/V of LN(x)   (modules.py:472-488; attentions.py:651-686)
-            const bool qkv_tiled = nat && prefer_tiled(e, M, 3 * D, D);
+            const bool qkv_tiled = prefer_tiled(e, M, 3 * D, D);
             const bool ln_fused = rs_gemm_supported(D) && !qkv_tiled;      // pre-norm computed in the QKV kernel's prologue
             if (!ln_fused) { PROF(PC_LAYERNORM, 0, (double)M * D * 6); EC_TRY(launch_layernorm(x, M, D, W.ln_att.g, W.ln_att.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
             { PROF(PC_GEMM_OTHER, 2.0 * M * 3.0 * D * D, (double)M * D * 2 + 3.0 * D * D * 2 + (double)M * D * 8);
               if (ln_fused) {
-                  if (nat) { p.W = W.qkv_nat.w; p.ldw = W.qkv_nat.ldw; p.bias = W.qkv_nat.bias; }
+                  p.W = W.qkv_nat.w; p.ldw = W.qkv_nat.ldw; p.bias = W.qkv_nat.bias;          // rows permuted inside every 32-row chunk
                   p.X = x; p.ldx = D; p.ln_g = W.ln_att.g; p.ln_b = W.ln_att.b;
-                  EC_TRY(launch_rs_gemm(p, nat ? 4 : 3, st));
+                  EC_TRY(launch_rs_gemm(p, 4, st));
               } else {
                   p.wide = e->wide_gemm;
-                  EC_TRY(launch_gemm(p, nat ? EPI_QKV_NAT : EPI_QKV, st));
+                  EC_TRY(launch_gemm(p, EPI_QKV_NAT, st));
               } }
         }
         trace_block(e, st, k, "x_ffn1", x, M, D, D, 0);
@@ -287,7 +280,7 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         {
             { PROF(PC_MISC, 0, 0);
               if (rg) EC_ABL(64, EC_TRY(launch_attn_pad_rows_ragged(p.qu, p.kh, p.vt, W.u, D, G, br.rows_at(k), st)));
-              else EC_TRY(nat ? launch_attn_pad_rows_nat(p, B, st) : launch_attn_pad_rows(p, B, st)); }
+              else EC_TRY(launch_attn_pad_rows_nat(p, B, st)); }
             // positional embeddings E = pos_layer(R) (attentions.py:588 / 678): input independent, tiny (2Tp-G rows)
             GemmParams pe{};
             // relative tables: R[m] = sinusoid(Tp - 1 - G/2 - m), m < 2 Tp - G; causal: R[m] = sinusoid(Tp - 1 - m), m < Tp (attentions.py:1243-1251, 1296-1309)
@@ -295,43 +288,38 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             pe.A = W.pos_table + (size_t)(b.max_pos - Tp + (c.causal ? 0 : G / 2)) * ld8(D); pe.lda = ld8(D);
             pe.W = W.pos.w; pe.ldw = W.pos.ldw; pe.bias = W.pos.bias;
             pe.M = erows; pe.N = D; pe.K = D;
-            pe.T = erows; pe.G = G; pe.H = H; pe.D = D; pe.d = d; pe.dpad = dpad; pe.Tg = c.causal ? Tg : 2 * Tg - 1; pe.Tgp = 0;
-            pe.kh = reinterpret_cast<bf16_t*>(ws + w.eh_blk[k]);
-            pe.C = pe.kh; pe.ldc = D;
+            bf16_t* eh = reinterpret_cast<bf16_t*>(ws + w.eh_blk[k]);
+            pe.C = eh; pe.ldc = D;
             if (Tp > b.max_pos) return fail("sequence longer than max_pos_encoding");
             if (!e_cached) { PROF(PC_GEMM_OTHER, 2.0 * erows * (double)D * D, (double)erows * D * 4 + (double)D * D * 2);
-                             EC_TRY(launch_gemm(pe, nat ? EPI_BF16 : EPI_HEADS, st)); }
-            if (e->trace_arena && nat) {    // the attention kernel's operands, natural layout: rows b Tp + t (ragged: the group-padded row space), pad rows filled; E rows m < erows
+                             EC_TRY(launch_gemm(pe, EPI_BF16, st)); }
+            if (e->trace_arena) {    // the attention kernel's operands: rows b Tp + t (ragged: the group-padded row space), pad rows filled; E rows m < erows
                 const int64_t qrows = rg ? (int64_t)M : (int64_t)B * Tp;
                 trace_block(e, st, k, "qu", p.qu, qrows, D, D, 1);
                 trace_block(e, st, k, "k", p.kh, qrows, D, D, 1);
                 trace_block(e, st, k, "v", p.vt, qrows, D, D, 1);
-                trace_block(e, st, k, "e", pe.kh, erows, D, D, 1);
+                trace_block(e, st, k, "e", eh, erows, D, D, 1);
             }
             AttnParams ap{};
-            ap.qu = p.qu; ap.kh = p.kh; ap.vt = p.vt; ap.eh = pe.kh;
+            ap.qu = p.qu; ap.kh = p.kh; ap.vt = p.vt; ap.eh = eh;
             ap.dvu = W.dvu; ap.dvu_ld = W.dvu_ld;
             ap.lens = br.lens_at(k);
             ap.B = B; ap.H = H; ap.T = T; ap.G = G; ap.D = D; ap.d = d; ap.dpad = dpad; ap.Tg = Tg; ap.Tgp = Tgp;
-            if (nat) { ap.q_bstride = (long long)Tp * D; ap.q_hstride = d; ap.q_rowstride = G * D; ap.e_hstride = d; ap.e_rowstride = G * D; }
-            else { ap.q_bstride = (long long)H * Tg * dpad; ap.q_hstride = (long long)Tg * dpad; ap.q_rowstride = dpad;
-                   ap.e_hstride = (long long)(2 * Tg - 1) * dpad; ap.e_rowstride = dpad; }
+            ap.q_bstride = (long long)Tp * D; ap.q_hstride = d; ap.q_rowstride = G * D; ap.e_hstride = d; ap.e_rowstride = G * D;
             ap.out = o; ap.ldo = ld8(D); ap.scale = 1.0f / std::sqrt((float)d);
             const Band bd = band(c, mask_stride, G);
             ap.band_l = bd.l; ap.band_r = bd.r;
             ap.causal = c.causal;
             const bool streaming = c.causal || ap.band_l < Tg || ap.band_r < Tg;
-            if (streaming && !(nat && relpos_attention2_supported(dpad) && e->attention_v2))
-                return fail("streaming contexts / causal attention run on attention2.hip (natural layout, padded head width <= 160, option attention_v2 != 0)");
+            if (streaming && !(relpos_attention2_supported(dpad) && e->attention_v2))
+                return fail("streaming contexts / causal attention run on attention2.hip (padded head width <= 160, option attention_v2 != 0)");
             if (rg) {
                 if (!relpos_attention2_supported(dpad)) return fail("ragged batches need attention2.hip (padded head width <= 160)");
                 ap.rag_off = br.off_at(k); ap.rag_wg = br.wg_off + (size_t)k * (B + 1); ap.rag_nwg = s.wgs[k]; ap.rag_tgmax = Tg;
             }
             { PROF(PC_ATTENTION, 2.0 * H * (rg ? s.tg2[k] : (double)B * Tg * Tg) * d * 3.0, (double)M * D * 2 * 5);
               if (rg || streaming) EC_ABL(1, EC_TRY(launch_relpos_attention2(ap, 1, st))); else
-              // attention2.hip reads the natural layout only (its column masks assume the next head's finite data behind a head span); the
-              // head-major test layout of odd head widths (EFFCONF_HEAD_MAJOR_ODD) stays on attention.hip
-              if (e->attention_v2 && nat && relpos_attention2_supported(dpad)) EC_TRY(launch_relpos_attention2(ap, e->attention_v2, st));
+              if (e->attention_v2 && relpos_attention2_supported(dpad)) EC_TRY(launch_relpos_attention2(ap, e->attention_v2, st));
               else EC_TRY(launch_relpos_attention(ap, st)); }
             if ((int)e->att_out.size() == nb && e->att_out[k]) {       // opt-in: the reference's att_w of this block (encoders.py:129)
                 // ragged batches: (B, H, Tg of the LONGEST utterance, same) per block, an utterance's own Tg x Tg block = its map run alone, zeros elsewhere
@@ -380,7 +368,7 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             bool next_head = false;
             if (!last) {
                 const EcBlock& nbk = e->blocks[k + 1];
-                next_head = W.cc_full && nbk.dim_model <= e->chain_max_dim && e->bw[k + 1].chain_in && chain_full_supported(De, pair_on(e, De) ? 256 : e->chain_full_max) && (((nbk.group_size * nbk.dim_model / nbk.num_heads) % 2) == 0 || !head_major_odd) && nbk.dim_model == De;
+                next_head = W.cc_full && nbk.dim_model <= e->chain_max_dim && e->bw[k + 1].chain_in && chain_full_supported(De, pair_on(e, De) ? 256 : e->chain_full_max) && nbk.dim_model == De;
             }
             ChainParams cp{};
             cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;

@@ -5,14 +5,14 @@
 // Replaces every nn.Linear / pointwise Conv1d on the hot path of the reference
 // (models/layers.py:57-67, 122-136; call sites modules.py:378-382, 502-508, attentions.py:57-60, 471;
 // encoders.py:116) together with the element-wise op that follows it (Swish, GLU, residual add,
-// +u/+v and the (B,T,D)->(B,H,T/G,d) head split of attentions.py:674-686).
+// +u of attentions.py:674-686; the head split is index arithmetic in the attention kernels).
 //
 // Tiling: 128 x BN x 64 block tile, 4 waves (2x2), each wave 64 x BN/2 built from
 // v_mfma_f32_32x32x16_bf16; register-staged global->LDS double buffer with one barrier per k-tile;
 // LDS rows padded by 16 B (row stride 144 B = 9 x 16 B slots, conflict-free for ds_read_b128).
 // M is large (B*T), N and K are small/odd multiples of 4: A tail chunks are masked in registers,
 // weights are zero-padded once at pack time.
-#include "kernels.h"
+#include "gemm_epilogue.h"
 
 namespace {
 
@@ -20,17 +20,10 @@ constexpr int BM = 128;
 constexpr int BK = 64;
 constexpr int LROW = BK * 2 + 16;   // bytes per LDS row
 
-struct FastDiv {   // exact for n * d < 2^32
-    uint32_t mul, d;
-    __host__ __device__ FastDiv() : mul(0), d(1) {}
-    __host__ explicit FastDiv(uint32_t dd) : mul(dd > 1 ? (uint32_t)((1ull << 32) / dd + 1) : 0), d(dd) {}
-    __device__ __forceinline__ uint32_t div(uint32_t n) const { return d == 1 ? n : __umulhi(n, mul); }
-};
-
 struct GemmDev {
     GemmParams p;
-    FastDiv fG, fD, fd;
-    bool staged;          // bf16 row outputs leave through the LDS-staged 16-byte-piece epilogue (alignment checked by launch_gemm)
+    FastDiv32 fD;         // EPI_QKV_NAT: stacked Q | K | V column -> tensor
+    bool staged;          // the output leaves through the LDS-staged 16-byte-piece epilogue (gemm_staged_ok)
 };
 
 template <int BN, int EPI>
@@ -155,120 +148,16 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmDev gd) {
 
     // ---- epilogue.  C layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
     const int lcol = lane & 31, lrow = 4 * (lane >> 5);
-    if ((EPI == EPI_BF16 || EPI == EPI_SWISH_BF16 || EPI == EPI_QKV_NAT) && gd.staged) {
-        // bf16 row outputs: the wave's 64 x BN/2 tile goes through LDS (the operand buffers are free now) and leaves as 16-byte
-        // pieces, 64-128 contiguous bytes per row and 8-16 rows per store instruction.  One 2-byte global store per element (64
-        // store instructions per wave, each touching two 64-byte row fragments) was half of the kernel (s_memtime phases: 51 %).
-        constexpr int WCOLS = BN / 2, PITCH = WCOLS * 2 + 16, PPR = WCOLS / 8, RPI = 64 / PPR;
-        __syncthreads();                                   // every wave is done with the last k-tile
-        char* wbuf = smem + wave * 64 * PITCH;
-        static_assert(4 * 64 * PITCH <= 2 * (BM + BN) * LROW, "staging fits the operand buffers");
-#pragma unroll
-        for (int ni = 0; ni < NF; ++ni) {
-            const int n = n0 + wn * WCOLS + ni * 32 + lcol;
-            const int nc = n < p.N ? n : p.N - 1;
-            float add = p.bias[nc];
-            if constexpr (EPI == EPI_QKV_NAT) { const int which = gd.fD.div(nc); if (which == 0) add += p.u[nc]; }
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float val = acc[mi][ni][r] + add;
-                    if constexpr (EPI == EPI_SWISH_BF16) val = swishf_(val);
-                    if (n >= p.N) val = 0.f;               // pad columns of the row buffers stay zero
-                    const int row = mi * 32 + (r & 3) + 8 * (r >> 2) + lrow;
-                    *reinterpret_cast<bf16_t*>(wbuf + row * PITCH + (ni * 32 + lcol) * 2) = f2bf(val);
-                }
+    if constexpr (EPI != EPI_F32) {
+        if (gd.staged) {       // gemm_epilogue.h: all 64 rows of the wave's tile staged at once
+            constexpr int STAGE = 64 * EpiStage<NF, EPI>::PITCH;
+            static_assert(4 * STAGE <= 2 * (BM + BN) * LROW, "staging fits the operand buffers");
+            __syncthreads();                                   // every wave is done with the last k-tile
+            staged_epilogue<NF, EPI, 64>(acc, p, gd.fD, smem + wave * STAGE, m0 + wm * 64, n0 + wn * (BN / 2), lane);
+            return;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int piece = lane % PPR, prow = lane / PPR;
-        const int nb = n0 + wn * WCOLS + piece * 8;       // first column of this lane's 8-column piece
-        const int Tp = p.Tg * p.G;
-#pragma unroll
-        for (int it = 0; it < 64 / RPI; ++it) {
-            const int row = it * RPI + prow, m = m0 + wm * 64 + row;
-            const uint4 v = *reinterpret_cast<const uint4*>(wbuf + row * PITCH + piece * 16);
-            if (m >= p.M) continue;
-            if constexpr (EPI == EPI_QKV_NAT) {
-                if (nb >= p.N) continue;                   // D % 8 == 0 (checked by the launcher): a piece never straddles Q | K | V
-                const int which = gd.fD.div(nb), nn = nb - which * p.D;
-                const int b = m / p.T, t = m - b * p.T;
-                bf16_t* dst = which == 1 ? p.kh : (which == 2 ? p.vt : p.qu);
-                *reinterpret_cast<uint4*>(dst + ((size_t)b * Tp + t) * p.D + nn) = v;
-            } else {
-                if (nb < p.ldc) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + nb) = v;
-            }
-        }
-        return;
     }
-    if (EPI == EPI_GLU_BF16 && gd.staged) {
-        // a wave's 64 columns are (a | b) of 32 output channels: stage 64 rows x 32 channels of bf16, leave as 16-byte pieces
-        constexpr int PITCH = 32 * 2 + 16, PPR = 4, RPI = 16;
-        __syncthreads();
-        char* wbuf = smem + wave * 64 * PITCH;
-        const int jc = (n0 + wn * 64) / 2;                 // first output channel of this wave
-        const float ba = p.bias[n0 + wn * 64 + lcol], bb = p.bias[n0 + wn * 64 + 32 + lcol];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mi * 32 + (r & 3) + 8 * (r >> 2) + lrow;
-                *reinterpret_cast<bf16_t*>(wbuf + row * PITCH + lcol * 2) = f2bf((acc[mi][0][r] + ba) * sigmoidf_(acc[mi][NF - 1][r] + bb));
-            }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int piece = lane % PPR, prow = lane / PPR, jb = jc + piece * 8;
-#pragma unroll
-        for (int it = 0; it < 64 / RPI; ++it) {
-            const int row = it * RPI + prow, m = m0 + wm * 64 + row;
-            const uint4 v = *reinterpret_cast<const uint4*>(wbuf + row * PITCH + piece * 16);
-            if (m < p.M && jb < p.ldc) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + jb) = v;
-        }
-        return;
-    }
-    if (EPI == EPI_RESID_F32 && gd.staged) {
-        // fp32 residual rows: stage the wave's 64 x BN/2 tile of (acc + bias), then per 16-byte piece: residual in, sum out
-        constexpr int WCOLS = BN / 2, PITCH = WCOLS * 4 + 16, PPR = WCOLS / 4, RPI = 64 / PPR, NIT = 64 / RPI;
-        static_assert(4 * 64 * PITCH <= 2 * (BM + BN) * LROW, "staging fits the operand buffers");
-        __syncthreads();
-        char* wbuf = smem + wave * 64 * PITCH;
-#pragma unroll
-        for (int ni = 0; ni < NF; ++ni) {
-            const int n = n0 + wn * WCOLS + ni * 32 + lcol;
-            const float bias = p.bias[n < p.N ? n : p.N - 1];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = mi * 32 + (r & 3) + 8 * (r >> 2) + lrow;
-                    *reinterpret_cast<float*>(wbuf + row * PITCH + (ni * 32 + lcol) * 4) = p.alpha * (acc[mi][ni][r] + bias);
-                }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int piece = lane % PPR, prow = lane / PPR, nb = n0 + wn * WCOLS + piece * 4;
-        const int nbc = nb < p.N - 4 ? nb : p.N - 4;
-        float4 rv[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {                 // all residual pieces first (unconditional, clamped)
-            const int m = m0 + wm * 64 + it * RPI + prow;
-            rv[it] = *reinterpret_cast<const float4*>(p.R + (size_t)(m < p.M ? m : p.M - 1) * p.ldr + nbc);
-        }
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) asm volatile("" : "+v"(rv[it].x), "+v"(rv[it].y), "+v"(rv[it].z), "+v"(rv[it].w));
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) {
-            const int row = it * RPI + prow, m = m0 + wm * 64 + row;
-            const float4 a = *reinterpret_cast<const float4*>(wbuf + row * PITCH + piece * 16);
-            if (m < p.M && nb < p.N)
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + nb) = make_float4(rv[it].x + a.x, rv[it].y + a.y, rv[it].z + a.z, rv[it].w + a.w);
-        }
-        return;
-    }
+    // unstaged fallbacks (ldc, D or a pointer fails the 16-byte rules) and EPI_F32: one store per element
     if constexpr (EPI == EPI_GLU_BF16) {
         static_assert(BN == 128, "GLU needs both halves in one wave");
         const int j = (n0 + wn * 64) / 2 + lcol;           // output channel
@@ -283,40 +172,9 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmDev gd) {
                     if (m < p.M) C[(size_t)m * p.ldc + j] = f2bf((acc[mi][0][r] + ba) * sigmoidf_(acc[mi][1][r] + bb));
                 }
         }
-    } else if constexpr (EPI == EPI_QKV || EPI == EPI_HEADS) {
-        // rows m = (b, t); grouped view: t = G*tq + toff; flat = toff*D + nn; head h = flat / d, x = flat % d
-        int b0 = 0, t0 = m0 + wm * 64;
-        if (EPI == EPI_QKV) { b0 = t0 / p.T; t0 -= b0 * p.T; }
-#pragma unroll
-        for (int ni = 0; ni < NF; ++ni) {
-            const int n = n0 + wn * (BN / 2) + ni * 32 + lcol;
-            if (n >= p.N) continue;
-            int which = 1, nn = n;
-            if (EPI == EPI_QKV) { which = gd.fD.div(n); nn = n - which * p.D; }
-            const float bias = p.bias[n];
-            float bu = 0.f;
-            if (EPI == EPI_QKV && which == 0) bu = p.u[nn];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rr = mi * 32 + (r & 3) + 8 * (r >> 2) + lrow;
-                    if (m0 + wm * 64 + rr >= p.M) continue;
-                    int b = b0, t = t0 + rr;
-                    if (EPI == EPI_QKV) while (t >= p.T) { t -= p.T; ++b; }
-                    const int tq = gd.fG.div(t), toff = t - tq * p.G;
-                    const int flat = toff * p.D + nn;
-                    const int h = gd.fd.div(flat), x = flat - h * p.d;
-                    const float val = acc[mi][ni][r] + bias;
-                    const size_t idx = ((size_t)(b * p.H + h) * p.Tg + tq) * p.dpad + x;
-                    if (which == 0) p.qu[idx] = f2bf(val + bu);
-                    else if (which == 1) p.kh[idx] = f2bf(val);
-                    else p.vt[idx] = f2bf(val);
-                }
-        }
     } else if constexpr (EPI == EPI_QKV_NAT) {
         // natural layout: out[which][(b*Tp + t)][nn], which = n / D; rows m = (b, t)
-        const int Tp = p.Tg * p.G;
+        const int Tp = p.Tp;
         int b0 = (m0 + wm * 64) / p.T, t0 = (m0 + wm * 64) - b0 * p.T;
 #pragma unroll
         for (int ni = 0; ni < NF; ++ni) {
@@ -434,26 +292,7 @@ int launch_gemm(const GemmParams& p, int epi, hipStream_t s) {
     }
     GemmDev gd;
     gd.p = p;
-    {
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        gd.staged = false;
-        if (epi == EPI_BF16 || epi == EPI_SWISH_BF16) gd.staged = p.ldc % 8 == 0 && al16(p.C);
-        if (epi == EPI_QKV_NAT) gd.staged = p.D % 8 == 0 && al16(p.qu) && al16(p.kh) && al16(p.vt);
-        if (epi == EPI_GLU_BF16) gd.staged = p.ldc % 8 == 0 && al16(p.C);
-        if (epi == EPI_RESID_F32) gd.staged = p.N % 4 == 0 && p.N >= 4 && p.ldc % 4 == 0 && p.ldr % 4 == 0 && al16(p.C) && al16(p.R);
-    }
-    if (epi == EPI_QKV || epi == EPI_HEADS || epi == EPI_QKV_NAT) {
-        gd.fG = FastDiv(p.G); gd.fD = FastDiv(p.D); gd.fd = FastDiv(p.d);
-    }
-    switch (epi) {
-        case EPI_F32: return launch_bn<EPI_F32>(gd, s);
-        case EPI_BF16: return launch_bn<EPI_BF16>(gd, s);
-        case EPI_SWISH_BF16: return launch_bn<EPI_SWISH_BF16>(gd, s);
-        case EPI_RESID_F32: return launch_bn<EPI_RESID_F32>(gd, s);
-        case EPI_GLU_BF16: return launch_bn<EPI_GLU_BF16>(gd, s);
-        case EPI_QKV: return launch_bn<EPI_QKV>(gd, s);
-        case EPI_HEADS: return launch_bn<EPI_HEADS>(gd, s);
-        case EPI_QKV_NAT: return launch_bn<EPI_QKV_NAT>(gd, s);
-    }
-    return -3;
+    gd.staged = gemm_staged_ok(p, epi);       // (EPI_F32 stays unstaged in this kernel whatever the answer)
+    if (epi == EPI_QKV_NAT) gd.fD = FastDiv32(p.D);
+    return gemm_epi_dispatch(epi, [&](auto e) { return launch_bn<decltype(e)::value>(gd, s); });
 }

@@ -14,8 +14,9 @@
 //     instruction still fetches 8 whole 128-byte row segments.
 //   * K tail (K % 64 != 0, K % 8 == 0): chunks at or beyond column K are fetched from a 16-byte zero block instead of the row, so
 //     neither stale workspace bytes nor the next row's data reach the MFMA (the packed weights are zero there as well).
-//   * Epilogues leave through a per-wave LDS staging region as 16-byte pieces (bf16 rows, fp32 residual rows, GLU, natural-layout
-//     Q+u | K | V), 32 rows at a time.
+//   * Epilogues leave through a per-wave LDS staging region as 16-byte pieces (bf16 rows, fp32 residual rows, GLU, Q+u | K | V rows),
+//     32 rows at a time: the bf16 forms are gemm_epilogue.h's, shared with gemm.hip; the fp32 form is this file's own (see there).
+#include "gemm_epilogue.h"
 #include "rowstat.h"
 
 namespace {
@@ -134,92 +135,18 @@ __global__ __launch_bounds__(G_NW * 64, 2) void gemm256_kernel(const G256Dev gd)
     }
     wg_barrier();                         // the operand buffers are free: they become the staging regions below
 
-    // ---- epilogue.  C layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
-    const int lcol = lr, lrow = 4 * half;
+    // ---- epilogue: 32 rows per pass.  C layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    using ST = EpiStage<NF, EPI>;
+    char* wbuf = smem + wave * 32 * ST::PITCH;
     const int nw0 = n0 + wn * WCOLS;       // first column of this wave
-    if constexpr (EPI == EPI_BF16 || EPI == EPI_SWISH_BF16 || EPI == EPI_QKV_NAT) {
-        constexpr int PITCH = WCOLS * 2 + 16, PPR = WCOLS / 8, RPI = 64 / PPR, NIT = 32 / RPI;
-        char* wbuf = smem + wave * 32 * PITCH;
-        float add[NF];
-#pragma unroll
-        for (int ni = 0; ni < NF; ++ni) {
-            const int n = nw0 + ni * 32 + lcol, nc = n < p.N ? n : p.N - 1;
-            add[ni] = p.bias[nc];
-            if constexpr (EPI == EPI_QKV_NAT) { if (gd.fD.div(nc) == 0) add[ni] += p.u[nc]; }
-        }
-        const int piece = lane % PPR, prow = lane / PPR;
-        const int nb = nw0 + piece * 8;
-        const int Tp = p.Tg * p.G;
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-            for (int ni = 0; ni < NF; ++ni) {
-                const bool live = nw0 + ni * 32 + lcol < p.N;    // pad columns of the row buffers stay zero
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float val = acc[mi][ni][r] + add[ni];
-                    if constexpr (EPI == EPI_SWISH_BF16) val = swishf_(val);
-                    val = live ? val : 0.f;
-                    const int row = (r & 3) + 8 * (r >> 2) + lrow;
-                    *reinterpret_cast<bf16_t*>(wbuf + row * PITCH + (ni * 32 + lcol) * 2) = f2bf(val);
-                }
-            }
-            wave_sync();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int row = it * RPI + prow, m = m0 + wm * 64 + mi * 32 + row;
-                const uint4 v = *reinterpret_cast<const uint4*>(wbuf + row * PITCH + piece * 16);
-                if (m >= p.M) continue;
-                if constexpr (EPI == EPI_QKV_NAT) {
-                    if (nb >= p.N) continue;                     // D % 8 == 0 (launcher): a piece never straddles Q | K | V
-                    const int which = gd.fD.div(nb), nn = nb - which * p.D;
-                    const int b = m / p.T, t = m - b * p.T;
-                    bf16_t* dst = which == 1 ? p.kh : (which == 2 ? p.vt : p.qu);
-                    *reinterpret_cast<uint4*>(dst + ((size_t)b * Tp + t) * p.D + nn) = v;
-                } else {
-                    if (nb < p.ldc) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + nb) = v;
-                }
-            }
-            wave_sync();
-        }
-    } else if constexpr (EPI == EPI_GLU_BF16) {
-        // W rows interleaved per 32 channels (a | b): fragment pairs (2q, 2q+1) of a wave are (a, b) of 32 output channels
-        constexpr int NP = NF / 2, PITCH = NP * 64 + 16, PPR = NP * 4, RPI = 64 / PPR, NIT = 32 / RPI;
-        static_assert(NF % 2 == 0, "GLU needs both halves in one wave");
-        char* wbuf = smem + wave * 32 * PITCH;
-        float ba[NP], bb[NP];
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-            const int na = nw0 + q * 64 + lcol, nbb = na + 32;
-            ba[q] = p.bias[na < p.N ? na : p.N - 1];
-            bb[q] = p.bias[nbb < p.N ? nbb : p.N - 1];
-        }
-        const int piece = lane % PPR, prow = lane / PPR;
-        const int jb = nw0 / 2 + piece * 8;                      // first output channel of this lane's piece
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-            for (int q = 0; q < NP; ++q) {
-                const bool live = nw0 + q * 64 + lcol < p.N;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + lrow;
-                    const float val = (acc[mi][2 * q][r] + ba[q]) * sigmoidf_(acc[mi][2 * q + 1][r] + bb[q]);
-                    *reinterpret_cast<bf16_t*>(wbuf + row * PITCH + (q * 32 + lcol) * 2) = f2bf(live ? val : 0.f);
-                }
-            }
-            wave_sync();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int row = it * RPI + prow, m = m0 + wm * 64 + mi * 32 + row;
-                const uint4 v = *reinterpret_cast<const uint4*>(wbuf + row * PITCH + piece * 16);
-                if (m < p.M && jb < p.ldc) *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + jb) = v;
-            }
-            wave_sync();
-        }
-    } else {   // EPI_RESID_F32 / EPI_F32: fp32 rows, residual in and sum out per 16-byte piece
-        constexpr int PITCH = WCOLS * 4 + 16, PPR = WCOLS / 4, RPI = 64 / PPR, NIT = 32 / RPI;
-        char* wbuf = smem + wave * 32 * PITCH;
+    if constexpr (!ST::F32OUT) {
+        staged_epilogue<NF, EPI, 32>(acc, p, gd.fD, wbuf, m0 + wm * 64, nw0, lane);
+    } else {
+        // fp32 rows (EPI_F32, EPI_RESID_F32): residual in and sum out per 16-byte piece, the residual pieces of a pass loaded AHEAD of its staging writes.
+        // Kept here: through gemm_epilogue.h's fp32 form - with the loads in this place - the 256 x 256 residual launches were 2 - 8 % slower (tools/gemm_bench.py,
+        // parent and new alternating, profiles/gemm_epilogue_single_source.txt); the listings differ in register allocation only and did not explain it
+        const int lcol = lr, lrow = 4 * half;
+        constexpr int PITCH = ST::PITCH, PPR = ST::PPR, RPI = ST::RPI, NIT = 32 / RPI;
         float bias[NF];
 #pragma unroll
         for (int ni = 0; ni < NF; ++ni) { const int n = nw0 + ni * 32 + lcol; bias[ni] = p.bias[n < p.N ? n : p.N - 1]; }
@@ -262,8 +189,7 @@ int launch256_t(G256Dev& gd, hipStream_t s) {
     const GemmParams& p = gd.p;
     gd.n_tiles = (p.N + BN - 1) / BN;
     gd.m_tiles = (p.M + G_BM - 1) / G_BM;
-    constexpr int WCOLS = BN / 2;
-    constexpr int stage = G_NW * 32 * (WCOLS * 4 + 16);          // the widest (fp32) staging region
+    constexpr int stage = G_NW * 32 * EpiStage<BN / 64, EPI_F32>::PITCH;   // the widest (fp32) staging region, whatever the epilogue
     constexpr int ring = 2 * (G_BM + BN) * G_ROWB;
     const int lds = ring > stage ? ring : stage;
     static LdsAttr attr;
@@ -279,17 +205,12 @@ int launch256_bn(G256Dev& gd, int bn, hipStream_t s) {
 
 }  // namespace
 
-// what the kernel needs beyond launch_gemm's own checks: whole 16-byte k-chunks and 16-byte-aligned row / piece addresses
+// what the kernel needs beyond launch_gemm's own checks: whole 16-byte k-chunks, 16-byte-aligned operand rows, and an output that can leave staged
+// (this kernel has no other epilogue)
 bool gemm256_supported(const GemmParams& p, int epi) {
     auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     if (p.K % 8 || p.lda % 8 || p.ldw % 64 || p.ldw < ec_round_up(p.K, 64) || !al16(p.A) || !al16(p.W)) return false;
-    switch (epi) {
-        case EPI_BF16: case EPI_SWISH_BF16: case EPI_GLU_BF16: return p.ldc % 8 == 0 && al16(p.C);
-        case EPI_QKV_NAT: return p.D % 8 == 0 && al16(p.qu) && al16(p.kh) && al16(p.vt);
-        case EPI_RESID_F32: return p.N % 4 == 0 && p.N >= 4 && p.ldc % 4 == 0 && p.ldr % 4 == 0 && al16(p.C) && al16(p.R);
-        case EPI_F32: return p.N % 4 == 0 && p.N >= 4 && p.ldc % 4 == 0 && al16(p.C);
-    }
-    return false;
+    return gemm_staged_ok(p, epi);
 }
 
 // bn: 256 or 128 columns per workgroup tile
@@ -299,13 +220,5 @@ int launch_gemm256(const GemmParams& p, int epi, int bn, hipStream_t s) {
     G256Dev gd;
     gd.p = p;
     gd.fD = FastDiv32(epi == EPI_QKV_NAT ? p.D : 1);
-    switch (epi) {
-        case EPI_F32: return launch256_bn<EPI_F32>(gd, bn, s);
-        case EPI_BF16: return launch256_bn<EPI_BF16>(gd, bn, s);
-        case EPI_SWISH_BF16: return launch256_bn<EPI_SWISH_BF16>(gd, bn, s);
-        case EPI_RESID_F32: return launch256_bn<EPI_RESID_F32>(gd, bn, s);
-        case EPI_GLU_BF16: return launch256_bn<EPI_GLU_BF16>(gd, bn, s);
-        case EPI_QKV_NAT: return launch256_bn<EPI_QKV_NAT>(gd, bn, s);
-    }
-    return -3;
+    return gemm_epi_dispatch(epi, [&](auto e) { return launch256_bn<decltype(e)::value>(gd, bn, s); });
 }

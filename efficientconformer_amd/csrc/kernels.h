@@ -31,9 +31,7 @@ enum GemmEpilogue {
     EPI_SWISH_BF16 = 2,  // C bf16 [M][ldc]           = swish(acc + bias)
     EPI_RESID_F32 = 3,   // C f32 [M][ldc]            = R[m][n] + alpha * (acc + bias)   (R may alias C)
     EPI_GLU_BF16 = 4,    // C bf16 [M][ldc], N/2 cols = a * sigmoid(b); W rows interleaved in blocks of 32 (a|b)
-    EPI_QKV = 5,         // scatter to head-major Qu, Qv, K and key-major V^T (see GemmParams)
-    EPI_HEADS = 6,       // scatter a single matrix to head-major [H][rows/G][dpad]   (positional E)
-    EPI_QKV_NAT = 7,     // Q+u, Q+v, K, V as plain row-major [B*Tp][D] bf16 ("natural" layout; attention does the head split)
+    EPI_QKV_NAT = 5,     // Q+u, K, V as plain row-major [B*Tp][D] bf16 ("natural" layout; attention does the head split)
 };
 
 struct GemmParams {
@@ -44,9 +42,9 @@ struct GemmParams {
     int M, N, K;
     void* C; int ldc;
     const float* R; int ldr; float alpha;
-    // EPI_QKV / EPI_HEADS: rows m = (b, t) with t < T; grouped attention view
-    int T, G, H, D, d, dpad, Tg, Tgp;
-    bf16_t *qu, *kh, *vt;              // Q + u, K, V: [B][H][Tg][dpad] (head major) or rows (b*Tp + t)*D (natural); Q + v is derived in the attention kernel
+    // Q | K | V outputs: rows m = (b, t) with t < T go to rows b * Tp + t of D columns (Tp = T rounded up to the attention group size)
+    int T, Tp, D;
+    bf16_t *qu, *kh, *vt;              // Q + u, K, V: [B * Tp][D]; Q + v is derived in the attention kernel
     const float *u, *v;                // [D] content / position bias (attentions.py:474-475)
     // row-stationary kernels only: if X != null the A operand is LayerNorm(X[m][0..K)) (eps 1e-6, fp32 two-pass statistics)
     // computed in the prologue from the fp32 residual stream instead of being read from A
@@ -72,9 +70,8 @@ struct FfnParams {
     float alpha;
     const float *ln_g, *ln_b;          // if non-null: a = LayerNorm(X) computed in the prologue (A is ignored)
 };
-// single row-stationary GEMM (K <= 384); epi: 0 residual fp32, 1 fp32, 2 GLU bf16 (N = packed a|b rows), 3 QKV head-major
-// scatter, 4 QKV natural layout (weight rows permuted inside every 32-row chunk, see pack_linear_chunkperm)
-// (GemmParams fields as for launch_gemm; `vt` receives V in the SAME head-major row-major layout as K)
+// single row-stationary GEMM (K <= 384); epi: 0 residual fp32, 1 fp32, 2 GLU bf16 (N = packed a|b rows), 4 Q | K | V rows (weight rows
+// permuted inside every 32-row chunk, see pack_linear_chunkperm)   (GemmParams fields as for launch_gemm)
 bool rs_gemm_supported(int K);
 bool rs_gemm_resident_supported(int K, int N);   // residual / fp32 epilogues keep the whole output row in registers
 int launch_rs_gemm(const GemmParams& p, int epi, hipStream_t s);
@@ -137,11 +134,11 @@ int launch_emit_rows(const float* x, int D, const int* off, const int* len, int 
 
 // ---------------------------------------------------------------- attention  (attention.hip)
 struct AttnParams {
-    const bf16_t *qu, *kh, *vt, *eh;        // see GemmParams; eh [H][2Tg-1][dpad]
+    const bf16_t *qu, *kh, *vt, *eh;        // see GemmParams; eh: the positional rows E [2Tp-G][D]
     const float* dvu; int dvu_ld;           // (v - u) per head column [H][dvu_ld] (zero beyond d): Q + v = (Q + u) + (v - u)
     // element strides: row (b, h, tq) of Q/K/V starts at b*q_bstride + h*q_hstride + tq*q_rowstride; E row r of head h at
-    // h*e_hstride + r*e_rowstride.  head-major: (H*Tg*dpad, Tg*dpad, dpad) / ((2Tg-1)*dpad, dpad);
-    // natural [B*Tp][D]: (Tp*D, d, G*D) / (d, G*D) — a grouped row is G consecutive rows, head h is the span [h*d, (h+1)*d)
+    // h*e_hstride + r*e_rowstride.  The rows [B*Tp][D] the GEMMs write: (Tp*D, d, G*D) / (d, G*D) — a grouped row is G consecutive
+    // rows, head h is the span [h*d, (h+1)*d)
     long long q_bstride, q_hstride, e_hstride; int q_rowstride, e_rowstride;
     const int* lens;                        // [B] valid frames at this stage (keys j with G*j >= lens[b] are masked)
     int B, H, T, G, D, d, dpad, Tg, Tgp;
@@ -164,8 +161,7 @@ int launch_attention_probs(const AttnParams& p, float* att, hipStream_t s);
 bool relpos_attention2_supported(int dpad);
 int launch_relpos_attention2(const AttnParams& p, int waves, hipStream_t s);
 // rows t in [T, Tp) of the grouped view: Qu=u, Qv=v, K=V=0  (attentions.py:107-138, 671-675)
-int launch_attn_pad_rows(const GemmParams& p, int B, hipStream_t s);       // head-major buffers
-int launch_attn_pad_rows_nat(const GemmParams& p, int B, hipStream_t s);   // natural [B*Tp][D] buffers
+int launch_attn_pad_rows_nat(const GemmParams& p, int B, hipStream_t s);   // rectangular batches: rows b*Tp + t of [B*Tp][D]
 int launch_attn_pad_rows_ragged(bf16_t* qu, bf16_t* kh, bf16_t* vt, const float* u, int D, int G, const RaggedRows& rg, hipStream_t s);
 
 // ---------------------------------------------------------------- convolutions  (conv.hip)

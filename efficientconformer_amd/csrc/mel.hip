@@ -70,13 +70,6 @@ __device__ __forceinline__ void dft8(float2 (&v)[8]) {
     }
 }
 
-// LDS operations of one wave execute in order; this only stops the compiler from reordering across the hand-off
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // Diagnostic variants (V != 0, tools/mel_repro.py; the product launches V = 0, whose code and LDS layout are unchanged):
 //   V & 1  canary words in front of and behind the per-wave exchange buffers, checked when the workgroup exits (dbg[0])
 //   V & 2  every wave-level hand-off verifies itself: own writes read back (dbg[1], [3], [5]) and every exchanged value read twice

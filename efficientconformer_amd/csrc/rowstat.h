@@ -98,11 +98,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // native vector: 
 constexpr int STG_ROW = 272;
 constexpr int STG_BYTES = 32 * STG_ROW;
 
-__device__ __forceinline__ void wave_sync() {          // LDS operations of one wave execute in order; this pins the compiler
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 // window = bytes [wbyte, wbyte + 256) of rows m_base .. m_base + 31 (row pitch `pitch` bytes, `row_bytes` readable bytes per
 // row, a multiple of 16); out-of-range rows / pieces are clamped to valid addresses (their contents are never used)
 template <int OFF, int N>
@@ -233,12 +228,5 @@ template <int KS> __host__ __device__ constexpr bool ks_skip_last(int ks_valid) 
 // k-step s takes part in the products over the model width: all but the last one of a KPAD instance.  Compile-time in every (fully unrolled) loop: the dropped
 // step costs no fragment read, no MFMA and no registers for its activation fragment
 template <int KS, bool KPAD> __host__ __device__ constexpr bool kstep(int s) { return s < KS - 1 || !KPAD; }
-
-struct FastDiv32 {   // exact for n * d < 2^32
-    uint32_t mul, d;
-    __host__ __device__ FastDiv32() : mul(0), d(1) {}
-    __host__ explicit FastDiv32(uint32_t dd) : mul(dd > 1 ? (uint32_t)((1ull << 32) / dd + 1) : 0), d(dd) {}
-    __device__ __forceinline__ uint32_t div(uint32_t n) const { return d == 1 ? n : __umulhi(n, mul); }
-};
 
 }  // namespace

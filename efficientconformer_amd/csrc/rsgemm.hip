@@ -393,14 +393,13 @@ int launch_ffn_t(const FfnParams& p, hipStream_t s) {
 //   RS_F32   : y[m][n] = acc + bias[n]                          fp32   (conv_res 1x1 strided conv, blocks.py:106-110)
 //   RS_GLU   : g[m][j] = (acc_a + b_a) * sigmoid(acc_b + b_b)   bf16   (pointwise-1 + GLU, modules.py:513-514;
 //              weight rows interleaved per 32 channels: chunk 2i = a, chunk 2i+1 = b)
-//   RS_QKV   : Q+u, Q+v, K, V scattered to head-major [B][H][Tg][dpad] (attentions.py:651-686)   (odd d fallback)
-//   RS_QKV_NAT: Q+u, Q+v, K, V as plain rows [B*Tp][D] with 8-byte row-contiguous stores; the weight rows of every
+//   RS_QKV_NAT: Q+u, K, V as plain rows [B*Tp][D] (attentions.py:651-686) with 8-byte row-contiguous stores; the weight rows of every
 //              32-row chunk are permuted at pack time (row j <-> column 16(j>>4) + 8((j>>2)&1) + 4((j>>3)&1) + (j&3)) so that
 //              a lane's accumulators r = 0..7 / 8..15 are the columns 32c + 16(r>>3) + 8*half + (r&7): each 16-byte store of a
 //              lane pair fills one 32-byte sector per row (half-filled sectors doubled the HBM write traffic: profiles/r1_06)
-enum { RS_RESID = 0, RS_F32 = 1, RS_GLU = 2, RS_QKV = 3, RS_QKV_NAT = 4 };
+enum { RS_RESID = 0, RS_F32 = 1, RS_GLU = 2, RS_QKV_NAT = 4 };
 
-struct RsDev { GemmParams p; int nchunks; FastDiv32 fD, fd; };
+struct RsDev { GemmParams p; int nchunks; FastDiv32 fD; };
 
 // G = output tiles (32 columns each) accumulated in registers before they are flushed.  Flushes of the QKV / GLU
 // variants contain only stores and sit at the FRONT of an iteration (before the next DMA issue).  The counted vmcnt never
@@ -443,7 +442,7 @@ void rs_gemm_kernel(const RsDev gd) {
     // QKV epilogues: the rel-pos bias u (D floats; Q + v is derived from Q + u in the attention kernel) also lives in LDS.  Read from global inside the flush (under the
     // `which == 0` branch) every Q tile exposed one L2 round trip before its stores: ~16 of them per workgroup.
     float* su = sbet + KS * 16;
-    if constexpr (EPI == RS_QKV || EPI == RS_QKV_NAT)
+    if constexpr (EPI == RS_QKV_NAT)
         for (int i = tid; i < p.D; i += NTHR) su[i] = p.u[i];                            // visible after the first wg_barrier
     const bool fuse_ln = p.X != nullptr;
     if (fuse_ln) {
@@ -476,23 +475,14 @@ void rs_gemm_kernel(const RsDev gd) {
             xf[rt][s] = as_bf16x8(mask_chunk(raw[s], (m < p.M) ? p.K - c0 : 0));
         }
     }
-    // per-row constants of the QKV scatter
-    int qb[RT], qtq[RT], qtoff[RT];
+    // per-row constants of the Q | K | V rows
     size_t qrow[RT];
     if constexpr (EPI == RS_QKV_NAT) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
             const int m = rowm[rt] < p.M ? rowm[rt] : p.M - 1;
             const int b = m / p.T, t = m - b * p.T;
-            qrow[rt] = ((size_t)b * (p.Tg * p.G) + t) * p.D;
-        }
-    }
-    if constexpr (EPI == RS_QKV) {
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-            const int m = rowm[rt] < p.M ? rowm[rt] : p.M - 1;
-            const int b = m / p.T, t = m - b * p.T;
-            qb[rt] = b; qtq[rt] = t / p.G; qtoff[rt] = t - qtq[rt] * p.G;
+            qrow[rt] = ((size_t)b * p.Tp + t) * p.D;
         }
     }
 #pragma unroll
@@ -562,7 +552,7 @@ void rs_gemm_kernel(const RsDev gd) {
                         *reinterpret_cast<uint2*>(gr + j) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
                     }
                     }
-                } else if constexpr (EPI == RS_QKV_NAT) {
+                } else {   // RS_QKV_NAT
                     // columns 32(c0+g) + 16*half + r: two runs of 8 consecutive columns -> 16-byte stores when D % 8 == 0
                     // (a run never straddles the Q|K|V boundary), else four runs of 4 (8-byte stores)
                     if ((p.D & 7) == 0) {
@@ -604,38 +594,6 @@ void rs_gemm_kernel(const RsDev gd) {
                                     bf16_t* dst = which == 1 ? p.kh : p.vt;
                                     *reinterpret_cast<uint2*>(dst + idx) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
                                 }
-                            }
-                        }
-                    }
-                } else {   // RS_QKV
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int nl = q * 8 + half * 4, n0 = (c0 + g) * CH + nl;
-                        if (n0 >= p.N) continue;
-                        // D % 4 == 0: the 4 columns share `which`; heads may split inside the group only between pairs when d is even
-                        const int which = gd.fD.div(n0), nn0 = n0 - which * p.D;
-                        bf16_t* dst = which == 1 ? p.kh : (which == 2 ? p.vt : p.qu);
-#pragma unroll
-                        for (int i2 = 0; i2 < 4; i2 += 2) {
-                            const float v0 = acc[rt][g][q * 4 + i2] + bias[nl + i2], v1 = acc[rt][g][q * 4 + i2 + 1] + bias[nl + i2 + 1];
-                            const int flat = qtoff[rt] * p.D + nn0 + i2;
-                            const int h = gd.fd.div(flat), x = flat - h * p.d;
-                            const size_t idx = ((size_t)(qb[rt] * p.H + h) * p.Tg + qtq[rt]) * p.dpad + x;
-                            if ((p.d & 1) == 0) {
-                                if (which == 0) {
-                                    const float u0 = su[nn0 + i2], u1 = su[nn0 + i2 + 1];
-                                    *reinterpret_cast<uint32_t*>(p.qu + idx) = pack_bf2(v0 + u0, v1 + u1);
-                                } else {
-                                    *reinterpret_cast<uint32_t*>(dst + idx) = pack_bf2(v0, v1);
-                                }
-                            } else {
-                                const int flat1 = flat + 1;
-                                const int h1 = gd.fd.div(flat1), x1 = flat1 - h1 * p.d;
-                                const size_t idx1 = ((size_t)(qb[rt] * p.H + h1) * p.Tg + qtq[rt]) * p.dpad + x1;
-                                if (which == 0) {
-                                    p.qu[idx] = f2bf(v0 + su[nn0 + i2]);
-                                    p.qu[idx1] = f2bf(v1 + su[nn0 + i2 + 1]);
-                                } else { dst[idx] = f2bf(v0); dst[idx1] = f2bf(v1); }
                             }
                         }
                     }
@@ -686,7 +644,7 @@ void rs_gemm_kernel(const RsDev gd) {
 
 template <int KS, int G, int RT, int NW, int NBUF, int EPI>
 int launch_rs_t(const RsDev& gd, hipStream_t s) {
-    const int lds = NBUF * CH * KS * 32 + gd.nchunks * CH * 4 + KS * 32 * 4 + ((EPI == RS_QKV || EPI == RS_QKV_NAT) ? ((gd.p.D + 3) & ~3) * 4 : 0);
+    const int lds = NBUF * CH * KS * 32 + gd.nchunks * CH * 4 + KS * 32 * 4 + (EPI == RS_QKV_NAT ? ((gd.p.D + 3) & ~3) * 4 : 0);
     if (lds > 160 * 1024) return -4;
     if (gd.p.ldw < KS * 16) return -6;      // every weight row is read KS * 16 columns wide: the packing must be at least that wide
     if ((EPI == RS_RESID || EPI == RS_F32) && gd.nchunks > G) return -5;
@@ -745,19 +703,18 @@ int launch_ffn_fused(const FfnParams& p, hipStream_t s) {
 bool rs_gemm_supported(int K) { return K % 4 == 0 && K <= 384; }
 bool rs_gemm_resident_supported(int K, int N) { return rs_gemm_supported(K) && N <= 384; }
 
-// epi: RS_* (0 resid, 1 f32, 2 glu, 3 qkv).  W packed [>= nchunks*32][ldw >= round_up(K,64)], bias padded likewise.
+// epi: RS_* (0 resid, 1 f32, 2 glu, 4 Q | K | V rows).  W packed [>= nchunks*32][ldw >= round_up(K,64)], bias padded likewise.
 int launch_rs_gemm(const GemmParams& p, int epi, hipStream_t s) {
     if (p.M <= 0 || p.N <= 0) return 0;
     if (!rs_gemm_supported(p.K) || p.lda % 8 || p.ldw % 8) return -2;
     RsDev gd;
     gd.p = p;
     gd.nchunks = (p.N + CH - 1) / CH;
-    if (epi == RS_QKV || epi == RS_QKV_NAT) { gd.fD = FastDiv32(p.D); gd.fd = FastDiv32(p.d); }
+    if (epi == RS_QKV_NAT) gd.fD = FastDiv32(p.D);
     switch (epi) {
         case RS_RESID: return launch_rs_ks<RS_RESID>(gd, s);
         case RS_F32: return launch_rs_ks<RS_F32>(gd, s);
         case RS_GLU: return launch_rs_ks<RS_GLU>(gd, s);
-        case RS_QKV: return launch_rs_ks<RS_QKV>(gd, s);
         case RS_QKV_NAT: return launch_rs_ks<RS_QKV_NAT>(gd, s);
     }
     return -3;

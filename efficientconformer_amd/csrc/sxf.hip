@@ -28,12 +28,6 @@ constexpr int SS_ROWS = 34;                                      // 32 key rows 
 constexpr int SS_LD = 36;                                        // floats per key row of a wave's skew buffer (conflict-free: see the writer below; ds_*_b32 bank = dword mod 32 inside a 32-lane group)
 constexpr int VROW = 64 * 2 + 16;                                // bytes per row of the V^T tiles (64 keys)
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding GLOBAL load (s_waitcnt vmcnt(0)), i.e. for the next
 // tile's prefetch the moment it was issued
 

@@ -89,7 +89,9 @@ int effconf_encoder_load_tensor(EcEncoder* enc, const char* key, const float* ho
 int effconf_encoder_finalize(EcEncoder* enc);
 
 /* ---- forward ------------------------------------------------------------------------------ */
-/* Bytes of scratch a forward of this shape needs (n = samples per row if from_audio, else mel frames). */
+/* Bytes of scratch a forward of this shape needs (n = samples per row if from_audio, else mel frames).  Since the head-major layout left,
+ * the Q / K / V buffers are rows x D for rectangular batches too (as for ragged ones): the answer is smaller than it was wherever the grouped
+ * head width is no multiple of 32.  Query it; do not assume an earlier value. */
 size_t effconf_encoder_workspace_bytes(const EcEncoder* enc, int32_t batch, int32_t n, int32_t from_audio);
 /* Output frames T_out for an input of n samples / mel frames (encoders.py:139 bookkeeping). */
 int32_t effconf_encoder_out_frames(const EcEncoder* enc, int32_t n, int32_t from_audio);
@@ -393,12 +395,13 @@ int effconf_lm_step(EcLm* lm, const int32_t* tokens, const float* h_in, const fl
  *   up to the summation order (a bf16 output may move by one ulp).
  * "chain_pair" (default 5): kernel selection of the chains at padded width 256: 5 = csrc/chain3.hip for chain A and csrc/chain2.hip for chain B,
  *   0 = csrc/chain.hip everywhere (the reference; bit-identical).  Any other value is refused.
- * "chain_full_max" (widest stage that runs chain A as one kernel; set before finalize to widen), "head_major_odd" (0 / 1), "exact_attention" (0 tiled / 2 tiled with 16-row workgroups / 1 one wave per query row; fp32 mode, bit-identical): tuning / test switches of the kernel launchers that were
+ * "chain_full_max" (widest stage that runs chain A as one kernel; set before finalize to widen), "exact_attention" (0 tiled / 2 tiled with 16-row workgroups / 1 one wave per query row; fp32 mode, bit-identical): tuning / test switches of the kernel launchers that were
  *   process-global EFFCONF_* environment variables until round 2; per handle now.  (Still read from the environment, once: EFFCONF_POISON_GUARDS at
  *   create.  The in-kernel phase profilers - EFFCONF_{CHAIN,CHAIN2,CHAIN3,ATTN,FFN}_PHASES - and EFFCONF_ATTN_ABLATE exist in the tuning library of
  *   tools/build_ablate.py only.)
  * Removed options (tuning-only kernel variants; set_option now fails with "unknown option"): "chain_count_stores", "chain_variant", "chain_pair_min_d",
- *   "chain_pair_min_m", "chain_nt", "chain_w2cm", "rs_variant", "ffn_variant", "attn_waves".  No exported symbol or struct changed.
+ *   "chain_pair_min_m", "chain_nt", "chain_w2cm", "rs_variant", "ffn_variant", "attn_waves"; and "head_major_odd", the head-major [B][H][Tg][dpad] Q / K / V / E layout nothing ran any more (the attention kernels read the
+ *   rows [B*Tp][D] the GEMMs write at any alignment).  No exported symbol or struct changed.
  * "exact_fp32" (default 0): fp32-operand precision mode (csrc/exact.hip): every GEMM on fp32 MFMA, fp32 attention / convolutions,
  *   so that greedy CTC label sequences equal the reference's CPU fp32 path (model_ctc.py:99-133) wherever its top-2 logit margins
  *   exceed fp32 summation-order noise; ~10x slower than the default bf16-operand path.  Set to 1 BEFORE effconf_encoder_finalize

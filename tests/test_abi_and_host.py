@@ -401,7 +401,7 @@ def test_product_library_has_no_profiling_instance_and_no_tuning_only_option():
     assert h, lib.effconf_last_error()
     try:
         for name in ("chain_count_stores", "chain_variant", "chain_pair_min_d", "chain_pair_min_m", "chain_nt", "chain_w2cm", "rs_variant",
-                     "ffn_variant", "attn_waves"):
+                     "ffn_variant", "attn_waves", "head_major_odd"):
             assert lib.effconf_encoder_set_option(h, name.encode(), 0) != 0, name
             assert b"unknown option" in lib.effconf_last_error(), name
         for value in (1, 2, 3, 4, 6):

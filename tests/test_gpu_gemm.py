@@ -88,7 +88,7 @@ def _case(M, N, K, epi, wide, seed=0, lda_pad=0):
     assert err < tol, (M, N, K, epi, wide, err)
     if c.dtype == torch.bfloat16 and ldc > want.shape[1]:
         assert (c[:, want.shape[1]:].float() == 0).all()        # pad columns of a bf16 row buffer are written as zeros
-    return got
+    return c
 
 
 SHAPES = [(300, 512, 512), (1000, 2048, 512), (513, 720, 2880), (777, 2880, 720), (256, 256, 64), (1, 128, 360), (2049, 360, 1440),
@@ -110,10 +110,21 @@ def test_glu_epilogue_vs_fp32_reference(shape, wide):
     _case(M, N, K, GLU, wide, seed=N)
 
 
-def test_tile_choices_agree_bit_for_bit_on_fp32_outputs():
-    """Every tile shape accumulates a k-ordered chain of the same MFMA over the same 16-wide k-steps: identical fp32 results."""
-    outs = [_case(1000, 2048, 512, F32, wide, seed=3) for wide in (1, 2, 3)]
-    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+# (129, 320, 200): row tail, K tail and gemm.hip's 64-wide tile; (300, 360, 512): column tail inside a 128-wide tile; GLU: N = 2 x channels
+TILE_SHAPES = {F32: [(129, 320, 200), (300, 360, 512), (1000, 2048, 512)], BF16: [(129, 320, 200), (300, 360, 512)], SWISH: [(129, 320, 200), (300, 360, 512)],
+               RESID: [(129, 320, 200), (300, 360, 512)], GLU: [(129, 128, 200), (300, 1024, 512)]}
+
+
+def test_tile_choices_agree_bit_for_bit():
+    """Every tile shape accumulates a k-ordered chain of the same MFMA over the same 16-wide k-steps, and both tiled kernels finish it with the same
+    expressions (acc + bias, the same Swish and sigmoid, alpha * (acc + bias) staged as fp32 before the residual add): identical output buffers for every
+    epilogue, the pad columns of the bf16 row buffers included.  One test over all five epilogues (11 cases of three launches, about a second together)."""
+    for epi, shapes in TILE_SHAPES.items():
+        for M, N, K in shapes:
+            outs = [_case(M, N, K, epi, wide, seed=3) for wide in (1, 2, 3)]
+            assert outs[0].dtype == (torch.float32 if epi in (F32, RESID) else torch.bfloat16), (epi, M, N, K)
+            assert torch.equal(outs[0], outs[1]), ("256 x 256 tile differs", epi, M, N, K)
+            assert torch.equal(outs[0], outs[2]), ("256 x 128 tile differs", epi, M, N, K)
 
 
 def test_operand_row_pitch_larger_than_k_and_poisoned_tail_columns():
