@@ -4,6 +4,7 @@
 // Everything the forward path does is "enqueue kernels on the caller's stream": no allocation, no synchronisation, no host<->device copies (graph-capturable).
 #include "forward_common.h"
 #include "pack.h"
+#include "routes.h"
 
 #include <cstring>
 
@@ -138,11 +139,7 @@ int effconf_encoder_finalize(EcEncoder* e) {
     if (hipDeviceSynchronize() != hipSuccess) return fail("upload failed");
     e->host.clear();
     e->e_cache.clear();
-    {   // tiled_auto: the widest stage of the configuration decides (a property of the configuration, never of the batch: one path per handle)
-        int dmax = 0;
-        for (const EcBlock& b : e->blocks) dmax = std::max(dmax, std::max(b.dim_model, b.dim_expand));
-        e->tiled_auto_on = dmax > e->tiled_min_k && dmax <= 384;
-    }
+    e->tiled_auto_on = tiled_auto_rule(e);
     e->finalized = true;
     return 0;
 }

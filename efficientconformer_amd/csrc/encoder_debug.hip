@@ -1,28 +1,76 @@
 // The effconf_debug_* entries of include/effconf_debug.h: libeffconf_debug.so only (tests and tools), never linked into libeffconf.so.
 #include "encoder_state.h"
 #include "pack.h"
+#include "routes.h"
+
+#include <cstdio>
 #include "../../include/effconf_debug.h"
 
-extern "C" {
+namespace {
 
-int effconf_debug_pack_digest(EcEncoder* e, uint64_t* digest, int64_t* buffers, int64_t* bytes) {
-    if (!e) return fail("null encoder");
-    // The packing runs on a scratch copy of the handle that borrows the host tensors, so e itself never holds a packed pointer: it stays not finalized, and a
-    // later effconf_encoder_finalize works as if this had not run.  No HIP call: the copy owns no device buffer and upload only hashes.
+// The packing runs on a scratch copy `t` of the handle that borrows the host tensors, so e itself never holds a packed pointer: it stays not finalized, and a
+// later effconf_encoder_finalize works as if this had not run.  No HIP call: the copy owns no device buffer and upload only hashes (and returns a non-null
+// token, so "image exists" reads as after a real finalize).  then(t): what to read off the packed copy
+template <class F>
+int dry_pack(EcEncoder* e, EcEncoder::PackDigest* d, F then) {
     std::map<std::string, HostTensor> host = std::move(e->host);
     e->host.clear();
     EcEncoder t(*e);
     t.host = std::move(host);
     t.cfg.blocks = t.blocks.data();
     t.allocs.clear();
-    EcEncoder::PackDigest d;
-    t.dry = &d;
+    t.dry = d;
     const int rc = pack_encoder(&t);
     e->host = std::move(t.host);
+    if (rc == 0) { t.tiled_auto_on = tiled_auto_rule(&t); then(t); }
+    return rc;
+}
+
+const char* const kFront[] = {"two_layer", "chunked", "row_stationary", "tiled_fused", "conv_gemm"};
+const char* const kHead[] = {"prev_tail", "chain", "modules"};
+const char* const kTail[] = {"full", "tail", "modules"};
+
+}  // namespace
+
+extern "C" {
+
+int effconf_debug_pack_digest(EcEncoder* e, uint64_t* digest, int64_t* buffers, int64_t* bytes) {
+    if (!e) return fail("null encoder");
+    EcEncoder::PackDigest d;
+    const int rc = dry_pack(e, &d, [](const EcEncoder&) {});
     if (digest) *digest = d.sum;
     if (buffers) *buffers = d.buffers;
     if (bytes) *bytes = d.bytes;
     return rc;
+}
+
+int effconf_debug_routes(EcEncoder* e, int32_t ragged, char* text, size_t cap) {
+    if (!e || !text || !cap) return fail("null argument");
+    std::string out;
+    EcEncoder::PackDigest d;
+    const int rc = dry_pack(e, &d, [&](const EcEncoder& t) {
+        char ln[256];
+        const FrontScratch fs = front_scratch(&t, ragged != 0, 1, 64, 32);
+        snprintf(ln, sizeof(ln), "front %s sub=%d sub1=%d xrect=%d\n", kFront[front_route(&t, ragged != 0)], fs.sub != 0, fs.sub1 != 0, fs.xrect != 0);
+        out += ln;
+        for (size_t k = 0; k < t.blocks.size(); ++k) {
+            const EcBlock& b = t.blocks[k];
+            const BlockRoutes r = block_routes(&t, k);
+            const bool hm = r.head == HEAD_MODULES, tm = r.tail == TAIL_MODULES, bm = !r.chain_b;
+            const AttentionRoute ar = attention_route(&t, ec_round_up(b.group_size * b.dim_model / b.num_heads, 32), ragged != 0, false);      // full context
+            auto pick = [](bool applies, bool yes, const char* a, const char* n) { return !applies ? "-" : (yes ? a : n); };
+            snprintf(ln, sizeof(ln), "block %d D=%d De=%d head=%s ffn1=%s qkv=%s attention=%s b=%s outp=%s pw1=%s dw=%s res=%s tail=%s pw2=%s ffn2=%s\n", (int)k, b.dim_model,
+                     b.dim_expand, kHead[r.head], pick(hm, r.ffn1_fused, "fused", "tiled"), pick(hm, r.qkv_rs, "ln_rs", "ln+tiled"),
+                     ar.refusal ? "refused" : (ar.waves == 0 ? "attention" : (ar.waves == 1 ? "attention2/1" : "attention2/2")), r.chain_b ? "chain" : "modules",
+                     pick(bm, r.outp_rs, "rs", "tiled"), pick(bm, r.pw1_rs, "ln_rs", "ln+tiled"), r.dw_mfma && t.bw[k].dw_a ? "mfma" : "valu",
+                     pick(b.dim_model != b.dim_expand, r.res_rs, "rs", "tiled"), kTail[r.tail], pick(tm, r.pw2_rs, "rs", "tiled"), pick(tm, r.ffn2_fused, "ln_fused", "ln+tiled"));
+            out += ln;
+        }
+    });
+    if (rc) return rc;
+    if (out.size() + 1 > cap) return fail("effconf_debug_routes: text buffer too small");
+    memcpy(text, out.c_str(), out.size() + 1);
+    return 0;
 }
 
 int effconf_debug_mel(EcEncoder* e, int32_t variant, int32_t extra_lds, const float* audio, int32_t batch, int32_t n_samples, float* mel,

@@ -2,6 +2,7 @@
 // ConformerEncoder.forward (reference models/encoders.py:97-142) and ConformerBlock.forward (models/blocks.py:119-137); see DESIGN.md for the kernel map.
 // Also the per-module entries of the C ABI, which exist only on this file's helpers.
 #include "forward_common.h"
+#include "routes.h"
 
 #include <cmath>
 
@@ -28,18 +29,10 @@ Workspace make_workspace(const EcEncoder* e, const Shapes& s, bool from_audio) {
         mc = std::max(mc, Mo * ld8(De) * 2);
     }
     w.mel = take(from_audio ? B * e->cfg.n_mels * s.Tm * 4 : 0);
-    const int C = e->cfg.sub_filters[e->cfg.sub_layers - 1];
-    int F = e->cfg.n_mels; for (int i = 0; i < e->cfg.sub_layers; ++i) F /= 2;
-    const bool rag_unfused = s.ragged && !(e->fuse_subsample == 2 && e->lin_rs);        // (s.Tm = the input's row pitch in ragged batches)
-    size_t T1r = (size_t)s.T1;
-    if (s.ragged) { T1r = (size_t)s.Tm; for (int i = 0; i < e->cfg.sub_layers; ++i) T1r = (T1r - 1) / 2 + 1; }      // rows per utterance of the rectangular image
-    // scratch of the unfused front ends; ragged rows: every utterance's frames rounded up to the first block's group size
-    w.sub = take(s.ragged && !rag_unfused ? 0 : B * (T1r + (s.ragged ? e->blocks[0].group_size - 1 : 0)) * C * F * 2);
-    w.xrect = take(rag_unfused ? B * T1r * e->blocks[0].dim_model * 4 : 0);
-    {   // two-layer subsampler: channel-last layer-1 activation [B][F/2][T after layer 1][Cp]
-        const size_t tl1 = (s.Tm - 1) / 2 + 1;
-        w.sub1 = take(e->cfg.sub_layers == 2 ? B * (e->cfg.n_mels / 2) * tl1 * ec_round_up(e->cfg.sub_filters[0], 64) * 2 : 0);
-    }
+    size_t T1r = (size_t)s.T1;         // frames per utterance after the subsampling at the input's row pitch (ragged: s.Tm is that pitch, s.T1 the longest utterance's)
+    if (s.ragged) { T1r = (size_t)s.Tm; for (int i = 0; i < e->cfg.sub_layers; ++i) T1r = (T1r - 1) / 2 + 1; }
+    const FrontScratch fs = front_scratch(e, s.ragged, B, (size_t)s.Tm, T1r);
+    w.sub = take(fs.sub); w.xrect = take(fs.xrect); w.sub1 = take(fs.sub1);
     w.x0 = take(mx); w.x1 = take(mx);
     w.a = take(ma); w.hbuf = take(mh);
     w.qu = take(mq); w.kh = take(mq); w.vt = take(mq); w.eh = take(me);
@@ -71,26 +64,22 @@ int run_gemm(EcEncoder* e, int cls, hipStream_t st, const bf16_t* A, int lda, in
     return launch_gemm(p, epi, st);
 }
 
-// x += alpha * FFN(a)  — fused row-stationary kernel when the width allows, else two tiled GEMMs
-// ln != null: the pre-norm is computed inside the fused kernel's prologue (a is not read); the tiled fallback needs `a`
 inline int F1c(const EcBlock& b) { return ec_round_up(b.dim_model * b.ff_ratio, 32); }
 
-// POST half of a chain A: the block's FFN1 (pre-norm ln[2]), attention pre-norm ln[3] and stacked Q/K/V projection
+// POST half of a chain A: the block's FFN1 and stacked Q/K/V projection (both pre-norms folded into the weights at pack time)
 void fill_chain_head(ChainParams& cp, const BlockW& W, int D, int Fp, int T, int Tp, const GemmParams& q) {
     cp.D = D;
-    cp.ln[2] = ChainLn{W.ln_ffn1.g, W.ln_ffn1.b};
-    cp.ln[3] = ChainLn{W.ln_att.g, W.ln_att.b};
-    cp.f[1] = ChainFfn{W.c_f1a.w, W.c_f1a.ldw, W.c_f1a.bias, W.c_f1b, W.ffn1_b.ldw, W.c_f1b2, Fp, W.c_f1b_cm};
-    cp.g1 = ChainGemm{W.c_qkv.w, W.c_qkv.ldw, W.c_qkv.bias, W.c_qkv_chunks};
+    cp.f[1] = ChainFfn{W.c_f1a.w, W.c_f1a.ldw, W.c_f1b, W.ffn1_b.ldw, Fp, W.c_f1b_cm};
+    cp.g1 = ChainGemm{W.c_qkv.w, W.c_qkv.ldw, W.c_qkv_chunks};
     cp.qu = q.qu; cp.kh = q.kh; cp.vt = q.vt; cp.u = W.u; cp.v = W.v; cp.T = T; cp.Tp = Tp;
 }
 
-bool prefer_tiled(const EcEncoder* e, int M, int N, int K);
-
-int run_ffn(EcEncoder* e, hipStream_t st, const bf16_t* a, int M, int D, const PackedLinear& L1, const PackedLinear& L2,
+// x += 1/2 FFN(a): the fused row-stationary kernel (routes.h: ffn_fused; ln != null: the pre-norm is computed in its prologue and `a` is not read), else
+// two tiled GEMMs on `a`
+int run_ffn(EcEncoder* e, hipStream_t st, bool fused, const bf16_t* a, int M, int D, const PackedLinear& L1, const PackedLinear& L2,
             const bf16_t* w2p, float* x, bf16_t* hbuf, const LNp* ln = nullptr) {
     const int F = L1.N;
-    if (ffn_fused_supported(D) && !(prefer_tiled(e, M, F, D) && !ln)) {
+    if (fused) {
         PROF(PC_GEMM_FFN, 4.0 * M * (double)D * F, (double)M * D * 10 + 4.0 * D * F);
         FfnParams p{};
         p.A = a; p.lda = ld8(D); p.X = x; p.ldx = D; p.Y = x; p.ldy = D;
@@ -104,23 +93,12 @@ int run_ffn(EcEncoder* e, hipStream_t st, const bf16_t* a, int M, int D, const P
     return run_gemm(e, PC_GEMM_FFN, st, hbuf, F, M, L2, EPI_RESID_F32, x, D, x, D, 0.5f);
 }
 
-// Widths 257 .. 384 (EfficientConformer Large stage 1, Medium stage 3) fit the row-stationary kernels, but at 24 k-steps those run one
-// wave per SIMD and stream every weight per 32-row tile: 60 - 200 TFLOP/s (profiles/r2_03_large_kernel_stats.txt).  `wide_gemm` 2 / 3
-// sends these layers to LayerNorm + the tiled GEMMs instead.  Only when forced: chosen by row count (gemm256.hip's tiles filling the
-// chip) it was -3 % kernel time on Large and wall-neutral, and it made a forward's bits depend on how the batch is split into row ranges
-// (the two paths round differently; tools/robustness_sweep.py) - the gemm.hip / gemm256.hip choice does not (bit-identical kernels).
-bool prefer_tiled(const EcEncoder* e, int M, int N, int K) {
-    (void)M; (void)N;
-    return (e->wide_gemm == 2 || e->wide_gemm == 3 || (e->wide_gemm == 0 && (e->tiled_auto == 2 || (e->tiled_auto && e->tiled_auto_on)))) && K > e->tiled_min_k && K % 8 == 0;
-}
-
-// row-stationary single GEMM when K <= 384, else the tiled kernel
-int run_rs_or_tiled(EcEncoder* e, int cls, hipStream_t st, const bf16_t* A, int lda, int M, const PackedLinear& L, int rs_epi,
+// One GEMM on the row-stationary kernel (rs: routes.h gemm_row_stat) or the tiled one.  lnX / ln: the operand is LayerNorm(lnX) - computed in the
+// row-stationary kernel's prologue, or by a LayerNorm launch into A in front of the tiled kernel
+int run_rs_or_tiled(EcEncoder* e, bool rs, int cls, hipStream_t st, const bf16_t* A, int lda, int M, const PackedLinear& L, int rs_epi,
                     int tiled_epi, void* C, int ldc, const float* R = nullptr, int ldr = 0, float alpha = 1.f,
                     const float* lnX = nullptr, const LNp* ln = nullptr) {
-    const bool ok = (rs_epi == 0 || rs_epi == 1) ? rs_gemm_resident_supported(L.K, L.N) : rs_gemm_supported(L.K);
-    if (!ok) return run_gemm(e, cls, st, A, lda, M, L, tiled_epi, C, ldc, R, ldr, alpha);
-    if (prefer_tiled(e, M, L.N, L.K)) {
+    if (!rs) {
         if (lnX && ln) { PROF(PC_LAYERNORM, 0, (double)M * L.K * 6); EC_TRY(launch_layernorm(lnX, M, L.K, ln->g, ln->b, nullptr, const_cast<bf16_t*>(A), lda, nullptr, nullptr, st)); }
         return run_gemm(e, cls, st, A, lda, M, L, tiled_epi, C, ldc, R, ldr, alpha);
     }
@@ -136,14 +114,7 @@ int run_rs_or_tiled(EcEncoder* e, int cls, hipStream_t st, const bf16_t* A, int 
 // Conv2dSubsampling (modules.py:232-249) + transpose + Linear (encoders.py:113-116): mel (B, n_mels, s.Tm) -> x fp32 (s.Min[0] rows, D0).  The one list of the bf16
 // schedule's front-end routes, for rectangular batches (rg = null: rows (b, t), B * T1) and ragged ones (rg: the batch's descriptors; x = the ragged row space).
 // sub / act1: bf16 scratch of the unfused variants (the subsampler's output rows / the two-layer subsampler's layer-1 image); xrect: ragged two-layer route only.
-// sublinear3.hip: option fuse_subsample = 3 (every one-layer front end it is built for) or 2 = the default where sublinear2.hip has no instance or runs one workgroup per
-// CU (channel counts / widths above 128); a debug trace keeps the kernels that write the "subsample" activation only when fuse_subsample = 0
-bool use_sublinear3(const EcEncoder* e) {
-    if (!e->sub3.wimg || e->cfg.sub_layers != 1) return false;
-    if (e->fuse_subsample == 3) return true;
-    return e->fuse_subsample == 2 && e->sub3_auto && (e->cfg.sub_filters[0] > 128 || e->blocks[0].dim_model > 128);
-}
-
+// The route: routes.h front_route
 int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, const Shapes& s, const BatchRows* rg, bf16_t* sub, bf16_t* act1, float* xrect, float* x) {
     const EcConfig& c = e->cfg;
     const int B = s.B, Tm = s.Tm, C0 = c.sub_filters[0], F2 = c.n_mels / 2, Ksub = C0 * F2, N = e->lin.N;
@@ -151,7 +122,8 @@ int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, const S
     const int* mel_len = rg ? rg->mel_len : nullptr;
     const double Mr = (double)s.Min[0];                            // rows of x
     const int Tl1 = (Tm - 1) / 2 + 1;                              // frames after one layer, at the input's pitch
-    if (c.sub_layers == 2) {
+    const FrontRoute route = front_route(e, rg != nullptr);
+    if (route == FRONT_TWO_LAYER) {
         // two-layer subsampler (the plain Conformer configurations).  Ragged: both convolutions and the Linear on the RECTANGULAR image at the input's pitch - layer 1
         // zero-fills every utterance's image behind its own last frame, so layer 2 sees the zero padding of the utterance run alone - then the valid rows are gathered
         // into the ragged row space
@@ -164,17 +136,17 @@ int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, const S
         trace_add(e, st, "subsample", sub, (int64_t)B * T2, F2q * C1, F2q * C1, 1);           // the RECTANGULAR image's rows (b, t)
         EC_TRY(run_gemm(e, PC_GEMM_OTHER, st, sub, F2q * C1, B * T2, e->lin, EPI_F32, rg ? xrect : x, N));
         if (rg) { PROF(PC_MISC, 0, Mr * N * 8); EC_TRY(launch_gather_rows(xrect, N, T2, r0, x, st)); }
-    } else if (use_sublinear3(e)) {                                // sublinear3.hip: workgroup = (utterance, 128 frames)
+    } else if (route == FRONT_CHUNKED) {                           // sublinear3.hip: workgroup = (utterance, 128 frames)
         PROF(PC_SUBCONV, 2.0 * 9 * Mr * Ksub + 2.0 * Mr * Ksub * N, (double)B * c.n_mels * Tm * 4 + Mr * N * 4);
         EC_TRY(launch_sublinear3(sub_chunk_params(e, e->sub3, mel, s, rg, x), st));
-    } else if (e->fuse_subsample >= 2 && e->lin_rs) {              // sublinear2.hip indexes the ragged rows itself
+    } else if (route == FRONT_ROW_STAT) {                          // sublinear2.hip indexes the ragged rows itself
         PROF(PC_SUBCONV, 2.0 * 9 * Mr * Ksub + 2.0 * Mr * Ksub * N, (double)B * c.n_mels * Tm * 4 + Mr * N * 4);
         EC_ABL(rg ? 32 : 0, EC_TRY(launch_sublinear2(mel, B, c.n_mels, Tm, s.T1, e->conv_tab, e->lin_rs, e->lin.bias, C0, N, x, N, st, rg ? &r0 : nullptr, mel_len)));
-    } else if (!rg && e->fuse_subsample && e->lin_fused) {         // sublinear.hip: rectangular batches only
+    } else if (route == FRONT_TILED_FUSED) {                       // sublinear.hip: rectangular batches only
         PROF(PC_SUBCONV, 2.0 * 9 * Mr * Ksub + 2.0 * Mr * Ksub * N, (double)B * c.n_mels * Tm * 4 + Mr * N * 4);
         EC_TRY(launch_sublinear_fused(mel, B, c.n_mels, Tm, s.T1, e->sub_w9, e->sub_b, C0, e->lin_fused, e->lin_fused_ld, e->lin.bias, N, x, N, st));
     } else {
-        // conv + GEMM (wide front ends: Large with sub3_auto = 0).  Ragged: the conv (zero padding at every utterance's own last mel frame) writes the RAGGED rows
+        // FRONT_CONV_GEMM (wide front ends: Large with sub3_auto = 0).  Ragged: the conv (zero padding at every utterance's own last mel frame) writes the RAGGED rows
         // itself (tiles behind an utterance's own end exit; group-padding rows = zeros) and the Linear runs on those rows only.  Group-padding rows of x = the Linear's
         // bias (finite; no kernel mixes them into valid rows).  Tcover >= every utterance's frames rounded up to the group size
         const int Tcover = rg ? Tl1 + e->blocks[0].group_size - 1 : s.T1;
@@ -186,9 +158,8 @@ int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, const S
     return 0;
 }
 
-static const void* dw_mfma_table(const EcEncoder* e, const uint16_t* t, int ks) { return (e->dwconv_mfma == 2 || (e->dwconv_mfma == 1 && ks == 15)) ? t : nullptr; }
-// chain launches of width D that go to chain2.hip / chain3.hip (launch_chain's rule): there the tail and the next head of chain A are one kernel up to D = 256
-static bool pair_on(const EcEncoder* e, int D) { return e->chain_pair && chain3_supported(D); }
+// the launch options every chain carries
+ChainParams chain_params(const EcEncoder* e) { ChainParams cp{}; cp.small_m = e->chain_small_m; cp.pair = e->chain_pair; return cp; }
 
 }  // namespace
 
@@ -218,14 +189,18 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
     bf16_t* gbuf = reinterpret_cast<bf16_t*>(ws + w.gbuf);
     bf16_t* cbuf = reinterpret_cast<bf16_t*>(ws + w.cbuf);
     bf16_t* xs = reinterpret_cast<bf16_t*>(ws + w.xs);
-    bool have_a = false, head_done = false;
+    bool have_a = false;
+    std::vector<BlockRoutes> routes;           // decided here, once per forward (routes.h); the loop below only reads them
+    for (int k = 0; k < nb; ++k) routes.push_back(block_routes(e, k));
     const ECache ec = e_cache_begin(e, st, ws, s, w.eh_blk[0], true);
     const bool e_cached = ec.hit;
 
+    const int wide_gemm = e->wide_gemm;        // GemmParams::wide of the tiled Q/K/V GEMM (launch_gemm only)
     int mask_stride = 1;                       // product of the strides of the blocks before block k
     for (int k = 0; k < nb; ++k) {
         const EcBlock& b = e->blocks[k];
         const BlockW& W = e->bw[k];
+        const BlockRoutes& r = routes[k];
         const int T = s.Tin[k], To = s.Tout[k], D = b.dim_model, De = b.dim_expand;      // ragged: the LONGEST utterance's frames
         const int M = (int)s.Min[k], Mo = (int)s.Mout[k];
         const int G = b.group_size, H = b.num_heads;
@@ -237,21 +212,17 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         // rows (b, t) -> Q / K / V rows b * Tp + t; a ragged batch keeps every utterance's rows group-padded in the residual stream itself,
         // so the map is the identity: ONE "utterance" of M rows
         const int qT = rg ? M : T, qTp = rg ? M : Tp;
-        const bool chain_head = e->fuse_chain && W.chain_in && chain_head_supported(D) && D <= e->chain_max_dim;          // FFN1 + QKV of this block as a fused chain
-        const bool chain_b = e->fuse_chain && W.chain_in && D <= e->chain_max_dim;                      // out-proj + LN + pointwise-1/GLU
-        const bool chain_tail = e->fuse_chain && W.chain_out && chain_tail_supported(De) && De <= e->chain_max_dim;                  // pointwise-2 + FFN2 + block norm (+ next block's head)
         GemmParams p{};
         p.A = a; p.lda = ld8(D); p.W = W.qkv.w; p.ldw = W.qkv.ldw; p.bias = W.qkv.bias;
         p.M = M; p.N = 3 * D; p.K = D;
         p.T = qT; p.Tp = qTp; p.D = D;
         p.qu = reinterpret_cast<bf16_t*>(ws + w.qu);
         p.kh = reinterpret_cast<bf16_t*>(ws + w.kh); p.vt = reinterpret_cast<bf16_t*>(ws + w.vt);
-        p.u = W.u; p.v = W.v;
-        if (head_done) {
+        p.u = W.u; p.v = W.v; p.wide = wide_gemm;
+        if (r.head == HEAD_PREV_TAIL) {
             // FFN1 and the Q/K/V projection of this block already ran inside the previous block's tail chain
-        } else if (chain_head) {
-            ChainParams cp{};
-            cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
+        } else if (r.head == HEAD_CHAIN) {
+            ChainParams cp = chain_params(e);
             fill_chain_head(cp, W, D, F1c(b), qT, qTp, p);
             cp.M = M; cp.X = x; cp.ldx = D; cp.Y = x; cp.ldy = D; cp.consts = W.cc_head;
             PROF(PC_GEMM_FFN, 2.0 * M * (double)D * (2.0 * D * b.ff_ratio + 3.0 * D), (double)M * D * 16 + 22.0 * D * D);
@@ -259,18 +230,15 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         } else {
             // ---- x += 1/2 FFN1(x)   (blocks.py:122; modules.py:385-392)
             { PROF(PC_LAYERNORM, 0, (double)M * D * 6); if (!have_a) EC_TRY(launch_layernorm(x, M, D, W.ln_ffn1.g, W.ln_ffn1.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
-            EC_TRY(run_ffn(e, st, a, M, D, W.ffn1_a, W.ffn1_b, W.ffn1_bp, x, hbuf));
-            // ---- Q/K/V of LN(x)   (modules.py:472-488; attentions.py:651-686)
-            const bool qkv_tiled = prefer_tiled(e, M, 3 * D, D);
-            const bool ln_fused = rs_gemm_supported(D) && !qkv_tiled;      // pre-norm computed in the QKV kernel's prologue
-            if (!ln_fused) { PROF(PC_LAYERNORM, 0, (double)M * D * 6); EC_TRY(launch_layernorm(x, M, D, W.ln_att.g, W.ln_att.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
+            EC_TRY(run_ffn(e, st, r.ffn1_fused, a, M, D, W.ffn1_a, W.ffn1_b, W.ffn1_bp, x, hbuf));
+            // ---- Q/K/V of LN(x)   (modules.py:472-488; attentions.py:651-686): row-stationary = the pre-norm in the kernel's prologue
+            if (!r.qkv_rs) { PROF(PC_LAYERNORM, 0, (double)M * D * 6); EC_TRY(launch_layernorm(x, M, D, W.ln_att.g, W.ln_att.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
             { PROF(PC_GEMM_OTHER, 2.0 * M * 3.0 * D * D, (double)M * D * 2 + 3.0 * D * D * 2 + (double)M * D * 8);
-              if (ln_fused) {
+              if (r.qkv_rs) {
                   p.W = W.qkv_nat.w; p.ldw = W.qkv_nat.ldw; p.bias = W.qkv_nat.bias;          // rows permuted inside every 32-row chunk
                   p.X = x; p.ldx = D; p.ln_g = W.ln_att.g; p.ln_b = W.ln_att.b;
                   EC_TRY(launch_rs_gemm(p, 4, st));
               } else {
-                  p.wide = e->wide_gemm;
                   EC_TRY(launch_gemm(p, EPI_QKV_NAT, st));
               } }
         }
@@ -311,72 +279,55 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             ap.band_l = bd.l; ap.band_r = bd.r;
             ap.causal = c.causal;
             const bool streaming = c.causal || ap.band_l < Tg || ap.band_r < Tg;
-            if (streaming && !(relpos_attention2_supported(dpad) && e->attention_v2))
-                return fail("streaming contexts / causal attention run on attention2.hip (padded head width <= 160, option attention_v2 != 0)");
+            const AttentionRoute ar = attention_route(e, dpad, rg, streaming);
+            if (ar.refusal) return fail(ar.refusal);
             if (rg) {
-                if (!relpos_attention2_supported(dpad)) return fail("ragged batches need attention2.hip (padded head width <= 160)");
                 ap.rag_off = br.off_at(k); ap.rag_wg = br.wg_off + (size_t)k * (B + 1); ap.rag_nwg = s.wgs[k]; ap.rag_tgmax = Tg;
             }
             { PROF(PC_ATTENTION, 2.0 * H * (rg ? s.tg2[k] : (double)B * Tg * Tg) * d * 3.0, (double)M * D * 2 * 5);
-              if (rg || streaming) EC_ABL(1, EC_TRY(launch_relpos_attention2(ap, 1, st))); else
-              if (e->attention_v2 && relpos_attention2_supported(dpad)) EC_TRY(launch_relpos_attention2(ap, e->attention_v2, st));
+              if (ar.waves) EC_ABL(rg || streaming ? 1 : 0, EC_TRY(launch_relpos_attention2(ap, ar.waves, st)));
               else EC_TRY(launch_relpos_attention(ap, st)); }
             if ((int)e->att_out.size() == nb && e->att_out[k]) {       // opt-in: the reference's att_w of this block (encoders.py:129)
                 // ragged batches: (B, H, Tg of the LONGEST utterance, same) per block, an utterance's own Tg x Tg block = its map run alone, zeros elsewhere
                 EC_TRY(launch_attention_probs(ap, e->att_out[k], st));
             }
             trace_block(e, st, k, "att_o", o, M, D, ld8(D), 1);
-            if (chain_b) {
-                ChainParams cp{};
-                cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
+            if (r.chain_b) {
+                ChainParams cp = chain_params(e);
                 cp.M = M; cp.D = D; cp.X = x; cp.ldx = D; cp.Y = x; cp.ldy = D; cp.A = o; cp.lda = ld8(D);
-                cp.g0 = ChainGemm{W.c_outp.w, W.c_outp.ldw, W.c_outp.bias, 0};
-                cp.ln[0] = ChainLn{W.ln_conv.g, W.ln_conv.b};
-                cp.g1 = ChainGemm{W.c_pw1.w, W.c_pw1.ldw, W.c_pw1.bias, W.c_pw1_chunks};
+                cp.g0 = ChainGemm{W.c_outp.w, W.c_outp.ldw, 0};
+                cp.g1 = ChainGemm{W.c_pw1.w, W.c_pw1.ldw, W.c_pw1_chunks};
                 cp.glu = gbuf; cp.ldg = ld8(De); cp.Ng = De; cp.T = qT; cp.Tp = qTp; cp.consts = W.cc_b;
                 PROF(PC_GEMM_OTHER, 2.0 * M * (double)D * (D + 2.0 * De), (double)M * D * 10 + (double)M * De * 2 + 2.0 * D * (D + 2.0 * De));
                 EC_ABL(4, EC_TRY(launch_chain(cp, CHAIN_B, st)));
             } else {
-                EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, o, ld8(D), M, W.outp, 0, EPI_RESID_F32, x, D, x, D, 1.0f));
+                EC_TRY(run_rs_or_tiled(e, r.outp_rs, PC_GEMM_OTHER, st, o, ld8(D), M, W.outp, 0, EPI_RESID_F32, x, D, x, D, 1.0f));
             }
             trace_block(e, st, k, "x_mhsa", x, M, D, D, 0);
         }
 
         // ---- x = conv_res(x) + ConvModule(x)   (blocks.py:129; modules.py:511-522)
-        if (chain_b) {
-        } else if (rs_gemm_supported(D)) {
-            EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De), nullptr, 0, 1.f, x, &W.ln_conv));
-        } else {
-            { PROF(PC_LAYERNORM, 0, (double)M * D * 6); EC_TRY(launch_layernorm(x, M, D, W.ln_conv.g, W.ln_conv.b, nullptr, a, ld8(D), nullptr, nullptr, st)); }
-            EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De)));
-        }
+        if (!r.chain_b) EC_TRY(run_rs_or_tiled(e, r.pw1_rs, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De), nullptr, 0, 1.f, x, &W.ln_conv));
         trace_block(e, st, k, "glu", gbuf, M, De, ld8(De), 1);
         const RaggedConv rc = rg ? br.conv_at(k, Mo, true) : RaggedConv{};
-        { PROF(PC_DWCONV, 2.0 * Mo * (double)De * b.kernel_size, (double)M * De * 2 + (double)Mo * De * 2); EC_ABL(8, EC_TRY(launch_dwconv(gbuf, B, T, To, De, ld8(De), W.dw_w, W.dw_b, b.kernel_size, b.conv_stride, cbuf, st, rg ? &rc : nullptr, c.causal, dw_mfma_table(e, W.dw_a, b.kernel_size), W.dw_a3))); }
+        { PROF(PC_DWCONV, 2.0 * Mo * (double)De * b.kernel_size, (double)M * De * 2 + (double)Mo * De * 2); EC_ABL(8, EC_TRY(launch_dwconv(gbuf, B, T, To, De, ld8(De), W.dw_w, W.dw_b, b.kernel_size, b.conv_stride, cbuf, st, rg ? &rc : nullptr, c.causal, r.dw_mfma ? W.dw_a : nullptr, W.dw_a3))); }
         mask_stride *= b.conv_stride;
         trace_block(e, st, k, "dw", cbuf, Mo, De, ld8(De), 1);
         if (D != De) {   // 1x1 strided conv on frames 0, s, 2s, ...  (blocks.py:106-110)
             { PROF(PC_MISC, 0, (double)Mo * D * 6); EC_ABL(64, EC_TRY(launch_cast_rows(x, D, T, b.conv_stride, To, B, xs, ld8(D), st, rg ? &rc : nullptr))); }
-            EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, xs, ld8(D), Mo, W.res, 1, EPI_F32, xalt, De));
+            EC_TRY(run_rs_or_tiled(e, r.res_rs, PC_GEMM_OTHER, st, xs, ld8(D), Mo, W.res, 1, EPI_F32, xalt, De));
             std::swap(x, xalt);
         } else if (b.conv_stride > 1) {
             return fail("strided block without expansion is not native (no shipped config uses it)");
         }
         const bool last = (k == nb - 1);
         float* xo = (last && !rg) ? out : x;        // ragged: the last block writes its rows in place; emit_rows pads them into `out` below
-        if (chain_tail) {
-            bool next_head = false;
-            if (!last) {
-                const EcBlock& nbk = e->blocks[k + 1];
-                next_head = W.cc_full && nbk.dim_model <= e->chain_max_dim && e->bw[k + 1].chain_in && chain_full_supported(De, pair_on(e, De) ? 256 : e->chain_full_max) && nbk.dim_model == De;
-            }
-            ChainParams cp{};
-            cp.small_m = e->chain_small_m; cp.pair = e->chain_pair;
+        if (r.tail != TAIL_MODULES) {
+            const bool next_head = r.tail == TAIL_FULL;
+            ChainParams cp = chain_params(e);
             cp.M = Mo; cp.D = De; cp.X = x; cp.ldx = De; cp.Y = xo; cp.ldy = De; cp.A = cbuf; cp.lda = ld8(De);
-            cp.g0 = ChainGemm{W.c_pw2.w, W.c_pw2.ldw, W.c_pw2.bias, 0};
-            cp.ln[0] = ChainLn{W.ln_ffn2.g, W.ln_ffn2.b};
-            cp.ln[1] = ChainLn{W.ln_out.g, W.ln_out.b};
-            cp.f[0] = ChainFfn{W.c_f2a.w, W.c_f2a.ldw, W.c_f2a.bias, W.c_f2b, W.ffn2_b.ldw, W.c_f2b2, ec_round_up(De * b.ff_ratio, 32), W.c_f2b_cm};
+            cp.g0 = ChainGemm{W.c_pw2.w, W.c_pw2.ldw, 0};
+            cp.f[0] = ChainFfn{W.c_f2a.w, W.c_f2a.ldw, W.c_f2b, W.ffn2_b.ldw, ec_round_up(De * b.ff_ratio, 32), W.c_f2b_cm};
             double fl = 2.0 * Mo * (double)De * (De + 2.0 * De * b.ff_ratio), by = (double)Mo * De * 10 + 2.0 * De * De * (1 + 2.0 * b.ff_ratio);
             if (next_head) {
                 const EcBlock& nbk = e->blocks[k + 1];
@@ -390,22 +341,16 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             }
             cp.consts = next_head ? W.cc_full : W.cc_tail;
             { PROF(PC_GEMM_FFN, fl, by); EC_ABL(2, EC_TRY(launch_chain(cp, next_head ? CHAIN_A_FULL : CHAIN_A_TAIL, st))); }
-            head_done = next_head;
             have_a = false;
             if (last) { trace_block(e, st, k, "out", xo, Mo, De, De, 0); }
             continue;
         }
-        head_done = false;
-        EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, cbuf, ld8(De), Mo, W.pw2, 0, EPI_RESID_F32, x, De, x, De, 1.0f));
+        EC_TRY(run_rs_or_tiled(e, r.pw2_rs, PC_GEMM_OTHER, st, cbuf, ld8(De), Mo, W.pw2, 0, EPI_RESID_F32, x, De, x, De, 1.0f));
         trace_block(e, st, k, "x_conv", x, Mo, De, De, 0);
 
         // ---- x += 1/2 FFN2(x); x = LN(x)   (blocks.py:132-135)
-        if (ffn_fused_supported(De) && !prefer_tiled(e, Mo, De * b.ff_ratio, De)) {
-            EC_TRY(run_ffn(e, st, a, Mo, De, W.ffn2_a, W.ffn2_b, W.ffn2_bp, x, hbuf, &W.ln_ffn2));
-        } else {
-            { PROF(PC_LAYERNORM, 0, (double)Mo * De * 6); EC_TRY(launch_layernorm(x, Mo, De, W.ln_ffn2.g, W.ln_ffn2.b, nullptr, a, ld8(De), nullptr, nullptr, st)); }
-            EC_TRY(run_ffn(e, st, a, Mo, De, W.ffn2_a, W.ffn2_b, W.ffn2_bp, x, hbuf));
-        }
+        if (!r.ffn2_fused) { PROF(PC_LAYERNORM, 0, (double)Mo * De * 6); EC_TRY(launch_layernorm(x, Mo, De, W.ln_ffn2.g, W.ln_ffn2.b, nullptr, a, ld8(De), nullptr, nullptr, st)); }
+        EC_TRY(run_ffn(e, st, r.ffn2_fused, a, Mo, De, W.ffn2_a, W.ffn2_b, W.ffn2_bp, x, hbuf, r.ffn2_fused ? &W.ln_ffn2 : nullptr));
         // block-final norm fused with the next block's FFN1 pre-norm (both read the same rows)
         { PROF(PC_LAYERNORM, 0, (double)Mo * De * 10); EC_TRY(launch_layernorm(x, Mo, De, W.ln_out.g, W.ln_out.b, xo, last ? nullptr : a, ld8(De),
                                 last ? nullptr : e->bw[k + 1].ln_ffn1.g, last ? nullptr : e->bw[k + 1].ln_ffn1.b, st)); }
@@ -449,14 +394,9 @@ size_t effconf_module_workspace_bytes(const EcEncoder* e, int32_t batch, int32_t
         mx = std::max(mx, D * ((size_t)b.ff_ratio + 4) * 2 + 64);
     }
     const size_t rows = (size_t)batch * frames;
-    size_t sub = 0;
-    {   // subsampler scratch: frames = mel frames here
-        const int L = e->cfg.sub_layers, C = e->cfg.sub_filters[L - 1];
-        int F = e->cfg.n_mels; for (int i = 0; i < L; ++i) F /= 2;
-        const size_t t1 = (frames - 1) / 2 + 1;
-        sub = al((size_t)batch * t1 * C * F * 2) + (L == 2 ? al((size_t)batch * (e->cfg.n_mels / 2) * t1 * ec_round_up(e->cfg.sub_filters[0], 64) * 2) : 0);
-    }
-    return std::max(al(rows * mx) + 4 * 256, sub + 256);
+    // effconf_subsample's scratch: frames = mel frames here; its rows counted after ONE layer (an upper bound for the two-layer subsampler, kept)
+    const FrontScratch fs = front_scratch(e, false, (size_t)batch, (size_t)frames, (size_t)(frames - 1) / 2 + 1);
+    return std::max(al(rows * mx) + 4 * 256, al(fs.sub) + al(fs.sub1) + 256);
 }
 
 int effconf_ffn(EcEncoder* e, int32_t block, int32_t which, const float* x, int32_t rows, float* y, void* workspace, size_t workspace_bytes,
@@ -476,9 +416,9 @@ int effconf_ffn(EcEncoder* e, int32_t block, int32_t which, const float* x, int3
     const LNp& ln = which == 1 ? W.ln_ffn1 : W.ln_ffn2;
     const PackedLinear &L1 = which == 1 ? W.ffn1_a : W.ffn2_a, &L2 = which == 1 ? W.ffn1_b : W.ffn2_b;
     const bf16_t* w2p = which == 1 ? W.ffn1_bp : W.ffn2_bp;
-    if (ffn_fused_supported(D)) return run_ffn(e, st, a, rows, D, L1, L2, w2p, y, hbuf, &ln);       // pre-norm in the kernel's prologue
-    EC_TRY(launch_layernorm(y, rows, D, ln.g, ln.b, nullptr, a, ld8(D), nullptr, nullptr, st));
-    return run_ffn(e, st, a, rows, D, L1, L2, w2p, y, hbuf);
+    const bool fused = ffn_fused_module(D);      // not the forward's ffn_fused: this entry keeps the fused kernel where tiled_auto / wide_gemm send a forward to the tiled GEMMs
+    if (!fused) EC_TRY(launch_layernorm(y, rows, D, ln.g, ln.b, nullptr, a, ld8(D), nullptr, nullptr, st));
+    return run_ffn(e, st, fused, a, rows, D, L1, L2, w2p, y, hbuf, fused ? &ln : nullptr);       // fused: pre-norm in the kernel's prologue
 }
 
 int effconf_conv_module(EcEncoder* e, int32_t block, const float* x, int32_t batch, int32_t frames, float* y, void* workspace,
@@ -495,16 +435,12 @@ int effconf_conv_module(EcEncoder* e, int32_t block, const float* x, int32_t bat
     bf16_t* a = reinterpret_cast<bf16_t*>(ws);
     bf16_t* gbuf = reinterpret_cast<bf16_t*>(ws + a_bytes);
     bf16_t* cbuf = reinterpret_cast<bf16_t*>(ws + a_bytes + g_bytes);
+    const BlockRoutes r = block_routes(e, block);
     // LayerNorm -> pointwise-1 + GLU (modules.py:511-514)
-    if (rs_gemm_supported(D)) {
-        EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De), nullptr, 0, 1.f, x, &W.ln_conv));
-    } else {
-        EC_TRY(launch_layernorm(x, M, D, W.ln_conv.g, W.ln_conv.b, nullptr, a, ld8(D), nullptr, nullptr, st));
-        EC_TRY(run_rs_or_tiled(e, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De)));
-    }
+    EC_TRY(run_rs_or_tiled(e, r.pw1_rs, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De), nullptr, 0, 1.f, x, &W.ln_conv));
     // depthwise conv + BatchNorm + Swish (modules.py:516-518), pointwise-2 (modules.py:519)
-    EC_TRY(launch_dwconv(gbuf, batch, T, To, De, ld8(De), W.dw_w, W.dw_b, b.kernel_size, b.conv_stride, cbuf, st, nullptr, e->cfg.causal, dw_mfma_table(e, W.dw_a, b.kernel_size), W.dw_a3));
-    return run_rs_or_tiled(e, PC_GEMM_OTHER, st, cbuf, ld8(De), Mo, W.pw2, 1, EPI_F32, y, De);
+    EC_TRY(launch_dwconv(gbuf, batch, T, To, De, ld8(De), W.dw_w, W.dw_b, b.kernel_size, b.conv_stride, cbuf, st, nullptr, e->cfg.causal, r.dw_mfma ? W.dw_a : nullptr, W.dw_a3));
+    return run_rs_or_tiled(e, r.pw2_rs, PC_GEMM_OTHER, st, cbuf, ld8(De), Mo, W.pw2, 1, EPI_F32, y, De);
 }
 
 int effconf_subsample(EcEncoder* e, const float* mel, int32_t batch, int32_t n_frames, float* y, void* workspace, size_t workspace_bytes,
@@ -512,12 +448,9 @@ int effconf_subsample(EcEncoder* e, const float* mel, int32_t batch, int32_t n_f
     if (!e || !e->finalized) return fail("encoder not finalized");
     if (!mel || !y || batch <= 0 || n_frames <= 0 || !workspace) return fail("bad argument");
     const Shapes s = make_shapes(e, batch, n_frames);
-    const int L = e->cfg.sub_layers, C = e->cfg.sub_filters[L - 1];
-    int F = e->cfg.n_mels; for (int i = 0; i < L; ++i) F /= 2;
-    const size_t sub_bytes = al((size_t)batch * s.T1 * C * F * 2);
-    const size_t tl1 = (n_frames - 1) / 2 + 1;
-    const size_t act_bytes = L == 2 ? al((size_t)batch * (e->cfg.n_mels / 2) * tl1 * ec_round_up(e->cfg.sub_filters[0], 64) * 2) : 0;
-    if (workspace_bytes < sub_bytes + act_bytes) return fail("workspace too small");
+    const FrontScratch fs = front_scratch(e, false, (size_t)batch, (size_t)n_frames, (size_t)s.T1);
+    const size_t sub_bytes = al(fs.sub);
+    if (workspace_bytes < sub_bytes + al(fs.sub1)) return fail("workspace too small");
     char* ws = reinterpret_cast<char*>(workspace);
     return run_subsample_linear(e, (hipStream_t)stream, mel, s, nullptr, reinterpret_cast<bf16_t*>(ws), reinterpret_cast<bf16_t*>(ws + sub_bytes), nullptr, y);
 }

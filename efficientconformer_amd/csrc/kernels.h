@@ -82,21 +82,19 @@ int launch_ffn_fused(const FfnParams& p, hipStream_t s);
 // ---------------------------------------------------------------- fused row-local chains  (chain.hip)
 // One kernel runs a whole row-local stretch of the Conformer block on a 32-row tile per wave, the fp32 residual row staying in
 // registers between GEMMs (see chain.hip).  All weights are K-permuted per 16 (pack_linear_kperm), rows padded to 64.
-struct ChainGemm { const bf16_t* w; int ldw; const float* bias; int nchunks; };        // nchunks = 64-row chunks
-struct ChainFfn { const bf16_t* w1; int ldw1; const float* b1; const bf16_t* w2; int ldw2; const float* b2; int Fp; const bf16_t* w2cm; };   // w2cm: w2 chunk-major (chain3.hip; null below padded width 256)   // w2, b2 pre-scaled by 1/2
-struct ChainLn { const float* g; const float* b; };
+struct ChainGemm { const bf16_t* w; int ldw; int nchunks; };        // nchunks = 64-row chunks; the bias: in the constant block
+struct ChainFfn { const bf16_t* w1; int ldw1; const bf16_t* w2; int ldw2; int Fp; const bf16_t* w2cm; };   // w2cm: w2 chunk-major (chain3.hip; null below padded width 256)   // w2 pre-scaled by 1/2; b1, b2 / 2: in the constant block
 struct ChainParams {
     int M, D;
     const float* X; int ldx;            // residual stream in
     float* Y; int ldy;                  // residual stream out (may alias X)
     const bf16_t* A; int lda;           // bf16 activation feeding g0 (depthwise-conv output / attention output)
     ChainGemm g0;                       // pointwise-2 or attention output projection: x += g0(A)
-    ChainLn ln[4];                      // only ln[1] (block norm, applied in fp32) is read: the pre-norms' gamma / beta are folded into the following weights at pack time
     ChainFfn f[2];                      // chain A: ffn2, ffn1 (of the next block)
     ChainGemm g1;                       // chain A: stacked QKV (natural layout, chunk-permuted rows); chain B: pointwise-1 (a|b interleaved per 32)
     bf16_t *qu, *kh, *vt; const float *u, *v; int T, Tp;          // QKV outputs (Q + u, K, V): rows (b, t) -> (b*Tp + t)*D
     bf16_t* glu; int ldg, Ng;           // GLU output [M][ldg], Ng channels
-    const float* consts;                // biases / block-norm gamma, beta / u, v as ONE zero padded block laid out by chain_const_layout
+    const float* consts;                // biases / block-norm gamma, beta / u, v as ONE zero padded block laid out by chain_const_layout (the pre-norms' gamma / beta are folded into the following weights at pack time)
     int small_m;                        // option "chain_small_m": launches of at most this many rows use 2-wave workgroups (64 rows): see launch_chain_kind
     int pair;                           // option "chain_pair": 5 = chain3.hip (chain A) / chain2.hip (chain B) at padded width 256; 0 = chain.hip everywhere
 };

@@ -1,6 +1,7 @@
 // Weight packing (pack.h).  First half: the image builders, pure host arithmetic.  Second half: the steps of effconf_encoder_finalize - each finds its
 // tensors among the loaded host tensors, calls a builder, uploads the result and stores the pointer; `upload` (encoder_state.h) is their only way to a device.
 #include "pack.h"
+#include "routes.h"
 
 #include <algorithm>
 
@@ -607,7 +608,9 @@ int pack_chain_consts(EcEncoder* e) {
         }
         if (W.chain_out && chain_tail_supported(De)) {
             W.cc_tail = upload(e, chain_const_block(CHAIN_A_TAIL, De, &W, nullptr, &b, nullptr));
-            if (chain_full_supported(De, std::max(e->chain_full_max, chain3_supported(De) ? 256 : 0)) && k + 1 < e->blocks.size() && e->bw[k + 1].chain_in && e->blocks[k + 1].dim_model == De)
+            // The forward's rule (routes.h tail_route) with "the width has a chain3.hip instance" for its chain_pair_on: with chain_pair = 0 set before finalize
+            // and chain_full_max < De the block is built and no forward reads it (kept: the option may be set back without a second finalize)
+            if (chain_full_fits(e, k, chain3_supported(De)))
                 W.cc_full = upload(e, chain_const_block(CHAIN_A_FULL, De, &W, &e->bw[k + 1], &b, &e->blocks[k + 1]));
         }
     }

@@ -118,10 +118,13 @@ int effconf_encoder_forward_mel(EcEncoder* enc, const float* mel, const int64_t*
  *              the kernels index rows with the device copy inside grids / a workspace sized from the host copy, so a device length that
  *              exceeds its host twin is an out-of-bounds access.  (The Python wrapper checks on request: ConformerEncoder.check_host_lengths.)
  *   out        dev f32 (batch, out_frames, D_last): utterance b's T_out(b) frames, zeros behind them; out_frames >= the longest T_out
- * Workspace: effconf_encoder_workspace_bytes_ragged(enc, x_len_host, batch, n, from_audio).  Front ends: sublinear2.hip indexes the ragged
- * rows itself (one subsampling layer, <= 192 filters and <= 192-wide first stage); wider one-layer and the two-layer subsamplers run on the
- * rectangular image (zero padding at every utterance's own end) and gather the valid rows.  Needs head widths <= 160 (attention2.hip);
- * bf16 path only. */
+ * Workspace: effconf_encoder_workspace_bytes_ragged(enc, x_len_host, batch, n, from_audio), under the options the forward will run with.  Front ends:
+ * sublinear2.hip / sublinear3.hip and the one-layer conv + GEMM route write the ragged rows themselves; the two-layer subsampler runs on the rectangular
+ * image (zero padding at every utterance's own end) and gathers the valid rows.  The size holds the front end's scratch only where the chosen route
+ * ("fuse_subsample" below) uses it: none for the fused kernels (before, every ragged route but sublinear2.hip under "fuse_subsample" = 2 reserved the
+ * subsampler's output rows and a rectangular Linear output - EfficientConformer Large under defaults, any model under "fuse_subsample" = 3), the subsampler's
+ * output rows for conv + GEMM (no rectangular Linear output any more), both plus the layer-1 image for two layers.  Rectangular sizes are unchanged.
+ * Needs head widths <= 160 (attention2.hip); bf16 path only. */
 size_t effconf_encoder_workspace_bytes_ragged(const EcEncoder* enc, const int64_t* x_len_host, int32_t batch, int32_t n, int32_t from_audio);
 int effconf_encoder_forward_ragged(EcEncoder* enc, const float* x, const int64_t* x_len, const int64_t* x_len_host, int32_t batch, int32_t n,
                                    int32_t from_audio, float* out, int32_t out_frames, int64_t* out_len, void* workspace,
@@ -369,11 +372,12 @@ int effconf_lm_step(EcLm* lm, const int32_t* tokens, const float* h_in, const fl
  * so a caller that alternates workspaces (one per stream) keeps all of them warm.  Enable ONLY if the caller leaves the
  * workspaces untouched between forwards; setting the option again (to any value) forgets every tag — do that when a
  * workspace is freed and its address may be reused.  Host calls on one handle must not run concurrently (they only enqueue).
- * "fuse_subsample" (default 2): conv-subsampling + Linear as 0 = separate conv and GEMM kernels, 1 = sublinear.hip (tiled GEMM whose A tile is
- *   produced by a VALU convolution), 2 = sublinear2.hip (row-stationary, the convolution on the MFMA pipe with a bf16 hi / lo operand
- *   split; falls back to 1 where the shape is not supported; front ends wider than 128 channels / columns - EfficientConformer Medium, Large - run
- *   sublinear3.hip instead: option "sub3_auto", default 1), 3 = sublinear3.hip (round 6: the same fusion in chunks of (output frequency, 32 channels), any
- *   channel count / width up to 384; bit-identical to sublinear2.hip where both exist, slower there).
+ * "fuse_subsample" (default 2): conv-subsampling + Linear (one subsampling layer; two layers have one route) as 0 = separate conv and GEMM kernels,
+ *   1 = sublinear.hip (tiled GEMM whose A tile is produced by a VALU convolution; rectangular batches), 2 = sublinear2.hip (row-stationary, the convolution
+ *   on the MFMA pipe with a bf16 hi / lo operand split; 80 mels, <= 192 filters / columns), 3 = sublinear3.hip (the same fusion in chunks of (output
+ *   frequency, 32 channels), any channel count, widths up to 384; bit-identical to sublinear2.hip where both exist, slower there).  A value whose kernel is
+ *   not built for the shape takes the next lower one that is; with 2, front ends wider than 128 channels / columns - EfficientConformer Medium, Large -
+ *   run sublinear3.hip (option "sub3_auto", default 1).  The precedence in full: csrc/routes.h front_route (printed by effconf_debug_routes).
  * "tiled_auto" (default 1; round 6): with "wide_gemm" = 0, a configuration whose widest stage lies in ("tiled_min_k" = 256, 384] - EfficientConformer Medium's
  *   D = 360 - runs that stage as LayerNorm + tiled GEMMs instead of the row-stationary kernels (+ 2.3 % on Medium; decided per configuration at finalize,
  *   never per batch: one rounding path per handle).  0 = the row-stationary kernels as before.

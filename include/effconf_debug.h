@@ -65,6 +65,14 @@ int effconf_debug_lds_fill(int32_t mode, int32_t blocks, int32_t waves, const vo
  * compare digests within one machine only (tools/pack_digest.py, tests/test_pack_host.py). */
 int effconf_debug_pack_digest(EcEncoder* enc, uint64_t* digest, int64_t* buffers, int64_t* bytes);
 
+/* HOST function (no GPU, no HIP call): which kernels a bf16 forward of `enc` would run under its current options (csrc/routes.h - the functions the forward
+ * itself reads), after the same dry run of the packing as above, so `enc` need not be finalized and is left as it was.  Writes NUL-terminated text into
+ * `text` (`cap` bytes; 256 per block + 256 suffice): one line "front <two_layer|chunked|row_stationary|tiled_fused|conv_gemm> sub=.. sub1=.. xrect=.." (the
+ * route of a rectangular / ragged batch and the workspace scratch it needs) and one line per block, "block k D=.. De=.. head=<prev_tail|chain|modules> ffn1=..
+ * qkv=.. attention=<attention|attention2/1|attention2/2|refused> b=<chain|modules> outp=.. pw1=.. dw=<mfma|valu> res=.. tail=<full|tail|modules> pw2=.. ffn2=..";
+ * a field that does not apply to the block's route reads "-".  Attention is reported for full context (no streaming mask). */
+int effconf_debug_routes(EcEncoder* enc, int32_t ragged, char* text, size_t cap);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -19,8 +19,8 @@ Conventions
   False (per-module kernels: norm.hip launch_layernorm, the prologue LayerNorm of rsgemm.hip): operand q(LN(x) * gamma + beta), weight q(W).
 * FFN: hidden q(swish(.)) (chain.hip ffn_stage: pack_bf2(swishf_(h[r]), ...)), second weight q(W2 / 2) and bias b2 / 2 (pack.hip
   pack_ffn2_permuted(..., 0.5f) and the ``hb`` vectors next to it; the per-module kernel multiplies by alpha = 0.5 after the product, which is
-  the same number), accumulated onto the float32 residual row.  Block-final LayerNorm: float32, affine, not rounded (ChainParams::ln[1],
-  chain.hip ln_inplace).
+  the same number), accumulated onto the float32 residual row.  Block-final LayerNorm: float32, affine, not rounded (gamma / beta in the chains'
+  constant block, chain.hip ln_inplace).
 * Chain B: x += att_o . q(Wo)^T + bo, then glu = q(a * sigmoid(b)) of the pointwise-1 product on the (folded) conv-module LayerNorm (chain.hip:
   "a * sigmoid(b) for channels ..." / pack_bf2(o[0], o[1])).
 * Depthwise convolution: BatchNorm folded into taps and bias in float32 (pack.hip bn_fold, conv_bn_fold and the "[k][De] fp32" table), bf16 input, output

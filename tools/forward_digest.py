@@ -5,6 +5,7 @@ requested and - with a trace arena attached - the ordered list of trace entries 
     python tools/forward_digest.py --compact          # the trace list folded into its count and one SHA-256 (the form kept in profiles/)
     python tools/forward_digest.py Tiny               # the cases of one model
     python tools/forward_digest.py --front-end        # only the front-end cases (front_end_cases)
+    python tools/forward_digest.py --block-routes     # only the per-block route cases (block_routes_cases)
 
 Checking a change of the host side (csrc/encoder.hip, forward_*.hip): run this on the tree before and on the tree after ON THE SAME GPU and compare the lines; a
 forward that enqueues the same kernels with the same arguments in the same order gives the same bytes.  Weights: the recipe of tools/pack_digest.py; inputs:
@@ -174,6 +175,19 @@ def front_end_cases():
     return out
 
 
+def block_routes_cases():
+    """(model, precision, [(label, options)]): the per-block routes of the bf16 schedule (csrc/routes.h: block_routes, attention_route) the defaults do not take -
+    per-module kernels instead of the chains (all of them, the wide stages only, the tail + head pair only), chain.hip instead of chain2.hip / chain3.hip,
+    attention.hip and the 4-wave attention2.hip, the VALU depthwise kernel; Medium's D = 360 stage on the row-stationary and on the tiled kernels, and both forced
+    tile widths of the tiled GEMMs.  Options persist on a handle, so every case sets the whole set; each runs rectangular and ragged with a trace."""
+    small = {"fuse_chain": 1, "chain_pair": 5, "chain_full_max": 192, "chain_max_dim": 256, "attention_v2": 1, "dwconv_mfma": 1}
+    medium = {"tiled_auto": 1, "wide_gemm": 0}
+    one = lambda base, name, v: ("%s=%d" % (name, v), {**base, name: v})
+    return [("EfficientConformerCTCSmall", "bf16", [one(small, *nv) for nv in (("fuse_chain", 0), ("chain_pair", 0), ("chain_full_max", 0), ("chain_max_dim", 128),
+                                                                                ("attention_v2", 0), ("attention_v2", 2), ("dwconv_mfma", 0))]),
+            ("EfficientConformerCTCMedium", "bf16", [("defaults", medium)] + [one(medium, *nv) for nv in (("tiled_auto", 0), ("tiled_auto", 2), ("wide_gemm", 2), ("wide_gemm", 3))])]
+
+
 def emit(compact: bool, head: dict, res: dict):
     if compact and "trace" in res:
         t = res.pop("trace")
@@ -186,7 +200,7 @@ def main(argv):
     only = [a for a in argv if not a.startswith("--")]
     lib = _lib.load()
     for model in MODELS:
-        if "--front-end" in argv or (only and model not in only):
+        if "--front-end" in argv or "--block-routes" in argv or (only and model not in only):
             continue
         for precision in pack_digest.PRECISIONS:
             hd = Handle(lib, model, precision)
@@ -197,7 +211,8 @@ def main(argv):
                     emit(compact, {"model": model, "precision": precision, "case": label}, forward(hd, **kw))
             finally:
                 hd.close()
-    for model, precision, cases in front_end_cases():
+    sections = [("front end", front_end_cases())] * ("--block-routes" not in argv) + [("block routes", block_routes_cases())] * ("--front-end" not in argv)
+    for section, (model, precision, cases) in [(name, c) for name, cs in sections for c in cs]:
         if only and model not in only:
             continue
         hd = Handle(lib, model, precision)
@@ -206,10 +221,10 @@ def main(argv):
                 for k, v in opts.items():
                     hd.option(k, v)
                 for ragged in (False, True):
-                    emit(compact, {"model": model, "precision": precision, "case": "front end, %s, %s" % (label, "ragged" if ragged else "rect")}, forward(hd, ragged=ragged, trace=True))
+                    emit(compact, {"model": model, "precision": precision, "case": "%s, %s, %s" % (section, label, "ragged" if ragged else "rect")}, forward(hd, ragged=ragged, trace=True))
         finally:
             hd.close()
-    if "--front-end" not in argv and (not only or CONTEXT_MODEL in only):
+    if "--front-end" not in argv and "--block-routes" not in argv and (not only or CONTEXT_MODEL in only):
         for label, precision, ctx, kw, opts in context_cases():
             hd = Handle(lib, CONTEXT_MODEL, precision, **ctx)
             try:
