@@ -16,17 +16,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libeffconf.so")
 LIB_DEBUG = os.path.join(HERE, "libeffconf_debug.so")
-SOURCES = ["gemm.hip", "gemm256.hip", "rsgemm.hip", "chain.hip", "chain2.hip", "chain3.hip", "norm.hip", "conv.hip", "sublinear.hip", "sublinear2.hip", "sublinear3.hip", "conv2.hip", "mel.hip", "ctc.hip", "rnnt.hip", "rnnt_beam.hip", "rnnt_lattice.hip", "rnnt_align.hip", "lm.hip", "ctc_beam.hip", "ctc_align.hip", "attention.hip", "attention2.hip", "exact.hip", "split.hip", "sxf.hip", "sxf_ffn.hip", "sxf_chain.hip", "sxf_sub.hip", "hostpack.hip", "pack.hip", "forward_bf16.hip", "forward_exact.hip", "encoder.hip"]
+SOURCES = ["gemm.hip", "gemm256.hip", "rsgemm.hip", "chain.hip", "chain2.hip", "chain3.hip", "norm.hip", "conv.hip", "sublinear.hip", "sublinear2.hip", "sublinear3.hip", "conv2.hip", "mel.hip", "ctc.hip", "rnnt.hip", "rnnt_beam.hip", "rnnt_lattice.hip", "rnnt_align.hip", "lm.hip", "ctc_beam.hip", "ctc_align.hip", "attention.hip", "attention2.hip", "exact.hip", "split.hip", "sxf.hip", "sxf_chain.hip", "sxf_sub.hip", "hostpack.hip", "pack.hip", "forward_bf16.hip", "forward_exact.hip", "encoder.hip"]
 # (source, object, extra flags): further compilations of a source under other flags
 # No packed-fp32 VALU instructions in product kernels: v_pk_{add,mul,fma}_f32 with an op_sel low-lane swizzle return wrong values
 # next to another wave's bf16 MFMA on gfx950 (measured: profiles/r2_mel_packed_fp32_hazard.txt; guard: _isa_guard.py).
 # Cost of the flag for the whole library: 7.56 -> 7.60 ms per bench step.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# libeffconf_debug.so (tests / tools only, include/effconf_debug.h) = the product objects with mel.hip and sxf_ffn.hip recompiled under -DEFFCONF_DEBUG_ABI
-# (the diagnostic mel_kernel variants, the fused FFN's ablation switches) + encoder_debug.hip (every effconf_debug_* entry point), debug.hip and the packed-fp32
+# libeffconf_debug.so (tests / tools only, include/effconf_debug.h) = the product objects with mel.hip recompiled under -DEFFCONF_DEBUG_ABI
+# (the diagnostic mel_kernel variants) + encoder_debug.hip (every effconf_debug_* entry point), debug.hip and the packed-fp32
 # build of mel.hip - the hazard reproducers need the instructions they demonstrate, so those two are compiled WITHOUT the flag below.  Every host file of the
 # library is compiled once; nothing of this is linked into libeffconf.so.
-DEBUG_REPLACES = {"mel.hip": "mel_dbg.o", "sxf_ffn.hip": "sxf_ffn_dbg.o"}
+DEBUG_REPLACES = {"mel.hip": "mel_dbg.o"}
 DEBUG_OBJECTS = [("encoder_debug.hip", "encoder_debug.o", NO_PACKED_FP32), ("debug.hip", "debug.o", []), ("mel.hip", "mel_pk.o", ["-DMEL_PK_BUILD"])]
 # sxf_chain.hip: the source-scheduled F2 + Swish body is ~400 unrolled iterations of a 13-way switch - beyond the default cost bound of `#pragma unroll`, and a loop
 # left rolled indexes its register arrays dynamically (= scratch memory)

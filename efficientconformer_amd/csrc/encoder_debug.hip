@@ -66,6 +66,23 @@ int effconf_debug_routes(EcEncoder* e, int32_t ragged, char* text, size_t cap) {
                      pick(b.dim_model != b.dim_expand, r.res_rs, "rs", "tiled"), kTail[r.tail], pick(tm, r.pw2_rs, "rs", "tiled"), pick(tm, r.ffn2_fused, "ln_fused", "ln+tiled"));
             out += ln;
         }
+        if (!t.exact_split) return;
+        // the label-exact split schedule, per kind of forward: as it runs untraced, with a debug trace (option trace_fused decides), with attention maps requested
+        const char* const kinds[] = {"untraced", "traced", "maps"};
+        for (int kind = 0; kind < 3; ++kind) {
+            const ExactForwardRoutes f = exact_forward_routes(&t, kind == 1, kind == 2);
+            snprintf(ln, sizeof(ln), "split %s family=%s front=%s causal=%s\n", kinds[kind], f.fused ? "fused" : "modules", f.sublin ? "sublin" : "modules", f.refusal ? "refused" : "ok");
+            out += ln;
+            for (size_t k = 0; k < t.blocks.size(); ++k) {
+                const EcBlock& b = t.blocks[k];
+                const ExactBlockRoutes r = exact_block_routes(&t, f, k, true, true);      // rectangular and ragged batches alike: a block reads the rows its predecessor wrote
+                auto pick = [](bool applies, bool yes) { return !applies ? "-" : (yes ? "fused" : "ln+gemms"); };
+                snprintf(ln, sizeof(ln), "split %s block %d D=%d De=%d head=%s ffn1=%s attention=%s b=%s tail=%s ffn2=%s\n", kinds[kind], (int)k, b.dim_model, b.dim_expand, kHead[r.head],
+                         pick(r.head == HEAD_MODULES, r.ffn1_fused), f.fused ? "sxf" : (exact_attention_split(&t, b.group_size * b.dim_model / b.num_heads, b.num_heads) ? "sx" : "ex"),
+                         r.chain_b ? "chain" : "modules", kTail[r.tail], pick(r.tail == TAIL_MODULES, r.ffn2_fused));
+                out += ln;
+            }
+        }
     });
     if (rc) return rc;
     if (out.size() + 1 > cap) return fail("effconf_debug_routes: text buffer too small");
@@ -136,19 +153,6 @@ int effconf_debug_dwconv(const uint16_t* g, int32_t batch, int32_t frames, int32
     (void)hipStreamSynchronize(st);
     (void)hipFree(dw); (void)hipFree(db); if (dt) (void)hipFree(dt);
     return rc ? fail("launch_dwconv failed rc=" + std::to_string(rc)) : 0;
-}
-
-int effconf_debug_sxf_ffn(EcEncoder* e, int32_t block, int32_t which, const float* x, int32_t rows, float* y, int32_t with_norm, int32_t ablate, void* stream) {
-    if (!e || !e->finalized || block < 0 || block >= (int)e->blocks.size() || which < 1 || which > 2 || !x || !y || rows <= 0) return fail("bad argument");
-    const BlockW& W = e->bw[block];
-    if (!W.xf_img[which - 1]) return fail("no fused split FFN image for this block (finalize with exact_fp32 = 2; width not built, or a folded weight beyond the image's range)");
-    SxfFfnParams fp{};
-    const int D = which == 2 ? e->blocks[block].dim_expand : e->blocks[block].dim_model;
-    fp.X = x; fp.ldx = D; fp.Y = y; fp.ldy = D; fp.wimg = W.xf_img[which - 1]; fp.b2 = W.xf_b2[which - 1]; fp.M = rows; fp.D = D; fp.nchunk = W.xf_nch[which - 1];
-    if (with_norm) { fp.ln_g = W.ln_out.g; fp.ln_b = W.ln_out.b; }
-    fp.ablate = ablate;
-    EC_TRY(launch_sxf_ffn(fp, reinterpret_cast<hipStream_t>(stream)));
-    return 0;
 }
 
 int effconf_debug_spin(double microseconds, void* stream) {

@@ -36,10 +36,10 @@ struct BlockW {
     const bf16_t *c_f1b = nullptr, *c_f2b = nullptr; const float *c_f1b2 = nullptr, *c_f2b2 = nullptr;
     int c_qkv_chunks = 0, c_pw1_chunks = 0;
     std::vector<float> h_ln_out_g, h_ln_out_b, h_u, h_v, h_f1b2, h_f2b2;     // host copies for the chains' constant blocks
-    // split mode (sxf_ffn.hip): weight images of the two feed-forward modules, b2 / 2, hidden chunks
-    const uint16_t *xf_img[2] = {nullptr, nullptr}; const float* xf_b2[2] = {nullptr, nullptr}; int xf_nch[2] = {0, 0};
     // split mode (sxf_chain.hip): images in the accumulator layout's k order - out-proj / pointwise-2 (F2), pointwise-1 with GLU row pairs / Q | K | V (F1, pre-norm
-    // folded), the two feed-forward modules; biases of the F2 products
+    // folded), the two feed-forward modules xc_f (each on its own: null = LayerNorm + two GEMMs for that module) with b2 / 2 and their chunks of 32 hidden units;
+    // biases of the F2 products
+    const float* xf_b2[2] = {nullptr, nullptr}; int xf_nch[2] = {0, 0};
     const uint16_t *xc_wo = nullptr, *xc_p1 = nullptr, *xc_p2 = nullptr, *xc_qkv = nullptr, *xc_f[2] = {nullptr, nullptr};
     const float *xc_bo = nullptr, *xc_bp2 = nullptr; int xc_nch_p1 = 0;
     bool xc_in = false, xc_out = false;          // the D-wide (out-proj, pointwise-1, FFN1, Q K V) / De-wide (pointwise-2, FFN2) images exist
@@ -85,7 +85,7 @@ struct EcEncoder {
     int split_chain = 1;                     // split mode: the row-local work of a block as two kernels (sxf_chain.hip) where the width is built; 0 = per-module kernels (tests)
     int sub3_auto = 1;                       // with fuse_subsample = 2: front ends wider than 128 channels / columns on sublinear3.hip (0: the narrower kernels where built, else conv + GEMM)
     int split_sublin = 1;                    // split mode: Conv2dSubsampling + Linear as one kernel (sxf_sub.hip) for the one-layer subsampler; 0 = conv kernel + GEMM [+ row gather] (tests)
-    int split_ffn = 1;                       // split mode: the feed-forward modules as one kernel each (sxf_ffn.hip) where the width is built; 0 = LayerNorm + two GEMMs (tests)
+    int split_ffn = 1;                       // split mode: a feed-forward module outside a chain as one kernel (sxf_chain.hip's FFN-only form) where its image exists; 0 = LayerNorm + two GEMMs, and no chains (tests)
     bool trace_fused = false;                // split mode: a debug trace keeps the fused kernels (sxf_sub.hip, sxf_chain.hip) and records what THEY write; 0 = a trace selects the per-module kernels
     int exact_attention = 0;                 // fp32 mode: 0 tiled attention kernel (2: its 16-row shape), 1 one wave per query row (round 2's); bit-identical
     // two-layer subsampler (plain Conformer configs): layer-2 implicit-GEMM weight [N][9*Cp] (tap, c_in), folded bias, Cp

@@ -100,9 +100,6 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
                  int64_t* out_len, hipStream_t st, int out_frames);
 int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int from_audio, const Shapes& s, const XWorkspace& w, char* ws, float* out,
                   int64_t* out_len, hipStream_t st, int out_frames);
-// split mode (exact_fp32 = 2) with every head width / stage width on the fused kernels of sxf*.hip: the kernel family forward_exact runs (with no attention
-// maps requested), and the one that takes ragged batches
-bool split_fused_ok(const EcEncoder* e);
 
 // ------------------------------------------------------------------ per-launch profiler
 struct ProfScope {

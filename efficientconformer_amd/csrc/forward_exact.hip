@@ -1,6 +1,7 @@
 // The label-exact forward schedule: fp32 activations everywhere, every product either on the fp32 matrix pipe (exact_fp32 = 1, exact.hip) or on the fp16
 // matrix pipe with split operand pairs (exact_fp32 = 2, split.hip / sxf*.hip).  One schedule, two kernel families (forward_exact).
 #include "forward_common.h"
+#include "routes.h"
 
 // rows come from the Shapes totals: B * T for rectangular batches, the sums over the utterances for ragged ones (s.Tm = the input's row pitch there)
 XWorkspace make_xworkspace(const EcEncoder* e, const Shapes& s) {
@@ -129,14 +130,24 @@ int xffn(EcEncoder* e, hipStream_t st, float* x, int rows, int dim, int ratio, c
     return xresid(e, st, hb, dim * ratio, rows, module + ".layers.4", dim, dim * ratio, x, 0.5f, ffn);
 }
 
-}  // namespace
-
-bool split_fused_ok(const EcEncoder* e) {
-    if (!e->exact_split) return false;
-    for (const EcBlock& b : e->blocks)
-        if (!sxf_attention_supported(b.group_size * b.dim_model / b.num_heads) || b.dim_model % 4 || b.dim_expand % 4) return false;
-    return true;
+// One FeedForwardModule outside a chain: xo = x + 1/2 FFN(LN(x)), then xo = ln_out(xo) where ln_out is given (blocks.py:122, 132-135).  fused: the FFN-only form of
+// sxc_a_kernel on the module's chain image, else LayerNorm + two GEMMs (in place on x) [+ LayerNorm]
+int xffn_module(EcEncoder* e, hipStream_t st, bool fused, size_t k, int which, float* x, float* xo, int rows, const LNp* ln_out, float* a, float* hb) {
+    const EcBlock& b = e->blocks[k];
+    const BlockW& W = e->bw[k];
+    const int dim = which ? b.dim_expand : b.dim_model;
+    if (fused) {
+        SxcAParams cp{};
+        cp.xres = x; cp.y = xo; cp.M = rows; cp.D = dim; cp.w_f2 = W.xc_f[which]; cp.nch_f2 = W.xf_nch[which]; cp.b_f2 = W.xf_b2[which];
+        if (ln_out) { cp.ln_g = ln_out->g; cp.ln_b = ln_out->b; }
+        PROF(PC_GEMM_FFN, 4.0 * rows * (double)dim * dim * b.ff_ratio, (double)rows * dim * 8 + 16.0 * dim * dim * b.ff_ratio);
+        return launch_sxc_a(cp, st);
+    }
+    EC_TRY(xffn(e, st, x, rows, dim, b.ff_ratio, which ? W.ln_ffn2 : W.ln_ffn1, "blocks." + std::to_string(k) + (which ? ".feed_forward_module2" : ".feed_forward_module1"), a, hb));
+    return ln_out ? xlayernorm(e, st, x, rows, dim, *ln_out, xo) : 0;
 }
+
+}  // namespace
 
 // ------------------------------------------------------------------ the label-exact forward.  Reference: encoders.py:97-142, blocks.py:119-137,
 // attentions.py:506-529, 549-718, 1243-1247, layers.py:97-101.  One schedule on one of two kernel families:
@@ -152,10 +163,12 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
     const EcConfig& c = e->cfg;
     const int B = s.B, nb = (int)e->blocks.size();
     const bool rg = s.ragged;
-    const bool fused = split_fused_ok(e) && e->att_out.empty();
-    // finite left / right contexts: the band mask is part of every label-exact attention kernel; `causal` (causal relative tables, causal depthwise
-    // padding: attentions.py:506, 1243-1247; layers.py:97-101) exists in the fused family only - the per-module kernels have none
-    if (!fused && c.causal) return fail("the label-exact modes have no causal kernels (causal relative tables / depthwise pre-padding): bf16 path only");
+    // every kernel choice of this forward (routes.h), decided here; the schedule below only reads them
+    const ExactForwardRoutes fr = exact_forward_routes(e, e->trace_arena != nullptr, !e->att_out.empty());
+    if (fr.refusal) return fail(fr.refusal);
+    const bool fused = fr.fused;
+    std::vector<ExactBlockRoutes> routes(nb);
+    for (int k = 0; k < nb; ++k) routes[k] = exact_block_routes(e, fr, k, k > 0 && s.Min[k] == s.Mout[k - 1], k + 1 < nb && s.Min[k + 1] == s.Mout[k]);
     // The E image of the fused family is cached like the bf16 path's E; the tag is never equal to a bf16 forward's on the same workspace.  A debug trace wants
     // the projections recorded, and the per-module family lays its own buffers over the workspace: both drop whatever cache is there and leave none
     // (fp32 -> bf16 -> fp32 -> bf16 on one workspace otherwise ends with attention reading fp32 activations as E)
@@ -177,9 +190,7 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
     int T1r = s.Tm; for (int i = 0; i < c.sub_layers; ++i) T1r = (T1r - 1) / 2 + 1;
     // one-layer subsampler: convolution + Swish + Linear as ONE kernel on the frames that exist (sxf_sub.hip) - the (frames, C F') activation stays in registers.
     // A debug trace wants that activation ("subsample"): per-module kernels then, unless option trace_fused keeps the forward as it runs untraced
-    const bool tr_modules = e->trace_arena && !e->trace_fused;
-    const bool sublin = fused && e->split_sublin && e->xsub.wimg && c.sub_layers == 1 && !tr_modules;
-    if (sublin) {
+    if (fr.sublin) {
         const double Mr = (double)s.Min[0], Ks = (double)C0 * e->xsub.fo;
         PROF(PC_SUBCONV, 2.0 * Mr * Ks * (9.0 + D0), (double)B * c.n_mels * s.Tm * 4 + Mr * D0 * 4);
         EC_TRY(launch_sxf_sublin(sub_chunk_params(e, e->xsub, mel, s, rg ? &br : nullptr, x), st));
@@ -208,13 +219,11 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
           *cbuf = F32(w.c), *xs = F32(w.xs);
     uint16_t *kpk = reinterpret_cast<uint16_t*>(ws + w.kp), *vpk = reinterpret_cast<uint16_t*>(ws + w.vp);
     int mask_stride = 1;                       // product of the strides of the blocks before block k
-    // the feed-forward modules as one kernel each where the width is built (sxf_ffn.hip), and the row-local work between attention and the depthwise
-    // convolution as two kernels per block (sxf_chain.hip); a debug trace wants the intermediate states, which the chains never write: per-module kernels
-    // then (option trace_fused: the chains stay, and the trace holds what they write to memory)
-    const bool ffn_fused = fused && e->split_ffn;
-    const bool chains = ffn_fused && e->split_chain && !tr_modules;
-    bool head_done = false;                    // this block's FFN1 + Q / K / V projections ran at the end of the previous block's chain A
+    // the row-local work between attention and the depthwise convolution as two kernels per block, and a feed-forward module outside them as one (sxf_chain.hip);
+    // a debug trace wants the intermediate states, which the chains never write: per-module kernels then (option trace_fused: the chains stay, and the trace
+    // holds what they write to memory)
     for (int k = 0; k < nb; ++k) {
+        const ExactBlockRoutes& rt = routes[k];
         const EcBlock& b = e->blocks[k];
         const BlockW& W = e->bw[k];
         const int T = s.Tin[k], To = s.Tout[k], D = b.dim_model, De = b.dim_expand;          // ragged: the LONGEST utterance's frames
@@ -224,10 +233,10 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
         const std::string m = p + ".multi_head_self_attention_module", cm = p + ".convolution_module.layers";
         // Rows of Q / K / V: rectangular (b, t) -> b Tp + t, ragged: the identity (the residual stream keeps every utterance group-padded)
         const int qr = rg ? 0 : T, qp = rg ? 0 : Tp;
-        const bool chain_in = chains && W.xc_in, chain_out = chains && W.xc_out;
-        if (head_done) {
+        const bool head_done = rt.tail == TAIL_FULL;      // the next block's FFN1 + Q / K / V projections run at the end of this block's chain A
+        if (rt.head == HEAD_PREV_TAIL) {
             trace(k, "x_ffn1", x, M, D);      // nothing to run: x is the stream after FFN1, Q / K / V are written
-        } else if (chain_in) {
+        } else if (rt.head == HEAD_CHAIN) {
             SxcAParams cp{};
             cp.head = 1; cp.y = x; cp.M = M; cp.D = D; cp.w_f1 = W.xc_f[0]; cp.nch_f1 = W.xf_nch[0]; cp.b_f1 = W.xf_b2[0]; cp.w_qkv = W.xc_qkv;
             cp.q = q; cp.qkv_stride = w.qkv_stride; cp.q_rows = qr; cp.q_pitch = qp; cp.qkv_bytes = (2 * w.qkv_stride + (size_t)s.Mq[k] * D) * 4;
@@ -236,14 +245,7 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
             trace(k, "x_ffn1", x, M, D);
         } else {
             // ---- x += 1/2 FFN1(LN(x))   (blocks.py:122; modules.py:385-392)
-            if (W.xf_img[0] && ffn_fused) {
-                SxfFfnParams fp{};
-                fp.X = x; fp.ldx = D; fp.Y = x; fp.ldy = D; fp.wimg = W.xf_img[0]; fp.b2 = W.xf_b2[0]; fp.M = M; fp.D = D; fp.nchunk = W.xf_nch[0];
-                PROF(PC_GEMM_FFN, 4.0 * M * (double)D * D * b.ff_ratio, (double)M * D * 8 + 16.0 * D * D * b.ff_ratio);
-                EC_TRY(launch_sxf_ffn(fp, st));
-            } else {
-                EC_TRY(xffn(e, st, x, M, D, b.ff_ratio, W.ln_ffn1, p + ".feed_forward_module1", a, hb));
-            }
+            EC_TRY(xffn_module(e, st, rt.ffn1_fused, k, 0, x, x, M, nullptr, a, hb));
             trace(k, "x_ffn1", x, M, D);
             // ---- x += MHSA(LN(x))   (blocks.py:125-126; attentions.py:549-718).  Chunk-padding rows of Q / K / V (attentions.py:107-138, 671) are never written:
             //      the fused attention kernel substitutes them, the per-module ones read the zeros of a memset
@@ -262,7 +264,6 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
                 EC_TRY(xgemm(e, st, a, D, M, m + ".mhsa.value_layer", D, D, v, D, proj));
             }
         }
-        head_done = false;
         // rows (b, t) -> b Tp + t of the projections (chunk-padding rows: whatever the workspace held)
         ftrace(k, "q", q, s.Mq[k], D); ftrace(k, "k", kk, s.Mq[k], D); ftrace(k, "v", v, s.Mq[k], D);
         if (Tp > b.max_pos) return fail("sequence longer than max_pos_encoding");
@@ -292,11 +293,11 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
             ap.att = (int)e->att_out.size() == nb ? e->att_out[k] : nullptr;
             ap.band_l = bd.l; ap.band_r = bd.r;
             PROF(PC_ATTENTION, 2.0 * B * H * (double)Tg * Tg * d * 3.0, (double)M * D * 4 * 5);
-            if (e->exact_split && sx_attention_supported(d) && (long long)B * H <= 65535) EC_TRY(launch_sx_attention(ap, F32(w.scores), st));
+            if (exact_attention_split(e, d, (long long)B * H)) EC_TRY(launch_sx_attention(ap, F32(w.scores), st));
             else EC_TRY(launch_ex_attention(ap, st));
         }
         ftrace(k, "att_o", o, s.Mq[k], D);
-        if (chain_in) {       // x += O Wo^T + bo;  g = GLU(LN(x) Wp1^T + bp1)
+        if (rt.chain_b) {     // x += O Wo^T + bo;  g = GLU(LN(x) Wp1^T + bp1)
             SxcBParams cp{};
             cp.o = o; cp.o_rows = qr; cp.o_pitch = qp; cp.x = x; cp.g = g; cp.M = M; cp.D = D; cp.De = De;
             cp.w_o = W.xc_wo; cp.b_o = W.xc_bo; cp.w_p1 = W.xc_p1; cp.nch_p1 = W.xc_nch_p1;
@@ -339,19 +340,18 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
         }
         const bool to_out = k == nb - 1 && !rg;       // ragged: the last block's rows stay in the workspace; emit_ragged pads them into `out`
         float* xo = to_out ? out : xalt;
-        if (chain_out) {      // x = xres + C Wp2^T + bp2;  x += 1/2 FFN2(LN(x));  xo = LN(x);  [next block: xo += 1/2 FFN1(LN(xo)); Q | K | V]
+        if (rt.tail != TAIL_MODULES) {      // x = xres + C Wp2^T + bp2;  x += 1/2 FFN2(LN(x));  xo = LN(x);  [next block: xo += 1/2 FFN1(LN(xo)); Q | K | V]
             SxcAParams cp{};
             cp.tail = 1; cp.c = cbuf; cp.xres = x; cp.y = xo; cp.M = Mo; cp.D = De;
             cp.w_p2 = W.xc_p2; cp.b_p2 = W.xc_bp2; cp.w_f2 = W.xc_f[1]; cp.nch_f2 = W.xf_nch[1]; cp.b_f2 = W.xf_b2[1]; cp.ln_g = W.ln_out.g; cp.ln_b = W.ln_out.b;
             double fl = Mo * (double)De * De * (2.0 + 4.0 * b.ff_ratio), by = (double)Mo * De * 16 + De * (double)De * (4.0 + 16.0 * b.ff_ratio);
-            if (k + 1 < nb && e->bw[k + 1].xc_in && e->blocks[k + 1].dim_model == De && (int)s.Min[k + 1] == Mo) {
+            if (head_done) {
                 const EcBlock& bn = e->blocks[k + 1];
                 const BlockW& Wn = e->bw[k + 1];
                 const int Tn = s.Tin[k + 1];
                 cp.head = 1; cp.w_f1 = Wn.xc_f[0]; cp.nch_f1 = Wn.xf_nch[0]; cp.b_f1 = Wn.xf_b2[0]; cp.w_qkv = Wn.xc_qkv;
                 cp.q = q; cp.qkv_stride = w.qkv_stride; cp.q_rows = rg ? 0 : Tn; cp.q_pitch = rg ? 0 : ec_round_up(Tn, bn.group_size); cp.qkv_bytes = (2 * w.qkv_stride + (size_t)s.Mq[k + 1] * De) * 4;
                 fl += Mo * (double)De * De * (4.0 * bn.ff_ratio + 6.0); by += (double)Mo * De * 20 + De * (double)De * (16.0 * bn.ff_ratio + 12.0);
-                head_done = true;
             }
             PROF(PC_GEMM_FFN, fl, by);
             EC_TRY(launch_sxc_a(cp, st));
@@ -359,16 +359,7 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
             EC_TRY(xresid(e, st, cbuf, De, Mo, cm + ".7", De, De, x, 1.0f));
             trace(k, "x_conv", x, Mo, De);
             // ---- x += 1/2 FFN2(LN(x)); x = LN(x)   (blocks.py:132-135)
-            if (W.xf_img[1] && ffn_fused) {
-                SxfFfnParams fp{};
-                fp.X = x; fp.ldx = De; fp.Y = xo; fp.ldy = De; fp.wimg = W.xf_img[1]; fp.b2 = W.xf_b2[1]; fp.M = Mo; fp.D = De; fp.nchunk = W.xf_nch[1];
-                fp.ln_g = W.ln_out.g; fp.ln_b = W.ln_out.b;
-                PROF(PC_GEMM_FFN, 4.0 * Mo * (double)De * De * b.ff_ratio, (double)Mo * De * 8 + 16.0 * De * De * b.ff_ratio);
-                EC_TRY(launch_sxf_ffn(fp, st));
-            } else {
-                EC_TRY(xffn(e, st, x, Mo, De, b.ff_ratio, W.ln_ffn2, p + ".feed_forward_module2", a, hb));
-                EC_TRY(xlayernorm(e, st, x, Mo, De, W.ln_out, xo));
-            }
+            EC_TRY(xffn_module(e, st, rt.ffn2_fused, k, 1, x, xo, Mo, &W.ln_out, a, hb));
         }
         if (!to_out) std::swap(x, xalt);
         if (!head_done) trace(k, "out", xo, Mo, De);      // a merged head has already made xo the next block's x_ffn1

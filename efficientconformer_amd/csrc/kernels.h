@@ -257,18 +257,6 @@ int launch_sxf_pack_kv(const SxfAttnParams& p, hipStream_t s);       // K / V (f
 // E = pos_layer(R) fp32 [erows_grouped * G][D] -> its image, the positional bias (v - u) E^T in column d
 int launch_sxf_pack_e(const float* e, const float* u, const float* vb, int erows_grouped, int H, int G, int D, int d, uint16_t* ep, hipStream_t s);
 int launch_sxf_attention(const SxfAttnParams& p, hipStream_t s);
-// FeedForwardModule + half-step residual (+ optional block-final LayerNorm) as one split-precision kernel (sxf_ffn.hip)
-struct SxfFfnParams {
-    const float* X; int ldx;       // residual stream in [M][ldx]
-    float* Y; int ldy;             // out (may alias X): x + 1/2 FFN(LN(x)), or LayerNorm of that when ln_g != null
-    const uint16_t* wimg;          // weight image, chunk-major: per 32 hidden units [W1 hi 32 x DP1 | W1 lo | W2 hi DP2 x 32 | W2 lo] fp16 (pack_sxf_ffn in encoder.hip:
-                                   // pre-norm gamma / beta and b1 folded into W1 / its column D, W2 pre-scaled by 1/2 with its k order permuted to the accumulator layout)
-    const float* b2;               // [DP2] b2 / 2, zero padded
-    const float *ln_g, *ln_b;      // optional LayerNorm applied to the result (blocks.py:135), [D]
-    int M, D, nchunk;
-    int ablate;                    // timing-only ablations (tools/sxf_ffn_probe.py through the diagnostic library; 0 in the product): 1 no first product, 2 no Swish,
-                                   // 4 no second product, 8 no weight stream after the first chunk, 16 no per-chunk barrier
-};
 // Conv2dSubsampling (one layer) + transpose / flatten + Linear as one kernel, chunked over (output frequency, 32 channels) (sub_chunked.h): bf16 (sublinear3.hip)
 // and split precision (sxf_sub.hip: fp16 operand halves at 2^10)
 struct SubChunkParams {
@@ -293,10 +281,6 @@ inline int sub_chunked_tiles(int N) {
 }
 int launch_sublinear3(const SubChunkParams& p, hipStream_t s);
 int launch_sxf_sublin(const SubChunkParams& p, hipStream_t s);
-void sxf_ffn_shape(int D, int* ks1, int* nt2);
-bool sxf_ffn_supported(int D);
-size_t sxf_ffn_image_halfs(int D, int F);
-int launch_sxf_ffn(const SxfFfnParams& p, hipStream_t s);
 // Split-precision row-local chains (sxf_chain.hip): the work of a block between attention and the depthwise convolution as one kernel each.  Weight images: fp16
 // (h | l) planes at the weight scale 2^10, chunk-major, k order = the accumulator layout's (pack_sxc_* in encoder.hip); "F1" = 32 outputs x all inputs per chunk with
 // the bias in column D, "F2" = all outputs x 32 inputs per chunk, an FFN image = both per chunk of 32 hidden units.
@@ -309,14 +293,14 @@ struct SxcBParams {                // chain B: x += O Wo^T + bo;  g = GLU(LN(x) 
     const uint16_t* w_p1; int nch_p1;          // F1 image of pointwise-1 (conv-module LayerNorm folded in): chunk pairs (32 value rows, their 32 gate rows)
 };
 struct SxcAParams {                // chain A.  tail: x = xres + C Wp2^T + bp2; x += 1/2 FFN2(LN(x)); y = LN(x).  head: y += 1/2 FFN1(LN(y)); Q | K | V = LN(y) Wqkv^T + b
-    int tail, head;                // at least one
+    int tail, head;                // neither: one FeedForwardModule alone, y = xres + 1/2 FFN(LN(xres)) on the w_f2 image, then y = LN(y) where ln_g is given
     const float* c;                // tail: conv-module activations [M][D] (depthwise conv output)
-    const float* xres;             // tail: residual input [M][D] (the stream, or conv_res of it)
+    const float* xres;             // tail: residual input [M][D] (the stream, or conv_res of it); the module alone: its input rows (may be y: in place)
     float* y;                      // [M][D]: tail: the block's output (scratch for x on the way); head: updated in place (head alone: the input stream)
     int M, D;
     const uint16_t* w_p2; const float* b_p2;   // F2 image of pointwise-2 + bias
-    const uint16_t* w_f2; int nch_f2; const float* b_f2;     // FFN2 image (pre-norm folded), b2 / 2
-    const float *ln_g, *ln_b;      // block-final LayerNorm [D]
+    const uint16_t* w_f2; int nch_f2; const float* b_f2;     // FFN2 image (pre-norm folded), b2 / 2, chunks of 32 hidden units; the module alone: whichever FFN it is
+    const float *ln_g, *ln_b;      // block-final LayerNorm [D] (the module alone: optional)
     const uint16_t* w_f1; int nch_f1; const float* b_f1;     // head: FFN1 image of the NEXT block, b2 / 2
     const uint16_t* w_qkv;         // head: F1 image of Q | K | V (each padded to 32 ceil(D / 32) rows; attention pre-norm folded)
     float* q; size_t qkv_stride;   // head: Q at q, K at q + qkv_stride, V at q + 2 qkv_stride (fp32 [.][D])
@@ -324,6 +308,7 @@ struct SxcAParams {                // chain A.  tail: x = xres + C Wp2^T + bp2; 
     int q_rows, q_pitch;           // head: row remap of the Q / K / V rows (as o_rows / o_pitch)
 };
 bool sxc_supported(int D);
+void sxc_shape(int D, int* ks, int* nt);      // the instance of width D: k-steps of an F1 product (D columns + the bias column), 32-row output tiles
 int launch_sxc_b(const SxcBParams& p, hipStream_t s);
 int launch_sxc_a(const SxcAParams& p, hipStream_t s);
 // fp32 depthwise conv + folded BatchNorm + Swish; rc != null: per-utterance row ranges (tcap_max = the longest utterance's padded output rows)

@@ -7,7 +7,7 @@
 #include <cmath>
 #include <cstring>
 
-// Largest |value x 2^10| the fused split images (sxf_sub / sxf_ffn / sxf_chain) hold as two fp16 halves (fp16 max 65504): |w| < 63.48 after
+// Largest |value x 2^10| the fused split images (sxf_sub / sxf_chain) hold as two fp16 halves (fp16 max 65504): |w| < 63.48 after
 // folding.  An image with a value beyond it is not built - that block / the front end runs the per-module split kernels - and the per-module
 // images (h = fp16(w)) refuse |w| >= kSplitImgMax itself (split-mode operand envelopes).  Nothing is clamped.
 constexpr float kSplitImgMax = 65000.f;

@@ -298,25 +298,25 @@ bool split_pair_image(const std::vector<const float*>& rows, int K, Img* hi, Img
     return true;
 }
 
-// F1 chunks (sxf_ffn.hip, sxf_chain.hip), chunk c at base + c * stride: 32 output rows (of `rows`, 32 per chunk; null = padding) x DP1 columns, h plane then l plane
-// (f16_pair_s10); gamma folded into the weights, W beta + bias in column K.  acc_order: columns in accumulator order (sxf_chain.hip: the operand is a converted
-// accumulator tile); else natural order and every folded value rounded to fp32 first (sxf_ffn.hip's image).  false: an element was refused
-bool f1_chunk(Img& img, size_t base, size_t stride, int DP1, int K, const std::vector<const float*>& rows, const std::vector<float>& bias, const float* g, const float* beta, bool acc_order = true) {
+// F1 chunks (sxf_chain.hip), chunk c at base + c * stride: 32 output rows (of `rows`, 32 per chunk; null = padding) x DP1 columns, h plane then l plane
+// (f16_pair_s10); gamma folded into the weights, W beta + bias in column K; columns in accumulator order (the operand is a converted accumulator tile).
+// false: an element was refused
+bool f1_chunk(Img& img, size_t base, size_t stride, int DP1, int K, const std::vector<const float*>& rows, const std::vector<float>& bias, const float* g, const float* beta) {
     bool ok = true;
     for (size_t r = 0; r < rows.size(); ++r) {
         if (!rows[r]) continue;
         uint16_t* at = &img[base + r / 32 * stride + r % 32 * DP1];
-        auto put = [&](int col, double v) { ok &= f16_pair_s10(acc_order ? v : (double)(float)v, at + col, at + 32 * DP1 + col); };
+        auto put = [&](int col, double v) { ok &= f16_pair_s10(v, at + col, at + 32 * DP1 + col); };
         double bsum = bias[r];
         for (int col = 0; col < DP1; ++col) {
-            const int f = acc_order ? acc16(col) : col;
+            const int f = acc16(col);
             if (f >= K) continue;
             const double wv = rows[r][f];
             if (beta) bsum += wv * beta[f];
             put(col, g ? wv * g[f] : wv);
         }
         for (int col = 0; col < DP1; ++col)
-            if ((acc_order ? acc16(col) : col) == K) put(col, bsum);
+            if (acc16(col) == K) put(col, bsum);
     }
     return ok;
 }
@@ -333,16 +333,16 @@ bool f2_chunk(Img& img, size_t base, size_t stride, int DP2, int nch, const floa
     return ok;
 }
 
-// One FeedForwardModule at width D as per 32 hidden units an F1 chunk (pre-norm folded) + an F2 chunk (W2 / 2): xf_img (sxf_ffn.hip, natural F1 order) and
-// xc_f (sxf_chain.hip, accumulator order); kernels.h: SxfFfnParams.  Empty: a folded value the image cannot hold
-Img ffn_image(const float* g, const float* beta, const float* w1, const float* b1, const float* w2, int D, int F, bool acc_order) {
-    int ks, nt; sxf_ffn_shape(D, &ks, &nt);
+// One FeedForwardModule at width D as per 32 hidden units an F1 chunk (pre-norm folded) + an F2 chunk (W2 / 2): xc_f (sxf_chain.hip; kernels.h: SxcAParams
+// w_f1 / w_f2).  Empty: a folded value the image cannot hold
+Img ffn_image(const float* g, const float* beta, const float* w1, const float* b1, const float* w2, int D, int F) {
+    int ks, nt; sxc_shape(D, &ks, &nt);
     const int DP1 = 16 * ks, DP2 = 32 * nt, nch = (F + 31) / 32;
     const size_t per = (size_t)64 * (DP1 + DP2);
     std::vector<const float*> rows(32 * nch, nullptr); std::vector<float> bias(32 * nch, 0.f);
     for (int h = 0; h < F; ++h) { rows[h] = w1 + (size_t)h * D; bias[h] = b1[h]; }
     Img img((size_t)nch * per, 0);
-    if (!f1_chunk(img, 0, per, DP1, D, rows, bias, g, beta, acc_order) || !f2_chunk(img, (size_t)64 * DP1, per, DP2, nch, w2, D, F, 0.5)) img.clear();
+    if (!f1_chunk(img, 0, per, DP1, D, rows, bias, g, beta) || !f2_chunk(img, (size_t)64 * DP1, per, DP2, nch, w2, D, F, 0.5)) img.clear();
     return img;
 }
 
@@ -714,49 +714,36 @@ int pack_split_front_end(EcEncoder* e) {
     return 0;
 }
 
-// One FeedForwardModule's image for the fused split kernels, or empty (a tensor missing / mis-shaped, or a folded value the image cannot hold)
-Img split_ffn_image(const EcEncoder* e, size_t k, int which, bool acc_order, const HostTensor** b2_out = nullptr) {
+// One FeedForwardModule for sxf_chain.hip: its image xc_f[which], b2 / 2 and the chunk count.  Nothing is set where the width is not built, a tensor is missing
+// or mis-shaped, or a folded value is beyond the image's range: that FFN runs as LayerNorm + two split GEMMs, and no chain of its side is built
+void pack_split_ffn(EcEncoder* e, size_t k, int which) {
     const int D = which ? e->blocks[k].dim_expand : e->blocks[k].dim_model, F = D * e->blocks[k].ff_ratio;
     const std::string pf = "blocks." + std::to_string(k) + (which ? ".feed_forward_module2.layers." : ".feed_forward_module1.layers.");
     const HostTensor *g = find(e, pf + "0.weight"), *bt = find(e, pf + "0.bias"), *w1 = find(e, pf + "1.weight"), *b1 = find(e, pf + "1.bias"), *w2 = find(e, pf + "4.weight"), *b2 = find(e, pf + "4.bias");
-    if (!sized(g, D) || !sized(bt, D) || !sized(w1, (int64_t)F * D) || !sized(b1, F) || !sized(w2, (int64_t)F * D) || (b2_out && !sized(b2, D))) return Img();
-    if (b2_out) *b2_out = b2;
-    return ffn_image(fdata(g), fdata(bt), fdata(w1), fdata(b1), fdata(w2), D, F, acc_order);
-}
-
-// split mode: weight images of the fused FFN kernel (sxf_ffn.hip); an FFN without an image (and the chains using it) runs per-module
-int pack_split_ffn(EcEncoder* e) {
-    for (size_t k = 0; k < e->blocks.size(); ++k)
-        for (int which = 0; which < 2; ++which) {
-            const int D = which ? e->blocks[k].dim_expand : e->blocks[k].dim_model, F = D * e->blocks[k].ff_ratio;
-            const HostTensor* b2 = nullptr;
-            if (!sxf_ffn_supported(D)) continue;
-            const Img img = split_ffn_image(e, k, which, false, &b2);
-            if (img.empty()) continue;
-            int ks1, nt2; sxf_ffn_shape(D, &ks1, &nt2);
-            e->bw[k].xf_img[which] = upload(e, img); e->bw[k].xf_b2[which] = upload(e, padded(b2->data, 32 * nt2, 0.5f)); e->bw[k].xf_nch[which] = (F + 31) / 32;
-        }
-    return 0;
+    if (!sxc_supported(D) || !sized(g, D) || !sized(bt, D) || !sized(w1, (int64_t)F * D) || !sized(b1, F) || !sized(w2, (int64_t)F * D) || !sized(b2, D)) return;
+    const Img img = ffn_image(fdata(g), fdata(bt), fdata(w1), fdata(b1), fdata(w2), D, F);
+    if (img.empty()) return;
+    int ks, nt; sxc_shape(D, &ks, &nt);
+    BlockW& W = e->bw[k];
+    W.xf_b2[which] = upload(e, padded(b2->data, 32 * nt, 0.5f)); W.xf_nch[which] = (F + 31) / 32; W.xc_f[which] = upload(e, img);
 }
 
 // split mode: weight images of the split chains (sxf_chain.hip; kernels.h: SxcBParams / SxcAParams), all in accumulator order - every operand of a product is a
 // converted accumulator tile: out-proj / pointwise-2 (F2 chunks), pointwise-1 with GLU row pairs / Q | K | V (F1 chunks, pre-norm folded), the two FFN modules.
-// A part with a folded value its images cannot hold is not built
+// A part with a folded value its images cannot hold is not built; xc_in / xc_out: every image of that side exists.  An FFN image stands on its own - the module
+// runs as the chain kernel's FFN-only form where its siblings were refused
 int pack_split_chains(EcEncoder* e) {
     for (size_t k = 0; k < e->blocks.size(); ++k) {
         const EcBlock& b = e->blocks[k];
         BlockW& W = e->bw[k];
         const int D = b.dim_model, De = b.dim_expand;
         const std::string pb = "blocks." + std::to_string(k), mh = pb + ".multi_head_self_attention_module.", cm = pb + ".convolution_module.layers.";
-        auto ffn = [&](int which) -> const uint16_t* {
-            const Img img = W.xf_b2[which] ? split_ffn_image(e, k, which, true) : Img();
-            return img.empty() ? nullptr : upload(e, img);
-        };
+        pack_split_ffn(e, k, 0); pack_split_ffn(e, k, 1);
         const HostTensor *wo = find(e, mh + "mhsa.output_layer.weight"), *bo = find(e, mh + "mhsa.output_layer.bias"), *lg = find(e, cm + "0.weight"), *lb = find(e, cm + "0.bias"),
                          *w1 = find(e, cm + "2.weight"), *b1 = find(e, cm + "2.bias"), *ag = find(e, mh + "norm.weight"), *ab = find(e, mh + "norm.bias"), *wq[3], *bq[3];
-        if (sxc_supported(D) && sxf_ffn_supported(D) && sized(wo, D * D) && sized(bo, D) && sized(lg, D) && sized(lb, D) && sized(w1, (int64_t)2 * De * D) && sized(b1, 2 * De) &&
+        if (sxc_supported(D) && sized(wo, D * D) && sized(bo, D) && sized(lg, D) && sized(lb, D) && sized(w1, (int64_t)2 * De * D) && sized(b1, 2 * De) &&
             sized(ag, D) && sized(ab, D) && find_qkv(e, mh + "mhsa.", D, wq, bq)) {
-            int ks, nt; sxf_ffn_shape(D, &ks, &nt);
+            int ks, nt; sxc_shape(D, &ks, &nt);
             const int DP1 = 16 * ks, DP2 = 32 * nt, nte = (De + 31) / 32;
             Img io((size_t)nt * 64 * DP2, 0), ip((size_t)2 * nte * 64 * DP1, 0), iq((size_t)3 * nt * 64 * DP1, 0);
             std::vector<const float*> prow, qrow; std::vector<float> pbias, qbias;
@@ -765,18 +752,16 @@ int pack_split_chains(EcEncoder* e) {
             if (f2_chunk(io, 0, (size_t)64 * DP2, DP2, nt, fdata(wo), D, D, 1.0) && f1_chunk(ip, 0, (size_t)64 * DP1, DP1, D, prow, pbias, fdata(lg), fdata(lb)) &&
                 f1_chunk(iq, 0, (size_t)64 * DP1, DP1, D, qrow, qbias, fdata(ag), fdata(ab))) {
                 W.xc_wo = upload(e, io); W.xc_bo = upload(e, padded(bo->data, DP2)); W.xc_p1 = upload(e, ip); W.xc_nch_p1 = 2 * nte; W.xc_qkv = upload(e, iq);
-                W.xc_f[0] = ffn(0);
                 W.xc_in = W.xc_f[0] != nullptr;
             }
         }
-        if (sxc_supported(De) && sxf_ffn_supported(De)) {
-            int ks, nt; sxf_ffn_shape(De, &ks, &nt);
+        if (sxc_supported(De)) {
+            int ks, nt; sxc_shape(De, &ks, &nt);
             const int DP2 = 32 * nt;
             const HostTensor *w2 = find(e, cm + "7.weight"), *b2 = find(e, cm + "7.bias");
             Img i2((size_t)nt * 64 * DP2, 0);
             if (sized(w2, (int64_t)De * De) && sized(b2, De) && f2_chunk(i2, 0, (size_t)64 * DP2, DP2, nt, fdata(w2), De, De, 1.0)) {
                 W.xc_p2 = upload(e, i2); W.xc_bp2 = upload(e, padded(b2->data, DP2));
-                W.xc_f[1] = ffn(1);
                 W.xc_out = W.xc_f[1] != nullptr;
             }
         }
@@ -794,6 +779,6 @@ int pack_encoder(EcEncoder* e) {
     if ((rc = pack_fp32_tensors(e))) return rc;
     e->xsplit.clear();
     e->xsub = SubChunkImg{};
-    if (e->exact_split && ((rc = pack_split_front_end(e)) || (rc = pack_split_modules(e)) || (rc = pack_split_ffn(e)) || (rc = pack_split_chains(e)))) return rc;
+    if (e->exact_split && ((rc = pack_split_front_end(e)) || (rc = pack_split_modules(e)) || (rc = pack_split_chains(e)))) return rc;
     return pack_fp32_tables(e);
 }

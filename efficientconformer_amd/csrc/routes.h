@@ -1,6 +1,6 @@
-// Which kernel every step of the bf16 forward runs: pure functions of the handle after packing (options and "image exists" pointers) and of the two batch
-// properties that matter (ragged, streaming).  The ONE place that decides: forward_bf16.hip's schedule and per-module entries, its workspace layout and
-// pack.hip's "which images to build" read these and hold no predicate of their own.  Host only, no HIP call; nothing here is cached on the handle - a forward
+// Which kernel every step of a forward runs - the bf16 schedule, and in its last section the label-exact split schedule: pure functions of the handle after packing (options and "image exists" pointers) and of the two batch
+// properties that matter (ragged, streaming).  The ONE place that decides: forward_bf16.hip's schedule and per-module entries, its workspace layout,
+// pack.hip's "which images to build" and forward_exact.hip's schedule read these and hold no predicate of their own.  Host only, no HIP call; nothing here is cached on the handle - a forward
 // computes its routes on entry (a handful of integer compares per block), so an option set between two forwards needs no invalidation.
 #pragma once
 #include "encoder_state.h"
@@ -144,3 +144,63 @@ inline AttentionRoute attention_route(const EcEncoder* e, int dpad, bool ragged,
     if (ragged || streaming) return {1, nullptr};
     return {v2 ? e->attention_v2 : 0, nullptr};
 }
+
+// ------------------------------------------------------------------ label-exact split schedule (forward_exact.hip; fp32 mode = its per-module family)
+// Split mode with every block on widths the fused kernels take (sxf.hip attention at the head width, 16-byte rows): the sxf_* family can run at all.
+// encoder.hip's ragged and streaming entries refuse a label-exact forward without it
+inline bool split_fused_ok(const EcEncoder* e) {
+    if (!e->exact_split) return false;
+    for (const EcBlock& b : e->blocks)
+        if (!sxf_attention_supported(b.group_size * b.dim_model / b.num_heads) || b.dim_model % 4 || b.dim_expand % 4) return false;
+    return true;
+}
+
+// Per forward.  traced: a debug trace is recorded (it wants the intermediate states the fused kernels keep in registers, unless option trace_fused keeps the
+// forward as it runs untraced); maps: attention maps were requested (a by-product of the scores in memory: per-module attention only)
+struct ExactForwardRoutes {
+    bool fused;            // kernel family: sxf*.hip (ragged batches, causal kernels, the E cache) | per-module exact.hip / split.hip
+    bool sublin;           // Conv2dSubsampling + Linear as sxf_sub.hip, else conv kernel(s) + GEMM [+ row gather]
+    bool ffn;              // a stand-alone FeedForwardModule as the FFN-only form of sxc_a_kernel where its image exists (option split_ffn), else LayerNorm + two GEMMs
+    bool chains;           // the row-local chains of sxf_chain.hip where their images exist (options split_chain and split_ffn: the chains contain the modules)
+    const char* refusal;   // no kernel takes this forward: the error text
+};
+inline ExactForwardRoutes exact_forward_routes(const EcEncoder* e, bool traced, bool maps) {
+    const bool tr_modules = traced && !e->trace_fused;
+    ExactForwardRoutes f;
+    f.fused = split_fused_ok(e) && !maps;
+    f.sublin = f.fused && e->split_sublin && e->xsub.wimg && e->cfg.sub_layers == 1 && !tr_modules;
+    f.ffn = f.fused && e->split_ffn;
+    f.chains = f.ffn && e->split_chain && !tr_modules;
+    // finite left / right contexts: the band mask is part of every label-exact attention kernel; `causal` (causal relative tables, causal depthwise
+    // padding: attentions.py:506, 1243-1247; layers.py:97-101) exists in the fused family only
+    f.refusal = !f.fused && e->cfg.causal ? "the label-exact modes have no causal kernels (causal relative tables / depthwise pre-padding): bf16 path only" : nullptr;
+    return f;
+}
+
+// Per block, the row-local work as in BlockRoutes.  rows_carry: block k + 1 reads exactly the rows block k writes (Min[k + 1] == Mout[k]) - a shape fact the
+// caller knows; without it a tail cannot take the next head along
+struct ExactBlockRoutes {
+    HeadRoute head;        // FFN1 + Q/K/V: in the previous block's chain A / chain A's head form / per-module kernels
+    bool ffn1_fused;       // HEAD_MODULES: FFN1 on the FFN-only form, else LayerNorm + two GEMMs
+    bool chain_b;          // out-projection + LayerNorm + pointwise-1 / GLU as sxc_b_kernel, else per-module kernels
+    TailRoute tail;        // pointwise-2 + FFN2 + block norm: chain A with the next block's head / chain A's tail form / per-module kernels
+    bool ffn2_fused;       // TAIL_MODULES: FFN2 + block norm on the FFN-only form, else LayerNorm + two GEMMs + LayerNorm
+};
+inline TailRoute exact_tail_route(const EcEncoder* e, const ExactForwardRoutes& f, size_t k, bool rows_carry) {
+    if (!(f.chains && e->bw[k].xc_out)) return TAIL_MODULES;
+    return k + 1 < e->blocks.size() && e->bw[k + 1].xc_in && e->blocks[k + 1].dim_model == e->blocks[k].dim_expand && rows_carry ? TAIL_FULL : TAIL_ONLY;
+}
+inline ExactBlockRoutes exact_block_routes(const EcEncoder* e, const ExactForwardRoutes& f, size_t k, bool rows_carry_in, bool rows_carry_out) {
+    const BlockW& W = e->bw[k];
+    const bool chain_d = f.chains && W.xc_in;
+    ExactBlockRoutes r;
+    r.head = k > 0 && exact_tail_route(e, f, k - 1, rows_carry_in) == TAIL_FULL ? HEAD_PREV_TAIL : (chain_d ? HEAD_CHAIN : HEAD_MODULES);
+    r.ffn1_fused = f.ffn && W.xc_f[0];
+    r.chain_b = chain_d;
+    r.tail = exact_tail_route(e, f, k, rows_carry_out);
+    r.ffn2_fused = f.ffn && W.xc_f[1];
+    return r;
+}
+
+// Per-module attention of head width d on batch_heads = B H (score tiles ride in a 16-bit grid dimension): split.hip's sx_attention, else exact.hip's ex_attention
+inline bool exact_attention_split(const EcEncoder* e, int d, long long batch_heads) { return e->exact_split && sx_attention_supported(d) && batch_heads <= 65535; }

@@ -32,7 +32,7 @@ __device__ __forceinline__ void split2(float x0, float x1, uint32_t& hi, uint32_
     lo = cl.u;
 }
 
-// Same-scale variant (round 6, sxf_ffn.hip): x S = h + l with BOTH halves at the scale S (a power of two that puts the operand's usual magnitude around
+// Same-scale variant (round 6, sxf_chain.hip / sxf_sub.hip / sxf.hip): x S = h + l with BOTH halves at the scale S (a power of two that puts the operand's usual magnitude around
 // 2^5 .. 2^12, so l - 2^-11 of h - is a normal fp16 number for every element that matters: an element so small that its l underflows contributes < 2^-25 S^-1
 // absolutely).  The three products h h' + h l' + l h' then share ONE fp32 accumulator at the scale S S' (undone by an exact multiply at the end): no correction
 // accumulator, no fold - the sum rounds like the fp32 accumulation of the reference's own GEMM.  Inputs are the already scaled values.

@@ -1,14 +1,16 @@
 // Split-precision row-local chains (round 6): everything of a Conformer block between two non-row-local kernels (attention, depthwise convolution) as ONE kernel,
-// in the arithmetic of sxf_ffn.hip (fp32 tensors; every product on the fp16 matrix pipe with same-scale operand halves x S = h + l, three MFMAs per product, one fp32
+// and a FeedForwardModule that stands alone as one more form of the same kernel (fp32 tensors; every product on the fp16 matrix pipe with same-scale operand halves x S = h + l, three MFMAs per product, one fp32
 // accumulator).  Reference: blocks.py:119-137, modules.py:385-395, 511-522, attentions.py:651-686, 716.
 //
 //   chain B    : x += O Wo^T + bo (attentions.py:716, blocks.py:126);  g = GLU(LN(x) Wp1^T + bp1)  (modules.py:511-515)
 //   chain A    : tail  x = xres + C Wp2^T + bp2 (modules.py:519-522, blocks.py:129);  x += 1/2 FFN2(LN(x));  y = LN(x)  (blocks.py:132-135)
 //                head  y += 1/2 FFN1(LN(y)) (next block, blocks.py:122);  Q | K | V = LN(y) Wqkv^T + b  (attentions.py:651-653)
 //                (tail alone: the last block; head alone: the first block)
+//                neither  y = x + 1/2 FFN(LN(x)) [; y = LN(y)]: a module outside a chain (option split_chain = 0, a trace without trace_fused, a block whose other
+//                chain images were refused), in place (FFN1) or into the block's output buffer (FFN2 + the block norm), on the same image as inside a chain
 //
 // Before: nine launches per block for this work (LayerNorm x 2, GEMM x 4, GLU, FFN x 2), each paying its own prologue / epilogue over the fp32 rows at one wave per
-// SIMD - `tools/sxf_ffn_probe.py`: 40 us of a 98 us FFN launch at D = 120 are there with every product removed.  Here a wave keeps its 32 rows TRANSPOSED in the
+// SIMD - profiles/r6_13_ffn_probe.txt: 40 us of a 98 us FFN launch at D = 120 are there with every product removed.  Here a wave keeps its 32 rows TRANSPOSED in the
 // accumulator layout from the first load to the last store:
 //   * a row tile enters through `load_acc` (the accumulator layout: lane (lr, kh) holds features 32 t + 8 rq + 4 kh .. + 3 of row lr) and becomes split B fragments by
 //     `acc_to_frags` - so does every accumulator of a finished product, which makes ONE k order for every weight image: inside a 16-block, position 8 kh + e holds
@@ -27,7 +29,7 @@ namespace {
 
 using namespace sx;
 
-constexpr float SA = 256.0f, SW = 1024.0f, UNS = 1.0f / (256.0f * 1024.0f);      // LayerNorm-ed operands | weights (the scales of sxf_ffn.hip)
+constexpr float SA = 256.0f, SW = 1024.0f, UNS = 1.0f / (256.0f * 1024.0f);      // LayerNorm-ed operands | weights (pack.h f16_pair_s10)
 constexpr float SR = 64.0f, UNS_R = 1.0f / (64.0f * 1024.0f);                    // operands that are NOT LayerNorm-ed (attention output, conv-module activations): range 1023
 constexpr int ROW2 = 80;                                                         // bytes per F2 image row in LDS: 32 inputs (64 B) + 16
 enum { MODE_F1 = 1, MODE_F2 = 2, MODE_FFN = 3 };
@@ -468,7 +470,7 @@ __device__ __forceinline__ void g2_swish(const char* st, int lr, int kh, const f
 // FeedForwardModule body, software-pipelined over the chunks of 32 hidden units: iteration c = F1 of chunk c (the weight-ring pieces between its k-steps), then F2
 // of chunk c - 1 with the Swish of chunk c between its MFMAs.  The weight parts move in units (Ring::fetch_unit): F1 part of chunk c + 1 and F2 part of chunk c
 // are published in iteration c - the F1 slot of ring stage (c + 1) & 1 was last read in iteration c - 1, the F2 slot of stage c & 1 (by the F2 of chunk c - 2) likewise.
-// FeedForwardModule body, plain form: per chunk of 32 hidden units F1, Swish, F2 (sxf_ffn.hip's loop)
+// FeedForwardModule body, plain form: per chunk of 32 hidden units F1, Swish, F2
 template <int KS, int NT>
 __device__ __forceinline__ void stage_ffn_plain(Ring<KS, NT, MODE_FFN>& ring, char* sm, int lr, int kh, const f16x8 (&ah)[KS], const f16x8 (&al)[KS], f32x16 (&oacc)[NT]) {
     using L = CL<KS, NT>;
@@ -591,7 +593,7 @@ __global__ __launch_bounds__(256, waves_per_simd(KS)) void sxc_b_kernel(const Sx
     });
 }
 
-// ---- chain A: TAIL and / or HEAD
+// ---- chain A: TAIL and / or HEAD; neither: one FeedForwardModule alone, y = x + 1/2 FFN(LN(x)) from p.xres (which may be y), then y = LN(y) where ln_g is given
 template <int KS, int NT, bool TAIL, bool HEAD>
 __global__ __launch_bounds__(256) void sxc_a_kernel(const SxcAParams p) {
     using L = CL<KS, NT>;
@@ -636,13 +638,22 @@ __global__ __launch_bounds__(256) void sxc_a_kernel(const SxcAParams p) {
             stage_ffn<KS, NT>(rh, sm, lr, kh, ah, al, acc);
         }
     } else {
+        const float* xr = HEAD ? yr : p.xres + (size_t)row * D;   // the module alone: its own input rows, read again for the residual by the same lane
         Ring<KS, NT, MODE_FFN> rh;
-        rh.init(p.w_f1, p.nch_f1, tid, sm);
+        rh.init(HEAD ? p.w_f1 : p.w_f2, HEAD ? p.nch_f1 : p.nch_f2, tid, sm);
         rh.fetch0();
-        load_acc<NT>(yr, D, kh, acc);
+        load_acc<NT>(xr, D, kh, acc);
         row_stats<NT>(acc, D, kh, mean, rstd);
         acc_to_frags<KS, NT>(acc, mean, rstd * SA, SA, D, kh, ah, al);
         stage_ffn<KS, NT>(rh, sm, lr, kh, ah, al, acc);
+        if (!HEAD) {
+            add_residual<NT>(acc, UNS, xr, p.b_f2, D, kh);        // y = x + 1/2 FFN(LN(x))
+            if (p.ln_g) {                                         // the same for every lane of the grid
+                row_stats<NT>(acc, D, kh, mean, rstd);
+                apply_ln<NT>(acc, mean, rstd, p.ln_g, p.ln_b, D, kh);
+            }
+            store_acc<NT>(oby, y_off, acc, D, kh, live);
+        }
     }
     if (HEAD) {
         Ring<KS, NT, MODE_F1> rq;
@@ -690,43 +701,50 @@ template <int KS, int NT>
 int launch_a(const SxcAParams& p, hipStream_t s) {
     if (p.tail && p.head) return launch_a2<KS, NT, true, true>(p, s);
     if (p.tail) return launch_a2<KS, NT, true, false>(p, s);
-    return launch_a2<KS, NT, false, true>(p, s);
+    if (p.head) return launch_a2<KS, NT, false, true>(p, s);
+    return launch_a2<KS, NT, false, false>(p, s);
 }
+
+// Instance of a width: k-steps of an F1 product (D columns + the bias column), 32-row tiles of an output row
+constexpr int shape_ks(int D) { return (D + 1 + 15) / 16; }
+constexpr int shape_nt(int D) { return (D + 31) / 32; }
+template <int D>
+struct Width {
+    static constexpr int KS = shape_ks(D), NT = shape_nt(D);
+    static_assert(D % 4 == 0, "rows are read and written as 16-byte quads");
+    static_assert(16 * KS > D && 16 * (KS - 1) <= D, "the bias column D lies in the last k-step");
+    static_assert(32 * NT >= D && 32 * (NT - 1) < D && KS <= 2 * NT + 1, "an F2 product's 2 NT k-steps cover the operand's fragments");
+};
 
 }  // namespace
 
-// widths of the shipped configurations (the Tiny test config included); everything else stays on the per-module kernels
+// widths of the shipped configurations (the Tiny test config included); everything else stays on the per-module kernels.  The ONE list: sxc_supported and the
+// dispatch of both launchers are generated from it
+#define SXC_WIDTHS(X) X(24) X(32) X(48) X(100) X(120) X(140) X(144) X(168) X(176) X(180) X(200) X(240) X(256)
+
+void sxc_shape(int D, int* ks, int* nt) { *ks = shape_ks(D); *nt = shape_nt(D); }
 bool sxc_supported(int D) {
-    switch (D) { case 24: case 32: case 48: case 100: case 120: case 140: case 144: case 168: case 176: case 180: case 200: case 240: case 256: return true; default: return false; }
+#define SXC_CASE(W) case W:
+    switch (D) { SXC_WIDTHS(SXC_CASE) return true; default: return false; }
+#undef SXC_CASE
 }
 
-#define SXC_DISPATCH(FN, P)                                  \
-    switch ((P).D) {                                         \
-        case 24: return FN<2, 1>(P, s);                      \
-        case 32: return FN<3, 1>(P, s);                      \
-        case 48: return FN<4, 2>(P, s);                      \
-        case 100: return FN<7, 4>(P, s);                     \
-        case 120: return FN<8, 4>(P, s);                     \
-        case 140: return FN<9, 5>(P, s);                     \
-        case 144: return FN<10, 5>(P, s);                    \
-        case 168: return FN<11, 6>(P, s);                    \
-        case 176: case 180: return FN<12, 6>(P, s);          \
-        case 200: return FN<13, 7>(P, s);                    \
-        case 240: return FN<16, 8>(P, s);                    \
-        case 256: return FN<17, 8>(P, s);                    \
-    }                                                        \
-    return -2;
+#define SXC_LAUNCH_A(W) case W: return launch_a<Width<W>::KS, Width<W>::NT>(p, s);
+#define SXC_LAUNCH_B(W) case W: return launch_b<Width<W>::KS, Width<W>::NT>(p, s);
 
 int launch_sxc_b(const SxcBParams& p, hipStream_t s) {
     if (p.M <= 0) return 0;
     if (!sxc_supported(p.D) || p.De % 4 || !p.w_o || !p.w_p1 || !p.b_o || p.nch_p1 <= 0 || (p.nch_p1 & 1)) return -2;
-    SXC_DISPATCH(launch_b, p)
+    switch (p.D) { SXC_WIDTHS(SXC_LAUNCH_B) }
+    return -2;
 }
 
 int launch_sxc_a(const SxcAParams& p, hipStream_t s) {
     if (p.M <= 0) return 0;
-    if (!sxc_supported(p.D) || (!p.tail && !p.head)) return -2;
-    if (p.tail && (!p.w_p2 || !p.w_f2 || !p.b_p2 || !p.b_f2 || !p.ln_g || !p.ln_b || !p.c || !p.xres || p.nch_f2 <= 0)) return -2;
+    if (!sxc_supported(p.D) || !p.y) return -2;
+    if (p.tail && (!p.w_p2 || !p.b_p2 || !p.c || !p.ln_g)) return -2;
+    if ((p.tail || !p.head) && (!p.w_f2 || !p.b_f2 || !p.xres || p.nch_f2 <= 0 || !p.ln_g != !p.ln_b)) return -2;      // the module alone: FFN "2" of the params, ln optional
     if (p.head && (!p.w_f1 || !p.w_qkv || !p.b_f1 || !p.q || p.nch_f1 <= 0)) return -2;
-    SXC_DISPATCH(launch_a, p)
+    switch (p.D) { SXC_WIDTHS(SXC_LAUNCH_A) }
+    return -2;
 }

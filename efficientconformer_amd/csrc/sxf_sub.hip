@@ -3,14 +3,14 @@
 //
 // The per-module path (exact.hip ex_conv2d_flat1_kernel + split.hip sx_gemm_kernel [+ gather_rows_kernel for ragged batches]) writes the (frames, C F') fp32
 // activation to HBM and reads it back - 2 x 2.8 GB per Small step at B = 256, 2.6 of the split step's 21 serial milliseconds - and runs both on the rectangle a row
-// range's LONGEST utterance spans.  Here the activation never leaves the registers; the structure is sxf_ffn.hip's (a wave keeps 32 frames, TRANSPOSED: frames = MFMA
+// range's LONGEST utterance spans.  Here the activation never leaves the registers; the structure is that of sxf_chain.hip's FFN stage (a wave keeps 32 frames, TRANSPOSED: frames = MFMA
 // columns = lanes), with the 3 x 3 mel patch in the place of the normalised row:
 //   * hidden unit (f', c) = Swish(BN(conv)) of output frequency f' and channel c; chunk = 32 channels of one f' (k index c F' + f' of the Linear, encoders.py:114);
 //   * first product  H^T = Wc_cb P_f'^T : A operand = the conv taps of 32 channels (9 taps x BN scale, the BN shift + conv bias in tap 9 against a constant 1; 16-wide
 //     k-step), B operand = this lane's patch mel[2 f' - 1 .. 2 f' + 1][2 t - 1 .. 2 t + 1] (zero outside the utterance's own image: what it sees when run alone), three
 //     MFMAs (h h, h l, l h); the patch rows are carried from f' to f' + 1 (row 2 f' + 1 is the next patch's first) and the next two rows are requested one f' ahead;
 //   * Swish on the accumulator registers, which ARE the B fragments of the second product  Y^T += Wl_chunk H^T  (k order of the Linear's image permuted to the
-//     accumulator layout at pack time, encoder.hip); Linear images stream through the two-stage LDS ring of sxf_ffn.hip (one LDS-only barrier per chunk);
+//     accumulator layout at pack time, encoder.hip); Linear images stream through the two-stage LDS ring of sxf_chain.hip (one LDS-only barrier per chunk);
 //   * ragged batches: workgroup = (utterance, 128 frames); rows off[b] + t, the group-padding rows behind an utterance's last frame are written as zeros (what
 //     gather_rows_kernel left there).  Arithmetic: same-scale split (sx_common.h split2s): mel at 2^6, activations at 2^8, weights at 2^10, one fp32 accumulator per sum.
 #include "kernels.h"

@@ -185,7 +185,7 @@ def split_image_values(plan: EncoderPlan, sd: Dict[str, np.ndarray]) -> Dict[str
 def _boundary(plan: EncoderPlan, sd: Dict[str, np.ndarray]) -> None:
     """Profile ``boundary``: synthetic weights except for one folded value of each fused split image moved ACROSS the images' limit
     (|w| < 65000 / 1024 = 63.48 after folding; csrc/pack.h kSplitImgMax) to ~100, and one moved just below it.  Targets the fused images of
-    sxf_sub.hip (conv tap x BN scale, BN shift), sxf_ffn.hip / sxf_chain.hip (gamma W1, the bias column b1 + W1 beta) and sxf_chain.hip's
+    sxf_sub.hip (conv tap x BN scale, BN shift), sxf_chain.hip (gamma W1, the bias column b1 + W1 beta) and sxf_chain.hip's
     pointwise-1 (gamma W, conv-module LayerNorm folded).  The values below the limit are as close to it as the ACTIVATION envelopes allow on
     the tests' inputs: 60 for biases / shifts and for the pointwise-1 gate row (sigmoid input); 40 for gamma W1 (the Swish operand, |x| < 255,
     sees 40 x a LayerNorm-ed value); 12 for a subsampler tap (the Swish operand sees 12 x |mel| <= 12 x 20.7).  Block 0 carries the FFN1 and

@@ -410,15 +410,18 @@ int effconf_lm_step(EcLm* lm, const int32_t* tokens, const float* h_in, const fl
  *   so that greedy CTC label sequences equal the reference's CPU fp32 path (model_ctc.py:99-133) wherever its top-2 logit margins
  *   exceed fp32 summation-order noise; ~10x slower than the default bf16-operand path.  Set to 1 BEFORE effconf_encoder_finalize
  *   (the fp32 tensors are uploaded there; the workspace query then covers both modes); afterwards it toggles the mode per handle.
- *   2 (round 4, csrc/split.hip; round 6, csrc/sxf.hip + sxf_ffn.hip + sxf_chain.hip): fp32 tensors with every GEMM and the attention products on the fp16
+ *   2 (round 4, csrc/split.hip; round 6, csrc/sxf.hip + sxf_chain.hip): fp32 tensors with every GEMM and the attention products on the fp16
  *   matrix pipe, each operand split into two fp16 numbers (three MFMAs per product, products accurate to ~2^-21): label sequences identical to the
  *   reference's on every golden and on the bench's oracle samples of Small / Medium / Large.  Round 6: ONE attention kernel per block with the scores on the
  *   CU, the row-local work of a block as two kernels, the front end as one kernel, ragged batches, causal and streaming configurations - 2.6x the bf16 step on
  *   EfficientConformerCTCSmall (5.7x in round 5), 2.4x / 2.7x on Medium / Large.  Set to 2 BEFORE finalize (the split weight images are built there; such a handle then serves 2, 1 and 0);
  *   a handle finalized with 1 refuses 2.
- * "split_chain" (default 1), "split_ffn" (default 1): split mode on the fused row-local kernels (csrc/sxf_chain.hip; csrc/sxf_ffn.hip when split_chain = 0);
+ * "split_chain" (default 1), "split_ffn" (default 1): split mode on the fused row-local kernels of csrc/sxf_chain.hip.  split_chain: the row-local work of a
+ *   block as two chain kernels where their images exist (they contain the feed-forward modules, so split_ffn = 0 switches them off too).  split_ffn: a
+ *   feed-forward module that stands alone (split_chain = 0, a trace without trace_fused, a block whose other chain images were refused for range) runs as one
+ *   kernel - the FFN-only form of the chain kernel, on the chain's own image - where that image exists; 0 = LayerNorm + two split GEMMs.
  *   0 / 0 = LayerNorm, split GEMM, GLU kernels per module (tests: the same results within a few 1e-6, another summation order).  A debug trace
- *   (effconf_encoder_trace_*) runs the per-module kernels: the chains never write the intermediate states.
+ *   (effconf_encoder_trace_*) runs the per-module kernels around the FFN-only form: the chains never write the intermediate states.
  * "trace_fused" (default 0; tests): 1 = a debug trace of the split mode keeps the fused kernels an untraced forward runs (csrc/sxf_sub.hip, csrc/sxf_chain.hip;
  *   the output is bit-identical to the untraced forward's) and records what THEY write to memory: "linear", per block "x_ffn1" (after a head launch or a merged
  *   tail + head), "q" / "k" / "v" (Q without u; chunk-padding rows are never written), "e" (the fp32 positional projection), "att_o", "x_mhsa", "glu", "dw",

@@ -46,11 +46,6 @@ int effconf_debug_pack_dwconv_mfma(const float* w_kc, int32_t ksize, int32_t cha
  * use_mfma: 1 = dwconv_mfma_kernel (stride 1, kernel size 15 / 31 / 7), 0 = dwconv_kernel (VALU).  causal: pre-padding (k - 1, 0) instead of "same". */
 int effconf_debug_dwconv(const uint16_t* g, int32_t batch, int32_t frames, int32_t channels, int32_t ld, const float* w_kc_host, const float* bias_host,
                          int32_t ksize, int32_t stride, int32_t use_mfma, int32_t causal, uint16_t* out, void* stream);
-/* The fused split-precision FeedForwardModule kernel alone (csrc/sxf_ffn.hip; reference modules.py:385-395, blocks.py:122, 132-135) on a handle finalized with
- * exact_fp32 = 2: y = x + 1/2 FFN_which(LayerNorm(x)) on fp32 rows (rows, D), with_norm != 0: followed by the block-final LayerNorm.  ablate: timing-only switches
- * of the diagnostic build (1 no first product, 2 no Swish, 4 no second product, 8 no weight stream, 16 no per-chunk barrier; results are wrong by construction);
- * tools/sxf_ffn_probe.py. */
-int effconf_debug_sxf_ffn(EcEncoder* enc, int32_t block, int32_t which, const float* x, int32_t rows, float* y, int32_t with_norm, int32_t ablate, void* stream);
 /* One idle wave that occupies `stream` for `microseconds` (tools/overlap_probe.py: the duration of an xGMI transfer a single GPU cannot make). */
 int effconf_debug_spin(double microseconds, void* stream);
 /* diagnostics (tools/lds_fill_rate_probe.py): `blocks` workgroups of `waves` waves each walk the same `window` bytes of `src` (dev) into LDS, `kib_per_wave`
@@ -65,12 +60,16 @@ int effconf_debug_lds_fill(int32_t mode, int32_t blocks, int32_t waves, const vo
  * compare digests within one machine only (tools/pack_digest.py, tests/test_pack_host.py). */
 int effconf_debug_pack_digest(EcEncoder* enc, uint64_t* digest, int64_t* buffers, int64_t* bytes);
 
-/* HOST function (no GPU, no HIP call): which kernels a bf16 forward of `enc` would run under its current options (csrc/routes.h - the functions the forward
+/* HOST function (no GPU, no HIP call): which kernels a forward of `enc` would run under its current options (csrc/routes.h - the functions the forward
  * itself reads), after the same dry run of the packing as above, so `enc` need not be finalized and is left as it was.  Writes NUL-terminated text into
  * `text` (`cap` bytes; 256 per block + 256 suffice): one line "front <two_layer|chunked|row_stationary|tiled_fused|conv_gemm> sub=.. sub1=.. xrect=.." (the
  * route of a rectangular / ragged batch and the workspace scratch it needs) and one line per block, "block k D=.. De=.. head=<prev_tail|chain|modules> ffn1=..
  * qkv=.. attention=<attention|attention2/1|attention2/2|refused> b=<chain|modules> outp=.. pw1=.. dw=<mfma|valu> res=.. tail=<full|tail|modules> pw2=.. ffn2=..";
- * a field that does not apply to the block's route reads "-".  Attention is reported for full context (no streaming mask). */
+ * a field that does not apply to the block's route reads "-".  Attention is reported for full context (no streaming mask).
+ * A handle set to exact_fp32 = 2 gets, after these, the label-exact split schedule (`cap`: 1024 per block suffice) for each kind of forward, <kind> = untraced |
+ * traced (a debug trace is recorded: option trace_fused decides) | maps (attention maps requested): "split <kind> family=<fused|modules> front=<sublin|modules>
+ * causal=<ok|refused>" and per block "split <kind> block k D=.. De=.. head=<prev_tail|chain|modules> ffn1=<fused|ln+gemms|-> attention=<sxf|sx|ex>
+ * b=<chain|modules> tail=<full|tail|modules> ffn2=<fused|ln+gemms|->" (attention of the per-module family: for a batch of one utterance). */
 int effconf_debug_routes(EcEncoder* enc, int32_t ragged, char* text, size_t cap);
 
 #if defined(__GNUC__) || defined(__clang__)

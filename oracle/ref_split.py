@@ -6,9 +6,9 @@ CORRECT split kernel may differ from that reference by: the operand pairs of the
 plugged into the same stage functions through ref_bf16.product_like (every matrix product) and ref_bf16._SPLIT_OPS (the front end's convolution).
 
 The kernels' arithmetic
-* Same-scale pair (sx_common.h split2s; sxf_ffn.hip, sxf_chain.hip, sxf_sub.hip, sxf.hip): the operand times its power-of-two scale S, h = fp16 toward zero
+* Same-scale pair (sx_common.h split2s; sxf_chain.hip, sxf_sub.hip, sxf.hip): the operand times its power-of-two scale S, h = fp16 toward zero
   (``__builtin_amdgcn_cvt_pkrtz``: v_cvt_pkrtz_f16_f32 truncates and saturates at 65504), l = fp16 round-to-nearest of x S - h (``__builtin_convertvector``).
-  Scales, per operand class (split-mode operand envelopes): SA = 2^8 LayerNorm-ed rows and Swish outputs (sxf_ffn.hip:27, sxf_chain.hip:32 -
+  Scales, per operand class (split-mode operand envelopes): SA = 2^8 LayerNorm-ed rows and Swish outputs (sxf_chain.hip: SA, SR, SW -
   acc_to_frags(acc, mean, rstd * SA, SA, ...), swish_frags ``(z * SA) * rcp``; sxf_sub.hip:25 hidden activation), SR = 2^6 operands that are not LayerNorm-ed - the
   attention output and the depthwise output (sxf_chain.hip:33, acc_to_frags(acc, 0.f, SR, SR, ...)), SP = 2^6 the mel patch (sxf_sub.hip:25), SQK = SV_ = 2^8
   Q + u, K, E, V and SP_ = 2^10 the probabilities (sxf.hip:26), SW = 2^10 every weight image (pack.h f16_pair_s10: ws = float(w 1024), h = (_Float16)ws - round to
@@ -54,10 +54,10 @@ from .ref_bf16 import hardware_like, ident, product_like
 F64, F32 = torch.float64, torch.float32
 SA, SR, SW, SP, SQK, SV_, SP_ = 256.0, 64.0, 1024.0, 64.0, 256.0, 256.0, 1024.0
 LO_SCALE = 2048.0
-# the scale of the activation operand of every product the fused kernels run (sxf_ffn.hip, sxf_chain.hip, sxf_sub.hip)
+# the scale of the activation operand of every product the fused kernels run (sxf_chain.hip, sxf_sub.hip)
 FUSED_SCALE = {"ffn1": SA, "ffn2": SA, "qkv": SA, "pw1": SA, "linear": SA, "out": SR, "pw2": SR}
 CHAIN_KINDS = frozenset(("ffn1", "ffn2", "qkv", "pw1", "out", "pw2"))      # split_chain = 1 at a width the chains are built for
-FFN_KINDS = frozenset(("ffn1", "ffn2"))                                     # split_chain = 0, split_ffn = 1: sxf_ffn.hip only
+FFN_KINDS = frozenset(("ffn1", "ffn2"))                                     # split_chain = 0, split_ffn = 1: the FFN-only form of sxf_chain.hip's chain A only
 NO_KINDS = frozenset()                                                      # every product on split.hip
 
 

@@ -24,12 +24,12 @@ from oracle.ref_bf16 import ident, stage_ratios, worst_element
 from oracle.ref_split import CHAIN_KINDS, FFN_KINDS, NO_KINDS, keep, split_runs, split_term
 
 F64, F32 = torch.float64, torch.float32
-SXC_WIDTHS = (24, 32, 48, 100, 120, 140, 144, 168, 176, 180, 200, 240, 256)      # sxf_chain.hip sxc_supported, sxf_ffn.hip sxf_ffn_supported
+SXC_WIDTHS = (24, 32, 48, 100, 120, 140, 144, 168, 176, 180, 200, 240, 256)      # sxf_chain.hip SXC_WIDTHS (held to it on the CPU: tests/test_routes_host.py)
 EPS = 2.0 ** -23
 
 
 def split_route(plan, opts):
-    """What forward_exact (fused kernel family) chooses for these options: {"chain": the row-local chains (split_chain and split_ffn), "ffn": sxf_ffn.hip where no chain runs,
+    """What forward_exact (fused kernel family) chooses for these options: {"chain": the row-local chains (split_chain and split_ffn), "ffn": the FFN-only form of sxc_a_kernel where no chain runs,
     "sublin": sxf_sub.hip}.  A traced forward takes this route only with trace_fused = 1; otherwise chain = sublin = False."""
     fused = bool(opts.get("trace_fused", 0))
     ffn = bool(opts.get("split_ffn", 1))
@@ -42,7 +42,7 @@ def _kinds(route, width):
     if width in SXC_WIDTHS and route["chain"]:
         return CHAIN_KINDS, True
     if width in SXC_WIDTHS and route["ffn"]:
-        return FFN_KINDS, True          # sxf_ffn.hip folds its LayerNorm; every other product: LayerNorm kernel + split.hip
+        return FFN_KINDS, True          # the FFN-only form folds its LayerNorm; every other product: LayerNorm kernel + split.hip
     return NO_KINDS, False
 
 

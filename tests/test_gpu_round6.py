@@ -239,8 +239,9 @@ def test_split_mode_ragged_batch_equals_utterances_alone_and_the_oracle(name, ex
 def test_split_chains_vs_per_module_kernels_and_the_oracle(name, tm, lens, ragged):
     """sxf_chain.hip: out-proj + residual + LayerNorm + pointwise-1 + GLU as one kernel, pointwise-2 + residual + FFN2 + block LayerNorm + the next block's FFN1 +
     attention pre-norm + Q | K | V as another (blocks.py:119-137, modules.py:385-395, 511-522, attentions.py:651-653, 716).  The split mode with the chains (the
-    default) against (i) the same mode on the per-module kernels (`split_chain = 0`: LayerNorm, split GEMM, GLU and FFN kernels - a different summation order, so
-    a few 1e-6, not bit equality) and (ii) the oracle within the split mode's stated 2e-4 / 2e-5; rectangular batches with pad frames (the Q / K / V and
+    default) against (i) the same mode on the per-module kernels (`split_chain = 0`: LayerNorm, split GEMM, GLU kernels and the FFN-only form of chain A - a
+    different summation order, so a few 1e-6, not bit equality; that leg shares the FFN body with the chains, so also with `split_ffn = 0` beside it: LayerNorm +
+    split GEMMs, code the chains share nothing with, to the same bound) and (ii) the oracle within the split mode's stated 2e-4 / 2e-5; rectangular batches with pad frames (the Q / K / V and
     attention-output row remap) and ragged ones; every width a shipped configuration <= 256 has (24 .. 256: 100 / 140 / 200, 120 / 168 / 240, 144, 176, 180 / 256)
     incl. the stage transitions (D != De) and both subsampler forms."""
     m, sd = _model(name, 11)
@@ -252,10 +253,16 @@ def test_split_chains_vs_per_module_kernels_and_the_oracle(name, tm, lens, ragge
     out, out_len, _ = m.encoder.forward_mel(mel_d, ln_d)
     m.encoder.set_option("split_chain", 0)
     base, base_len, _ = m.encoder.forward_mel(mel_d, ln_d)
+    m.encoder.set_option("split_ffn", 0)
+    gemms, gemms_len, _ = m.encoder.forward_mel(mel_d, ln_d)
+    m.encoder.set_option("split_ffn", 1)
     m.encoder.set_option("split_chain", 1)
-    assert torch.equal(out_len, base_len)
+    assert torch.equal(out_len, base_len) and torch.equal(out_len, gemms_len)
     d = (out - base).abs()
     print("%s ragged=%s chains vs per-module kernels: max %.2e mean %.2e" % (name, ragged, float(d.max()), float(d.mean())))
+    assert float(d.max()) < 1e-4 and float(d.mean()) < 1e-5
+    d = (out - gemms).abs()
+    print("%s ragged=%s chains vs LayerNorm + split GEMMs: max %.2e mean %.2e" % (name, ragged, float(d.max()), float(d.mean())))
     assert float(d.max()) < 1e-4 and float(d.mean()) < 1e-5
     if ragged:
         for b, l in enumerate(lens):

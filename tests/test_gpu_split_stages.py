@@ -1,8 +1,8 @@
 """-m gpu: every split-mode kernel (precision = "split") against its float64 reference, stage by stage, teacher forced.
 
 One forward through ``trace_forward_mel`` per case.  With option ``trace_fused = 1`` the trace keeps the fused kernels an untraced forward runs
-(sxf_sublin_kernel, sxc_a_kernel, sxc_b_kernel) and records what they write to memory; without it - and with split_chain = split_sublin = split_ffn = 0 - the
-per-module kernels (split.hip sx_gemm_kernel, LayerNorm, sxf_glu_kernel, the fp32 convolutions) run.  Every stage is recomputed on the CPU FROM THE GPU'S OWN
+(sxf_sublin_kernel, sxc_a_kernel, sxc_b_kernel) and records what they write to memory - with split_chain = 0 beside it, the feed-forward modules alone on the
+FFN-only form of sxc_a_kernel between per-module kernels; without it - and with split_chain = split_sublin = split_ffn = 0 - the per-module kernels (split.hip sx_gemm_kernel, LayerNorm, sxf_glu_kernel, the fp32 convolutions) run.  Every stage is recomputed on the CPU FROM THE GPU'S OWN
 TRACED INPUT of that stage (tests/split_parity.py), in float64 - ref_bf16's stage functions with every rounding off: the split mode's contract is "no rounding
 anywhere" - and, as the noise model, by oracle/ref_split.py's split_runs: torch's float32 run, the kernels' float32 LayerNorm / sigmoid / exp formulas with the
 hardware functions moved by 0, +-1, +-2 ulps, and the emulated fp16 operand pairs (h toward zero, l to nearest, a_h w_h + a_h w_l + a_l w_h in float32).
@@ -25,11 +25,14 @@ pytestmark = pytest.mark.gpu
 
 PER_MODULE = {"split_chain": 0, "split_sublin": 0, "split_ffn": 0}
 FUSED = {"trace_fused": 1}
+FFN_ONLY = {"trace_fused": 1, "split_chain": 0}      # every FFN as the FFN-only form of sxc_a_kernel (in place: FFN1; to another buffer, with the block norm: FFN2)
 _SM, _T4 = "EfficientConformerCTCSmall", [333, 250, 97, 12]
 # name, mel frames, lengths, ragged, options, encoder_params overrides, weight profile, mel kind, block stages too
 CASES = (
     [("Tiny", 333, _T4, rg, o, {}, "synthetic", "mel", True) for rg in (False, True) for o in (FUSED, PER_MODULE)]
     + [(_SM, 420, [420, 333, 201], rg, FUSED, {}, "synthetic", "mel", True) for rg in (False, True)]
+    + [("Tiny", 333, _T4, rg, FFN_ONLY, {}, "synthetic", "mel", True) for rg in (False, True)]               # widths 24 / 32 / 48, a last workgroup with clamped rows
+    + [(_SM, 420, [420, 333, 201], rg, FFN_ONLY, {}, "synthetic", "mel", True) for rg in (False, True)]      # widths 120 / 168 / 240
     + [("EfficientConformerCTCMedium", 300, [300, 177], True, FUSED, {}, "synthetic", "mel", True),          # chains at 180 / 256, per-module kernels at 360; head width 135
        ("ConformerCTCSmall", 260, [260, 121], False, FUSED, {}, "synthetic", "mel", True),                  # width 176, two-layer subsampler, kernel 31
        ("EfficientConformerTransducerSmall", 300, [300, 222], True, FUSED, {}, "synthetic", "mel", True),   # widths 100 / 140 / 200
@@ -104,3 +107,16 @@ def test_a_traced_fused_forward_is_the_untraced_forward_bit_for_bit(ragged):
     enc.set_option("trace_fused", 0)
     _, _, got0 = enc.trace_forward_mel(*args, arena_bytes=1 << 29)
     assert "blocks.0.x_conv" in got0 and "subsample" in got0 and "blocks.0.glu" in got0 and "blocks.0.e" in got0
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["rect", "ragged"])
+@pytest.mark.parametrize("name,tm,lens", [("Tiny", 333, _T4), (_SM, 420, [420, 333, 201])], ids=["Tiny", _SM])
+def test_the_ffn_only_form_equals_the_chain_head_bit_for_bit(name, tm, lens, ragged):
+    """Block 0's first FFN as chain A's head form (trace_fused = 1) and as the FFN-only form of the same kernel (split_chain = 0 beside it): the same inlined
+    functions on the same ``linear`` rows and the same image, so ``blocks.0.x_ffn1`` is bit-identical.  ``linear`` first: a mismatch then points at the kernel."""
+    enc, sd, mel, ln, args, out, out_len, head = _traced((name, tm, lens, ragged, FUSED, {}, "synthetic", "mel", True))
+    enc.set_option("split_chain", 0)
+    _, _, alone = enc.trace_forward_mel(*args, arena_bytes=1 << 29)
+    assert "blocks.0.x_conv" not in head and "blocks.0.x_conv" in alone                # the routes: chains | per-module kernels around the FFN-only form
+    assert torch.equal(head["linear"], alone["linear"])
+    assert torch.equal(head["blocks.0.x_ffn1"], alone["blocks.0.x_ffn1"])

@@ -177,7 +177,7 @@ def test_trained_statistics_ragged_batch_vs_float64_oracle(name, precision):
 @pytest.mark.parametrize("name", ["Tiny", "EfficientConformerCTCSmall", "EfficientConformerCTCMedium", "ConformerCTCSmall"])
 @pytest.mark.parametrize("ragged", [False, True])
 def test_fused_split_vs_per_module_split_on_stressed_weights(name, profile, ragged):
-    """The split mode with its fused images (sxf_sub / sxf_ffn / sxf_chain: values held as w x 2^10 in two fp16 halves, |w| < 63.48 after folding)
+    """The split mode with its fused images (sxf_sub / sxf_chain: values held as w x 2^10 in two fp16 halves, |w| < 63.48 after folding)
     against the same mode on the per-module kernels (split_chain = split_ffn = split_sublin = 0: images h = fp16(w), l = fp16((w - h) 2^11)), within
     1e-4 / 1e-5; both within the oracle bound.  `boundary` puts one folded value of every fused image at ~100: an image that cannot hold its values
     must not be used (the per-module kernels run for that block / front end), never clamped."""

@@ -20,17 +20,22 @@ _spec.loader.exec_module(pack_digest)
 # (model, precision) -> (buffers, bytes) of the packers as they were inside encoder.hip (the parent of the commit that moved them), weights: the recipe of
 # tests/test_gpu_exact_and_sweep.py::_model (CTC head, vocab capped at 256, seed 7).  EfficientConformerCTCLarge in split mode (1701 buffers, 1 586 994 444
 # bytes) takes 5 s per dry run: it is in the parity table of profiles/pack_digest_parity.txt only.
+# The split entries are that commit's minus the natural-order FFN images of the fused FFN kernel the chain kernel has since replaced (profiles/
+# split_one_ffn_kernel.txt): one buffer of 2 ceil(F / 32) 64 (16 KS + 32 NT) bytes per feed-forward module of a width D in the chains' list, KS = ceil((D + 1) / 16),
+# NT = ceil(D / 32), F = 4 D.  Tiny 865 - 12, 10649972 - 729088; ConformerCTCSmall 2202 - 32, 302505404 - 34603008; EfficientConformerCTCSmall 2091 - 30,
+# 323482128 - 35942400; EfficientConformerCTCMedium 2055 - 21 (eleven modules at 360 have no image), 560470972 - 36126720; EfficientConformerTransducerSmall
+# 2091 - 30, 251017056 - 25804800.
 PARENT = {
     ("Tiny", "bf16"): (375, 5655092),
-    ("Tiny", "split"): (865, 10649972),
+    ("Tiny", "split"): (853, 9920884),
     ("ConformerCTCSmall", "bf16"): (947, 91079292),
-    ("ConformerCTCSmall", "split"): (2202, 302505404),
+    ("ConformerCTCSmall", "split"): (2170, 267902396),
     ("EfficientConformerCTCSmall", "bf16"): (908, 96120272),
-    ("EfficientConformerCTCSmall", "split"): (2091, 323482128),
+    ("EfficientConformerCTCSmall", "split"): (2061, 287539728),
     ("EfficientConformerCTCMedium", "bf16"): (860, 163303564),
-    ("EfficientConformerCTCMedium", "split"): (2055, 560470972),
+    ("EfficientConformerCTCMedium", "split"): (2034, 524344252),
     ("EfficientConformerTransducerSmall", "bf16"): (908, 85047552),
-    ("EfficientConformerTransducerSmall", "split"): (2091, 251017056),
+    ("EfficientConformerTransducerSmall", "split"): (2061, 225212256),
     ("EfficientConformerCTCLarge", "bf16"): (633, 431002156),
 }
 

@@ -1,5 +1,5 @@
-// Stand-alone host program for a sanitizer run of csrc/routes.h (not part of the test suite): front_route / front_scratch, block_routes and attention_route on a
-// hand-filled two-block handle under a sweep of the options they read.  routes.h calls the kernels' own `*_supported` predicates, so the program links the product
+// Stand-alone host program for a sanitizer run of csrc/routes.h (not part of the test suite): front_route / front_scratch, block_routes and attention_route, and
+// the split schedule's exact_forward_routes / exact_block_routes / exact_attention_split, on a hand-filled two-block handle under a sweep of the options they read.  routes.h calls the kernels' own `*_supported` predicates, so the program links the product
 // objects of an in-tree build; no kernel is launched and no device is needed.  From the repository root, after `python -m efficientconformer_amd._build`:
 //   hipcc --offload-arch=gfx950 -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -c tools/routes_sanitize.cpp -o routes_sanitize.o
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined routes_sanitize.o $(ls efficientconformer_amd/build/*.o | grep -v -e _dbg.o -e _pk.o -e debug.o) -o routes_sanitize
@@ -43,6 +43,30 @@ int main() {
                     const AttentionRoute a = attention_route(&e, dpad, ragged != 0, streaming != 0);
                     sum += a.waves + (a.refusal ? a.refusal[0] : 0);
                 }
+        }
+        ++calls;
+    }
+    // the label-exact split schedule: which images exist x its four options x the kind of forward x the shape fact of the merged head
+    e.blocks[1] = EcBlock{120, 120, 4, 4, 15, 3, 512, 1};
+    e.blocks[0].dim_expand = 120; e.blocks[0].conv_stride = 1;
+    for (int mode = 0; mode < 2; ++mode)
+    for (int images = 0; images < 64; ++images)
+    for (int opts = 0; opts < 16; ++opts)
+    for (int kind = 0; kind < 3; ++kind)
+    for (int carry = 0; carry < 2; ++carry) {
+        e.exact_split = mode != 0; e.cfg.sub_layers = 1; e.cfg.causal = images & 1;
+        e.xsub.wimg = images & 1 ? &image : nullptr;
+        for (int k = 0; k < 2; ++k) {
+            BlockW& W = e.bw[k];
+            W.xc_f[0] = images & (2 << k) ? &image : nullptr; W.xc_f[1] = images & (8 << k) ? &image : nullptr;
+            W.xc_in = W.xc_f[0] && (images & 32); W.xc_out = W.xc_f[1] != nullptr;
+        }
+        e.split_chain = opts & 1; e.split_ffn = (opts >> 1) & 1; e.split_sublin = (opts >> 2) & 1; e.trace_fused = (opts & 8) != 0;
+        const ExactForwardRoutes f = exact_forward_routes(&e, kind == 1, kind == 2);
+        sum += f.fused + 2 * f.sublin + 4 * f.ffn + 8 * f.chains + (f.refusal ? f.refusal[0] : 0) + split_fused_ok(&e);
+        for (size_t k = 0; k < e.blocks.size(); ++k) {
+            const ExactBlockRoutes r = exact_block_routes(&e, f, k, carry != 0, carry != 0);
+            sum += r.head + 3 * r.tail + r.ffn1_fused + r.chain_b + r.ffn2_fused + exact_attention_split(&e, 90, images * 2048LL);
         }
         ++calls;
     }
