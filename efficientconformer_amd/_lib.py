@@ -53,6 +53,9 @@ SIGNATURES = {
     "effconf_mel_frontend": (C.c_int, [_P, _F32P, _I32, _I32, _F32P, _P]),
     "effconf_encoder_attention_dims": (C.c_int, [_P, _I32, _I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "effconf_encoder_set_attention_outputs": (C.c_int, [_P, C.POINTER(C.c_void_p), _I32]),
+    "effconf_encoder_set_interctc": (C.c_int, [_P, C.POINTER(C.c_int32), _I32, _I32]),
+    "effconf_encoder_set_interctc_outputs": (C.c_int, [_P, C.POINTER(C.c_void_p), _I32]),
+    "effconf_interctc": (C.c_int, [_P, _I32, _F32P, _I32, _F32P, _F32P, _P, _SZ, _P]),
     "effconf_host_pack_rows": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), _I32, C.c_void_p, C.c_int64, _I32, _I32]),
     "effconf_ctc_greedy": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _P, _F32P, _P, _SZ, _P]),
     "effconf_ctc_greedy_bf16": (C.c_int, [_P, _P, _I64P, _I32, _I32, _P, _P, _F32P, _P, _SZ, _P]),

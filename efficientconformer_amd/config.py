@@ -79,6 +79,10 @@ class EncoderPlan:
     left_context: int = 1 << 30    # frames after the subsampling; >= any sequence length = unlimited (the shipped configs: max_pos_encoding)
     right_context: int = 1 << 30
     blocks: List[BlockPlan] = field(default_factory=list)
+    # self-conditioned CTC (encoders.py:144-215): filled only for ConformerEncoderInterCTC (build_plan(params, interctc=True)); the plain encoder
+    # ignores the keys, as the reference's does
+    interctc_blocks: List[int] = field(default_factory=list)
+    interctc_vocab: int = 0
 
     @property
     def dim_out(self) -> int:
@@ -102,8 +106,9 @@ class EncoderPlan:
         return t1, ts
 
 
-def build_plan(params: dict) -> EncoderPlan:
-    """Validate an ``encoder_params`` dict and resolve the per-block plan."""
+def build_plan(params: dict, interctc: bool = False) -> EncoderPlan:
+    """Validate an ``encoder_params`` dict and resolve the per-block plan.  `interctc`: the plan of ``ConformerEncoderInterCTC`` - ``interctc_blocks``
+    and ``vocab_size`` are required and checked; without it both keys are ignored (the reference's ``ConformerEncoder`` never reads them)."""
     p = params
     if p.get("arch", "Conformer") != "Conformer":
         raise Exception("Unknown encoder architecture:", p.get("arch"))
@@ -177,6 +182,24 @@ def build_plan(params: dict) -> EncoderPlan:
             group_size=g, max_pos=int(p["max_pos_encoding"]) // stride ** n_gt_s,
             conv_stride=int(cs), mask_stride=mask_stride))
         mask_stride *= int(cs)
+    if interctc:
+        # encoders.py:150-161: one linear_expand_k / linear_proj_k pair per listed block, on that block's output width
+        if "interctc_blocks" not in p:
+            raise Exception("InterCTC encoder needs encoder_params['interctc_blocks']")
+        ids = list(p["interctc_blocks"] or [])
+        for k in ids:
+            if isinstance(k, bool) or not isinstance(k, int):
+                raise Exception("interctc_blocks must be a list of ints; got %r" % (k,))
+            if not 0 <= k < len(plan.blocks):
+                raise Exception("interctc_blocks: block %d is outside 0..%d" % (k, len(plan.blocks) - 1))
+        if len(set(ids)) != len(ids):
+            raise Exception("interctc_blocks lists a block twice: %r" % (ids,))
+        if "vocab_size" not in p:
+            raise Exception("InterCTC encoder needs encoder_params['vocab_size'] (InterCTC sets it from tokenizer_params)")
+        vocab = p["vocab_size"]
+        if isinstance(vocab, bool) or not isinstance(vocab, int) or vocab < 2:
+            raise Exception("InterCTC vocab_size must be an int >= 2; got %r" % (vocab,))
+        plan.interctc_blocks, plan.interctc_vocab = sorted(ids), vocab
     return plan
 
 

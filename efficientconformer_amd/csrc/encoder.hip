@@ -294,6 +294,30 @@ int effconf_encoder_set_attention_outputs(EcEncoder* e, float* const* maps, int3
     return 0;
 }
 
+/* Self-conditioned CTC (reference encoders.py:144-215) */
+int effconf_encoder_set_interctc(EcEncoder* e, const int32_t* blocks, int32_t n, int32_t vocab_size) {
+    if (!e) return fail("null encoder");
+    if (n < 0 || (n > 0 && !blocks)) return fail("effconf_encoder_set_interctc: null / negative block list");
+    std::vector<int> ks(blocks, blocks + n);
+    std::sort(ks.begin(), ks.end());
+    for (int i = 0; i < n; ++i) {
+        if (ks[i] < 0 || ks[i] >= (int)e->blocks.size()) return fail("effconf_encoder_set_interctc: block " + std::to_string(ks[i]) + " is outside 0.." + std::to_string(e->blocks.size() - 1));
+        if (i > 0 && ks[i] == ks[i - 1]) return fail("effconf_encoder_set_interctc: block " + std::to_string(ks[i]) + " is listed twice");
+    }
+    if (n > 0 && vocab_size < 2) return fail("effconf_encoder_set_interctc: vocab_size must be >= 2");
+    e->ic_blocks = ks; e->ic_vocab = n > 0 ? vocab_size : 0; e->ic_out.clear();
+    e->finalized = false;          // the images of the steps are built by finalize (which also refuses what the kernel does not take)
+    return 0;
+}
+
+int effconf_encoder_set_interctc_outputs(EcEncoder* e, float* const* probs, int32_t n) {
+    if (!e) return fail("null encoder");
+    if (!probs || n == 0) { e->ic_out.clear(); return 0; }
+    if (n != (int)e->ic_blocks.size()) return fail("effconf_encoder_set_interctc_outputs: one pointer per InterCTC block in block order (null = skip that block)");
+    e->ic_out.assign(probs, probs + n);
+    return 0;
+}
+
 int effconf_encoder_set_option(EcEncoder* e, const char* name, int32_t value) {
     if (!e || !name) return fail("null argument");
     if (!strcmp(name, "fuse_subsample")) { if (value < 0 || value > 3) return fail("fuse_subsample: 0, 1, 2 or 3"); e->fuse_subsample = value; return 0; }

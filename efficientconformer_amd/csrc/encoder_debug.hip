@@ -66,6 +66,10 @@ int effconf_debug_routes(EcEncoder* e, int32_t ragged, char* text, size_t cap) {
                      pick(b.dim_model != b.dim_expand, r.res_rs, "rs", "tiled"), kTail[r.tail], pick(tm, r.pw2_rs, "rs", "tiled"), pick(tm, r.ffn2_fused, "ln_fused", "ln+tiled"));
             out += ln;
         }
+        for (int k : t.ic_blocks) {      // handles with self-conditioned CTC steps only (a handle that finalize would refuse never gets here)
+            snprintf(ln, sizeof(ln), "interctc %d De=%d V=%d route=%s\n", k, t.blocks[k].dim_expand, t.ic_vocab, interctc_route(&t, k) == IC_FUSED ? "fused" : "refused");
+            out += ln;
+        }
         if (!t.exact_split) return;
         // the label-exact split schedule, per kind of forward: as it runs untraced, with a debug trace (option trace_fused decides), with attention maps requested
         const char* const kinds[] = {"untraced", "traced", "maps"};

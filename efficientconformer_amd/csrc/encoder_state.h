@@ -128,6 +128,16 @@ struct EcEncoder {
     std::map<std::string, const float*> xw;
     std::map<std::pair<int, int>, const float*> xtab;
     const float *xsub_scale[2] = {nullptr, nullptr}, *xsub_shift[2] = {nullptr, nullptr};
+    // self-conditioned CTC (effconf_encoder_set_interctc): the listed blocks in block order, the vocabulary, and per listed block the images of interctc.hip -
+    // linear_expand_k as a plain packed Linear (rows = vocabulary entries), linear_proj_k with its K (vocabulary) index in accumulator order
+    struct InterCtcW { PackedLinear expand; const bf16_t* proj = nullptr; int proj_ld = 0; const float* proj_b = nullptr; };
+    std::vector<int> ic_blocks; int ic_vocab = 0;
+    std::vector<InterCtcW> ic_w;             // [ic_blocks.size()], filled by finalize
+    std::vector<float*> ic_out;              // per listed block: device buffer for the probabilities of the next forward, or null
+    int ic_index(size_t k) const {           // position of block k among the listed blocks, -1: no step after block k
+        for (size_t i = 0; i < ic_blocks.size(); ++i) if (ic_blocks[i] == (int)k) return (int)i;
+        return -1;
+    }
     // per-launch event profiler (bench / tuning only; off by default)
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;          // pairs

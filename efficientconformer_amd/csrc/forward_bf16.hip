@@ -46,6 +46,9 @@ Workspace make_workspace(const EcEncoder* e, const Shapes& s, bool from_audio) {
         w.tile_off = take(nbk * (B + 1) * 4);
     }
     for (size_t k = 0; k < esz.size(); ++k) w.eh_blk.push_back(take(esz[k]));
+    size_t mic = 0;                    // InterCTC handles only (every other configuration: zero bytes, the layout as it was)
+    for (int k : e->ic_blocks) mic = std::max(mic, (size_t)s.Mout[k] * e->ic_vocab * 4);
+    w.icp = take(mic);
     w.preds = take(0);
     w.total = off;
     return w;
@@ -161,6 +164,20 @@ int run_subsample_linear(EcEncoder* e, hipStream_t st, const float* mel, const S
 // the launch options every chain carries
 ChainParams chain_params(const EcEncoder* e) { ChainParams cp{}; cp.small_m = e->chain_small_m; cp.pair = e->chain_pair; return cp; }
 
+// Self-conditioned CTC step i (of listed block k) on the product kernel: y = x + softmax(x We^T + be) Wp^T + bp on `rows` dense fp32 rows (y may alias x), the
+// normalised probabilities to probs (rows, V) where given
+int run_interctc(EcEncoder* e, hipStream_t st, int i, const float* x, int rows, float* y, float* probs) {
+    const EcEncoder::InterCtcW& W = e->ic_w[i];
+    const int De = e->blocks[e->ic_blocks[i]].dim_expand, V = e->ic_vocab;
+    InterCtcParams p{};
+    p.X = x; p.ldx = De; p.Y = y; p.ldy = De;
+    p.W1 = W.expand.w; p.ldw1 = W.expand.ldw; p.b1 = W.expand.bias; p.W2 = W.proj; p.ldw2 = W.proj_ld; p.b2 = W.proj_b;
+    p.M = rows; p.D = De; p.V = V; p.Vp = ec_round_up(V, 32); p.probs = probs;
+    PROF(PC_GEMM_OTHER, 4.0 * rows * (double)De * V * (probs ? 1.5 : 1.0), (double)rows * De * 8 + 4.0 * De * V + (probs ? (double)rows * V * 4 : 0.0));
+    EC_TRY(launch_interctc(p, st));
+    return 0;
+}
+
 }  // namespace
 
 // Ragged batches (s.ragged): every utterance runs at its own length in one concatenated row space (kernels.h: RaggedRows) - the row-local
@@ -194,6 +211,27 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
     for (int k = 0; k < nb; ++k) routes.push_back(block_routes(e, k));
     const ECache ec = e_cache_begin(e, st, ws, s, w.eh_blk[0], true);
     const bool e_cached = ec.hit;
+
+    // The self-conditioned CTC step after block k (encoders.py:209-213), in place on the block's output rows (group-padding rows of a ragged batch are just rows).
+    // Probabilities: written only where somebody reads them - the caller's buffer (rectangular batches: rows (b, t) ARE (B, T_k, V); ragged ones go through the
+    // workspace and are padded per utterance) or a debug trace
+    auto interctc_step = [&](int k, float* rows, int Mo) -> int {
+        const int i = e->ic_index(k);
+        if (i < 0) return 0;
+        const int V = e->ic_vocab, De = e->blocks[k].dim_expand;
+        float* user = e->ic_out.size() == e->ic_blocks.size() ? e->ic_out[i] : nullptr;
+        float* scratch = reinterpret_cast<float*>(ws + w.icp);
+        float* probs = user && !rg ? user : (user || e->trace_arena ? scratch : nullptr);
+        EC_TRY(run_interctc(e, st, i, rows, Mo, rows, probs));
+        trace_block(e, st, k, "x_interctc", rows, Mo, De, De, 0);
+        if (probs) trace_block(e, st, k, "interctc_p", probs, Mo, V, V, 0);
+        if (user && rg) {
+            const RaggedRows rl = br.rows_at(k + 1);
+            PROF(PC_MISC, 0, (double)Mo * V * 4 + (double)B * s.Tout[k] * V * 4);
+            EC_TRY(launch_emit_rows(scratch, V, rl.off, rl.len, B, s.Tout[k], user, st));
+        }
+        return 0;
+    };
 
     const int wide_gemm = e->wide_gemm;        // GemmParams::wide of the tiled Q/K/V GEMM (launch_gemm only)
     int mask_stride = 1;                       // product of the strides of the blocks before block k
@@ -342,7 +380,8 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             cp.consts = next_head ? W.cc_full : W.cc_tail;
             { PROF(PC_GEMM_FFN, fl, by); EC_ABL(2, EC_TRY(launch_chain(cp, next_head ? CHAIN_A_FULL : CHAIN_A_TAIL, st))); }
             have_a = false;
-            if (last) { trace_block(e, st, k, "out", xo, Mo, De, De, 0); }
+            if (last || interctc_after(e, k)) { trace_block(e, st, k, "out", xo, Mo, De, De, 0); }      // (a step's input is part of its trace)
+            EC_TRY(interctc_step(k, xo, Mo));
             continue;
         }
         EC_TRY(run_rs_or_tiled(e, r.pw2_rs, PC_GEMM_OTHER, st, cbuf, ld8(De), Mo, W.pw2, 0, EPI_RESID_F32, x, De, x, De, 1.0f));
@@ -351,11 +390,13 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         // ---- x += 1/2 FFN2(x); x = LN(x)   (blocks.py:132-135)
         if (!r.ffn2_fused) { PROF(PC_LAYERNORM, 0, (double)Mo * De * 6); EC_TRY(launch_layernorm(x, Mo, De, W.ln_ffn2.g, W.ln_ffn2.b, nullptr, a, ld8(De), nullptr, nullptr, st)); }
         EC_TRY(run_ffn(e, st, r.ffn2_fused, a, Mo, De, W.ffn2_a, W.ffn2_b, W.ffn2_bp, x, hbuf, r.ffn2_fused ? &W.ln_ffn2 : nullptr));
-        // block-final norm fused with the next block's FFN1 pre-norm (both read the same rows)
-        { PROF(PC_LAYERNORM, 0, (double)Mo * De * 10); EC_TRY(launch_layernorm(x, Mo, De, W.ln_out.g, W.ln_out.b, xo, last ? nullptr : a, ld8(De),
-                                last ? nullptr : e->bw[k + 1].ln_ffn1.g, last ? nullptr : e->bw[k + 1].ln_ffn1.b, st)); }
-        have_a = !last;
+        // block-final norm fused with the next block's FFN1 pre-norm (both read the same rows) - unless an InterCTC step rewrites those rows first
+        const bool next_a = !last && !interctc_after(e, k);
+        { PROF(PC_LAYERNORM, 0, (double)Mo * De * 10); EC_TRY(launch_layernorm(x, Mo, De, W.ln_out.g, W.ln_out.b, xo, next_a ? a : nullptr, ld8(De),
+                                next_a ? e->bw[k + 1].ln_ffn1.g : nullptr, next_a ? e->bw[k + 1].ln_ffn1.b : nullptr, st)); }
+        have_a = next_a;
         trace_block(e, st, k, "out", xo, Mo, De, De, 0);
+        EC_TRY(interctc_step(k, xo, Mo));
     }
     e_cache_end(e, ws, s, ec);
     if (rg) EC_TRY(emit_ragged(e, st, br, x, out_frames, out));
@@ -419,6 +460,16 @@ int effconf_ffn(EcEncoder* e, int32_t block, int32_t which, const float* x, int3
     const bool fused = ffn_fused_module(D);      // not the forward's ffn_fused: this entry keeps the fused kernel where tiled_auto / wide_gemm send a forward to the tiled GEMMs
     if (!fused) EC_TRY(launch_layernorm(y, rows, D, ln.g, ln.b, nullptr, a, ld8(D), nullptr, nullptr, st));
     return run_ffn(e, st, fused, a, rows, D, L1, L2, w2p, y, hbuf, fused ? &ln : nullptr);       // fused: pre-norm in the kernel's prologue
+}
+
+int effconf_interctc(EcEncoder* e, int32_t block, const float* x, int32_t rows, float* y, float* probs, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    (void)workspace; (void)workspace_bytes;          // the fused kernel keeps the logits on the CU: no scratch
+    if (!e || !e->finalized) return fail("encoder not finalized");
+    if (block < 0 || block >= (int)e->blocks.size() || !x || !y || rows <= 0) return fail("bad argument");
+    const int i = e->ic_index(block);
+    if (i < 0) return fail("effconf_interctc: block " + std::to_string(block) + " has no InterCTC step (effconf_encoder_set_interctc)");
+    return run_interctc(e, (hipStream_t)stream, i, x, rows, y, probs);
 }
 
 int effconf_conv_module(EcEncoder* e, int32_t block, const float* x, int32_t batch, int32_t frames, float* y, void* workspace,

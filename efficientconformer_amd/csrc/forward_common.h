@@ -84,6 +84,7 @@ struct Workspace {
     size_t mel, sub, sub1, x0, x1, a, hbuf, qu, kh, vt, eh, o, gbuf, cbuf, xs, lens, preds;
     size_t mel_len = 0, row_off = 0, wg_off = 0, tile_off = 0;     // ragged descriptors (ints)
     size_t xrect = 0;                                              // ragged + unfused front end: rectangular Linear output before the gather
+    size_t icp = 0;                                                // InterCTC handles: (rows, V) fp32 probabilities of one step - the trace's copy, a ragged batch's side output before it is padded
     std::vector<size_t> eh_blk;   // per-block E (kept across forwards for the cache)
 };
 // label-exact schedule (forward_exact.hip: make_xworkspace); the mel image of an audio forward sits behind `total`

@@ -29,6 +29,7 @@ XWorkspace make_xworkspace(const EcEncoder* e, const Shapes& s) {
         mg = std::max(mg, Mi * De);
         mc = std::max(mc, Mo * De);
         if (D != De) mxs = std::max(mxs, Mo * D);
+        if (e->ic_index(k) >= 0) mh = std::max(mh, Mo * (size_t)e->ic_vocab);      // the (rows, V) logits / probabilities of an InterCTC step live in the FFN's hidden plane
     }
     const int L = e->cfg.sub_layers;
     size_t T1r = s.Tm; for (int i = 0; i < L; ++i) T1r = (T1r - 1) / 2 + 1;          // rows per utterance of the rectangular front end (ragged: at the input's pitch)
@@ -363,6 +364,22 @@ int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int fro
         }
         if (!to_out) std::swap(x, xalt);
         if (!head_done) trace(k, "out", xo, Mo, De);      // a merged head has already made xo the next block's x_ffn1
+        // ---- self-conditioned CTC (encoders.py:209-213): p = softmax(linear_expand_k(x)) in the reference's order, x += linear_proj_k(p) - three launches, the
+        //      logits in memory (routes.h: a listed block's tail never carries the next head, so xo holds the block's output here)
+        if (const int ic = e->ic_index(k); ic >= 0) {
+            const int V = e->ic_vocab;
+            const std::string ks = std::to_string(k);
+            EC_TRY(xgemm(e, st, xo, De, Mo, "linear_expand_" + ks, V, De, hb, V));
+            { PROF(PC_MISC, 0, (double)Mo * V * 12); EC_TRY(launch_row_softmax(hb, Mo, V, st)); }
+            EC_TRY(xresid(e, st, hb, V, Mo, "linear_proj_" + ks, De, V, xo, 1.0f));
+            trace(k, "x_interctc", xo, Mo, De);
+            ftrace(k, "interctc_p", hb, Mo, V);
+            if (float* user = e->ic_out.size() == e->ic_blocks.size() ? e->ic_out[ic] : nullptr) {
+                PROF(PC_MISC, 0, (double)Mo * V * 8);
+                if (rg) { const RaggedRows rl = br.rows_at(k + 1); EC_TRY(launch_emit_rows(hb, V, rl.off, rl.len, B, s.Tout[k], user, st)); }
+                else if (hipMemcpyAsync(user, hb, (size_t)Mo * V * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail("copy failed");
+            }
+        }
     }
     e_cache_end(e, ws, s, ec);
     if (rg) EC_TRY(emit_ragged(e, st, br, x, out_frames, out));

@@ -78,6 +78,24 @@ int launch_rs_gemm(const GemmParams& p, int epi, hipStream_t s);
 bool ffn_fused_supported(int D);
 int launch_ffn_fused(const FfnParams& p, hipStream_t s);
 
+// ---------------------------------------------------------------- self-conditioned CTC step  (interctc.hip)
+// y = x + softmax(q(x) We^T + be) Wp^T + bp on fp32 rows [M][ld] (y may alias x; null: probabilities only), probs (optional) fp32 [M][V], normalised
+// W1 : We as bf16 [>= Vp][ldw1 >= 16 * interctc_ks_class(D)], rows = vocabulary entries, zero padded;  b1 [>= V]
+// W2 : Wp as bf16 [>= 16 * interctc_ks_class(D)][ldw2 >= Vp], the vocabulary (K) index permuted within groups of 16 (rsgemm.hip);  b2 [>= D]
+struct InterCtcParams {
+    const float* X; int ldx;
+    float* Y; int ldy;
+    const bf16_t* W1; int ldw1; const float* b1;
+    const bf16_t* W2; int ldw2; const float* b2;
+    int M, D, V, Vp;                   // Vp = round_up(V, 32)
+    float* probs;
+};
+int interctc_ks_class(int D);          // k-steps of the kernel instance that serves width D (0: none - D % 4, D > 768)
+bool interctc_supported(int D, int V); // D % 4 == 0, D <= 768, 2 <= V <= 1024
+int launch_interctc(const InterCtcParams& p, hipStream_t s);
+// exact modes: z[M][V] -> softmax(z) in place, exp(z - max) / sum in the reference's order
+int launch_row_softmax(float* z, int M, int V, hipStream_t s);
+
 
 // ---------------------------------------------------------------- fused row-local chains  (chain.hip)
 // One kernel runs a whole row-local stretch of the Conformer block on a 32-row tile per wave, the fp32 residual row staying in

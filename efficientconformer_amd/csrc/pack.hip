@@ -617,6 +617,36 @@ int pack_chain_consts(EcEncoder* e) {
     return 0;
 }
 
+// Self-conditioned CTC: per listed block k the two images of interctc.hip (kernels.h: InterCtcParams) - linear_expand_k [V][De] as a plain packed Linear whose
+// rows are at least as wide as the kernel instance reads them, linear_proj_k [De][V] padded to that instance's row count with its K (vocabulary) index in
+// accumulator order - and the fp32 biases.  The label-exact modes find the same tensors by prefix (pack_fp32_tensors, pack_split_modules)
+int pack_interctc(EcEncoder* e) {
+    e->ic_w.assign(e->ic_blocks.size(), EcEncoder::InterCtcW());
+    const int V = e->ic_vocab;
+    for (size_t i = 0; i < e->ic_blocks.size(); ++i) {
+        const size_t k = (size_t)e->ic_blocks[i];
+        const int De = e->blocks[k].dim_expand;
+        if (interctc_route(e, k) == IC_REFUSED) return fail(interctc_refusal(e, k));
+        const std::string ex = "linear_expand_" + std::to_string(k), pr = "linear_proj_" + std::to_string(k);
+        const HostTensor *we = find(e, ex + ".weight"), *be = find(e, ex + ".bias"), *wp = find(e, pr + ".weight"), *bp = find(e, pr + ".bias");
+        if (!we) return fail("missing tensor " + ex + ".weight");
+        if (!be) return fail("missing tensor " + ex + ".bias");
+        if (!wp) return fail("missing tensor " + pr + ".weight");
+        if (!bp) return fail("missing tensor " + pr + ".bias");
+        if (!sized(we, (int64_t)V * De) || !sized(be, V)) return fail("shape mismatch for " + ex);
+        if (!sized(wp, (int64_t)V * De) || !sized(bp, De)) return fail("shape mismatch for " + pr);
+        const int cols = 16 * interctc_ks_class(De);          // columns of We / rows of Wp the kernel instance of this width streams
+        EcEncoder::InterCtcW& W = e->ic_w[i];
+        if (!put_linear(e, pack_linear(row_ptrs(fdata(we), V, De), be->data, De, false, nullptr, nullptr, cols), &W.expand)) return fail("upload failed");
+        std::vector<const float*> rows(cols, nullptr);
+        for (int n = 0; n < De; ++n) rows[n] = fdata(wp) + (size_t)n * V;
+        const Linear L = pack_linear(rows, {}, V, true);
+        W.proj = upload(e, L.w); W.proj_ld = L.ldw; W.proj_b = upload(e, padded(bp->data, cols));
+        if (!W.proj || !W.proj_b) return fail("upload failed");
+    }
+    return 0;
+}
+
 int pack_ctc_head(EcEncoder* e) {
     const HostTensor *w = find(e, "fc.weight"), *b = find(e, "fc.bias");
     const int D = e->blocks.back().dim_expand, V = e->cfg.vocab_size;
@@ -773,7 +803,7 @@ int pack_split_chains(EcEncoder* e) {
 
 int pack_encoder(EcEncoder* e) {
     int rc;
-    if ((rc = pack_front_end(e)) || (rc = pack_blocks(e)) || (rc = pack_chain_consts(e)) || (rc = pack_ctc_head(e)) || (rc = pack_mel_tables(e))) return rc;
+    if ((rc = pack_front_end(e)) || (rc = pack_blocks(e)) || (rc = pack_chain_consts(e)) || (rc = pack_interctc(e)) || (rc = pack_ctc_head(e)) || (rc = pack_mel_tables(e))) return rc;
     e->xw.clear(); e->xtab.clear();
     if (!e->exact_pack) return 0;
     if ((rc = pack_fp32_tensors(e))) return rc;

@@ -6,6 +6,7 @@
 #include "encoder_state.h"
 
 #include <algorithm>
+#include <string>
 
 // Widths 257 .. 384 (EfficientConformer Large stage 1, Medium stage 3) fit the row-stationary kernels, but at 24 k-steps those run one
 // wave per SIMD and stream every weight per 32-row tile: 60 - 200 TFLOP/s (profiles/r2_03_large_kernel_stats.txt).  `wide_gemm` 2 / 3
@@ -107,11 +108,24 @@ struct BlockRoutes {
     bool ffn2_fused;   // TAIL_MODULES: FFN2 on the fused kernel with the LayerNorm in its prologue, else LayerNorm + two tiled GEMMs
 };
 
+// ------------------------------------------------------------------ self-conditioned CTC step after block k (effconf_encoder_set_interctc)
+// The step rewrites the block's output rows before the next block reads them, so a block followed by one never takes the next block's head along (TAIL_FULL ->
+// TAIL_ONLY below, in both schedules), and its block-final LayerNorm must not pre-compute the next block's FFN1 operand from the pre-step rows (interctc_after)
+inline bool interctc_after(const EcEncoder* e, size_t k) { return e->ic_index(k) >= 0; }
+// bf16 schedule: the fused kernel of interctc.hip, or no kernel (finalize refuses the handle with interctc_refusal's text).  A function of the configuration only,
+// never of the row count - as prefer_tiled above
+enum InterCtcRoute { IC_FUSED, IC_REFUSED };
+inline InterCtcRoute interctc_route(const EcEncoder* e, size_t k) { return interctc_supported(e->blocks[k].dim_expand, e->ic_vocab) ? IC_FUSED : IC_REFUSED; }
+inline std::string interctc_refusal(const EcEncoder* e, size_t k) {
+    return "InterCTC step after block " + std::to_string(k) + " (dim_expand " + std::to_string(e->blocks[k].dim_expand) + ", vocab_size " + std::to_string(e->ic_vocab) +
+           "): the fused kernel takes dim_expand % 4 == 0, dim_expand <= 768 and 2 <= vocab_size <= 1024";
+}
+
 inline TailRoute tail_route(const EcEncoder* e, size_t k) {
     const int De = e->blocks[k].dim_expand;
     if (!(e->fuse_chain && e->bw[k].chain_out && chain_tail_supported(De) && De <= e->chain_max_dim)) return TAIL_MODULES;
     // cc_full: pack.hip built the constant block (chain_full_fits under ITS pair rule); k + 1's width = De <= chain_max_dim
-    return e->bw[k].cc_full && chain_full_fits(e, k, chain_pair_on(e, De)) ? TAIL_FULL : TAIL_ONLY;
+    return e->bw[k].cc_full && chain_full_fits(e, k, chain_pair_on(e, De)) && !interctc_after(e, k) ? TAIL_FULL : TAIL_ONLY;
 }
 
 inline BlockRoutes block_routes(const EcEncoder* e, size_t k) {
@@ -188,7 +202,7 @@ struct ExactBlockRoutes {
 };
 inline TailRoute exact_tail_route(const EcEncoder* e, const ExactForwardRoutes& f, size_t k, bool rows_carry) {
     if (!(f.chains && e->bw[k].xc_out)) return TAIL_MODULES;
-    return k + 1 < e->blocks.size() && e->bw[k + 1].xc_in && e->blocks[k + 1].dim_model == e->blocks[k].dim_expand && rows_carry ? TAIL_FULL : TAIL_ONLY;
+    return k + 1 < e->blocks.size() && e->bw[k + 1].xc_in && e->blocks[k + 1].dim_model == e->blocks[k].dim_expand && rows_carry && !interctc_after(e, k) ? TAIL_FULL : TAIL_ONLY;
 }
 inline ExactBlockRoutes exact_block_routes(const EcEncoder* e, const ExactForwardRoutes& f, size_t k, bool rows_carry_in, bool rows_carry_out) {
     const BlockW& W = e->bw[k];

@@ -72,11 +72,12 @@ class _BlockHolder(nn.Module):
 
 
 class ConformerEncoder(nn.Module):
+    _interctc = False      # ConformerEncoderInterCTC: the plan carries interctc_blocks / vocab_size (this class ignores both keys, as the reference's does)
 
     def __init__(self, params: dict):
         super().__init__()
         self.params = dict(params)
-        self.plan: EncoderPlan = build_plan(params)
+        self.plan: EncoderPlan = build_plan(params, interctc=self._interctc)
         plan = self.plan
         sub = _Holder()
         layers, cin = [], 1
@@ -254,6 +255,9 @@ class ConformerEncoder(nn.Module):
         self._exact_packed = self._exact
         for oname, oval in self._options.items():
             _lib.check(lib.effconf_encoder_set_option(h, oname.encode(), oval), "set_option(%s)" % oname)
+        if self.plan.interctc_blocks:        # before finalize: it packs linear_expand_k / linear_proj_k and refuses what the kernel does not take
+            ids = (C.c_int32 * len(self.plan.interctc_blocks))(*self.plan.interctc_blocks)
+            _lib.check(lib.effconf_encoder_set_interctc(h, ids, len(self.plan.interctc_blocks), int(self.plan.interctc_vocab)), "set_interctc")
         tensors = dict(super().state_dict())
         if self._head is not None:
             tensors["fc.weight"], tensors["fc.bias"] = self._head.weight, self._head.bias
@@ -298,12 +302,13 @@ class ConformerEncoder(nn.Module):
         return ws
 
     def _run(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_audio: bool, range_hook: Optional[Callable] = None,
-             x_len_host=None, range_pad=None, return_attentions: bool = False):
+             x_len_host=None, range_pad=None, return_attentions: bool = False, return_interctc: bool = False):
+        """-> (out, out_len, attentions, interctc_probs); ``forward`` / ``forward_mel`` return what their class promises of it."""
         if x.is_cuda:
             # the C library allocates packed weights on, and launches on, the CURRENT device: make that the input's device
             with torch.cuda.device(x.device):
-                return self._run_on_device(x, x_len, from_audio, range_hook, x_len_host, range_pad, return_attentions)
-        return self._run_on_device(x, x_len, from_audio, range_hook, x_len_host, range_pad, return_attentions)
+                return self._run_on_device(x, x_len, from_audio, range_hook, x_len_host, range_pad, return_attentions, return_interctc)
+        return self._run_on_device(x, x_len, from_audio, range_hook, x_len_host, range_pad, return_attentions, return_interctc)
 
     def _range_pads(self, ranges, n, from_audio, lens, lens_given, x_len_host, range_pad):
         """Padded length (samples / mel frames) of every row range in trimmed mode, or None (every range keeps the batch's)."""
@@ -351,7 +356,7 @@ class ConformerEncoder(nn.Module):
         return [(cuts[i], cuts[i + 1]) for i in range(nsub)]
 
     def _run_on_device(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_audio: bool, range_hook: Optional[Callable],
-                       x_len_host=None, range_pad=None, return_attentions: bool = False):
+                       x_len_host=None, range_pad=None, return_attentions: bool = False, return_interctc: bool = False):
         if self.training:
             raise RuntimeError("efficientconformer_amd.ConformerEncoder is an inference path: call .eval()")
         if not x.is_cuda:
@@ -408,6 +413,17 @@ class ConformerEncoder(nn.Module):
             attentions = [torch.zeros(batch, heads[k], tg[k], tg[k], dtype=torch.float32, device=x.device) for k in range(nb)]
             _lib.check(lib.effconf_encoder_set_attention_outputs(self._handle, (C.c_void_p * nb)(*[a.data_ptr() for a in attentions]), nb),
                        "set_attention_outputs")
+        interctc_probs = []
+        if return_interctc and self.plan.interctc_blocks:
+            # the reference's fourth return value (encoders.py:211-215): softmax(linear_expand_k(x)) of every listed block, (B, T_k, V) fp32, written by the
+            # library next to the forward (effconf_encoder_set_interctc_outputs); like the attention maps: opt-in, the whole batch as ONE row range.
+            # Ragged batches: T_k of the longest utterance, an utterance's own frames and zeros behind them
+            nsub = 1
+            n_long = int(host_lens.max()) if self.ragged else n
+            ts = (self.plan.lengths(n_long)[2] if from_audio else self.plan.lengths_from_mel(n_long)[1])
+            interctc_probs = [torch.zeros(batch, ts[k], self.plan.interctc_vocab, dtype=torch.float32, device=x.device) for k in self.plan.interctc_blocks]
+            _lib.check(lib.effconf_encoder_set_interctc_outputs(self._handle, (C.c_void_p * len(interctc_probs))(*[t.data_ptr() for t in interctc_probs]),
+                                                                len(interctc_probs)), "set_interctc_outputs")
         ranges = self.row_ranges(batch, nsub, host_lens)
         pads = None if self.ragged else self._range_pads(ranges, n, from_audio, lens, lens_given, x_len_host, range_pad)
         fn_ragged = lib.effconf_encoder_forward_ragged
@@ -440,6 +456,8 @@ class ConformerEncoder(nn.Module):
             finally:
                 if return_attentions:
                     _lib.check(lib.effconf_encoder_set_attention_outputs(self._handle, None, 0), "set_attention_outputs")
+                if interctc_probs:
+                    _lib.check(lib.effconf_encoder_set_interctc_outputs(self._handle, None, 0), "set_interctc_outputs")
             if range_hook is not None:
                 range_hook(0, batch, out, out_len)
         else:
@@ -492,7 +510,7 @@ class ConformerEncoder(nn.Module):
                         range_hook(lo, hi, out, out_len)     # called with the range's stream current: rows [lo, hi) of `out` are enqueued
             for st in streams:
                 cur.wait_stream(st)                      # joined: the caller continues on its own stream
-        return out, (out_len if lens_given else None), attentions
+        return out, (out_len if lens_given else None), attentions, interctc_probs
 
     def forward(self, x: torch.Tensor, x_len: Optional[torch.Tensor] = None, range_hook: Optional[Callable] = None,
                 x_len_host=None, range_pad=None, return_attentions: bool = False):
@@ -505,12 +523,12 @@ class ConformerEncoder(nn.Module):
         ``x_len_host`` (the lengths as a host sequence) / ``range_pad`` (one padded length per row range) serve ``trim_sub_batches``.
         ``attentions`` is a list of ``None`` per block unless ``return_attentions=True``: then the reference's per-block softmax maps
         (B, H, Tg, Tg) (encoders.py:126-142), at the price of one extra kernel per block and a single row range."""
-        return self._run(x, x_len, True, range_hook, x_len_host, range_pad, return_attentions)
+        return self._run(x, x_len, True, range_hook, x_len_host, range_pad, return_attentions)[:3]
 
     def forward_mel(self, mel: torch.Tensor, mel_len: Optional[torch.Tensor] = None, range_hook: Optional[Callable] = None,
                     x_len_host=None, range_pad=None, return_attentions: bool = False):
         """Enter after AudioPreprocessing: mel (B, n_mels, Tm), lengths in frames (the parity boundary)."""
-        return self._run(mel, mel_len, False, range_hook, x_len_host, range_pad, return_attentions)
+        return self._run(mel, mel_len, False, range_hook, x_len_host, range_pad, return_attentions)[:3]
 
     def mel_frontend(self, x: torch.Tensor, x_len: Optional[torch.Tensor] = None):
         """AudioPreprocessing.forward (reference modules.py:87-106) on the GPU."""
@@ -541,7 +559,7 @@ class ConformerEncoder(nn.Module):
         arena = torch.zeros(arena_bytes, dtype=torch.uint8, device=mel.device)
         _lib.check(lib.effconf_encoder_set_trace(self._handle, arena.data_ptr(), arena.numel()), "set_trace")
         try:
-            out, out_len, _ = fwd(mel, mel_len)
+            out, out_len = fwd(mel, mel_len)[:2]
             torch.cuda.synchronize()
             res = {}
             name = C.create_string_buffer(64)
@@ -557,3 +575,33 @@ class ConformerEncoder(nn.Module):
             return out, out_len, res
         finally:
             lib.effconf_encoder_set_trace(self._handle, None, 0)
+
+
+class ConformerEncoderInterCTC(ConformerEncoder):
+    """Drop-in for the reference's ``ConformerEncoderInterCTC`` (models/encoders.py:144-215): self-conditioned CTC.  After every block k listed in
+    ``params["interctc_blocks"]``:  p = softmax(linear_expand_k(x));  x = x + linear_proj_k(p)  - one fused HIP kernel per step on the bf16 path
+    (csrc/interctc.hip: the (rows, vocab) logits stay on the CU), GEMM + row softmax + GEMM in the label-exact modes.  ``params["vocab_size"]`` is
+    required (``InterCTC`` sets it from the tokenizer).  The holder ``nn.Linear`` modules sit under the reference's attribute names, so the
+    ``state_dict`` keys are the reference's.
+
+    ``forward`` / ``forward_mel`` return ``(x, x_len, attentions, interctc_probs)``: ``interctc_probs`` is ``[]`` unless ``return_interctc=True`` -
+    then one fp32 (B, T_k, V) tensor per listed block in block order (ragged batches: zeros behind an utterance's own frames), at the price of one
+    light extra kernel per step and a single row range.  Everything else - ragged batches, ``sub_batches``, ``precision``, the trace - is the parent's."""
+    _interctc = True
+
+    def __init__(self, params: dict):
+        super().__init__(params)
+        self.interctc_blocks = list(self.plan.interctc_blocks)
+        for k in self.interctc_blocks:       # encoders.py:152-161
+            de = self.plan.blocks[k].dim_expand
+            setattr(self, "linear_expand_%d" % k, nn.Linear(de, self.plan.interctc_vocab))
+            setattr(self, "linear_proj_%d" % k, nn.Linear(self.plan.interctc_vocab, de))
+        self.eval()
+
+    def forward(self, x: torch.Tensor, x_len: Optional[torch.Tensor] = None, range_hook: Optional[Callable] = None,
+                x_len_host=None, range_pad=None, return_attentions: bool = False, return_interctc: bool = False):
+        return self._run(x, x_len, True, range_hook, x_len_host, range_pad, return_attentions, return_interctc)
+
+    def forward_mel(self, mel: torch.Tensor, mel_len: Optional[torch.Tensor] = None, range_hook: Optional[Callable] = None,
+                    x_len_host=None, range_pad=None, return_attentions: bool = False, return_interctc: bool = False):
+        return self._run(mel, mel_len, False, range_hook, x_len_host, range_pad, return_attentions, return_interctc)

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib, _targets
 from .config import load_config
-from .encoders import ConformerEncoder
+from .encoders import ConformerEncoder, ConformerEncoderInterCTC
 
 
 class Alignment(NamedTuple):
@@ -89,13 +89,14 @@ def select_nbest(am_score: torch.Tensor, lm_score: torch.Tensor, token_len: torc
 
 
 class ModelCTC(nn.Module):
+    _encoder_cls = ConformerEncoder
 
     def __init__(self, encoder_params: dict, tokenizer_params: dict, training_params: Optional[dict] = None,
                  decoding_params: Optional[dict] = None, name: str = "model", tokenizer=None):
         super().__init__()
         if encoder_params.get("arch", "Conformer") != "Conformer":
             raise Exception("Unknown encoder architecture:", encoder_params.get("arch"))
-        self.encoder = ConformerEncoder(encoder_params)
+        self.encoder = self._encoder_cls(encoder_params)
         self.fc = nn.Linear(self.encoder.plan.dim_out, tokenizer_params["vocab_size"])
         self.encoder.attach_head(self.fc)
         decoding_params = decoding_params or {}
@@ -115,6 +116,8 @@ class ModelCTC(nn.Module):
     @classmethod
     def from_config(cls, cfg, tokenizer=None):
         cfg = load_config(cfg)
+        if cls is ModelCTC and cfg.get("model_type") == "InterCTC":      # functions.py:59-66: model_type selects the class
+            cls = InterCTC
         return cls(cfg["encoder_params"], cfg["tokenizer_params"], cfg.get("training_params"),
                    cfg.get("decoding_params"), cfg.get("model_name", "model"), tokenizer)
 
@@ -140,7 +143,7 @@ class ModelCTC(nn.Module):
     # ---- reference ModelCTC.forward (model_ctc.py:57-68): batch = (x, y, x_len, y_len)
     def forward(self, batch, return_attentions: bool = False):
         x, _, x_len, _ = batch
-        enc, enc_len, attentions = self.encoder(x, x_len, return_attentions=return_attentions)
+        enc, enc_len, attentions = self.encoder(x, x_len, return_attentions=return_attentions)[:3]
         logits, _, _ = self._head(enc, enc_len, want_logits=True)
         return logits, enc_len, attentions
 
@@ -318,7 +321,7 @@ class ModelCTC(nn.Module):
                 tns.record_stream(st)
 
         with torch.cuda.device(x.device):
-            enc, enc_len, _ = (self.encoder.forward_mel if from_mel else self.encoder)(x, x_len, range_hook=hook, **encoder_kwargs)
+            enc, enc_len = (self.encoder.forward_mel if from_mel else self.encoder)(x, x_len, range_hook=hook, **encoder_kwargs)[:2]
         return enc, enc_len, state["labels"], state["label_len"]
 
     def greedy_labels(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_mel: bool = False, *, label_exact: Optional[str] = None,
@@ -331,7 +334,7 @@ class ModelCTC(nn.Module):
         if label_exact is not None:
             labels, label_len, _ = self.greedy_exact(x, x_len, float("inf") if label_exact == "always" else band, from_mel)
         else:
-            enc, enc_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+            enc, enc_len = (self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len))[:2]      # [:2]: the InterCTC encoder returns four values
             _, labels, label_len = self._head(enc, enc_len)
         labels, label_len = labels.cpu(), label_len.cpu()          # one D2H copy per batch, not one per token
         return [labels[b, :int(label_len[b])].tolist() for b in range(labels.shape[0])]
@@ -421,7 +424,7 @@ class ModelCTC(nn.Module):
         self._check_beam(beam, self.fc.out_features)
         if not x.is_cuda:
             raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
-        enc, enc_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+        enc, enc_len = (self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len))[:2]      # [:2]: the InterCTC encoder returns four values
         logits, _, _ = self._head(enc, enc_len, want_logits=True)
         tokens, token_len, _ = self.decode_logits_beam(logits, enc_len, beam)
         tokens, token_len = tokens[:, 0].cpu(), token_len[:, 0].cpu()          # one D2H copy per batch
@@ -544,7 +547,7 @@ class ModelCTC(nn.Module):
     def _logits(self, x, x_len, from_mel):
         if not x.is_cuda:
             raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
-        enc, enc_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
+        enc, enc_len = (self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len))[:2]      # [:2]: the InterCTC encoder returns four values
         return self._head(enc, enc_len, want_logits=True) + (enc_len,)
 
     def _records(self, out, tg, tl) -> List[Alignment]:
@@ -580,3 +583,24 @@ class ModelCTC(nn.Module):
         u = min(int(labels.shape[1]), 2047)
         tg, tl = labels[:, :u].contiguous(), label_len.to(torch.int64)
         return self._records(self.align_logits(logits, enc_len, tg, tl), tg, tl)
+
+
+class InterCTC(ModelCTC):
+    """The reference's ``InterCTC`` model (models/model_ctc.py:183-215; ``model_type: "InterCTC"``): a CTC model on ``ConformerEncoderInterCTC`` -
+    self-conditioned CTC after the blocks of ``encoder_params["interctc_blocks"]``, with ``vocab_size`` taken from the tokenizer params.
+    ``forward(batch)`` returns the reference's four values (logits, lengths, attentions, interctc_probs); every decoder of ``ModelCTC`` - greedy,
+    ``greedy_exact``, beam search, rescoring, ``align``, ``score_labels``, ``greedy_alignment`` - is inherited unchanged: they read the encoder's output
+    rows only.  Training (``LossInterCTC``) is out of scope, as for ``ModelCTC``."""
+    _encoder_cls = ConformerEncoderInterCTC
+
+    def __init__(self, encoder_params: dict, tokenizer_params: dict, training_params: Optional[dict] = None,
+                 decoding_params: Optional[dict] = None, name: str = "model", tokenizer=None):
+        encoder_params = dict(encoder_params)
+        encoder_params["vocab_size"] = tokenizer_params["vocab_size"]          # model_ctc.py:189
+        super().__init__(encoder_params, tokenizer_params, training_params, decoding_params, name, tokenizer)
+
+    def forward(self, batch, return_attentions: bool = False, return_interctc: bool = True):
+        x, _, x_len, _ = batch
+        enc, enc_len, attentions, interctc_probs = self.encoder(x, x_len, return_attentions=return_attentions, return_interctc=return_interctc)
+        logits, _, _ = self._head(enc, enc_len, want_logits=True)
+        return logits, enc_len, attentions, interctc_probs

@@ -69,6 +69,10 @@ def param_specs(plan: EncoderPlan) -> List[Spec]:
         out += _ln(p + ".norm", de)
         if b.transition:
             out += [(p + ".conv_res.1.weight", (de, d, 1), W), (p + ".conv_res.1.bias", (de,), B)]
+    # self-conditioned CTC (encoders.py:152-161): after all blocks, on the listed block's output width; nothing for a plan without such blocks
+    for k in plan.interctc_blocks:
+        de, v = plan.blocks[k].dim_expand, plan.interctc_vocab
+        out += _lin("linear_expand_%d" % k, v, de) + _lin("linear_proj_%d" % k, de, v)
     return out
 
 

@@ -468,6 +468,21 @@ int effconf_encoder_trace_entry(const EcEncoder* enc, int32_t i, char* name64, i
 int effconf_encoder_attention_dims(EcEncoder* enc, int32_t n, int32_t from_audio, int32_t* heads, int32_t* tg);
 int effconf_encoder_set_attention_outputs(EcEncoder* enc, float* const* maps, int32_t n_blocks);
 
+/* ---- self-conditioned CTC (the reference's ConformerEncoderInterCTC, encoders.py:144-215): after every listed block
+ *     p = softmax(linear_expand_k(x));  x = x + linear_proj_k(p)
+ * effconf_encoder_set_interctc: between create and finalize; blocks = n distinct block indices, vocab_size in 2..1024, every listed block's dim_expand
+ * <= 768 (checked at finalize, which then also requires linear_expand_<k>.{weight (V, De), bias (V)} and linear_proj_<k>.{weight (De, V), bias (De)}
+ * through effconf_encoder_load_tensor).  n = 0 removes the steps.
+ * effconf_encoder_set_interctc_outputs: like effconf_encoder_set_attention_outputs - one device buffer per LISTED block in block order (null = skip,
+ * probs = null or n = 0 clears); every following forward writes the fp32 probabilities (batch, T_k, V), T_k = frames leaving block k (ragged
+ * batches: T_k of the longest utterance, an utterance's own frames and zeros behind them).
+ * effconf_interctc: ONE step of listed block `block` on the product kernel: x, y fp32 (rows, dim_expand) dense, y may alias x; probs (rows, V) or
+ * null.  workspace is not used by the bf16 kernel (may be null). */
+int effconf_encoder_set_interctc(EcEncoder* enc, const int32_t* blocks, int32_t n, int32_t vocab_size);
+int effconf_encoder_set_interctc_outputs(EcEncoder* enc, float* const* probs, int32_t n);
+int effconf_interctc(EcEncoder* enc, int32_t block, const float* x, int32_t rows, float* y, float* probs, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* ---- host helper of the batching front door (reference: utils/preprocessing.py:33-45, collate_fn_pad zero-pads a sorted batch) -------
  * Copies n host rows src[i][0 .. len[i]) to dst + i * pitch (floats) on `threads` host threads, zero-filling dst[i][len[i] .. pitch) when
  * zero_pad != 0 (ragged batches never read the pad samples: pass 0).  dst is typically pinned memory, so that ONE H2D copy follows.  No

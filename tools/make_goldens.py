@@ -11,7 +11,8 @@ It refuses to run where /root/reference is absent (e.g. the GPU box).
     python tools/make_goldens.py            # regenerate every fixture
     python tools/make_goldens.py --only-rnnt-beam   # only tests/golden/rnnt_beam_*.npz (from the stored rnnt_*.npz encoder outputs)
     python tools/make_goldens.py --only-rnnt-lattice   # only tests/golden/rnnt_lattice_*.npz (from the stored rnnt_*.npz encoder outputs)
-    python tools/make_goldens.py --only-lm             # only tests/golden/lm_*.npz (LSTM language model; TinyLM's rescoring bias from tiny_T*.npz)
+    python tools/make_goldens.py --only-interctc       # only tests/golden/interctc_tiny_*.npz (the reference's ConformerEncoderInterCTC on Tiny)
+    python tools/make_goldens.py --only-lm           # only tests/golden/lm_*.npz (LSTM language model; TinyLM's rescoring bias from tiny_T*.npz)
 """
 import os
 import sys
@@ -388,10 +389,44 @@ def streaming_goldens(enc_mod):
              **{"cfg/" + k: np.int64(v) for k, v in extra.items()})
 
 
+def interctc_goldens(enc_mod):
+    """Self-conditioned CTC: the reference's own ConformerEncoderInterCTC (encoders.py:144-215) driven from mel on Tiny with interctc_blocks = [1, 3, 5]
+    (both transition blocks and the last block) and vocabulary 32, the two batches of tiny_T*.npz, weight seed 7, in the two weight recipes of
+    tests/interctc_ref.py (flat: the key-seeded tensors; peaky: confident rows, p.max() = 1).  Arrays and key names only."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import interctc_ref as IR
+    params = IR.tiny_params()
+    plan = build_plan(params, interctc=True)
+    for recipe in IR.RECIPES:
+        sd = IR.tiny_state_dict(recipe)
+        for tm, lens in IR.BATCHES:
+            mel, ln = IR.tiny_mel(tm, lens)
+            model = enc_mod.ConformerEncoderInterCTC(dict(params)).eval()
+            model.load_state_dict(to_torch({k: v for k, v in sd.items() if not k.startswith("fc.")}), strict=True)
+            keys = sorted(model.state_dict().keys())
+            fc = nn.Linear(plan.dim_out, IR.TINY_VOCAB).eval()
+            fc.load_state_dict({"weight": torch.from_numpy(sd["fc.weight"]), "bias": torch.from_numpy(sd["fc.bias"])})
+            model.preprocessing.forward = lambda x, l: (x, l)      # frontend lives in torchaudio (absent): start from mel
+            with torch.no_grad():
+                x, out_len, _, probs = model(torch.from_numpy(mel), torch.from_numpy(ln))
+                logits = fc(x)
+            lab, offs = pack_labels(greedy_reference(logits, out_len))
+            arrs = {"mel_seed": np.int64(4321 + tm), "weight_seed": np.int64(IR.WEIGHT_SEED), "mel_len": ln, "vocab_size": np.int64(IR.TINY_VOCAB),
+                    "interctc_blocks": np.asarray(IR.TINY_BLOCKS, dtype=np.int64), "out": x.numpy(), "out_len": out_len.numpy(), "logits": logits.numpy(),
+                    "labels": lab, "label_offsets": offs, "state_dict_keys": np.frombuffer("\n".join(keys).encode(), dtype=np.uint8)}
+            for k, p in zip(IR.TINY_BLOCKS, probs):
+                arrs["probs_%d" % k] = p.numpy()
+            pmax, pmin = max(float(p.max()) for p in probs), min(float(p.min()) for p in probs)
+            print("  %s T%d: p.max %.6g p.min %.3g, labels per utterance %s" % (recipe, tm, pmax, pmin, np.diff(offs).tolist()))
+            save("interctc_tiny_%s_T%d" % (recipe, tm), **arrs)
+
+
 def main():
     torch.manual_seed(0)
     torch.set_num_threads(8)
     enc_mod, att_mod = import_reference()
+    if "--only-interctc" in sys.argv:
+        return interctc_goldens(enc_mod)
     if "--only-rnnt" in sys.argv:
         return rnnt_goldens(enc_mod)
     if "--only-rnnt-beam" in sys.argv:
@@ -406,6 +441,7 @@ def main():
     rnnt_beam_goldens()
     rnnt_lattice_goldens()
     streaming_goldens(enc_mod)
+    interctc_goldens(enc_mod)
     # lm_goldens() reads tiny_T*.npz: after section 1 below (or --only-lm on stored ones)
 
     # ---- 1. tiny config: every module output, two sequence lengths (T1 % 3 == 0 and != 0)
