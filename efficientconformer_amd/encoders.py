@@ -17,15 +17,15 @@ Differences from the reference, by design (HISTORY.md):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import os
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _native
 from .config import EncoderPlan, build_plan
 
 
@@ -88,7 +88,7 @@ class ConformerEncoder(nn.Module):
         self.subsampling_module = sub
         self.linear = nn.Linear(plan.dim_in, plan.blocks[0].dim_model)
         self.blocks = nn.ModuleList([_BlockHolder(bp) for bp in plan.blocks])
-        self._handle = None
+        self._native = _native.Handle("encoder")
         self._packed = False
         self._packed_device = -1                  # the C library packs weights on the device that is current at pack time
         object.__setattr__(self, "_head", None)   # not a sub-module: keeps state_dict keys equal to the reference's
@@ -188,6 +188,11 @@ class ConformerEncoder(nn.Module):
             f *= b.conv_stride
         return f
 
+    @property
+    def _handle(self):
+        """The native encoder handle (None before the first pack); ``self._native`` owns it."""
+        return self._native.ptr
+
     def _param_device(self):
         return self.linear.weight.device
 
@@ -242,45 +247,27 @@ class ConformerEncoder(nn.Module):
         if self._packed and self._packed_device == dev:
             return
         lib = _lib.load()
-        if self._handle is not None:
-            lib.effconf_encoder_destroy(self._handle)
-            self._handle = None
         cfg, keep = self._make_config()
-        h = lib.effconf_encoder_create(C.byref(cfg))
-        if not h:
-            raise _lib.EffconfError("effconf_encoder_create: %s" % lib.effconf_last_error().decode())
-        self._handle = h
-        if self._exact:
-            _lib.check(lib.effconf_encoder_set_option(h, b"exact_fp32", int(self._exact)), "set_option(exact_fp32)")
-        self._exact_packed = self._exact
-        for oname, oval in self._options.items():
-            _lib.check(lib.effconf_encoder_set_option(h, oname.encode(), oval), "set_option(%s)" % oname)
-        if self.plan.interctc_blocks:        # before finalize: it packs linear_expand_k / linear_proj_k and refuses what the kernel does not take
-            ids = (C.c_int32 * len(self.plan.interctc_blocks))(*self.plan.interctc_blocks)
-            _lib.check(lib.effconf_encoder_set_interctc(h, ids, len(self.plan.interctc_blocks), int(self.plan.interctc_vocab)), "set_interctc")
+
+        def before_load(h):      # before finalize: some options shape what it builds
+            if self._exact:
+                _lib.check(lib.effconf_encoder_set_option(h, b"exact_fp32", int(self._exact)), "set_option(exact_fp32)")
+            self._exact_packed = self._exact
+            for oname, oval in self._options.items():
+                _lib.check(lib.effconf_encoder_set_option(h, oname.encode(), oval), "set_option(%s)" % oname)
+            if self.plan.interctc_blocks:        # finalize packs linear_expand_k / linear_proj_k and refuses what the kernel does not take
+                ids = (C.c_int32 * len(self.plan.interctc_blocks))(*self.plan.interctc_blocks)
+                _lib.check(lib.effconf_encoder_set_interctc(h, ids, len(self.plan.interctc_blocks), int(self.plan.interctc_vocab)), "set_interctc")
+
         tensors = dict(super().state_dict())
         if self._head is not None:
             tensors["fc.weight"], tensors["fc.bias"] = self._head.weight, self._head.bias
-        for key, t in tensors.items():
-            if key.endswith("num_batches_tracked"):
-                continue
-            arr = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-            _lib.check(lib.effconf_encoder_load_tensor(h, key.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim),
-                       "load_tensor(%s)" % key)
-        _lib.check(lib.effconf_encoder_finalize(h), "finalize")
+        self._native.rebuild(cfg, [(k, t) for k, t in tensors.items() if not k.endswith("num_batches_tracked")], before_load)
         # this wrapper owns its workspaces exclusively, so the input-independent positional projections may be cached
-        _lib.check(lib.effconf_encoder_set_option(h, b"cache_pos_embeddings", 1), "set_option")
+        _lib.check(lib.effconf_encoder_set_option(self._handle, b"cache_pos_embeddings", 1), "set_option")
         self._ws.clear()
         self._packed = True
         self._packed_device = dev
-
-    def __del__(self):
-        try:
-            if self._handle is not None and _lib._lib is not None:
-                _lib._lib.effconf_encoder_destroy(self._handle)
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ forward
     def _workspace(self, batch: int, n: int, from_audio: bool, device, nbytes: Optional[int] = None) -> torch.Tensor:
@@ -292,11 +279,7 @@ class ConformerEncoder(nn.Module):
             nbytes = _lib.load().effconf_encoder_workspace_bytes(self._handle, batch, n, int(from_audio))
         ws = self._ws.get(key)
         if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            fill = os.environ.get("EFFCONF_POISON_WORKSPACE", "")
-            if fill:                # test hook (include/effconf.h): the byte a fresh workspace is filled with - 255 = NaN patterns, 127 =
-                ws.fill_(int(fill)) # huge finite values, 0 = zeros; a kernel that reads workspace nobody wrote shows up as a difference
-            self._ws[key] = ws
+            ws = self._ws[key] = _native.workspace(nbytes, device)
             # a fresh workspace has no valid positional-embedding cache, even if the allocator reuses an old address
             _lib.check(_lib.load().effconf_encoder_set_option(self._handle, b"cache_pos_embeddings", 1), "set_option")
         return ws
@@ -355,6 +338,133 @@ class ConformerEncoder(nn.Module):
             cuts = [c - c % 16 for c in cuts[:-1]] + [batch]
         return [(cuts[i], cuts[i + 1]) for i in range(nsub)]
 
+    @staticmethod
+    def stream_plan(nsub: int, sub_batch_streams: Optional[int], caller_stream_slot) -> List[tuple]:
+        """The enqueue order of a forward's `nsub` row ranges: [(range index, stream slot, on the caller's stream)].  Range i runs on slot
+        i % smax (smax = `sub_batch_streams`, at most - and by default - one slot per range); slot 0 is the caller's stream, and the ranges of the
+        other slots are enqueued first: the side streams run while the host enqueues the rest.  `caller_stream_slot` False: plain order, every
+        slot a side stream.  Pure: no GPU."""
+        smax = nsub if not sub_batch_streams else max(1, min(int(sub_batch_streams), nsub))
+        if caller_stream_slot is False:
+            return [(i, i % smax, False) for i in range(nsub)]
+        order = [i for i in range(nsub) if i % smax != 0] + [i for i in range(nsub) if i % smax == 0]
+        return [(i, i % smax, i % smax == 0) for i in order]
+
+    def _host_lengths(self, x_len, lens: torch.Tensor, x_len_host, batch: int) -> np.ndarray:
+        """The host copy of a ragged batch's lengths ONCE, validated before anything is sized from it (without x_len_host: one device sync)."""
+        if self._exact == 1:
+            raise RuntimeError("ragged batches run on the bf16 path and in precision = 'split' (precision = 'fp32' keeps rectangular batches)")
+        hl = x_len_host if x_len_host is not None else lens.cpu()
+        host_lens = np.ascontiguousarray(np.asarray(hl.cpu() if torch.is_tensor(hl) else hl, dtype=np.int64))
+        if host_lens.shape != (batch,):
+            raise ValueError("x_len_host needs one length per utterance")
+        if x_len_host is not None and self.check_host_lengths and not self._capturing(lens.device):
+            # Remembered only for the caller's OWN tensor object (no dtype / device conversion happened: `lens is x_len`), held by a strong reference
+            # together with its version counter: a converted temporary - or a tensor the caller freed - can come back from the caching allocator at the
+            # same address with version 0 and different lengths (round 5 keyed the memo by data_ptr and skipped the comparison then).
+            hb = host_lens.tobytes()
+            memo = self._len_verified
+            same = lens is x_len and memo is not None and memo[0] is x_len and memo[1] == x_len._version and memo[2] == hb
+            if not same:
+                if not np.array_equal(host_lens, lens.cpu().numpy()):
+                    raise ValueError("x_len_host differs from x_len: the ragged forward sizes its grids and workspace from the host lengths "
+                                     "and indexes with the device lengths - they must be the same numbers")
+                self._len_verified = (x_len, x_len._version, hb) if lens is x_len else None
+        return host_lens
+
+    @contextlib.contextmanager
+    def _optional_outputs(self, batch: int, n_long: int, from_audio: bool, device, attention_maps: bool, interctc: bool):
+        """-> (attentions, interctc_probs) for one forward of the whole batch as ONE row range (`n_long`: the longest utterance of a ragged batch,
+        else the row length): the library writes both next to the forward while their pointers are set, and they are cleared on exit."""
+        lib = _lib.load()
+        nb = len(self.plan.blocks)
+        attentions, interctc_probs, to_clear = [None] * nb, [], []
+        try:
+            if attention_maps:
+                # the reference's third return value (encoders.py:126-142): one (B, H, Tg, Tg) softmax map per block
+                # (ragged batches, round 4: the same rectangles sized for the LONGEST utterance of the batch; an utterance's own Tg x Tg block is
+                # its map when run alone, the rest is zero)
+                heads, tg = (C.c_int32 * nb)(), (C.c_int32 * nb)()
+                _lib.check(lib.effconf_encoder_attention_dims(self._handle, n_long, int(from_audio), heads, tg), "attention_dims")
+                # zeros: "an utterance's own block = its map, the rest zero" does not depend on the kernel writing every element (opt-in path, cheap)
+                attentions = [torch.zeros(batch, heads[k], tg[k], tg[k], dtype=torch.float32, device=device) for k in range(nb)]
+                _lib.check(lib.effconf_encoder_set_attention_outputs(self._handle, (C.c_void_p * nb)(*[a.data_ptr() for a in attentions]), nb),
+                           "set_attention_outputs")
+                to_clear.append((lib.effconf_encoder_set_attention_outputs, "set_attention_outputs"))
+            if interctc:
+                # the reference's fourth return value (encoders.py:211-215): softmax(linear_expand_k(x)) of every listed block, (B, T_k, V) fp32.
+                # Ragged batches: T_k of the longest utterance, an utterance's own frames and zeros behind them
+                ts = (self.plan.lengths(n_long)[2] if from_audio else self.plan.lengths_from_mel(n_long)[1])
+                interctc_probs = [torch.zeros(batch, ts[k], self.plan.interctc_vocab, dtype=torch.float32, device=device) for k in self.plan.interctc_blocks]
+                _lib.check(lib.effconf_encoder_set_interctc_outputs(self._handle, (C.c_void_p * len(interctc_probs))(*[t.data_ptr() for t in interctc_probs]),
+                                                                    len(interctc_probs)), "set_interctc_outputs")
+                to_clear.append((lib.effconf_encoder_set_interctc_outputs, "set_interctc_outputs"))
+            yield attentions, interctc_probs
+        finally:
+            for clear, what in to_clear:
+                _lib.check(clear(self._handle, None, 0), what)
+
+    def _launch_range(self, x, lens, host_lens, n: int, from_audio: bool, out, out_len, lo: int, hi: int, pad: Optional[int] = None):
+        """Rows [lo, hi) on the current stream, written straight into out[lo:hi].  `host_lens` given: the ragged forward.  `pad` given: the rows
+        as their own batch, padded to pad <= n - what the reference computes when these utterances are collated alone."""
+        lib, dev, t_out = _lib.load(), x.device, out.shape[1]
+        if host_lens is not None:
+            hptr = host_lens[lo:hi].ctypes.data_as(C.c_void_p)
+            nbytes = lib.effconf_encoder_workspace_bytes_ragged(self._handle, hptr, hi - lo, n, int(from_audio))
+            if nbytes == 0:
+                raise _lib.EffconfError("ragged batch: a length is out of range (audio: n_fft / 2 < len <= row length)")
+            ws = self._workspace(hi - lo, n, from_audio, dev, nbytes)
+            _lib.check(lib.effconf_encoder_forward_ragged(self._handle, x[lo:].data_ptr(), lens[lo:].data_ptr(), hptr, hi - lo, n, int(from_audio),
+                                                          out[lo:].data_ptr(), t_out, out_len[lo:].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                          torch.cuda.current_stream(dev).cuda_stream), "encoder_forward_ragged")
+            return
+        xi, oi = x[lo:], out[lo:]
+        if pad is not None:
+            xi, n = (x[lo:hi, :pad] if from_audio else x[lo:hi, :, :pad]).contiguous(), pad
+            ti = lib.effconf_encoder_out_frames(self._handle, n, int(from_audio))
+            oi = out[lo:hi] if ti == t_out else torch.empty(hi - lo, ti, self.plan.dim_out, dtype=torch.float32, device=dev)
+        fn = lib.effconf_encoder_forward if from_audio else lib.effconf_encoder_forward_mel
+        ws = self._workspace(hi - lo, n, from_audio, dev)
+        _lib.check(fn(self._handle, xi.data_ptr(), lens[lo:].data_ptr(), hi - lo, n, oi.data_ptr(), out_len[lo:].data_ptr(),
+                      ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "encoder_forward")
+        if oi.shape[1] != t_out:
+            out[lo:hi, :oi.shape[1]] = oi
+            out[lo:hi, oi.shape[1]:] = 0
+
+    def _fan_out(self, ranges, pads, range_hook, x, lens, host_lens, n: int, from_audio: bool, out, out_len):
+        """The row ranges on concurrent streams, in ``stream_plan``'s order; joined: the caller continues on its own stream."""
+        cur = torch.cuda.current_stream(x.device)
+        streams = []
+        # Stream slot 0 IS the caller's stream; slots 1 .. smax - 1 are side streams that fork from an event recorded before anything of
+        # this forward is enqueued.  (Measured on the MI355X: with more than four HIP streams active in the process the ranges stop
+        # overlapping - three side streams + the caller's idle stream + ONE more (a collective's stream, a consumer's stream) turned a
+        # 5.5 ms step into 7.4 ms, `GPU_MAX_HW_QUEUES` notwithstanding - so the forward itself uses smax streams, not smax + 1, and leaves
+        # room for the process group's own stream.)
+        fork = torch.cuda.Event()
+        fork.record(cur)
+        for i, slot, on_caller in self.stream_plan(len(ranges), self.sub_batch_streams, self.caller_stream_slot):
+            if on_caller:
+                st = cur
+            else:
+                # earlier row ranges get the higher priority (opt-in `stagger_ranges`): range 0 leaves the last stage first
+                prio = -1 if (i == 0 and self.stagger_ranges) else 0
+                key = (str(x.device), slot, prio)        # the priority is part of the key: `stagger_ranges` may change after the first forward
+                if key not in self._sub_streams:
+                    self._sub_streams[key] = torch.cuda.Stream(device=x.device, priority=prio)
+                st = self._sub_streams[key]
+                if st not in streams:
+                    st.wait_event(fork)              # inputs (and anything queued before this forward) are ready
+                    streams.append(st)
+            lo, hi = ranges[i]
+            with torch.cuda.stream(st):
+                self._launch_range(x, lens, host_lens, n, from_audio, out, out_len, lo, hi, None if pads is None else pads[i])
+                if st is not cur:
+                    x.record_stream(st); lens.record_stream(st); out.record_stream(st); out_len.record_stream(st)
+                if range_hook is not None:
+                    range_hook(lo, hi, out, out_len)     # called with the range's stream current: rows [lo, hi) of `out` are enqueued
+        for st in streams:
+            cur.wait_stream(st)
+
     def _run_on_device(self, x: torch.Tensor, x_len: Optional[torch.Tensor], from_audio: bool, range_hook: Optional[Callable],
                        x_len_host=None, range_pad=None, return_attentions: bool = False, return_interctc: bool = False):
         if self.training:
@@ -365,99 +475,24 @@ class ConformerEncoder(nn.Module):
         self._ensure_packed()
         x = x.contiguous().float()
         batch, n = (x.shape[0], x.shape[1]) if from_audio else (x.shape[0], x.shape[2])
-        lens_given = x_len is not None
-        lens = (x_len if lens_given else torch.full((batch,), n, dtype=torch.int64)).to(x.device, torch.int64).contiguous()
+        lens = _native.lengths(x_len, batch, n, x.device)
         t_out = lib.effconf_encoder_out_frames(self._handle, n, int(from_audio))
         out = torch.empty(batch, t_out, self.plan.dim_out, dtype=torch.float32, device=x.device)
         out_len = torch.empty(batch, dtype=torch.int64, device=x.device)
-        fn = lib.effconf_encoder_forward if from_audio else lib.effconf_encoder_forward_mel
-
-        def launch(lo: int, hi: int):      # rows [lo, hi) on the current stream, written straight into out[lo:hi]
-            ws = self._workspace(hi - lo, n, from_audio, x.device)
-            _lib.check(fn(self._handle, x[lo:].data_ptr(), lens[lo:].data_ptr(), hi - lo, n, out[lo:].data_ptr(), out_len[lo:].data_ptr(),
-                          ws.data_ptr(), ws.numel(), torch.cuda.current_stream(x.device).cuda_stream), "encoder_forward")
-
         nsub = self.sub_batches if self.sub_batches is not None else (2 if batch >= self.sub_batch_min else 1)
         nsub = max(1, min(int(nsub), batch))
-        attentions = [None] * len(self.plan.blocks)
-        host_lens = None
-        if self.ragged:            # the host copy of the lengths ONCE, validated before anything is sized from it (without x_len_host: one device sync)
-            if self._exact == 1:
-                raise RuntimeError("ragged batches run on the bf16 path and in precision = 'split' (precision = 'fp32' keeps rectangular batches)")
-            hl = x_len_host if x_len_host is not None else lens.cpu()
-            host_lens = np.ascontiguousarray(np.asarray(hl.cpu() if torch.is_tensor(hl) else hl, dtype=np.int64))
-            if host_lens.shape != (batch,):
-                raise ValueError("x_len_host needs one length per utterance")
-            if x_len_host is not None and self.check_host_lengths and not self._capturing(x.device):
-                # Remembered only for the caller's OWN tensor object (no dtype / device conversion happened: `lens is x_len`), held by a strong reference
-                # together with its version counter: a converted temporary - or a tensor the caller freed - can come back from the caching allocator at the
-                # same address with version 0 and different lengths (round 5 keyed the memo by data_ptr and skipped the comparison then).
-                hb = host_lens.tobytes()
-                memo = self._len_verified
-                same = lens is x_len and memo is not None and memo[0] is x_len and memo[1] == x_len._version and memo[2] == hb
-                if not same:
-                    if not np.array_equal(host_lens, lens.cpu().numpy()):
-                        raise ValueError("x_len_host differs from x_len: the ragged forward sizes its grids and workspace from the host lengths "
-                                         "and indexes with the device lengths - they must be the same numbers")
-                    self._len_verified = (x_len, x_len._version, hb) if lens is x_len else None
-        if return_attentions:
-            # the reference's third return value (encoders.py:126-142): one (B, H, Tg, Tg) softmax map per block, written by the library
-            # next to the forward (effconf_encoder_set_attention_outputs); the whole batch as ONE rectangular range
-            # (ragged batches, round 4: the same rectangles sized for the LONGEST utterance of the batch; an utterance's own Tg x Tg block is
-            # its map when run alone, the rest is zero)
-            nsub, nb = 1, len(self.plan.blocks)
-            heads, tg = (C.c_int32 * nb)(), (C.c_int32 * nb)()
-            n_att = int(host_lens.max()) if self.ragged else n
-            _lib.check(lib.effconf_encoder_attention_dims(self._handle, n_att, int(from_audio), heads, tg), "attention_dims")
-            # zeros: "an utterance's own block = its map, the rest zero" does not depend on the kernel writing every element (opt-in path, cheap)
-            attentions = [torch.zeros(batch, heads[k], tg[k], tg[k], dtype=torch.float32, device=x.device) for k in range(nb)]
-            _lib.check(lib.effconf_encoder_set_attention_outputs(self._handle, (C.c_void_p * nb)(*[a.data_ptr() for a in attentions]), nb),
-                       "set_attention_outputs")
-        interctc_probs = []
-        if return_interctc and self.plan.interctc_blocks:
-            # the reference's fourth return value (encoders.py:211-215): softmax(linear_expand_k(x)) of every listed block, (B, T_k, V) fp32, written by the
-            # library next to the forward (effconf_encoder_set_interctc_outputs); like the attention maps: opt-in, the whole batch as ONE row range.
-            # Ragged batches: T_k of the longest utterance, an utterance's own frames and zeros behind them
+        host_lens = self._host_lengths(x_len, lens, x_len_host, batch) if self.ragged else None
+        return_interctc = return_interctc and bool(self.plan.interctc_blocks)
+        attentions, interctc_probs = [None] * len(self.plan.blocks), []
+        extras = contextlib.nullcontext((attentions, interctc_probs))
+        if return_attentions or return_interctc:      # opt-in outputs: the whole batch as ONE row range
             nsub = 1
-            n_long = int(host_lens.max()) if self.ragged else n
-            ts = (self.plan.lengths(n_long)[2] if from_audio else self.plan.lengths_from_mel(n_long)[1])
-            interctc_probs = [torch.zeros(batch, ts[k], self.plan.interctc_vocab, dtype=torch.float32, device=x.device) for k in self.plan.interctc_blocks]
-            _lib.check(lib.effconf_encoder_set_interctc_outputs(self._handle, (C.c_void_p * len(interctc_probs))(*[t.data_ptr() for t in interctc_probs]),
-                                                                len(interctc_probs)), "set_interctc_outputs")
+            extras = self._optional_outputs(batch, int(host_lens.max()) if self.ragged else n, from_audio, x.device, return_attentions, return_interctc)
         ranges = self.row_ranges(batch, nsub, host_lens)
-        pads = None if self.ragged else self._range_pads(ranges, n, from_audio, lens, lens_given, x_len_host, range_pad)
-        fn_ragged = lib.effconf_encoder_forward_ragged
-
-        def launch_ragged(lo: int, hi: int):
-            hp = host_lens[lo:hi]
-            hptr = hp.ctypes.data_as(C.c_void_p)
-            nbytes = lib.effconf_encoder_workspace_bytes_ragged(self._handle, hptr, hi - lo, n, int(from_audio))
-            if nbytes == 0:
-                raise _lib.EffconfError("ragged batch: a length is out of range (audio: n_fft / 2 < len <= row length)")
-            ws = self._workspace(hi - lo, n, from_audio, x.device, nbytes)
-            _lib.check(fn_ragged(self._handle, x[lo:].data_ptr(), lens[lo:].data_ptr(), hptr, hi - lo, n, int(from_audio), out[lo:].data_ptr(), t_out,
-                                 out_len[lo:].data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(x.device).cuda_stream), "encoder_forward_ragged")
-
-        def launch_trimmed(lo: int, hi: int, ni: int):
-            # the rows as their own batch, padded to ni <= n: what the reference computes when these utterances are collated alone
-            xi = (x[lo:hi, :ni] if from_audio else x[lo:hi, :, :ni]).contiguous()
-            ti = lib.effconf_encoder_out_frames(self._handle, ni, int(from_audio))
-            oi = out[lo:hi] if ti == t_out else torch.empty(hi - lo, ti, self.plan.dim_out, dtype=torch.float32, device=x.device)
-            ws = self._workspace(hi - lo, ni, from_audio, x.device)
-            _lib.check(fn(self._handle, xi.data_ptr(), lens[lo:].data_ptr(), hi - lo, ni, oi.data_ptr(), out_len[lo:].data_ptr(),
-                          ws.data_ptr(), ws.numel(), torch.cuda.current_stream(x.device).cuda_stream), "encoder_forward")
-            if ti != t_out:
-                out[lo:hi, :ti] = oi
-                out[lo:hi, ti:] = 0
-
+        pads = None if self.ragged else self._range_pads(ranges, n, from_audio, lens, x_len is not None, x_len_host, range_pad)
         if nsub == 1:
-            try:
-                (launch_ragged if self.ragged else launch)(0, batch)
-            finally:
-                if return_attentions:
-                    _lib.check(lib.effconf_encoder_set_attention_outputs(self._handle, None, 0), "set_attention_outputs")
-                if interctc_probs:
-                    _lib.check(lib.effconf_encoder_set_interctc_outputs(self._handle, None, 0), "set_interctc_outputs")
+            with extras as (attentions, interctc_probs):
+                self._launch_range(x, lens, host_lens, n, from_audio, out, out_len, 0, batch)
             if range_hook is not None:
                 range_hook(0, batch, out, out_len)
         else:
@@ -467,50 +502,10 @@ class ConformerEncoder(nn.Module):
                 mel = torch.empty(batch, self.plan.n_mels, tm, dtype=torch.float32, device=x.device)
                 _lib.check(lib.effconf_mel_frontend(self._handle, x.data_ptr(), batch, n, mel.data_ptr(),
                                                     torch.cuda.current_stream(x.device).cuda_stream), "mel_frontend")
-                x, n, from_audio, fn = mel, tm, False, lib.effconf_encoder_forward_mel
+                x, n, from_audio = mel, tm, False
                 lens = torch.div(lens, self.plan.hop_length, rounding_mode="floor") + 1
-            cur = torch.cuda.current_stream(x.device)
-            streams = []
-            smax = nsub if not self.sub_batch_streams else max(1, min(int(self.sub_batch_streams), nsub))
-            # Stream slot 0 IS the caller's stream; slots 1 .. smax - 1 are side streams that fork from an event recorded before anything of
-            # this forward is enqueued.  (Measured on the MI355X: with more than four HIP streams active in the process the ranges stop
-            # overlapping - three side streams + the caller's idle stream + ONE more (a collective's stream, a consumer's stream) turned a
-            # 5.5 ms step into 7.4 ms, `GPU_MAX_HW_QUEUES` notwithstanding - so the forward itself uses smax streams, not smax + 1, and leaves
-            # room for the process group's own stream.)  The side streams are enqueued first: they run while the host enqueues the rest.
-            fork = torch.cuda.Event()
-            fork.record(cur)
-            order = [i for i in range(nsub) if i % smax != 0] + [i for i in range(nsub) if i % smax == 0]
-            if self.caller_stream_slot is False:
-                order = list(range(nsub))
-            for i in order:
-                slot = i % smax
-                if slot == 0 and self.caller_stream_slot is not False:
-                    st = cur
-                else:
-                    # earlier row ranges get the higher priority (opt-in `stagger_ranges`): range 0 leaves the last stage first
-                    prio = -1 if (i == 0 and self.stagger_ranges) else 0
-                    key = (str(x.device), slot, prio)        # the priority is part of the key: `stagger_ranges` may change after the first forward
-                    if key not in self._sub_streams:
-                        self._sub_streams[key] = torch.cuda.Stream(device=x.device, priority=prio)
-                    st = self._sub_streams[key]
-                    if st not in streams:
-                        st.wait_event(fork)              # inputs (and anything queued before this forward) are ready
-                        streams.append(st)
-                lo, hi = ranges[i]
-                with torch.cuda.stream(st):
-                    if self.ragged:
-                        launch_ragged(lo, hi)
-                    elif pads is None:
-                        launch(lo, hi)
-                    else:
-                        launch_trimmed(lo, hi, pads[i])
-                    if st is not cur:
-                        x.record_stream(st); lens.record_stream(st); out.record_stream(st); out_len.record_stream(st)
-                    if range_hook is not None:
-                        range_hook(lo, hi, out, out_len)     # called with the range's stream current: rows [lo, hi) of `out` are enqueued
-            for st in streams:
-                cur.wait_stream(st)                      # joined: the caller continues on its own stream
-        return out, (out_len if lens_given else None), attentions, interctc_probs
+            self._fan_out(ranges, pads, range_hook, x, lens, host_lens, n, from_audio, out, out_len)
+        return out, (out_len if x_len is not None else None), attentions, interctc_probs
 
     def forward(self, x: torch.Tensor, x_len: Optional[torch.Tensor] = None, range_hook: Optional[Callable] = None,
                 x_len_host=None, range_pad=None, return_attentions: bool = False):

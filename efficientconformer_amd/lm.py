@@ -9,15 +9,12 @@ Training (``forward`` with gradients, the cross-entropy loss) is out of scope.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 from typing import Optional
 
-import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, _targets
+from . import _lib, _native, _targets
 from .config import load_config
 from .transducer import RnnDecoder
 
@@ -26,7 +23,7 @@ from .transducer import RnnDecoder
 WORKSPACE_CAP = 1 << 30
 
 
-class LanguageModel(nn.Module):
+class LanguageModel(_native.NativeModel):
 
     def __init__(self, lm_params: dict, tokenizer_params: Optional[dict] = None, training_params: Optional[dict] = None,
                  decoding_params: Optional[dict] = None, name: Optional[str] = None, tokenizer=None):
@@ -45,7 +42,7 @@ class LanguageModel(nn.Module):
         self._cfg = (vocab, int(lm_params["dim_model"]), int(lm_params["num_layers"]))
         self.tokenizer = tokenizer
         self.name = name
-        self._handle = None
+        self._native = _native.Handle("lm")
         self._packed = False
         self.eval()
 
@@ -55,62 +52,24 @@ class LanguageModel(nn.Module):
         return cls(cfg["lm_params"], cfg.get("tokenizer_params"), cfg.get("training_params"), cfg.get("decoding_params"),
                    cfg.get("model_name"), tokenizer)
 
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        sd = {k.replace(".module.", "."): v for k, v in state_dict.items()}          # model.py:367-370
-        r = super().load_state_dict(sd, strict=strict, **kw)
+    def _invalidate(self):
         self._packed = False
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self._packed = False
-        return r
-
-    def load(self, path):
-        """Reference ``Model.load`` (model.py:361-384): a ``.ckpt`` path or dict; restores weights and the pickled tokenizer."""
-        from .checkpoint import load_checkpoint
-        return load_checkpoint(self, path)
 
     # ------------------------------------------------------------------ native handle
+    @property
+    def _handle(self):
+        """The native LM handle (None before the first pack); ``self._native`` owns it."""
+        return self._native.ptr
+
     def _ensure(self):
         if self._packed:
             return
-        lib = _lib.load()
-        if self._handle is not None:
-            lib.effconf_lm_destroy(self._handle)
-            self._handle = None
-        cfg = _lib.EcLmConfig(*self._cfg)
-        handle = lib.effconf_lm_create(C.byref(cfg))
-        if not handle:
-            raise _lib.EffconfError("effconf_lm_create: %s" % lib.effconf_last_error().decode())
-        self._handle = handle
-        for key, t in self.state_dict().items():
-            arr = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-            _lib.check(lib.effconf_lm_load_tensor(handle, key.encode(), arr.ctypes.data_as(C.c_void_p), shape, arr.ndim), "lm_load_tensor(%s)" % key)
-        _lib.check(lib.effconf_lm_finalize(handle), "lm_finalize")
+        self._native.rebuild(_lib.EcLmConfig(*self._cfg), self.state_dict().items())
         self._packed = True
 
-    def __del__(self):
-        try:
-            if self._handle is not None and _lib._lib is not None:
-                _lib._lib.effconf_lm_destroy(self._handle)
-        except Exception:
-            pass
-
     def _device(self):
-        dev = self.fc.weight.device
-        if dev.type != "cuda":
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
-        return dev
-
-    @staticmethod
-    def _workspace(nbytes: int, device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        fill = os.environ.get("EFFCONF_POISON_WORKSPACE", "")
-        if fill:                    # test hook (include/effconf.h): the byte a fresh workspace is filled with
-            ws.fill_(int(fill))
-        return ws
+        _native.require_hip(self.fc.weight)
+        return self.fc.weight.device
 
     def chunk_size(self) -> int:
         """Sequences per native call: the largest multiple of 64 whose workspace stays under ``WORKSPACE_CAP`` (at least 64)."""
@@ -152,10 +111,7 @@ class LanguageModel(nn.Module):
             lib = _lib.load()
             for lo in range(0, n, step):
                 m = min(step, n - lo)
-                nbytes = int(lib.effconf_lm_workspace_bytes(self._handle, m, u))
-                if nbytes == 0:
-                    raise _lib.EffconfError("effconf_lm_workspace_bytes rejected (n %d, U %d): %s" % (m, u, lib.effconf_last_error().decode()))
-                ws = self._workspace(nbytes, dev)
+                ws = _native.workspace(_native.sized(lib, "effconf_lm", lib.effconf_lm_workspace_bytes(self._handle, m, u), n=m, U=u), dev)
                 _lib.check(lib.effconf_lm_score(self._handle, tg[lo:].data_ptr(), tl[lo:].data_ptr(), m, u, tmp,
                                                 token_logp[lo:].data_ptr() if want_tokens else None, score[lo:].data_ptr(), status[lo:].data_ptr(),
                                                 ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream), "lm_score")
@@ -167,8 +123,7 @@ class LanguageModel(nn.Module):
     def decode(self, x: torch.Tensor, hidden=None):
         """Reference signature (lm.py:55-63): x (N, 1) token ids, hidden = (h, c) of shape (num_layers, N, dim_model) or None (zeros) ->
         (logits (N, 1, V): the raw fc outputs, no temperature; (h', c'))."""
-        if not x.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(x)
         if x.dim() != 2 or x.shape[1] != 1:
             raise _lib.EffconfError("decode takes one token per sequence, x of shape (N, 1); got %s" % (tuple(x.shape),))
         dev = x.device
@@ -188,7 +143,7 @@ class LanguageModel(nn.Module):
         with torch.cuda.device(dev):
             self._ensure()
             lib = _lib.load()
-            ws = self._workspace(int(lib.effconf_lm_workspace_bytes(self._handle, n, 0)), dev)
+            ws = _native.workspace(lib.effconf_lm_workspace_bytes(self._handle, n, 0), dev)
             _lib.check(lib.effconf_lm_step(self._handle, tok.data_ptr(), None if hin is None else hin.data_ptr(), None if cin is None else cin.data_ptr(),
                                            n, logits.data_ptr(), hout.data_ptr(), cout.data_ptr(), ws.data_ptr(), ws.numel(),
                                            torch.cuda.current_stream(dev).cuda_stream), "lm_step")
@@ -199,8 +154,7 @@ class LanguageModel(nn.Module):
         [0, x_0 .. x_{U-1}], through ``decode`` steps.  Rows at or beyond x_len + 1 are fc's bias, as the reference's padded LSTM output (zeros)
         gives them."""
         x, x_len, _ = batch
-        if not x.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(x)
         b, u = x.shape
         xp = torch.nn.functional.pad(x.to(torch.int32), pad=(1, 0, 0, 0), value=0)
         out = torch.empty(b, u + 1, self._cfg[0], dtype=torch.float32, device=x.device)

@@ -15,14 +15,13 @@ algorithm: log P(y | x), -ctc_loss without the host copy) run on the same logits
 """
 from __future__ import annotations
 
-import os
 from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, _targets
+from . import _lib, _native, _targets
 from .config import load_config
 from .encoders import ConformerEncoder, ConformerEncoderInterCTC
 
@@ -88,7 +87,7 @@ def select_nbest(am_score: torch.Tensor, lm_score: torch.Tensor, token_len: torc
     return best.clamp(max=beam - 1), total
 
 
-class ModelCTC(nn.Module):
+class ModelCTC(_native.NativeModel):
     _encoder_cls = ConformerEncoder
 
     def __init__(self, encoder_params: dict, tokenizer_params: dict, training_params: Optional[dict] = None,
@@ -121,24 +120,8 @@ class ModelCTC(nn.Module):
         return cls(cfg["encoder_params"], cfg["tokenizer_params"], cfg.get("training_params"),
                    cfg.get("decoding_params"), cfg.get("model_name", "model"), tokenizer)
 
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        # strip the DDP / DataParallel infix first (model.py:367-370: "encoder.module.preprocessing.*" in a raw DDP state dict),
-        # then drop torchaudio's frontend buffers (the native frontend builds its own window / filterbank tables)
-        sd = {k.replace(".module.", "."): v for k, v in state_dict.items()}
-        sd = {k: v for k, v in sd.items() if not k.startswith("encoder.preprocessing.")}
-        r = super().load_state_dict(sd, strict=strict, **kw)
+    def _invalidate(self):
         self.encoder.repack()
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self.encoder.repack()
-        return r
-
-    def load(self, path):
-        """Reference ``Model.load`` (model.py:361-384): a ``.ckpt`` path or dict; restores weights and the pickled tokenizer."""
-        from .checkpoint import load_checkpoint
-        return load_checkpoint(self, path)
 
     # ---- reference ModelCTC.forward (model_ctc.py:57-68): batch = (x, y, x_len, y_len)
     def forward(self, batch, return_attentions: bool = False):
@@ -147,81 +130,90 @@ class ModelCTC(nn.Module):
         logits, _, _ = self._head(enc, enc_len, want_logits=True)
         return logits, enc_len, attentions
 
-    def _head(self, enc: torch.Tensor, enc_len: Optional[torch.Tensor], want_logits: bool = False):
-        lib = _lib.load()
-        if not enc.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+    # workspace of the greedy head per frame of the (rows, t) rectangle: the i32 argmax the collapse reads and, in the margin instance, the fp32
+    # top-2 margin next to it (the sizes effconf_ctc_greedy / _bf16 / _margin check, csrc/encoder.hip)
+    _GREEDY_WS, _MARGIN_WS = 4, 8
+
+    def _greedy_rows(self, rows: torch.Tensor, as_bf16: bool, lens: torch.Tensor, lo: int, hi: int, labels, label_len, logits=None, margins=None):
+        """The greedy head on utterances [lo, hi) of `rows` (B, T, D) - and of every other tensor given - on the current stream:
+        effconf_ctc_greedy / effconf_ctc_greedy_bf16, or with `margins` = (frame_margin or None, min_margin, min_frame) effconf_ctc_greedy_margin."""
+        lib, b, t = _lib.load(), hi - lo, rows.shape[1]
+        ws = _native.workspace(b * t * (self._GREEDY_WS if margins is None else self._MARGIN_WS), rows.device)
+        stream = torch.cuda.current_stream(rows.device).cuda_stream
+        at = lambda tns: None if tns is None else tns[lo:].data_ptr()
+        if margins is None:
+            fn = lib.effconf_ctc_greedy_bf16 if as_bf16 else lib.effconf_ctc_greedy
+            _lib.check(fn(self.encoder._handle, at(rows), at(lens), b, t, at(labels), at(label_len), at(logits), ws.data_ptr(), ws.numel(), stream),
+                       "ctc_greedy")
+        else:
+            frame_margin, min_margin, min_frame = margins
+            _lib.check(lib.effconf_ctc_greedy_margin(self.encoder._handle, at(rows), int(as_bf16), at(lens), b, t, at(labels), at(label_len), at(logits),
+                                                     at(frame_margin), at(min_margin), at(min_frame), ws.data_ptr(), ws.numel(), stream),
+                       "ctc_greedy_margin")
+
+    def _head_inputs(self, enc: torch.Tensor, enc_len: Optional[torch.Tensor]):
+        """-> (rows, as_bf16, lengths) as the greedy head takes them."""
+        _native.require_hip(enc)
         # bf16 rows (a gathered chunk of the multi-rank path on a bf16 wire) go to the head as they are: effconf_ctc_greedy_bf16 - no widening pass,
         # two MFMAs per 16 k, labels identical to the fp32-input head on the same values
         # (only while the handle's head IS the split-bf16 kernel, option ctc_mfma = 2, the default: with 0 / 1 the fp32 head is a k-ordered fp32 chain and the
         # bf16 rows are widened to it, so gathered and local chunks keep producing the same labels)
         as_bf16 = enc.dtype == torch.bfloat16 and self.encoder.precision == "bf16" and self.encoder._options.get("ctc_mfma", 2) == 2
         enc = enc.contiguous() if as_bf16 else enc.contiguous().float()
+        return enc, as_bf16, _native.lengths(enc_len, enc.shape[0], enc.shape[1], enc.device)
+
+    def _head(self, enc: torch.Tensor, enc_len: Optional[torch.Tensor], want_logits: bool = False):
+        enc, as_bf16, enc_len = self._head_inputs(enc, enc_len)
         b, t, _ = enc.shape
-        if enc_len is None:
-            enc_len = torch.full((b,), t, dtype=torch.int64, device=enc.device)
-        enc_len = enc_len.to(enc.device, torch.int64).contiguous()
         labels = torch.empty(b, t, dtype=torch.int32, device=enc.device)
         label_len = torch.empty(b, dtype=torch.int32, device=enc.device)
         logits = torch.empty(b, t, self.fc.out_features, dtype=torch.float32, device=enc.device) if want_logits else None
-        ws = torch.empty(b * t * 4, dtype=torch.uint8, device=enc.device)
         with torch.cuda.device(enc.device):          # the C library launches on the current device
             self.encoder._ensure_packed()
-            fn = lib.effconf_ctc_greedy_bf16 if as_bf16 else lib.effconf_ctc_greedy
-            _lib.check(fn(self.encoder._handle, enc.data_ptr(), enc_len.data_ptr(), b, t, labels.data_ptr(),
-                          label_len.data_ptr(), logits.data_ptr() if want_logits else None, ws.data_ptr(),
-                          ws.numel(), torch.cuda.current_stream(enc.device).cuda_stream), "ctc_greedy")
+            self._greedy_rows(enc, as_bf16, enc_len, 0, b, labels, label_len, logits)
         return logits, labels, label_len
-
-    def _margin_call(self, rows: torch.Tensor, as_bf16: bool, lens: torch.Tensor, b: int, t: int, labels, label_len, logits, frame_margin, min_margin,
-                     min_frame):
-        """effconf_ctc_greedy_margin on `b` utterances of `t` frames starting at the given tensors' first elements, on the current stream."""
-        ws = torch.empty(b * t * 8, dtype=torch.uint8, device=rows.device)
-        _lib.check(_lib.load().effconf_ctc_greedy_margin(self.encoder._handle, rows.data_ptr(), int(as_bf16), lens.data_ptr(), b, t, labels.data_ptr(),
-                                                         label_len.data_ptr(), None if logits is None else logits.data_ptr(),
-                                                         None if frame_margin is None else frame_margin.data_ptr(), min_margin.data_ptr(),
-                                                         min_frame.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                         torch.cuda.current_stream(rows.device).cuda_stream), "ctc_greedy_margin")
 
     def head_margins(self, enc: torch.Tensor, enc_len: Optional[torch.Tensor], want_logits: bool = False) -> HeadMargins:
         """``_head`` with the top-2 logit margin of every frame and its minimum per utterance (effconf_ctc_greedy_margin): the same head kernel as
         ``_head`` takes for this handle and row type, so labels, label counts and logits are bit-identical to its; frame_margin is the fp32 difference
         of the two largest logits of a frame (0 for a duplicated maximum)."""
-        if not enc.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
-        as_bf16 = enc.dtype == torch.bfloat16 and self.encoder.precision == "bf16" and self.encoder._options.get("ctc_mfma", 2) == 2
-        enc = enc.contiguous() if as_bf16 else enc.contiguous().float()
+        enc, as_bf16, enc_len = self._head_inputs(enc, enc_len)
         b, t, _ = enc.shape
         dev = enc.device
-        if enc_len is None:
-            enc_len = torch.full((b,), t, dtype=torch.int64, device=dev)
-        enc_len = enc_len.to(dev, torch.int64).contiguous()
         out = HeadMargins(torch.empty(b, t, dtype=torch.int32, device=dev), torch.empty(b, dtype=torch.int32, device=dev),
                           torch.empty(b, t, dtype=torch.float32, device=dev), torch.empty(b, dtype=torch.float32, device=dev),
                           torch.empty(b, dtype=torch.int32, device=dev),
                           torch.empty(b, t, self.fc.out_features, dtype=torch.float32, device=dev) if want_logits else None)
         with torch.cuda.device(dev):          # the C library launches on the current device
             self.encoder._ensure_packed()
-            self._margin_call(enc, as_bf16, enc_len, b, t, out.labels, out.label_len, out.logits, out.frame_margin, out.min_margin, out.min_frame)
+            self._greedy_rows(enc, as_bf16, enc_len, 0, b, out.labels, out.label_len, out.logits, (out.frame_margin, out.min_margin, out.min_frame))
         return out
 
-    def _encode_margins(self, x, x_len, from_mel, x_len_host):
-        """Encoder + margin head, the head per row range on that range's stream as in ``encode_greedy`` -> (labels, label_len, min_margin, min_frame)."""
+    def _range_head(self, margins: bool):
+        """-> (range_hook, state) for ``ConformerEncoder.forward``: the hook runs the greedy head on a row range, on that range's stream, into outputs
+        for the whole batch that the first range allocates - state["labels"] (B, T) i32, state["label_len"] (B,) i32 and, with `margins`,
+        state["min_margin"] (B,) f32 / state["min_frame"] (B,) i32."""
         state = {}
 
         def hook(lo, hi, out, out_len):
-            b, t = out.shape[0], out.shape[1]
             if not state:
+                b, t = out.shape[0], out.shape[1]
                 state["labels"] = torch.empty(b, t, dtype=torch.int32, device=out.device)
                 state["label_len"] = torch.empty(b, dtype=torch.int32, device=out.device)
-                state["min_margin"] = torch.empty(b, dtype=torch.float32, device=out.device)
-                state["min_frame"] = torch.empty(b, dtype=torch.int32, device=out.device)
-            self._margin_call(out[lo:], False, out_len[lo:], hi - lo, t, state["labels"][lo:], state["label_len"][lo:], None, None,
-                              state["min_margin"][lo:], state["min_frame"][lo:])
+                if margins:
+                    state["min_margin"] = torch.empty(b, dtype=torch.float32, device=out.device)
+                    state["min_frame"] = torch.empty(b, dtype=torch.int32, device=out.device)
+            self._greedy_rows(out, False, out_len, lo, hi, state["labels"], state["label_len"],
+                              margins=(None, state["min_margin"], state["min_frame"]) if margins else None)
             st = torch.cuda.current_stream(out.device)
             for tns in state.values():
                 tns.record_stream(st)
 
+        return hook, state
+
+    def _encode_margins(self, x, x_len, from_mel, x_len_host):
+        """Encoder + margin head, the head per row range on that range's stream as in ``encode_greedy`` -> (labels, label_len, min_margin, min_frame)."""
+        hook, state = self._range_head(margins=True)
         (self.encoder.forward_mel if from_mel else self.encoder)(x, x_len, range_hook=hook, x_len_host=x_len_host)
         return state["labels"], state["label_len"], state["min_margin"], state["min_frame"]
 
@@ -242,8 +234,7 @@ class ModelCTC(nn.Module):
         `x_len_host` is not given), so it refuses to run while a stream is being captured.  The handle is packed for the split mode once (it serves
         the bf16 path as well); ``precision`` is "bf16" again on return, also after an error."""
         enc = self.encoder
-        if not x.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(x)
         if not enc.ragged:
             raise RuntimeError("greedy_exact needs encoder.ragged = True: only a ragged forward gives an utterance the same labels in every batch")
         if enc.precision != "bf16":
@@ -303,23 +294,7 @@ class ModelCTC(nn.Module):
         fc + argmax + collapse of range i overlaps the other ranges' encoder kernels instead of running after the join
         (reference: model_ctc.py:90-133 runs them one after the other).  Returns (enc, enc_len, labels, label_len); the labels are
         the same as ``_head(enc, enc_len)`` on the joined output - the head is row-local."""
-        lib = _lib.load()
-        state = {}
-
-        def hook(lo, hi, out, out_len):
-            if "labels" not in state:
-                b, t = out.shape[0], out.shape[1]
-                state["labels"] = torch.empty(b, t, dtype=torch.int32, device=out.device)
-                state["label_len"] = torch.empty(b, dtype=torch.int32, device=out.device)
-            t = out.shape[1]
-            st = torch.cuda.current_stream(out.device)
-            ws = torch.empty((hi - lo) * t * 4, dtype=torch.uint8, device=out.device)
-            _lib.check(lib.effconf_ctc_greedy(self.encoder._handle, out[lo:].data_ptr(), out_len[lo:].data_ptr(), hi - lo, t,
-                                              state["labels"][lo:].data_ptr(), state["label_len"][lo:].data_ptr(), None, ws.data_ptr(),
-                                              ws.numel(), st.cuda_stream), "ctc_greedy")
-            for tns in (state["labels"], state["label_len"]):
-                tns.record_stream(st)
-
+        hook, state = self._range_head(margins=False)
         with torch.cuda.device(x.device):
             enc, enc_len = (self.encoder.forward_mel if from_mel else self.encoder)(x, x_len, range_hook=hook, **encoder_kwargs)[:2]
         return enc, enc_len, state["labels"], state["label_len"]
@@ -365,22 +340,16 @@ class ModelCTC(nn.Module):
             raise _lib.EffconfError("logits must be (batch, frames, vocab); got shape %s" % (tuple(logits.shape),))
         b, t, v = logits.shape
         self._check_beam(beam, v)
-        if not logits.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(logits)
         lib = _lib.load()
-        nbytes = int(lib.effconf_ctc_beam_workspace_bytes(b, t, v, beam))
-        if nbytes == 0:
-            raise _lib.EffconfError("effconf_ctc_beam_workspace_bytes rejected (batch %d, T %d, vocab %d, beam %d): %s"
-                                    % (b, t, v, beam, lib.effconf_last_error().decode()))
+        nbytes = _native.sized(lib, "effconf_ctc_beam", lib.effconf_ctc_beam_workspace_bytes(b, t, v, beam), batch=b, T=t, vocab=v, beam=beam)
         with torch.cuda.device(logits.device):
             logits = logits.contiguous().float()
-            if logits_len is None:
-                logits_len = torch.full((b,), t, dtype=torch.int64, device=logits.device)
-            logits_len = logits_len.to(device=logits.device, dtype=torch.int64).contiguous()
+            logits_len = _native.lengths(logits_len, b, t, logits.device)
             tokens = torch.empty(b, beam, t, dtype=torch.int32, device=logits.device)
             token_len = torch.empty(b, beam, dtype=torch.int32, device=logits.device)
             score = torch.empty(b, beam, dtype=torch.float32, device=logits.device)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=logits.device)
+            ws = _native.workspace(nbytes, logits.device)
             _lib.check(lib.effconf_ctc_beam(logits.data_ptr(), logits_len.data_ptr(), b, t, v, beam, float(self.tmp), tokens.data_ptr(),
                                             token_len.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
                                             torch.cuda.current_stream(logits.device).cuda_stream), "ctc_beam")
@@ -422,8 +391,7 @@ class ModelCTC(nn.Module):
         """Best CTC beam-search label-id sequence per utterance: encoder, head logits (``_head(want_logits=True)``), effconf_ctc_beam."""
         beam = int(self.beam_size if beam_size is None else beam_size)
         self._check_beam(beam, self.fc.out_features)
-        if not x.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(x)
         enc, enc_len = (self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len))[:2]      # [:2]: the InterCTC encoder returns four values
         logits, _, _ = self._head(enc, enc_len, want_logits=True)
         tokens, token_len, _ = self.decode_logits_beam(logits, enc_len, beam)
@@ -507,8 +475,7 @@ class ModelCTC(nn.Module):
             raise _lib.EffconfError("vocab_size must be in 2 .. 1024 for the CTC alignment; got %d" % v)
         if not 0 < self.tmp < float("inf"):
             raise _lib.EffconfError("decoding_params['tmp'] must be > 0; got %r" % (self.tmp,))
-        if not logits.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(logits)
         dev = logits.device
         tg, tl = self._targets(targets, target_len, dev)
         if tg.shape[0] != b or tl.shape[0] != b:
@@ -517,15 +484,10 @@ class ModelCTC(nn.Module):
         if u > 2047:
             raise _lib.EffconfError("at most 2047 target tokens per utterance; got %d" % u)
         lib = _lib.load()
-        nbytes = int(lib.effconf_ctc_align_workspace_bytes(b, t, v, u))
-        if nbytes == 0:
-            raise _lib.EffconfError("effconf_ctc_align_workspace_bytes rejected (batch %d, T %d, vocab %d, U %d): %s"
-                                    % (b, t, v, u, lib.effconf_last_error().decode()))
+        nbytes = _native.sized(lib, "effconf_ctc_align", lib.effconf_ctc_align_workspace_bytes(b, t, v, u), batch=b, T=t, vocab=v, U=u)
         with torch.cuda.device(dev):
             logits = logits.contiguous().float()
-            if logits_len is None:
-                logits_len = torch.full((b,), t, dtype=torch.int64, device=dev)
-            logits_len = logits_len.to(device=dev, dtype=torch.int64).contiguous()
+            logits_len = _native.lengths(logits_len, b, t, dev)
             out = {"log_likelihood": torch.empty(b, dtype=torch.float32, device=dev), "status": torch.empty(b, dtype=torch.int32, device=dev)}
             if not scores_only:
                 out["score"] = torch.empty(b, dtype=torch.float32, device=dev)
@@ -533,10 +495,7 @@ class ModelCTC(nn.Module):
                 out["token_start"] = torch.empty(b, u, dtype=torch.int32, device=dev)
                 out["token_end"] = torch.empty(b, u, dtype=torch.int32, device=dev)
                 out["token_logp"] = torch.empty(b, u, dtype=torch.float32, device=dev)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            fill = os.environ.get("EFFCONF_POISON_WORKSPACE", "")
-            if fill:                # test hook (include/effconf.h): the byte a fresh workspace is filled with
-                ws.fill_(int(fill))
+            ws = _native.workspace(nbytes, dev)
             ptr = lambda k: out[k].data_ptr() if k in out else None
             _lib.check(lib.effconf_ctc_align(logits.data_ptr(), logits_len.data_ptr(), b, t, v, tg.data_ptr(), tl.data_ptr(), u, float(self.tmp),
                                              ptr("log_likelihood"), ptr("score"), ptr("status"), ptr("frame_token"), ptr("token_start"),
@@ -545,8 +504,7 @@ class ModelCTC(nn.Module):
         return out
 
     def _logits(self, x, x_len, from_mel):
-        if not x.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(x)
         enc, enc_len = (self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len))[:2]      # [:2]: the InterCTC encoder returns four values
         return self._head(enc, enc_len, want_logits=True) + (enc_len,)
 

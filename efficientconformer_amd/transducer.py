@@ -14,15 +14,13 @@ and ``align`` the frame at which each token is emitted (csrc/rnnt_align.hip: for
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
 from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, _targets
+from . import _lib, _native, _targets
 from .config import load_config
 from .encoders import ConformerEncoder
 
@@ -70,7 +68,7 @@ class JointNetwork(nn.Module):
         self.joint_mode, self.act_name = params["joint_mode"], params["act"]
 
 
-class Transducer(nn.Module):
+class Transducer(_native.NativeModel):
 
     def __init__(self, encoder_params: dict, decoder_params: dict, joint_params: dict, tokenizer_params: Optional[dict] = None,
                  training_params: Optional[dict] = None, decoding_params: Optional[dict] = None, name: str = "model",
@@ -92,7 +90,7 @@ class Transducer(nn.Module):
                      decoder_params["vocab_size"], decoder_params["num_layers"])
         self.tokenizer = tokenizer
         self.name = name
-        self._rnnt = None
+        self._native = _native.Handle("rnnt")
         self._rnnt_packed = False
         self._beam_ws = None
         self.eval()
@@ -103,26 +101,9 @@ class Transducer(nn.Module):
         return cls(cfg["encoder_params"], cfg["decoder_params"], cfg["joint_params"], cfg.get("tokenizer_params"),
                    cfg.get("training_params"), cfg.get("decoding_params"), cfg.get("model_name", "model"), tokenizer)
 
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        # strip the DDP / DataParallel infix first (model.py:367-370: "encoder.module.preprocessing.*" in a raw DDP state dict),
-        # then drop torchaudio's frontend buffers (the native frontend builds its own window / filterbank tables)
-        sd = {k.replace(".module.", "."): v for k, v in state_dict.items()}
-        sd = {k: v for k, v in sd.items() if not k.startswith("encoder.preprocessing.")}
-        r = super().load_state_dict(sd, strict=strict, **kw)
+    def _invalidate(self):
         self.encoder.repack()
         self._rnnt_packed = False
-        return r
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        self.encoder.repack()
-        self._rnnt_packed = False
-        return r
-
-    def load(self, path):
-        """Reference ``Model.load`` (model.py:361-384): a ``.ckpt`` path or dict; restores weights and the pickled tokenizer."""
-        from .checkpoint import load_checkpoint
-        return load_checkpoint(self, path)
 
     def forward(self, batch):
         raise NotImplementedError("Transducer.forward returns the (B, T, U+1, V) training logits (transducer.py:88-107): training is out of "
@@ -130,35 +111,20 @@ class Transducer(nn.Module):
                                   "transcript, score_labels() its log-likelihood, align() its token frames")
 
     # ------------------------------------------------------------------ native handle
+    @property
+    def _rnnt(self):
+        """The native decoder handle (None before the first pack); ``self._native`` owns it."""
+        return self._native.ptr
+
     def _ensure_rnnt(self):
         if self._rnnt_packed:
             return
-        lib = _lib.load()
-        if self._rnnt is not None:
-            lib.effconf_rnnt_destroy(self._rnnt)
-            self._rnnt = None
         de, h, j, v, layers = self._cfg
         cfg = _lib.EcRnntConfig(de, h, j, v, layers, int(self.max_consec_dec_step), _JOINT_MODES[self.joint_network.joint_mode],
                                 _JOINT_ACTS[self.joint_network.act_name])
-        handle = lib.effconf_rnnt_create(C.byref(cfg))
-        if not handle:
-            raise _lib.EffconfError("effconf_rnnt_create: %s" % lib.effconf_last_error().decode())
-        self._rnnt = handle
-        for prefix, mod in (("decoder.", self.decoder), ("joint_network.", self.joint_network)):
-            for key, t in mod.state_dict().items():
-                arr = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-                shape = (C.c_int64 * max(arr.ndim, 1))(*arr.shape)
-                _lib.check(lib.effconf_rnnt_load_tensor(handle, (prefix + key).encode(), arr.ctypes.data_as(C.c_void_p), shape,
-                                                        arr.ndim), "rnnt_load_tensor(%s)" % key)
-        _lib.check(lib.effconf_rnnt_finalize(handle), "rnnt_finalize")
+        self._native.rebuild(cfg, [(prefix + key, t) for prefix, mod in (("decoder.", self.decoder), ("joint_network.", self.joint_network))
+                                   for key, t in mod.state_dict().items()])
         self._rnnt_packed = True
-
-    def __del__(self):
-        try:
-            if self._rnnt is not None and _lib._lib is not None:
-                _lib._lib.effconf_rnnt_destroy(self._rnnt)
-        except Exception:
-            pass
 
     def set_decode_option(self, name: str, value: int):
         """Forward an option to the native decoder (effconf_rnnt_set_option), e.g. ``cluster_decode`` = -1 auto / 0 / 1."""
@@ -168,8 +134,7 @@ class Transducer(nn.Module):
     # ------------------------------------------------------------------ decoding
     def decode_encoded(self, f: torch.Tensor, f_len: Optional[torch.Tensor]):
         """Greedy RNN-T decode of encoder outputs f (B, T, Denc) fp32 on the GPU -> (tokens (B, max_tok) i32, token_len (B) i32)."""
-        if not f.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(f)
         with torch.cuda.device(f.device):             # the C library allocates / launches on the current device
             return self._decode_encoded(f, f_len)
 
@@ -178,13 +143,11 @@ class Transducer(nn.Module):
         lib = _lib.load()
         f = f.contiguous().float()
         b, t, _ = f.shape
-        if f_len is None:
-            f_len = torch.full((b,), t, dtype=torch.int64, device=f.device)
-        f_len = f_len.to(device=f.device, dtype=torch.int64).contiguous()
+        f_len = _native.lengths(f_len, b, t, f.device)
         max_tok = int(lib.effconf_rnnt_max_tokens(self._rnnt, t))
         tokens = torch.empty(b, max_tok, dtype=torch.int32, device=f.device)
         token_len = torch.empty(b, dtype=torch.int32, device=f.device)
-        ws = torch.empty(int(lib.effconf_rnnt_workspace_bytes(self._rnnt, b, t)), dtype=torch.uint8, device=f.device)
+        ws = _native.workspace(lib.effconf_rnnt_workspace_bytes(self._rnnt, b, t), f.device)
         _lib.check(lib.effconf_rnnt_greedy(self._rnnt, f.data_ptr(), f_len.data_ptr(), b, t, tokens.data_ptr(), token_len.data_ptr(),
                                            max_tok, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(f.device).cuda_stream),
                    "rnnt_greedy")
@@ -211,8 +174,7 @@ class Transducer(nn.Module):
         """Beam search of encoder outputs f (B, T, Denc) fp32 on the GPU (effconf_rnnt_beam) -> (tokens (B, max_tokens) i32,
         token_len (B) i32, score (B) f32, status (B) i32).  status 1 / 2: the utterance hit the expansion / token cap and has no tokens.
         Defaults: beam_size = self.beam_size, max_expansions_per_frame = 16 * beam, max_tokens = max(16, beam) * T."""
-        if not f.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(f)
         with torch.cuda.device(f.device):
             return self._decode_encoded_beam(f, f_len, beam_size, max_expansions_per_frame, max_tokens)
 
@@ -227,20 +189,16 @@ class Transducer(nn.Module):
         lib = _lib.load()
         f = f.contiguous().float()
         b, t, _ = f.shape
-        if f_len is None:
-            f_len = torch.full((b,), t, dtype=torch.int64, device=f.device)
-        f_len = f_len.to(device=f.device, dtype=torch.int64).contiguous()
+        f_len = _native.lengths(f_len, b, t, f.device)
         max_exp = int(16 * beam if max_expansions_per_frame is None else max_expansions_per_frame)
         max_tok = int(max(16, beam) * max(t, 1) if max_tokens is None else max_tokens)
-        nbytes = int(lib.effconf_rnnt_beam_workspace_bytes(self._rnnt, b, t, beam, max_exp, max_tok))
-        if nbytes == 0:
-            raise _lib.EffconfError("effconf_rnnt_beam_workspace_bytes rejected (batch %d, T %d, beam %d, max_expansions %d, max_tokens %d): %s"
-                                    % (b, t, beam, max_exp, max_tok, lib.effconf_last_error().decode()))
+        nbytes = _native.sized(lib, "effconf_rnnt_beam", lib.effconf_rnnt_beam_workspace_bytes(self._rnnt, b, t, beam, max_exp, max_tok),
+                               batch=b, T=t, beam=beam, max_expansions=max_exp, max_tokens=max_tok)
         tokens = torch.empty(b, max_tok, dtype=torch.int32, device=f.device)
         token_len = torch.empty(b, dtype=torch.int32, device=f.device)
         score = torch.empty(b, dtype=torch.float32, device=f.device)
         status = torch.empty(b, dtype=torch.int32, device=f.device)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+        ws = _native.workspace(nbytes, f.device)
         _lib.check(lib.effconf_rnnt_beam(self._rnnt, f.data_ptr(), f_len.data_ptr(), b, t, beam, float(self.tmp), max_exp, tokens.data_ptr(),
                                          token_len.data_ptr(), score.data_ptr(), status.data_ptr(), max_tok, ws.data_ptr(), ws.numel(),
                                          torch.cuda.current_stream(f.device).cuda_stream), "rnnt_beam")
@@ -288,14 +246,6 @@ class Transducer(nn.Module):
         strings (needs a tokenizer).  A list is padded on the host and copied once."""
         return _targets.targets(self.tokenizer, y, y_len, device)
 
-    @staticmethod
-    def _workspace(nbytes: int, device):
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        fill = os.environ.get("EFFCONF_POISON_WORKSPACE", "")
-        if fill:                    # test hook (include/effconf.h): the byte a fresh workspace is filled with
-            ws.fill_(int(fill))
-        return ws
-
     def lattice(self, f: torch.Tensor, f_len: Optional[torch.Tensor], y, y_len=None):
         """The RNN-T lattice of encoder outputs f (B, T, Denc) fp32 and transcripts `y` ((B, U) integers + `y_len`, or a list of id lists) on
         the GPU (effconf_rnnt_lattice), temperature ``self.tmp`` -> (lp_blank, lp_label (B, T, U + 1) f32, status (B,) i32).  For t < f_len[b],
@@ -303,8 +253,7 @@ class Transducer(nn.Module):
         are the entries of log_softmax(joint logits) the RNN-T loss reads.  include/effconf.h has the details."""
         if f.dim() != 3:
             raise _lib.EffconfError("encoder outputs must be (batch, frames, dim); got shape %s" % (tuple(f.shape),))
-        if not f.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(f)
         if not 0 < self.tmp < float("inf"):
             raise _lib.EffconfError("decoding_params['tmp'] must be > 0; got %r" % (self.tmp,))
         dev = f.device
@@ -316,18 +265,13 @@ class Transducer(nn.Module):
         with torch.cuda.device(dev):
             self._ensure_rnnt()
             lib = _lib.load()
-            nbytes = int(lib.effconf_rnnt_lattice_workspace_bytes(self._rnnt, b, t, u))
-            if nbytes == 0:
-                raise _lib.EffconfError("effconf_rnnt_lattice_workspace_bytes rejected (batch %d, T %d, U %d): %s"
-                                        % (b, t, u, lib.effconf_last_error().decode()))
+            nbytes = _native.sized(lib, "effconf_rnnt_lattice", lib.effconf_rnnt_lattice_workspace_bytes(self._rnnt, b, t, u), batch=b, T=t, U=u)
             f = f.contiguous().float()
-            if f_len is None:
-                f_len = torch.full((b,), t, dtype=torch.int64, device=dev)
-            f_len = f_len.to(device=dev, dtype=torch.int64).contiguous()
+            f_len = _native.lengths(f_len, b, t, dev)
             lp_blank = torch.empty(b, t, u + 1, dtype=torch.float32, device=dev)
             lp_label = torch.empty(b, t, u + 1, dtype=torch.float32, device=dev)
             status = torch.empty(b, dtype=torch.int32, device=dev)
-            ws = self._workspace(nbytes, dev)
+            ws = _native.workspace(nbytes, dev)
             _lib.check(lib.effconf_rnnt_lattice(self._rnnt, f.data_ptr(), f_len.data_ptr(), b, t, tg.data_ptr(), tl.data_ptr(), u, float(self.tmp),
                                                 lp_blank.data_ptr(), lp_label.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
                                                 torch.cuda.current_stream(dev).cuda_stream), "rnnt_lattice")
@@ -347,17 +291,11 @@ class Transducer(nn.Module):
         u = e - 1
         dev = lp_blank.device
         lib = _lib.load()
-        nbytes = int(lib.effconf_rnnt_align_workspace_bytes(b, t, u))
-        if nbytes == 0:
-            raise _lib.EffconfError("effconf_rnnt_align_workspace_bytes rejected (batch %d, T %d, U %d): %s"
-                                    % (b, t, u, lib.effconf_last_error().decode()))
-        if not lp_blank.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        nbytes = _native.sized(lib, "effconf_rnnt_align", lib.effconf_rnnt_align_workspace_bytes(b, t, u), batch=b, T=t, U=u)
+        _native.require_hip(lp_blank)
         with torch.cuda.device(dev):
             lp_blank, lp_label = lp_blank.contiguous().float(), lp_label.contiguous().float()
-            if f_len is None:
-                f_len = torch.full((b,), t, dtype=torch.int64, device=dev)
-            f_len = torch.as_tensor(f_len).to(device=dev, dtype=torch.int64).contiguous()
+            f_len = _native.lengths(f_len, b, t, dev)
             y_len = torch.as_tensor(y_len).to(device=dev, dtype=torch.int64).contiguous()
             if f_len.shape[0] != b or y_len.shape[0] != b:
                 raise _lib.EffconfError("lengths: %d / %d entries for %d utterances" % (f_len.shape[0], y_len.shape[0], b))
@@ -367,7 +305,7 @@ class Transducer(nn.Module):
                 out["score"] = torch.empty(b, dtype=torch.float32, device=dev)
                 out["token_frame"] = torch.empty(b, u, dtype=torch.int32, device=dev)
                 out["token_logp"] = torch.empty(b, u, dtype=torch.float32, device=dev)
-            ws = self._workspace(nbytes, dev)
+            ws = _native.workspace(nbytes, dev)
             ptr = lambda k: out[k].data_ptr() if k in out else None
             _lib.check(lib.effconf_rnnt_align(lp_blank.data_ptr(), lp_label.data_ptr(), f_len.data_ptr(), y_len.data_ptr(), b, t, u,
                                               ptr("log_likelihood"), ptr("score"), ptr("token_frame"), ptr("token_logp"), ptr("status"),
@@ -375,8 +313,7 @@ class Transducer(nn.Module):
         return out
 
     def _encode(self, x, x_len, from_mel):
-        if not x.is_cuda:
-            raise RuntimeError("efficientconformer_amd runs on a HIP device only (no CPU fallback)")
+        _native.require_hip(x)
         f, f_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
         return f, f_len
 

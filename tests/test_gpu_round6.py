@@ -287,7 +287,7 @@ def test_split_chains_vs_per_module_kernels_and_the_oracle(name, tm, lens, ragge
                                           ("ConformerCTCSmall", 260, [260, 180, 33])])
 def test_forward_on_a_poisoned_fresh_workspace_is_bit_identical(monkeypatch, name, tm, lens, precision, chain):
     """The caller owns the workspace and may hand over ANY bytes (a recycled allocation of another dtype holds NaN / Inf patterns with probability ~1/32 per
-    half word).  EFFCONF_POISON_WORKSPACE (encoders.py `_workspace`) fills every fresh workspace with a byte: 255 = NaN patterns in fp32 / bf16 / fp16.  A kernel
+    half word).  EFFCONF_POISON_WORKSPACE (_native.py `workspace`) fills every fresh workspace with a byte: 255 = NaN patterns in fp32 / bf16 / fp16.  A kernel
     that reads a byte nobody wrote - and scales it by a zero weight or a zero mask instead of selecting - turns that into a NaN in a VALID output: found on the
     split GEMM's A-tile tail at K < 32 (the last row read the bytes behind the buffer and multiplied them by 0), fixed by a select.  Every mode, rectangular and
     ragged, the traced (per-module) forward too: output bit-identical to the forward on a zero-filled workspace, and finite."""
