@@ -59,6 +59,13 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Inclusive prefix sum over the 64 lanes of a wave (__shfl_up ladder); lane = threadIdx.x & 63
+__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o); if (lane >= o) v += t; }
+    return v;
+}
+
 struct FastDiv32 {   // n / d by one multiply-high; exact for n * d < 2^32
     uint32_t mul, d;
     __host__ __device__ FastDiv32() : mul(0), d(1) {}

@@ -36,12 +36,6 @@ __global__ void lengths_kernel(const int64_t* __restrict__ x_len, int B, int fro
 // waves (four until round 4: the 48 scans of a 15-block encoder ran twelve deep per wave, 20 us at the head of every range's stream; three
 // deep now): thread b computes utterance b's lengths; then every (position, array) pair is one wave-parallel exclusive scan (64 utterances per
 // step, __shfl_up ladder) - a serial scan per thread cost ~0.1 ms of dependent global accesses at the head of every forward.
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o); if (lane >= o) v += t; }
-    return v;
-}
-
 __global__ __launch_bounds__(1024) void lengths_ragged_kernel(const int64_t* __restrict__ x_len, int B, int from_audio, int hop, int sub_layers,
                                                              const int* __restrict__ block_stride, const int* __restrict__ group,
                                                              const int* __restrict__ heads, int n_blocks, int* stage_lens, int* mel_len,

@@ -30,48 +30,21 @@
 //     most), otherwise in the workspace; the backtrace (one thread) then walks len dependent loads from LDS or, for long utterances,
 //     from memory.  A parallel epilogue turns the path into frame_token, the token spans and the per-token sums.
 //   VIT = false (all four alignment outputs NULL): the forward half alone, no v, no backpointers; log_likelihood is bit-identical.
-#include "kernels.h"
-#include "common.h"
-#include "../../include/effconf.h"
+#include "decode_common.h"
 
 #include <cmath>
 
 int ec_fail(const char* msg);
 
+using namespace ecrnnt;
+using namespace ecdec;
+
 namespace {
 
-constexpr int AT = 256;                           // threads per utterance
+constexpr int AT = CTC_ALIGN_THREADS;             // threads per utterance
 constexpr int MAXV = 1024;                        // largest vocabulary
 constexpr int MAXU = 2047;                        // largest target: S <= 4095 <= 16 states per thread
 constexpr int LDS_MAX = 128 * 1024;               // LDS per workgroup at the most (160 KiB per CU)
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int spt_of(int u_max) {                           // the launch's states per thread: 1, 2, 4, 8 or 16
-    const int s = 2 * u_max + 1;
-    int spt = 1;
-    while (AT * spt < s) spt <<= 1;
-    return spt;
-}
-
-struct CtcAlignLayout {
-    int E, spt, rbmax;                            // emission row stride, states per thread at the most, backpointer bytes per frame at the most
-    size_t emit, path, bp, bp_utt, total;
-};
-
-CtcAlignLayout ctc_align_layout(int batch, int t_out, int u_max) {
-    CtcAlignLayout L{};
-    L.E = u_max + 1;
-    L.spt = spt_of(u_max);
-    L.rbmax = AT * ((L.spt + 3) / 4);
-    size_t o = 0;
-    L.emit = o; o = al256(o + (size_t)batch * t_out * L.E * 4);
-    L.path = o; o = al256(o + (size_t)batch * t_out * 4);
-    L.bp_utt = al256((size_t)t_out * L.rbmax);
-    L.bp = o; o += (size_t)batch * L.bp_utt;
-    L.total = o + 256;                            // + 256: the caller's pointer is aligned up
-    return L;
-}
 
 const char* ctc_align_check(int32_t batch, int32_t t_out, int32_t vocab, int32_t u_max) {
     if (vocab < 2 || vocab > MAXV) return "ctc align: vocab must be in 2 .. 1024";
@@ -89,8 +62,6 @@ struct CtcAlignArgs {
     float* ll; float* score; int* status;
     int* frame_token; int* token_start; int* token_end; float* token_logp;
 };
-
-__device__ __forceinline__ int clamp_len(long long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
 
 // ---------------------------------------------------------------------------------------------------------------- emissions
 __global__ __launch_bounds__(AT) void ctc_emit_kernel(const CtcAlignArgs a, const int rows) {
@@ -141,6 +112,8 @@ __global__ __launch_bounds__(AT) void ctc_emit_kernel(const CtcAlignArgs a, cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------- trellis
+// three-way logaddexp in the logf form of the CTC loss this kernel follows (rnnt_align.hip's lse2 is its two-way sibling); ctc_beam.hip's lse is the log1pf
+// form of the prefix beam search: different formulas on purpose
 __device__ __forceinline__ float lse3(float p, float q, float r) {
     const float m = fmaxf(fmaxf(p, q), r);
     const float ms = m == -INFINITY ? 0.f : m;
@@ -177,7 +150,7 @@ __global__ __launch_bounds__(AT) void ctc_trellis_kernel(const CtcAlignArgs a) {
         int bad = 0, rep = 0;
         for (int u = tid; u < U; u += AT) {
             const int c = y[u];
-            bad |= (c < 1 || c >= a.V);
+            bad |= token_refused(c, a.V);
             rep += (u > 0 && c == y[u - 1]);
         }
         if (bad) atomicOr(&s_bad, 1);
@@ -337,7 +310,7 @@ int effconf_ctc_align(const float* logits, const int64_t* out_len, int32_t batch
         return ec_fail("null argument");
     const CtcAlignLayout L = ctc_align_layout(batch, t_out, u_max);
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_ctc_align_workspace_bytes)");
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
     const bool vit = frame_token || token_start || token_end || token_logp;
     if (vit && !score) return ec_fail("null argument");
     CtcAlignArgs a{};

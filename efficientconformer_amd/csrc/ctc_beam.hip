@@ -17,12 +17,13 @@
 //   * Prefix identity is string identity: an append-only trie of (parent node, token) in the workspace with a (parent, token) -> node hash
 //     index, so a prefix that leaves the beam and comes back gets its old node, and "P c is a member" is a compare of (parent, token).
 // All arithmetic of an utterance is in a fixed order, so its results do not depend on the batch, the T padding or the run.
-#include "kernels.h"
-#include "../../include/effconf.h"
+#include "decode_common.h"
 
 #include <cmath>
 
 int ec_fail(const char* msg);
+
+using namespace ecdec;
 
 namespace {
 
@@ -34,30 +35,6 @@ constexpr int TPT = MAXV / CT;                    // tokens per thread (contiguo
 constexpr int MAXK = 2 * MAXB + 1;                // top tokens per frame
 constexpr int MAXS = 2 * MAXB + MAXB * MAXB;      // candidate slots: members, repeat extensions, plain extensions
 constexpr unsigned long long HEMPTY = ~0ull;
-
-struct CtcBeamLayout {
-    int ncap, hcap;                               // trie nodes, hash slots per utterance
-    size_t utt, per_utt, trace, nodes, hkeys, hvals, total;
-};
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-CtcBeamLayout ctc_beam_layout(int batch, int t_out, int beam) {
-    CtcBeamLayout L{};
-    L.ncap = 1 + beam * t_out;                    // the empty prefix + at most `beam` new prefixes per frame
-    int h = 1;
-    while (h < 2 * L.ncap) h <<= 1;
-    L.hcap = h;
-    L.utt = al256((size_t)batch * 16);
-    size_t o = 0;
-    L.trace = o; o = al256(o + (size_t)t_out * beam * 16);
-    L.nodes = o; o = al256(o + (size_t)L.ncap * 16);
-    L.hkeys = o; o = al256(o + (size_t)h * 8);
-    L.hvals = o; o = al256(o + (size_t)h * 4);
-    L.per_utt = o;
-    L.total = L.utt + (size_t)batch * o + 256;    // + 256: the caller's pointer is aligned up
-    return L;
-}
 
 const char* ctc_beam_check(int32_t batch, int32_t t_out, int32_t vocab, int32_t beam) {
     if (beam < 1 || beam > MAXB) return "ctc beam search: beam must be in 1 .. 32";
@@ -74,6 +51,8 @@ struct CtcBeamArgs {
     int* tokens; int* token_len; float* score;
 };
 
+// logaddexp in the log1pf form of the prefix beam search this kernel follows; rnnt_align.hip's lse2 and ctc_align.hip's lse3 are the logf form of the losses
+// they follow: different formulas on purpose
 __device__ __forceinline__ float lse(float a, float b) {
     const float m = fmaxf(a, b);
     if (m == -INFINITY) return -INFINITY;
@@ -89,12 +68,6 @@ __device__ __forceinline__ unsigned okey(float f) {
 // candidate order as one integer, larger = earlier: score desc (-0 counts as +0), then ck asc; 0 = empty slot
 __device__ __forceinline__ unsigned long long cand_key(float s, int ck) {
     return ((unsigned long long)okey(s == 0.f ? 0.f : s) << 32) | (unsigned)(0x7fffffff - ck);
-}
-
-__device__ __forceinline__ int wave_scan_incl(int v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o); if (lane >= o) v += t; }
-    return v;
 }
 
 __device__ __forceinline__ unsigned hash_slot(int par, int c, unsigned mask) {
@@ -226,7 +199,7 @@ __global__ __launch_bounds__(CT) void ctc_beam_kernel(const CtcBeamArgs a) {
                 unsigned hv[4], c = 0u;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { hv[j] = h[255 - 4 * lane - j]; c += hv[j]; }
-                const int incl = wave_scan_incl((int)c, lane), excl = incl - (int)c;
+                const int incl = wave_incl_scan((int)c, lane), excl = incl - (int)c;
                 if (excl < need && incl >= need) {
                     int cum = excl, j = 0;
                     while (cum + (int)hv[j] < need) { cum += (int)hv[j]; ++j; }
@@ -243,7 +216,7 @@ __global__ __launch_bounds__(CT) void ctc_beam_kernel(const CtcBeamArgs a) {
         int nt = 0;
 #pragma unroll
         for (int q = 0; q < TPT; ++q) nt += (tid * TPT + q < V && key[q] == prefix);
-        const int incl = wave_scan_incl(nt, lane);
+        const int incl = wave_incl_scan(nt, lane);
         if (lane == 63) sscan[wave] = incl;
         __syncthreads();
         int toff = incl - nt;
@@ -431,10 +404,10 @@ int effconf_ctc_beam(const float* logits, const int64_t* out_len, int32_t batch,
     if (!out_len || !token_len || !score || !workspace || (t_out > 0 && (!logits || !tokens))) return ec_fail("null argument");
     const CtcBeamLayout L = ctc_beam_layout(batch, t_out, beam);
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_ctc_beam_workspace_bytes)");
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
     CtcBeamArgs a{};
     a.logits = logits; a.lens = out_len; a.T = t_out; a.V = vocab; a.beam = beam; a.tmp = temperature;
-    a.utt = ws + L.utt; a.stats = reinterpret_cast<int*>(ws); a.L = L;
+    a.utt = ws + L.utt; a.stats = reinterpret_cast<int*>(ws + L.stats); a.L = L;
     a.tokens = tokens; a.token_len = token_len; a.score = score;
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(batch), dim3(CT), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : ec_fail("ctc_beam launch failed");

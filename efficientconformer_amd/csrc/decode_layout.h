@@ -1,0 +1,183 @@
+// Workspace layouts of the seven decoder files (rnnt.hip, rnnt_beam.hip, rnnt_lattice.hip, rnnt_align.hip, lm.hip, ctc_beam.hip, ctc_align.hip), written on
+// one plan type.  Plain C++ without a HIP call: every `effconf_*_workspace_bytes` and every entry point's carve read the same function, and
+// tools/decoder_layout_sanitize.cpp compiles this header for the host alone.
+//
+// The rule, once: a region starts at a multiple of 256 bytes from the base; the base is the caller's pointer aligned up to 256 bytes (once); the size an entry
+// reports is the end of the last region plus ONE 256-byte slack, which that alignment can spend at the most.
+#pragma once
+#include "../../include/effconf.h"
+
+#include <cstddef>
+#include <cstdint>
+
+namespace ecdec {
+
+struct WsPlan {
+    size_t end = 0;
+    static size_t up(size_t x) { return (x + 255) & ~(size_t)255; }
+    size_t take(size_t bytes) { const size_t off = up(end); end = off + bytes; return off; }
+    size_t stride() const { return up(end); }                        // a sub-plan (one utterance's regions) as the element of an array
+    size_t total() const { return end + 256; }
+    static char* base(void* p) { return reinterpret_cast<char*>(up(reinterpret_cast<uintptr_t>(p))); }
+};
+
+// ---------------------------------------------------------------------------------------------------------------- rnnt.hip: greedy
+// fe = linear_encoder(f) [B][T][J]; cluster decode <CW workgroups, CU utterances, CKF frames> adds, per cluster: one barrier counter per 256-byte line, then ONE
+// status word behind the counters (sync: cleared by one memset before every launch), and the exchange buffers of h, linear_decoder(h) and the argmax candidates.
+struct GreedyLayout { int ncl; size_t fe, sync, status, sync_bytes, xh, xgd, xav, xai, total; };
+
+inline GreedyLayout greedy_layout(const EcRnntConfig& c, int batch, int t_out, int CW, int CU, int CKF) {
+    GreedyLayout L{};
+    WsPlan p;
+    L.ncl = (batch + CU - 1) / CU;
+    L.fe = p.take((size_t)batch * t_out * c.dim_joint * 4);
+    L.sync_bytes = (size_t)L.ncl * 256 + 256;
+    L.sync = p.take(L.sync_bytes);
+    L.status = L.sync + (size_t)L.ncl * 256;
+    L.xh = p.take((size_t)L.ncl * CU * c.dim_decoder * 4);
+    L.xgd = p.take((size_t)L.ncl * CU * c.dim_joint * 4);
+    L.xav = p.take((size_t)L.ncl * CW * CU * CKF * 4);
+    L.xai = p.take((size_t)L.ncl * CW * CU * CKF * 4);
+    L.total = p.total();
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- rnnt_beam.hip
+constexpr int BEAM_SLACK = 64;      // evaluated, not yet popped hypotheses per frame (room for evaluating ahead of the pops)
+constexpr int BEAM_HYP_BYTES = 32;  // sizeof(Hyp)
+
+struct BeamLayout {
+    int beam, maxexp, ecap, acap, tcap, ns, nnodes;
+    size_t stats, fe, utt, per_utt;                                      // byte offsets / stride
+    size_t nodes, topv, topl, a, b, trail, total;
+};
+
+inline BeamLayout beam_layout(const EcRnntConfig& c, int batch, int t_out, int beam, int maxexp) {
+    BeamLayout L{};
+    L.beam = beam; L.maxexp = maxexp;
+    L.ecap = maxexp + BEAM_SLACK;                                        // evaluations per frame: one per pop + the slack
+    L.acap = beam + maxexp * beam;                                       // A: the carried beam + beam children per pop
+    L.tcap = 1 + t_out * maxexp;                                         // trail: the start token + one entry per pop
+    L.ns = 2 * c.dim_decoder + c.dim_joint;                              // node: h', c', linear_decoder(h')
+    L.nnodes = 2 * beam + L.ecap;                                        // two carry sets (previous / next frame) + the frame's arena
+    WsPlan u;                                                            // one utterance
+    L.nodes = u.take((size_t)L.nnodes * L.ns * 4);
+    L.topv = u.take((size_t)L.ecap * beam * 4);
+    L.topl = u.take((size_t)L.ecap * beam * 4);
+    L.a = u.take((size_t)L.acap * BEAM_HYP_BYTES);
+    L.b = u.take((size_t)beam * BEAM_HYP_BYTES);
+    L.trail = u.take((size_t)L.tcap * 8);
+    L.per_utt = u.stride();
+    WsPlan p;
+    L.stats = p.take((size_t)batch * 16);
+    L.fe = p.take((size_t)batch * t_out * c.dim_joint * 4);
+    L.utt = p.take((size_t)batch * L.per_utt);
+    L.total = p.total();
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- rnnt_lattice.hip
+struct LatLayout { size_t tlen, ulen, start, h, gd, fe, total; };        // byte offsets
+
+inline LatLayout lat_layout(const EcRnntConfig& c, int batch, int t_out, int u_max) {
+    LatLayout L{};
+    WsPlan p;
+    L.tlen = p.take((size_t)batch * 4);
+    L.ulen = p.take((size_t)batch * 4);
+    L.start = p.take(((size_t)batch + 1) * 4);
+    L.h = p.take((size_t)batch * (u_max + 1) * c.dim_decoder * 4);
+    L.gd = p.take((size_t)batch * (u_max + 1) * c.dim_joint * 4);
+    L.fe = p.take(WsPlan::up((size_t)batch * t_out * c.dim_joint * 4));   // rounded: the size this entry has reported since it exists
+    L.total = p.total();
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- rnnt_align.hip
+struct RnntAlignLayout { int wpu; size_t bp, bp_utt, total; };           // back-pointer words per column, byte offsets
+
+inline RnntAlignLayout rnnt_align_layout(int batch, int t_out, int u_max) {
+    RnntAlignLayout L{};
+    L.wpu = (t_out + 31) / 32;
+    WsPlan u;
+    u.take((size_t)(u_max + 1) * L.wpu * 4);
+    L.bp_utt = u.stride();
+    WsPlan p;
+    L.bp = p.take((size_t)batch * L.bp_utt);
+    L.total = p.total();
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- lm.hip
+constexpr int LM_NPADQ = 64;        // the state holds the sequences rounded up to this many columns: every column tile a kernel touches exists
+inline int lm_npad(int n) { return (n + LM_NPADQ - 1) / LM_NPADQ * LM_NPADQ; }
+
+// i32 ulen[n]; then per layer l: h[l][2][Np][H] (k-permuted), c[l][Np][H]
+struct LmLayout { size_t ulen, state, layer, total; };
+
+inline LmLayout lm_layout(const EcLmConfig& c, int n) {
+    LmLayout L{};
+    WsPlan p;
+    L.ulen = p.take((size_t)n * 4);
+    L.layer = (size_t)3 * lm_npad(n) * c.dim_model * 4;
+    L.state = p.take((size_t)c.num_layers * L.layer);
+    L.total = p.total();
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ctc_beam.hip
+struct CtcBeamLayout {
+    int ncap, hcap;                               // trie nodes, hash slots per utterance
+    size_t stats, utt, per_utt, trace, nodes, hkeys, hvals, total;
+};
+
+inline CtcBeamLayout ctc_beam_layout(int batch, int t_out, int beam) {
+    CtcBeamLayout L{};
+    L.ncap = 1 + beam * t_out;                    // the empty prefix + at most `beam` new prefixes per frame
+    int h = 1;
+    while (h < 2 * L.ncap) h <<= 1;
+    L.hcap = h;
+    WsPlan u;                                     // one utterance
+    L.trace = u.take((size_t)t_out * beam * 16);
+    L.nodes = u.take((size_t)L.ncap * 16);
+    L.hkeys = u.take((size_t)h * 8);
+    L.hvals = u.take((size_t)h * 4);
+    L.per_utt = u.stride();
+    WsPlan p;
+    L.stats = p.take((size_t)batch * 16);
+    L.utt = p.take((size_t)batch * L.per_utt);
+    L.total = p.total();
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ctc_align.hip
+constexpr int CTC_ALIGN_THREADS = 256;            // threads per utterance
+
+inline int ctc_align_spt(int u_max) {             // the launch's states per thread: 1, 2, 4, 8 or 16
+    const int s = 2 * u_max + 1;
+    int spt = 1;
+    while (CTC_ALIGN_THREADS * spt < s) spt <<= 1;
+    return spt;
+}
+
+struct CtcAlignLayout {
+    int E, spt, rbmax;                            // emission row stride, states per thread at the most, backpointer bytes per frame at the most
+    size_t emit, path, bp, bp_utt, total;
+};
+
+inline CtcAlignLayout ctc_align_layout(int batch, int t_out, int u_max) {
+    CtcAlignLayout L{};
+    L.E = u_max + 1;
+    L.spt = ctc_align_spt(u_max);
+    L.rbmax = CTC_ALIGN_THREADS * ((L.spt + 3) / 4);
+    WsPlan u;
+    u.take((size_t)t_out * L.rbmax);
+    L.bp_utt = u.stride();
+    WsPlan p;
+    L.emit = p.take((size_t)batch * t_out * L.E * 4);
+    L.path = p.take((size_t)batch * t_out * 4);
+    L.bp = p.take((size_t)batch * L.bp_utt);
+    L.total = p.total();
+    return L;
+}
+
+}  // namespace ecdec

@@ -9,20 +9,20 @@
 //     owns 16 hidden units = the four gate row tiles {j0, H + j0, 2H + j0, 3H + j0} (torch gate order i, f, g, o) and CT 16-sequence column
 //     tiles: one weight float4 per gate feeds 4 CT MFMAs.  Grid: (hidden tiles / 4 waves) x (column tiles / CT), so a step covers the chip
 //     where one workgroup per 16 sequences (rnnt_lattice.hip's prediction network) would leave it idle.  The state lives in global memory
-//     with k permuted as the weight images (kperm, rnnt_common.h): a lane's B operand of a 16-block is ONE 16-byte load, and no LDS is used (16
+//     with k permuted as the weight images (kperm, decode_common.h): a lane's B operand of a 16-block is ONE 16-byte load, and no LDS is used (16
 //     state vectors at H = 4096 are 256 KiB).  Layer 0: K = H against W_hh, the input term from the table Gin0[y] = W_ih0 emb[y] + b_ih0 + b_hh0
 //     (built at finalize as effconf_rnnt_finalize builds gin).  Layers l >= 1: K = 2H against the image of [W_ih_l | W_hh_l]: first the layer
 //     below's h of THIS step, then this layer's h of the previous step; k ascends within each part.  h is double buffered between steps; a
 //     sequence with u >= len keeps (h, c) through a select, and a wave whose column tiles hold finished sequences only returns at once
 //     (wave-uniform; nothing reads such a state again; LanguageModel sorts the sequences by length, so such tiles exist).
-//   * lm_head_kernel<FULL>: fc as a GEMM over the vocabulary tiles of 32 sequences per workgroup (rnnt_joint_kernel's loop).  FULL = false: the
+//   * lm_head_kernel<FULL>: fc as a GEMM over the vocabulary tiles of 32 sequences per workgroup (vocab_lse_tiles, the loop rnnt_joint_kernel runs).  FULL = false: the
 //     lane's running (max, sum exp) of (acc + b) / tmp and the pick of column y_u, merged in a fixed order (k-slots of a wave, then waves 0 .. 7);
 //     ONE float per (sequence, position) leaves the kernel, and score[n] += it (a launch per position: u ascending).  FULL = true (the decode
 //     step): the raw logits row acc + b.  V % 16 != 0: rows clamped on load, masked with -inf.
 // A column of an MFMA tile depends on that column of B alone and unused columns are zero: a sequence's results are bit-identical alone, in any
 // batch, in any order, under a larger u_max, with garbage behind its length and on a workspace filled with any byte (the state is cleared by a
 // memset on the stream, nothing else is read before it is written).
-#include "rnnt_common.h"
+#include "decode_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,11 +30,12 @@
 int ec_fail(const char* msg);
 
 using namespace ecrnnt;
+using namespace ecdec;
 
 struct EcLm {
     EcLmConfig cfg;
-    std::map<std::string, EcRnntHostT> host;
-    std::vector<void*> allocs;
+    EcHostTensors host;
+    DeviceAllocs allocs;
     const float* gin0 = nullptr;          // [V][4H]
     const float4* w16[4] = {};            // layer 0: kperm16(W_hh0) [H/16][4][4H]; l >= 1: kperm16([W_ih_l | W_hh_l]) [2H/16][4][4H]
     const float* bsum[4] = {};            // l >= 1: b_ih_l + b_hh_l [4H]
@@ -50,12 +51,9 @@ constexpr int SW = ST / 64;
 constexpr int HT = 512;          // threads of a head workgroup
 constexpr int HW = HT / 64;
 constexpr int HC = 32;           // sequences per head workgroup: two column tiles
-constexpr int NPADQ = 64;        // the state holds the sequences rounded up to this many columns: every column tile a kernel touches exists
 constexpr int MAX_H = 4096, MAX_L = 4, MAX_U = 4096;
 constexpr int MAX_N = 1 << 21;   // the step grid's y extent is Np / 64 at most: 32768 < 65536
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-int npad(int n) { return (n + NPADQ - 1) / NPADQ * NPADQ; }
 
 const char* cfg_check(const EcLmConfig& c) {
     if (c.dim_model % 16 != 0) return "lm: dim_model must be a multiple of 16";
@@ -72,18 +70,6 @@ const char* shape_check(const EcLm* lm, int32_t n, int32_t u_max) {
     if (u_max < 0 || u_max > MAX_U) return "lm: u_max must be in 0 .. 4096";
     if ((int64_t)n * u_max >= (1ll << 31)) return "lm: n * u_max must be below 2^31";
     return nullptr;
-}
-
-// workspace (the pointer aligned up to 256 bytes): i32 ulen[n]; then per layer l: h[l][2][Np][H] (k-permuted), c[l][Np][H]
-struct LmLayout { size_t ulen, state, layer, total; };
-
-LmLayout lm_layout(const EcLmConfig& c, int n) {
-    LmLayout L{};
-    L.ulen = 0;
-    L.state = al256((size_t)n * 4);
-    L.layer = (size_t)3 * npad(n) * c.dim_model * 4;
-    L.total = L.state + (size_t)c.num_layers * L.layer + 256;
-    return L;
 }
 
 struct StepArgs {
@@ -185,13 +171,10 @@ __global__ __launch_bounds__(ST) void lm_lstm_step_kernel(const StepArgs a) {
         float cn[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float ig = sigmoid_precise(acc[0][c][e] + bi[e]), fg = sigmoid_precise(acc[1][c][e] + bf[e]);
-            const float gg = tanhf(acc[2][c][e] + bg[e]), og = sigmoid_precise(acc[3][c][e] + bo[e]);
-            const float cv = fg * cold[e] + ig * gg;
-            const float hv = og * tanhf(cv);
+            const LstmState s = lstm_cell(acc[0][c][e] + bi[e], acc[1][c][e] + bf[e], acc[2][c][e] + bg[e], acc[3][c][e] + bo[e], cold[e]);
             const size_t hi = (size_t)n * H + kperm(unit0 + e);
-            a.hn[hi] = adv ? hv : a.hp[hi];          // (n, unit) belongs to this lane alone
-            cn[e] = adv ? cv : cold[e];
+            a.hn[hi] = adv ? s.h : a.hp[hi];         // (n, unit) belongs to this lane alone
+            cn[e] = adv ? s.c : cold[e];
         }
         *reinterpret_cast<float4*>(cr) = make_float4(cn[0], cn[1], cn[2], cn[3]);
     }
@@ -206,18 +189,9 @@ struct PrepArgs {
 __global__ __launch_bounds__(256) void lm_prep_kernel(const PrepArgs a) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= a.N) return;
-    const long long ul = a.len[n];
-    int st = 0, U = 0;
-    if (ul < 0 || ul > a.umax) st = 2;
-    else {
-        U = (int)ul;
-        for (int u = 0; u < U; ++u) {
-            const int c = a.tokens[(size_t)n * a.umax + u];
-            if (c < 1 || c >= a.V) st = 2;
-        }
-    }
+    const int st = transcript_status(a.len[n], a.umax, a.tokens + (size_t)n * a.umax, a.V);
     a.status[n] = st;
-    a.ulen[n] = st ? -1 : U;                         // -1: the sequence never advances and every token_logp of its row is -inf
+    a.ulen[n] = st ? -1 : (int)a.len[n];             // -1: the sequence never advances and every token_logp of its row is -inf
     a.score[n] = st ? -INFINITY : 0.f;
 }
 
@@ -232,13 +206,21 @@ struct HeadArgs {
     int u, umax, N, H, V; float tmp;
 };
 
-// running (max, sum exp) of a sequence's logits: merge of two partial results; an empty part is (-inf, 0)
-__device__ __forceinline__ void ms_merge(float& m, float& s, float om, float os) {
-    const float nm = fmaxf(m, om);
-    const float ea = m == -INFINITY ? 0.f : expf(m - nm), eb = om == -INFINITY ? 0.f : expf(om - nm);
-    s = s * ea + os * eb;
-    m = nm;
-}
+// vocab_lse_tiles' picks for the lane's two sequences j and 16 + j: the label entry of each (scoring), or the whole row (the decode step; null: beyond the batch)
+struct LmLabelPick {
+    float* label; int y0, y1;                        // this lane's slot of s_label (the second sequence's is 16 further)
+    __device__ __forceinline__ void operator()(int n, float v0, float v1) const {
+        if (n == y0) label[0] = v0;
+        if (n == y1) label[16] = v1;
+    }
+};
+struct LmLogitsPick {
+    float* row0; float* row1;
+    __device__ __forceinline__ void operator()(int n, float v0, float v1) const {
+        if (row0) row0[n] = v0;
+        if (row1) row1[n] = v1;
+    }
+};
 
 template <bool FULL>
 __global__ __launch_bounds__(HT) void lm_head_kernel(const HeadArgs a) {
@@ -265,102 +247,22 @@ __global__ __launch_bounds__(HT) void lm_head_kernel(const HeadArgs a) {
             return;
         }
     }
-    const int ntile = (V + 15) / 16;
-    const size_t bs = (size_t)4 * V;                 // float4s per 16-block of the weight image: [g][n]
     const float* x0 = a.h + (size_t)(c0 + j) * H + 4 * g;
     const float* x1 = a.h + (size_t)(c0 + 16 + j) * H + 4 * g;
-    const int y0 = FULL ? -1 : s_y[j], y1 = FULL ? -1 : s_y[16 + j];
-    float m0 = -INFINITY, m1 = -INFINITY, r0 = 0.f, r1 = 0.f;     // the lane's running (max, sum) of sequences j and 16 + j
-    for (int tp = wave; 2 * tp < ntile; tp += HW) {
-        const float4* wp[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int n = 16 * (2 * tp + i) + j;
-            wp[i] = a.wfc16 + (size_t)g * V + (n < V ? n : V - 1);     // clamped: rows at or beyond V are masked below
-        }
-        f32x4 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float4 wn[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) wn[i] = wp[i][0];
-        for (int q = 0; q < K16; ++q) {
-            float4 wv[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) wv[i] = wn[i];
-            const int qn = q + 1 < K16 ? q + 1 : q;                  // last pass: a harmless re-load
-#pragma unroll
-            for (int i = 0; i < 2; ++i) wn[i] = wp[i][(size_t)qn * bs];
-            const float4 xa = *reinterpret_cast<const float4*>(x0 + 16 * q);
-            const float4 xb = *reinterpret_cast<const float4*>(x1 + 16 * q);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].x, xa.x, acc[i][0], 0, 0, 0);
-                acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].x, xb.x, acc[i][1], 0, 0, 0);
-                acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].y, xa.y, acc[i][0], 0, 0, 0);
-                acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].y, xb.y, acc[i][1], 0, 0, 0);
-                acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].z, xa.z, acc[i][0], 0, 0, 0);
-                acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].z, xb.z, acc[i][1], 0, 0, 0);
-                acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].w, xa.w, acc[i][0], 0, 0, 0);
-                acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv[i].w, xb.w, acc[i][1], 0, 0, 0);
-            }
-        }
-        // ---- epilogue of the pair: row 4 g + e of tile i = vocabulary entry n, column j = sequence
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int nb = 16 * (2 * tp + i) + 4 * g;
-            if (FULL) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int n = nb + e;
-                    if (n < V) {
-                        const float bias = a.bfc[n];
-                        if (c0 + j < a.N) a.logits[(size_t)(c0 + j) * V + n] = acc[i][0][e] + bias;
-                        if (c0 + 16 + j < a.N) a.logits[(size_t)(c0 + 16 + j) * V + n] = acc[i][1][e] + bias;
-                    }
-                }
-            } else {
-                float v0[4], v1[4];
-                float t0 = -INFINITY, t1 = -INFINITY;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int n = nb + e;
-                    const float bias = a.bfc[n < V ? n : V - 1];
-                    v0[e] = n < V ? (acc[i][0][e] + bias) / a.tmp : -INFINITY;
-                    v1[e] = n < V ? (acc[i][1][e] + bias) / a.tmp : -INFINITY;
-                    t0 = fmaxf(t0, v0[e]); t1 = fmaxf(t1, v1[e]);
-                    if (n == y0) s_label[j] = v0[e];
-                    if (n == y1) s_label[16 + j] = v1[e];
-                }
-                if (nb < V) {                        // at least one entry: nb itself
-                    float p0 = 0.f, p1 = 0.f;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { p0 += expf(v0[e] - t0); p1 += expf(v1[e] - t1); }     // exp(-inf) = 0 for the masked entries
-                    ms_merge(m0, r0, t0, p0);
-                    ms_merge(m1, r1, t1, p1);
-                }
-            }
-        }
+    float ms[4];                                     // the lane's running (max, sum) of sequences j and 16 + j
+    if (FULL) {                                      // the raw logits row acc + b: tmp = 1 (x / 1 = x), the running sums are dead code
+        float* row0 = c0 + j < a.N ? a.logits + (size_t)(c0 + j) * V : nullptr;
+        float* row1 = c0 + 16 + j < a.N ? a.logits + (size_t)(c0 + 16 + j) * V : nullptr;
+        vocab_lse_tiles<1, HW>(a.wfc16, a.bfc, V, K16, x0, x1, 1.f, LmLogitsPick{row0, row1}, ms);
+        return;
     }
-    if (FULL) return;
-    // ---- merge the k-slots of the wave (g = 0 + 1, 2 + 3, then the two halves), then the waves in order
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-        const float om0 = __shfl_xor(m0, o), os0 = __shfl_xor(r0, o), om1 = __shfl_xor(m1, o), os1 = __shfl_xor(r1, o);
-        if (!(lane & o)) { ms_merge(m0, r0, om0, os0); ms_merge(m1, r1, om1, os1); }
-    }
-    if (g == 0) { s_m[wave][j] = m0; s_s[wave][j] = r0; s_m[wave][16 + j] = m1; s_s[wave][16 + j] = r1; }
-    __syncthreads();
+    vocab_lse_tiles<1, HW>(a.wfc16, a.bfc, V, K16, x0, x1, a.tmp, LmLabelPick{s_label + j, s_y[j], s_y[16 + j]}, ms);
+    const float lse = vocab_lse_merge<HW>(ms, s_m, s_s);
     if (tid < HC && c0 + tid < a.N) {
         const int n = c0 + tid;
         float out = a.ulen[n] < 0 ? -INFINITY : 0.f;                 // a refused sequence: -inf; at or beyond the length: 0
         if (s_y[tid] >= 0) {
-            float m = s_m[0][tid], s = s_s[0][tid];
-#pragma unroll
-            for (int q = 1; q < HW; ++q) ms_merge(m, s, s_m[q][tid], s_s[q][tid]);
-            out = s_label[tid] - (m + logf(s));
+            out = s_label[tid] - lse;
             a.score[n] += out;                       // one launch per position on one stream: u ascending
         }
         if (a.token_logp) a.token_logp[(size_t)n * a.umax + a.u] = out;
@@ -389,25 +291,10 @@ __global__ __launch_bounds__(256) void lm_state_out_kernel(const float* state, s
     if (c_out) c_out[i] = base[(size_t)2 * Np * H + (size_t)n * H + k];
 }
 
-void* upload(EcLm* lm, const void* src, size_t bytes) {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-    lm->allocs.push_back(d);
-    if (src && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
-}
-
-const EcRnntHostT* need(EcLm* lm, const std::string& key, std::initializer_list<int64_t> shape, std::string& err) {
-    auto it = lm->host.find(key);
-    if (it == lm->host.end()) { if (err.empty()) err = "missing tensor " + key; return nullptr; }
-    if (it->second.shape != std::vector<int64_t>(shape)) { if (err.empty()) err = "bad shape for " + key; return nullptr; }
-    return &it->second;
-}
-
 // one LSTM step of layer l on buffers cur -> 1 - cur of the state
 int launch_step(const EcLm* lm, float* state, size_t layer_floats, int l, int cur, int N, const int* tok, long long tok_stride, int tok_off, const int* ulen, int u,
                 hipStream_t s) {
-    const int H = lm->cfg.dim_model, Np = npad(N);
+    const int H = lm->cfg.dim_model, Np = lm_npad(N);
     const size_t buf = (size_t)Np * H;
     float* base = state + (size_t)l * layer_floats;
     StepArgs a{};
@@ -442,17 +329,13 @@ EcLm* effconf_lm_create(const EcLmConfig* c) {
 
 void effconf_lm_destroy(EcLm* lm) {
     if (!lm) return;
-    for (void* p : lm->allocs) (void)hipFree(p);
+    lm->allocs.free_all();
     delete lm;
 }
 
 int effconf_lm_load_tensor(EcLm* lm, const char* key, const float* host, const int64_t* shape, int32_t ndim) {
     if (!lm || !key || !host || (ndim > 0 && !shape)) return ec_fail("null argument");
-    EcRnntHostT t;
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
-    t.data.assign(host, host + n);
-    lm->host[key] = std::move(t);
+    host_tensor_put(lm->host, key, host, shape, ndim);
     lm->finalized = false;
     return 0;
 }
@@ -461,30 +344,35 @@ int effconf_lm_finalize(EcLm* lm) {
     if (!lm) return ec_fail("null handle");
     const int H = lm->cfg.dim_model, V = lm->cfg.vocab_size, L = lm->cfg.num_layers;
     // every tensor is looked up before the first device call: a missing key is reported without a GPU
-    std::string err;
-    const EcRnntHostT* emb = need(lm, "decoder.embedding.weight", {V, H}, err);
-    const EcRnntHostT* wfc = need(lm, "fc.weight", {V, H}, err);
-    const EcRnntHostT* bfc = need(lm, "fc.bias", {V}, err);
+    std::string err;                                 // the first tensor that is missing or misshapen
+    auto need = [&](const std::string& key, std::initializer_list<int64_t> shape) {
+        std::string e;
+        const EcRnntHostT* t = ::need(lm->host, key, shape, e);
+        if (!t && err.empty()) err = e;
+        return t;
+    };
+    const EcRnntHostT* emb = need("decoder.embedding.weight", {V, H});
+    const EcRnntHostT* wfc = need("fc.weight", {V, H});
+    const EcRnntHostT* bfc = need("fc.bias", {V});
     const EcRnntHostT *wih[MAX_L], *whh[MAX_L], *bih[MAX_L], *bhh[MAX_L];
     for (int l = 0; l < L; ++l) {
         const std::string p = "decoder.rnn.", sfx = "_l" + std::to_string(l);
-        wih[l] = need(lm, p + "weight_ih" + sfx, {4 * H, H}, err);
-        whh[l] = need(lm, p + "weight_hh" + sfx, {4 * H, H}, err);
-        bih[l] = need(lm, p + "bias_ih" + sfx, {4 * H}, err);
-        bhh[l] = need(lm, p + "bias_hh" + sfx, {4 * H}, err);
+        wih[l] = need(p + "weight_ih" + sfx, {4 * H, H});
+        whh[l] = need(p + "weight_hh" + sfx, {4 * H, H});
+        bih[l] = need(p + "bias_ih" + sfx, {4 * H});
+        bhh[l] = need(p + "bias_hh" + sfx, {4 * H});
     }
     if (!err.empty()) return ec_fail(err.c_str());
-    for (void* p : lm->allocs) (void)hipFree(p);
-    lm->allocs.clear();
+    lm->allocs.free_all();
     lm->finalized = false;
     bool ok = true;
     for (int l = 0; l < L; ++l) {
         std::vector<float> bs(4 * H);
         for (int i = 0; i < 4 * H; ++i) bs[i] = bih[l]->data[i] + bhh[l]->data[i];
-        lm->bsum[l] = (const float*)upload(lm, bs.data(), bs.size() * 4);
+        lm->bsum[l] = (const float*)lm->allocs.upload(bs.data(), bs.size() * 4);
         if (l == 0) {
             const std::vector<float> img = kperm16(whh[0]->data, 4 * H, H);
-            lm->w16[0] = (const float4*)upload(lm, img.data(), img.size() * 4);
+            lm->w16[0] = (const float4*)lm->allocs.upload(img.data(), img.size() * 4);
         } else {
             std::vector<float> cat((size_t)4 * H * 2 * H);           // [W_ih_l | W_hh_l]: rows of 2H
             for (int r = 0; r < 4 * H; ++r) {
@@ -492,26 +380,24 @@ int effconf_lm_finalize(EcLm* lm) {
                 std::copy(whh[l]->data.begin() + (size_t)r * H, whh[l]->data.begin() + (size_t)(r + 1) * H, cat.begin() + (size_t)r * 2 * H + H);
             }
             const std::vector<float> img = kperm16(cat, 4 * H, 2 * H);
-            lm->w16[l] = (const float4*)upload(lm, img.data(), img.size() * 4);
+            lm->w16[l] = (const float4*)lm->allocs.upload(img.data(), img.size() * 4);
         }
         ok = ok && lm->bsum[l] && lm->w16[l];
     }
     {
         const std::vector<float> img = kperm16(wfc->data, V, H);
-        lm->wfc16 = (const float4*)upload(lm, img.data(), img.size() * 4);
+        lm->wfc16 = (const float4*)lm->allocs.upload(img.data(), img.size() * 4);
     }
-    lm->bfc = (const float*)upload(lm, bfc->data.data(), bfc->data.size() * 4);
-    float* d_emb = (float*)upload(lm, emb->data.data(), emb->data.size() * 4);
-    float* d_wih = (float*)upload(lm, wih[0]->data.data(), wih[0]->data.size() * 4);
-    float* d_gin = (float*)upload(lm, nullptr, (size_t)V * 4 * H * 4);
+    lm->bfc = (const float*)lm->allocs.upload(bfc->data.data(), bfc->data.size() * 4);
+    float* d_emb = (float*)lm->allocs.upload(emb->data.data(), emb->data.size() * 4);
+    float* d_wih = (float*)lm->allocs.upload(wih[0]->data.data(), wih[0]->data.size() * 4);
+    float* d_gin = (float*)lm->allocs.upload(nullptr, (size_t)V * 4 * H * 4);
     if (!ok || !lm->wfc16 || !lm->bfc || !d_emb || !d_wih || !d_gin) return ec_fail("lm: device allocation / upload failed");
     // Gin0[y] = W_ih0 emb[y] + (b_ih0 + b_hh0) for every token id; row 0 from the embedding row the checkpoint holds
     if (launch_sgemm_nt(d_emb, H, d_wih, H, lm->bsum[0], d_gin, 4 * H, V, 4 * H, H, nullptr) != 0) return ec_fail("lm: Gin GEMM launch failed");
     if (hipDeviceSynchronize() != hipSuccess) return ec_fail("lm: Gin GEMM failed");
-    for (void* p : {(void*)d_emb, (void*)d_wih}) {       // only the Gin GEMM read them
-        (void)hipFree(p);
-        lm->allocs.erase(std::find(lm->allocs.begin(), lm->allocs.end(), p));
-    }
+    lm->allocs.release(d_emb);                           // only the Gin GEMM read them
+    lm->allocs.release(d_wih);
     lm->gin0 = d_gin;
     lm->finalized = true;
     return 0;
@@ -532,10 +418,10 @@ int effconf_lm_score(EcLm* lm, const int32_t* tokens, const int64_t* token_len, 
     const LmLayout L = lm_layout(lm->cfg, n);
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_lm_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
     int* ulen = reinterpret_cast<int*>(ws + L.ulen);
     float* state = reinterpret_cast<float*>(ws + L.state);
-    const int H = lm->cfg.dim_model, V = lm->cfg.vocab_size, NL = lm->cfg.num_layers, Np = npad(n);
+    const int H = lm->cfg.dim_model, V = lm->cfg.vocab_size, NL = lm->cfg.num_layers, Np = lm_npad(n);
     const size_t layer_floats = L.layer / 4;
     PrepArgs p{tokens, reinterpret_cast<const long long*>(token_len), n, u_max, V, ulen, status, score};
     hipLaunchKernelGGL(lm_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p);
@@ -566,9 +452,9 @@ int effconf_lm_step(EcLm* lm, const int32_t* tokens, const float* h_in, const fl
     const LmLayout L = lm_layout(lm->cfg, n);
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_lm_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
     float* state = reinterpret_cast<float*>(ws + L.state);
-    const int H = lm->cfg.dim_model, V = lm->cfg.vocab_size, NL = lm->cfg.num_layers, Np = npad(n);
+    const int H = lm->cfg.dim_model, V = lm->cfg.vocab_size, NL = lm->cfg.num_layers, Np = lm_npad(n);
     const size_t layer_floats = L.layer / 4;
     const size_t cells = (size_t)NL * Np * H;
     hipLaunchKernelGGL(lm_state_in_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, h_in, c_in, state, layer_floats, NL, n, Np, H);

@@ -19,7 +19,7 @@
 // All arithmetic is fp32 (the decisions feed back into the recurrence: one flipped argmax changes every later token,
 // so the head is kept at the reference's precision; softmax().log().argmax() of transducer.py:164 is argmax(logits)).
 // Bound: L2 -> CU bandwidth on the weights (4H*H*4 + J*H*4 bytes per token, V*J*4 per joint pass).
-#include "rnnt_common.h"
+#include "decode_common.h"
 
 #include <cmath>
 #include <cstdio>
@@ -33,6 +33,7 @@
 int ec_fail(const char* msg);
 
 using namespace ecrnnt;
+using namespace ecdec;
 
 namespace {
 
@@ -162,10 +163,9 @@ __global__ __launch_bounds__(NT) void rnnt_greedy_kernel(RnntDev w, const float*
         }
         __syncthreads();
         for (int j = tid; j < H; j += NT) {
-            const float ig = sigmoid_precise(sg[j]), fg = sigmoid_precise(sg[H + j]), gg = tanhf(sg[2 * H + j]), og = sigmoid_precise(sg[3 * H + j]);
-            const float c = fg * sc[j] + ig * gg;
-            sc[j] = c;
-            sh[j] = og * tanhf(c);
+            const LstmState s = lstm_cell(sg[j], sg[H + j], sg[2 * H + j], sg[3 * H + j], sc[j]);
+            sc[j] = s.c;
+            sh[j] = s.h;
         }
         __syncthreads();
         // ---- gd = linear_decoder(h)
@@ -396,10 +396,9 @@ __global__ __launch_bounds__(CNT) void rnnt_cluster_kernel(const ClusterArgs a) 
                 float hv = sh[u * H + kperm(wg * HU + unit)];
                 if (s_need[u] && s_step[u] < s_T[u]) {
                     const float* g = sg + u * 4 * HU + unit;
-                    const float ig = sigmoid_precise(g[0]), fg = sigmoid_precise(g[HU]), gg = tanhf(g[2 * HU]), og = sigmoid_precise(g[3 * HU]);
-                    const float c = fg * sc[i] + ig * gg;
-                    sc[i] = c;
-                    hv = og * tanhf(c);
+                    const LstmState s = lstm_cell(g[0], g[HU], g[2 * HU], g[3 * HU], sc[i]);
+                    sc[i] = s.c;
+                    hv = s.h;
                 }
                 xstore(xh + u * H + wg * HU + unit, hv);
             }
@@ -554,7 +553,7 @@ __global__ __launch_bounds__(CNT) void rnnt_cluster_kernel(const ClusterArgs a) 
 
 template <int CW, int CU, int CKF>
 struct ClusterShape {
-    static size_t exchange_bytes(int ncl, int H, int J) { return (size_t)ncl * ((size_t)CU * H * 4 + (size_t)CU * J * 4 + (size_t)CW * CU * CKF * 8 + 256) + 256; }
+    static GreedyLayout layout(const EcRnntConfig& c, int batch, int t_out) { return greedy_layout(c, batch, t_out, CW, CU, CKF); }
     static size_t lds_bytes(int H, int J) { const int HU = H / CW; return (size_t)(CU * H + CU * J + CU * CKF * J + CU * HU + CU * 4 * HU + CU * CKF * 16) * 4; }
     static bool supported(const EcRnntConfig& c) {
         // 16-blocks of k in groups of CMB; whole 16-row tiles of gate rows; at most 4 gate tiles per wave and one vocabulary tile per wave; the state in LDS
@@ -567,19 +566,6 @@ using ShapeB = ClusterShape<16, 16, 1>;
 
 using HostT = EcRnntHostT;
 
-}  // namespace
-
-
-namespace {
-
-void* upload(EcRnnt* r, const void* src, size_t bytes) {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-    r->allocs.push_back(d);
-    if (src && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
-}
-
 // W [N][K] row-major -> float4 image [K/4][N]
 std::vector<float> kmajor4(const std::vector<float>& W, int N, int K) {
     std::vector<float> o((size_t)N * K);
@@ -587,13 +573,6 @@ std::vector<float> kmajor4(const std::vector<float>& W, int N, int K) {
         for (int n = 0; n < N; ++n)
             for (int e = 0; e < 4; ++e) o[((size_t)k4 * N + n) * 4 + e] = W[(size_t)n * K + 4 * k4 + e];
     return o;
-}
-
-const HostT* need(EcRnnt* r, const char* key, std::initializer_list<int64_t> shape, std::string& err) {
-    auto it = r->host.find(key);
-    if (it == r->host.end()) { err = std::string("missing tensor ") + key; return nullptr; }
-    if (it->second.shape != std::vector<int64_t>(shape)) { err = std::string("bad shape for ") + key; return nullptr; }
-    return &it->second;
 }
 
 }  // namespace
@@ -613,62 +592,57 @@ EcRnnt* effconf_rnnt_create(const EcRnntConfig* c) {
 
 void effconf_rnnt_destroy(EcRnnt* r) {
     if (!r) return;
-    for (void* p : r->allocs) (void)hipFree(p);
+    r->allocs.free_all();
     delete r;
 }
 
 int effconf_rnnt_load_tensor(EcRnnt* r, const char* key, const float* host, const int64_t* shape, int32_t ndim) {
     if (!r || !key || !host) return ec_fail("null argument");
-    HostT t;
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= shape[i]; }
-    t.data.assign(host, host + n);
-    r->host[key] = std::move(t);
+    host_tensor_put(r->host, key, host, shape, ndim);
     r->finalized = false;
     return 0;
 }
 
 int effconf_rnnt_finalize(EcRnnt* r) {
     if (!r) return ec_fail("null handle");
-    for (void* p : r->allocs) (void)hipFree(p);
-    r->allocs.clear();
+    r->allocs.free_all();
     const int H = r->cfg.dim_decoder, J = r->cfg.dim_joint, V = r->cfg.vocab_size, De = r->cfg.dim_encoder;
     std::string err;
-    const HostT* emb = need(r, "decoder.embedding.weight", {V, H}, err);
-    const HostT* wih = need(r, "decoder.rnn.weight_ih_l0", {4 * H, H}, err);
-    const HostT* whh = need(r, "decoder.rnn.weight_hh_l0", {4 * H, H}, err);
-    const HostT* bih = need(r, "decoder.rnn.bias_ih_l0", {4 * H}, err);
-    const HostT* bhh = need(r, "decoder.rnn.bias_hh_l0", {4 * H}, err);
-    const HostT* we = need(r, "joint_network.linear_encoder.weight", {J, De}, err);
-    const HostT* be = need(r, "joint_network.linear_encoder.bias", {J}, err);
-    const HostT* wd = need(r, "joint_network.linear_decoder.weight", {J, H}, err);
-    const HostT* bd = need(r, "joint_network.linear_decoder.bias", {J}, err);
-    const HostT* wj = need(r, "joint_network.linear_joint.weight", {V, J}, err);
-    const HostT* bj = need(r, "joint_network.linear_joint.bias", {V}, err);
+    const HostT* emb = need(r->host, "decoder.embedding.weight", {V, H}, err);
+    const HostT* wih = need(r->host, "decoder.rnn.weight_ih_l0", {4 * H, H}, err);
+    const HostT* whh = need(r->host, "decoder.rnn.weight_hh_l0", {4 * H, H}, err);
+    const HostT* bih = need(r->host, "decoder.rnn.bias_ih_l0", {4 * H}, err);
+    const HostT* bhh = need(r->host, "decoder.rnn.bias_hh_l0", {4 * H}, err);
+    const HostT* we = need(r->host, "joint_network.linear_encoder.weight", {J, De}, err);
+    const HostT* be = need(r->host, "joint_network.linear_encoder.bias", {J}, err);
+    const HostT* wd = need(r->host, "joint_network.linear_decoder.weight", {J, H}, err);
+    const HostT* bd = need(r->host, "joint_network.linear_decoder.bias", {J}, err);
+    const HostT* wj = need(r->host, "joint_network.linear_joint.weight", {V, J}, err);
+    const HostT* bj = need(r->host, "joint_network.linear_joint.bias", {V}, err);
     if (!emb || !wih || !whh || !bih || !bhh || !we || !be || !wd || !bd || !wj || !bj) return ec_fail(err.c_str());
     std::vector<float> bsum(4 * H);
     for (int i = 0; i < 4 * H; ++i) bsum[i] = bih->data[i] + bhh->data[i];
     const std::vector<float> whh4 = kmajor4(whh->data, 4 * H, H), wd4 = kmajor4(wd->data, J, H), wj4 = kmajor4(wj->data, V, J);
-    float* d_emb = (float*)upload(r, emb->data.data(), emb->data.size() * 4);
-    float* d_wih = (float*)upload(r, wih->data.data(), wih->data.size() * 4);
-    float* d_bsum = (float*)upload(r, bsum.data(), bsum.size() * 4);
-    float* d_gin = (float*)upload(r, nullptr, (size_t)V * 4 * H * 4);
-    r->dev.whh4 = (const float4*)upload(r, whh4.data(), whh4.size() * 4);
-    r->dev.wd4 = (const float4*)upload(r, wd4.data(), wd4.size() * 4);
-    r->dev.bd = (const float*)upload(r, bd->data.data(), bd->data.size() * 4);
-    r->dev.wj4 = (const float4*)upload(r, wj4.data(), wj4.size() * 4);
-    r->dev.bj = (const float*)upload(r, bj->data.data(), bj->data.size() * 4);
+    float* d_emb = (float*)r->allocs.upload(emb->data.data(), emb->data.size() * 4);
+    float* d_wih = (float*)r->allocs.upload(wih->data.data(), wih->data.size() * 4);
+    float* d_bsum = (float*)r->allocs.upload(bsum.data(), bsum.size() * 4);
+    float* d_gin = (float*)r->allocs.upload(nullptr, (size_t)V * 4 * H * 4);
+    r->dev.whh4 = (const float4*)r->allocs.upload(whh4.data(), whh4.size() * 4);
+    r->dev.wd4 = (const float4*)r->allocs.upload(wd4.data(), wd4.size() * 4);
+    r->dev.bd = (const float*)r->allocs.upload(bd->data.data(), bd->data.size() * 4);
+    r->dev.wj4 = (const float4*)r->allocs.upload(wj4.data(), wj4.size() * 4);
+    r->dev.bj = (const float*)r->allocs.upload(bj->data.data(), bj->data.size() * 4);
     r->dev.whh16 = r->dev.wd16 = r->dev.wj16 = nullptr;
     if (ShapeA::supported(r->cfg) || ShapeB::supported(r->cfg) || beam_dims_supported(r->cfg)) {
         const std::vector<float> a16 = kperm16(whh->data, 4 * H, H), b16 = kperm16(wd->data, J, H), c16 = kperm16(wj->data, V, J);
-        r->dev.whh16 = (const float4*)upload(r, a16.data(), a16.size() * 4);
-        r->dev.wd16 = (const float4*)upload(r, b16.data(), b16.size() * 4);
-        r->dev.wj16 = (const float4*)upload(r, c16.data(), c16.size() * 4);
+        r->dev.whh16 = (const float4*)r->allocs.upload(a16.data(), a16.size() * 4);
+        r->dev.wd16 = (const float4*)r->allocs.upload(b16.data(), b16.size() * 4);
+        r->dev.wj16 = (const float4*)r->allocs.upload(c16.data(), c16.size() * 4);
         if (!r->dev.whh16 || !r->dev.wd16 || !r->dev.wj16) return ec_fail("device allocation / upload failed");
     }
-    r->we = (float*)upload(r, we->data.data(), we->data.size() * 4);
-    r->be = (float*)upload(r, be->data.data(), be->data.size() * 4);
-    r->wd = (float*)upload(r, wd->data.data(), wd->data.size() * 4);
+    r->we = (float*)r->allocs.upload(we->data.data(), we->data.size() * 4);
+    r->be = (float*)r->allocs.upload(be->data.data(), be->data.size() * 4);
+    r->wd = (float*)r->allocs.upload(wd->data.data(), wd->data.size() * 4);
     if (!d_emb || !d_wih || !d_bsum || !d_gin || !r->dev.whh4 || !r->dev.wd4 || !r->dev.bd || !r->dev.wj4 || !r->dev.bj || !r->we || !r->be || !r->wd)
         return ec_fail("device allocation / upload failed");
     // Gin[y] = W_ih emb[y] + (b_ih + b_hh)   for every token id (Embedding rows are the only LSTM inputs, decoders.py:55)
@@ -682,8 +656,7 @@ int effconf_rnnt_finalize(EcRnnt* r) {
 
 size_t effconf_rnnt_workspace_bytes(const EcRnnt* r, int32_t batch, int32_t t_out) {
     if (!r || batch < 0 || t_out < 0) return 0;
-    const size_t ex = std::max(ShapeA::exchange_bytes((batch + 7) / 8, r->cfg.dim_decoder, r->cfg.dim_joint), ShapeB::exchange_bytes((batch + 15) / 16, r->cfg.dim_decoder, r->cfg.dim_joint));
-    return (size_t)batch * t_out * r->cfg.dim_joint * 4 + 256 + ex;
+    return std::max(ShapeA::layout(r->cfg, batch, t_out).total, ShapeB::layout(r->cfg, batch, t_out).total);     // whichever decode runs: fe is the first region of both
 }
 
 int effconf_rnnt_set_option(EcRnnt* r, const char* name, int32_t value) {
@@ -714,7 +687,8 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
     if (workspace_bytes < effconf_rnnt_workspace_bytes(r, batch, t_out)) return ec_fail("workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int H = r->cfg.dim_decoder, J = r->cfg.dim_joint, De = r->cfg.dim_encoder;
-    float* fe = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
+    float* fe = reinterpret_cast<float*>(ws + ShapeA::layout(r->cfg, batch, t_out).fe);
     // linear_encoder(f) for every frame of the batch, once (joint_networks.py:82 recomputes it per decision)
     if (launch_sgemm_nt(enc_out, De, r->we, De, r->be, fe, J, batch * t_out, J, De, s) != 0) return ec_fail("linear_encoder GEMM launch failed");
     // auto: clusters only while they need at most half of the CUs with the by-cluster mapping (two decodes on two streams must not starve
@@ -724,20 +698,18 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
     auto run_cluster = [&](auto shape, auto cw_c, auto cu_c, auto ckf_c) -> int {
         using Shape = decltype(shape);
         constexpr int CW = decltype(cw_c)::value, CU = decltype(cu_c)::value, CKF = decltype(ckf_c)::value;
-        const int ncl = (batch + CU - 1) / CU;
+        const GreedyLayout L = Shape::layout(r->cfg, batch, t_out);
+        const int ncl = L.ncl;
         if (ncl * CW > 256) return ec_fail("cluster decode needs every workgroup resident: batch <= 256");
-        char* ex = reinterpret_cast<char*>(fe) + (size_t)batch * t_out * J * 4;
-        ex = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ex) + 255) & ~(uintptr_t)255);
         ClusterArgs a{};
         a.w = r->dev; a.fe = fe; a.lens = out_len; a.T = t_out; a.B = batch; a.tokens = tokens; a.counts = token_len; a.max_tok = max_tokens;
         a.ncl = ncl; a.by_slice = r->cluster_by_slice;
-        a.cnt = reinterpret_cast<unsigned*>(ex); a.status = reinterpret_cast<int*>(ex + (size_t)ncl * 256);
-        char* p = ex + (size_t)ncl * 256 + 256;
-        a.xh = reinterpret_cast<float*>(p); p += (size_t)ncl * CU * H * 4;
-        a.xgd = reinterpret_cast<float*>(p); p += (size_t)ncl * CU * J * 4;
-        a.xav = reinterpret_cast<float*>(p); p += (size_t)ncl * CW * CU * CKF * 4;
-        a.xai = reinterpret_cast<int*>(p);
-        if (hipMemsetAsync(ex, 0, (size_t)ncl * 256 + 256, s) != hipSuccess) return ec_fail("memset failed");
+        a.cnt = reinterpret_cast<unsigned*>(ws + L.sync); a.status = reinterpret_cast<int*>(ws + L.status);
+        a.xh = reinterpret_cast<float*>(ws + L.xh);
+        a.xgd = reinterpret_cast<float*>(ws + L.xgd);
+        a.xav = reinterpret_cast<float*>(ws + L.xav);
+        a.xai = reinterpret_cast<int*>(ws + L.xai);
+        if (hipMemsetAsync(ws + L.sync, 0, L.sync_bytes, s) != hipSuccess) return ec_fail("memset failed");
         const size_t lds = Shape::lds_bytes(H, J);
         static LdsAttr attr;
         ensure_dynamic_lds(reinterpret_cast<const void*>(&rnnt_cluster_kernel<CW, CU, CKF>), (int)lds, attr);

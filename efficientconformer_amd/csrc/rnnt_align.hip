@@ -11,30 +11,18 @@
 // token_frame[u] = the frame at which token u is emitted, token_logp[u] = lp_label there.
 // VIT = false (score NULL): the forward half alone, no v, no back-pointers; log_likelihood is bit-identical.
 // Every value of an utterance is computed by the same instructions in the same order whatever the batch and the T / U padding.
-#include "kernels.h"
-#include "common.h"
-#include "../../include/effconf.h"
+#include "decode_common.h"
 
 #include <cmath>
 
 int ec_fail(const char* msg);
 
+using namespace ecrnnt;
+using namespace ecdec;
+
 namespace {
 
 constexpr int MAXU = 1023;
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct RnntAlignLayout { int wpu; size_t bp, bp_utt, total; };      // words per column, byte offsets
-
-RnntAlignLayout rnnt_align_layout(int batch, int t_out, int u_max) {
-    RnntAlignLayout L{};
-    L.wpu = (t_out + 31) / 32;
-    L.bp = 0;
-    L.bp_utt = al256((size_t)(u_max + 1) * L.wpu * 4);
-    L.total = (size_t)batch * L.bp_utt + 256;       // + 256: the caller's pointer is aligned up
-    return L;
-}
 
 const char* rnnt_align_check(int32_t batch, int32_t t_out, int32_t u_max) {
     if (u_max < 0 || u_max > MAXU) return "rnnt align: u_max must be in 0 .. 1023";
@@ -50,6 +38,8 @@ struct RnntAlignArgs {
     float* ll; float* score; int* token_frame; float* token_logp; int* status;
 };
 
+// logaddexp in the logf form of the RNN-T loss this kernel follows; ctc_align.hip's lse3 is its three-way sibling, ctc_beam.hip's lse a different formula
+// (log1pf, after the CTC beam search's reference): three functions on purpose
 __device__ __forceinline__ float lse2(float p, float q) {
     const float m = fmaxf(p, q);
     const float ms = m == -INFINITY ? 0.f : m;
@@ -61,11 +51,10 @@ template <bool VIT>
 __global__ __launch_bounds__(1024) void rnnt_dp_kernel(const RnntAlignArgs a) {
     __shared__ float sA[2][MAXU + 1], sV[2][MAXU + 1];
     const int tid = threadIdx.x, b = blockIdx.x, E = a.E;
-    const long long tl = a.lens[b], ul = a.target_len[b];
-    const int T = tl < 0 ? 0 : (tl > a.T ? a.T : (int)tl);
-    int st = a.status[b];
-    if (ul < 0 || ul > a.umax) st = 2;
-    const int U = st == 2 ? 0 : (int)ul;
+    const int T = clamp_len(a.lens[b], a.T);
+    int st = a.status[b];                            // the lattice's verdict on the tokens; the length is checked again
+    if (transcript_status(a.target_len[b], a.umax, nullptr, 0)) st = 2;
+    const int U = st == 2 ? 0 : (int)a.target_len[b];
     if (st == 0 && T == 0 && U > 0) st = 1;
     const bool run = st == 0 && T > 0;
     const float* lpb = a.lpb + (size_t)b * a.T * E;
@@ -164,7 +153,7 @@ int effconf_rnnt_align(const float* lp_blank, const float* lp_label, const int64
     if (!score && (token_frame || token_logp)) return ec_fail("null argument");
     const RnntAlignLayout L = rnnt_align_layout(batch, t_out, u_max);
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_rnnt_align_workspace_bytes)");
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
     RnntAlignArgs a{};
     a.lpb = lp_blank; a.lpl = lp_label; a.lens = out_len; a.target_len = target_len;
     a.T = t_out; a.umax = u_max; a.E = u_max + 1; a.wpu = L.wpu;

@@ -21,7 +21,7 @@
 // Bounds: at most max_expansions pops per frame (status 1 when B is still short: the reference would loop on), at most max_tokens
 // tokens in the answer (status 2); a capped utterance returns no tokens.  All storage is in the caller's workspace, sized by
 // effconf_rnnt_beam_workspace_bytes from (batch, T, beam, max_expansions).
-#include "rnnt_common.h"
+#include "decode_common.h"
 
 #include <cmath>
 #include <cstring>
@@ -29,13 +29,14 @@
 int ec_fail(const char* msg);
 
 using namespace ecrnnt;
+using namespace ecdec;
 
 namespace {
 
 constexpr int BT = 512;          // threads per utterance
 constexpr int BNW = BT / 64;     // waves
 constexpr int MAXC = 16;         // columns of an MFMA tile = largest beam and evaluation batch
-constexpr int SLACK = 64;        // evaluated, not yet popped hypotheses per frame (room for evaluating ahead of the pops)
+constexpr int SLACK = BEAM_SLACK;
 
 enum : int { H_READY = 1, H_POPPED = 2, H_EVAL = 4 };   // flags; bits 4.. hold the evaluation slot
 
@@ -43,38 +44,7 @@ enum : int { H_READY = 1, H_POPPED = 2, H_EVAL = 4 };   // flags; bits 4.. hold 
 // y the token the decoder runs on.  After evaluation `node` is the decoder output in both cases.  `lab` >= 0: a label appended to the
 // trail `trail` when the hypothesis is popped (len already counts it).
 struct Hyp { float key; float score; int len; int trail; int lab; int y; int node; int flags; };
-static_assert(sizeof(Hyp) == 32, "Hyp");
-
-struct BeamLayout {
-    int beam, maxexp, ecap, acap, tcap, ns, nnodes;
-    size_t stats, fe, utt, per_utt;                                      // byte offsets / stride
-    size_t nodes, topv, topl, a, b, trail, total;
-};
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-BeamLayout beam_layout(const EcRnntConfig& c, int batch, int t_out, int beam, int maxexp) {
-    BeamLayout L{};
-    L.beam = beam; L.maxexp = maxexp;
-    L.ecap = maxexp + SLACK;                                             // evaluations per frame: one per pop + the slack
-    L.acap = beam + maxexp * beam;                                       // A: the carried beam + beam children per pop
-    L.tcap = 1 + t_out * maxexp;                                         // trail: the start token + one entry per pop
-    L.ns = 2 * c.dim_decoder + c.dim_joint;                              // node: h', c', linear_decoder(h')
-    L.nnodes = 2 * beam + L.ecap;                                        // two carry sets (previous / next frame) + the frame's arena
-    L.stats = 0;
-    L.fe = al256((size_t)batch * 16);
-    L.utt = L.fe + al256((size_t)batch * t_out * c.dim_joint * 4);
-    size_t o = 0;
-    L.nodes = o; o = al256(o + (size_t)L.nnodes * L.ns * 4);
-    L.topv = o;  o = al256(o + (size_t)L.ecap * beam * 4);
-    L.topl = o;  o = al256(o + (size_t)L.ecap * beam * 4);
-    L.a = o;     o = al256(o + (size_t)L.acap * sizeof(Hyp));
-    L.b = o;     o = al256(o + (size_t)beam * sizeof(Hyp));
-    L.trail = o; o = al256(o + (size_t)L.tcap * 8);
-    L.per_utt = o;
-    L.total = L.utt + (size_t)batch * o + 256;                           // + 256: the caller's pointer is aligned up
-    return L;
-}
+static_assert(sizeof(Hyp) == BEAM_HYP_BYTES, "Hyp");
 
 size_t beam_lds_bytes(const EcRnntConfig& c) {
     const int H = c.dim_decoder, J = c.dim_joint, P = H > J ? H : J;
@@ -107,6 +77,17 @@ __device__ __forceinline__ void block_best(float& v, int& i, float* s_rv, int* s
         if (before(s_rv[q], s_ri[q], v, i)) { v = s_rv[q]; i = s_ri[q]; }
     __syncthreads();
 }
+
+// lstm_step16's view of one hypothesis column: a pending column steps from its state node (null: zeros) into its output node and into sy (the mat-vec operand
+// of linear_decoder, k-permuted); a ready column only zeroes its sy entries
+struct BeamColumn {
+    const float* gin; bool live; const float* from; float* to; float* sy; int H;
+    __device__ __forceinline__ float c_old(int unit) const { return from ? from[H + unit] : 0.f; }
+    __device__ __forceinline__ void put(int unit, float h, float c) const {
+        if (live) { to[unit] = h; to[H + unit] = c; }
+        sy[kperm(unit)] = h;
+    }
+};
 
 __global__ __launch_bounds__(BT) void rnnt_beam_kernel(const BeamArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -214,30 +195,9 @@ __global__ __launch_bounds__(BT) void rnnt_beam_kernel(const BeamArgs a) {
                     }
                     __syncthreads();
                     const bool pend = s_cpend[j] != 0;
-                    for (int ub = wave; ub < H / 16; ub += BNW) {
-                        int nrow[4];
-                        f32x4 acc[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) { nrow[q] = q * H + 16 * ub + j; acc[q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-                        mfma_rows16_any<4>(w.whh16, 4 * H, H / 16, nrow, sx + j * P + 4 * g, acc);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {                    // row 4 g + e of the tiles = hidden unit, column j = hypothesis
-                            const int unit = 16 * ub + 4 * g + e;
-                            float hv = 0.f;
-                            if (pend) {
-                                const float* gin = w.gin + (size_t)s_cy[j] * 4 * H;
-                                const float ig = sigmoid_precise(acc[0][e] + gin[unit]), fg = sigmoid_precise(acc[1][e] + gin[H + unit]);
-                                const float gg = tanhf(acc[2][e] + gin[2 * H + unit]), og = sigmoid_precise(acc[3][e] + gin[3 * H + unit]);
-                                const float cold = s_cst[j] >= 0 ? nodes[(size_t)s_cst[j] * ns + H + unit] : 0.f;
-                                const float c = fg * cold + ig * gg;
-                                hv = og * tanhf(c);
-                                float* on = nodes + (size_t)s_cout[j] * ns;
-                                on[unit] = hv;
-                                on[H + unit] = c;
-                            }
-                            sy[j * H + kperm(unit)] = hv;
-                        }
-                    }
+                    const BeamColumn col{w.gin + (size_t)s_cy[j] * 4 * H, pend, s_cst[j] >= 0 ? nodes + (size_t)s_cst[j] * ns : nullptr,
+                                         nodes + (size_t)s_cout[j] * ns, sy + j * H, H};
+                    for (int ub = wave; ub < H / 16; ub += BNW) lstm_step16(w, ub, sx + j * P + 4 * g, col);
                     __syncthreads();
                     // ---- linear_decoder(h') of the pending columns
                     for (int tt = wave; tt < J / 16; tt += BNW) {
@@ -398,7 +358,7 @@ int effconf_rnnt_beam(EcRnnt* r, const float* enc_out, const int64_t* out_len, i
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_rnnt_beam_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
     const int J = r->cfg.dim_joint, De = r->cfg.dim_encoder;
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
     float* fe = reinterpret_cast<float*>(ws + L.fe);
     // linear_encoder(f) for every frame of the batch, once (joint_networks.py:82 recomputes it per decision)
     if (launch_sgemm_nt(enc_out, De, r->we, De, r->be, fe, J, batch * t_out, J, De, s) != 0) return ec_fail("linear_encoder GEMM launch failed");

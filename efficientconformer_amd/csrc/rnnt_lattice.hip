@@ -11,7 +11,7 @@
 //     but no frames), the clamped lengths, and the exclusive prefix sum of the cell counts T_b (U_b + 1) - the joint kernel walks the
 //     cells of the batch as ONE dense list, so ragged batches cost what their cells cost and nothing for the padding.
 //   * rnnt_prednet_kernel: the teacher-forced prediction network.  One workgroup per 16 utterances = the 16 columns of the fp32 MFMA tiles
-//     of the beam search's LSTM step (rnnt_beam.hip: gates = Gin[y] + W_hh h, torch gate order i, f, g, o, sigmoid_precise / tanhf, k
+//     of lstm_step16 (decode_common.h, the beam search's LSTM step as well: gates = Gin[y] + W_hh h, torch gate order i, f, g, o, sigmoid_precise / tanhf, k
 //     ascending); the workgroup loops over u = 0 .. u_max and writes h_u.  A column's arithmetic does not depend on the other 15.
 //   * linear_decoder over all B (u_max + 1) rows and linear_encoder over all B T rows: launch_sgemm_nt, as the beam search does.
 //   * rnnt_joint_kernel: a tiled GEMM with M = cells, K = J, N = V.  A workgroup (8 waves) owns 32 consecutive cells of the dense list: it
@@ -24,13 +24,14 @@
 // the logits would carry a relative error of ~2^-16 per product against the 8 x float32-noise bound the planes are held to.
 // Every value of a cell is computed by the same instructions in the same order wherever the cell sits in the dense list: a plane entry
 // depends on its own utterance only.  Cells outside an utterance's rectangle are 0 in both planes (a memset before the joint kernel).
-#include "rnnt_common.h"
+#include "decode_common.h"
 
 #include <cmath>
 
 int ec_fail(const char* msg);
 
 using namespace ecrnnt;
+using namespace ecdec;
 
 namespace {
 
@@ -40,25 +41,6 @@ constexpr int MAXC = 16;         // utterances per prediction-network workgroup 
 constexpr int CT = 32;           // cells per joint workgroup: two column groups
 constexpr int ZPAD = 4;          // floats between z rows: the 16 lanes of a k-slot read 16 different bank quads
 constexpr int MAXU = 1023;
-
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct LatLayout {
-    size_t tlen, ulen, start, h, gd, fe, total;     // byte offsets
-};
-
-LatLayout lat_layout(const EcRnntConfig& c, int batch, int t_out, int u_max) {
-    LatLayout L{};
-    size_t o = 0;
-    L.tlen = o;  o = al256(o + (size_t)batch * 4);
-    L.ulen = o;  o = al256(o + (size_t)batch * 4);
-    L.start = o; o = al256(o + ((size_t)batch + 1) * 4);
-    L.h = o;     o = al256(o + (size_t)batch * (u_max + 1) * c.dim_decoder * 4);
-    L.gd = o;    o = al256(o + (size_t)batch * (u_max + 1) * c.dim_joint * 4);
-    L.fe = o;    o = al256(o + (size_t)batch * t_out * c.dim_joint * 4);
-    L.total = o + 256;                               // + 256: the caller's pointer is aligned up
-    return L;
-}
 
 size_t joint_lds_bytes(const EcRnntConfig& c) { return (size_t)CT * (c.dim_joint + ZPAD) * 4; }
 size_t pred_lds_bytes(const EcRnntConfig& c) { return (size_t)3 * MAXC * c.dim_decoder * 4; }
@@ -91,18 +73,10 @@ __global__ __launch_bounds__(PT) void rnnt_lattice_prep_kernel(const LatArgs a) 
     for (int i = 0; i < per; ++i) {
         const int b = tid * per + i;
         if (b >= B) break;
-        const long long tl = a.out_len[b], ul = a.target_len[b];
-        int Tb = tl < 0 ? 0 : (tl > a.T ? a.T : (int)tl);
-        int st = 0, U = 0;
-        if (ul < 0 || ul > a.umax) st = 2;
-        else {
-            U = (int)ul;
-            for (int u = 0; u < U; ++u) {
-                const int c = a.targets[(size_t)b * a.umax + u];
-                if (c < 1 || c >= a.w.V) st = 2;
-            }
-        }
-        if (st == 2) { U = 0; Tb = 0; }              // no cells: the planes' rows stay 0
+        int Tb = clamp_len(a.out_len[b], a.T);
+        int st = transcript_status(a.target_len[b], a.umax, a.targets + (size_t)b * a.umax, a.w.V);
+        int U = st ? 0 : (int)a.target_len[b];
+        if (st == 2) Tb = 0;                         // no cells: the planes' rows stay 0
         else if (Tb == 0 && U > 0) st = 1;
         a.status[b] = st; a.tlen[b] = Tb; a.ulen[b] = U;
         sum += Tb * (U + 1);
@@ -125,6 +99,19 @@ __global__ __launch_bounds__(PT) void rnnt_lattice_prep_kernel(const LatArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- prediction network
+// lstm_step16's view of one utterance column: c in LDS (natural order), h into the other half of the LDS double buffer (k-permuted) and, for an utterance of the
+// batch, into the workspace row of this step.  (column, unit) belongs to one lane alone.
+struct PredColumn {
+    const float* gin; float* c; float* hn; float* out;
+    static constexpr bool live = true;
+    __device__ __forceinline__ float c_old(int unit) const { return c[unit]; }
+    __device__ __forceinline__ void put(int unit, float h, float cv) const {
+        c[unit] = cv;
+        hn[kperm(unit)] = h;
+        if (out) out[unit] = h;
+    }
+};
+
 __global__ __launch_bounds__(PT) void rnnt_prednet_kernel(const LatArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const RnntDev& w = a.w;
@@ -145,38 +132,22 @@ __global__ __launch_bounds__(PT) void rnnt_prednet_kernel(const LatArgs a) {
             s_y[u & 1][tid] = y;
         }
         __syncthreads();                             // s_y, and the previous step's h
-        const float* hp = hx[u & 1];
-        float* hn = hx[(u + 1) & 1];
-        for (int ub = wave; ub < H / 16; ub += PNW) {
-            int nrow[4];
-            f32x4 acc[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { nrow[q] = q * H + 16 * ub + j; acc[q] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-            mfma_rows16_any<4>(w.whh16, 4 * H, H / 16, nrow, hp + j * H + 4 * g, acc);
-            const float* gin = w.gin + (size_t)s_y[u & 1][j] * 4 * H;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {            // row 4 g + e of the tiles = hidden unit, column j = utterance
-                const int unit = 16 * ub + 4 * g + e;
-                const float ig = sigmoid_precise(acc[0][e] + gin[unit]), fg = sigmoid_precise(acc[1][e] + gin[H + unit]);
-                const float gg = tanhf(acc[2][e] + gin[2 * H + unit]), og = sigmoid_precise(acc[3][e] + gin[3 * H + unit]);
-                const float c = fg * sc[j * H + unit] + ig * gg;
-                const float hv = og * tanhf(c);
-                sc[j * H + unit] = c;                // (j, unit) belongs to this lane alone
-                hn[j * H + kperm(unit)] = hv;
-                if (live) a.h[((size_t)bj * (a.umax + 1) + u) * H + unit] = hv;
-            }
-        }
+        const PredColumn col{w.gin + (size_t)s_y[u & 1][j] * 4 * H, sc + j * H, hx[(u + 1) & 1] + j * H,
+                             live ? a.h + ((size_t)bj * (a.umax + 1) + u) * H : nullptr};
+        for (int ub = wave; ub < H / 16; ub += PNW) lstm_step16(w, ub, hx[u & 1] + j * H + 4 * g, col);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- joint lattice
-// running (max, sum exp) of a cell's logits: merge of two partial results; an empty part is (-inf, 0)
-__device__ __forceinline__ void ms_merge(float& m, float& s, float om, float os) {
-    const float nm = fmaxf(m, om);
-    const float ea = m == -INFINITY ? 0.f : expf(m - nm), eb = om == -INFINITY ? 0.f : expf(om - nm);
-    s = s * ea + os * eb;
-    m = nm;
-}
+// vocab_lse_tiles' pick of the lane's two cells j and 16 + j: the blank entry and each cell's label entry
+struct LatticePick {
+    float* blank; float* label; int y0, y1;          // this lane's slots of s_blank / s_label (the second cell's are 16 further)
+    __device__ __forceinline__ void operator()(int n, float v0, float v1) const {
+        if (n == 0) { blank[0] = v0; blank[16] = v1; }
+        if (n == y0) label[0] = v0;
+        if (n == y1) label[16] = v1;
+    }
+};
 
 __global__ __launch_bounds__(PT) void rnnt_joint_kernel(const LatArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sz[];     // [CT][J + ZPAD] z, k-permuted
@@ -192,12 +163,7 @@ __global__ __launch_bounds__(PT) void rnnt_joint_kernel(const LatArgs a) {
         const int c = c0 + tid;
         int b = -1, t = 0, u = 0, y = -1;
         if (c < total) {
-            int lo = 0, hi = a.B - 1;                // the last b with start[b] <= c (utterances without cells share a start)
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (a.start[mid] <= c) lo = mid; else hi = mid - 1;
-            }
-            b = lo;
+            b = ragged_find(a.start, a.B, c);        // the last b with start[b] <= c (utterances without cells share a start)
             const int r = c - a.start[b], eu = a.ulen[b] + 1;
             t = r / eu; u = r - t * eu;
             y = u < a.ulen[b] ? a.targets[(size_t)b * a.umax + u] : -1;
@@ -221,98 +187,10 @@ __global__ __launch_bounds__(PT) void rnnt_joint_kernel(const LatArgs a) {
     }
     __syncthreads();
     // ---- logits tile by tile: wave `wave` owns the tile pairs wave, wave + 8, ..; acc[i][c] = tile i of the pair x column group c
-    const int ntile = (V + 15) / 16;
-    const size_t bs = (size_t)4 * V;                 // float4s per 16-block of the weight image: [g][n]
-    const float* x0 = sz + j * P + 4 * g;
-    const float* x1 = sz + (16 + j) * P + 4 * g;
-    const int y0 = s_y[j], y1 = s_y[16 + j];
-    float m0 = -INFINITY, m1 = -INFINITY, r0 = 0.f, r1 = 0.f;     // the lane's running (max, sum) of cells j and 16 + j
-    for (int tp = wave; 2 * tp < ntile; tp += PNW) {
-        const float4* wp[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int n = 16 * (2 * tp + i) + j;
-            wp[i] = w.wj16 + (size_t)g * V + (n < V ? n : V - 1);     // clamped: rows at or beyond V are masked below
-        }
-        f32x4 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float4 wc[2][2], wn[2][2];                   // [16-block of the pair in flight][tile]
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) wc[q][i] = wp[i][(size_t)(q < K16 ? q : K16 - 1) * bs];
-        for (int q0 = 0; q0 < K16; q0 += 2) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int qn = q0 + 2 + q < K16 ? q0 + 2 + q : K16 - 1;      // past the end: a harmless re-load
-#pragma unroll
-                for (int i = 0; i < 2; ++i) wn[q][i] = wp[i][(size_t)qn * bs];
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                if (q0 + q < K16) {
-                    const float4 xa = *reinterpret_cast<const float4*>(x0 + 16 * (q0 + q));
-                    const float4 xb = *reinterpret_cast<const float4*>(x1 + 16 * (q0 + q));
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].x, xa.x, acc[i][0], 0, 0, 0);
-                        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].x, xb.x, acc[i][1], 0, 0, 0);
-                        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].y, xa.y, acc[i][0], 0, 0, 0);
-                        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].y, xb.y, acc[i][1], 0, 0, 0);
-                        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].z, xa.z, acc[i][0], 0, 0, 0);
-                        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].z, xb.z, acc[i][1], 0, 0, 0);
-                        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].w, xa.w, acc[i][0], 0, 0, 0);
-                        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wc[q][i].w, xb.w, acc[i][1], 0, 0, 0);
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int i = 0; i < 2; ++i) wc[q][i] = wn[q][i];
-        }
-        // ---- epilogue of the pair: row 4 g + e of tile i = vocabulary entry n, column j = cell
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int nb = 16 * (2 * tp + i) + 4 * g;
-            float v0[4], v1[4];
-            float t0 = -INFINITY, t1 = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int n = nb + e;
-                const float bias = w.bj[n < V ? n : V - 1];
-                v0[e] = n < V ? (acc[i][0][e] + bias) / a.tmp : -INFINITY;
-                v1[e] = n < V ? (acc[i][1][e] + bias) / a.tmp : -INFINITY;
-                t0 = fmaxf(t0, v0[e]); t1 = fmaxf(t1, v1[e]);
-                if (n == 0) { s_blank[j] = v0[e]; s_blank[16 + j] = v1[e]; }
-                if (n == y0) s_label[j] = v0[e];
-                if (n == y1) s_label[16 + j] = v1[e];
-            }
-            if (nb < V) {                            // at least one entry: nb itself
-                float p0 = 0.f, p1 = 0.f;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { p0 += expf(v0[e] - t0); p1 += expf(v1[e] - t1); }     // exp(-inf) = 0 for the masked entries
-                ms_merge(m0, r0, t0, p0);
-                ms_merge(m1, r1, t1, p1);
-            }
-        }
-    }
-    // ---- merge the k-slots of the wave (g = 0 + 1, 2 + 3, then the two halves), then the waves in order
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-        const float om0 = __shfl_xor(m0, o), os0 = __shfl_xor(r0, o), om1 = __shfl_xor(m1, o), os1 = __shfl_xor(r1, o);
-        if (!(lane & o)) { ms_merge(m0, r0, om0, os0); ms_merge(m1, r1, om1, os1); }
-    }
-    if (g == 0) { s_m[wave][j] = m0; s_s[wave][j] = r0; s_m[wave][16 + j] = m1; s_s[wave][16 + j] = r1; }
-    __syncthreads();
+    float ms[4];                                     // the lane's running (max, sum) of cells j and 16 + j
+    vocab_lse_tiles<2, PNW>(w.wj16, w.bj, V, K16, sz + j * P + 4 * g, sz + (16 + j) * P + 4 * g, a.tmp, LatticePick{s_blank + j, s_label + j, s_y[j], s_y[16 + j]}, ms);
+    const float lse = vocab_lse_merge<PNW>(ms, s_m, s_s);
     if (tid < CT && s_b[tid] >= 0) {
-        float m = s_m[0][tid], s = s_s[0][tid];
-#pragma unroll
-        for (int q = 1; q < PNW; ++q) ms_merge(m, s, s_m[q][tid], s_s[q][tid]);
-        const float lse = m + logf(s);
         const size_t o = ((size_t)s_b[tid] * a.T + s_t[tid]) * E + s_u[tid];
         a.lpb[o] = s_blank[tid] - lse;
         a.lpl[o] = s_y[tid] >= 0 ? s_label[tid] - lse : -INFINITY;
@@ -342,7 +220,7 @@ int effconf_rnnt_lattice(EcRnnt* r, const float* enc_out, const int64_t* out_len
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_rnnt_lattice_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
     const int H = r->cfg.dim_decoder, J = r->cfg.dim_joint, De = r->cfg.dim_encoder, E = u_max + 1;
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    char* ws = WsPlan::base(workspace);
     LatArgs a{};
     a.w = r->dev; a.out_len = out_len; a.target_len = target_len; a.targets = targets;
     a.B = batch; a.T = t_out; a.umax = u_max; a.tmp = temperature;

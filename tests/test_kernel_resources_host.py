@@ -1,4 +1,5 @@
-"""Compile-time resources of the stage-2 / stage-3 chain kernels and of the head-width-64 attention kernel (no GPU: hipcc cross-compiles for gfx950).
+"""Compile-time resources of the stage-2 / stage-3 chain kernels, of the head-width-64 attention kernel and of the decoder kernels (no GPU: hipcc cross-compiles
+for gfx950).
 
 A scratch reload inside one of these kernels waits on the vmcnt queue its own prefetches are in (LDS-DMAs of the weight ring, the K / V / E loads one key block
 ahead): the reload of a spilled lane constant drains what was just issued.  The kernels are kept free of scratch altogether; their occupancy (waves per SIMD) is
@@ -92,6 +93,25 @@ SCRATCH_BOUNDED = [
     ("chain.hip", "chain_kernel<12, 8, 3, 1, false>", 2, 96),
     ("chain.hip", "chain_kernel<12, 8, 3, 3, false>", 2, 84),
 ]
+# the decoders: the occupancies their kernels had before the LSTM cell, the 16-column LSTM step and the vocabulary log-softmax loop moved into decode_common.h
+# (profiles/decoder_common.txt has the registers before and after), and no scratch
+DECODERS = [
+    ("rnnt.hip", "rnnt_greedy_kernel", 4, 0),
+    ("rnnt.hip", "rnnt_cluster_kernel<8, 8, 2>", 2, 0),
+    ("rnnt.hip", "rnnt_cluster_kernel<16, 16, 1>", 2, 0),
+    ("rnnt_beam.hip", "rnnt_beam_kernel", 4, 0),
+    ("rnnt_lattice.hip", "rnnt_prednet_kernel", 5, 0),
+    ("rnnt_lattice.hip", "rnnt_joint_kernel", 6, 0),
+    ("lm.hip", "lm_lstm_step_kernel<4>", 2, 0),
+    ("lm.hip", "lm_lstm_step_kernel<2>", 4, 0),
+    ("lm.hip", "lm_lstm_step_kernel<1>", 7, 0),
+    ("lm.hip", "lm_head_kernel<false>", 8, 0),
+    ("lm.hip", "lm_head_kernel<true>", 8, 0),
+    ("ctc_beam.hip", "ctc_beam_kernel", 4, 0),
+    ("ctc_align.hip", "ctc_trellis_kernel<16, true>", 4, 0),
+    ("ctc_align.hip", "ctc_trellis_kernel<16, false>", 6, 0),
+]
+STAY_AT_ZERO = STAY_AT_ZERO + DECODERS
 
 
 @pytest.mark.parametrize("source,kernel,occupancy,scratch", BROUGHT_TO_ZERO + STAY_AT_ZERO, ids=[k for _, k, _, _ in BROUGHT_TO_ZERO + STAY_AT_ZERO])
