@@ -564,6 +564,21 @@ struct ClusterShape {
 using ShapeA = ClusterShape<8, 8, 2>;
 using ShapeB = ClusterShape<16, 16, 1>;
 
+// Which kernel decodes `batch` utterances: 0 rnnt_greedy_kernel (one workgroup per utterance), 1 ShapeA, 2 ShapeB - the one decision of effconf_rnnt_greedy, and
+// what effconf_rnnt_greedy_route reports.  A cluster shape runs when the config allows it and either it is forced (cluster_decode = 1, every workgroup resident:
+// at most 256) or - auto - the batch fills two of its clusters and all its workgroups are resident (by-cluster mapping: at most half of the CUs: two decodes on
+// two streams must not starve each other's cluster-mates, a spinning workgroup keeps its CU; by-slice mapping: a cluster is CW CONSECUTIVE workgroups, whatever
+// part of a launch is resident consists of whole clusters plus at most one split at the dispatch frontier, so a launch may use every CU).
+// cluster_shape = 1 asks for ShapeB first; where ShapeB does not run (config or batch) the decision is cluster_shape = 0's.  A forced ShapeA is returned whatever
+// the batch: beyond 256 utterances the launch refuses (no quiet per-utterance decode of a forced cluster decode).
+int greedy_route(const EcRnntConfig& c, int cluster_mode, int cluster_shape, int by_slice, int batch) {
+    if (cluster_mode == 0 || batch <= 0) return 0;
+    auto fits = [&](int cw, int cu) { return batch >= 2 * cu && ((batch + cu - 1) / cu) * cw <= (by_slice ? 256 : 128); };
+    if (cluster_shape == 1 && ShapeB::supported(c) && (cluster_mode == 1 ? ((batch + 15) / 16) * 16 <= 256 : fits(16, 16))) return 2;
+    if (ShapeA::supported(c) && (cluster_mode == 1 || fits(8, 8))) return 1;
+    return 0;
+}
+
 using HostT = EcRnntHostT;
 
 // W [N][K] row-major -> float4 image [K/4][N]
@@ -663,13 +678,22 @@ int effconf_rnnt_set_option(EcRnnt* r, const char* name, int32_t value) {
     if (!r || !name) return ec_fail("null argument");
     if (!strcmp(name, "cluster_decode")) { r->cluster_mode = value; return 0; }
     if (!strcmp(name, "cluster_by_slice")) { r->cluster_by_slice = value != 0; return 0; }
-    if (!strcmp(name, "cluster_shape")) { r->cluster_shape = value; return 0; }
+    if (!strcmp(name, "cluster_shape")) {
+        if (value < -1 || value > 1) return ec_fail("cluster_shape must be -1 (default), 0 or 1");
+        r->cluster_shape = value;
+        return 0;
+    }
     if (!strcmp(name, "beam_eval_batch")) {
         if (value < 1 || value > 16) return ec_fail("beam_eval_batch must be 1 .. 16");
         r->beam_eval_batch = value;
         return 0;
     }
     return ec_fail("unknown option");
+}
+
+int effconf_rnnt_greedy_route(const EcRnnt* r, int32_t batch) {
+    if (!r) return ec_fail("null handle");
+    return greedy_route(r->cfg, r->cluster_mode, r->cluster_shape, r->cluster_by_slice, batch);
 }
 
 int32_t effconf_rnnt_max_tokens(const EcRnnt* r, int32_t t_out) {
@@ -691,10 +715,6 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
     float* fe = reinterpret_cast<float*>(ws + ShapeA::layout(r->cfg, batch, t_out).fe);
     // linear_encoder(f) for every frame of the batch, once (joint_networks.py:82 recomputes it per decision)
     if (launch_sgemm_nt(enc_out, De, r->we, De, r->be, fe, J, batch * t_out, J, De, s) != 0) return ec_fail("linear_encoder GEMM launch failed");
-    // auto: clusters only while they need at most half of the CUs with the by-cluster mapping (two decodes on two streams must not starve
-    // each other's cluster-mates: a spinning workgroup keeps its CU).
-    // With the by-slice mapping a cluster is 8 CONSECUTIVE workgroups: whatever part of a launch is resident consists of whole clusters plus
-    // at most one split at the dispatch frontier, so decodes sharing the GPU cannot starve each other and a launch may use every CU.
     auto run_cluster = [&](auto shape, auto cw_c, auto cu_c, auto ckf_c) -> int {
         using Shape = decltype(shape);
         constexpr int CW = decltype(cw_c)::value, CU = decltype(cu_c)::value, CKF = decltype(ckf_c)::value;
@@ -716,14 +736,9 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
         hipLaunchKernelGGL((rnnt_cluster_kernel<CW, CU, CKF>), dim3(ncl * CW), dim3(CNT), lds, s, a);
         return hipGetLastError() == hipSuccess ? 0 : ec_fail("rnnt cluster launch failed");
     };
-    // a cluster shape runs when the batch fills two of its clusters and all its workgroups are resident (by-cluster mapping: at most half of the CUs)
-    auto fits = [&](int cw, int cu) { return batch >= 2 * cu && ((batch + cu - 1) / cu) * cw <= (r->cluster_by_slice ? 256 : 128); };
-    if (r->cluster_mode != 0) {
-        const bool okB = ShapeB::supported(r->cfg) && r->cluster_shape == 1 && (r->cluster_mode == 1 ? ((batch + 15) / 16) * 16 <= 256 : fits(16, 16));
-        const bool okA = ShapeA::supported(r->cfg) && r->cluster_shape != 1 && (r->cluster_mode == 1 || fits(8, 8));
-        if (okB) return run_cluster(ShapeB{}, std::integral_constant<int, 16>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, 1>{});
-        if (okA) return run_cluster(ShapeA{}, std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
-    }
+    const int route = greedy_route(r->cfg, r->cluster_mode, r->cluster_shape, r->cluster_by_slice, batch);
+    if (route == 2) return run_cluster(ShapeB{}, std::integral_constant<int, 16>{}, std::integral_constant<int, 16>{}, std::integral_constant<int, 1>{});
+    if (route == 1) return run_cluster(ShapeA{}, std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{}, std::integral_constant<int, 2>{});
     const size_t lds = (size_t)(2 * H + 4 * H + J + KF * J + 2 * KF * (NT / 64)) * 4;
     hipLaunchKernelGGL(rnnt_greedy_kernel, dim3(batch), dim3(NT), lds, s, r->dev, fe, out_len, t_out, tokens, token_len, max_tokens);
     return hipGetLastError() == hipSuccess ? 0 : ec_fail("rnnt_greedy launch failed");

@@ -280,8 +280,13 @@ int32_t effconf_rnnt_max_tokens(const EcRnnt* r, int32_t t_out);
  * share the GPU cannot starve each other); 0: the members of a cluster share an XCD and must all be resident - auto then stops at 128
  * utterances.  The spin is bounded: a starved cluster gives up with undefined tokens instead of hanging.  All paths produce identical
  * tokens.  "cluster_shape" (round 6): 0 (default) clusters of 8 workgroups x 8 utterances x 2 encoder frames per joint pass, 1 = 16 x 16 x 1 where the
- * decoder / joint widths leave LDS for it (<= 768; half the weight bytes per round - measured no faster: profiles/r6_33_rnnt_cluster_shapes.txt). */
+ * decoder / joint widths leave LDS for it (<= 768; half the weight bytes per round - measured no faster: profiles/r6_33_rnnt_cluster_shapes.txt);
+ * where 16 x 16 x 1 does not run (config or batch) the decision is that of 0.  -1 = 0; any other value is refused. */
 int effconf_rnnt_set_option(EcRnnt* r, const char* name, int32_t value);
+/* The kernel effconf_rnnt_greedy runs for `batch` utterances under the config and the options set so far: 0 one workgroup per utterance,
+ * 1 clusters of 8 x 8 x 2, 2 clusters of 16 x 16 x 1 (-1: null handle).  Host only: needs neither finalize nor a device.  A forced cluster
+ * decode ("cluster_decode" = 1) of more than 256 utterances reports 1 and effconf_rnnt_greedy refuses it. */
+int effconf_rnnt_greedy_route(const EcRnnt* r, int32_t batch);
 int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len, int32_t batch, int32_t t_out,
                         int32_t* tokens, int32_t* token_len, int32_t max_tokens, void* workspace, size_t workspace_bytes,
                         void* stream);

@@ -42,8 +42,10 @@ def joint_logits(sd: Dict, f_t: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     return _t(sd, "joint_network.linear_joint.weight") @ torch.tanh(fe + gd) + _t(sd, "joint_network.linear_joint.bias")
 
 
-def greedy_decode(sd: Dict, f: torch.Tensor, f_len, max_consec_dec_step: int = 5, with_margins: bool = False):
+def greedy_decode(sd: Dict, f: torch.Tensor, f_len, max_consec_dec_step: int = 5, with_margins: bool = False, dtype=None):
     """Transducer.gready_search_decoding (reference models/transducer.py:139-186) on encoder outputs f (B, T, Denc).
+    ``dtype`` (None: the weights' own): weights, encoder outputs and the LSTM state are evaluated in it - torch.float64 is the high-precision
+    reference of the kernels' float32 arithmetic.
 
     Per utterance: start token 0 and zero LSTM state (151-152); the decoder advances only after an emitted token (159);
     a decision is the argmax of the joint logits (164: softmax().log().argmax() has the same argmax); blank (0) or
@@ -52,11 +54,15 @@ def greedy_decode(sd: Dict, f: torch.Tensor, f_len, max_consec_dec_step: int = 5
     the smallest top-2 logit margin seen per utterance."""
     out: List[List[int]] = []
     margins: List[float] = []
-    hd = _t(sd, "decoder.rnn.weight_hh_l0").shape[1]
+    if dtype is not None:
+        sd = {k: _t(sd, k).to(dtype) for k in sd if k.startswith(("decoder.", "joint_network."))}
+        f = f.to(dtype)
+    whh = _t(sd, "decoder.rnn.weight_hh_l0")
+    hd = whh.shape[1]
     with torch.no_grad():
         for b in range(f.shape[0]):
             y: List[int] = [0]
-            h, c = torch.zeros(hd), torch.zeros(hd)
+            h, c = torch.zeros(hd, dtype=whh.dtype), torch.zeros(hd, dtype=whh.dtype)
             enc_step, consec, worst = 0, 0, float("inf")
             n = int(f_len[b])
             while enc_step < n:

@@ -18,21 +18,22 @@ import torch
 from oracle.ref_transducer import joint_logits, lstm_step
 
 
-def _sd64(sd: Dict) -> Dict[str, torch.Tensor]:
-    return {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)).to(torch.float64)
+def _sd64(sd: Dict, dtype=torch.float64) -> Dict[str, torch.Tensor]:
+    return {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(v)).to(dtype)
             for k, v in sd.items() if k.startswith(("decoder.", "joint_network."))}
 
 
-def beam_decode(sd: Dict, f: torch.Tensor, f_len, beam: int, tmp: float = 1.0, max_expansions: Optional[int] = None):
+def beam_decode(sd: Dict, f: torch.Tensor, f_len, beam: int, tmp: float = 1.0, max_expansions: Optional[int] = None, dtype=torch.float64):
     """-> list (one per utterance) of dicts: tokens (without the start token), score (float64 logp_score of the answer),
-    expansions (pops per frame), capped (True when a frame needed more than max_expansions pops; tokens then [])."""
-    sd = _sd64(sd)
+    expansions (pops per frame), capped (True when a frame needed more than max_expansions pops; tokens then []).
+    dtype: torch.float32 evaluates the same program in float32 (what the reference's own rounding does to it)."""
+    sd = _sd64(sd, dtype)
     hd = sd["decoder.rnn.weight_hh_l0"].shape[1]
-    f = f.to(torch.float64)
+    f = f.to(dtype)
     out = []
     with torch.no_grad():
         for b in range(f.shape[0]):
-            zero = (torch.zeros(hd, dtype=torch.float64), torch.zeros(hd, dtype=torch.float64))
+            zero = (torch.zeros(hd, dtype=dtype), torch.zeros(hd, dtype=dtype))
             # a hypothesis: prediction, score, state (h, c) the decoder runs from, and the memo of that decoder step (a blank child
             # keeps its parent's prediction and state, so its decoder output is the parent's)
             B = [{"pred": [0], "score": 0.0, "state": zero, "dec": None}]

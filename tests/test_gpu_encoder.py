@@ -423,13 +423,19 @@ def test_rnnt_cluster_decode_equals_per_utterance_decode(golden_dir, name, tag, 
     f = f0[rows].clone()
     lens = torch.tensor([max(0, int(l0[r]) - 3 * (i // f0.shape[0])) for i, r in enumerate(rows)])   # ragged, incl. repeated golden rows
     f, lens = f.cuda(), lens.cuda()
+    from efficientconformer_amd import _lib
+    route_of = _lib.load().effconf_rnnt_greedy_route
     m.set_decode_option("cluster_decode", 0)
+    assert route_of(m._rnnt, nb) == 0
     ref_t, ref_n = m.decode_encoded(f, lens)
     m.set_decode_option("cluster_decode", 1)
     for shape in (0, 1):                              # 8 workgroups x 8 utterances x 2 frames per joint pass / 16 x 16 x 1 (round 6: half the weight bytes per round)
         m.set_decode_option("cluster_shape", shape)
         for by_slice in (0, 1):                       # workgroup -> XCD mapping: a cluster on one XCD / slice k of every cluster on XCD k
             m.set_decode_option("cluster_by_slice", by_slice)
+            # Medium runs the cluster kernel it is asked for.  TinyTransducer (H = 32: no cluster shape takes it) runs route 0, the per-utterance kernel, under
+            # every option: its cases compare that kernel with itself (tests/test_gpu_rnnt_shapes.py runs the cluster kernels at small widths)
+            assert route_of(m._rnnt, nb) == (0 if name == "TinyTransducer" else shape + 1), (name, shape, by_slice)
             got_t, got_n = m.decode_encoded(f, lens)
             assert torch.equal(got_n, ref_n) and torch.equal(got_t, ref_t), (shape, by_slice)
     m.set_decode_option("cluster_shape", -1)
@@ -438,6 +444,7 @@ def test_rnnt_cluster_decode_equals_per_utterance_decode(golden_dir, name, tag, 
         want = g["tokens_" + tag][offs[b]:offs[b + 1]].tolist()
         assert got_t[b, :int(got_n[b])].tolist() == want
     m.set_decode_option("cluster_decode", -1)
+    assert route_of(m._rnnt, nb) == (0 if name == "TinyTransducer" else 1)       # auto: 8 x 8 x 2 from 16 utterances
     auto_t, auto_n = m.decode_encoded(f, lens)
     assert torch.equal(auto_t, ref_t) and torch.equal(auto_n, ref_n)
 
