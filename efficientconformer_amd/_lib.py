@@ -114,6 +114,7 @@ DEBUG_SIGNATURES = {
     "effconf_debug_dwconv": (C.c_int, [_P, _I32, _I32, _I32, _I32, _F32P, _F32P, _I32, _I32, _I32, _I32, _P, _P]),
     "effconf_debug_pack_digest": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "effconf_debug_routes": (C.c_int, [_P, _I32, C.c_char_p, _SZ]),
+    "effconf_debug_relpos_attention": (C.c_int, [_P, _P, _P, _P, _F32P, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _SZ, _P]),
     "effconf_debug_gemm": (C.c_int, [_P, _I32, _P, _I32, _P, _I32, _I32, _I32, _I32, _I32, _P, _I32, _P, _I32, C.c_float, _P]),
 }
 

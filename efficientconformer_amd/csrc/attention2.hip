@@ -34,8 +34,12 @@ constexpr int SKEW_LD = 68;     // floats per query row of a skew buffer: the 64
                                 // applied by the WRITER (band position -> key column), rows are 64 instead of 80 + 4 floats: 52 KB of LDS at head width 64 - three
                                 // workgroups per CU fit (56 KB: two)
 constexpr float RESCALE_T = 4.0f;   // deferred accumulator rescale: threshold on the growth of a row maximum, log2 units
-constexpr float NEG_BIG = -1.0e30f;  // masked score / initial row maximum: finite, so that (max - max) never becomes inf - inf; whatever a row
-                                     // accumulates while its maximum still is NEG_BIG is wiped by the first real score (alpha = exp2(-huge) = 0)
+constexpr float NEG_BIG = -0x1p100f; // masked score / initial row maximum: finite, so that (max - max) never becomes inf - inf; whatever a row
+                                     // accumulates while its maximum still is NEG_BIG is wiped by the first real score (alpha = exp2(-huge) = 0).
+                                     // A POWER OF TWO: NEG_BIG * scale2 is then exact, so fmaf(NEG_BIG, scale2, -NEG_BIG * scale2) is 0 and such a row accumulates
+                                     // p = 1 on finite V.  With -1e30 the rounded product left a residual of +-1e21: exp2 = inf at head widths 30, 45, 64, 96, 160, 192
+                                     // (0 by luck at 32, 42, 60, 90, 128, 135), and inf * alpha = NaN in every row whose FIRST visited key block held no visible key -
+                                     // any band_l < 64 from the second query tile on, or a dead tile's live rows (tests/test_gpu_attention_edges.py)
 
 __device__ __forceinline__ uint4 ld16(const bf16_t* p) {       // 16-byte global load from a 2-byte aligned address (natural layout, odd d)
     typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(2)));

@@ -94,6 +94,63 @@ int effconf_debug_routes(EcEncoder* e, int32_t ragged, char* text, size_t cap) {
     return 0;
 }
 
+int effconf_debug_relpos_attention(const uint16_t* qu, const uint16_t* k, const uint16_t* v, const uint16_t* e, const float* dvu, int32_t dvu_ld,
+                                   const int64_t* lens_dev, const int64_t* lens_host, int32_t batch, int32_t heads, int32_t frames, int32_t group, int32_t dim,
+                                   uint16_t* out, int32_t ld_out, int32_t variant, int32_t band_l, int32_t band_r, int32_t causal, int32_t ragged,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (!qu || !k || !v || !e || !dvu || !lens_dev || !lens_host || !out || !workspace) return fail("null argument");
+    if (batch <= 0 || heads <= 0 || frames <= 0 || group <= 0 || !(group & 1) || dim <= 0 || (group * dim) % heads) return fail("bad attention shape");
+    const int Tp = ec_round_up(frames, group), Tg = Tp / group, d = group * dim / heads, dpad = ec_round_up(d, 32);
+    if (dpad > 192 || dvu_ld < dpad || ld_out < dim) return fail("unsupported head width / leading dimension");
+    if (variant < 0 || variant > 2) return fail("attention variant: 0, 1 or 2");
+    if (band_l < 0 || band_r < 0) return fail("band_l / band_r: grouped positions >= 0 (>= Tg: unlimited)");
+    if (causal && band_r != 0) return fail("causal attention: band_r must be 0 (the kernel masks j > i through the band only)");
+    // ---- the forward's route under option attention_v2 = variant (forward_bf16.hip), refusals included: all of it before the first HIP call
+    const bool rg = ragged != 0, streaming = causal || band_l < Tg || band_r < Tg;
+    EcEncoder opt;
+    opt.attention_v2 = variant;
+    const AttentionRoute ar = attention_route(&opt, dpad, rg, streaming);
+    if (ar.refusal) return fail(ar.refusal);
+    if (ar.waves != variant)
+        return fail("the forward's route runs another kernel than the variant asked for (attention_route: streaming and ragged batches on attention2.hip variant 1, padded head width 192 on attention.hip)");
+    if (workspace_bytes < ((size_t)7 * batch + 8) * 4) return fail("workspace too small");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int* wsi = reinterpret_cast<int*>(workspace);
+
+    AttnParams ap{};
+    ap.qu = qu; ap.kh = k; ap.vt = v; ap.eh = e; ap.dvu = dvu; ap.dvu_ld = dvu_ld;
+    ap.B = batch; ap.H = heads; ap.T = frames; ap.G = group; ap.D = dim; ap.d = d; ap.dpad = dpad; ap.Tg = Tg; ap.Tgp = ec_round_up(Tg, 8);
+    ap.q_bstride = (long long)Tp * dim; ap.q_hstride = d; ap.q_rowstride = group * dim; ap.e_hstride = d; ap.e_rowstride = group * dim;
+    ap.out = out; ap.ldo = ld_out; ap.scale = 1.0f / std::sqrt((float)d);
+    ap.band_l = band_l; ap.band_r = band_r; ap.causal = causal ? 1 : 0;
+    if (rg) {
+        // the descriptors of begin_forward (forward_common.h) for an encoder of ONE block without subsampling; the host totals as make_shapes_ragged takes them
+        int tmax = 0, nwg = 0;
+        for (int b = 0; b < batch; ++b) {
+            if (lens_host[b] < 0 || lens_host[b] > frames) return fail("ragged lengths: 0 .. frames");
+            tmax = std::max(tmax, (int)lens_host[b]);
+            nwg += heads * ec_cdiv(ec_round_up((int)lens_host[b], group) / group, 64);
+        }
+        if (tmax != frames) return fail("ragged batch: frames = the longest utterance (the positional rows are built for it)");
+        int* cfg = wsi;                                            // block_stride, group, heads of the one block
+        int* lens = cfg + 4;                                       // [2][batch]: entering / leaving the block
+        int* mel_len = lens + 2 * batch;
+        int* row_off = mel_len + batch;                            // [2][batch + 1]
+        int* wg_off = row_off + 2 * (batch + 1);
+        int* tile_off = wg_off + (batch + 1);
+        const int host_cfg[3] = {1, group, heads};
+        if (hipMemcpyAsync(cfg, host_cfg, sizeof(host_cfg), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail("copy failed");
+        EC_TRY(launch_lengths_ragged(lens_dev, batch, 0, 1, 0, cfg, cfg + 1, cfg + 2, 1, lens, mel_len, row_off, wg_off, tile_off, nullptr, st));
+        ap.lens = lens; ap.rag_off = row_off; ap.rag_wg = wg_off; ap.rag_nwg = nwg; ap.rag_tgmax = Tg;
+    } else {
+        EC_TRY(launch_lengths(lens_dev, batch, 0, 1, 0, nullptr, 0, wsi, nullptr, st));
+        ap.lens = wsi;
+    }
+    if (ar.waves) EC_TRY(launch_relpos_attention2(ap, ar.waves, st));
+    else EC_TRY(launch_relpos_attention(ap, st));
+    return 0;
+}
+
 int effconf_debug_mel(EcEncoder* e, int32_t variant, int32_t extra_lds, const float* audio, int32_t batch, int32_t n_samples, float* mel,
                       uint32_t* counters, void* stream) {
     if (!e || !e->finalized) return fail("encoder not finalized");

@@ -418,7 +418,7 @@ int effconf_relpos_attention(const uint16_t* qu, const uint16_t* k, const uint16
     ap.B = batch; ap.H = heads; ap.T = frames; ap.G = group; ap.D = dim; ap.d = d; ap.dpad = dpad; ap.Tg = Tg; ap.Tgp = ec_round_up(Tg, 8);
     ap.q_bstride = (long long)Tp * dim; ap.q_hstride = d; ap.q_rowstride = group * dim; ap.e_hstride = d; ap.e_rowstride = group * dim;
     ap.out = out; ap.ldo = ld_out; ap.scale = 1.0f / std::sqrt((float)d);
-    ap.band_l = ap.band_r = 1 << 30;          // full context (the streaming variants are tested end to end against the reference goldens)
+    ap.band_l = ap.band_r = 1 << 30;          // full context, rectangular; bands, causal tables and ragged batches: effconf_debug_relpos_attention (tests/test_gpu_attention_edges.py)
     if (variant == 0) { EC_TRY(launch_relpos_attention(ap, (hipStream_t)stream)); return 0; }
     if ((variant != 1 && variant != 2) || !relpos_attention2_supported(dpad)) return fail("attention variant not available for this head width");
     EC_TRY(launch_relpos_attention2(ap, variant, (hipStream_t)stream));

@@ -72,6 +72,22 @@ int effconf_debug_pack_digest(EcEncoder* enc, uint64_t* digest, int64_t* buffers
  * b=<chain|modules> tail=<full|tail|modules> ffn2=<fused|ln+gemms|->" (attention of the per-module family: for a batch of one utterance). */
 int effconf_debug_routes(EcEncoder* enc, int32_t ragged, char* text, size_t cap);
 
+/* The attention kernels alone over the whole AttnParams contract (csrc/kernels.h; tests/test_gpu_attention_edges.py): effconf_relpos_attention's operands and
+ * layout - qu / k / v dev bf16 rows of `dim` columns with the chunk-padding rows in place, e the positional rows [2 Tp - group][dim], dvu [heads][dvu_ld],
+ * out [rows][ld_out] - plus the streaming band, causal tables and ragged batches.  band_l / band_r: grouped positions, >= Tg = unlimited, passed on as they
+ * are; causal: e holds Tp rows (the non-negative distances) and band_r must be 0, as the forward's plan guarantees - the kernel masks j > i through the band only.
+ * lens_dev: dev int64 [batch] valid frames, lens_host: the same numbers on the host (as a forward gets both).  The int32 lengths the kernel reads are written
+ * into `workspace` (dev, (7 batch + 8) * 4 bytes) by the forward's own length kernels.
+ * ragged = 0: rows b * Tp + t, `frames` per utterance (keys behind lens[b] masked; every query row computed).
+ * ragged = 1: utterances concatenated, each padded to a multiple of `group`, every frame valid; frames = the longest length (e is built for it); the
+ *   descriptors rag_off / rag_wg come from launch_lengths_ragged as in a forward (one block, no subsampling), rag_nwg from lens_host.
+ * variant 0 attention.hip, 1 / 2 attention2.hip: routed through attention_route (csrc/routes.h) as under option attention_v2 = variant, so streaming or
+ * ragged with variant 0 or padded head width 192 is refused with the forward's text; a route that would run another variant than the one asked for is refused too. */
+int effconf_debug_relpos_attention(const uint16_t* qu, const uint16_t* k, const uint16_t* v, const uint16_t* e, const float* dvu, int32_t dvu_ld,
+                                   const int64_t* lens_dev, const int64_t* lens_host, int32_t batch, int32_t heads, int32_t frames, int32_t group, int32_t dim,
+                                   uint16_t* out, int32_t ld_out, int32_t variant, int32_t band_l, int32_t band_r, int32_t causal, int32_t ragged,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

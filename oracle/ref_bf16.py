@@ -350,21 +350,43 @@ def attention(qu: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: torch.Tenso
     envelope sum_j p_ij |v_j| of every output element.  ``plan``: an EncoderPlan with causal / streaming contexts (as ref_encoder.conformer_block).
     Tests only: ``exact_qv`` builds qv without its rounding, ``key_shift`` moves the key mask by that many groups."""
     pm = "blocks.%d.multi_head_self_attention_module.mhsa." % bp.index
-    qu, k, v, e = qu.to(dtype), k.to(dtype), v.to(dtype), e.to(dtype)
-    bsz, tp, dim = qu.shape
-    g, h = bp.group_size, bp.num_heads
     if rnd is ident:
-        qv = qu + (_w(sd, pm + "v", dtype) - _w(sd, pm + "u", dtype))
+        dvu = _w(sd, pm + "v", dtype) - _w(sd, pm + "u", dtype)
     else:
-        dvu = (_w(sd, pm + "v", torch.float32) - _w(sd, pm + "u", torch.float32)).to(dtype)
-        qv = qu + dvu if exact_qv else rnd(qu + dvu)
+        dvu = _w(sd, pm + "v", torch.float32) - _w(sd, pm + "u", torch.float32)
     ctx = {}
     if plan is not None and (plan.causal or plan.left_context < (1 << 30) or plan.right_context < (1 << 30)):
         ctx = dict(causal=plan.causal, left=plan.left_context, right=plan.right_context, mask_stride=bp.mask_stride)
+    return attention_operands(qu, k, v, e, dvu, lens, t, bp.num_heads, bp.group_size, dtype, rnd, round_p, exact_qv, key_shift, ctx)
+
+
+DEAD_ROW = -5e8     # a score row whose maximum lies below this carries the -1e9 of the mask on every key
+
+
+def attention_operands(qu: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: torch.Tensor, dvu: torch.Tensor, lens: Optional[torch.Tensor], t: int,
+                       heads: int, group: int, dtype, rnd: Callable = q, round_p: bool = False, exact_qv: bool = False, key_shift: int = 0,
+                       ctx: Optional[dict] = None, edit_scores: Optional[Callable] = None, dead_rows: str = "auto"):
+    """``attention`` on explicit operands: dvu (D,) = v - u as the kernel holds it (float32 numbers; rnd = ident: any), ``ctx`` the keyword arguments
+    relpos_scores takes for causal / streaming contexts.
+    Dead rows - queries whose every key is masked (the whole band in the padding; every query of an empty utterance): the reference adds -1e9 to every
+    score of the row in float32, which IS -1e9 for |s| < 32, so its softmax is uniform over all Tg key groups, the chunk-padding group included
+    (attentions.py:701; the kernels: attention2.hip ``tile_dead``).  float64 keeps s - 1e9 apart, so dead_rows = "auto" sets those rows' scores to 0 in
+    float64 runs and leaves float32 runs as they come out; "keep" never touches them (tests/test_attention_cases_host.py proves the two equal).
+    Tests only: ``edit_scores(s, again)`` returns the scores to use instead of s (B, H, Tg, Tg) - again(e=None, **ctx) evaluates relpos_scores on the same
+    operands with another table / other contexts - the hook the injected faults of tests/attention_cases.py go through."""
+    qu, k, v, e, dvu = qu.to(dtype), k.to(dtype), v.to(dtype), e.to(dtype), dvu.to(dtype)
+    bsz, tp, dim = qu.shape
+    g, h = group, heads
+    qv = qu + dvu if (rnd is ident or exact_qv) else rnd(qu + dvu)
+    ctx = dict(ctx or {})
     ml = lens
     if key_shift:
         ml = (lens if lens is not None else torch.full((bsz,), t)) + key_shift * g
     s = R.relpos_scores(qu, qv, k, e, ml, t, h, g, **ctx)
+    if edit_scores is not None:
+        s = edit_scores(s, lambda table=None, **kw: R.relpos_scores(qu, qv, k, e if table is None else table.to(dtype), ml, t, h, g, **dict(ctx, **kw)))
+    if dead_rows == "auto" and dtype == torch.float64:
+        s = torch.where(s.amax(-1, keepdim=True) < DEAD_ROW, torch.zeros_like(s), s)
     tg, d = tp // g, g * dim // h
     vh = v.reshape(bsz, tg, h, d).transpose(1, 2)
     pr = _exp(s - s.amax(-1, keepdim=True))

@@ -21,7 +21,7 @@ excluded by the row map and their count is asserted.  Each case prints the worst
 Routes: the fused chains (folded LayerNorm) wherever the stage width allows - asserted per block through `x_conv` being absent from the trace - in their
 2-wave and 8-wave forms (chain_small_m = 0 / 1 << 30, or the row count), chain3 / chain2 against chain.hip at padded width 256 (chain_pair = 5 / 0), the
 per-module kernels (fuse_chain = 0 and Medium's D = 360 stage), attention.hip and the VALU depthwise kernel (attention_v2 = 0, dwconv_mfma = 0; strided blocks
-always), one causal and one streaming configuration, synthetic and `trained` weights.  The Q / K / V and GLU route (folded or per-module) leaves no trace
+always), one causal and one streaming configuration at 700 frames and three at 1001 (key blocks skipped from the left, tiles of live and dead rows, 64-wide heads under a band), synthetic and `trained` weights.  The Q / K / V and GLU route (folded or per-module) leaves no trace
 entry: it is asserted through the data (the other route's reference must fit worse; tests/bf16_parity.py).
 
 The front end and block 0's first FFN (tests/bf16_parity.py check_front, run by every case of both tests): where separate kernels write the subsampler's
@@ -70,6 +70,7 @@ def _model(name, profile, extra):
 
 # name, mel frames, lengths, ragged, options, encoder_params overrides, weight profile
 _L4 = [700, 561, 330, 97]
+_L3 = [1001, 778, 97]
 # Tiny's tensors are 24 .. 48 columns wide: the share of correctly rounded outputs is a counting statistic (one flipped tie of a LayerNorm-ed operand moves
 # 10 - 40 % of a row's outputs), and at a few hundred rows the float32 runs expect less than one such event per tensor - nothing a factor can be applied to.
 # Twelve utterances give 7212 rows at stage 0 (more than chain_small_m = 4096: the 8-wave shapes by row count), 3606 and 1206 at the later stages.
@@ -94,11 +95,19 @@ CASES = [
     ("ConformerCTCSmall", 520, [520, 401, 263, 97], True, {"chain_small_m": 0}, {}, "synthetic"),
     ("EfficientConformerCTCSmall", 700, _L4, False, {}, {"causal": True}, "synthetic"),
     ("EfficientConformerCTCSmall", 700, _L4, True, {}, {"left_context": 64, "right_context": 8}, "synthetic"),
+    # 167 grouped rows under a band of 21 at stage 0, 251 rows under 32 at stage 1: the third query tile starts at key block 1 (kbeg > 0 in attention2.hip); the
+    # rectangular case's 97-frame utterance leaves query tiles that mix live and dead rows (whole band in the padding: uniform over all key groups)
+    ("EfficientConformerCTCSmall", 1001, _L3, True, {}, {"left_context": 64, "right_context": 8}, "synthetic"),
+    ("EfficientConformerCTCSmall", 1001, _L3, False, {}, {"causal": True, "left_context": 64}, "synthetic"),
+    # 64-wide heads at stages 1 and 2 (Small's widths are 90 / 42 / 60): 126 rows under a band of 32 - rows of the second query tile whose first visited key
+    # block holds none of their keys, NaN before NEG_BIG of attention2.hip became a power of two
+    ("EfficientConformerCTCMedium", 1001, _L3, True, {}, {"left_context": 64, "right_context": 8}, "synthetic"),
 ]
 
 
 def _id(c):
-    return "-".join([c[0], "ragged" if c[3] else "rect"] + ["%s=%d" % kv for kv in sorted(c[4].items())] + ["%s=%s" % kv for kv in sorted(c[5].items())] + [c[6]])
+    long = ["T%d" % c[1]] if c[2] is _L3 else []          # the ids of the earlier cases stay as they were
+    return "-".join([c[0], "ragged" if c[3] else "rect"] + long + ["%s=%d" % kv for kv in sorted(c[4].items())] + ["%s=%s" % kv for kv in sorted(c[5].items())] + [c[6]])
 
 
 @pytest.mark.parametrize("case", CASES, ids=_id)

@@ -40,7 +40,10 @@ CASES = (
     + [(n, max(e), e, True, FUSED, {}, "synthetic", "mel", True) for n in (_SM, "Tiny") for e in (_EDGE_A, _EDGE_B)]
     + [(_SM, 1400, _SHORT, True, FUSED, {}, "synthetic", "mel", True),
        (_SM, 420, [420, 333, 201], False, FUSED, {"causal": True}, "synthetic", "mel", True),
-       (_SM, 420, [420, 333, 201], True, FUSED, {"left_context": 64, "right_context": 8}, "synthetic", "mel", True)]
+       (_SM, 420, [420, 333, 201], True, FUSED, {"left_context": 64, "right_context": 8}, "synthetic", "mel", True),
+       # 167 / 251 grouped rows under bands of 21 / 32: sxf_attention_kernel skips key blocks from the left (jt_lo > 0); rectangular: tiles of live and dead rows
+       (_SM, 1001, [1001, 778, 97], True, FUSED, {"left_context": 64, "right_context": 8}, "synthetic", "mel", True),
+       (_SM, 1001, [1001, 778, 97], False, FUSED, {"causal": True, "left_context": 64}, "synthetic", "mel", True)]
     + [(_SM, 420, [420, 333, 201], rg, FUSED, {}, "trained", "mel", True) for rg in (False, True)]
     + [(_SM, 420, [420, 333, 201], rg, o, {}, "trained", "floor", False) for rg in (False, True) for o in (FUSED, PER_MODULE)]
 )
