@@ -75,7 +75,10 @@ SIGNATURES = {
     "effconf_rnnt_greedy": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _P, _I32, _P, _SZ, _P]),
     "effconf_rnnt_beam_workspace_bytes": (_SZ, [_P, _I32, _I32, _I32, _I32, _I32]),
     "effconf_rnnt_beam": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _F32P, _P, _I32, _P, _SZ, _P]),
-    "effconf_rnnt_lattice_workspace_bytes": (_SZ, [_P, _I32, _I32, _I32]),
+    "effconf_rnnt_beam_lm_workspace_bytes": (_SZ, [_P, _P, _I32, _I32, _I32, _I32, _I32]),
+    "effconf_rnnt_beam_lm": (C.c_int, [_P, _P, _F32P, _I64P, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float, _I32, _P, _P, _F32P, _P, _I32,
+                                       C.POINTER(C.c_int32), _P, _SZ, _P]),
+    "effconf_rnnt_lattice_workspace_bytes":(_SZ, [_P, _I32, _I32, _I32]),
     "effconf_rnnt_lattice": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _I64P, _I32, C.c_float, _F32P, _F32P, _P, _P, _SZ, _P]),
     "effconf_rnnt_align_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
     "effconf_rnnt_align": (C.c_int, [_F32P, _F32P, _I64P, _I64P, _I32, _I32, _I32, _F32P, _F32P, _P, _F32P, _P, _P, _SZ, _P]),

@@ -267,7 +267,7 @@ def named_config(name: str) -> dict:
         d = _RNNT_DIM[name]
         cfg["decoder_params"] = {"arch": "RNN", "num_layers": 1, "dim_model": d, "vocab_size": vocab}
         cfg["joint_params"] = {"joint_mode": "sum", "dim_model": d, "act": "tanh"}
-        # the beam search part of the shipped configs' decoding_params (the n-gram / LM fusion entries are not implemented)
+        # the beam search part of the shipped configs' decoding_params (lm_weight / lm_tmp: Transducer's neural-LM fusion; the n-gram entries are not implemented)
         cfg["decoding_params"] = {"beam_size": 16, "tmp": 1}
     else:
         # the same for the CTC configs (ctcdecode's beam search; the n-gram entries are not implemented)

@@ -308,6 +308,24 @@ struct DeviceAllocs {
     }
 };
 
+// ---- lm.hip's column step, for the fused beam search of rnnt_beam.hip (internal: not part of the C ABI).  One LM step of `ncol` columns on the caller's
+// stream: pack the live requests into the first columns of the step state (slot[n]: request n's packed column, -1 when it is not live; slot[ncol + d]: the token
+// of packed column d), gather the (h, c) of their source nodes (-1: zeros), lm_lstm_step_kernel per layer (a column tile without a live column returns at once),
+// lm_head_kernel<true> for the raw logits rows logits[packed column][V], scatter the new (h, c) to the destination nodes.  A request is int4 {token, source
+// node, destination node, live}; request n belongs to utterance n / cols_per_utt, whose LM nodes of node_floats floats start at utt + that * per_utt + lmnodes.
+// lm_ws: the 256-aligned region of lm_layout(cfg, ncol).  Every column's result is that of effconf_lm_step on it alone, wherever it is packed.
+struct EcLm;
+namespace ecdec {
+struct LmColumns {
+    const int4* req; int ncol, cols_per_utt;
+    int* slot;                                                        // [2 * ncol]
+    char* utt; size_t per_utt, lmnodes; int node_floats;
+    float* logits;
+};
+const EcLmConfig* lm_handle_config(const EcLm* lm, bool finalized);    // null: no handle, or (finalized asked for) not finalized
+int lm_columns_step(const EcLm* lm, const LmColumns& a, char* lm_ws, hipStream_t s);
+}  // namespace ecdec
+
 struct EcRnnt {
     EcRnntConfig cfg;
     EcHostTensors host;

@@ -52,21 +52,26 @@ struct BeamLayout {
     size_t nodes, topv, topl, a, b, trail, total;
 };
 
-inline BeamLayout beam_layout(const EcRnntConfig& c, int batch, int t_out, int beam, int maxexp) {
-    BeamLayout L{};
+// one utterance's regions of the search on the plan `u` (beam_layout and beam_lm_layout continue from here)
+inline void beam_utt_regions(BeamLayout& L, WsPlan& u, const EcRnntConfig& c, int t_out, int beam, int maxexp) {
     L.beam = beam; L.maxexp = maxexp;
     L.ecap = maxexp + BEAM_SLACK;                                        // evaluations per frame: one per pop + the slack
     L.acap = beam + maxexp * beam;                                       // A: the carried beam + beam children per pop
     L.tcap = 1 + t_out * maxexp;                                         // trail: the start token + one entry per pop
     L.ns = 2 * c.dim_decoder + c.dim_joint;                              // node: h', c', linear_decoder(h')
     L.nnodes = 2 * beam + L.ecap;                                        // two carry sets (previous / next frame) + the frame's arena
-    WsPlan u;                                                            // one utterance
     L.nodes = u.take((size_t)L.nnodes * L.ns * 4);
     L.topv = u.take((size_t)L.ecap * beam * 4);
     L.topl = u.take((size_t)L.ecap * beam * 4);
     L.a = u.take((size_t)L.acap * BEAM_HYP_BYTES);
     L.b = u.take((size_t)beam * BEAM_HYP_BYTES);
     L.trail = u.take((size_t)L.tcap * 8);
+}
+
+inline BeamLayout beam_layout(const EcRnntConfig& c, int batch, int t_out, int beam, int maxexp) {
+    BeamLayout L{};
+    WsPlan u;                                                            // one utterance
+    beam_utt_regions(L, u, c, t_out, beam, maxexp);
     L.per_utt = u.stride();
     WsPlan p;
     L.stats = p.take((size_t)batch * 16);
@@ -120,6 +125,46 @@ inline LmLayout lm_layout(const EcLmConfig& c, int n) {
     L.ulen = p.take((size_t)n * 4);
     L.layer = (size_t)3 * lm_npad(n) * c.dim_model * 4;
     L.state = p.take((size_t)c.num_layers * L.layer);
+    L.total = p.total();
+    return L;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- rnnt_beam.hip with a neural LM (shallow fusion)
+// The search's regions, and per utterance an LM node array on the index space of the decoder nodes: node = the LM's state after the hypothesis' last token
+// ([layer][h k-permuted | c], 2 * layers * dim_model floats), then its row lm_weight is applied to (vocab floats).  Per call: one request (token, source node,
+// destination node, live) per column, BEAM_LM_COLS columns per utterance, and its packed column + the packed columns' tokens (slot); one resume record per utterance; the round's counter of suspended utterances; the
+// dense state of one LM step over batch * BEAM_LM_COLS columns (lm_layout) and its raw logits rows.
+constexpr int BEAM_LM_COLS = 16;          // columns of an evaluation batch at the most
+constexpr int BEAM_LM_RESUME_INTS = 32;   // phase, frame, na, nb, pops, used, ntrail, status, columns, three counters, then the selected columns
+
+struct BeamLmLayout {
+    BeamLayout s;                                                        // s.total is not set: `total` below is the call's size
+    int nls, vocab;                                                      // floats of an LM node's state; its row follows
+    size_t lmnodes;                                                      // inside an utterance
+    size_t req, slot, resume, counter, lm, logits, total;
+    LmLayout lml;                                                        // offsets from `lm`
+};
+
+inline BeamLmLayout beam_lm_layout(const EcRnntConfig& c, const EcLmConfig& m, int batch, int t_out, int beam, int maxexp) {
+    BeamLmLayout L{};
+    WsPlan u;
+    beam_utt_regions(L.s, u, c, t_out, beam, maxexp);
+    L.nls = 2 * m.num_layers * m.dim_model;
+    L.vocab = m.vocab_size;
+    L.lmnodes = u.take((size_t)L.s.nnodes * (L.nls + L.vocab) * 4);
+    L.s.per_utt = u.stride();
+    const int ncol = batch * BEAM_LM_COLS;
+    L.lml = lm_layout(m, ncol);
+    WsPlan p;
+    L.s.stats = p.take((size_t)batch * 16);
+    L.s.fe = p.take((size_t)batch * t_out * c.dim_joint * 4);
+    L.s.utt = p.take((size_t)batch * L.s.per_utt);
+    L.req = p.take((size_t)ncol * 16);
+    L.slot = p.take((size_t)ncol * 8);
+    L.resume = p.take((size_t)batch * BEAM_LM_RESUME_INTS * 4);
+    L.counter = p.take(4);
+    L.lm = p.take(L.lml.total - 256);                                    // a sub-plan: its own slack is not needed inside an aligned region
+    L.logits = p.take((size_t)ncol * m.vocab_size * 4);
     L.total = p.total();
     return L;
 }

@@ -19,6 +19,8 @@
 //     lane's running (max, sum exp) of (acc + b) / tmp and the pick of column y_u, merged in a fixed order (k-slots of a wave, then waves 0 .. 7);
 //     ONE float per (sequence, position) leaves the kernel, and score[n] += it (a launch per position: u ascending).  FULL = true (the decode
 //     step): the raw logits row acc + b.  V % 16 != 0: rows clamped on load, masked with -inf.
+//   * ecdec::lm_columns_step (decode_common.h; not part of the C ABI): the decode step on the LM nodes of the fused RNN-T beam search (rnnt_beam.hip) - the live
+//     requests of all utterances packed into the first columns of the step state, the two kernels above, the new states scattered back to the nodes.
 // A column of an MFMA tile depends on that column of B alone and unused columns are zero: a sequence's results are bit-identical alone, in any
 // batch, in any order, under a larger u_max, with garbage behind its length and on a workspace filled with any byte (the state is cleared by a
 // memset on the stream, nothing else is read before it is written).
@@ -251,6 +253,11 @@ __global__ __launch_bounds__(HT) void lm_head_kernel(const HeadArgs a) {
     const float* x1 = a.h + (size_t)(c0 + 16 + j) * H + 4 * g;
     float ms[4];                                     // the lane's running (max, sum) of sequences j and 16 + j
     if (FULL) {                                      // the raw logits row acc + b: tmp = 1 (x / 1 = x), the running sums are dead code
+        if (a.ulen) {                                // the column step of the fused beam search: workgroup-uniform, no live column among these 32
+            bool any = false;
+            for (int i = 0; i < HC; ++i) any = any || (c0 + i < a.N && a.ulen[c0 + i] > 0);
+            if (!any) return;
+        }
         float* row0 = c0 + j < a.N ? a.logits + (size_t)(c0 + j) * V : nullptr;
         float* row1 = c0 + 16 + j < a.N ? a.logits + (size_t)(c0 + 16 + j) * V : nullptr;
         vocab_lse_tiles<1, HW>(a.wfc16, a.bfc, V, K16, x0, x1, 1.f, LmLogitsPick{row0, row1}, ms);
@@ -315,7 +322,90 @@ int launch_step(const EcLm* lm, float* state, size_t layer_floats, int l, int cu
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the fused beam search's column step
+// The live requests are packed into the first columns of the step state, in request order: an evaluation batch seldom fills its 16 columns, and a column tile
+// without a live column costs nothing.  LM nodes ([layer][h k-permuted | c], then the node's row) <-> the packed state.  Columns at or beyond the live count keep
+// whatever the state holds: a column of an MFMA tile depends on that column alone, and nothing reads its results.
+__device__ __forceinline__ float* lm_node(const LmColumns& a, int n, int node) {
+    return reinterpret_cast<float*>(a.utt + (size_t)(n / a.cols_per_utt) * a.per_utt + a.lmnodes) + (size_t)node * a.node_floats;
+}
+
+// slot[n] = the packed column of request n (-1: not live), slot[ncol + d] = the token of packed column d, ulen[d] = d < live count.  One workgroup: thread t owns
+// the requests t * per .. t * per + per - 1, an inclusive scan over the threads' counts orders them.
+constexpr int IT = 1024;
+__global__ __launch_bounds__(IT) void lm_columns_index_kernel(const LmColumns a, int* ulen) {
+    __shared__ int s_cnt[IT];
+    const int tid = threadIdx.x, per = (a.ncol + IT - 1) / IT, lo = tid * per, hi = lo + per < a.ncol ? lo + per : a.ncol;
+    int cnt = 0;
+    for (int n = lo; n < hi; ++n) cnt += a.req[n].w != 0;
+    s_cnt[tid] = cnt;
+    __syncthreads();
+    for (int o = 1; o < IT; o <<= 1) {
+        const int v = tid >= o ? s_cnt[tid - o] : 0;
+        __syncthreads();
+        s_cnt[tid] += v;
+        __syncthreads();
+    }
+    int d = s_cnt[tid] - cnt;
+    const int total = s_cnt[IT - 1];
+    for (int n = lo; n < hi; ++n) {
+        const int4 rq = a.req[n];                    // token, source node (-1: zero state), destination node, live
+        a.slot[n] = rq.w ? d : -1;
+        if (rq.w) a.slot[a.ncol + d++] = rq.x;
+    }
+    for (int n = lo; n < hi; ++n) ulen[n] = n < total ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void lm_columns_in_kernel(const LmColumns a, float* state, size_t layer_floats, int L, int Np, int H) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)a.ncol * L * H) return;
+    const int k = (int)(i % H), l = (int)((i / H) % L), n = (int)(i / ((size_t)H * L));
+    const int d = a.slot[n];
+    if (d < 0) return;
+    const int src_node = a.req[n].y;
+    const float* src = src_node >= 0 ? lm_node(a, n, src_node) + (size_t)l * 2 * H : nullptr;
+    float* base = state + (size_t)l * layer_floats;
+    base[(size_t)d * H + k] = src ? src[k] : 0.f;                                  // buffer 0: the step's input
+    base[(size_t)2 * Np * H + (size_t)d * H + k] = src ? src[H + k] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void lm_columns_out_kernel(const LmColumns a, const float* state, size_t layer_floats, int L, int Np, int H) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)a.ncol * L * H) return;
+    const int k = (int)(i % H), l = (int)((i / H) % L), n = (int)(i / ((size_t)H * L));
+    const int d = a.slot[n];
+    if (d < 0) return;
+    float* dst = lm_node(a, n, a.req[n].z) + (size_t)l * 2 * H;
+    const float* base = state + (size_t)l * layer_floats;
+    dst[k] = base[(size_t)Np * H + (size_t)d * H + k];                             // buffer 1: the step's output
+    dst[H + k] = base[(size_t)2 * Np * H + (size_t)d * H + k];
+}
+
 }  // namespace
+
+const EcLmConfig* ecdec::lm_handle_config(const EcLm* lm, bool finalized) { return lm && (lm->finalized || !finalized) ? &lm->cfg : nullptr; }
+
+int ecdec::lm_columns_step(const EcLm* lm, const LmColumns& a, char* lm_ws, hipStream_t s) {
+    const LmLayout L = lm_layout(lm->cfg, a.ncol);
+    int* ulen = reinterpret_cast<int*>(lm_ws + L.ulen);
+    float* state = reinterpret_cast<float*>(lm_ws + L.state);
+    const int H = lm->cfg.dim_model, V = lm->cfg.vocab_size, NL = lm->cfg.num_layers, Np = lm_npad(a.ncol);
+    const size_t layer_floats = L.layer / 4, cells = (size_t)a.ncol * NL * H;
+    const unsigned grid = (unsigned)((cells + 255) / 256);
+    hipLaunchKernelGGL(lm_columns_index_kernel, dim3(1), dim3(IT), 0, s, a, ulen);
+    hipLaunchKernelGGL(lm_columns_in_kernel, dim3(grid), dim3(256), 0, s, a, state, layer_floats, NL, Np, H);
+    if (hipGetLastError() != hipSuccess) return -1;
+    for (int l = 0; l < NL; ++l)
+        if (launch_step(lm, state, layer_floats, l, 0, a.ncol, a.slot + a.ncol, 1, 0, ulen, 0, s) != 0) return -1;
+    HeadArgs h{};
+    h.wfc16 = lm->wfc16; h.bfc = lm->bfc;
+    h.h = state + (size_t)(NL - 1) * layer_floats + (size_t)Np * H;
+    h.ulen = ulen; h.logits = a.logits; h.N = a.ncol; h.H = H; h.V = V; h.tmp = 1.f;
+    hipLaunchKernelGGL(lm_head_kernel<true>, dim3(Np / HC), dim3(HT), 0, s, h);
+    if (hipGetLastError() != hipSuccess) return -1;
+    hipLaunchKernelGGL(lm_columns_out_kernel, dim3(grid), dim3(256), 0, s, a, state, layer_floats, NL, Np, H);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 extern "C" {
 

@@ -6,14 +6,17 @@ state-dict keys and method names (``gready_search_decoding``, the reference's sp
 of the reference — one decoder call, one joint call and one ``.argmax()`` host sync per decision — runs as one
 persistent HIP kernel per batch (effconf_rnnt_greedy).  ``beam_search_decoding`` (transducer.py:188-327) runs as one persistent
 HIP kernel per batch as well (effconf_rnnt_beam, one workgroup per utterance), with the reference's algorithm, tie rules and fp32
-scores; the neural-LM and n-gram (KenLM) shallow fusion terms are not implemented, which is what the reference computes without an LM
-checkpoint and n-gram file.  For a KNOWN transcript, ``lattice`` gives the two log-probabilities per (t, u) cell the RNN-T loss sees
+scores.  With a ``LanguageModel`` attached as ``lm`` (or passed) and ``lm_weight`` > 0 the search adds the reference's neural-LM shallow
+fusion term (transducer.py:259-273: ``lm_weight * (lm.decode(y, hidden_lm) / lm_tmp).softmax().log()`` before the top-k; effconf_rnnt_beam_lm:
+the search kernel and one chip-wide LM step over every utterance's pending hypotheses alternate).  The n-gram (KenLM) terms are not
+implemented.  For a KNOWN transcript, ``lattice`` gives the two log-probabilities per (t, u) cell the RNN-T loss sees
 (csrc/rnnt_lattice.hip: the (B, T, U + 1, V) logits of transducer.py:88-107 never reach memory), ``score_labels`` log P(y | x) = -rnnt_loss
 and ``align`` the frame at which each token is emitted (csrc/rnnt_align.hip: forward recursion and Viterbi over the lattice).  Training
 (``forward`` with gradients, the RNN-T loss' backward) is out of scope (HISTORY.md).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import List, NamedTuple, Optional
 
 import numpy as np
@@ -23,6 +26,10 @@ import torch.nn as nn
 from . import _lib, _native, _targets
 from .config import load_config
 from .encoders import ConformerEncoder
+
+# One call's workspace of the fused beam search stays under this many bytes where more than one utterance is decoded: per utterance the LM nodes
+# take (2 * beam + max_expansions + 64) * (2 * num_layers * dim_model + vocab) * 4 bytes (LM-RNN 4096 x 3 at beam 16: 36 MB, 256 utterances 9.2 GB).
+BEAM_LM_WORKSPACE_CAP = 16 << 30
 
 _JOINT_MODES = {"sum": 0}
 _JOINT_ACTS = {"tanh": 0}
@@ -86,6 +93,11 @@ class Transducer(_native.NativeModel):
         decoding_params = decoding_params or {}
         self.beam_size = int(decoding_params.get("beam_size", 1))                    # model.py:60-61
         self.tmp = float(decoding_params.get("tmp", 1))
+        # the reference's attribute and decoding_params (model.py:70-72): a LanguageModel attached by the caller, fused into the beam search.  Assigning
+        # one registers it as a submodule, as in the reference: state_dict() then carries its tensors under ``lm.``
+        self.lm = None
+        self.lm_weight = float(decoding_params.get("lm_weight", 0))
+        self.lm_tmp = float(decoding_params.get("lm_tmp", 1))
         self._cfg = (self.encoder.plan.dim_out, decoder_params["dim_model"], joint_params["dim_model"],
                      decoder_params["vocab_size"], decoder_params["num_layers"])
         self.tokenizer = tokenizer
@@ -93,6 +105,7 @@ class Transducer(_native.NativeModel):
         self._native = _native.Handle("rnnt")
         self._rnnt_packed = False
         self._beam_ws = None
+        self._beam_rounds = None
         self.eval()
 
     @classmethod
@@ -173,12 +186,38 @@ class Transducer(_native.NativeModel):
                             max_expansions_per_frame: Optional[int] = None, max_tokens: Optional[int] = None):
         """Beam search of encoder outputs f (B, T, Denc) fp32 on the GPU (effconf_rnnt_beam) -> (tokens (B, max_tokens) i32,
         token_len (B) i32, score (B) f32, status (B) i32).  status 1 / 2: the utterance hit the expansion / token cap and has no tokens.
-        Defaults: beam_size = self.beam_size, max_expansions_per_frame = 16 * beam, max_tokens = max(16, beam) * T."""
-        _native.require_hip(f)
-        with torch.cuda.device(f.device):
-            return self._decode_encoded_beam(f, f_len, beam_size, max_expansions_per_frame, max_tokens)
+        Defaults: beam_size = self.beam_size, max_expansions_per_frame = 16 * beam, max_tokens = max(16, beam) * T.
+        With ``self.lm`` attached and ``self.lm_weight`` > 0 this is ``decode_encoded_beam_lm`` on them (the fused search)."""
+        return self.decode_encoded_beam_lm(f, f_len, beam_size, max_expansions_per_frame, max_tokens)
 
-    def _decode_encoded_beam(self, f, f_len, beam_size, max_expansions_per_frame, max_tokens):
+    def decode_encoded_beam_lm(self, f: torch.Tensor, f_len: Optional[torch.Tensor], beam_size: Optional[int] = None,
+                               max_expansions_per_frame: Optional[int] = None, max_tokens: Optional[int] = None, lm=None,
+                               lm_weight: Optional[float] = None, lm_tmp: Optional[float] = None):
+        """``decode_encoded_beam`` with the fusion arguments spelled out: lm (default ``self.lm``), lm_weight (``self.lm_weight``), lm_tmp
+        (``self.lm_tmp``).  With a LanguageModel and a weight > 0 the search fuses the LM's log-probabilities (effconf_rnnt_beam_lm; the batch is
+        split into chunks whose workspace stays under ``BEAM_LM_WORKSPACE_CAP``); without an LM, or at weight 0, it is the plain search
+        (effconf_rnnt_beam).  A negative or non-finite weight with an LM raises ValueError."""
+        lm, weight, ltmp = self._fusion(lm, lm_weight, lm_tmp)
+        _native.require_hip(f)
+        if lm is not None:
+            _native.require_hip(lm.fc.weight)
+        with torch.cuda.device(f.device):
+            return self._decode_encoded_beam(f, f_len, beam_size, max_expansions_per_frame, max_tokens, lm, weight, ltmp)
+
+    def _fusion(self, lm, lm_weight, lm_tmp):
+        """(lm or None, weight, lm_tmp) a beam search runs with: the arguments, else the attributes; None when there is nothing to fuse."""
+        lm = self.lm if lm is None else lm
+        weight = float(self.lm_weight if lm_weight is None else lm_weight)
+        ltmp = float(self.lm_tmp if lm_tmp is None else lm_tmp)
+        if lm is None or weight == 0:
+            return None, 0.0, ltmp
+        if not 0 < weight < float("inf"):
+            raise ValueError("lm_weight must be >= 0 and finite; got %r" % (weight,))
+        if not 0 < ltmp < float("inf"):
+            raise ValueError("lm_tmp must be > 0 and finite; got %r" % (ltmp,))
+        return lm, weight, ltmp
+
+    def _decode_encoded_beam(self, f, f_len, beam_size, max_expansions_per_frame, max_tokens, lm=None, lm_weight=0.0, lm_tmp=1.0):
         beam = int(self.beam_size if beam_size is None else beam_size)
         vocab = self._cfg[3]
         if not 1 <= beam <= min(16, vocab):
@@ -192,32 +231,61 @@ class Transducer(_native.NativeModel):
         f_len = _native.lengths(f_len, b, t, f.device)
         max_exp = int(16 * beam if max_expansions_per_frame is None else max_expansions_per_frame)
         max_tok = int(max(16, beam) * max(t, 1) if max_tokens is None else max_tokens)
-        nbytes = _native.sized(lib, "effconf_rnnt_beam", lib.effconf_rnnt_beam_workspace_bytes(self._rnnt, b, t, beam, max_exp, max_tok),
-                               batch=b, T=t, beam=beam, max_expansions=max_exp, max_tokens=max_tok)
         tokens = torch.empty(b, max_tok, dtype=torch.int32, device=f.device)
         token_len = torch.empty(b, dtype=torch.int32, device=f.device)
         score = torch.empty(b, dtype=torch.float32, device=f.device)
         status = torch.empty(b, dtype=torch.int32, device=f.device)
-        ws = _native.workspace(nbytes, f.device)
-        _lib.check(lib.effconf_rnnt_beam(self._rnnt, f.data_ptr(), f_len.data_ptr(), b, t, beam, float(self.tmp), max_exp, tokens.data_ptr(),
-                                         token_len.data_ptr(), score.data_ptr(), status.data_ptr(), max_tok, ws.data_ptr(), ws.numel(),
-                                         torch.cuda.current_stream(f.device).cuda_stream), "rnnt_beam")
-        self._beam_ws = (ws, b)
+        stream = torch.cuda.current_stream(f.device).cuda_stream
+        if lm is None:
+            nbytes = _native.sized(lib, "effconf_rnnt_beam", lib.effconf_rnnt_beam_workspace_bytes(self._rnnt, b, t, beam, max_exp, max_tok),
+                                   batch=b, T=t, beam=beam, max_expansions=max_exp, max_tokens=max_tok)
+            ws = _native.workspace(nbytes, f.device)
+            _lib.check(lib.effconf_rnnt_beam(self._rnnt, f.data_ptr(), f_len.data_ptr(), b, t, beam, float(self.tmp), max_exp, tokens.data_ptr(),
+                                             token_len.data_ptr(), score.data_ptr(), status.data_ptr(), max_tok, ws.data_ptr(), ws.numel(), stream),
+                       "rnnt_beam")
+            self._beam_ws, self._beam_rounds = [(ws, b)], None
+            return tokens, token_len, score, status
+        lm._ensure()
+        size = lambda n: _native.sized(lib, "effconf_rnnt_beam_lm",
+                                       lib.effconf_rnnt_beam_lm_workspace_bytes(self._rnnt, lm._handle, n, t, beam, max_exp, max_tok),
+                                       batch=n, T=t, beam=beam, max_expansions=max_exp, max_tokens=max_tok)
+        # rows are independent: chunks of utterances whose workspace stays under the cap (one utterance at the least)
+        step = max(1, b)
+        while step > 1 and size(step) > BEAM_LM_WORKSPACE_CAP:
+            step = (step + 1) // 2
+        self._beam_ws, self._beam_rounds = [], []
+        rounds = C.c_int32(0)
+        for lo in range(0, b, step):
+            n = min(step, b - lo)
+            ws = _native.workspace(size(n), f.device)
+            _lib.check(lib.effconf_rnnt_beam_lm(self._rnnt, lm._handle, f[lo:].data_ptr(), f_len[lo:].data_ptr(), n, t, beam, float(self.tmp),
+                                                lm_weight, lm_tmp, max_exp, tokens[lo:].data_ptr(), token_len[lo:].data_ptr(), score[lo:].data_ptr(),
+                                                status[lo:].data_ptr(), max_tok, C.byref(rounds), ws.data_ptr(), ws.numel(), stream), "rnnt_beam_lm")
+            self._beam_ws.append((ws, n))
+            self._beam_rounds.append(int(rounds.value))
         return tokens, token_len, score, status
 
     def last_beam_stats(self) -> np.ndarray:
-        """Per-utterance counters of the last decode_encoded_beam call: (B, 4) i32 = evaluation batches, evaluated hypotheses,
+        """Per-utterance counters of the last decode_encoded_beam / decode_encoded_beam_lm call: (B, 4) i32 = evaluation batches, evaluated hypotheses,
         expansions, frames (the head of the workspace, include/effconf.h)."""
-        ws, b = self._beam_ws
-        off = (-ws.data_ptr()) % 256
-        return ws[off:off + 16 * b].view(torch.int32).view(b, 4).cpu().numpy()
+        out = []
+        for ws, b in self._beam_ws:
+            off = (-ws.data_ptr()) % 256
+            out.append(ws[off:off + 16 * b].view(torch.int32).view(b, 4).cpu().numpy())
+        return np.concatenate(out) if out else np.zeros((0, 4), dtype=np.int32)
+
+    def last_beam_rounds(self) -> Optional[List[int]]:
+        """Search launches of the last decode_encoded_beam / decode_encoded_beam_lm call, one entry per chunk of the batch (an LM step ran between two of them); None after
+        a plain search, which is one launch."""
+        return self._beam_rounds
 
     def beam_tokens(self, x: torch.Tensor, x_len: Optional[torch.Tensor], beam_size: Optional[int] = None,
-                    from_mel: bool = False) -> List[List[int]]:
-        """Beam-search token-id sequences (without the start token), one list per utterance.  Raises EffconfError naming the
-        utterances that hit the expansion or token cap (never a silently truncated result)."""
+                    from_mel: bool = False, lm=None, lm_weight: Optional[float] = None, lm_tmp: Optional[float] = None) -> List[List[int]]:
+        """Beam-search token-id sequences (without the start token), one list per utterance; lm / lm_weight / lm_tmp as decode_encoded_beam_lm.
+        Raises EffconfError naming the utterances that hit the expansion or token cap (never a silently truncated result)."""
+        self._fusion(lm, lm_weight, lm_tmp)                            # the argument rules, before the encoder runs
         f, f_len, _ = self.encoder.forward_mel(x, x_len) if from_mel else self.encoder(x, x_len)
-        tokens, token_len, _, status = self.decode_encoded_beam(f, f_len, beam_size)
+        tokens, token_len, _, status = self.decode_encoded_beam_lm(f, f_len, beam_size, lm=lm, lm_weight=lm_weight, lm_tmp=lm_tmp)
         tokens, token_len, status = tokens.cpu(), token_len.cpu(), status.cpu()
         capped = {1: [i for i in range(len(status)) if int(status[i]) == 1], 2: [i for i in range(len(status)) if int(status[i]) == 2]}
         if capped[1] or capped[2]:
@@ -232,7 +300,8 @@ class Transducer(_native.NativeModel):
 
     def beam_search_decoding(self, x, x_len, beam_size=None):
         """Reference name and signature (transducer.py:188).  Decoded strings when a tokenizer is attached
-        (``tokenizer.decode(best_hyp["prediction"][1:])`` per utterance, transducer.py:323), otherwise the id lists."""
+        (``tokenizer.decode(best_hyp["prediction"][1:])`` per utterance, transducer.py:323), otherwise the id lists.  With ``self.lm`` attached and
+        ``self.lm_weight`` > 0 the search fuses the LM (``self.lm_tmp``), as the reference's does."""
         ids = self.beam_tokens(x, x_len, beam_size)
         return [self.tokenizer.decode(i) for i in ids] if self.tokenizer is not None else ids
 

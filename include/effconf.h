@@ -351,6 +351,25 @@ int effconf_lm_load_tensor(EcLm* lm, const char* key, const float* host, const i
  * k-permuted weight images (W_hh0; [W_ih_l | W_hh_l] for l >= 1; fc); uploads.  A missing or mis-shaped tensor is reported before any
  * device call. */
 int effconf_lm_finalize(EcLm* lm);
+/* RNN-T beam search with neural-LM shallow fusion (transducer.py:259-273, 291-306): as effconf_rnnt_beam, with
+ *   logP += lm_weight * (lm.decode(y, hidden_lm) / lm_tmp).softmax().log()
+ * added to the joint's log-probabilities before the top `beam` entries are taken; a label child takes the LM's new state, a blank child keeps its
+ * parent's.  The n-gram terms of the reference are not implemented.  lm: a finalized handle whose vocab_size is the transducer's; lm_weight > 0 and
+ * lm_tmp > 0, both finite (weight 0 is effconf_rnnt_beam).  Outputs, status codes, zero-filled tails and the four counters at the head of the workspace
+ * as effconf_rnnt_beam.  The search kernel (one workgroup per utterance) and one LM step over batch * 16 columns (the kernels of effconf_lm_step: the
+ * LM's weights stream once per step for all utterances) alternate on `stream`; after every search launch the host reads the number of utterances that
+ * wait for the LM (4 bytes, one stream synchronise), so the call returns with the results complete and CANNOT be captured in a graph.  At most
+ * t_out * (max_expansions + 1) + 2 search launches; rounds_out (host, may be NULL) receives their number.  A row's results do not depend on the rows
+ * sharing the call, on "beam_eval_batch" or on the workspace's contents.  The workspace holds, per utterance, an LM node (2 * num_layers * dim_model
+ * + vocab_size floats) beside each of the 2 * beam + max_expansions + 64 decoder nodes: callers split large batches (rows are independent).
+ * effconf_rnnt_beam_lm_workspace_bytes needs no finalized handles and returns 0 for arguments effconf_rnnt_beam_lm rejects. */
+size_t effconf_rnnt_beam_lm_workspace_bytes(const EcRnnt* r, const EcLm* lm, int32_t batch, int32_t t_out, int32_t beam, int32_t max_expansions,
+                                            int32_t max_tokens);
+int effconf_rnnt_beam_lm(EcRnnt* r, EcLm* lm, const float* enc_out, const int64_t* out_len, int32_t batch, int32_t t_out, int32_t beam,
+                         float temperature, float lm_weight, float lm_tmp, int32_t max_expansions, int32_t* tokens, int32_t* token_len,
+                         float* score, int32_t* status, int32_t max_tokens, int32_t* rounds_out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* Workspace of effconf_lm_score and effconf_lm_step (the latter: any u_max, e.g. 0): 256 + al(4 n) + num_layers * 3 * Np * dim_model * 4 bytes,
  * Np = n rounded up to 64, al(x) = x rounded up to 256.  After the 256-byte aligned pointer: i32 ulen[n]; at al(4 n) per layer l the blocks
  * h[2][Np][dim_model] (k permuted within every 16: position (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); step u reads buffer u & 1 and

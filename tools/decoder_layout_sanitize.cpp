@@ -1,4 +1,4 @@
-// Stand-alone host program for a sanitizer run of csrc/decode_layout.h (not part of the test suite): WsPlan and the seven decoder layouts written on it, over
+// Stand-alone host program for a sanitizer run of csrc/decode_layout.h (not part of the test suite): WsPlan and the decoder layouts written on it (the seven entries' and the fused beam search's), over
 // the grid of tests/test_decoder_layout_host.py.  For every layout: the regions are 256-aligned, ascending and disjoint, an utterance's regions stay inside its
 // stride, and for every misalignment of the caller's pointer (p % 256 in steps of 16) the aligned base plus the end of the last region stays inside
 // p + total() - the property the greedy decoder's hand carve lacked.  Plain C++, no device, nothing linked.  From the repository root:
@@ -103,6 +103,34 @@ int main() {
             const LmLayout L = lm_layout(c, n);
             if (L.layer != (size_t)3 * lm_npad(n) * d[1] * 4) fail("a layer that is not h[2] + c of the padded batch", "lm_layout");
             check_total("lm_layout", {{L.ulen, (size_t)n * 4}, {L.state, (size_t)d[2] * L.layer}}, L.total);
+        }
+    }
+    // the beam search with an LM: the search's regions + LM nodes per utterance, then requests, resume records, the round counter, the LM step state and its logits
+    for (const auto& d : rnnt) {
+        if (d[1] % 16 || d[2] % 16) continue;
+        EcRnntConfig c{};
+        c.dim_encoder = d[0]; c.dim_decoder = d[1]; c.dim_joint = d[2]; c.vocab_size = d[3]; c.num_layers = 1; c.max_consec_dec_step = 5;
+        const int lmdims[][2] = {{32, 2}, {48, 3}, {4096, 3}};
+        for (const auto& m : lmdims) {
+            EcLmConfig mc{};
+            mc.vocab_size = d[3]; mc.dim_model = m[0]; mc.num_layers = m[1];
+            for (int b : batches) for (int t : frames) for (int beam : beams) {
+                if (beam > 16 || t < 1 || (m[0] == 4096 && b > 19)) continue;
+                const BeamLmLayout L = beam_lm_layout(c, mc, b, t, beam, 16 * beam);
+                const BeamLayout P = beam_layout(c, b, t, beam, 16 * beam);
+                const size_t ncol = (size_t)b * BEAM_LM_COLS, nlm = (size_t)L.nls + L.vocab;
+                if (L.nls != 2 * m[1] * m[0] || L.vocab != d[3]) fail("an LM node that is not (h, c) per layer + the row", "beam_lm_layout");
+                if (L.s.nodes != P.nodes || L.s.topv != P.topv || L.s.topl != P.topl || L.s.a != P.a || L.s.b != P.b || L.s.trail != P.trail || L.s.nnodes != P.nnodes)
+                    fail("search regions that are not beam_layout's", "beam_lm_layout");
+                check_regions("beam_lm_layout (utterance)", {{L.s.nodes, (size_t)L.s.nnodes * L.s.ns * 4}, {L.s.topv, (size_t)L.s.ecap * beam * 4}, {L.s.topl, (size_t)L.s.ecap * beam * 4},
+                                                              {L.s.a, (size_t)L.s.acap * BEAM_HYP_BYTES}, {L.s.b, (size_t)beam * BEAM_HYP_BYTES}, {L.s.trail, (size_t)L.s.tcap * 8},
+                                                              {L.lmnodes, (size_t)L.s.nnodes * nlm * 4}}, L.s.per_utt);
+                const LmLayout M = lm_layout(mc, (int)ncol);
+                check_regions("beam_lm_layout (LM step)", {{L.lml.ulen, ncol * 4}, {L.lml.state, (size_t)m[1] * L.lml.layer}}, M.total - 256);
+                if (L.lml.layer != M.layer || L.lml.state != M.state) fail("an LM step state that is not lm_layout's", "beam_lm_layout");
+                check_total("beam_lm_layout", {{L.s.stats, (size_t)b * 16}, {L.s.fe, (size_t)b * t * d[2] * 4}, {L.s.utt, (size_t)b * L.s.per_utt}, {L.req, ncol * 16}, {L.slot, ncol * 8},
+                                               {L.resume, (size_t)b * BEAM_LM_RESUME_INTS * 4}, {L.counter, 4}, {L.lm, M.total - 256}, {L.logits, ncol * d[3] * 4}}, L.total);
+            }
         }
     }
     std::printf("decoder_layout_sanitize: %lld layouts checked\n", checked);

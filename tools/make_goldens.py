@@ -10,6 +10,7 @@ It refuses to run where /root/reference is absent (e.g. the GPU box).
 
     python tools/make_goldens.py            # regenerate every fixture
     python tools/make_goldens.py --only-rnnt-beam   # only tests/golden/rnnt_beam_*.npz (from the stored rnnt_*.npz encoder outputs)
+    python tools/make_goldens.py --only-rnnt-beam-lm   # only tests/golden/rnnt_beam_lm_*.npz (the beam search with the reference's LM attached; stored rnnt_*.npz, lm_TinyLM.npz)
     python tools/make_goldens.py --only-rnnt-lattice   # only tests/golden/rnnt_lattice_*.npz (from the stored rnnt_*.npz encoder outputs)
     python tools/make_goldens.py --only-interctc       # only tests/golden/interctc_tiny_*.npz (the reference's ConformerEncoderInterCTC on Tiny)
     python tools/make_goldens.py --only-lm           # only tests/golden/lm_*.npz (LSTM language model; TinyLM's rescoring bias from tiny_T*.npz)
@@ -180,9 +181,10 @@ def rnnt_goldens(enc_mod):
         save("rnnt_" + name, **arrs)
 
 
-def reference_rnnt_beam(f, f_len, dec_params, joint_params, sd, beam_size):
+def reference_rnnt_beam(f, f_len, dec_params, joint_params, sd, beam_size, lm=None, lm_weight=0, lm_tmp=1):
     """Execute the reference's own Transducer.beam_search_decoding (transducer.py:188-327) on given encoder outputs, in the state of a
-    plain checkpoint load: no n-gram file (ngram_path None) and no LM (lm None, lm_weight 0), temperature 1."""
+    plain checkpoint load: no n-gram file (ngram_path None) and no LM (lm None, lm_weight 0), temperature 1 - or with `lm` (reference_lm)
+    attached as Model.lm, lm_weight and lm_tmp as decoding_params set them (model.py:70-72)."""
     _stub_third_party()
     import models.transducer as tr
     import models.decoders as dec
@@ -193,7 +195,7 @@ def reference_rnnt_beam(f, f_len, dec_params, joint_params, sd, beam_size):
     obj.joint_network = jn.JointNetwork(f.shape[-1], dec_params["dim_model"], dec_params["vocab_size"], joint_params).eval()
     obj.decoder.load_state_dict(to_torch({k[len("decoder."):]: v for k, v in sd.items() if k.startswith("decoder.")}), strict=True)
     obj.joint_network.load_state_dict(to_torch({k[len("joint_network."):]: v for k, v in sd.items() if k.startswith("joint_network.")}), strict=True)
-    obj.beam_size, obj.tmp, obj.ngram_path, obj.lm, obj.lm_weight = beam_size, 1, None, None, 0
+    obj.beam_size, obj.tmp, obj.ngram_path, obj.lm, obj.lm_weight, obj.lm_tmp = beam_size, 1, None, lm, lm_weight, lm_tmp
 
     class _Ids:                                   # tokenizer.decode(one id list per utterance) -> keep the ids
         @staticmethod
@@ -221,6 +223,32 @@ def rnnt_beam_goldens():
             arrs["tokens_b%d" % beam], arrs["offsets_b%d" % beam] = pack_labels(toks)
             print("  %s beam %d: tokens per utterance %s (frames %s)" % (name, beam, [len(t) for t in toks], f_len.tolist()))
         save("rnnt_beam_" + name, **arrs)
+
+
+RNNT_BEAM_LM = dict(blank_bias=2.0, lm_weight=0.3, lm_tmp=1.0)
+
+
+def rnnt_beam_lm_goldens():
+    """RNN-T beam search with neural-LM shallow fusion: the reference's own beam_search_decoding with its LanguageModel (TinyLM of lm_TinyLM.npz: weight seed
+    and fc bias) attached, on the encoder outputs stored in rnnt_TinyTransducer.npz.  Blank bias 2.0: at 1.2 the LM's mass on token 0 keeps blank out of
+    the top of the popped hypothesis at beam 4 and the reference's loop does not end."""
+    name, beams = "TinyTransducer", (4, 16)
+    cfg = named_config(name)
+    g = np.load(os.path.join(OUT, "rnnt_%s.npz" % name))
+    gl = np.load(os.path.join(OUT, "lm_TinyLM.npz"))
+    lm_params = dict(LM_MODELS[0][1])
+    lm_sd = synth.make_lm_state_dict(lm_params, int(gl["weight_seed"]), bias=gl["fc_bias_extra"])
+    f, f_len, seed = torch.from_numpy(g["f"]), torch.from_numpy(g["f_len"]), int(g["weight_seed"])
+    sd = synth.make_transducer_state_dict(f.shape[-1], cfg["decoder_params"], cfg["joint_params"], seed, blank_bias=RNNT_BEAM_LM["blank_bias"])
+    arrs = {"weight_seed": np.int64(seed), "blank_bias": np.float32(RNNT_BEAM_LM["blank_bias"]), "beams": np.asarray(beams, dtype=np.int32),
+            "lm_weight": np.float64(RNNT_BEAM_LM["lm_weight"]), "lm_tmp": np.float64(RNNT_BEAM_LM["lm_tmp"]),
+            "lm_weight_seed": np.int64(gl["weight_seed"]), "fc_bias_extra": gl["fc_bias_extra"]}
+    for beam in beams:
+        toks = reference_rnnt_beam(f, f_len, cfg["decoder_params"], cfg["joint_params"], sd, beam, reference_lm(lm_params, lm_sd, False),
+                                   RNNT_BEAM_LM["lm_weight"], RNNT_BEAM_LM["lm_tmp"])
+        arrs["tokens_b%d" % beam], arrs["offsets_b%d" % beam] = pack_labels(toks)
+        print("  %s + TinyLM beam %d: tokens per utterance %s (frames %s)" % (name, beam, [len(t) for t in toks], f_len.tolist()))
+    save("rnnt_beam_lm_" + name, **arrs)
 
 
 RNNT_LATTICE = (("TinyTransducer", (5, 0, 9, 3), 501), ("EfficientConformerTransducerMedium", (17, 30), 502))
@@ -431,6 +459,8 @@ def main():
         return rnnt_goldens(enc_mod)
     if "--only-rnnt-beam" in sys.argv:
         return rnnt_beam_goldens()
+    if "--only-rnnt-beam-lm" in sys.argv:
+        return rnnt_beam_lm_goldens()
     if "--only-rnnt-lattice" in sys.argv:
         return rnnt_lattice_goldens()
     if "--only-lm" in sys.argv:
@@ -457,6 +487,7 @@ def main():
         arrs["labels"], arrs["label_offsets"] = lab, offs
         save("tiny_T%d" % tm, **arrs)
     lm_goldens()
+    rnnt_beam_lm_goldens()                                   # reads lm_TinyLM.npz
 
     # ---- 2. EfficientConformerCTCSmall, B=4, Tm=1001, ragged
     mel, ln = synth.make_mel(4, 80, 1001, [1001, 900, 800, 700], seed=4321)
