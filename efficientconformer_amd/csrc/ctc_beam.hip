@@ -17,6 +17,22 @@
 //   * Prefix identity is string identity: an append-only trie of (parent node, token) in the workspace with a (parent, token) -> node hash
 //     index, so a prefix that leaves the beam and comes back gets its old node, and "P c is a member" is a compare of (parent, token).
 // All arithmetic of an utterance is in a fixed order, so its results do not depend on the batch, the T padding or the run.
+//
+// With a neural LM (effconf_ctc_beam_lm, ctc_beam_lm_kernel: ctc_beam_search.h with LM = true): candidates are ranked by
+//   total(Q) = s(Q) + lm_weight * L(Q) + length_bonus * |Q|      (fp32, every operation rounded on its own, in that order)
+// with L(()) = 0, L(P c) = L(P) + row_P[c], row_P = log softmax(fc(h_P) / lm_tmp), h_P the LSTM state after [0] + P.  L is stored in the trie node when the
+// node is created, so every later use of the prefix sees the same bits.  The acoustic recursion is untouched.
+//   * Exact pruning: a member's plain extensions score total(P) + lp[c] + w row_P[c] + bonus (up to rounding): only its `beam` best by a_P[c] = lp[c] + w row_P[c]
+//     can survive.  The select is per member (one wave per member: `beam` rounds of a wave-wide maximum over the plain tokens, order a desc, id asc); the
+//     frame-global top-K is not used.  Rows are read from the member's LM slot in global memory (L2), never staged in LDS.
+//   * LM slots: an utterance has 2 beam + 1 slots of the node layout ecdec::lm_columns_step reads and writes (state, then the row).  Slot 0 is the empty
+//     prefix's for the whole call.  A member keeps its slot while it stays in the beam; a candidate that enters the beam as an extension takes the lowest slot
+//     of 1 .. 2 beam that no member of the OLD beam holds (its parent is one of them and must stay valid until the LM step has run; the survivors are among
+//     them too).  The old beam holds at most `beam` of these slots and at most `beam` candidates enter, so 2 beam slots plus the root always suffice.
+//   * Rounds: when a frame's new beam holds members without a row, the workgroup saves its beam to the resume record, writes one request (token, parent's
+//     slot, its slot, live) per rank, counts itself in the round counter and exits; the host runs ONE LM step for the requests of all utterances and
+//     launches again.  On resume the raw logits rows are turned into log-softmax rows in the slots (one wave per row).  An utterance whose new beam needs no
+//     LM goes on in the same launch; a finished utterance's workgroup returns at once; the hash index is initialised in the first launch only.
 #include "decode_common.h"
 
 #include <cmath>
@@ -51,6 +67,22 @@ struct CtcBeamArgs {
     int* tokens; int* token_len; float* score;
 };
 
+// the fused search's side of the arguments (empty for the plain search)
+struct CtcLmSide {
+    int4* req;               // [B][beam] requests of the round: token, source slot, destination slot, live
+    const int* slot;         // [B * beam] packed column of every request of the last LM step
+    const float* logits;     // [packed column][V] raw logits rows of the last LM step
+    int* resume;             // [B][CTC_LM_RESUME_INTS]; [0]: 0 start, 1 suspended, 2 finished
+    int* active;             // utterances suspended in this launch
+    size_t lmnodes, trace2;  // offsets inside an utterance
+    int nls;                 // floats of a slot's state; its row follows
+    float w, tmp, bonus;
+    float* total; float* lm_score;
+};
+
+enum { R_PHASE = 0, R_FRAME, R_N, R_NN, R_NCLO, R_NCHI, R_NREQ };
+static_assert(R_NREQ < CTC_LM_RESUME_HEAD, "resume record");
+
 // logaddexp in the log1pf form of the prefix beam search this kernel follows; rnnt_align.hip's lse2 and ctc_align.hip's lse3 are the logf form of the losses
 // they follow: different formulas on purpose
 __device__ __forceinline__ float lse(float a, float b) {
@@ -80,310 +112,45 @@ __device__ __forceinline__ unsigned long long hload(const unsigned long long* p)
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// a + w x and total(Q) with every operation rounded on its own, in the order of model_ctc.select_nbest.  The pragma: the compiler's default contraction would
+// fuse a product into the sum that follows it (also through the _rn intrinsics, which are plain operators)
+__device__ __forceinline__ float lm_scaled_sum(float a, float w, float x) {
+#pragma clang fp contract(off)
+    const float wx = w * x;
+    return a + wx;
+}
+
+__device__ __forceinline__ float fused_total(float s, float L, int len, float w, float bonus) {
+#pragma clang fp contract(off)
+    const float bl = bonus * (float)len;
+    return lm_scaled_sum(s, w, L) + bl;
+}
+
+// ctc_beam_search.h is the search itself
 __global__ __launch_bounds__(CT) void ctc_beam_kernel(const CtcBeamArgs a) {
-    __shared__ float slp[MAXV];                   // the frame's log-probabilities
-    __shared__ int spos[MAXV];                    // token -> position in the frame's top-K list, -1 otherwise
-    __shared__ unsigned hist[2][256];
-    __shared__ unsigned long long selk[MAXK];     // top-K tokens, unordered: (okey(lp) << 32) | ~id, larger = earlier
-    __shared__ int stop[MAXK];                    // top-K tokens in (lp desc, id asc) order
-    __shared__ float sredm[CNW], sreds[CNW];
-    __shared__ int sscan[CNW];
-    // the beam, double buffered by frame parity, rank order
-    __shared__ int bnode[2][MAXB], blast[2][MAXB], bpar[2][MAXB], bdep[2][MAXB];
-    __shared__ float bpb[2][MAXB], bpnb[2][MAXB], bs[2][MAXB];
-    __shared__ int bpm[MAXB];                     // rank of the member whose prefix is this member's parent, -1: none
-    __shared__ unsigned bexcl[MAXB][3];           // top-K positions that are not plain extensions of the member
-    // candidates: [0, n) members, [n, 2n) repeat extensions, [2n, 2n + n beam) plain extensions (member i: 2n + i beam + r)
-    __shared__ float cs[MAXS], cpb[MAXS], cpnb[MAXS];
-    __shared__ int ck[MAXS];                      // ((last token + 1) << 16) | canonical index; INT_MAX: empty slot
-    __shared__ unsigned long long ckey[MAXS];     // cand_key(cs, ck); 0: empty slot
-    __shared__ int nsel[MAXB];                    // candidate slot of each rank of the next beam
-    __shared__ int s_n, s_nn, s_nsel, s_nvalid, s_digit, s_need;
+    constexpr bool LM = false;
+    const CtcLmSide fz{};
+#include "ctc_beam_search.h"
+}
 
-    const CtcBeamLayout& L = a.L;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.x, V = a.V, beam = a.beam, T = a.T;
-    const int K = 2 * beam + 1 < V ? 2 * beam + 1 : V;
-    long long lenll = a.lens[b];
-    const int len = lenll < 0 ? 0 : (lenll > T ? T : (int)lenll);
-    char* base = a.utt + (size_t)b * L.per_utt;
-    int4* trace = reinterpret_cast<int4*>(base + L.trace);
-    int4* nodes = reinterpret_cast<int4*>(base + L.nodes);
-    unsigned long long* hkeys = reinterpret_cast<unsigned long long*>(base + L.hkeys);
-    int* hvals = reinterpret_cast<int*>(base + L.hvals);
-    const unsigned hmask = (unsigned)L.hcap - 1;
-    const float* lrow = a.logits + (size_t)b * T * V;
+__global__ __launch_bounds__(CT) void ctc_beam_lm_kernel(const CtcBeamArgs a, const CtcLmSide fz) {
+    constexpr bool LM = true;
+#include "ctc_beam_search.h"
+}
 
-    for (int i = tid; i < L.hcap; i += CT) __hip_atomic_store(hkeys + i, HEMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int i = tid; i < MAXV; i += CT) spos[i] = -1;
-    hist[0][tid] = 0u;
-    if (tid == 0) {
-        nodes[0] = make_int4(-1, -1, 0, 0);
-        bnode[0][0] = 0; blast[0][0] = -1; bpar[0][0] = -1; bdep[0][0] = 0;
-        bpb[0][0] = 0.f; bpnb[0][0] = -INFINITY; bs[0][0] = 0.f;
-        s_n = 1; s_nn = 1; s_nsel = 0; s_nvalid = 0;
-    }
-    float nx[TPT];
-#pragma unroll
-    for (int q = 0; q < TPT; ++q) {
-        const int v = tid * TPT + q;
-        nx[q] = (len > 0 && v < V) ? lrow[v] : 0.f;
-    }
-    int cur = 0;
-    long long ncand = 0;
-    __syncthreads();
+// before the first search launch: every utterance asks for the empty prefix's row, request (token 0, no source, slot 0) at rank 0
+__global__ __launch_bounds__(256) void ctc_beam_lm_root_kernel(int4* req, int ncol, int beam) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < ncol) req[i] = i % beam == 0 ? make_int4(0, -1, 0, 1) : make_int4(0, 0, 0, 0);
+}
 
-    for (int t = 0; t < len; ++t) {
-        float x[TPT];
-#pragma unroll
-        for (int q = 0; q < TPT; ++q) x[q] = nx[q];
-        if (t + 1 < len) {                         // prefetch frame t + 1 under this frame's work
-#pragma unroll
-            for (int q = 0; q < TPT; ++q) {
-                const int v = tid * TPT + q;
-                if (v < V) nx[q] = lrow[(size_t)(t + 1) * V + v];
-            }
-        }
-        // ---- lp = (x / tmp).softmax().log() in fp32
-        float m = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < TPT; ++q) {
-            const int v = tid * TPT + q;
-            x[q] = x[q] / a.tmp;
-            if (v < V) m = fmaxf(m, x[q]);
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if (lane == 0) sredm[wave] = m;
-        __syncthreads();
-        m = sredm[0];
-#pragma unroll
-        for (int w = 1; w < CNW; ++w) m = fmaxf(m, sredm[w]);
-        float e[TPT], ssum = 0.f;
-#pragma unroll
-        for (int q = 0; q < TPT; ++q) {
-            const int v = tid * TPT + q;
-            e[q] = v < V ? expf(x[q] - m) : 0.f;
-            ssum += e[q];
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) ssum += __shfl_xor(ssum, o);
-        if (lane == 0) sreds[wave] = ssum;
-        __syncthreads();
-        ssum = sreds[0];
-#pragma unroll
-        for (int w = 1; w < CNW; ++w) ssum += sreds[w];
-        unsigned key[TPT];
-#pragma unroll
-        for (int q = 0; q < TPT; ++q) {
-            const int v = tid * TPT + q;
-            key[q] = 0u;
-            if (v < V) {
-                const float l = logf(e[q] / ssum);
-                slp[v] = l;
-                key[q] = okey(l);
-            }
-        }
-        // ---- radix select: the K-th largest key (8 bits per pass); `need` = how many keys equal to it are taken
-        unsigned prefix = 0u, pmask = 0u;
-        int need = K;
-        for (int pass = 0; pass < 4; ++pass) {
-            const int shift = 24 - 8 * pass;
-            unsigned* h = hist[pass & 1];
-#pragma unroll
-            for (int q = 0; q < TPT; ++q)
-                if (tid * TPT + q < V && (key[q] & pmask) == prefix) atomicAdd(h + ((key[q] >> shift) & 255u), 1u);
-            hist[(pass + 1) & 1][tid] = 0u;
-            __syncthreads();
-            if (wave == 0) {                       // lane l holds digits 255 - 4 l .. 252 - 4 l (descending)
-                unsigned hv[4], c = 0u;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { hv[j] = h[255 - 4 * lane - j]; c += hv[j]; }
-                const int incl = wave_incl_scan((int)c, lane), excl = incl - (int)c;
-                if (excl < need && incl >= need) {
-                    int cum = excl, j = 0;
-                    while (cum + (int)hv[j] < need) { cum += (int)hv[j]; ++j; }
-                    s_digit = 255 - 4 * lane - j;
-                    s_need = need - cum;
-                }
-            }
-            __syncthreads();
-            prefix |= (unsigned)s_digit << shift;
-            pmask |= 255u << shift;
-            need = s_need;
-        }
-        // ---- the K tokens: keys above the threshold, and the `need` lowest ids among the keys equal to it
-        int nt = 0;
-#pragma unroll
-        for (int q = 0; q < TPT; ++q) nt += (tid * TPT + q < V && key[q] == prefix);
-        const int incl = wave_incl_scan(nt, lane);
-        if (lane == 63) sscan[wave] = incl;
-        __syncthreads();
-        int toff = incl - nt;
-        for (int w = 0; w < wave; ++w) toff += sscan[w];
-#pragma unroll
-        for (int q = 0; q < TPT; ++q) {
-            const int v = tid * TPT + q;
-            if (v >= V) continue;
-            bool sel = key[q] > prefix;
-            if (key[q] == prefix) { sel = toff < need; ++toff; }
-            if (sel) selk[atomicAdd(&s_nsel, 1)] = ((unsigned long long)key[q] << 32) | (0xffffffffu - (unsigned)v);
-        }
-        const int n = s_n;
-        // parent member of every member (a compare of nodes: node identity is string identity)
-        if (tid < n) {
-            const int par = bpar[cur][tid];
-            int pm = -1;
-            if (par >= 0)
-                for (int j = 0; j < n; ++j) if (bnode[cur][j] == par) pm = j;
-            bpm[tid] = pm;
-        }
-        __syncthreads();
-        if (tid < K) {                             // order the K tokens by (lp desc, id asc): one 64-bit compare per pair
-            const unsigned long long kv = selk[tid];
-            int r = 0;
-#pragma unroll 8
-            for (int j = 0; j < K; ++j) r += selk[j] > kv;
-            const int v = (int)(0xffffffffu - (unsigned)kv);
-            stop[r] = v;
-            spos[v] = r;
-        }
-        const int S = 2 * n + n * beam;
-        for (int j = 2 * n + tid; j < S; j += CT) { ck[j] = 0x7fffffff; ckey[j] = 0ull; }
-        __syncthreads();
-        // ---- members: exclusion masks, the member candidate (merges included) and the repeat extension
-        if (tid < n) {
-            const int i = tid, li = blast[cur][i];
-            unsigned ex[3] = {0u, 0u, 0u};
-            auto setb = [&](int p) { if (p >= 0) ex[p >> 5] |= 1u << (p & 31); };
-            setb(spos[0]);
-            if (li >= 0) setb(spos[li]);
-            bool rep = li >= 0;
-            for (int k = 0; k < n; ++k)
-                if (bpm[k] == i) {
-                    const int lk = blast[cur][k];
-                    setb(spos[lk]);
-                    if (lk == li) rep = false;     // P last(P) is a member: the repeat term goes to that member
-                }
-            bexcl[i][0] = ex[0]; bexcl[i][1] = ex[1]; bexcl[i][2] = ex[2];
-            const float si = bs[cur][i];
-            float nb = li >= 0 ? slp[li] + bpnb[cur][i] : -INFINITY;
-            const int pm = bpm[i];
-            if (pm >= 0) nb = lse(nb, slp[li] + (li == blast[cur][pm] ? bpb[cur][pm] : bs[cur][pm]));
-            const float bb = slp[0] + si;
-            cs[i] = lse(bb, nb); cpb[i] = bb; cpnb[i] = nb; ck[i] = ((li + 1) << 16) | i; ckey[i] = cand_key(cs[i], ck[i]);
-            if (rep) {
-                const float r = slp[li] + bpb[cur][i];
-                cs[n + i] = r; cpb[n + i] = -INFINITY; cpnb[n + i] = r; ck[n + i] = ((li + 1) << 16) | (n + i * V + li);
-                ckey[n + i] = cand_key(r, ck[n + i]);
-            } else {
-                ck[n + i] = 0x7fffffff; ckey[n + i] = 0ull;
-            }
-        }
-        __syncthreads();
-        // ---- plain extensions: member i's r-th plain token in top-K order, r < beam
-        for (int j = tid; j < n * K; j += CT) {
-            const int i = j / K, p = j - i * K;
-            const unsigned w = bexcl[i][p >> 5];
-            if (w & (1u << (p & 31))) continue;
-            int r = __popc(~w & ((1u << (p & 31)) - 1u));
-            for (int q = 0; q < (p >> 5); ++q) r += __popc(~bexcl[i][q]);
-            if (r >= beam) continue;
-            const int c = stop[p], slot = 2 * n + i * beam + r;
-            const float nb = slp[c] + bs[cur][i];
-            const int k = ((c + 1) << 16) | (n + i * V + c);
-            cs[slot] = nb; cpb[slot] = -INFINITY; cpnb[slot] = nb; ck[slot] = k; ckey[slot] = cand_key(nb, k);
-        }
-        __syncthreads();
-        if (tid < K) spos[stop[tid]] = -1;
-        // ---- selection: rank = number of candidates before this one (one 64-bit compare per pair; empty slots never count)
-        for (int j = tid; j < S; j += CT) {
-            const unsigned long long kj = ckey[j];
-            if (kj == 0ull) continue;
-            int r = 0;
-#pragma unroll 8
-            for (int q = 0; q < S; ++q) r += ckey[q] > kj;
-            if (r < beam) nsel[r] = j;
-            atomicAdd(&s_nvalid, 1);
-        }
-        __syncthreads();
-        // ---- the next beam: nodes of new prefixes (old node if the string was seen before), trace
-        if (wave == 0) {
-            const int nv = s_nvalid, nnew = nv < beam ? nv : beam, nn0 = s_nn, nxt = cur ^ 1;
-            int node = -1, last = -1, par = -1, dep = 0;
-            float pb = -INFINITY, pnb = -INFINITY, sc = -INFINITY;
-            bool isnew = false;
-            unsigned long long hk = 0ull;
-            if (lane < nnew) {
-                const int j = nsel[lane], kj = ck[j], idx = kj & 0xffff;
-                pb = cpb[j]; pnb = cpnb[j]; sc = cs[j];
-                if (idx < n) {
-                    node = bnode[cur][idx]; last = blast[cur][idx]; par = bpar[cur][idx]; dep = bdep[cur][idx];
-                } else {
-                    const int i = (idx - n) / V, c = idx - n - i * V;
-                    par = bnode[cur][i]; last = c; dep = bdep[cur][i] + 1;
-                    hk = ((unsigned long long)(unsigned)par << 32) | (unsigned)c;
-                    unsigned sl = hash_slot(par, c, hmask);
-                    for (unsigned pr = 0; pr <= hmask; ++pr) {
-                        const unsigned long long k = hload(hkeys + sl);
-                        if (k == hk) { node = __hip_atomic_load(hvals + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-                        if (k == HEMPTY) break;
-                        sl = (sl + 1) & hmask;
-                    }
-                    isnew = node < 0;
-                }
-            }
-            const unsigned long long nm = __ballot(isnew);
-            if (isnew) {
-                node = nn0 + __popcll(nm & ((1ull << lane) - 1ull));
-                nodes[node] = make_int4(par, last, dep, 0);
-                unsigned sl = hash_slot(par, last, hmask);
-                for (unsigned pr = 0; pr <= hmask; ++pr) {
-                    if (atomicCAS(hkeys + sl, HEMPTY, hk) == HEMPTY) {
-                        __hip_atomic_store(hvals + sl, node, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                    sl = (sl + 1) & hmask;
-                }
-            }
-            if (lane < beam) trace[(size_t)t * beam + lane] = make_int4(node, __float_as_int(pb), __float_as_int(pnb), __float_as_int(sc));
-            if (lane < nnew) {
-                bnode[nxt][lane] = node; blast[nxt][lane] = last; bpar[nxt][lane] = par; bdep[nxt][lane] = dep;
-                bpb[nxt][lane] = pb; bpnb[nxt][lane] = pnb; bs[nxt][lane] = sc;
-            }
-            if (lane == 0) {
-                ncand += nv;
-                s_nn = nn0 + __popcll(nm); s_n = nnew; s_nvalid = 0; s_nsel = 0;
-            }
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-    // ---- outputs in rank order: tokens by walking the trie from each member's node
-    const int n = s_n;
-    if (tid < beam) {
-        int* out = a.tokens + ((size_t)b * beam + tid) * T;
-        int d = 0;
-        float sc = -INFINITY;
-        if (tid < n) {
-            d = bdep[cur][tid];
-            sc = bs[cur][tid];
-            int node = bnode[cur][tid];
-            for (int i = d - 1; i >= 0; --i) { const int4 nd = nodes[node]; out[i] = nd.y; node = nd.x; }
-        }
-        a.token_len[(size_t)b * beam + tid] = d;
-        a.score[(size_t)b * beam + tid] = sc;
-    }
-    for (int j = tid; j < beam * T; j += CT) {
-        const int r = j / T, i = j - r * T;
-        if (i >= (r < n ? bdep[cur][r] : 0)) a.tokens[((size_t)b * beam + r) * T + i] = 0;
-    }
-    if (tid == 0) {
-        a.stats[4 * b + 0] = len;
-        a.stats[4 * b + 1] = (int)(ncand < 0x7fffffffll ? ncand : 0x7fffffffll);
-        a.stats[4 * b + 2] = s_nn;
-        a.stats[4 * b + 3] = 0;
-    }
+// the fused entry's own rules, after ctc_beam_check; *mc: the LM's config
+const char* ctc_beam_lm_check(const EcLm* lm, int32_t batch, int32_t vocab, int32_t beam, const EcLmConfig** mc) {
+    *mc = lm_handle_config(lm, false);
+    if (!*mc) return "ctc beam search: null lm handle";
+    if ((*mc)->vocab_size != vocab) return "ctc beam search: the LM's vocab_size differs from vocab";
+    if ((int64_t)batch * beam > (1 << 21)) return "ctc beam search: batch * beam must be at most 2^21 with an LM";
+    return nullptr;
 }
 
 }  // namespace
@@ -411,6 +178,63 @@ int effconf_ctc_beam(const float* logits, const int64_t* out_len, int32_t batch,
     a.tokens = tokens; a.token_len = token_len; a.score = score;
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(batch), dim3(CT), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : ec_fail("ctc_beam launch failed");
+}
+
+size_t effconf_ctc_beam_lm_workspace_bytes(const EcLm* lm, int32_t batch, int32_t t_out, int32_t vocab, int32_t beam) {
+    if (const char* e = ctc_beam_check(batch, t_out, vocab, beam)) { ec_fail(e); return 0; }
+    const EcLmConfig* mc;
+    if (const char* e = ctc_beam_lm_check(lm, batch, vocab, beam, &mc)) { ec_fail(e); return 0; }
+    return ctc_beam_lm_layout(*mc, batch, t_out, beam).total;
+}
+
+int effconf_ctc_beam_lm(EcLm* lm, const float* logits, const int64_t* out_len, int32_t batch, int32_t t_out, int32_t vocab, int32_t beam,
+                        float temperature, float lm_weight, float lm_tmp, float length_bonus, int32_t* tokens, int32_t* token_len, float* total,
+                        float* am_score, float* lm_score, int32_t* rounds_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const char* e = ctc_beam_check(batch, t_out, vocab, beam)) return ec_fail(e);
+    const EcLmConfig* mc;
+    if (const char* e = ctc_beam_lm_check(lm, batch, vocab, beam, &mc)) return ec_fail(e);
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return ec_fail("ctc beam search: temperature must be > 0");
+    if (!(lm_weight > 0.f) || !std::isfinite(lm_weight)) return ec_fail("ctc beam search: lm_weight must be > 0 (0: effconf_ctc_beam)");
+    if (!(lm_tmp > 0.f) || !std::isfinite(lm_tmp)) return ec_fail("ctc beam search: lm_tmp must be > 0");
+    if (!std::isfinite(length_bonus)) return ec_fail("ctc beam search: length_bonus must be finite");
+    if (!lm_handle_config(lm, true)) return ec_fail("ctc beam search: lm handle not finalized");
+    if (rounds_out) *rounds_out = 0;
+    if (batch == 0) return 0;
+    if (!out_len || !token_len || !total || !am_score || !lm_score || !workspace || (t_out > 0 && (!logits || !tokens))) return ec_fail("null argument");
+    const CtcBeamLmLayout L = ctc_beam_lm_layout(*mc, batch, t_out, beam);
+    if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_ctc_beam_lm_workspace_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = WsPlan::base(workspace);
+    CtcBeamArgs a{};
+    a.logits = logits; a.lens = out_len; a.T = t_out; a.V = vocab; a.beam = beam; a.tmp = temperature;
+    a.utt = ws + L.s.utt; a.stats = reinterpret_cast<int*>(ws + L.s.stats); a.L = L.s;
+    a.tokens = tokens; a.token_len = token_len; a.score = am_score;
+    CtcLmSide fz{};
+    fz.req = reinterpret_cast<int4*>(ws + L.req); fz.slot = reinterpret_cast<const int*>(ws + L.slot); fz.logits = reinterpret_cast<const float*>(ws + L.logits);
+    fz.resume = reinterpret_cast<int*>(ws + L.resume); fz.active = reinterpret_cast<int*>(ws + L.counter);
+    fz.lmnodes = L.lmnodes; fz.trace2 = L.trace2; fz.nls = L.nls; fz.w = lm_weight; fz.tmp = lm_tmp; fz.bonus = length_bonus;
+    fz.total = total; fz.lm_score = lm_score;
+    const int ncol = batch * beam;
+    LmColumns col{};
+    col.req = fz.req; col.ncol = ncol; col.cols_per_utt = beam; col.slot = reinterpret_cast<int*>(ws + L.slot);
+    col.utt = a.utt; col.per_utt = L.s.per_utt; col.lmnodes = L.lmnodes; col.node_floats = L.nls + L.vocab; col.logits = reinterpret_cast<float*>(ws + L.logits);
+    if (hipMemsetAsync(fz.resume, 0, (size_t)batch * CTC_LM_RESUME_INTS * 4, s) != hipSuccess) return ec_fail("ctc beam search: clearing the resume records failed");
+    hipLaunchKernelGGL(ctc_beam_lm_root_kernel, dim3((ncol + 255) / 256), dim3(256), 0, s, fz.req, ncol, beam);
+    if (hipGetLastError() != hipSuccess) return ec_fail("ctc_beam_lm_root launch failed");
+    if (lm_columns_step(lm, col, ws + L.lm, s) != 0) return ec_fail("ctc beam search: LM step launch failed");
+    // every launch advances each unfinished utterance by at least one frame; the last one finds nothing suspended
+    for (int round = 0;; ++round) {
+        if (round >= t_out + 2) return ec_fail("ctc beam search: the rounds did not end (internal error)");
+        if (hipMemsetAsync(fz.active, 0, 4, s) != hipSuccess) return ec_fail("ctc beam search: clearing the round counter failed");
+        hipLaunchKernelGGL(ctc_beam_lm_kernel, dim3(batch), dim3(CT), 0, s, a, fz);
+        if (hipGetLastError() != hipSuccess) return ec_fail("ctc_beam_lm launch failed");
+        int active = 0;
+        if (hipMemcpyAsync(&active, fz.active, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return ec_fail("ctc beam search: reading the round counter failed");
+        if (rounds_out) *rounds_out = round + 1;
+        if (active == 0) return 0;
+        if (lm_columns_step(lm, col, ws + L.lm, s) != 0) return ec_fail("ctc beam search: LM step launch failed");
+    }
 }
 
 }  // extern "C"

@@ -194,6 +194,49 @@ inline CtcBeamLayout ctc_beam_layout(int batch, int t_out, int beam) {
     return L;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- ctc_beam.hip with a neural LM (shallow fusion)
+// The search's regions, and per utterance: a second trace {f32 L, f32 total} per frame and rank, and 2 * beam + 1 LM slots of the node layout lm_columns_step
+// reads and writes ([layer][h k-permuted | c], 2 * layers * dim_model floats, then the slot's row: vocab floats).  Per call: one request (token, source slot,
+// destination slot, live) per rank of every utterance's beam with its packed column + the packed columns' tokens (slot); one resume record per utterance; the
+// round's counter of suspended utterances; the dense state of one LM step over batch * beam columns (lm_layout) and its raw logits rows.
+constexpr int CTC_LM_MAXB = 32;                                          // ctc_beam.hip's largest beam
+constexpr int CTC_LM_RESUME_HEAD = 16;    // phase, next frame, members, trie nodes, candidates (lo, hi), LM rows asked for, then unused
+constexpr int CTC_LM_RESUME_INTS = CTC_LM_RESUME_HEAD + 10 * CTC_LM_MAXB;    // then node, last, parent, depth, pb, pnb, s, L, slot, row pending: [32] each
+
+struct CtcBeamLmLayout {
+    CtcBeamLayout s;                                                     // s.total is not set: `total` below is the call's size
+    int nls, vocab, nslots;                                              // floats of an LM slot's state (its row follows), slots per utterance
+    size_t trace2, lmnodes;                                              // inside an utterance
+    size_t req, slot, resume, counter, lm, logits, total;
+    LmLayout lml;                                                        // offsets from `lm`
+};
+
+inline CtcBeamLmLayout ctc_beam_lm_layout(const EcLmConfig& m, int batch, int t_out, int beam) {
+    CtcBeamLmLayout L{};
+    L.s = ctc_beam_layout(batch, t_out, beam);
+    WsPlan u;                                                            // one utterance: the plain search's regions at their offsets, then the LM's
+    u.take(L.s.per_utt);
+    L.nls = 2 * m.num_layers * m.dim_model;
+    L.vocab = m.vocab_size;
+    L.nslots = 2 * beam + 1;
+    L.trace2 = u.take((size_t)t_out * beam * 8);
+    L.lmnodes = u.take((size_t)L.nslots * (L.nls + L.vocab) * 4);
+    L.s.per_utt = u.stride();
+    const int ncol = batch * beam;
+    L.lml = lm_layout(m, ncol);
+    WsPlan p;
+    L.s.stats = p.take((size_t)batch * 16);
+    L.s.utt = p.take((size_t)batch * L.s.per_utt);
+    L.req = p.take((size_t)ncol * 16);
+    L.slot = p.take((size_t)ncol * 8);
+    L.resume = p.take((size_t)batch * CTC_LM_RESUME_INTS * 4);
+    L.counter = p.take(4);
+    L.lm = p.take(L.lml.total - 256);                                    // a sub-plan: its own slack is not needed inside an aligned region
+    L.logits = p.take((size_t)ncol * m.vocab_size * 4);
+    L.total = p.total();
+    return L;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- ctc_align.hip
 constexpr int CTC_ALIGN_THREADS = 256;            // threads per utterance
 

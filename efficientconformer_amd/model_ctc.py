@@ -6,15 +6,17 @@
 (effconf_ctc_greedy) instead of ``nn.Linear`` + a Python loop with ``.item()`` per token.
 ``beam_search_decoding`` (model_ctc.py:138-181) is ctcdecode's CTC prefix beam search without the n-gram scorer: the head's
 fp32 logits go to one persistent HIP kernel per batch (effconf_ctc_beam, one workgroup per utterance) instead of a host copy and
-8 CPU processes.  The n-gram (KenLM) terms (``ngram_path``, ``ngram_alpha``, ``ngram_beta``), neural-LM fusion inside the search,
+8 CPU processes.  The n-gram (KenLM) terms (``ngram_path``, ``ngram_alpha``, ``ngram_beta``) and
 probability cutoffs below the shipped ones are not implemented; a ``LanguageModel`` attached as ``lm`` rescores the search's ranked n-best after
-it (``rescore_nbest``, ``beam_labels_rescored``, ``beam_search_rescored``; csrc/lm.hip).  Token timestamps and transcript scores come from the forced alignment instead:
+it (``rescore_nbest``, ``beam_labels_rescored``, ``beam_search_rescored``; csrc/lm.hip) or is fused INTO the search (``decode_logits_beam_lm``,
+``beam_labels_fused``, ``beam_search_fused``; effconf_ctc_beam_lm: every frame's candidates are ranked with the LM's score of the prefix).  Token timestamps and transcript scores come from the forced alignment instead:
 ``align`` / ``greedy_alignment`` (Viterbi over the CTC trellis: which frames each token covers) and ``score_labels`` (the CTC forward
 algorithm: log P(y | x), -ctc_loss without the host copy) run on the same logits in csrc/ctc_align.hip (effconf_ctc_align).  Training
 (losses with gradients, optimizer, schedules), WER scoring and word-level (SentencePiece-merging) timestamps are out of scope (HISTORY.md).
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import List, NamedTuple, Optional
 
 import numpy as np
@@ -58,6 +60,9 @@ class HeadMargins(NamedTuple):
 # over tools/label_exact_band.py's grid (profiles/label_exact_band.txt), rounded up to two digits: the worst spread, 2.97, comes from the
 # "trained" weight recipe of synth.make_stressed_state_dict on EfficientConformerCTCLarge (make_state_dict alone: 0.084).
 LABEL_EXACT_BAND = 6.0
+# Largest workspace of one effconf_ctc_beam_lm call: ``decode_logits_beam_lm`` splits the batch into chunks that stay under it (an utterance holds
+# 2 * beam + 1 LM slots of 2 * layers * dim_model + vocab floats; rows are independent)
+BEAM_LM_WORKSPACE_CAP = 16 << 30
 
 
 def select_rerun(min_margin: torch.Tensor, band: float) -> torch.Tensor:
@@ -105,6 +110,7 @@ class ModelCTC(_native.NativeModel):
         self.tokenizer = tokenizer
         self.name = name
         self._beam_ws = None
+        self._beam_rounds = None
         # the reference's attribute and decoding_params (model.py:70-72): a LanguageModel attached by the caller; rescoring only.  Assigning one
         # registers it as a submodule, as in the reference: state_dict() then carries its tensors under ``lm.``
         self.lm = None
@@ -353,17 +359,16 @@ class ModelCTC(_native.NativeModel):
             _lib.check(lib.effconf_ctc_beam(logits.data_ptr(), logits_len.data_ptr(), b, t, v, beam, float(self.tmp), tokens.data_ptr(),
                                             token_len.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
                                             torch.cuda.current_stream(logits.device).cuda_stream), "ctc_beam")
-        self._beam_ws = (ws, b, t, beam)
+        self._beam_ws, self._beam_rounds = ([(ws, b)], b, t, beam, 0), None
         return tokens, token_len, score
 
     def last_beam_trace(self) -> List[dict]:
-        """The workspace of the last decode_logits_beam call (layout: include/effconf.h), one dict per utterance: ``len`` (frames
-        decoded), ``candidates`` (candidates scored, summed over frames), ``node`` (len, beam) i32 and ``pb`` / ``pnb`` / ``score``
+        """The workspace of the last decode_logits_beam / decode_logits_beam_lm call (layout: include/effconf.h), one dict per utterance: ``len``
+        (frames decoded), ``candidates`` (candidates scored, summed over frames), ``lm_rows`` (LM evaluations the utterance asked for; 0: plain search), ``node`` (len, beam) i32 and ``pb`` / ``pnb`` / ``score``
         (len, beam) f32 = the beam after each frame in rank order (node -1: no member), ``parent`` / ``token`` / ``length`` (nodes,)
-        i32 = the prefix trie (node 0: the empty prefix)."""
-        ws, b, t, beam = self._beam_ws
-        raw = ws.cpu().numpy()
-        base = (-ws.data_ptr()) % 256                                  # the library aligns the workspace up to 256 bytes
+        i32 = the prefix trie (node 0: the empty prefix).  After a fused call also ``lm`` / ``total`` (len, beam) f32 = L and the total the ranks
+        are ordered by, and ``node_lm`` (nodes,) f32 = the L every trie node holds."""
+        chunks, _, t, beam, slot_floats = self._beam_ws
 
         def al(x):
             return (x + 255) // 256 * 256
@@ -373,17 +378,28 @@ class ModelCTC(_native.NativeModel):
             h <<= 1
         o_nodes = al(16 * t * beam)
         per_utt = o_nodes + al(16 * ncap) + al(8 * h) + al(4 * h)
-        stats = raw[base:base + 16 * b].view(np.int32).reshape(b, 4)
+        o_trace2 = per_utt
+        if slot_floats:
+            per_utt += al(8 * t * beam) + al(4 * (2 * beam + 1) * slot_floats)
         out = []
-        for i in range(b):
-            u = base + al(16 * b) + i * per_utt
-            n, nn = int(stats[i, 0]), int(stats[i, 2])
-            tr = raw[u:u + 16 * t * beam].view(np.int32).reshape(t, beam, 4)[:n]
-            trf = tr.view(np.float32)
-            nd = raw[u + o_nodes:u + o_nodes + 16 * ncap].view(np.int32).reshape(ncap, 4)[:nn]
-            out.append({"len": n, "candidates": int(stats[i, 1]), "node": tr[:, :, 0].copy(), "pb": trf[:, :, 1].copy(),
-                        "pnb": trf[:, :, 2].copy(), "score": trf[:, :, 3].copy(), "parent": nd[:, 0].copy(), "token": nd[:, 1].copy(),
-                        "length": nd[:, 2].copy()})
+        for ws, b in chunks:
+            base = (-ws.data_ptr()) % 256                              # the library aligns the workspace up to 256 bytes
+            head = ws[base:base + al(16 * b)].cpu().numpy()
+            stats = head[:16 * b].view(np.int32).reshape(b, 4)
+            for i in range(b):
+                u = base + al(16 * b) + i * per_utt
+                raw = ws[u:u + o_trace2 + (8 * t * beam if slot_floats else 0)].cpu().numpy()
+                n, nn = int(stats[i, 0]), int(stats[i, 2])
+                tr = raw[:16 * t * beam].view(np.int32).reshape(t, beam, 4)[:n]
+                trf = tr.view(np.float32)
+                nd = raw[o_nodes:o_nodes + 16 * ncap].view(np.int32).reshape(ncap, 4)[:nn]
+                d = {"len": n, "candidates": int(stats[i, 1]), "lm_rows": int(stats[i, 3]), "node": tr[:, :, 0].copy(), "pb": trf[:, :, 1].copy(),
+                     "pnb": trf[:, :, 2].copy(), "score": trf[:, :, 3].copy(), "parent": nd[:, 0].copy(), "token": nd[:, 1].copy(),
+                     "length": nd[:, 2].copy()}
+                if slot_floats:
+                    t2 = raw[o_trace2:o_trace2 + 8 * t * beam].view(np.float32).reshape(t, beam, 2)[:n]
+                    d.update(lm=t2[:, :, 0].copy(), total=t2[:, :, 1].copy(), node_lm=nd[:, 3].copy().view(np.float32))
+                out.append(d)
         return out
 
     def beam_labels(self, x: torch.Tensor, x_len: Optional[torch.Tensor], beam_size: Optional[int] = None,
@@ -403,6 +419,101 @@ class ModelCTC(_native.NativeModel):
         is attached (model_ctc.py:181), otherwise the id lists.  Without the n-gram terms: the ``ngram_*`` and ``lm_*`` entries of
         decoding_params are ignored."""
         ids = self.beam_labels(x, x_len, beam_size)
+        return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
+
+    # ------------------------------------------------------------------ beam search with the neural LM fused into it
+    def _fusion(self, lm, lm_weight, lm_tmp, length_bonus):
+        """(lm or None, weight, lm_tmp, bonus) a fused search runs with: the arguments, else the attributes.  lm None: nothing to fuse (no LM, or weight
+        0) - then a non-zero bonus is an error, there is no total to add it to.  A negative or non-finite weight with an LM, lm_tmp <= 0 and a non-finite
+        bonus raise ValueError."""
+        lm = self.lm if lm is None else lm
+        weight = float(self.lm_weight if lm_weight is None else lm_weight)
+        ltmp = float(self.lm_tmp if lm_tmp is None else lm_tmp)
+        bonus = float(length_bonus)
+        if not -float("inf") < bonus < float("inf"):
+            raise ValueError("length_bonus must be finite; got %r" % (bonus,))
+        if lm is None or weight == 0:
+            if bonus != 0:
+                raise ValueError("length_bonus needs a fused search: a LanguageModel and lm_weight > 0 (rescore_nbest takes a bonus without an LM)")
+            return None, 0.0, ltmp, 0.0
+        if not 0 < weight < float("inf"):
+            raise ValueError("lm_weight must be >= 0 and finite; got %r" % (weight,))
+        if not 0 < ltmp < float("inf"):
+            raise ValueError("lm_tmp must be > 0 and finite; got %r" % (ltmp,))
+        return lm, weight, ltmp, bonus
+
+    def decode_logits_beam_lm(self, logits: torch.Tensor, logits_len: Optional[torch.Tensor], beam_size: Optional[int] = None, lm=None,
+                              lm_weight: Optional[float] = None, lm_tmp: Optional[float] = None, length_bonus: float = 0.0):
+        """CTC prefix beam search with the LanguageModel fused INTO the search (effconf_ctc_beam_lm): every frame's candidates are
+        ranked by total = am_score + lm_weight * lm_score + length_bonus * token_len, lm_score = the LM's log-probability of the prefix ->
+        (tokens (B, beam, T) i32, token_len (B, beam) i32, total, am_score, lm_score (B, beam) f32), ranked by total.  lm / lm_weight / lm_tmp None:
+        ``self.lm`` / ``decoding_params["lm_weight"]`` / ``decoding_params["lm_tmp"]``.  With no LM or weight 0 (and bonus 0) it is
+        ``decode_logits_beam`` through the plain entry: total = am_score, lm_score 0.  The batch is split into chunks whose workspace stays under
+        ``BEAM_LM_WORKSPACE_CAP`` (rows are independent).  The call synchronises once per round (``last_beam_rounds``): not while a stream is captured."""
+        lm, weight, ltmp, bonus = self._fusion(lm, lm_weight, lm_tmp, length_bonus)
+        if lm is None:
+            tokens, token_len, score = self.decode_logits_beam(logits, logits_len, beam_size)
+            return tokens, token_len, score.clone(), score, torch.zeros_like(score)
+        beam = int(self.beam_size if beam_size is None else beam_size)
+        if logits.dim() != 3:
+            raise _lib.EffconfError("logits must be (batch, frames, vocab); got shape %s" % (tuple(logits.shape),))
+        b, t, v = logits.shape
+        self._check_beam(beam, v)
+        _native.require_hip(logits)
+        _native.require_hip(lm.fc.weight)
+        if lm._cfg[0] != v:
+            raise _lib.EffconfError("the LM's vocab_size is %d, the logits have %d entries" % (lm._cfg[0], v))
+        lib = _lib.load()
+        dev = logits.device
+        with torch.cuda.device(dev):
+            lm._ensure()
+            size = lambda n: _native.sized(lib, "effconf_ctc_beam_lm", lib.effconf_ctc_beam_lm_workspace_bytes(lm._handle, n, t, v, beam),
+                                           batch=n, T=t, vocab=v, beam=beam)
+            step = max(1, b)
+            while step > 1 and size(step) > BEAM_LM_WORKSPACE_CAP:
+                step = (step + 1) // 2
+            logits = logits.contiguous().float()
+            logits_len = _native.lengths(logits_len, b, t, dev)
+            tokens = torch.empty(b, beam, t, dtype=torch.int32, device=dev)
+            token_len = torch.empty(b, beam, dtype=torch.int32, device=dev)
+            total, am, lms = (torch.empty(b, beam, dtype=torch.float32, device=dev) for _ in range(3))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            chunks, rounds_all = [], []
+            rounds = C.c_int32(0)
+            for lo in range(0, b, step):
+                n = min(step, b - lo)
+                ws = _native.workspace(size(n), dev)
+                at = lambda x: x[lo:].data_ptr() if x.numel() else x.data_ptr()
+                _lib.check(lib.effconf_ctc_beam_lm(lm._handle, at(logits), at(logits_len), n, t, v, beam, float(self.tmp), weight, ltmp, bonus,
+                                                   at(tokens), at(token_len), at(total), at(am), at(lms), C.byref(rounds), ws.data_ptr(), ws.numel(),
+                                                   stream), "ctc_beam_lm")
+                chunks.append((ws, n))
+                rounds_all.append(int(rounds.value))
+        self._beam_ws = (chunks, b, t, beam, 2 * lm._cfg[2] * lm._cfg[1] + v)
+        self._beam_rounds = rounds_all
+        return tokens, token_len, total, am, lms
+
+    def last_beam_rounds(self) -> Optional[List[int]]:
+        """Search launches of the last ``decode_logits_beam_lm`` call, one entry per chunk of the batch (an LM step ran between two of them); None after
+        a plain search, which is one launch."""
+        return self._beam_rounds
+
+    def beam_labels_fused(self, x: torch.Tensor, x_len: Optional[torch.Tensor], beam_size: Optional[int] = None, from_mel: bool = False,
+                          lm=None, lm_weight: Optional[float] = None, length_bonus: float = 0.0) -> List[List[int]]:
+        """``beam_labels`` with the attached LanguageModel fused into the search (``decode_logits_beam_lm``): the label-id sequence of the best total
+        per utterance.  With no LM attached or lm_weight == 0 (and bonus 0): exactly ``beam_labels``' result."""
+        if self._fusion(lm, lm_weight, None, length_bonus)[0] is None:
+            return self.beam_labels(x, x_len, beam_size, from_mel)
+        beam = int(self.beam_size if beam_size is None else beam_size)
+        self._check_beam(beam, self.fc.out_features)
+        logits, _, _, enc_len = self._logits(x, x_len, from_mel)
+        tokens, token_len = self.decode_logits_beam_lm(logits, enc_len, beam, lm, lm_weight, None, length_bonus)[:2]
+        tokens, token_len = tokens[:, 0].cpu(), token_len[:, 0].cpu()          # one D2H copy per batch
+        return [tokens[i, :int(token_len[i])].tolist() for i in range(tokens.shape[0])]
+
+    def beam_search_fused(self, x, x_len, beam_size=None):
+        """``beam_search_decoding`` through ``beam_labels_fused``: strings when a tokenizer is attached, otherwise the id lists."""
+        ids = self.beam_labels_fused(x, x_len, beam_size)
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
 
     # ------------------------------------------------------------------ n-best rescoring with a neural LM

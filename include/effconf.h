@@ -370,6 +370,32 @@ int effconf_rnnt_beam_lm(EcRnnt* r, EcLm* lm, const float* enc_out, const int64_
                          float* score, int32_t* status, int32_t max_tokens, int32_t* rounds_out, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* CTC prefix beam search with neural-LM shallow fusion: effconf_ctc_beam's search with the candidates of every frame ranked by
+ *   total(Q) = s(Q) + lm_weight * L(Q) + length_bonus * |Q|        (fp32, every operation rounded on its own, in this order)
+ * s(Q) = log(P_blank + P_nonblank) as in effconf_ctc_beam, L(Q) = the LM's log-probability of the token string under LanguageModel's convention (the LM reads
+ * [0, Q_0, ..]; effconf_lm_score's fp32 sum in ascending position, rows log softmax(fc(h) / lm_tmp)).  L of a prefix is computed once, when its trie node is
+ * created, and kept in the node.  Ties: total desc, last token asc, canonical index, as effconf_ctc_beam.  Exact pruning is per member: of a member's plain
+ * extensions only its `beam` best by lp[c] + lm_weight * row[c] are scored.  The reference has no such search (ctcdecode fuses KenLM only).
+ * lm: a finalized handle whose vocab_size is `vocab`; lm_weight > 0 and lm_tmp > 0, finite (weight 0 is effconf_ctc_beam); length_bonus finite;
+ * effconf_ctc_beam's limits; batch * beam <= 2^21.  Outputs, ranked by total: tokens / token_len as effconf_ctc_beam, total, am_score (= s) and lm_score (= L)
+ * dev f32 (batch, beam); ranks without a hypothesis have length 0, total and am_score -inf, lm_score 0.
+ * The search kernel (one workgroup per utterance, resumable) and one LM step over batch * beam columns (the kernels of effconf_lm_step) alternate on `stream`:
+ * an utterance whose new beam holds prefixes without an LM row saves its beam and waits; after every search launch the host reads the number of waiting
+ * utterances (4 bytes, one stream synchronise), so the call returns with the results complete and CANNOT be captured in a graph.  Every launch advances each
+ * unfinished utterance by at least one frame: at most t_out + 2 search launches; rounds_out (host, may be NULL) receives their number.  A row's results
+ * do not depend on the rows sharing the call or on the workspace's contents.
+ * Workspace (effconf_ctc_beam_lm_workspace_bytes; needs no finalized handle, 0 for arguments the call rejects), S = 2 num_layers dim_model + vocab floats:
+ *   stats as effconf_ctc_beam, the fourth word = LM rows the utterance asked for (the empty prefix's included); utterance b at al(16 batch) + b * U', U' = U + al(8 t_out beam) + al(4 (2 beam + 1) S), U and its regions as effconf_ctc_beam,
+ *   a node's fourth word = the f32 L of its prefix:
+ *     trace2 [t_out][beam]   {f32 L, f32 total} of the beam after frame t (a rank without a member: 0, -inf)
+ *     LM slots [2 beam + 1]  per slot: per layer h (k-permuted as effconf_lm_workspace_bytes describes) and c, then the slot's log-probability row [vocab]
+ *   then requests int4 [batch beam], packed columns i32 [2 batch beam], resume records i32 [batch][336], the round counter, the LM step's state
+ *   (effconf_lm_workspace_bytes' layout for batch * beam sequences) and its raw logits rows f32 [batch beam][vocab]. */
+size_t effconf_ctc_beam_lm_workspace_bytes(const EcLm* lm, int32_t batch, int32_t t_out, int32_t vocab, int32_t beam);
+int effconf_ctc_beam_lm(EcLm* lm, const float* logits, const int64_t* out_len, int32_t batch, int32_t t_out, int32_t vocab, int32_t beam,
+                        float temperature, float lm_weight, float lm_tmp, float length_bonus, int32_t* tokens, int32_t* token_len, float* total,
+                        float* am_score, float* lm_score, int32_t* rounds_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Workspace of effconf_lm_score and effconf_lm_step (the latter: any u_max, e.g. 0): 256 + al(4 n) + num_layers * 3 * Np * dim_model * 4 bytes,
  * Np = n rounded up to 64, al(x) = x rounded up to 256.  After the 256-byte aligned pointer: i32 ulen[n]; at al(4 n) per layer l the blocks
  * h[2][Np][dim_model] (k permuted within every 16: position (k & ~15) | ((k & 3) << 2) | ((k >> 2) & 3); step u reads buffer u & 1 and

@@ -133,6 +133,26 @@ int main() {
             }
         }
     }
+    const int ctclm[][3] = {{32, 32, 1}, {257, 48, 3}, {1000, 4096, 3}};
+    for (const auto& d : ctclm) {
+        EcLmConfig mc{};
+        mc.vocab_size = d[0]; mc.dim_model = d[1]; mc.num_layers = d[2];
+        for (int b : batches) for (int t : frames) for (int beam : beams) {
+            if (d[1] == 4096 && b > 19) continue;
+            const CtcBeamLmLayout L = ctc_beam_lm_layout(mc, b, t, beam);
+            const CtcBeamLayout P = ctc_beam_layout(b, t, beam);
+            const size_t ncol = (size_t)b * beam, nlm = (size_t)L.nls + L.vocab;
+            if (L.nls != 2 * d[2] * d[1] || L.vocab != d[0] || L.nslots != 2 * beam + 1) fail("LM slots that are not 2 beam + 1 of (h, c) per layer + the row", "ctc_beam_lm_layout");
+            if (L.s.trace != P.trace || L.s.nodes != P.nodes || L.s.hkeys != P.hkeys || L.s.hvals != P.hvals || L.s.ncap != P.ncap || L.s.hcap != P.hcap)
+                fail("search regions that are not ctc_beam_layout's", "ctc_beam_lm_layout");
+            check_regions("ctc_beam_lm_layout (utterance)", {{L.s.trace, (size_t)t * beam * 16}, {L.s.nodes, (size_t)L.s.ncap * 16}, {L.s.hkeys, (size_t)L.s.hcap * 8},
+                                                              {L.s.hvals, (size_t)L.s.hcap * 4}, {L.trace2, (size_t)t * beam * 8}, {L.lmnodes, (size_t)L.nslots * nlm * 4}}, L.s.per_utt);
+            const LmLayout M = lm_layout(mc, (int)ncol);
+            if (L.lml.layer != M.layer || L.lml.state != M.state) fail("an LM step state that is not lm_layout's", "ctc_beam_lm_layout");
+            check_total("ctc_beam_lm_layout", {{L.s.stats, (size_t)b * 16}, {L.s.utt, (size_t)b * L.s.per_utt}, {L.req, ncol * 16}, {L.slot, ncol * 8},
+                                               {L.resume, (size_t)b * CTC_LM_RESUME_INTS * 4}, {L.counter, 4}, {L.lm, M.total - 256}, {L.logits, ncol * d[0] * 4}}, L.total);
+        }
+    }
     std::printf("decoder_layout_sanitize: %lld layouts checked\n", checked);
     return 0;
 }
