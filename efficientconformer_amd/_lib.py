@@ -56,6 +56,15 @@ SIGNATURES = {
     "effconf_encoder_set_interctc": (C.c_int, [_P, C.POINTER(C.c_int32), _I32, _I32]),
     "effconf_encoder_set_interctc_outputs": (C.c_int, [_P, C.POINTER(C.c_void_p), _I32]),
     "effconf_interctc": (C.c_int, [_P, _I32, _F32P, _I32, _F32P, _F32P, _P, _SZ, _P]),
+    "effconf_stream_align": (_I32, [_P]),
+    "effconf_stream_state_bytes": (_SZ, [_P, _I32, _I32]),
+    "effconf_stream_create": (_P, [_P, _I32, _I32, _P, _SZ]),
+    "effconf_stream_destroy": (None, [_P]),
+    "effconf_stream_reset": (C.c_int, [_P, _I32]),
+    "effconf_stream_workspace_bytes": (_SZ, [_P, _I32, _I32, _I32]),
+    "effconf_stream_push_mel": (C.c_int, [_P, C.POINTER(C.c_int32), _I32, _P, _I32, C.POINTER(C.c_int32), _P, _I32, _P, _P, _SZ, _P]),
+    "effconf_stream_attention": (C.c_int, [_P, _P, _P, _P, _I32, _F32P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _I32, _I32, _P]),
+    "effconf_stream_dwconv": (C.c_int, [_P, _I32, _I32, _F32P, _F32P, _I32, _I32, _P, _P, _P, _P, _P, _I32, _I32, _P, _I32, _P]),
     "effconf_host_pack_rows": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), _I32, C.c_void_p, C.c_int64, _I32, _I32]),
     "effconf_ctc_greedy": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _P, _F32P, _P, _SZ, _P]),
     "effconf_ctc_greedy_bf16": (C.c_int, [_P, _P, _I64P, _I32, _I32, _P, _P, _F32P, _P, _SZ, _P]),

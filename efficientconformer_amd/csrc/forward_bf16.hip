@@ -3,6 +3,7 @@
 // Also the per-module entries of the C ABI, which exist only on this file's helpers.
 #include "forward_common.h"
 #include "routes.h"
+#include "stream.h"
 
 #include <cmath>
 
@@ -185,7 +186,7 @@ int run_interctc(EcEncoder* e, hipStream_t st, int i, const float* x, int rows, 
 // index utterances through the descriptor arrays lengths_ragged_kernel leaves in the workspace.  out: (B, out_frames, D_last), zero filled
 // behind every utterance's own last frame.
 int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from_audio, const Shapes& s, const Workspace& w,
-                 char* ws, float* out, int64_t* out_len, hipStream_t st, int out_frames) {
+                 char* ws, float* out, int64_t* out_len, hipStream_t st, int out_frames, const StreamRound* sr) {
     const EcConfig& c = e->cfg;
     const int B = s.B, nb = (int)e->blocks.size();
     const bool rg = s.ragged;
@@ -196,6 +197,12 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
     // ---- Conv2dSubsampling (modules.py:232-249) + transpose + Linear (encoders.py:113-116)
     float* x = reinterpret_cast<float*>(ws + w.x0);
     float* xalt = reinterpret_cast<float*>(ws + w.x1);
+    if (sr) {
+        // a streaming round (stream.h): the rectangular front end over the streams' mel windows, then chunk row i = window row i + 1 into the ragged row space
+        const Shapes win = make_shapes(e, B, sr->mel_pitch);
+        EC_TRY(run_subsample_linear(e, st, sr->mel, win, nullptr, sr->sub, sr->sub1, nullptr, sr->xrect));
+        { PROF(PC_MISC, 0, (double)s.Min[0] * e->lin.N * 8); EC_TRY(launch_gather_rows(sr->xrect + e->lin.N, e->lin.N, win.T1, br.rows_at(0), x, st)); }
+    } else
     EC_TRY(run_subsample_linear(e, st, mel, s, rg ? &br : nullptr, reinterpret_cast<bf16_t*>(ws + w.sub), reinterpret_cast<bf16_t*>(ws + w.sub1),
                                 reinterpret_cast<float*>(ws + w.xrect), x));
     trace_add(e, st, "linear", x, s.Min[0], e->lin.N, e->lin.N, 0);
@@ -209,8 +216,8 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
     bool have_a = false;
     std::vector<BlockRoutes> routes;           // decided here, once per forward (routes.h); the loop below only reads them
     for (int k = 0; k < nb; ++k) routes.push_back(block_routes(e, k));
-    const ECache ec = e_cache_begin(e, st, ws, s, w.eh_blk[0], true);
-    const bool e_cached = ec.hit;
+    const ECache ec = sr ? ECache{} : e_cache_begin(e, st, ws, s, w.eh_blk[0], true);      // a streaming round reads the session's tables
+    const bool e_cached = sr || ec.hit;
 
     // The self-conditioned CTC step after block k (encoders.py:209-213), in place on the block's output rows (group-padding rows of a ragged batch are just rows).
     // Probabilities: written only where somebody reads them - the caller's buffer (rectangular batches: rows (b, t) ARE (B, T_k, V); ragged ones go through the
@@ -296,7 +303,7 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             pe.M = erows; pe.N = D; pe.K = D;
             bf16_t* eh = reinterpret_cast<bf16_t*>(ws + w.eh_blk[k]);
             pe.C = eh; pe.ldc = D;
-            if (Tp > b.max_pos) return fail("sequence longer than max_pos_encoding");
+            if (!sr && Tp > b.max_pos) return fail("sequence longer than max_pos_encoding");
             if (!e_cached) { PROF(PC_GEMM_OTHER, 2.0 * erows * (double)D * D, (double)erows * D * 4 + (double)D * D * 2);
                              EC_TRY(launch_gemm(pe, EPI_BF16, st)); }
             if (e->trace_arena) {    // the attention kernel's operands: rows b Tp + t (ragged: the group-padded row space), pad rows filled; E rows m < erows
@@ -317,15 +324,28 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
             ap.band_l = bd.l; ap.band_r = bd.r;
             ap.causal = c.causal;
             const bool streaming = c.causal || ap.band_l < Tg || ap.band_r < Tg;
-            const AttentionRoute ar = attention_route(e, dpad, rg, streaming);
+            const AttentionRoute ar = sr ? AttentionRoute{} : attention_route(e, dpad, rg, streaming);
             if (ar.refusal) return fail(ar.refusal);
             if (rg) {
                 ap.rag_off = br.off_at(k); ap.rag_wg = br.wg_off + (size_t)k * (B + 1); ap.rag_nwg = s.wgs[k]; ap.rag_tgmax = Tg;
             }
+            if (sr) {
+                // the chunk's queries against the stream's ring + the chunk's own keys, then the chunk's K / V rows join the ring
+                const StreamRound::Block& sb = sr->blk[k];
+                StreamAttnParams sp{};
+                sp.qu = p.qu; sp.k = p.kh; sp.v = p.vt; sp.e = sb.e; sp.n_dist = sb.n_dist; sp.dvu = W.dvu; sp.dvu_ld = W.dvu_ld;
+                sp.kc = sb.kc; sp.vc = sb.vc; sp.cap = sb.cap;
+                sp.row_off = br.off_at(k); sp.rows = br.lens_at(k); sp.cached = sb.cached; sp.pos = sb.pos; sp.slot = sr->slot;
+                sp.B = B; sp.H = H; sp.G = G; sp.D = D; sp.d = d; sp.dpad = dpad; sp.max_rows = T; sp.band_l = bd.l;
+                sp.out = o; sp.ldo = ld8(D); sp.scale = ap.scale;
+                { PROF(PC_ATTENTION, 2.0 * H * (double)M / G * (sb.cap + (double)Tg) * d * 3.0, (double)B * sb.cap * G * D * 4 + (double)M * D * 2 * 5);
+                  EC_TRY(launch_stream_attention(sp, st)); }
+                { PROF(PC_MISC, 0, (double)M * D * 8); EC_TRY(launch_stream_kv_append(sp, st)); }
+            } else
             { PROF(PC_ATTENTION, 2.0 * H * (rg ? s.tg2[k] : (double)B * Tg * Tg) * d * 3.0, (double)M * D * 2 * 5);
               if (ar.waves) EC_ABL(rg || streaming ? 1 : 0, EC_TRY(launch_relpos_attention2(ap, ar.waves, st)));
               else EC_TRY(launch_relpos_attention(ap, st)); }
-            if ((int)e->att_out.size() == nb && e->att_out[k]) {       // opt-in: the reference's att_w of this block (encoders.py:129)
+            if (!sr && (int)e->att_out.size() == nb && e->att_out[k]) {       // opt-in: the reference's att_w of this block (encoders.py:129)
                 // ragged batches: (B, H, Tg of the LONGEST utterance, same) per block, an utterance's own Tg x Tg block = its map run alone, zeros elsewhere
                 EC_TRY(launch_attention_probs(ap, e->att_out[k], st));
             }
@@ -348,6 +368,16 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         if (!r.chain_b) EC_TRY(run_rs_or_tiled(e, r.pw1_rs, PC_GEMM_OTHER, st, a, ld8(D), M, W.pw1, 2, EPI_GLU_BF16, gbuf, ld8(De), nullptr, 0, 1.f, x, &W.ln_conv));
         trace_block(e, st, k, "glu", gbuf, M, De, ld8(De), 1);
         const RaggedConv rc = rg ? br.conv_at(k, Mo, true) : RaggedConv{};
+        if (sr) {
+            // the k - 1 rows in front of the chunk come from the stream's state, which then takes the chunk's last rows
+            StreamDwParams dp{};
+            dp.g = gbuf; dp.ld = ld8(De); dp.C = De; dp.w_kc = W.dw_w; dp.bias = W.dw_b; dp.ksize = b.kernel_size; dp.stride = b.conv_stride;
+            dp.state = sr->blk[k].conv; dp.in_off = rc.in_off; dp.rows = rc.in_len; dp.hist = sr->blk[k].hist; dp.out_off = rc.out_off; dp.out_end = rc.out_off + 1;
+            dp.slot = sr->slot; dp.B = B; dp.max_rows = T; dp.out = cbuf;
+            PROF(PC_DWCONV, 2.0 * Mo * (double)De * b.kernel_size, (double)M * De * 2 + (double)Mo * De * 2);
+            EC_TRY(launch_stream_dwconv(dp, st));
+            EC_TRY(launch_stream_dwconv_state(dp, st));
+        } else
         { PROF(PC_DWCONV, 2.0 * Mo * (double)De * b.kernel_size, (double)M * De * 2 + (double)Mo * De * 2); EC_ABL(8, EC_TRY(launch_dwconv(gbuf, B, T, To, De, ld8(De), W.dw_w, W.dw_b, b.kernel_size, b.conv_stride, cbuf, st, rg ? &rc : nullptr, c.causal, r.dw_mfma ? W.dw_a : nullptr, W.dw_a3))); }
         mask_stride *= b.conv_stride;
         trace_block(e, st, k, "dw", cbuf, Mo, De, ld8(De), 1);
@@ -398,7 +428,7 @@ int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from
         trace_block(e, st, k, "out", xo, Mo, De, De, 0);
         EC_TRY(interctc_step(k, xo, Mo));
     }
-    e_cache_end(e, ws, s, ec);
+    if (!sr) e_cache_end(e, ws, s, ec);
     if (rg) EC_TRY(emit_ragged(e, st, br, x, out_frames, out));
     return 0;
 }

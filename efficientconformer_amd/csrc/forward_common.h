@@ -97,8 +97,9 @@ XWorkspace make_xworkspace(const EcEncoder* e, const Shapes& s);
 // ------------------------------------------------------------------ the two schedules: enqueue one forward on `st` (no allocation, no synchronisation, no
 // host <-> device copy: graph-capturable).  mel (B, n_mels, s.Tm) fp32; out (B, frames, D_last), ragged batches (s.ragged, out_frames > 0): zero filled
 // behind every utterance's own last frame
+struct StreamRound;   // stream.h: a round of a streaming session (ragged shapes; the front end, attention and depthwise convolution read the session's state)
 int forward_core(EcEncoder* e, const float* mel, const int64_t* in_len, int from_audio, const Shapes& s, const Workspace& w, char* ws, float* out,
-                 int64_t* out_len, hipStream_t st, int out_frames);
+                 int64_t* out_len, hipStream_t st, int out_frames, const StreamRound* sr = nullptr);
 int forward_exact(EcEncoder* e, const float* mel, const int64_t* in_len, int from_audio, const Shapes& s, const XWorkspace& w, char* ws, float* out,
                   int64_t* out_len, hipStream_t st, int out_frames);
 

@@ -525,6 +525,13 @@ class ConformerEncoder(nn.Module):
         """Enter after AudioPreprocessing: mel (B, n_mels, Tm), lengths in frames (the parity boundary)."""
         return self._run(mel, mel_len, False, range_hook, x_len_host, range_pad, return_attentions)[:3]
 
+    def open_stream(self, max_streams: int, max_frames: Optional[int] = None):
+        """A chunked streaming session of this (causal, bf16) encoder for `max_streams` streams: ``push_mel`` / ``push_audio`` encode only the new frames and the
+        concatenated outputs are the whole-utterance causal forward (efficientconformer_amd/streaming.py).  `max_frames`: the longest utterance in mel
+        frames - sizes the K / V caches, required where left_context is unlimited."""
+        from .streaming import StreamingEncoder
+        return StreamingEncoder(self, max_streams, max_frames)
+
     def mel_frontend(self, x: torch.Tensor, x_len: Optional[torch.Tensor] = None):
         """AudioPreprocessing.forward (reference modules.py:87-106) on the GPU."""
         lib = _lib.load()

@@ -140,6 +140,12 @@ class ModelCTC(_native.NativeModel):
     # top-2 margin next to it (the sizes effconf_ctc_greedy / _bf16 / _margin check, csrc/encoder.hip)
     _GREEDY_WS, _MARGIN_WS = 4, 8
 
+    def open_stream(self, max_streams: int, max_frames: Optional[int] = None):
+        """``ConformerEncoder.open_stream`` with the greedy head on the new frames: ``push_mel`` / ``push_audio`` return the new token ids per stream, the
+        repeat collapse carried across pushes (streaming.py: ctc_collapse_carry)."""
+        from .streaming import StreamingCTC
+        return StreamingCTC(self, max_streams, max_frames)
+
     def _greedy_rows(self, rows: torch.Tensor, as_bf16: bool, lens: torch.Tensor, lo: int, hi: int, labels, label_len, logits=None, margins=None):
         """The greedy head on utterances [lo, hi) of `rows` (B, T, D) - and of every other tensor given - on the current stream:
         effconf_ctc_greedy / effconf_ctc_greedy_bf16, or with `margins` = (frame_margin or None, min_margin, min_frame) effconf_ctc_greedy_margin."""

@@ -1,0 +1,312 @@
+"""Chunked streaming inference of causal encoders: a session keeps, per stream and per block, the attention keys / values of the left context and the last
+k - 1 inputs of the depthwise convolution (the C library's effconf_stream_*), encodes only the frames that are new, and the concatenation of its outputs is
+the whole-utterance causal forward.
+
+The session arithmetic is plain Python on the plan (no GPU, no library; tests/test_stream_host.py):
+  stream_align(plan)            chunk granularity in subsampled rows (12 for Tiny and every Efficient Conformer = 24 mel frames)
+  rows_to_encode(...)           the emission rule: after N mel frames of an unfinished stream N // 2 rows are complete (row t reads the mel frames
+                                2 t - 1 .. 2 t + 1) and whole multiples of the alignment are encoded; a final push encodes the remaining (N - 1) // 2 + 1 - done
+  cache_capacities(plan, ...)   grouped K / V rows kept per block: the band of forward_common.h (left_context // (mask_stride * group)), an unlimited
+                                left_context: what max_frames gives
+  ctc_collapse_carry(...)       greedy CTC collapse with the repeat carried across pushes
+"""
+from __future__ import annotations
+
+import ctypes as C
+from math import gcd
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import _lib, _native
+
+UNLIMITED = 1 << 30
+
+
+# ------------------------------------------------------------------ arithmetic (host only)
+def stream_refusal(plan, precision: str = "bf16", sub_batches: Optional[int] = 1) -> Optional[str]:
+    """Why a plan cannot stream (None: it can).  The library repeats the checks it can see (effconf_stream_create)."""
+    if not plan.causal:
+        return "streaming sessions need a causal plan (causal: true): the symmetric depthwise padding and the two-sided relative positions of other plans look ahead"
+    if 0 < plan.right_context < UNLIMITED:
+        return "streaming sessions with lookahead (right_context > 0) are not native"
+    if precision != "bf16":
+        return "streaming sessions run on the bf16 path (precision %r is not native)" % precision
+    if getattr(plan, "interctc_blocks", None):
+        return "streaming sessions of InterCTC encoders are not native"
+    if sub_batches is not None and sub_batches > 1:
+        return "streaming sessions run as one row range (sub_batches > 1 is refused)"
+    if plan.sub_layers != 1:
+        return "streaming sessions need the one-layer subsampler (the two-layer subsampler of the plain Conformer configurations is not native here)"
+    return None
+
+
+def stream_align(plan) -> int:
+    """Chunk granularity in subsampled rows: the least common multiple, over the blocks, of group_size x (product of the conv strides before the block) and of
+    the cumulative stride behind every strided block - a chunk that is a multiple starts every block on a whole attention group and every strided block on
+    an even row."""
+    lcm = lambda a, b: a // gcd(a, b) * b
+    l, ms = 1, 1
+    for bp in plan.blocks:
+        l = lcm(l, bp.group_size * ms)
+        ms *= bp.conv_stride
+        l = lcm(l, ms)
+    return l
+
+
+def rows_to_encode(frames: int, done: int, align: int, final: bool) -> int:
+    """Subsampled rows a stream encodes now: `frames` mel frames received in all, `done` rows encoded before."""
+    if final:
+        return max(((frames - 1) // 2 + 1 if frames > 0 else 0) - done, 0)
+    return max((frames // 2 - done) // align * align, 0)
+
+
+def block_rows(plan, rows: int) -> List[int]:
+    """Rows entering every block for `rows` subsampled rows, and (last entry) the rows leaving the encoder: T -> (T - 1) // s + 1 behind a strided block."""
+    out, t = [], rows
+    for bp in plan.blocks:
+        out.append(t)
+        if bp.conv_stride > 1 and t > 0:
+            t = (t - 1) // bp.conv_stride + 1
+    return out + [t]
+
+
+def cache_capacities(plan, max_frames: Optional[int] = None) -> List[int]:
+    """Grouped K / V rows every block keeps per stream: band(c, mask_stride, G).l of forward_common.h, capped by the grouped rows a block can see at all -
+    max_pos_encoding // G, or what max_frames mel frames bring to it.  An unlimited left_context is therefore sized by max_frames."""
+    rows = block_rows(plan, (max_frames - 1) // 2 + 1) if max_frames else None
+    out, ms = [], 1
+    for i, bp in enumerate(plan.blocks):
+        cap = min(plan.left_context // (ms * bp.group_size), bp.max_pos // bp.group_size)
+        out.append(cap if rows is None else min(cap, -(-rows[i] // bp.group_size)))
+        ms *= bp.conv_stride
+    return out
+
+
+def ctc_collapse_carry(frame_labels: Sequence[int], carry: int) -> Tuple[List[int], int]:
+    """Greedy CTC collapse of one push: `frame_labels` the argmax of every new frame, `carry` the label of the stream's last frame before it (0 = blank or
+    none).  -> (tokens to emit, new carry).  A label equal to the previous frame's is not emitted again - across the push boundary too; blank resets."""
+    out, prev = [], int(carry)
+    for l in frame_labels:
+        l = int(l)
+        if l != 0 and l != prev:
+            out.append(l)
+        prev = l
+    return out, prev
+
+
+def merge_collapsed(labels: Sequence[int], first: int, last: int, carry: int) -> Tuple[List[int], int]:
+    """The same from what the native greedy head returns for a push of at least one frame: its collapsed `labels` and the argmax of the first and of the
+    last frame."""
+    labels = [int(l) for l in labels]
+    if first != 0 and first == carry and labels:
+        labels = labels[1:]
+    return labels, int(last)
+
+
+# ------------------------------------------------------------------ the session
+class StreamingEncoder:
+    """``ConformerEncoder.open_stream``: `max_streams` independent streams; stream b is row b of every push."""
+
+    def __init__(self, encoder, max_streams: int, max_frames: Optional[int] = None):
+        why = stream_refusal(encoder.plan, encoder.precision, encoder.sub_batches)
+        if why:
+            raise _lib.EffconfError(why)
+        if max_streams < 1:
+            raise ValueError("max_streams must be >= 1")
+        self.encoder, self.plan = encoder, encoder.plan
+        self.max_streams, self.max_frames = int(max_streams), int(max_frames or 0)
+        self.align_rows = stream_align(self.plan)
+        self.align_frames = 2 * self.align_rows
+        self.device = encoder._param_device()
+        _native.require_hip(encoder.linear.weight)
+        lib = self._lib = _lib.load()
+        with torch.cuda.device(self.device):
+            encoder._ensure_packed()
+            self._enc_handle = encoder._handle
+            nbytes = _native.sized(lib, "effconf_stream_state", lib.effconf_stream_state_bytes(encoder._handle, self.max_streams, self.max_frames),
+                                   streams=self.max_streams, frames=self.max_frames)
+            self._state = _native.workspace(nbytes, self.device)
+            self._ptr = lib.effconf_stream_create(encoder._handle, self.max_streams, self.max_frames, self._state.data_ptr(), self._state.numel())
+        if not self._ptr:
+            raise _lib.EffconfError("effconf_stream_create: %s" % lib.effconf_last_error().decode())
+        self._ws = None
+        n_mels = self.plan.n_mels
+        self._zero2 = torch.zeros(n_mels, 2, dtype=torch.float32, device=self.device)
+        self._buf = [self._zero2 for _ in range(self.max_streams)]        # column c = mel frame 2 done - 2 + c (two zero columns in front of frame 0)
+        self._frames = [0] * self.max_streams
+        self._done = [0] * self.max_streams
+        self._ended = [False] * self.max_streams
+        # push_audio: samples from sample _s0 on (a multiple of the hop), frames emitted so far
+        self._audio = [None] * self.max_streams
+        self._s0 = [0] * self.max_streams
+        self._next_frame = [0] * self.max_streams
+
+    def close(self):
+        if getattr(self, "_ptr", None) and _lib._lib is not None:
+            self._lib.effconf_stream_destroy(self._ptr)
+        self._ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def frames_pending(self, stream: int) -> int:
+        """Mel frames of `stream` received and not yet covered by an encoded row's centre (what the alignment holds back)."""
+        return self._frames[stream] - 2 * self._done[stream] if not self._ended[stream] else 0
+
+    def reset(self, stream: int):
+        """`stream` starts a new utterance."""
+        _lib.check(self._lib.effconf_stream_reset(self._ptr, int(stream)), "stream_reset", self._lib)
+        self._buf[stream] = self._zero2
+        self._frames[stream] = self._done[stream] = 0
+        self._ended[stream] = False
+        self._audio[stream], self._s0[stream], self._next_frame[stream] = None, 0, 0
+
+    def _check_handle(self):
+        if self.encoder._handle != self._enc_handle:
+            raise _lib.EffconfError("the encoder was packed again after open_stream (new weights, options or precision): open a new session")
+
+    def push_mel(self, mel: torch.Tensor, mel_len, final=None):
+        """mel (B, n_mels, T) with B = max_streams, mel_len[b] new frames of stream b (any number, 0 included), final[b]: the stream ends with this push.
+        -> (out (B, t_new_max, D) fp32, zero behind every stream's new frames; out_len (B,) int64)."""
+        self._check_handle()
+        B = self.max_streams
+        lens = [int(v) for v in (mel_len.tolist() if isinstance(mel_len, torch.Tensor) else mel_len)]
+        final = [bool(v) for v in (final.tolist() if isinstance(final, torch.Tensor) else final)] if final is not None else [False] * B
+        if mel.shape[0] != B or len(lens) != B or len(final) != B:
+            raise ValueError("push_mel takes one row per stream of the session (%d)" % B)
+        _native.require_hip(mel)
+        mel = mel.float()
+        rows = []
+        for b in range(B):
+            if self._ended[b] and (lens[b] or final[b]):
+                raise _lib.EffconfError("stream %d has ended: reset it before it takes frames again" % b)
+            if lens[b]:
+                self._buf[b] = torch.cat([self._buf[b], mel[b, :, :lens[b]]], 1)
+                self._frames[b] += lens[b]
+            rows.append(0 if self._ended[b] else rows_to_encode(self._frames[b], self._done[b], self.align_rows, final[b]))
+        active = [b for b in range(B) if rows[b] > 0]
+        d_out = self.plan.blocks[-1].dim_expand
+        t_new = [block_rows(self.plan, r)[-1] if r else 0 for r in rows]
+        out = torch.zeros(B, max(t_new), d_out, dtype=torch.float32, device=self.device)
+        out_len = torch.tensor(t_new, dtype=torch.int64, device=self.device)
+        if active:
+            n, rmax = len(active), max(rows)
+            pitch = (2 * rmax + 2 + 7) // 8 * 8
+            staged = torch.zeros(n, self.plan.n_mels, pitch, dtype=torch.float32, device=self.device)
+            for i, b in enumerate(active):
+                w = min(self._buf[b].shape[1], 2 * rows[b] + 2)
+                staged[i, :, :w] = self._buf[b][:, :w]
+            lib = self._lib
+            with torch.cuda.device(self.device):
+                nbytes = _native.sized(lib, "effconf_stream", lib.effconf_stream_workspace_bytes(self._ptr, n, rmax, pitch), streams=n, rows=rmax, pitch=pitch)
+                if self._ws is None or self._ws.numel() < nbytes:
+                    self._ws = _native.workspace(nbytes, self.device)
+                o = torch.empty(n, max(t_new), d_out, dtype=torch.float32, device=self.device)
+                ol = torch.empty(n, dtype=torch.int64, device=self.device)
+                ids = (C.c_int32 * n)(*active)
+                rws = (C.c_int32 * n)(*[rows[b] for b in active])
+                _lib.check(lib.effconf_stream_push_mel(self._ptr, ids, n, staged.data_ptr(), pitch, rws, o.data_ptr(), o.shape[1], ol.data_ptr(), self._ws.data_ptr(),
+                                                       self._ws.numel(), torch.cuda.current_stream(self.device).cuda_stream), "stream_push_mel", lib)
+            out[active] = o
+        for b in range(B):
+            if rows[b]:
+                self._buf[b] = self._buf[b][:, 2 * rows[b]:]
+                self._done[b] += rows[b]
+            if final[b]:
+                self._ended[b] = True
+                self._buf[b] = self._zero2
+        return out, out_len
+
+    def push_audio(self, x: torch.Tensor, x_len, final=None):
+        """x (B, samples) with x_len[b] new samples of stream b.  The mel kernel runs over [kept tail | new samples] of every stream; only frames whose
+        n_fft-sample window lies inside the buffer are used (in the kernel's frame pairs), so the reflect padding applies at the true start and the true end
+        alone and the frames are those of the whole-signal front end, bit for bit.  -> push_mel's result."""
+        self._check_handle()
+        B, hop, half = self.max_streams, self.plan.hop_length, self.plan.n_fft // 2
+        lens = [int(v) for v in (x_len.tolist() if isinstance(x_len, torch.Tensor) else x_len)]
+        final = [bool(v) for v in (final.tolist() if isinstance(final, torch.Tensor) else final)] if final is not None else [False] * B
+        _native.require_hip(x)
+        new = []
+        for b in range(B):
+            if lens[b]:
+                piece = x[b, :lens[b]].float()
+                self._audio[b] = piece if self._audio[b] is None else torch.cat([self._audio[b], piece])
+            buf = self._audio[b]
+            L = 0 if buf is None else buf.shape[0]
+            end = self._s0[b] + L                                   # samples received in all
+            # global frame f is centred on sample f * hop; complete when its window ends inside the signal (final: the last frame is end // hop).  The mel kernel
+            # transforms the frames (2 m, 2 m + 1) as ONE complex FFT, so a frame carries rounding of its partner: frames are taken in whole pairs, from a buffer
+            # that starts on an even frame - the pairs, and so every bit, are those of the whole-signal front end
+            last = end // hop if final[b] else (end - half) // hop
+            if not final[b] and last % 2 == 0:
+                last -= 1
+            f0 = self._next_frame[b]
+            if L > half and last >= f0 and end > 0:
+                mel, _ = self.encoder.mel_frontend(buf[None])
+                j0 = f0 - self._s0[b] // hop
+                new.append(mel[0, :, j0: j0 + last - f0 + 1])
+                self._next_frame[b] = last + 1
+                s0 = max(((self._next_frame[b] * hop - half) // hop - 1) // 2 * 2 * hop, 0)          # an even frame; the next frame's window starts behind it
+                if s0 > self._s0[b]:
+                    self._audio[b] = buf[s0 - self._s0[b]:]
+                    self._s0[b] = s0
+            else:
+                new.append(None)
+        n_new = [0 if m is None else m.shape[1] for m in new]
+        mel = torch.zeros(B, self.plan.n_mels, max(max(n_new), 1), dtype=torch.float32, device=self.device)
+        for b, m in enumerate(new):
+            if m is not None:
+                mel[b, :, :m.shape[1]] = m
+        self.last_mel, self.last_mel_len = mel, n_new               # what this push added (tests)
+        return self.push_mel(mel, n_new, final)
+
+
+class StreamingCTC:
+    """``ModelCTC.open_stream``: the session plus the greedy head on the new frames, the repeat collapse carried across pushes."""
+
+    def __init__(self, model, max_streams: int, max_frames: Optional[int] = None):
+        self.model = model
+        self.session = StreamingEncoder(model.encoder, max_streams, max_frames)
+        self._carry = [0] * max_streams
+
+    align_frames = property(lambda self: self.session.align_frames)
+
+    def frames_pending(self, stream: int) -> int:
+        return self.session.frames_pending(stream)
+
+    def reset(self, stream: int):
+        self.session.reset(stream)
+        self._carry[stream] = 0
+
+    def _tokens(self, out: torch.Tensor, out_len: torch.Tensor) -> List[List[int]]:
+        B = out.shape[0]
+        lens = out_len.tolist()
+        if out.shape[1] == 0 or not any(lens):
+            return [[] for _ in range(B)]
+        head = lambda rows, ln: self.model._head(rows, ln)[1:]
+        labels, label_len = head(out, out_len)
+        one = (out_len > 0).to(torch.int64)
+        first, first_n = head(out[:, :1].contiguous(), one)
+        idx = (out_len - 1).clamp(min=0)
+        last, last_n = head(out[torch.arange(B, device=out.device), idx][:, None].contiguous(), one)
+        labels, label_len, first, first_n, last, last_n = (z.tolist() for z in (labels, label_len, first, first_n, last, last_n))
+        res = []
+        for b in range(B):
+            if not lens[b]:
+                res.append([])
+                continue
+            f = first[b][0] if first_n[b] else 0
+            l = last[b][0] if last_n[b] else 0
+            toks, self._carry[b] = merge_collapsed(labels[b][:label_len[b]], f, l, self._carry[b])
+            res.append(toks)
+        return res
+
+    def push_mel(self, mel, mel_len, final=None) -> List[List[int]]:
+        return self._tokens(*self.session.push_mel(mel, mel_len, final))
+
+    def push_audio(self, x, x_len, final=None) -> List[List[int]]:
+        return self._tokens(*self.session.push_audio(x, x_len, final))

@@ -533,6 +533,52 @@ int effconf_encoder_set_interctc_outputs(EcEncoder* enc, float* const* probs, in
 int effconf_interctc(EcEncoder* enc, int32_t block, const float* x, int32_t rows, float* y, float* probs, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- chunked streaming: the two frame-mixing kernels of a causal encoder that sees its input a chunk at a time, alone on caller-provided
+ * operands and state.  All arrays indexed by stream are device int32 [streams]; max_rows (host) >= every rows[b].
+ * effconf_stream_attention: stream b owns the rows [row_off[b], row_off[b] + round_up(rows[b], group)) of qu = Q + u, k, v (bf16 rows of `dim`
+ *   columns; group-padding rows of a final chunk: qu = u, k = v = 0) and of out (bf16 rows of ld_out columns; group-padding rows are written as
+ *   zeros).  rows[b] = 0: the stream idles.  pos[b] = absolute grouped position of its first query, cached[b] = valid grouped rows of its cache (the
+ *   positions pos - cached .. pos - 1).  k_cache / v_cache: [streams][capacity] slots of group * dim bf16, a ring - the grouped row of absolute
+ *   position p lives in slot p % capacity; no other slot is read.  e: the causal table in its own order, e_rows grouped rows of group * dim bf16 =
+ *   pos_layer(sinusoid(group * e_rows - 1 .. 0)): the distance i - j reads grouped row e_rows - 1 - (i - j) at every position;
+ *   e_rows > min(band_left, largest position).  Key j is visible
+ *   to query i iff 0 <= i - j <= band_left (>= 2^30: unlimited).  dvu: (v - u) per head column [heads][dvu_ld] fp32, zero beyond the head width.
+ *   qu, k, e and the rings need 16 bytes of readable slack behind their last row.  append != 0: the chunk's K / V rows then join the rings (of a
+ *   chunk longer than the ring its last `capacity` grouped rows); the caller advances pos and sets cached = min(cached + new rows, capacity).
+ * effconf_stream_dwconv: causal depthwise convolution (ksize 7 / 15 / 31, stride 1 / 2) + folded BatchNorm + Swish of the rows
+ *   g[in_off[b] .. + rows[b]) (bf16, ld columns, ld % 8 == 0) -> out[out_off[b] .. + (rows[b] - 1) / stride + 1).  taps: folded fp32 [ksize][channels],
+ *   bias [channels].  state: [streams][ksize - 1][ld] bf16, the rows in front of the chunk, of which the LAST hist[b] are valid (the others read as
+ *   zero, whatever they hold).  A chunk of a stride-2 layer starts on an even absolute row.  update_state != 0: the state then becomes the last
+ *   ksize - 1 rows of [state | chunk]; the caller sets hist = min(hist + rows, ksize - 1). */
+/* Streaming sessions.  A session keeps, for max_streams independent streams of a CAUSAL bf16 encoder, per block the attention keys / values of the left context
+ * (a ring of the band's length; an unlimited left_context: as many grouped rows as max_frames mel frames give - max_frames = 0 is then refused) and the last
+ * kernel_size - 1 inputs of the depthwise convolution, in ONE caller-provided device buffer of effconf_stream_state_bytes bytes that must outlive the session
+ * (its contents need no initialisation).  Refused with the reason: plans that are not causal, right_context > 0, precision "split" / "fp32", InterCTC
+ * encoders, the two-layer subsampler.
+ * effconf_stream_align: chunk granularity in subsampled rows (12 for every Efficient Conformer: 24 mel frames): every chunk of a stream but its last is a multiple.
+ * effconf_stream_push_mel: one round.  `streams`: n distinct stream ids (host); rows[b] >= 1 (host): subsampled rows stream streams[b] encodes now - a
+ *   multiple of the alignment unless this is the stream's last chunk.  mel: device fp32 (n, n_mels, mel_pitch), mel_pitch >= 2 max(rows) + 2; column c of
+ *   stream b = its mel frame 2 done_b - 2 + c (done_b = rows encoded before this round), ZERO in front of the utterance's first frame and behind its last one.
+ *   A row t reads the mel frames 2 t - 1 .. 2 t + 1, so after N frames of an unfinished stream N / 2 rows are complete; an ended stream has (N - 1) / 2 + 1.
+ *   out: (n, out_frames, D_last) fp32, zero behind every stream's new frames; out_len: device int64 [n], the new output frames.  The concatenation of a stream's
+ *   outputs is the whole-utterance causal forward of its mel frames.  effconf_stream_reset: the stream starts a new utterance. */
+typedef struct EcStream EcStream;
+int32_t effconf_stream_align(const EcEncoder* enc);
+size_t effconf_stream_state_bytes(const EcEncoder* enc, int32_t max_streams, int32_t max_frames);
+EcStream* effconf_stream_create(EcEncoder* enc, int32_t max_streams, int32_t max_frames, void* state, size_t state_bytes);
+void effconf_stream_destroy(EcStream* session);
+int effconf_stream_reset(EcStream* session, int32_t stream);
+size_t effconf_stream_workspace_bytes(const EcStream* session, int32_t n, int32_t max_rows, int32_t mel_pitch);
+int effconf_stream_push_mel(EcStream* session, const int32_t* streams, int32_t n, const float* mel, int32_t mel_pitch, const int32_t* rows, float* out,
+                            int32_t out_frames, int64_t* out_len, void* workspace, size_t workspace_bytes, void* stream);
+int effconf_stream_attention(const uint16_t* qu, const uint16_t* k, const uint16_t* v, const uint16_t* e, int32_t e_rows, const float* dvu, int32_t dvu_ld,
+                             uint16_t* k_cache, uint16_t* v_cache, int32_t capacity, const int32_t* row_off, const int32_t* rows, const int32_t* cached,
+                             const int32_t* pos, int32_t streams, int32_t max_rows, int32_t heads, int32_t group, int32_t dim, int32_t band_left,
+                             uint16_t* out, int32_t ld_out, int32_t append, void* stream);
+int effconf_stream_dwconv(const uint16_t* g, int32_t ld, int32_t channels, const float* taps, const float* bias, int32_t ksize, int32_t stride,
+                          uint16_t* state, const int32_t* in_off, const int32_t* rows, const int32_t* hist, const int32_t* out_off, int32_t streams,
+                          int32_t max_rows, uint16_t* out, int32_t update_state, void* stream);
+
 /* ---- host helper of the batching front door (reference: utils/preprocessing.py:33-45, collate_fn_pad zero-pads a sorted batch) -------
  * Copies n host rows src[i][0 .. len[i]) to dst + i * pitch (floats) on `threads` host threads, zero-filling dst[i][len[i] .. pitch) when
  * zero_pad != 0 (ragged batches never read the pad samples: pass 0).  dst is typically pinned memory, so that ONE H2D copy follows.  No
