@@ -11,9 +11,9 @@ from .transducer import Transducer, TransducerAlignment  # noqa: F401
 from .lm import LanguageModel  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .batching import FrontDoor, bucket_batches, collate_fn_pad  # noqa: F401
-from .streaming import StreamingCTC, StreamingEncoder, ctc_collapse_carry, stream_align  # noqa: F401
+from .streaming import RnntStreamState, StreamingCTC, StreamingEncoder, StreamingTransducer, ctc_collapse_carry, stream_align  # noqa: F401
 
-__all__ = ["ConformerEncoder", "ConformerEncoderInterCTC", "ModelCTC", "InterCTC", "model_from_config", "Alignment", "HeadMargins", "select_rerun", "select_nbest", "Transducer", "TransducerAlignment", "LanguageModel", "load_checkpoint", "save_checkpoint", "FrontDoor", "bucket_batches", "collate_fn_pad", "build_plan", "load_config", "named_config", "StreamingEncoder", "StreamingCTC", "stream_align", "ctc_collapse_carry"]
+__all__ = ["ConformerEncoder", "ConformerEncoderInterCTC", "ModelCTC", "InterCTC", "model_from_config", "Alignment", "HeadMargins", "select_rerun", "select_nbest", "Transducer", "TransducerAlignment", "LanguageModel", "load_checkpoint", "save_checkpoint", "FrontDoor", "bucket_batches", "collate_fn_pad", "build_plan", "load_config", "named_config", "StreamingEncoder", "StreamingCTC", "StreamingTransducer", "RnntStreamState", "stream_align", "ctc_collapse_carry"]
 
 
 def model_from_config(cfg, tokenizer=None):

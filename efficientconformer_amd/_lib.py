@@ -85,6 +85,11 @@ SIGNATURES = {
     "effconf_rnnt_set_option": (C.c_int, [_P, C.c_char_p, _I32]),
     "effconf_rnnt_greedy_route": (C.c_int, [_P, _I32]),
     "effconf_rnnt_greedy": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _P, _P, _I32, _P, _SZ, _P]),
+    "effconf_rnnt_stream_state_bytes": (_SZ, [_P, _I32]),
+    "effconf_rnnt_stream_init": (C.c_int, [_P, _P, _SZ, _I32, _P]),
+    "effconf_rnnt_stream_reset": (C.c_int, [_P, _P, _I32, _I32, _P]),
+    "effconf_rnnt_stream_workspace_bytes": (_SZ, [_P, _I32, _I32]),
+    "effconf_rnnt_greedy_resume": (C.c_int, [_P, _P, _I32, _P, _F32P, _I64P, _I32, _I32, _P, _P, _P, _P, _I32, _P, _SZ, _P]),
     "effconf_rnnt_beam_workspace_bytes": (_SZ, [_P, _I32, _I32, _I32, _I32, _I32]),
     "effconf_rnnt_beam": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _F32P, _P, _I32, _P, _SZ, _P]),
     "effconf_rnnt_beam_lm_workspace_bytes": (_SZ, [_P, _P, _I32, _I32, _I32, _I32, _I32]),

@@ -42,6 +42,33 @@ inline GreedyLayout greedy_layout(const EcRnntConfig& c, int batch, int t_out, i
     return L;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- rnnt.hip: greedy, resumed per stream
+// The caller's state buffer: i32 primed[max_streams], then one record per stream, rec_bytes apart: f32 h[H], c[H], gd[J] = linear_decoder(h) + bias.  The workspace
+// of a push is its fe = linear_encoder(f) [n][t_new][J] alone.
+struct RnntStreamLayout { size_t primed, rec, rec_bytes, total; };
+
+inline RnntStreamLayout rnnt_stream_layout(const EcRnntConfig& c, int max_streams) {
+    RnntStreamLayout L{};
+    WsPlan u;                                                            // one stream
+    u.take(((size_t)2 * c.dim_decoder + c.dim_joint) * 4);
+    L.rec_bytes = u.stride();
+    WsPlan p;
+    L.primed = p.take((size_t)max_streams * 4);
+    L.rec = p.take((size_t)max_streams * L.rec_bytes);
+    L.total = p.total();
+    return L;
+}
+
+struct RnntStreamWs { size_t fe, total; };
+
+inline RnntStreamWs rnnt_stream_ws(const EcRnntConfig& c, int n, int t_new) {
+    RnntStreamWs L{};
+    WsPlan p;
+    L.fe = p.take((size_t)n * t_new * c.dim_joint * 4);
+    L.total = p.total();
+    return L;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- rnnt_beam.hip
 constexpr int BEAM_SLACK = 64;      // evaluated, not yet popped hypotheses per frame (room for evaluating ahead of the pops)
 constexpr int BEAM_HYP_BYTES = 32;  // sizeof(Hyp)

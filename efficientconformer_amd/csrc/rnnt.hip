@@ -129,9 +129,57 @@ __device__ __forceinline__ void matvec(const float4* __restrict__ W4, int N, int
 }
 
 
-// One workgroup = one utterance.  fe: [B][T][J] = linear_encoder(f) incl. bias.
-__global__ __launch_bounds__(NT) void rnnt_greedy_kernel(RnntDev w, const float* __restrict__ fe, const int64_t* __restrict__ lens,
-                                                         int T, int* __restrict__ tokens, int* __restrict__ counts, int max_tok) {
+// One prediction-network step on token y and the decoder projection the joint reads: h, c -> h', c' (sg: the gate pre-activations), gd = linear_decoder(h') + bias.
+// Ends behind a barrier.
+__device__ __forceinline__ void decoder_step(const RnntDev& w, int y, float* sh, float* sc, float* sg, float* sgd) {
+    const int H = w.H, J = w.J, tid = threadIdx.x;
+    // ---- decoder step: gates = Gin[y] + W_hh h   (torch LSTM gate order i, f, g, o)
+    for (int n0 = 0; n0 < 4 * H; n0 += NT * 5) {
+        float acc[5][1];
+        matvec<5, 1>(w.whh4, 4 * H, H / 4, n0, sh, H, acc);
+#pragma unroll
+        for (int m = 0; m < 5; ++m) {
+            const int n = n0 + tid + NT * m;
+            if (n < 4 * H) sg[n] = acc[m][0] + w.gin[(size_t)y * 4 * H + n];
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < H; j += NT) {
+        const LstmState s = lstm_cell(sg[j], sg[H + j], sg[2 * H + j], sg[3 * H + j], sc[j]);
+        sc[j] = s.c;
+        sh[j] = s.h;
+    }
+    __syncthreads();
+    // ---- gd = linear_decoder(h)
+    for (int n0 = 0; n0 < J; n0 += NT * 2) {
+        float acc[2][1];
+        matvec<2, 1>(w.wd4, J, H / 4, n0, sh, H, acc);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const int n = n0 + tid + NT * m;
+            if (n < J) sgd[n] = acc[m][0] + w.bd[n];
+        }
+    }
+    __syncthreads();
+}
+
+// What a resumed decode adds to the whole-utterance one: workgroup b decodes the new frames of stream streams[b], whose record (h[H], c[H], gd[J] = linear_decoder(h) +
+// bias; primed[stream] != 0: the record holds the state at a frame boundary) it reads on entry and writes on exit.  At a frame boundary, and only there, the consecutive
+// counter is 0, the LSTM has consumed every emitted token and gd is what the next joint evaluation reads - so nothing else is carried.
+struct StreamIo {
+    const int* streams;      // [n] stream ids
+    int* primed;             // [max_streams]
+    float* rec;              // records, rec_floats apart
+    int rec_floats, max_streams;
+    int* token_frames;       // [n][max_tok] push-local frame of every token, -1 behind them; nullable
+    int* decoder_steps;      // [n] LSTM steps of this push; nullable
+};
+
+// One workgroup = one utterance (STREAM: one stream's push).  fe: [B][T][J] = linear_encoder(f) incl. bias.  The whole-utterance decode is "resume from a fresh state,
+// write no state": STREAM = false compiles every stream access away.
+template <bool STREAM>
+__device__ __forceinline__ void greedy_body(const RnntDev& w, const float* __restrict__ fe, const int64_t* __restrict__ lens, int T, int* __restrict__ tokens,
+                                            int* __restrict__ counts, int max_tok, const StreamIo& io) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int H = w.H, J = w.J, V = w.V;
     float* sh = lds;                       // [H]   h
@@ -143,42 +191,38 @@ __global__ __launch_bounds__(NT) void rnnt_greedy_kernel(RnntDev w, const float*
     int* sbi = reinterpret_cast<int*>(sbv + KF * (NT / 64));   // [KF][NT/64] wave-best indices
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
+    float* rec = nullptr;
+    int sid = 0;
+    bool primed = false;
+    if constexpr (STREAM) {
+        sid = io.streams[b];
+        if (sid < 0 || sid >= io.max_streams) {          // uniform: the whole workgroup leaves, nothing but the length is written
+            if (tid == 0) counts[b] = -1;
+            return;
+        }
+        rec = io.rec + (size_t)sid * io.rec_floats;
+        primed = io.primed[sid] != 0;
+    }
     int Tb = (int)lens[b];
     Tb = Tb < 0 ? 0 : (Tb > T ? T : Tb);
-    for (int i = tid; i < 2 * H; i += NT) sh[i] = 0.f;   // hidden = None -> zeros (decoders.py:59-60)
+    if (STREAM && primed) {                              // a record whose flag is clear is never read
+        for (int i = tid; i < 2 * H; i += NT) sh[i] = rec[i];
+        for (int i = tid; i < J; i += NT) sgd[i] = rec[2 * H + i];
+    } else {
+        for (int i = tid; i < 2 * H; i += NT) sh[i] = 0.f;   // hidden = None -> zeros (decoders.py:59-60)
+    }
     __syncthreads();
     int y = 0, enc_step = 0, consec = 0, ntok = 0;       // y = x.new_zeros(1,1) (transducer.py:151)
+    int nsteps = 0;
+    bool run_dec = !primed;                              // a primed stream runs no decoder step and no decoder projection until it emits a token
     const float* feb = fe + (size_t)b * T * J;
 
     while (enc_step < Tb) {
-        // ---- decoder step: gates = Gin[y] + W_hh h   (torch LSTM gate order i, f, g, o)
-        for (int n0 = 0; n0 < 4 * H; n0 += NT * 5) {
-            float acc[5][1];
-            matvec<5, 1>(w.whh4, 4 * H, H / 4, n0, sh, H, acc);
-#pragma unroll
-            for (int m = 0; m < 5; ++m) {
-                const int n = n0 + tid + NT * m;
-                if (n < 4 * H) sg[n] = acc[m][0] + w.gin[(size_t)y * 4 * H + n];
-            }
+        if (!STREAM || run_dec) {
+            decoder_step(w, y, sh, sc, sg, sgd);
+            ++nsteps;
         }
-        __syncthreads();
-        for (int j = tid; j < H; j += NT) {
-            const LstmState s = lstm_cell(sg[j], sg[H + j], sg[2 * H + j], sg[3 * H + j], sc[j]);
-            sc[j] = s.c;
-            sh[j] = s.h;
-        }
-        __syncthreads();
-        // ---- gd = linear_decoder(h)
-        for (int n0 = 0; n0 < J; n0 += NT * 2) {
-            float acc[2][1];
-            matvec<2, 1>(w.wd4, J, H / 4, n0, sh, H, acc);
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const int n = n0 + tid + NT * m;
-                if (n < J) sgd[n] = acc[m][0] + w.bd[n];
-            }
-        }
-        __syncthreads();
+        run_dec = true;
         // ---- joint loop: KF frames per pass, until a token is emitted or the utterance ends
         bool emitted = false;
         while (!emitted && enc_step < Tb) {
@@ -230,7 +274,10 @@ __global__ __launch_bounds__(NT) void rnnt_greedy_kernel(RnntDev w, const float*
                 if (pred == 0 || consec == w.max_consec) { consec = 0; ++enc_step; }
                 else {
                     ++consec;
-                    if (tid == 0 && ntok < max_tok) tokens[(size_t)b * max_tok + ntok] = pred;
+                    if (tid == 0 && ntok < max_tok) {
+                        tokens[(size_t)b * max_tok + ntok] = pred;
+                        if (STREAM && io.token_frames) io.token_frames[(size_t)b * max_tok + ntok] = enc_step;
+                    }
                     ++ntok;
                     y = pred;
                     emitted = true;
@@ -241,6 +288,27 @@ __global__ __launch_bounds__(NT) void rnnt_greedy_kernel(RnntDev w, const float*
     }
     if (tid == 0) counts[b] = ntok < max_tok ? ntok : max_tok;
     for (int i = ntok + tid; i < max_tok; i += NT) tokens[(size_t)b * max_tok + i] = 0;
+    if constexpr (STREAM) {
+        if (io.token_frames)
+            for (int i = ntok + tid; i < max_tok; i += NT) io.token_frames[(size_t)b * max_tok + i] = -1;
+        if (tid == 0 && io.decoder_steps) io.decoder_steps[b] = nsteps;
+        if (Tb > 0) {                                    // the loop ended behind a blank or a forced decision: a frame boundary.  No frame: the record stays as it is
+            for (int i = tid; i < 2 * H; i += NT) rec[i] = sh[i];
+            for (int i = tid; i < J; i += NT) rec[2 * H + i] = sgd[i];
+            if (tid == 0) io.primed[sid] = 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT) void rnnt_greedy_kernel(RnntDev w, const float* __restrict__ fe, const int64_t* __restrict__ lens,
+                                                         int T, int* __restrict__ tokens, int* __restrict__ counts, int max_tok) {
+    greedy_body<false>(w, fe, lens, T, tokens, counts, max_tok, StreamIo{});
+}
+
+// One workgroup = the new frames of one listed stream.  fe: [n][T][J] of the push.
+__global__ __launch_bounds__(NT) void rnnt_greedy_resume_kernel(RnntDev w, const float* __restrict__ fe, const int64_t* __restrict__ lens,
+                                                                int T, int* __restrict__ tokens, int* __restrict__ counts, int max_tok, StreamIo io) {
+    greedy_body<true>(w, fe, lens, T, tokens, counts, max_tok, io);
 }
 
 
@@ -742,6 +810,63 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
     const size_t lds = (size_t)(2 * H + 4 * H + J + KF * J + 2 * KF * (NT / 64)) * 4;
     hipLaunchKernelGGL(rnnt_greedy_kernel, dim3(batch), dim3(NT), lds, s, r->dev, fe, out_len, t_out, tokens, token_len, max_tokens);
     return hipGetLastError() == hipSuccess ? 0 : ec_fail("rnnt_greedy launch failed");
+}
+
+// ---- the greedy decode resumed per stream (include/effconf.h)
+size_t effconf_rnnt_stream_state_bytes(const EcRnnt* r, int32_t max_streams) {
+    if (!r) { ec_fail("null handle"); return 0; }
+    if (max_streams < 1) { ec_fail("max_streams must be >= 1"); return 0; }
+    return rnnt_stream_layout(r->cfg, max_streams).total;
+}
+
+int effconf_rnnt_stream_init(EcRnnt* r, void* state, size_t state_bytes, int32_t max_streams, void* stream) {
+    if (!r) return ec_fail("null handle");
+    if (!state) return ec_fail("null argument");
+    if (max_streams < 1) return ec_fail("max_streams must be >= 1");
+    const RnntStreamLayout L = rnnt_stream_layout(r->cfg, max_streams);
+    if (state_bytes < L.total) return ec_fail("stream state buffer too small (effconf_rnnt_stream_state_bytes)");
+    // the flags alone: a record whose flag is clear is never read
+    if (hipMemsetAsync(WsPlan::base(state) + L.primed, 0, (size_t)max_streams * 4, (hipStream_t)stream) != hipSuccess) return ec_fail("memset failed");
+    return 0;
+}
+
+int effconf_rnnt_stream_reset(EcRnnt* r, void* state, int32_t max_streams, int32_t stream_id, void* stream) {
+    if (!r) return ec_fail("null handle");
+    if (!state) return ec_fail("null argument");
+    if (max_streams < 1 || stream_id < 0 || stream_id >= max_streams) return ec_fail("stream id outside 0 .. max_streams - 1");
+    const RnntStreamLayout L = rnnt_stream_layout(r->cfg, max_streams);
+    if (hipMemsetAsync(WsPlan::base(state) + L.primed + (size_t)stream_id * 4, 0, 4, (hipStream_t)stream) != hipSuccess) return ec_fail("memset failed");
+    return 0;
+}
+
+size_t effconf_rnnt_stream_workspace_bytes(const EcRnnt* r, int32_t n, int32_t t_new) {
+    if (!r) { ec_fail("null handle"); return 0; }
+    if (n < 0 || t_new <= 0) { ec_fail("n must be >= 0 and t_new > 0"); return 0; }
+    return rnnt_stream_ws(r->cfg, n, t_new).total;
+}
+
+int effconf_rnnt_greedy_resume(EcRnnt* r, void* state, int32_t max_streams, const int32_t* streams, const float* enc_out, const int64_t* out_len,
+                               int32_t n, int32_t t_new, int32_t* tokens, int32_t* token_frames, int32_t* token_len, int32_t* decoder_steps,
+                               int32_t max_tokens, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!r || !r->finalized) return ec_fail("rnnt handle not finalized");
+    if (n < 0 || t_new <= 0 || max_streams < 1) return ec_fail("bad shape: n >= 0, t_new > 0, max_streams >= 1");
+    if (max_tokens < effconf_rnnt_max_tokens(r, t_new)) return ec_fail("token buffer smaller than max_consec_dec_step * t_new");
+    if (workspace_bytes < rnnt_stream_ws(r->cfg, n, t_new).total) return ec_fail("workspace too small");
+    if (n == 0) return 0;
+    if (!state || !streams || !enc_out || !out_len || !tokens || !token_len || !workspace) return ec_fail("null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const int H = r->cfg.dim_decoder, J = r->cfg.dim_joint, De = r->cfg.dim_encoder;
+    float* fe = reinterpret_cast<float*>(WsPlan::base(workspace) + rnnt_stream_ws(r->cfg, n, t_new).fe);
+    // rows are independent: a frame's fe is bit-identical however the frames are grouped into pushes
+    if (launch_sgemm_nt(enc_out, De, r->we, De, r->be, fe, J, n * t_new, J, De, s) != 0) return ec_fail("linear_encoder GEMM launch failed");
+    const RnntStreamLayout L = rnnt_stream_layout(r->cfg, max_streams);
+    char* st = WsPlan::base(state);
+    StreamIo io{};
+    io.streams = streams; io.primed = reinterpret_cast<int*>(st + L.primed); io.rec = reinterpret_cast<float*>(st + L.rec);
+    io.rec_floats = (int)(L.rec_bytes / 4); io.max_streams = max_streams; io.token_frames = token_frames; io.decoder_steps = decoder_steps;
+    const size_t lds = (size_t)(2 * H + 4 * H + J + KF * J + 2 * KF * (NT / 64)) * 4;
+    hipLaunchKernelGGL(rnnt_greedy_resume_kernel, dim3(n), dim3(NT), lds, s, r->dev, fe, out_len, t_new, tokens, token_len, max_tokens, io);
+    return hipGetLastError() == hipSuccess ? 0 : ec_fail("rnnt_greedy_resume launch failed");
 }
 
 }  // extern "C"

@@ -9,6 +9,9 @@ The session arithmetic is plain Python on the plan (no GPU, no library; tests/te
   cache_capacities(plan, ...)   grouped K / V rows kept per block: the band of forward_common.h (left_context // (mask_stride * group)), an unlimited
                                 left_context: what max_frames gives
   ctc_collapse_carry(...)       greedy CTC collapse with the repeat carried across pushes
+
+Transducers: ``RnntStreamState`` carries the prediction network's state per stream and resumes the greedy RNN-T decode on the new encoder frames
+(effconf_rnnt_greedy_resume); ``StreamingTransducer`` is the encoder session plus that decode.
 """
 from __future__ import annotations
 
@@ -310,3 +313,167 @@ class StreamingCTC:
 
     def push_audio(self, x, x_len, final=None) -> List[List[int]]:
         return self._tokens(*self.session.push_audio(x, x_len, final))
+
+
+# ------------------------------------------------------------------ RNN-T: the greedy decode resumed per stream
+class RnntStreamState:
+    """``Transducer.open_decode_stream``: the prediction network's state of `max_streams` streams (per stream h, c, linear_decoder(h) and one flag, in one
+    device buffer this object owns: include/effconf.h has the layout) and the greedy decode resumed from it, push by push (effconf_rnnt_greedy_resume).  The
+    tokens of a stream, whatever its push pattern, are those of one ``decode_encoded`` of the same frames on the per-utterance kernel."""
+
+    def __init__(self, model, max_streams: int):
+        if max_streams < 1:
+            raise ValueError("max_streams must be >= 1")
+        self.model, self.max_streams = model, int(max_streams)
+        weight = model.joint_network.linear_joint.weight
+        _native.require_hip(weight)
+        self.device = weight.device
+        lib = self._lib = _lib.load()
+        with torch.cuda.device(self.device):
+            model._ensure_rnnt()
+            self._handle, self._generation = model._rnnt, model._rnnt_generation
+            nbytes = _native.sized(lib, "effconf_rnnt_stream_state", lib.effconf_rnnt_stream_state_bytes(self._handle, self.max_streams), streams=self.max_streams)
+            self.state = _native.workspace(nbytes, self.device)
+            self.init()
+        self._ws = None
+
+    def _check_handle(self):
+        if not self.model._rnnt_packed or self.model._rnnt_generation != self._generation:
+            raise _lib.EffconfError("the decoder was packed again after open_decode_stream (new weights): open a new decode stream")
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def init(self):
+        """Every stream starts a new utterance (only the flags are written: a record whose flag is clear is never read)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.effconf_rnnt_stream_init(self._handle, self.state.data_ptr(), self.state.numel(), self.max_streams, self._stream()),
+                       "rnnt_stream_init", self._lib)
+
+    def reset(self, stream: int):
+        """`stream` starts a new utterance."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.effconf_rnnt_stream_reset(self._handle, self.state.data_ptr(), self.max_streams, int(stream), self._stream()),
+                       "rnnt_stream_reset", self._lib)
+
+    def state_views(self):
+        """(h (S, H), c (S, H), gd (S, J) fp32, primed (S,) i32): views of the state buffer (tests)."""
+        _, H, J, _, _ = self.model._cfg
+        up = lambda x: (x + 255) // 256 * 256
+        S, off = self.max_streams, (-self.state.data_ptr()) % 256
+        primed = self.state[off: off + 4 * S].view(torch.int32)
+        rec_bytes = up(4 * (2 * H + J))
+        lo = off + up(4 * S)
+        rec = self.state[lo: lo + S * rec_bytes].view(torch.float32).view(S, rec_bytes // 4)
+        return rec[:, :H], rec[:, H: 2 * H], rec[:, 2 * H: 2 * H + J], primed
+
+    def push(self, f: torch.Tensor, f_len, streams: Optional[Sequence[int]] = None):
+        """f (n, t_new, Denc) fp32 on the GPU: f_len[i] new encoder frames of stream streams[i] (default 0 .. n - 1; distinct ids) -> device tensors (tokens (n,
+        max_tok) i32 zero behind token_len, token_frames (n, max_tok) i32 the push-local frame of every token and -1 behind them, token_len (n,) i32,
+        decoder_steps (n,) i32 the prediction-network steps this push ran)."""
+        if f.dim() != 3:
+            raise _lib.EffconfError("encoder outputs must be (streams, frames, dim); got shape %s" % (tuple(f.shape),))
+        n = f.shape[0]
+        ids = list(range(n)) if streams is None else [int(s) for s in streams]
+        if len(ids) != n:
+            raise ValueError("push takes one stream id per row (%d rows, %d ids)" % (n, len(ids)))
+        if any(not 0 <= s < self.max_streams for s in ids):
+            raise ValueError("stream ids must be in 0 .. %d; got %s" % (self.max_streams - 1, ids))
+        if len(set(ids)) != n:
+            raise ValueError("stream ids of a push must be distinct; got %s" % (ids,))
+        return self._launch(f, f_len, ids)
+
+    def _launch(self, f, f_len, ids, out=None):
+        """``push`` behind its host checks of the ids.  `out`: the four output tensors to write instead of fresh ones (tests)."""
+        self._check_handle()
+        _native.require_hip(f)
+        lib, dev = self._lib, self.device
+        f = f.contiguous().float()
+        n, t, _ = f.shape
+        with torch.cuda.device(dev):
+            max_tok = int(lib.effconf_rnnt_max_tokens(self._handle, t))
+            if n == 0 or t == 0:              # nothing to launch: no token, no step
+                return (torch.zeros(n, max_tok, dtype=torch.int32, device=dev), torch.full((n, max_tok), -1, dtype=torch.int32, device=dev),
+                        torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+            # the kernel writes every element of the four for every listed stream
+            tokens, token_frames, token_len, steps = out if out is not None else (
+                torch.empty(n, max_tok, dtype=torch.int32, device=dev), torch.empty(n, max_tok, dtype=torch.int32, device=dev),
+                torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            f_len = _native.lengths(f_len, n, t, dev)
+            idt = torch.tensor(ids, dtype=torch.int32, device=dev)
+            nbytes = _native.sized(lib, "effconf_rnnt_stream", lib.effconf_rnnt_stream_workspace_bytes(self._handle, n, t), streams=n, frames=t)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = _native.workspace(nbytes, dev)
+            _lib.check(lib.effconf_rnnt_greedy_resume(self._handle, self.state.data_ptr(), self.max_streams, idt.data_ptr(), f.data_ptr(), f_len.data_ptr(), n, t,
+                                                      tokens.data_ptr(), token_frames.data_ptr(), token_len.data_ptr(), steps.data_ptr(), max_tok,
+                                                      self._ws.data_ptr(), self._ws.numel(), self._stream()), "rnnt_greedy_resume", lib)
+        return tokens, token_frames, token_len, steps
+
+
+class StreamingTransducer:
+    """``Transducer.open_stream``: the encoder session plus the resumed greedy decode on the new frames.  Only streams that received output frames are listed
+    in a push's decode."""
+
+    def __init__(self, model, max_streams: int, max_frames: Optional[int] = None):
+        self.model = model
+        self.session = StreamingEncoder(model.encoder, max_streams, max_frames)       # refuses what cannot stream (stream_refusal) before any device work
+        self.decoder = RnntStreamState(model, max_streams)
+        self.encoder = model.encoder
+        self._tokens = [[] for _ in range(max_streams)]
+        self._steps = [0] * max_streams
+        self._consumed = [0] * max_streams                       # encoder frames decoded so far
+        self.last_token_frames = [[] for _ in range(max_streams)]
+        self.last_encoded = None
+
+    align_frames = property(lambda self: self.session.align_frames)
+
+    def frames_pending(self, stream: int) -> int:
+        return self.session.frames_pending(stream)
+
+    def reset(self, stream: int):
+        """`stream` starts a new utterance."""
+        self.session.reset(stream)
+        self.decoder.reset(stream)
+        self._tokens[stream], self._steps[stream], self._consumed[stream] = [], 0, 0
+        self.last_token_frames[stream] = []
+
+    def tokens(self, stream: int) -> List[int]:
+        """The stream's hypothesis so far."""
+        return list(self._tokens[stream])
+
+    def text(self, stream: int) -> str:
+        if self.model.tokenizer is None:
+            raise _lib.EffconfError("text() needs a tokenizer attached to the model")
+        return self.model.tokenizer.decode([self._tokens[stream]])[0]
+
+    def decoder_steps(self, stream: int) -> int:
+        """Prediction-network steps of the stream so far: tokens + 1 once it has had a frame."""
+        return self._steps[stream]
+
+    def _decode(self, out: torch.Tensor, out_len: torch.Tensor) -> List[List[int]]:
+        self.last_encoded = (out, out_len)
+        B = out.shape[0]
+        lens = out_len.tolist()
+        new = [[] for _ in range(B)]
+        self.last_token_frames = [[] for _ in range(B)]
+        active = [b for b in range(B) if lens[b] > 0]
+        if not active:
+            return new
+        ix = torch.tensor(active, dtype=torch.int64, device=out.device)
+        tokens, frames, token_len, steps = (z.tolist() for z in self.decoder.push(out[ix], out_len[ix], active))
+        for i, b in enumerate(active):
+            k = token_len[i]
+            new[b] = tokens[i][:k]
+            self.last_token_frames[b] = [self._consumed[b] + t for t in frames[i][:k]]
+            self._tokens[b] += new[b]
+            self._steps[b] += steps[i]
+            self._consumed[b] += lens[b]
+        return new
+
+    def push_mel(self, mel, mel_len, final=None) -> List[List[int]]:
+        """``StreamingEncoder.push_mel``, then the decode of the new encoder frames -> the new token ids per stream.  ``last_token_frames[b]``: the encoder frame
+        (counted from the stream's start; x ``encoder.frame_seconds`` = seconds) at which each of them was emitted."""
+        return self._decode(*self.session.push_mel(mel, mel_len, final))
+
+    def push_audio(self, x, x_len, final=None) -> List[List[int]]:
+        return self._decode(*self.session.push_audio(x, x_len, final))

@@ -11,7 +11,8 @@ fusion term (transducer.py:259-273: ``lm_weight * (lm.decode(y, hidden_lm) / lm_
 the search kernel and one chip-wide LM step over every utterance's pending hypotheses alternate).  The n-gram (KenLM) terms are not
 implemented.  For a KNOWN transcript, ``lattice`` gives the two log-probabilities per (t, u) cell the RNN-T loss sees
 (csrc/rnnt_lattice.hip: the (B, T, U + 1, V) logits of transducer.py:88-107 never reach memory), ``score_labels`` log P(y | x) = -rnnt_loss
-and ``align`` the frame at which each token is emitted (csrc/rnnt_align.hip: forward recursion and Viterbi over the lattice).  Training
+and ``align`` the frame at which each token is emitted (csrc/rnnt_align.hip: forward recursion and Viterbi over the lattice).  ``open_stream`` / ``open_decode_stream`` decode
+streams push by push from a carried prediction-network state (effconf_rnnt_greedy_resume), with the tokens of the whole-utterance greedy decode.  Training
 (``forward`` with gradients, the RNN-T loss' backward) is out of scope (HISTORY.md).
 """
 from __future__ import annotations
@@ -104,6 +105,7 @@ class Transducer(_native.NativeModel):
         self.name = name
         self._native = _native.Handle("rnnt")
         self._rnnt_packed = False
+        self._rnnt_generation = 0                # counts the native handle's rebuilds: what a decode stream was opened on
         self._beam_ws = None
         self._beam_rounds = None
         self.eval()
@@ -138,6 +140,7 @@ class Transducer(_native.NativeModel):
         self._native.rebuild(cfg, [(prefix + key, t) for prefix, mod in (("decoder.", self.decoder), ("joint_network.", self.joint_network))
                                    for key, t in mod.state_dict().items()])
         self._rnnt_packed = True
+        self._rnnt_generation += 1
 
     def set_decode_option(self, name: str, value: int):
         """Forward an option to the native decoder (effconf_rnnt_set_option), e.g. ``cluster_decode`` = -1 auto / 0 / 1."""
@@ -180,6 +183,19 @@ class Transducer(_native.NativeModel):
         return self.tokenizer.decode(ids) if self.tokenizer is not None else ids
 
     greedy_search_decoding = gready_search_decoding
+
+    # ------------------------------------------------------------------ streaming
+    def open_decode_stream(self, max_streams: int):
+        """The greedy decode resumed per stream, the decoder alone: ``push(f, f_len, streams)`` decodes the new encoder frames of the listed streams from the
+        prediction-network state each of them carries (efficientconformer_amd/streaming.py: RnntStreamState; effconf_rnnt_greedy_resume)."""
+        from .streaming import RnntStreamState
+        return RnntStreamState(self, max_streams)
+
+    def open_stream(self, max_streams: int, max_frames: Optional[int] = None):
+        """``ConformerEncoder.open_stream`` on the (causal, bf16) encoder plus the resumed greedy decode: ``push_mel`` / ``push_audio`` return the new token ids
+        per stream, ``tokens(stream)`` the hypothesis so far (streaming.py: StreamingTransducer).  Greedy only: the beam searches do not stream."""
+        from .streaming import StreamingTransducer
+        return StreamingTransducer(self, max_streams, max_frames)
 
     # ------------------------------------------------------------------ beam search
     def decode_encoded_beam(self, f: torch.Tensor, f_len: Optional[torch.Tensor], beam_size: Optional[int] = None,

@@ -291,6 +291,31 @@ int effconf_rnnt_greedy(EcRnnt* r, const float* enc_out, const int64_t* out_len,
                         int32_t* tokens, int32_t* token_len, int32_t max_tokens, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* Streaming greedy decode: effconf_rnnt_greedy resumed per stream, push by push (one workgroup per listed stream; the cluster kernels are not part of it).  The
+ * tokens of a stream, whatever its push pattern, are those of one effconf_rnnt_greedy ("cluster_decode" = 0) call on the same frames.
+ * State: one caller-provided device buffer of effconf_rnnt_stream_state_bytes(r, max_streams) bytes.  From the buffer's address aligned up to 256 bytes:
+ *   offset 0                                   i32 primed[max_streams]   1: the record holds the stream's state at a frame boundary
+ *   offset up256(4 * max_streams) + s * R      f32 h[dim_decoder], c[dim_decoder], gd[dim_joint] of stream s, R = up256(4 * (2 * dim_decoder + dim_joint))
+ * (h, c: the prediction network's LSTM state after every token emitted so far; gd = linear_decoder(h) + bias, what the next joint evaluation reads).
+ * effconf_rnnt_stream_init clears every flag, effconf_rnnt_stream_reset the flag of one stream (which then starts a new utterance: zero state, start token 0);
+ * both write nothing else, and a record whose flag is clear is never read.  Several state buffers may be used with one handle.
+ * effconf_rnnt_greedy_resume: streams dev i32 (n) DISTINCT stream ids, enc_out dev f32 (n, t_new, dim_encoder) the new frames of the listed streams, out_len
+ * dev i64 (n) how many of them each stream has (0 allowed: its record is left untouched) -> tokens dev i32 (n, max_tokens), zero-filled tails; token_frames
+ * (nullable) dev i32 (n, max_tokens): the push-local frame at which each token was emitted, -1 behind them; token_len dev i32 (n); decoder_steps (nullable)
+ * dev i32 (n): prediction-network steps this push ran - a primed stream runs none until it emits a token, so over a stream's life they sum to tokens + 1 (0
+ * for a stream that never had a frame).  A listed id outside 0 .. max_streams - 1 gets token_len = -1 and nothing else is written for it.
+ * max_tokens >= effconf_rnnt_max_tokens(r, t_new): the bound holds per push, the consecutive-token counter is 0 at every frame boundary.  The workspace
+ * (effconf_rnnt_stream_workspace_bytes) holds linear_encoder(enc_out) of the push.  Refused before any launch: a handle that is not finalized, n < 0,
+ * t_new <= 0, a short token buffer or workspace; effconf_rnnt_stream_init refuses a short state buffer.  The two size queries return 0 for arguments the
+ * entries reject. */
+size_t effconf_rnnt_stream_state_bytes(const EcRnnt* r, int32_t max_streams);
+int effconf_rnnt_stream_init(EcRnnt* r, void* state, size_t state_bytes, int32_t max_streams, void* stream);
+int effconf_rnnt_stream_reset(EcRnnt* r, void* state, int32_t max_streams, int32_t stream_id, void* stream);
+size_t effconf_rnnt_stream_workspace_bytes(const EcRnnt* r, int32_t n, int32_t t_new);
+int effconf_rnnt_greedy_resume(EcRnnt* r, void* state, int32_t max_streams, const int32_t* streams, const float* enc_out, const int64_t* out_len,
+                               int32_t n, int32_t t_new, int32_t* tokens, int32_t* token_frames, int32_t* token_len, int32_t* decoder_steps,
+                               int32_t max_tokens, void* workspace, size_t workspace_bytes, void* stream);
+
 /* RNN-T beam search: Transducer.beam_search_decoding (transducer.py:188-327) without the neural-LM / n-gram terms, one persistent
  * workgroup per utterance.  1 <= beam <= min(16, vocab_size), temperature > 0 (decoding_params["tmp"]), dim_decoder and dim_joint
  * multiples of 16.  At most max_expansions hypotheses are expanded per frame and at most max_tokens tokens returned; status dev i32

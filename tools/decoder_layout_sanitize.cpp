@@ -63,6 +63,13 @@ int main() {
                 check_total("greedy_layout", {{L.fe, (size_t)b * t * J * 4}, {L.sync, L.sync_bytes}, {L.xh, n * s[1] * H * 4}, {L.xgd, n * s[1] * J * 4}, {L.xav, cand}, {L.xai, cand}},
                             L.total);
             }
+            {   // the resumed greedy decode: `b` listed streams' push workspace, and the state buffer of b streams
+                const RnntStreamWs W = rnnt_stream_ws(c, b, t);
+                check_total("rnnt_stream_ws", {{W.fe, (size_t)b * t * J * 4}}, W.total);
+                const RnntStreamLayout L = rnnt_stream_layout(c, b);
+                check_regions("rnnt_stream_layout (stream)", {{0, (2 * H + J) * 4}}, L.rec_bytes);
+                check_total("rnnt_stream_layout", {{L.primed, (size_t)b * 4}, {L.rec, (size_t)b * L.rec_bytes}}, L.total);
+            }
             for (int beam : beams) {
                 if (beam > 16) continue;
                 const BeamLayout L = beam_layout(c, b, t, beam, 16 * beam);
