@@ -71,6 +71,11 @@ SIGNATURES = {
     "effconf_ctc_greedy_margin": (C.c_int, [_P, _P, _I32, _I64P, _I32, _I32, _P, _P, _F32P, _F32P, _F32P, _P, _P, _SZ, _P]),
     "effconf_ctc_beam_workspace_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
     "effconf_ctc_beam": (C.c_int, [_F32P, _I64P, _I32, _I32, _I32, _I32, C.c_float, _P, _P, _F32P, _P, _SZ, _P]),
+    "effconf_ctc_beam_stream_state_bytes": (_SZ, [_I32, _I32, _I32]),
+    "effconf_ctc_beam_stream_init": (C.c_int, [_P, _SZ, _I32, _I32, _I32, _P]),
+    "effconf_ctc_beam_stream_reset": (C.c_int, [_P, _I32, _I32, _P]),
+    "effconf_ctc_beam_stream_workspace_bytes": (_SZ, [_I32, _I32, _I32]),
+    "effconf_ctc_beam_resume": (C.c_int, [_P, _I32, _I32, _I32, _P, _F32P, _I64P, _I32, _I32, _I32, C.c_float, _I32, _P, _P, _F32P, _P, _I32, _P, _SZ, _P]),
     "effconf_ctc_beam_lm_workspace_bytes": (_SZ, [_P, _I32, _I32, _I32, _I32]),
     "effconf_ctc_beam_lm": (C.c_int, [_P, _F32P, _I64P, _I32, _I32, _I32, _I32, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _F32P, _F32P, _F32P,
                                       C.POINTER(C.c_int32), _P, _SZ, _P]),

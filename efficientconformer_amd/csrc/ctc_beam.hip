@@ -33,6 +33,12 @@
 //     slot, its slot, live) per rank, counts itself in the round counter and exits; the host runs ONE LM step for the requests of all utterances and
 //     launches again.  On resume the raw logits rows are turned into log-softmax rows in the slots (one wave per row).  An utterance whose new beam needs no
 //     LM goes on in the same launch; a finished utterance's workgroup returns at once; the hash index is initialised in the first launch only.
+//
+// Resumed per stream (effconf_ctc_beam_resume, ctc_beam_resume_kernel: ctc_beam_search.h with STREAM = true): the plain search over the frames of one
+// push.  The search never looks ahead, so all it knows after a frame is the beam (per member: node, last token, parent, depth, pb, pnb, s) and the append-only trie
+// with its hash; both live in the stream's block of a caller-provided state buffer and outlive the call, so the beam after any pushes is bit for bit the beam of one
+// whole call.  A push's frames and trace are push-local; the trie is sized for max_frames frames of the stream.  Outputs: the ranks' tokens, lengths and scores as
+// the beam stands, and stable_len - the length of the common prefix of ALL members, which every later hypothesis begins with.
 #include "decode_common.h"
 
 #include <cmath>
@@ -60,6 +66,14 @@ const char* ctc_beam_check(int32_t batch, int32_t t_out, int32_t vocab, int32_t 
     return nullptr;
 }
 
+// the shape of a stream state: ctc_beam_check's limits with max_frames in t_out's place
+const char* ctc_beam_stream_check(int32_t max_streams, int32_t max_frames, int32_t beam) {
+    if (max_streams < 1) return "ctc beam search: max_streams must be >= 1";
+    if (max_frames < 1) return "ctc beam search: max_frames must be >= 1";
+    if (max_streams > (1 << 20)) return "ctc beam search: max_streams must be at most 2^20";
+    return ctc_beam_check(0, max_frames, 2, beam);
+}
+
 struct CtcBeamArgs {
     const float* logits; const int64_t* lens;
     int T, V, beam; float tmp;
@@ -82,6 +96,20 @@ struct CtcLmSide {
 
 enum { R_PHASE = 0, R_FRAME, R_N, R_NN, R_NCLO, R_NCHI, R_NREQ };
 static_assert(R_NREQ < CTC_LM_RESUME_HEAD, "resume record");
+
+// the resumed search's side of the arguments (empty for the two whole-utterance kernels).  There a.utt / a.L.per_utt / a.L.trace address the push's traces in the
+// workspace, a.L.nodes / hkeys / hvals / hcap are those of a stream's block, a.T is t_new and tokens / token_len / score are (n, nbest, ..)
+struct CtcStreamSide {
+    const int* streams;      // [n] listed stream ids
+    int* primed;             // [max_streams] 1: the record holds the stream's beam at a frame boundary
+    char* blocks;            // the streams' blocks, per_stream apart: record, trie nodes, hash
+    size_t per_stream, rec;  // rec: the record inside a block
+    int max_streams, max_frames, nbest, max_tokens;
+    int* stable_len;         // [n]
+};
+
+enum { S_FRAMES = 0, S_N, S_NN, S_NCLO, S_NCHI };    // the head of a stream's record
+static_assert(S_NCHI < CTC_STREAM_HEAD && CTC_STREAM_MAXB == MAXB && CTC_LM_MAXB == MAXB, "stream record");
 
 // logaddexp in the log1pf form of the prefix beam search this kernel follows; rnnt_align.hip's lse2 and ctc_align.hip's lse3 are the logf form of the losses
 // they follow: different formulas on purpose
@@ -128,13 +156,22 @@ __device__ __forceinline__ float fused_total(float s, float L, int len, float w,
 
 // ctc_beam_search.h is the search itself
 __global__ __launch_bounds__(CT) void ctc_beam_kernel(const CtcBeamArgs a) {
-    constexpr bool LM = false;
+    constexpr bool LM = false, STREAM = false;
     const CtcLmSide fz{};
+    const CtcStreamSide sz{};
 #include "ctc_beam_search.h"
 }
 
 __global__ __launch_bounds__(CT) void ctc_beam_lm_kernel(const CtcBeamArgs a, const CtcLmSide fz) {
-    constexpr bool LM = true;
+    constexpr bool LM = true, STREAM = false;
+    const CtcStreamSide sz{};
+#include "ctc_beam_search.h"
+}
+
+// one workgroup per listed stream: the plain search over the push's frames, from and to the stream's record
+__global__ __launch_bounds__(CT) void ctc_beam_resume_kernel(const CtcBeamArgs a, const CtcStreamSide sz) {
+    constexpr bool LM = false, STREAM = true;
+    const CtcLmSide fz{};
 #include "ctc_beam_search.h"
 }
 
@@ -178,6 +215,63 @@ int effconf_ctc_beam(const float* logits, const int64_t* out_len, int32_t batch,
     a.tokens = tokens; a.token_len = token_len; a.score = score;
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(batch), dim3(CT), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : ec_fail("ctc_beam launch failed");
+}
+
+// ---- the plain search resumed per stream (include/effconf.h)
+size_t effconf_ctc_beam_stream_state_bytes(int32_t max_streams, int32_t max_frames, int32_t beam) {
+    if (const char* e = ctc_beam_stream_check(max_streams, max_frames, beam)) { ec_fail(e); return 0; }
+    return ctc_beam_stream_layout(max_streams, max_frames, beam).total;
+}
+
+int effconf_ctc_beam_stream_init(void* state, size_t state_bytes, int32_t max_streams, int32_t max_frames, int32_t beam, void* stream) {
+    if (const char* e = ctc_beam_stream_check(max_streams, max_frames, beam)) return ec_fail(e);
+    if (!state) return ec_fail("null argument");
+    const CtcBeamStreamLayout L = ctc_beam_stream_layout(max_streams, max_frames, beam);
+    if (state_bytes < L.total) return ec_fail("stream state buffer too small (effconf_ctc_beam_stream_state_bytes)");
+    // the flags alone: a record whose flag is clear is never read, and the kernel initialises a stream's hash at its first frame
+    if (hipMemsetAsync(WsPlan::base(state) + L.primed, 0, (size_t)max_streams * 4, (hipStream_t)stream) != hipSuccess) return ec_fail("memset failed");
+    return 0;
+}
+
+int effconf_ctc_beam_stream_reset(void* state, int32_t max_streams, int32_t stream_id, void* stream) {
+    if (!state) return ec_fail("null argument");
+    if (max_streams < 1 || stream_id < 0 || stream_id >= max_streams) return ec_fail("stream id outside 0 .. max_streams - 1");
+    // primed[] is the first region of every layout: its offset depends on nothing
+    if (hipMemsetAsync(WsPlan::base(state) + (size_t)stream_id * 4, 0, 4, (hipStream_t)stream) != hipSuccess) return ec_fail("memset failed");
+    return 0;
+}
+
+size_t effconf_ctc_beam_stream_workspace_bytes(int32_t n, int32_t t_new, int32_t beam) {
+    if (const char* e = ctc_beam_check(n, t_new, 2, beam)) { ec_fail(e); return 0; }
+    return ctc_beam_stream_ws(n, t_new, beam).total;
+}
+
+int effconf_ctc_beam_resume(void* state, int32_t max_streams, int32_t max_frames, int32_t beam, const int32_t* streams, const float* logits,
+                            const int64_t* out_len, int32_t n, int32_t t_new, int32_t vocab, float temperature, int32_t nbest, int32_t* tokens,
+                            int32_t* token_len, float* score, int32_t* stable_len, int32_t max_tokens, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    if (const char* e = ctc_beam_stream_check(max_streams, max_frames, beam)) return ec_fail(e);
+    if (const char* e = ctc_beam_check(n, t_new, vocab, beam)) return ec_fail(e);
+    if (nbest < 1 || nbest > beam) return ec_fail("ctc beam search: nbest must be in 1 .. beam");
+    if (max_tokens < 1 || max_tokens > (1 << 24)) return ec_fail("ctc beam search: max_tokens must be in 1 .. 2^24 (no hypothesis is longer than max_frames)");
+    if (!(temperature > 0.f) || !std::isfinite(temperature)) return ec_fail("ctc beam search: temperature must be > 0");
+    const CtcBeamStreamWs W = ctc_beam_stream_ws(n, t_new, beam);
+    if (workspace_bytes < W.total) return ec_fail("workspace too small (effconf_ctc_beam_stream_workspace_bytes)");
+    if (n == 0) return 0;
+    if (!state || !streams || !out_len || !tokens || !token_len || !score || !stable_len || !workspace || (t_new > 0 && !logits)) return ec_fail("null argument");
+    const CtcBeamStreamLayout S = ctc_beam_stream_layout(max_streams, max_frames, beam);
+    char* ws = WsPlan::base(workspace);
+    char* st = WsPlan::base(state);
+    CtcBeamArgs a{};
+    a.logits = logits; a.lens = out_len; a.T = t_new; a.V = vocab; a.beam = beam; a.tmp = temperature;
+    a.utt = ws + W.trace; a.stats = reinterpret_cast<int*>(ws + W.stats);
+    a.L.ncap = S.ncap; a.L.hcap = S.hcap; a.L.per_utt = W.per_trace; a.L.trace = 0; a.L.nodes = S.nodes; a.L.hkeys = S.hkeys; a.L.hvals = S.hvals;
+    a.tokens = tokens; a.token_len = token_len; a.score = score;
+    CtcStreamSide sz{};
+    sz.streams = streams; sz.primed = reinterpret_cast<int*>(st + S.primed); sz.blocks = st + S.blocks; sz.per_stream = S.per_stream; sz.rec = S.rec;
+    sz.max_streams = max_streams; sz.max_frames = max_frames; sz.nbest = nbest; sz.max_tokens = max_tokens; sz.stable_len = stable_len;
+    hipLaunchKernelGGL(ctc_beam_resume_kernel, dim3(n), dim3(CT), 0, (hipStream_t)stream, a, sz);
+    return hipGetLastError() == hipSuccess ? 0 : ec_fail("ctc_beam_resume launch failed");
 }
 
 size_t effconf_ctc_beam_lm_workspace_bytes(const EcLm* lm, int32_t batch, int32_t t_out, int32_t vocab, int32_t beam) {

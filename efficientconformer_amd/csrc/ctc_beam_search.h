@@ -1,6 +1,8 @@
-// The body of the CTC prefix beam search, shared by the two kernels of ctc_beam.hip: NOT a stand-alone header.  ctc_beam.hip includes it inside
-// ctc_beam_kernel (LM = false: the plain search) and inside ctc_beam_lm_kernel (LM = true: the fused search, resumable); it reads `a` (CtcBeamArgs), `fz`
-// (CtcLmSide) and the constant `LM` of the enclosing kernel.  The search is written once; an `if constexpr (LM)` branch is not compiled into the plain kernel.
+// The body of the CTC prefix beam search, shared by the three kernels of ctc_beam.hip: NOT a stand-alone header.  ctc_beam.hip includes it inside
+// ctc_beam_kernel (LM = false: the plain search), inside ctc_beam_lm_kernel (LM = true: the fused search, resumable) and inside ctc_beam_resume_kernel (LM = false,
+// STREAM = true: the plain search of one push, its beam and trie carried in the stream's state); it reads `a` (CtcBeamArgs), `fz` (CtcLmSide), `sz` (CtcStreamSide)
+// and the constants `LM` and `STREAM` of the enclosing kernel.  The search is written once; an `if constexpr` branch is not compiled into the kernels it is not for.
+// STREAM: workgroup b runs stream sz.streams[b]; frames and trace are push-local (0 .. len - 1), the trie and its hash live in the stream's block of the state.
 // (As a function template called from two one-line kernels the plain kernel came out one VGPR larger than it was as a kernel of its own; as the kernel's own body
 // it is compiled to the registers it had.)
     __shared__ float slp[MAXV];                   // the frame's log-probabilities
@@ -31,11 +33,20 @@
     const int K = 2 * beam + 1 < V ? 2 * beam + 1 : V;
     long long lenll = a.lens[b];
     const int len = lenll < 0 ? 0 : (lenll > T ? T : (int)lenll);
+    int sid = b;
+    if constexpr (STREAM) {                        // the first guard, before any address of the state is formed (workgroup-uniform)
+        sid = sz.streams[b];
+        if (sid < 0 || sid >= sz.max_streams) {
+            if (tid < sz.nbest) a.token_len[(size_t)b * sz.nbest + tid] = -1;
+            return;
+        }
+    }
     char* base = a.utt + (size_t)b * L.per_utt;
+    char* tbase = STREAM ? sz.blocks + (size_t)sid * sz.per_stream : base;     // where the trie lives
     int4* trace = reinterpret_cast<int4*>(base + L.trace);
-    int4* nodes = reinterpret_cast<int4*>(base + L.nodes);
-    unsigned long long* hkeys = reinterpret_cast<unsigned long long*>(base + L.hkeys);
-    int* hvals = reinterpret_cast<int*>(base + L.hvals);
+    int4* nodes = reinterpret_cast<int4*>(tbase + L.nodes);
+    unsigned long long* hkeys = reinterpret_cast<unsigned long long*>(tbase + L.hkeys);
+    int* hvals = reinterpret_cast<int*>(tbase + L.hvals);
     const unsigned hmask = (unsigned)L.hcap - 1;
     const float* lrow = a.logits + (size_t)b * T * V;
     int t0 = 0;
@@ -54,15 +65,28 @@
         trace2 = reinterpret_cast<float2*>(base + fz.trace2);
         nf = fz.nls + V;
     }
+    int consumed = 0;                              // STREAM: frames of the stream before this push
+    if constexpr (STREAM) {
+        // the second guard: it reads the stream's flag and, where that is set, the frame count of its record - nothing else, and writes nothing (uniform)
+        rec = reinterpret_cast<int*>(tbase + sz.rec);
+        fresh = sz.primed[sid] == 0;
+        consumed = fresh ? 0 : rec[S_FRAMES];
+        if (len > sz.max_frames - consumed) {
+            if (tid < sz.nbest) a.token_len[(size_t)b * sz.nbest + tid] = -2;
+            return;
+        }
+    }
 
     if (fresh) {
-        for (int i = tid; i < L.hcap; i += CT) __hip_atomic_store(hkeys + i, HEMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // STREAM: a push without frames writes nothing to the state (the beam of a stream that never had a frame is the empty prefix, in LDS alone)
+        const int hinit = !STREAM || len > 0 ? L.hcap : 0;
+        for (int i = tid; i < hinit; i += CT) __hip_atomic_store(hkeys + i, HEMPTY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if constexpr (!LM) {
             for (int i = tid; i < MAXV; i += CT) spos[i] = -1;
             hist[0][tid] = 0u;
         }
         if (tid == 0) {
-            nodes[0] = make_int4(-1, -1, 0, 0);
+            if (!STREAM || len > 0) nodes[0] = make_int4(-1, -1, 0, 0);
             bnode[0][0] = 0; blast[0][0] = -1; bpar[0][0] = -1; bdep[0][0] = 0;
             bpb[0][0] = 0.f; bpnb[0][0] = -INFINITY; bs[0][0] = 0.f;
             s_n = 1; s_nn = 1; s_nsel = 0; s_nvalid = 0;
@@ -82,6 +106,20 @@
             nreq = rec[R_NREQ];
         }
         t0 = rec[R_FRAME];
+    } else if constexpr (STREAM) {                 // resume: the beam as the stream's last push with frames left it.  The LDS the radix select counts on is
+        const int* ra = rec + CTC_STREAM_HEAD;     // set in every launch
+        for (int i = tid; i < MAXV; i += CT) spos[i] = -1;
+        hist[0][tid] = 0u;
+        const int rn = rec[S_N] < beam ? rec[S_N] : beam;
+        if (tid < rn) {
+            bnode[0][tid] = ra[tid]; blast[0][tid] = ra[MAXB + tid]; bpar[0][tid] = ra[2 * MAXB + tid]; bdep[0][tid] = ra[3 * MAXB + tid];
+            bpb[0][tid] = __int_as_float(ra[4 * MAXB + tid]); bpnb[0][tid] = __int_as_float(ra[5 * MAXB + tid]);
+            bs[0][tid] = __int_as_float(ra[6 * MAXB + tid]);
+        }
+        if (tid == 0) {
+            s_n = rn; s_nn = rec[S_NN]; s_nsel = 0; s_nvalid = 0;
+            ncand0 = ((long long)rec[S_NCHI] << 32) | (unsigned)rec[S_NCLO];
+        }
     }
     float nx[TPT];
 #pragma unroll
@@ -477,8 +515,66 @@
             }
         }
     }
-    // ---- outputs in rank order: tokens by walking the trie from each member's node
     const int n = s_n;
+    if constexpr (STREAM) {
+    // ---- the record (only after a push with frames), then the outputs of the beam as it stands
+    if (len > 0) {
+        int* ra = rec + CTC_STREAM_HEAD;
+        if (tid < n) {
+            ra[tid] = bnode[cur][tid]; ra[MAXB + tid] = blast[cur][tid]; ra[2 * MAXB + tid] = bpar[cur][tid]; ra[3 * MAXB + tid] = bdep[cur][tid];
+            ra[4 * MAXB + tid] = __float_as_int(bpb[cur][tid]); ra[5 * MAXB + tid] = __float_as_int(bpnb[cur][tid]);
+            ra[6 * MAXB + tid] = __float_as_int(bs[cur][tid]);
+        }
+        if (tid == 0) {
+            rec[S_FRAMES] = consumed + len; rec[S_N] = n; rec[S_NN] = s_nn;
+            rec[S_NCLO] = (int)(unsigned)(ncand & 0xffffffffll); rec[S_NCHI] = (int)(ncand >> 32);
+            sz.primed[sid] = 1;
+        }
+    }
+    const int nbest = sz.nbest, MT = sz.max_tokens;
+    if (tid < nbest) {                             // token_len is the true depth; tokens beyond max_tokens are not written
+        int* out = a.tokens + ((size_t)b * nbest + tid) * MT;
+        int d = 0;
+        float sc = -INFINITY;
+        if (tid < n) {
+            d = bdep[cur][tid];
+            sc = bs[cur][tid];
+            int node = bnode[cur][tid];
+            for (int i = d - 1; i >= 0; --i) {
+                const int4 nd = nodes[node];
+                if (i < MT) out[i] = nd.y;
+                node = nd.x;
+            }
+        }
+        a.token_len[(size_t)b * nbest + tid] = d;
+        a.score[(size_t)b * nbest + tid] = sc;
+    }
+    for (int j = tid; j < nbest * MT; j += CT) {
+        const int r = j / MT, i = j - r * MT;
+        if (i >= (r < n ? bdep[cur][r] : 0)) a.tokens[((size_t)b * nbest + r) * MT + i] = 0;
+    }
+    // the longest common prefix of all members (one wave): lift every member's node to the smallest depth, then step the parents together until all agree.
+    // Node identity is string identity, so equal nodes at equal depth are equal prefixes; at depth 0 every node is the root
+    if (wave == 0) {
+        int node = lane < n ? bnode[cur][lane] : 0, d = lane < n ? bdep[cur][lane] : 0x7fffffff, dmin = d;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { const int od = __shfl_xor(dmin, o); dmin = od < dmin ? od : dmin; }
+        if (lane < n)
+            for (; d > dmin; --d) node = nodes[node].x;
+        while (dmin > 0 && __ballot(lane < n && node != __shfl(node, 0)) != 0ull) {      // wave-uniform; lane 0 is always a member
+            if (lane < n) node = nodes[node].x;
+            --dmin;
+        }
+        if (lane == 0) sz.stable_len[b] = dmin;
+    }
+    if (tid == 0) {
+        a.stats[4 * b + 0] = len;
+        a.stats[4 * b + 1] = (int)(ncand < 0x7fffffffll ? ncand : 0x7fffffffll);
+        a.stats[4 * b + 2] = s_nn;
+        a.stats[4 * b + 3] = consumed + len;
+    }
+    } else {
+    // ---- outputs in rank order: tokens by walking the trie from each member's node
     if (tid < beam) {
         int* out = a.tokens + ((size_t)b * beam + tid) * T;
         int d = 0;
@@ -508,4 +604,5 @@
         a.stats[4 * b + 2] = s_nn;
         a.stats[4 * b + 3] = LM ? nreq : 0;
         if constexpr (LM) rec[R_PHASE] = 2;
+    }
     }

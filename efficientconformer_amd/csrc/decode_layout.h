@@ -221,6 +221,53 @@ inline CtcBeamLayout ctc_beam_layout(int batch, int t_out, int beam) {
     return L;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- ctc_beam.hip: the plain search, resumed per stream
+// The caller's state buffer: i32 primed[max_streams], then one block per stream, per_stream apart: the record (a head of CTC_STREAM_HEAD i32: frames consumed,
+// members, trie nodes, candidates lo / hi, then unused; then node, last, parent, depth, pb, pnb, s: [32] each) and the stream's trie - nodes int4 [ncap], hash keys
+// u64 [hcap], hash nodes i32 [hcap], ncap = 1 + beam * max_frames, hcap as ctc_beam_layout's.  The workspace of a push: stats[n][4] and its trace [t_new][beam] int4
+// per listed stream.
+constexpr int CTC_STREAM_MAXB = 32;                                      // ctc_beam.hip's largest beam
+constexpr int CTC_STREAM_HEAD = 16;
+constexpr int CTC_STREAM_REC_INTS = CTC_STREAM_HEAD + 7 * CTC_STREAM_MAXB;
+
+struct CtcBeamStreamLayout {
+    int ncap, hcap;
+    size_t primed, blocks, per_stream, rec, nodes, hkeys, hvals, total;  // rec .. hvals: inside a stream's block
+};
+
+inline CtcBeamStreamLayout ctc_beam_stream_layout(int max_streams, int max_frames, int beam) {
+    CtcBeamStreamLayout L{};
+    L.ncap = 1 + beam * max_frames;
+    int h = 1;
+    while (h < 2 * L.ncap) h <<= 1;
+    L.hcap = h;
+    WsPlan u;                                     // one stream
+    L.rec = u.take((size_t)CTC_STREAM_REC_INTS * 4);
+    L.nodes = u.take((size_t)L.ncap * 16);
+    L.hkeys = u.take((size_t)h * 8);
+    L.hvals = u.take((size_t)h * 4);
+    L.per_stream = u.stride();
+    WsPlan p;
+    L.primed = p.take((size_t)max_streams * 4);
+    L.blocks = p.take((size_t)max_streams * L.per_stream);
+    L.total = p.total();
+    return L;
+}
+
+struct CtcBeamStreamWs { size_t stats, trace, per_trace, total; };
+
+inline CtcBeamStreamWs ctc_beam_stream_ws(int n, int t_new, int beam) {
+    CtcBeamStreamWs L{};
+    WsPlan u;                                     // one listed stream
+    u.take((size_t)t_new * beam * 16);
+    L.per_trace = u.stride();
+    WsPlan p;
+    L.stats = p.take((size_t)n * 16);
+    L.trace = p.take((size_t)n * L.per_trace);
+    L.total = p.total();
+    return L;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- ctc_beam.hip with a neural LM (shallow fusion)
 // The search's regions, and per utterance: a second trace {f32 L, f32 total} per frame and rank, and 2 * beam + 1 LM slots of the node layout lm_columns_step
 // reads and writes ([layer][h k-permuted | c], 2 * layers * dim_model floats, then the slot's row: vocab floats).  Per call: one request (token, source slot,

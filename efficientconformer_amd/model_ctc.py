@@ -11,7 +11,8 @@ probability cutoffs below the shipped ones are not implemented; a ``LanguageMode
 it (``rescore_nbest``, ``beam_labels_rescored``, ``beam_search_rescored``; csrc/lm.hip) or is fused INTO the search (``decode_logits_beam_lm``,
 ``beam_labels_fused``, ``beam_search_fused``; effconf_ctc_beam_lm: every frame's candidates are ranked with the LM's score of the prefix).  Token timestamps and transcript scores come from the forced alignment instead:
 ``align`` / ``greedy_alignment`` (Viterbi over the CTC trellis: which frames each token covers) and ``score_labels`` (the CTC forward
-algorithm: log P(y | x), -ctc_loss without the host copy) run on the same logits in csrc/ctc_align.hip (effconf_ctc_align).  Training
+algorithm: log P(y | x), -ctc_loss without the host copy) run on the same logits in csrc/ctc_align.hip (effconf_ctc_align).  On a stream the plain search is
+resumed push by push from a carried beam (``open_stream(..., beam_size=k)``, ``open_beam_decode_stream``; effconf_ctc_beam_resume).  Training
 (losses with gradients, optimizer, schedules), WER scoring and word-level (SentencePiece-merging) timestamps are out of scope (HISTORY.md).
 """
 from __future__ import annotations
@@ -140,11 +141,22 @@ class ModelCTC(_native.NativeModel):
     # top-2 margin next to it (the sizes effconf_ctc_greedy / _bf16 / _margin check, csrc/encoder.hip)
     _GREEDY_WS, _MARGIN_WS = 4, 8
 
-    def open_stream(self, max_streams: int, max_frames: Optional[int] = None):
+    def open_stream(self, max_streams: int, max_frames: Optional[int] = None, beam_size: Optional[int] = None):
         """``ConformerEncoder.open_stream`` with the greedy head on the new frames: ``push_mel`` / ``push_audio`` return the new token ids per stream, the
-        repeat collapse carried across pushes (streaming.py: ctc_collapse_carry)."""
-        from .streaming import StreamingCTC
+        repeat collapse carried across pushes (streaming.py: ctc_collapse_carry).  With a `beam_size`: a ``StreamingCTCBeam`` - the prefix beam search resumed
+        on the new rows' logits (effconf_ctc_beam_resume), which returns the newly COMMITTED tokens of every push and needs `max_frames`
+        (ValueError without it).  Not built: LM fusion in a streaming search, trie compaction for unbounded streams."""
+        from .streaming import StreamingCTC, StreamingCTCBeam
+        if beam_size is not None:
+            return StreamingCTCBeam(self, max_streams, max_frames, int(beam_size))
         return StreamingCTC(self, max_streams, max_frames)
+
+    def open_beam_decode_stream(self, max_streams: int, max_frames: int, beam_size: Optional[int] = None, device=None):
+        """The streaming decoder alone (the counterpart of ``Transducer.open_decode_stream``): a ``CtcBeamStreamState`` whose ``push`` resumes the CTC prefix
+        beam search of `max_streams` streams on new head logits; `max_frames` logit frames per utterance at the most; beam_size None: ``self.beam_size``.
+        `device`: where the state lives when the model's parameters are not on a HIP device (the decoder reads logits only)."""
+        from .streaming import CtcBeamStreamState
+        return CtcBeamStreamState(self, max_streams, max_frames, beam_size, device)
 
     def _greedy_rows(self, rows: torch.Tensor, as_bf16: bool, lens: torch.Tensor, lo: int, hi: int, labels, label_len, logits=None, margins=None):
         """The greedy head on utterances [lo, hi) of `rows` (B, T, D) - and of every other tensor given - on the current stream:

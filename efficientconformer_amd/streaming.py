@@ -9,6 +9,10 @@ The session arithmetic is plain Python on the plan (no GPU, no library; tests/te
   cache_capacities(plan, ...)   grouped K / V rows kept per block: the band of forward_common.h (left_context // (mask_stride * group)), an unlimited
                                 left_context: what max_frames gives
   ctc_collapse_carry(...)       greedy CTC collapse with the repeat carried across pushes
+  beam_push_refusal(...)        why a push of the resumed beam search is refused on the host; common_prefix_len: what its stable_len is
+
+CTC beam search: ``CtcBeamStreamState`` carries the beam and the prefix trie per stream and resumes the prefix beam search on the new logit frames
+(effconf_ctc_beam_resume); ``StreamingCTCBeam`` is the encoder session, the head and that search, and returns the tokens no later frame can change.
 
 Transducers: ``RnntStreamState`` carries the prediction network's state per stream and resumes the greedy RNN-T decode on the new encoder frames
 (effconf_rnnt_greedy_resume); ``StreamingTransducer`` is the encoder session plus that decode.
@@ -313,6 +317,247 @@ class StreamingCTC:
 
     def push_audio(self, x, x_len, final=None) -> List[List[int]]:
         return self._tokens(*self.session.push_audio(x, x_len, final))
+
+
+# ------------------------------------------------------------------ CTC: the prefix beam search resumed per stream
+def beam_push_refusal(ids: Sequence[int], new_frames: Sequence[int], consumed: Sequence[int], max_streams: int, max_frames: int) -> Optional[str]:
+    """Why a push of the resumed beam search is refused on the host (None: it is not): `ids` the listed streams, `new_frames[i]` the frames listed stream i
+    brings, `consumed[s]` the frames stream s has had.  Pure: no GPU, no library."""
+    if len(new_frames) != len(ids):
+        return "push takes one stream id per row (%d rows, %d ids)" % (len(new_frames), len(ids))
+    if any(not 0 <= s < max_streams for s in ids):
+        return "stream ids must be in 0 .. %d; got %s" % (max_streams - 1, list(ids))
+    if len(set(ids)) != len(ids):
+        return "stream ids of a push must be distinct; got %s" % (list(ids),)
+    for s, k in zip(ids, new_frames):
+        if k < 0 or consumed[s] + k > max_frames:
+            return "stream %d would hold %d frames: the stream state was sized for max_frames = %d" % (s, consumed[s] + k, max_frames)
+    return None
+
+
+def common_prefix_len(hyps: Sequence[Sequence[int]]) -> int:
+    """Length of the longest common prefix of token strings: what ``stable_len`` is for the members of a beam."""
+    if not hyps:
+        return 0
+    n = min(len(h) for h in hyps)
+    for i in range(n):
+        if any(h[i] != hyps[0][i] for h in hyps):
+            return i
+    return n
+
+
+class CtcBeamStreamState:
+    """``ModelCTC.open_beam_decode_stream``: the beam of `max_streams` streams (per stream the members' record and the stream's prefix trie, in one device
+    buffer this object owns: include/effconf.h has the layout) and the CTC prefix beam search resumed from it, push by push (effconf_ctc_beam_resume).  The
+    beam of a stream, whatever its push pattern, is bit for bit that of one ``decode_logits_beam`` of the same frames.  `max_frames`: logit frames (encoder
+    output rows) a stream can take before it is reset - the trie only grows.  Not built: LM fusion in a streaming search (``decode_logits_beam_lm`` is
+    whole-utterance only), a streaming RNN-T beam search, trie compaction for unbounded streams."""
+
+    def __init__(self, model, max_streams: int, max_frames: int, beam_size: Optional[int] = None, device=None):
+        if max_streams < 1:
+            raise ValueError("max_streams must be >= 1")
+        if max_frames is None or max_frames < 1:
+            raise ValueError("max_frames must be >= 1: the stream's prefix trie is sized by it")
+        self.model, self.max_streams, self.max_frames = model, int(max_streams), int(max_frames)
+        self.beam = int(model.beam_size if beam_size is None else beam_size)
+        model._check_beam(self.beam, model.fc.out_features)
+        if device is None:
+            _native.require_hip(model.fc.weight)
+            device = model.fc.weight.device
+        self.device = torch.device(device)
+        lib = self._lib = _lib.load()
+        nbytes = _native.sized(lib, "effconf_ctc_beam_stream_state", lib.effconf_ctc_beam_stream_state_bytes(self.max_streams, self.max_frames, self.beam),
+                               streams=self.max_streams, frames=self.max_frames, beam=self.beam)
+        self.state = _native.workspace(nbytes, self.device)
+        self._frames = [0] * self.max_streams
+        self._ws, self._last = None, None
+        self.init()
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def init(self):
+        """Every stream starts a new utterance (only the flags are written: a record whose flag is clear is never read)."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.effconf_ctc_beam_stream_init(self.state.data_ptr(), self.state.numel(), self.max_streams, self.max_frames, self.beam,
+                                                              self._stream()), "ctc_beam_stream_init", self._lib)
+        self._frames = [0] * self.max_streams
+
+    def reset(self, stream: int):
+        """`stream` starts a new utterance."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.effconf_ctc_beam_stream_reset(self.state.data_ptr(), self.max_streams, int(stream), self._stream()),
+                       "ctc_beam_stream_reset", self._lib)
+        self._frames[stream] = 0
+
+    def frames(self, stream: int) -> int:
+        """Logit frames `stream` has consumed since its last reset (host counter)."""
+        return self._frames[stream]
+
+    def state_views(self):
+        """(primed (S,) i32, records (S, 240) i32): views of the state buffer (tests)."""
+        up = lambda x: (x + 255) // 256 * 256
+        S, off = self.max_streams, (-self.state.data_ptr()) % 256
+        ncap = 1 + self.beam * self.max_frames
+        h = 1
+        while h < 2 * ncap:
+            h <<= 1
+        per = up(960) + up(16 * ncap) + up(8 * h) + up(4 * h)
+        primed = self.state[off: off + 4 * S].view(torch.int32)
+        lo = off + up(4 * S)
+        blocks = self.state[lo: lo + S * per].view(S, per)
+        return primed, blocks[:, :960].view(torch.int32)
+
+    def push(self, logits: torch.Tensor, logits_len, streams: Optional[Sequence[int]] = None, nbest: Optional[int] = None):
+        """logits (n, t_new, V) fp32 on the GPU: logits_len[i] new frames of stream streams[i] (default 0 .. n - 1; distinct ids; 0 frames: the stream's beam
+        is read, not changed) -> device tensors (tokens (n, nbest, max_tokens) i32 with zero tails, token_len (n, nbest) i32, score (n, nbest) f32, stable_len
+        (n,) i32), the beam after the push, best first; nbest None: the whole beam.  max_tokens = the most frames a listed stream has consumed (at least 1), so
+        nothing is truncated.  stable_len: the length of the common prefix of ALL members of the beam - these tokens are final.  Ids out of range, repeated ids
+        and a push past max_frames raise ValueError before any launch (the lengths are read on the host)."""
+        if logits.dim() != 3:
+            raise _lib.EffconfError("logits must be (streams, frames, vocab); got shape %s" % (tuple(logits.shape),))
+        n, t, v = logits.shape
+        self.model._check_beam(self.beam, v)
+        ids = list(range(n)) if streams is None else [int(s) for s in streams]
+        lens = [t] * n if logits_len is None else [int(x) for x in (logits_len.tolist() if isinstance(logits_len, torch.Tensor) else logits_len)]
+        lens = [min(max(k, 0), t) for k in lens]
+        why = beam_push_refusal(ids, lens, self._frames, self.max_streams, self.max_frames)
+        if why:
+            raise ValueError(why)
+        return self._launch(logits, lens, ids, int(self.beam if nbest is None else nbest))
+
+    def _launch(self, logits, lens, ids, nbest, out=None, max_tokens=None):
+        """``push`` behind its host checks of the ids and the capacity: the kernel's own guards answer a bad id with token_len -1 and a push past max_frames
+        with -2 and leave the state alone.  `out`: the four output tensors to write instead of fresh ones, `max_tokens` their width (tests)."""
+        _native.require_hip(logits)
+        lib, dev = self._lib, self.device
+        n, t, v = logits.shape
+        if not 1 <= nbest <= self.beam:
+            raise _lib.EffconfError("nbest must be in 1 .. beam (%d); got %d" % (self.beam, nbest))
+        if max_tokens is None:
+            max_tokens = max([1] + [self._frames[s] + k for s, k in zip(ids, lens) if 0 <= s < self.max_streams])
+        with torch.cuda.device(dev):
+            logits = logits.contiguous().float()
+            tokens, token_len, score, stable = out if out is not None else (
+                torch.empty(n, nbest, max_tokens, dtype=torch.int32, device=dev), torch.empty(n, nbest, dtype=torch.int32, device=dev),
+                torch.empty(n, nbest, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            ln = torch.tensor(lens, dtype=torch.int64, device=dev)
+            idt = torch.tensor(ids, dtype=torch.int32, device=dev)
+            nbytes = _native.sized(lib, "effconf_ctc_beam_stream", lib.effconf_ctc_beam_stream_workspace_bytes(n, t, self.beam), streams=n, frames=t, beam=self.beam)
+            if self._ws is None or self._ws.numel() < nbytes:
+                self._ws = _native.workspace(nbytes, dev)
+            _lib.check(lib.effconf_ctc_beam_resume(self.state.data_ptr(), self.max_streams, self.max_frames, self.beam, idt.data_ptr(),
+                                                   logits.data_ptr() if t > 0 and n > 0 else None, ln.data_ptr(), n, t, v, float(self.model.tmp), nbest,
+                                                   tokens.data_ptr(), token_len.data_ptr(), score.data_ptr(), stable.data_ptr(), max_tokens,
+                                                   self._ws.data_ptr(), self._ws.numel(), self._stream()), "ctc_beam_resume", lib)
+        took = [0 <= s < self.max_streams and self._frames[s] + k <= self.max_frames for s, k in zip(ids, lens)]
+        self._last = (n, t, [k if ok else None for k, ok in zip(lens, took)])
+        for s, k, ok in zip(ids, lens, took):
+            if ok:
+                self._frames[s] += k
+        return tokens, token_len, score, stable
+
+    def last_push_trace(self) -> List[Optional[dict]]:
+        """The workspace of the last push (layout: include/effconf.h), one dict per listed stream as ``ModelCTC.last_beam_trace`` gives per utterance, for the
+        push's frames: ``len`` (frames of the push), ``candidates`` / ``nodes`` (candidates scored / trie nodes of the stream so far), ``frames`` (frames
+        consumed so far), ``node`` (len, beam) i32 and ``pb`` / ``pnb`` / ``score`` (len, beam) f32.  None for a listed stream the kernel's guards turned away."""
+        import numpy as np
+        n, t, lens = self._last
+        al = lambda x: (x + 255) // 256 * 256
+        base = (-self._ws.data_ptr()) % 256
+        raw = self._ws[base: base + al(16 * n) + n * al(16 * t * self.beam)].cpu().numpy()
+        stats = raw[:16 * n].view(np.int32).reshape(n, 4)
+        out = []
+        for i in range(n):
+            if lens[i] is None:
+                out.append(None)
+                continue
+            u = al(16 * n) + i * al(16 * t * self.beam)
+            tr = raw[u: u + 16 * t * self.beam].view(np.int32).reshape(t, self.beam, 4)[:int(stats[i, 0])]
+            trf = tr.view(np.float32)
+            out.append({"len": int(stats[i, 0]), "candidates": int(stats[i, 1]), "nodes": int(stats[i, 2]), "frames": int(stats[i, 3]),
+                        "node": tr[:, :, 0].copy(), "pb": trf[:, :, 1].copy(), "pnb": trf[:, :, 2].copy(), "score": trf[:, :, 3].copy()})
+        return out
+
+
+class StreamingCTCBeam:
+    """``ModelCTC.open_stream(..., beam_size=k)``: the encoder session, the head's logits on the push's rows, and the prefix beam search resumed over the streams
+    that received rows.  ``push_mel`` / ``push_audio`` return, per stream, the NEWLY COMMITTED token ids - the growth of the beam's common prefix, which no later
+    frame can change - and at a stream's final push also the rest of the best hypothesis: the concatenation over an utterance's pushes is its final best
+    hypothesis, and it is that of ``decode_logits_beam`` on the concatenation of the session's own logits.  Not built: LM fusion in a streaming search, trie
+    compaction for unbounded streams (so `max_frames` is required)."""
+
+    def __init__(self, model, max_streams: int, max_frames: Optional[int], beam_size: int):
+        if max_frames is None or max_frames < 1:
+            raise ValueError("a streaming beam search needs max_frames (mel frames per utterance): the prefix trie of a stream only grows and is sized by the "
+                             "encoder rows that many frames can produce")
+        self.model = model
+        self.session = StreamingEncoder(model.encoder, max_streams, max_frames)       # refuses what cannot stream (stream_refusal) before any device work
+        rows = block_rows(model.encoder.plan, (int(max_frames) - 1) // 2 + 1)[-1]
+        self.decoder = CtcBeamStreamState(model, max_streams, max(rows, 1), beam_size, device=self.session.device)
+        self._committed = [[] for _ in range(max_streams)]
+        self._hyp = [[([], 0.0)] for _ in range(max_streams)]
+        self.last_push_logits = None
+
+    align_frames = property(lambda self: self.session.align_frames)
+
+    def frames_pending(self, stream: int) -> int:
+        return self.session.frames_pending(stream)
+
+    def reset(self, stream: int):
+        """`stream` starts a new utterance."""
+        self.session.reset(stream)
+        self.decoder.reset(stream)
+        self._committed[stream], self._hyp[stream] = [], [([], 0.0)]
+
+    def committed(self, stream: int) -> List[int]:
+        """The tokens returned so far: final."""
+        return list(self._committed[stream])
+
+    def hypothesis(self, stream: int) -> List[int]:
+        """Rank 0 of the beam as it stands (it begins with ``committed``)."""
+        return list(self._hyp[stream][0][0])
+
+    def nbest(self, stream: int) -> List[Tuple[List[int], float]]:
+        """[(ids, score)] of the beam as it stands, best first."""
+        return [(list(ids), sc) for ids, sc in self._hyp[stream]]
+
+    def text(self, stream: int) -> str:
+        if self.model.tokenizer is None:
+            raise _lib.EffconfError("text() needs a tokenizer attached to the model")
+        return self.model.tokenizer.decode([self.hypothesis(stream)])[0]
+
+    def _decode(self, out: torch.Tensor, out_len: torch.Tensor, final) -> List[List[int]]:
+        B = out.shape[0]
+        lens = out_len.tolist()
+        final = [False] * B if final is None else [bool(v) for v in (final.tolist() if isinstance(final, torch.Tensor) else final)]
+        new = [[] for _ in range(B)]
+        active = [b for b in range(B) if lens[b] > 0]
+        self.last_push_logits = None
+        if active:
+            ix = torch.tensor(active, dtype=torch.int64, device=out.device)
+            alen = out_len[ix].contiguous()
+            logits, _, _ = self.model._head(out[ix].contiguous(), alen, want_logits=True)
+            self.last_push_logits = (logits, alen, list(active))
+            tokens, token_len, score, stable = (z.tolist() for z in self.decoder.push(logits, [lens[b] for b in active], active))
+            for i, b in enumerate(active):
+                self._hyp[b] = [(tokens[i][r][:token_len[i][r]], score[i][r]) for r in range(len(score[i])) if score[i][r] != float("-inf") or r == 0]
+                best = self._hyp[b][0][0]
+                new[b] = best[len(self._committed[b]): stable[i]]
+                self._committed[b] += new[b]
+        for b in range(B):
+            if final[b]:
+                rest = self._hyp[b][0][0][len(self._committed[b]):]
+                new[b] = new[b] + rest
+                self._committed[b] += rest
+        return new
+
+    def push_mel(self, mel, mel_len, final=None) -> List[List[int]]:
+        """``StreamingEncoder.push_mel``, the head, then the resumed search of the new rows -> the newly committed token ids per stream."""
+        return self._decode(*self.session.push_mel(mel, mel_len, final), final)
+
+    def push_audio(self, x, x_len, final=None) -> List[List[int]]:
+        return self._decode(*self.session.push_audio(x, x_len, final), final)
 
 
 # ------------------------------------------------------------------ RNN-T: the greedy decode resumed per stream

@@ -181,6 +181,42 @@ int effconf_ctc_beam(const float* logits, const int64_t* out_len, int32_t batch,
                      float temperature, int32_t* tokens, int32_t* token_len, float* score, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* Streaming CTC prefix beam search: effconf_ctc_beam resumed per stream, push by push (one workgroup per listed stream).  The search visits frames
+ * in order and never looks ahead, so the beam of a stream after its pushes, whatever their pattern, is bit for bit that of one effconf_ctc_beam call on the same
+ * frames (tokens, lengths, scores, and the per-frame trace).  Not part of it: LM fusion (effconf_ctc_beam_lm), a compaction of the trie for unbounded streams.
+ * State: one caller-provided device buffer of effconf_ctc_beam_stream_state_bytes(max_streams, max_frames, beam) bytes.  From the buffer's address aligned up to
+ * 256 bytes (al(x) = x rounded up to 256):
+ *   offset 0                              i32 primed[max_streams]   1: the record holds the stream's beam at a frame boundary
+ *   offset al(4 max_streams) + s * P      the block of stream s, P = al(960) + al(16 N) + al(8 H) + al(4 H), N = 1 + beam max_frames trie nodes, H = smallest power
+ *                                         of two >= 2 N:
+ *     record i32 [240]                    head [16]: frames consumed, members, trie nodes, candidates scored (lo, hi), 11 unused; then [32] each of the members'
+ *                                         node, last token, parent node, depth (i32) and pb, pnb, score (f32), in rank order
+ *     nodes [N], hash keys u64 [H], hash nodes i32 [H]   the stream's trie, as in effconf_ctc_beam's workspace; it only grows until the stream is reset
+ * effconf_ctc_beam_stream_init clears every flag, effconf_ctc_beam_stream_reset the flag of one stream (which then starts a new utterance); both write nothing
+ * else.  A record whose flag is clear is never read; the kernel initialises a stream's hash at its first frame.  max_frames counts logit frames per utterance.
+ * effconf_ctc_beam_resume: max_streams, max_frames, beam as the state was sized with; streams dev i32 (n) DISTINCT stream ids; logits dev f32 (n, t_new, vocab) the
+ * new frames of the listed streams (t_new = 0 with logits NULL: every listed stream gets a read-only push); out_len dev i64 (n), clamped to [0, t_new]: frames at
+ * or beyond it are never read.  A stream with out_len 0 keeps its record untouched and gets the outputs of its beam as it stands (a stream that never had a frame:
+ * the empty prefix with score 0).  Outputs, ranks 0 .. nbest - 1 (1 <= nbest <= beam) of the beam after the push: tokens dev i32 (n, nbest, max_tokens) with
+ * zero-filled tails; token_len dev i32 (n, nbest) the true length, also where it exceeds max_tokens (it never exceeds the frames the stream has consumed); score dev
+ * f32 (n, nbest); stable_len dev i32 (n) the length of the longest common prefix of ALL members of the beam: every later hypothesis of the stream begins with these
+ * tokens.  A listed id outside 0 .. max_streams - 1 gets token_len = -1 for its ranks, a push that would take a stream past max_frames token_len = -2; nothing else
+ * is written for either, and the state stays as it was.
+ * Workspace (effconf_ctc_beam_stream_workspace_bytes):
+ *   [0, 16 n)                             i32 stats[n][4]: frames of the push, candidates scored so far, trie nodes so far, frames consumed so far
+ *   al(16 n) + i * al(16 t_new beam)      trace [t_new][beam] of listed stream i: {i32 node, f32 pb, f32 pnb, f32 score} after each frame of the push, as effconf_ctc_beam's
+ * Refused before any launch: effconf_ctc_beam's limits (beam 1 .. 32, vocab 2 .. 1024, beam * max_frames < 2^24), max_streams or max_frames < 1, nbest outside
+ * 1 .. beam, max_tokens outside 1 .. 2^24, a temperature that is not finite and positive, a short workspace, null arguments; effconf_ctc_beam_stream_init refuses a short state
+ * buffer.  The two size queries return 0 for arguments the entries reject. */
+size_t effconf_ctc_beam_stream_state_bytes(int32_t max_streams, int32_t max_frames, int32_t beam);
+int effconf_ctc_beam_stream_init(void* state, size_t state_bytes, int32_t max_streams, int32_t max_frames, int32_t beam, void* stream);
+int effconf_ctc_beam_stream_reset(void* state, int32_t max_streams, int32_t stream_id, void* stream);
+size_t effconf_ctc_beam_stream_workspace_bytes(int32_t n, int32_t t_new, int32_t beam);
+int effconf_ctc_beam_resume(void* state, int32_t max_streams, int32_t max_frames, int32_t beam, const int32_t* streams, const float* logits,
+                            const int64_t* out_len, int32_t n, int32_t t_new, int32_t vocab, float temperature, int32_t nbest, int32_t* tokens,
+                            int32_t* token_len, float* score, int32_t* stable_len, int32_t max_tokens, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 /* CTC forced alignment and transcript scoring: for every utterance the best alignment (Viterbi) of a given target to the frames and the
  * total CTC log-likelihood log P(target | audio) (-torch.nn.functional.ctc_loss of the log_softmax), one trellis of t_out frames and
  * 2 U + 1 states, blank 0.  logits dev f32 (batch, t_out, vocab), e.g. the logits output of effconf_ctc_greedy; per frame

@@ -101,6 +101,16 @@ int main() {
         check_regions("ctc_beam_layout (utterance)", {{L.trace, (size_t)t * beam * 16}, {L.nodes, (size_t)L.ncap * 16}, {L.hkeys, (size_t)L.hcap * 8}, {L.hvals, (size_t)L.hcap * 4}},
                       L.per_utt);
         check_total("ctc_beam_layout", {{L.stats, (size_t)b * 16}, {L.utt, (size_t)b * L.per_utt}}, L.total);
+        {   // the resumed search: `b` listed streams' push workspace, and the state buffer of b streams of t frames
+            const CtcBeamStreamWs W = ctc_beam_stream_ws(b, t, beam);
+            check_regions("ctc_beam_stream_ws (stream)", {{0, (size_t)t * beam * 16}}, W.per_trace);
+            check_total("ctc_beam_stream_ws", {{W.stats, (size_t)b * 16}, {W.trace, (size_t)b * W.per_trace}}, W.total);
+            const CtcBeamStreamLayout S = ctc_beam_stream_layout(b, t, beam);
+            if (S.ncap != L.ncap || S.hcap != L.hcap) fail("a trie that is not ctc_beam_layout's", "ctc_beam_stream_layout");
+            check_regions("ctc_beam_stream_layout (stream)", {{S.rec, (size_t)CTC_STREAM_REC_INTS * 4}, {S.nodes, (size_t)S.ncap * 16}, {S.hkeys, (size_t)S.hcap * 8},
+                                                               {S.hvals, (size_t)S.hcap * 4}}, S.per_stream);
+            check_total("ctc_beam_stream_layout", {{S.primed, (size_t)b * 4}, {S.blocks, (size_t)b * S.per_stream}}, S.total);
+        }
     }
     const int lms[][3] = {{40, 32, 1}, {50, 64, 2}, {1000, 1024, 4}};
     for (const auto& d : lms) {
