@@ -18,7 +18,7 @@
 //     index, so a prefix that leaves the beam and comes back gets its old node, and "P c is a member" is a compare of (parent, token).
 // All arithmetic of an utterance is in a fixed order, so its results do not depend on the batch, the T padding or the run.
 //
-// With a neural LM (effconf_ctc_beam_lm, ctc_beam_lm_kernel: ctc_beam_search.h with LM = true): candidates are ranked by
+// With a neural LM (effconf_ctc_beam_lm, ctc_beam_lm_kernel: ctc_beam_search<true, false>): candidates are ranked by
 //   total(Q) = s(Q) + lm_weight * L(Q) + length_bonus * |Q|      (fp32, every operation rounded on its own, in that order)
 // with L(()) = 0, L(P c) = L(P) + row_P[c], row_P = log softmax(fc(h_P) / lm_tmp), h_P the LSTM state after [0] + P.  L is stored in the trie node when the
 // node is created, so every later use of the prefix sees the same bits.  The acoustic recursion is untouched.
@@ -29,34 +29,25 @@
 //     prefix's for the whole call.  A member keeps its slot while it stays in the beam; a candidate that enters the beam as an extension takes the lowest slot
 //     of 1 .. 2 beam that no member of the OLD beam holds (its parent is one of them and must stay valid until the LM step has run; the survivors are among
 //     them too).  The old beam holds at most `beam` of these slots and at most `beam` candidates enter, so 2 beam slots plus the root always suffice.
-//   * Rounds: when a frame's new beam holds members without a row, the workgroup saves its beam to the resume record, writes one request (token, parent's
+//   * Rounds: when a frame's new beam holds members without a row, the workgroup saves its beam to its record (decode_layout.h), writes one request (token, parent's
 //     slot, its slot, live) per rank, counts itself in the round counter and exits; the host runs ONE LM step for the requests of all utterances and
 //     launches again.  On resume the raw logits rows are turned into log-softmax rows in the slots (one wave per row).  An utterance whose new beam needs no
 //     LM goes on in the same launch; a finished utterance's workgroup returns at once; the hash index is initialised in the first launch only.
 //
-// Resumed per stream (effconf_ctc_beam_resume, ctc_beam_resume_kernel: ctc_beam_search.h with STREAM = true): the plain search over the frames of one
+// Resumed per stream (effconf_ctc_beam_resume, ctc_beam_resume_kernel: ctc_beam_search<false, true>): the plain search over the frames of one
 // push.  The search never looks ahead, so all it knows after a frame is the beam (per member: node, last token, parent, depth, pb, pnb, s) and the append-only trie
 // with its hash; both live in the stream's block of a caller-provided state buffer and outlive the call, so the beam after any pushes is bit for bit the beam of one
 // whole call.  A push's frames and trace are push-local; the trie is sized for max_frames frames of the stream.  Outputs: the ranks' tokens, lengths and scores as
 // the beam stands, and stable_len - the length of the common prefix of ALL members, which every later hypothesis begins with.
-#include "decode_common.h"
+#include "ctc_beam_search.h"
 
 #include <cmath>
 
 int ec_fail(const char* msg);
 
-using namespace ecdec;
+using namespace ecctc;
 
 namespace {
-
-constexpr int CT = 256;                           // threads per utterance
-constexpr int CNW = CT / 64;                      // waves
-constexpr int MAXB = 32;                          // largest beam
-constexpr int MAXV = 1024;                        // largest vocabulary
-constexpr int TPT = MAXV / CT;                    // tokens per thread (contiguous: thread i owns i TPT .. i TPT + TPT - 1)
-constexpr int MAXK = 2 * MAXB + 1;                // top tokens per frame
-constexpr int MAXS = 2 * MAXB + MAXB * MAXB;      // candidate slots: members, repeat extensions, plain extensions
-constexpr unsigned long long HEMPTY = ~0ull;
 
 const char* ctc_beam_check(int32_t batch, int32_t t_out, int32_t vocab, int32_t beam) {
     if (beam < 1 || beam > MAXB) return "ctc beam search: beam must be in 1 .. 32";
@@ -74,106 +65,25 @@ const char* ctc_beam_stream_check(int32_t max_streams, int32_t max_frames, int32
     return ctc_beam_check(0, max_frames, 2, beam);
 }
 
-struct CtcBeamArgs {
-    const float* logits; const int64_t* lens;
-    int T, V, beam; float tmp;
-    char* utt; int* stats; CtcBeamLayout L;
-    int* tokens; int* token_len; float* score;
-};
-
-// the fused search's side of the arguments (empty for the plain search)
-struct CtcLmSide {
-    int4* req;               // [B][beam] requests of the round: token, source slot, destination slot, live
-    const int* slot;         // [B * beam] packed column of every request of the last LM step
-    const float* logits;     // [packed column][V] raw logits rows of the last LM step
-    int* resume;             // [B][CTC_LM_RESUME_INTS]; [0]: 0 start, 1 suspended, 2 finished
-    int* active;             // utterances suspended in this launch
-    size_t lmnodes, trace2;  // offsets inside an utterance
-    int nls;                 // floats of a slot's state; its row follows
-    float w, tmp, bonus;
-    float* total; float* lm_score;
-};
-
-enum { R_PHASE = 0, R_FRAME, R_N, R_NN, R_NCLO, R_NCHI, R_NREQ };
-static_assert(R_NREQ < CTC_LM_RESUME_HEAD, "resume record");
-
-// the resumed search's side of the arguments (empty for the two whole-utterance kernels).  There a.utt / a.L.per_utt / a.L.trace address the push's traces in the
-// workspace, a.L.nodes / hkeys / hvals / hcap are those of a stream's block, a.T is t_new and tokens / token_len / score are (n, nbest, ..)
-struct CtcStreamSide {
-    const int* streams;      // [n] listed stream ids
-    int* primed;             // [max_streams] 1: the record holds the stream's beam at a frame boundary
-    char* blocks;            // the streams' blocks, per_stream apart: record, trie nodes, hash
-    size_t per_stream, rec;  // rec: the record inside a block
-    int max_streams, max_frames, nbest, max_tokens;
-    int* stable_len;         // [n]
-};
-
-enum { S_FRAMES = 0, S_N, S_NN, S_NCLO, S_NCHI };    // the head of a stream's record
-static_assert(S_NCHI < CTC_STREAM_HEAD && CTC_STREAM_MAXB == MAXB && CTC_LM_MAXB == MAXB, "stream record");
-
-// logaddexp in the log1pf form of the prefix beam search this kernel follows; rnnt_align.hip's lse2 and ctc_align.hip's lse3 are the logf form of the losses
-// they follow: different formulas on purpose
-__device__ __forceinline__ float lse(float a, float b) {
-    const float m = fmaxf(a, b);
-    if (m == -INFINITY) return -INFINITY;
-    return m + log1pf(expf(-fabsf(a - b)));
+const char* ctc_beam_tmp_check(float temperature) {
+    return temperature > 0.f && std::isfinite(temperature) ? nullptr : "ctc beam search: temperature must be > 0";
 }
 
-// lp -> unsigned key with the same order (larger lp, larger key)
-__device__ __forceinline__ unsigned okey(float f) {
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+// what every entry passes to the search; the workspace side (utt, stats, L) is the entry's own
+CtcBeamArgs ctc_beam_args(const float* logits, const int64_t* lens, int32_t t, int32_t vocab, int32_t beam, float temperature, int32_t* tokens,
+                          int32_t* token_len, float* score) {
+    CtcBeamArgs a{};
+    a.logits = logits; a.lens = lens; a.T = t; a.V = vocab; a.beam = beam; a.tmp = temperature;
+    a.tokens = tokens; a.token_len = token_len; a.score = score;
+    return a;
 }
 
-// candidate order as one integer, larger = earlier: score desc (-0 counts as +0), then ck asc; 0 = empty slot
-__device__ __forceinline__ unsigned long long cand_key(float s, int ck) {
-    return ((unsigned long long)okey(s == 0.f ? 0.f : s) << 32) | (unsigned)(0x7fffffff - ck);
-}
+__global__ __launch_bounds__(CT) void ctc_beam_kernel(const CtcBeamArgs a) { ctc_beam_search<false, false>(a, CtcLmSide{}, CtcStreamSide{}); }
 
-__device__ __forceinline__ unsigned hash_slot(int par, int c, unsigned mask) {
-    unsigned h = (unsigned)par * 0x9E3779B1u ^ ((unsigned)c + 0x7F4A7C15u) * 0x85EBCA77u;
-    h ^= h >> 16;
-    return h & mask;
-}
-
-__device__ __forceinline__ unsigned long long hload(const unsigned long long* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// a + w x and total(Q) with every operation rounded on its own, in the order of model_ctc.select_nbest.  The pragma: the compiler's default contraction would
-// fuse a product into the sum that follows it (also through the _rn intrinsics, which are plain operators)
-__device__ __forceinline__ float lm_scaled_sum(float a, float w, float x) {
-#pragma clang fp contract(off)
-    const float wx = w * x;
-    return a + wx;
-}
-
-__device__ __forceinline__ float fused_total(float s, float L, int len, float w, float bonus) {
-#pragma clang fp contract(off)
-    const float bl = bonus * (float)len;
-    return lm_scaled_sum(s, w, L) + bl;
-}
-
-// ctc_beam_search.h is the search itself
-__global__ __launch_bounds__(CT) void ctc_beam_kernel(const CtcBeamArgs a) {
-    constexpr bool LM = false, STREAM = false;
-    const CtcLmSide fz{};
-    const CtcStreamSide sz{};
-#include "ctc_beam_search.h"
-}
-
-__global__ __launch_bounds__(CT) void ctc_beam_lm_kernel(const CtcBeamArgs a, const CtcLmSide fz) {
-    constexpr bool LM = true, STREAM = false;
-    const CtcStreamSide sz{};
-#include "ctc_beam_search.h"
-}
+__global__ __launch_bounds__(CT) void ctc_beam_lm_kernel(const CtcBeamArgs a, const CtcLmSide fz) { ctc_beam_search<true, false>(a, fz, CtcStreamSide{}); }
 
 // one workgroup per listed stream: the plain search over the push's frames, from and to the stream's record
-__global__ __launch_bounds__(CT) void ctc_beam_resume_kernel(const CtcBeamArgs a, const CtcStreamSide sz) {
-    constexpr bool LM = false, STREAM = true;
-    const CtcLmSide fz{};
-#include "ctc_beam_search.h"
-}
+__global__ __launch_bounds__(CT) void ctc_beam_resume_kernel(const CtcBeamArgs a, const CtcStreamSide sz) { ctc_beam_search<false, true>(a, CtcLmSide{}, sz); }
 
 // before the first search launch: every utterance asks for the empty prefix's row, request (token 0, no source, slot 0) at rank 0
 __global__ __launch_bounds__(256) void ctc_beam_lm_root_kernel(int4* req, int ncol, int beam) {
@@ -203,16 +113,14 @@ int effconf_ctc_beam(const float* logits, const int64_t* out_len, int32_t batch,
                      float temperature, int32_t* tokens, int32_t* token_len, float* score, void* workspace, size_t workspace_bytes,
                      void* stream) {
     if (const char* e = ctc_beam_check(batch, t_out, vocab, beam)) return ec_fail(e);
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return ec_fail("ctc beam search: temperature must be > 0");
+    if (const char* e = ctc_beam_tmp_check(temperature)) return ec_fail(e);
     if (batch == 0) return 0;
     if (!out_len || !token_len || !score || !workspace || (t_out > 0 && (!logits || !tokens))) return ec_fail("null argument");
     const CtcBeamLayout L = ctc_beam_layout(batch, t_out, beam);
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_ctc_beam_workspace_bytes)");
     char* ws = WsPlan::base(workspace);
-    CtcBeamArgs a{};
-    a.logits = logits; a.lens = out_len; a.T = t_out; a.V = vocab; a.beam = beam; a.tmp = temperature;
+    CtcBeamArgs a = ctc_beam_args(logits, out_len, t_out, vocab, beam, temperature, tokens, token_len, score);
     a.utt = ws + L.utt; a.stats = reinterpret_cast<int*>(ws + L.stats); a.L = L;
-    a.tokens = tokens; a.token_len = token_len; a.score = score;
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(batch), dim3(CT), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : ec_fail("ctc_beam launch failed");
 }
@@ -254,7 +162,7 @@ int effconf_ctc_beam_resume(void* state, int32_t max_streams, int32_t max_frames
     if (const char* e = ctc_beam_check(n, t_new, vocab, beam)) return ec_fail(e);
     if (nbest < 1 || nbest > beam) return ec_fail("ctc beam search: nbest must be in 1 .. beam");
     if (max_tokens < 1 || max_tokens > (1 << 24)) return ec_fail("ctc beam search: max_tokens must be in 1 .. 2^24 (no hypothesis is longer than max_frames)");
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return ec_fail("ctc beam search: temperature must be > 0");
+    if (const char* e = ctc_beam_tmp_check(temperature)) return ec_fail(e);
     const CtcBeamStreamWs W = ctc_beam_stream_ws(n, t_new, beam);
     if (workspace_bytes < W.total) return ec_fail("workspace too small (effconf_ctc_beam_stream_workspace_bytes)");
     if (n == 0) return 0;
@@ -262,11 +170,9 @@ int effconf_ctc_beam_resume(void* state, int32_t max_streams, int32_t max_frames
     const CtcBeamStreamLayout S = ctc_beam_stream_layout(max_streams, max_frames, beam);
     char* ws = WsPlan::base(workspace);
     char* st = WsPlan::base(state);
-    CtcBeamArgs a{};
-    a.logits = logits; a.lens = out_len; a.T = t_new; a.V = vocab; a.beam = beam; a.tmp = temperature;
+    CtcBeamArgs a = ctc_beam_args(logits, out_len, t_new, vocab, beam, temperature, tokens, token_len, score);
     a.utt = ws + W.trace; a.stats = reinterpret_cast<int*>(ws + W.stats);
     a.L.ncap = S.ncap; a.L.hcap = S.hcap; a.L.per_utt = W.per_trace; a.L.trace = 0; a.L.nodes = S.nodes; a.L.hkeys = S.hkeys; a.L.hvals = S.hvals;
-    a.tokens = tokens; a.token_len = token_len; a.score = score;
     CtcStreamSide sz{};
     sz.streams = streams; sz.primed = reinterpret_cast<int*>(st + S.primed); sz.blocks = st + S.blocks; sz.per_stream = S.per_stream; sz.rec = S.rec;
     sz.max_streams = max_streams; sz.max_frames = max_frames; sz.nbest = nbest; sz.max_tokens = max_tokens; sz.stable_len = stable_len;
@@ -287,7 +193,7 @@ int effconf_ctc_beam_lm(EcLm* lm, const float* logits, const int64_t* out_len, i
     if (const char* e = ctc_beam_check(batch, t_out, vocab, beam)) return ec_fail(e);
     const EcLmConfig* mc;
     if (const char* e = ctc_beam_lm_check(lm, batch, vocab, beam, &mc)) return ec_fail(e);
-    if (!(temperature > 0.f) || !std::isfinite(temperature)) return ec_fail("ctc beam search: temperature must be > 0");
+    if (const char* e = ctc_beam_tmp_check(temperature)) return ec_fail(e);
     if (!(lm_weight > 0.f) || !std::isfinite(lm_weight)) return ec_fail("ctc beam search: lm_weight must be > 0 (0: effconf_ctc_beam)");
     if (!(lm_tmp > 0.f) || !std::isfinite(lm_tmp)) return ec_fail("ctc beam search: lm_tmp must be > 0");
     if (!std::isfinite(length_bonus)) return ec_fail("ctc beam search: length_bonus must be finite");
@@ -299,10 +205,8 @@ int effconf_ctc_beam_lm(EcLm* lm, const float* logits, const int64_t* out_len, i
     if (workspace_bytes < L.total) return ec_fail("workspace too small (effconf_ctc_beam_lm_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
     char* ws = WsPlan::base(workspace);
-    CtcBeamArgs a{};
-    a.logits = logits; a.lens = out_len; a.T = t_out; a.V = vocab; a.beam = beam; a.tmp = temperature;
+    CtcBeamArgs a = ctc_beam_args(logits, out_len, t_out, vocab, beam, temperature, tokens, token_len, am_score);
     a.utt = ws + L.s.utt; a.stats = reinterpret_cast<int*>(ws + L.s.stats); a.L = L.s;
-    a.tokens = tokens; a.token_len = token_len; a.score = am_score;
     CtcLmSide fz{};
     fz.req = reinterpret_cast<int4*>(ws + L.req); fz.slot = reinterpret_cast<const int*>(ws + L.slot); fz.logits = reinterpret_cast<const float*>(ws + L.logits);
     fz.resume = reinterpret_cast<int*>(ws + L.resume); fz.active = reinterpret_cast<int*>(ws + L.counter);
@@ -312,7 +216,7 @@ int effconf_ctc_beam_lm(EcLm* lm, const float* logits, const int64_t* out_len, i
     LmColumns col{};
     col.req = fz.req; col.ncol = ncol; col.cols_per_utt = beam; col.slot = reinterpret_cast<int*>(ws + L.slot);
     col.utt = a.utt; col.per_utt = L.s.per_utt; col.lmnodes = L.lmnodes; col.node_floats = L.nls + L.vocab; col.logits = reinterpret_cast<float*>(ws + L.logits);
-    if (hipMemsetAsync(fz.resume, 0, (size_t)batch * CTC_LM_RESUME_INTS * 4, s) != hipSuccess) return ec_fail("ctc beam search: clearing the resume records failed");
+    if (hipMemsetAsync(fz.resume, 0, (size_t)batch * CTC_BEAM_LM_REC_INTS * 4, s) != hipSuccess) return ec_fail("ctc beam search: clearing the resume records failed");
     hipLaunchKernelGGL(ctc_beam_lm_root_kernel, dim3((ncol + 255) / 256), dim3(256), 0, s, fz.req, ncol, beam);
     if (hipGetLastError() != hipSuccess) return ec_fail("ctc_beam_lm_root launch failed");
     if (lm_columns_step(lm, col, ws + L.lm, s) != 0) return ec_fail("ctc beam search: LM step launch failed");

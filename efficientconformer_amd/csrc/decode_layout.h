@@ -222,13 +222,20 @@ inline CtcBeamLayout ctc_beam_layout(int batch, int t_out, int beam) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- ctc_beam.hip: the plain search, resumed per stream
-// The caller's state buffer: i32 primed[max_streams], then one block per stream, per_stream apart: the record (a head of CTC_STREAM_HEAD i32: frames consumed,
-// members, trie nodes, candidates lo / hi, then unused; then node, last, parent, depth, pb, pnb, s: [32] each) and the stream's trie - nodes int4 [ncap], hash keys
-// u64 [hcap], hash nodes i32 [hcap], ncap = 1 + beam * max_frames, hcap as ctc_beam_layout's.  The workspace of a push: stats[n][4] and its trace [t_new][beam] int4
-// per listed stream.
-constexpr int CTC_STREAM_MAXB = 32;                                      // ctc_beam.hip's largest beam
-constexpr int CTC_STREAM_HEAD = 16;
-constexpr int CTC_STREAM_REC_INTS = CTC_STREAM_HEAD + 7 * CTC_STREAM_MAXB;
+// The beam as a record, defined once for the two searches that carry a beam from one launch to the next: a head of CTC_REC_HEAD i32 (the enum; the rest unused),
+// then [CTC_BEAM_MAXB] each of the members' node, last token, parent node, depth (i32), pb, pnb, s (f32) in rank order - CTC_BEAM_REC_INTS, the record of a stream,
+// whose bytes include/effconf.h documents - and then, for the fused search alone, L (f32), LM slot and row pending (i32): CTC_BEAM_LM_REC_INTS.
+constexpr int CTC_BEAM_MAXB = 32;                                        // ctc_beam_search.h's largest beam
+enum : int { CTC_REC_FRAMES = 0,                                         // frames consumed: where the next launch goes on
+             CTC_REC_N, CTC_REC_NN, CTC_REC_NCLO, CTC_REC_NCHI,          // members, trie nodes, candidates scored (lo, hi)
+             CTC_REC_PHASE, CTC_REC_NREQ,                                // the fused search: 0 start (the entry's memset), 1 suspended, 2 finished; LM rows asked for
+             CTC_REC_HEAD = 16 };
+constexpr int CTC_BEAM_REC_INTS = CTC_REC_HEAD + 7 * CTC_BEAM_MAXB;
+constexpr int CTC_BEAM_LM_REC_INTS = CTC_BEAM_REC_INTS + 3 * CTC_BEAM_MAXB;
+
+// The caller's state buffer: i32 primed[max_streams], then one block per stream, per_stream apart: the record (CTC_BEAM_REC_INTS i32) and the stream's trie - nodes
+// int4 [ncap], hash keys u64 [hcap], hash nodes i32 [hcap], ncap = 1 + beam * max_frames, hcap as ctc_beam_layout's.  The workspace of a push: stats[n][4] and its
+// trace [t_new][beam] int4 per listed stream.
 
 struct CtcBeamStreamLayout {
     int ncap, hcap;
@@ -242,7 +249,7 @@ inline CtcBeamStreamLayout ctc_beam_stream_layout(int max_streams, int max_frame
     while (h < 2 * L.ncap) h <<= 1;
     L.hcap = h;
     WsPlan u;                                     // one stream
-    L.rec = u.take((size_t)CTC_STREAM_REC_INTS * 4);
+    L.rec = u.take((size_t)CTC_BEAM_REC_INTS * 4);
     L.nodes = u.take((size_t)L.ncap * 16);
     L.hkeys = u.take((size_t)h * 8);
     L.hvals = u.take((size_t)h * 4);
@@ -271,11 +278,8 @@ inline CtcBeamStreamWs ctc_beam_stream_ws(int n, int t_new, int beam) {
 // ---------------------------------------------------------------------------------------------------------------- ctc_beam.hip with a neural LM (shallow fusion)
 // The search's regions, and per utterance: a second trace {f32 L, f32 total} per frame and rank, and 2 * beam + 1 LM slots of the node layout lm_columns_step
 // reads and writes ([layer][h k-permuted | c], 2 * layers * dim_model floats, then the slot's row: vocab floats).  Per call: one request (token, source slot,
-// destination slot, live) per rank of every utterance's beam with its packed column + the packed columns' tokens (slot); one resume record per utterance; the
-// round's counter of suspended utterances; the dense state of one LM step over batch * beam columns (lm_layout) and its raw logits rows.
-constexpr int CTC_LM_MAXB = 32;                                          // ctc_beam.hip's largest beam
-constexpr int CTC_LM_RESUME_HEAD = 16;    // phase, next frame, members, trie nodes, candidates (lo, hi), LM rows asked for, then unused
-constexpr int CTC_LM_RESUME_INTS = CTC_LM_RESUME_HEAD + 10 * CTC_LM_MAXB;    // then node, last, parent, depth, pb, pnb, s, L, slot, row pending: [32] each
+// destination slot, live) per rank of every utterance's beam with its packed column + the packed columns' tokens (slot); one record of CTC_BEAM_LM_REC_INTS per
+// utterance; the round's counter of suspended utterances; the dense state of one LM step over batch * beam columns (lm_layout) and its raw logits rows.
 
 struct CtcBeamLmLayout {
     CtcBeamLayout s;                                                     // s.total is not set: `total` below is the call's size
@@ -303,7 +307,7 @@ inline CtcBeamLmLayout ctc_beam_lm_layout(const EcLmConfig& m, int batch, int t_
     L.s.utt = p.take((size_t)batch * L.s.per_utt);
     L.req = p.take((size_t)ncol * 16);
     L.slot = p.take((size_t)ncol * 8);
-    L.resume = p.take((size_t)batch * CTC_LM_RESUME_INTS * 4);
+    L.resume = p.take((size_t)batch * CTC_BEAM_LM_REC_INTS * 4);
     L.counter = p.take(4);
     L.lm = p.take(L.lml.total - 256);                                    // a sub-plan: its own slack is not needed inside an aligned region
     L.logits = p.take((size_t)ncol * m.vocab_size * 4);

@@ -11,7 +11,8 @@ file runs on older trees), one process.  The cases are small and chosen for the 
   transcript holding token V (status 2) and one with tokens but no frames (status 1), Viterbi and forward-only.
   LM (H, L, V) = (32, 1, 40), (64, 2, 50): N = 5 / 17 / 40 (the three lm_lstm_step_kernel instances), u_max 6 with lengths 0 .. 6 and one refused sequence,
   temperature 1 and 0.7; score, token_logprobs, decode (the full-logits head) and forward.
-  CTC beam search and alignment: B = 3 with a zero-length utterance, V = 40, beam 1 / 4 / 32.
+  CTC beam search and alignment: B = 3 with a zero-length utterance, V = 40, beam 1 / 4 / 32.  The three instances of the search (csrc/ctc_beam_search.h): plain;
+  fused with an LM (32, 1, 40), with its traces; resumed per stream, pushed whole, one frame at a time and in uneven pushes with one that has no frames.
 """
 from __future__ import annotations
 
@@ -123,6 +124,24 @@ def ctc_cases():
     lens = torch.tensor([29, 0, 17], dtype=torch.int64, device=DEV)
     for beam in (1, 4, 32):
         emit("ctc_beam", "B=3 T=29 V=40 beam=%d" % beam, *m.decode_logits_beam(logits, lens, beam))
+    traced = lambda dicts: [torch.from_numpy(np.ascontiguousarray(d[k])) for d in dicts if d is not None for k in sorted(d)]
+    # the fused search: one small LM, a length bonus; everything returned and the workspace's traces (L and total per frame and rank, L per trie node)
+    lm_params = dict(arch="RNN", vocab_size=v, dim_model=32, num_layers=1)
+    lm = LanguageModel(lm_params)
+    lm.load_state_dict({k: torch.from_numpy(a) for k, a in synth.make_lm_state_dict(lm_params, 5).items()})
+    lm = lm.to(DEV)
+    for beam in (1, 4, 32):
+        out = m.decode_logits_beam_lm(logits, lens, beam, lm=lm, lm_weight=0.5, lm_tmp=1.0, length_bonus=0.3)
+        emit("ctc_beam_lm", "B=3 T=29 V=40 beam=%d LM (32, 1, 40) w=0.5 bonus=0.3" % beam, *out, *traced(m.last_beam_trace()))
+    # the search resumed per stream: every push's outputs and trace, one line per push pattern (cuts between the pushes; 5, 5: a push without frames)
+    for beam in (1, 4, 32):
+        for name, cuts in (("whole", [0, t]), ("one frame at a time", list(range(t + 1))), ("5 + 0 + 1 + 11 + 12", [0, 5, 5, 6, 17, t])):
+            st = m.open_beam_decode_stream(3, t, beam, device=DEV)
+            seen = []
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                seen += list(st.push(logits[:, lo:hi], torch.clamp(lens - lo, min=0, max=hi - lo)))
+                seen += traced(st.last_push_trace())
+            emit("ctc_beam_stream", "B=3 T=29 V=40 beam=%d pushes: %s" % (beam, name), *seen)
     y = torch.from_numpy(g.integers(1, v, (3, 7)).astype(np.int32)).to(DEV)
     y[0, 3] = y[0, 2]                                                 # a repeated token: needs a blank between
     y_len = torch.tensor([7, 0, 5], dtype=torch.int64, device=DEV)

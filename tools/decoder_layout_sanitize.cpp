@@ -107,7 +107,7 @@ int main() {
             check_total("ctc_beam_stream_ws", {{W.stats, (size_t)b * 16}, {W.trace, (size_t)b * W.per_trace}}, W.total);
             const CtcBeamStreamLayout S = ctc_beam_stream_layout(b, t, beam);
             if (S.ncap != L.ncap || S.hcap != L.hcap) fail("a trie that is not ctc_beam_layout's", "ctc_beam_stream_layout");
-            check_regions("ctc_beam_stream_layout (stream)", {{S.rec, (size_t)CTC_STREAM_REC_INTS * 4}, {S.nodes, (size_t)S.ncap * 16}, {S.hkeys, (size_t)S.hcap * 8},
+            check_regions("ctc_beam_stream_layout (stream)", {{S.rec, (size_t)CTC_BEAM_REC_INTS * 4}, {S.nodes, (size_t)S.ncap * 16}, {S.hkeys, (size_t)S.hcap * 8},
                                                                {S.hvals, (size_t)S.hcap * 4}}, S.per_stream);
             check_total("ctc_beam_stream_layout", {{S.primed, (size_t)b * 4}, {S.blocks, (size_t)b * S.per_stream}}, S.total);
         }
@@ -167,7 +167,7 @@ int main() {
             const LmLayout M = lm_layout(mc, (int)ncol);
             if (L.lml.layer != M.layer || L.lml.state != M.state) fail("an LM step state that is not lm_layout's", "ctc_beam_lm_layout");
             check_total("ctc_beam_lm_layout", {{L.s.stats, (size_t)b * 16}, {L.s.utt, (size_t)b * L.s.per_utt}, {L.req, ncol * 16}, {L.slot, ncol * 8},
-                                               {L.resume, (size_t)b * CTC_LM_RESUME_INTS * 4}, {L.counter, 4}, {L.lm, M.total - 256}, {L.logits, ncol * d[0] * 4}}, L.total);
+                                               {L.resume, (size_t)b * CTC_BEAM_LM_REC_INTS * 4}, {L.counter, 4}, {L.lm, M.total - 256}, {L.logits, ncol * d[0] * 4}}, L.total);
         }
     }
     std::printf("decoder_layout_sanitize: %lld layouts checked\n", checked);
